@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- ALS rows solved / second over one full iteration (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|small]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|small] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,9 @@ all-gathers and k x k all-reduces included) on the synthetic C4 problem of BASEL
 (10M users x 1M items, 1e9 interactions requested, k=64; fits one MI355X).  The same total problem
 is used at every N (strong scaling): users and items are row-sharded across the ranks.  Inputs are
 generated on the GPU and resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR: after the timed steps rank 0 writes the factors they computed to DIR/*.npy (see dump_outputs).  The
+inputs are drawn from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -49,6 +52,8 @@ WORKLOADS = {
     "small": (200_000, 50_000, 10_000_000, 64, "small smoke workload 200K x 50K, 10M interactions requested, k=64"),
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
+DUMP_BYTES = 60_000_000  # --dump-outputs: everything written stays below 64 MB
+DUMP_SEED = 20240229     # --dump-outputs: the row sample of a side too large to write whole
 
 
 def cpu_model():
@@ -280,6 +285,23 @@ def unplanted_leg(torch, pkg, sharded, synth, n_users, n_items, nnz_req, k, args
     return out
 
 
+def dump_outputs(torch, path, factors, k):
+    """--dump-outputs: what the timed steps computed, as a caller of the iteration receives it -- the solved factor rows of
+    each side, `factors` = {name: (replica, first solved row, solved rows)}.  A side too large for its half of DUMP_BYTES is
+    written as a fixed seeded sample of its rows; <name>_rows.npy holds the row numbers (float64) beside <name>.npy (float32)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // len(factors) // (4 * k + 8)
+    for name, (F, lo, n) in factors.items():
+        if n <= cap:
+            rows = np.arange(n, dtype=np.int64)
+        else:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+        vals = F.index_select(0, torch.from_numpy(rows + lo).to(F.device)).float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), vals)
+        np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -305,7 +327,12 @@ def main():
     ap.add_argument("--no-fp32-leg", action="store_true", help="N=1: skip the leg that re-runs the workload with --gramian-mode fp32 (roofline_fp32)")
     ap.add_argument("--exchange-chunks", type=int, default=4,
                     help="N>1: solve each slice in this many row chunks and all-gather a finished chunk while the next is solved")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the factors X and Y they computed to DIR/X.npy, DIR/Y.npy (a fixed seeded "
+                         "row sample of a large side, row numbers in DIR/X_rows.npy, DIR/Y_rows.npy; under 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU over RCCL
@@ -454,6 +481,11 @@ def main():
     elapsed = time.perf_counter() - t0
     st = core.stats()
     add_tally(st)
+    if args.dump_outputs and rank == 0:
+        # rank 0's replicas hold every solved row after the exchange; c5rank / c4rank solve only the emulated rank's slices
+        first = {pkg.SIDE_X: prob["u_off"], pkg.SIDE_Y: prob["i_off"]} if rank_shape else {pkg.SIDE_X: 0, pkg.SIDE_Y: 0}
+        dump_outputs(torch, args.dump_outputs, {"X": (als.factors(pkg.SIDE_X), first[pkg.SIDE_X], n_users),
+                                                "Y": (als.factors(pkg.SIDE_Y), first[pkg.SIDE_Y], n_items)}, k)
     # the same K steps again without the per-half check (a diagnostic: what the check costs)
     core.reset_stats()       # (st above keeps the timed region's tallies)
     barrier()

@@ -3,7 +3,7 @@
 // ingest_text_kernels.h (one thread per line) and for the host by tests/cpp/text_parse_host.cpp, which is how
 // the arithmetic below is fuzzed against exact rational arithmetic without a GPU.
 //
-// What is restated (reference paths relative to /root/reference):
+// What is restated (reference paths relative to the myrrix-recommender source tree):
 //   InputFilesReader.readInputFiles, the body of the line loop
 //       online-local/src/net/myrrix/online/generation/InputFilesReader.java:92-158        ("IFR")
 //     IFR:101      empty line or first char '#'                      -> skipped
@@ -16,7 +16,7 @@
 //     IFR:153-157  two tags -> bad line
 //   LangUtils.parseFloat   common/src/net/myrrix/common/LangUtils.java:42-46  (non-finite rejected)
 //   OneWayMigrator         common/src/net/myrrix/common/OneWayMigrator.java (pinned by OneWayMigratorTest.java:28-29)
-// Third-party / JDK behaviour NOT under /root/reference, restated from the published behaviour:
+// Third-party / JDK behaviour NOT under the myrrix-recommender source tree, restated from the published behaviour:
 //   org.apache.mahout:mahout-core:0.8 AbstractIDMigrator.hash: MD5 of the UTF-8 bytes, first 8 digest
 //       bytes as a big-endian long (pinned by the reference's own OneWayMigratorTest vectors)
 //   com.google.guava:guava:14.0.1 CharMatcher.WHITESPACE: U+0009-000D, 0020, 0085, 00A0, 1680, 180E,

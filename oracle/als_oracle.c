@@ -14,7 +14,7 @@
  * UNPINNED: the apparent-rank value reported for a singular system (no reference test pins it;
  * restated from the published commons-math3 3.2 RRQRDecomposition.getRank algorithm).
  *
- * Third-party arithmetic not under /root/reference: org.apache.commons:commons-math3:3.2
+ * Third-party arithmetic not under the myrrix-recommender source tree: org.apache.commons:commons-math3:3.2
  * (pom.xml:81) -- RRQRDecomposition / QRDecomposition.Solver.  Restated below from the published
  * algorithm (Householder QR on the transposed storage with column pivoting by largest remaining
  * column norm; solve = apply Q^T, back-substitute R, undo the permutation).

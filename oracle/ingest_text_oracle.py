@@ -2,7 +2,7 @@
 section 8(f) row 2): bytes of the input files -> lines -> records, tag id sets, knownItemIDs.  Not
 product code: only tests/ (and tools/bench_ingest.py's cpu_baseline leg) may import it.
 
-Follows, in the reference's own order of evaluation (paths relative to /root/reference):
+Follows, in the reference's own order of evaluation (paths relative to the myrrix-recommender source tree):
   InputFilesReader.readInputFiles   online-local/src/net/myrrix/online/generation/InputFilesReader.java
       :71-86    *.csv / *.csv.gz / *.csv.zip, sorted by last-modified time (ByLastModifiedComparator.java:34-44)
       :92-98    one line counter and one bad-line counter over ALL files; "Too many bad lines" is thrown at the
@@ -24,7 +24,7 @@ Follows, in the reference's own order of evaluation (paths relative to /root/ref
 Pinned by the reference's OneWayMigratorTest.java:28-29 and LangUtilsTest.java:23-52 in
 tests/test_ingest_text_oracle.py.
 
-Behaviour of code that is NOT under /root/reference (the JDK, guava 14.0.1, mahout-core 0.8), restated from
+Behaviour of code that is NOT under the myrrix-recommender source tree (the JDK, guava 14.0.1, mahout-core 0.8), restated from
 its published behaviour -- PARITY UNPINNED for these corners, no JVM exists in the image:
   java.io.BufferedReader.readLine (\\n, \\r, \\r\\n), sun.nio.cs.UTF_8 decoding with replacement (JDK 8 malformed
   lengths), String.getBytes(UTF-8), Long.parseLong (JDK 7+), Float.parseFloat (FloatingDecimal.

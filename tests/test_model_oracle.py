@@ -65,11 +65,11 @@ def test_records_are_1024_bytes_and_values_straddle_them(rows):
     assert mo.parse(mo.stream(model, block=7))["X"] == model["X"]          # any record size reads back
 
 
-def test_errors():
+def test_errors(tmp_path):
     with pytest.raises(ValueError):
         mo.payload({"knownItemIDs": None, "X": {1: [float("nan")]}, "Y": {}})
     with pytest.raises(ValueError):
-        mo.write_generation(TINY, "/tmp/model.bin")
+        mo.write_generation(TINY, tmp_path / "model.bin")
     with pytest.raises(IOError):
         mo.parse(TINY_STREAM[:-20] + b"\x78")
     bad = bytearray(TINY_STREAM)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # two SQ counter passes over one 4096-query top-N call (one slot: the kernels one after the other), summarised per kernel
 export TMPDIR=/tmp
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/pmc_topn
 rm -rf $OUT; mkdir -p $OUT
 export MALS_TOPN_SLOTS=1

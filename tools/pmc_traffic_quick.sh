@@ -3,7 +3,7 @@
 set -u
 TAG=$1; shift
 export TMPDIR=/tmp
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/pmct_$TAG
 mkdir -p $OUT
 cd /tmp

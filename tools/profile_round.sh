@@ -5,7 +5,7 @@
 set -u
 TAG=${1:-r1}
 export TMPDIR=/tmp
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT

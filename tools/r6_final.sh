@@ -3,7 +3,7 @@
 # lines (one sort pipeline) and at 5e9 lines (C5's input, user-id range by user-id range) with the partitioned finish's kernel
 # trace at 2.5e9 records; top-N at 1M items, bulk calls and request threads, with its kernel trace.
 set -u
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd $ROOT
 export TMPDIR=/tmp
 tools/profile_round.sh r6c4 > gpurun_out/r6c4.log 2>&1
