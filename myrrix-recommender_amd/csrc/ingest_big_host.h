@@ -291,64 +291,52 @@ struct BigPart {  // what a user range leaves behind until the items are known
   int64_t n_records = 0, n_users = 0, nnz = 0, n_known = 0;
   int64_t u_base = 0, nnz_base = 0, known_base = 0;
   int64_t n_items_local = 0;
-  int64_t* item_ids = nullptr;     // the range's ascending item table
-  unsigned* item_alive = nullptr;  // ... and which of them own an entry here
-  int64_t* user_ids = nullptr;     // live users, ascending
-  int64_t* ptr_local = nullptr;    // [n_users + 1] offsets into the range's entries
-  int64_t* known_ptr_local = nullptr;
+  DeviceBuffer<int64_t> item_ids;     // the range's ascending item table
+  DeviceBuffer<unsigned> item_alive;  // ... and which of them own an entry here
+  DeviceBuffer<int64_t> user_ids;     // live users, ascending
+  DeviceBuffer<int64_t> ptr_local;    // [n_users + 1] offsets into the range's entries
+  DeviceBuffer<int64_t> known_ptr_local;
 };
 
 struct BigState {
   std::vector<BigPart> parts;
-  uint8_t* part = nullptr;
-  int64_t *pu = nullptr, *pi = nullptr;
-  float* pv = nullptr;
-  int64_t* d_split = nullptr;
-  int64_t* item_glob = nullptr;   // merged ascending item table
+  DeviceBuffer<uint8_t> part;
+  DeviceBuffer<int64_t> pu, pi;
+  DeviceBuffer<float> pv;
+  DeviceBuffer<int64_t> d_split;
+  DeviceBuffer<int64_t> item_glob;   // merged ascending item table
   int64_t n_item_glob = 0;
-  unsigned *alive_glob = nullptr, *new_i = nullptr, *cnt = nullptr;
-  unsigned long long* sums64 = nullptr;
-  int32_t* tile_row = nullptr;
-  ~BigState() {
-    dfree(tile_row);
-    for (BigPart& p : parts) {
-      dfree(p.item_ids); dfree(p.item_alive); dfree(p.user_ids); dfree(p.ptr_local); dfree(p.known_ptr_local);
-    }
-    dfree(part); dfree(pu); dfree(pi); dfree(pv); dfree(d_split); dfree(item_glob); dfree(alive_glob); dfree(new_i); dfree(cnt); dfree(sums64);
-  }
+  DeviceBuffer<unsigned> alive_glob, new_i, cnt;
+  DeviceBuffer<unsigned long long> sums64;
+  DeviceBuffer<int32_t> tile_row;
 };
 
 unsigned big_tiles(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + mals::BIG_TILE - 1) / mals::BIG_TILE); }
 
 // a = a U b for ascending tables (b's duplicates of a dropped); a is reallocated
-int big_merge_tables(mals_ingest g, Scratch& s, FinishTmp& t, int64_t*& a, int64_t& na, const int64_t* b, int64_t nb) {
+int big_merge_tables(mals_ingest g, Scratch& s, FinishTmp& t, DeviceBuffer<int64_t>& a, int64_t& na, const int64_t* b, int64_t nb) {
   if (nb == 0) return MALS_OK;
   if (na == 0) {
-    dfree(a);
-    ICHK(g, hipMalloc(&a, sizeof(int64_t) * (size_t)nb));
-    ICHK(g, hipMemcpyAsync(a, b, sizeof(int64_t) * (size_t)nb, hipMemcpyDeviceToDevice, g->stream));
+    ICHK(g, a.alloc((size_t)nb));
+    ICHK(g, hipMemcpyAsync(a.get(), b, sizeof(int64_t) * (size_t)nb, hipMemcpyDeviceToDevice, g->stream));
     na = nb;
     return MALS_OK;
   }
-  hipLaunchKernelGGL(big_fresh_kernel, dim3(blocks_for(nb)), dim3(256), 0, g->stream, b, nb, a, na, t.head);
+  hipLaunchKernelGGL(big_fresh_kernel, dim3(blocks_for(nb)), dim3(256), 0, g->stream, b, nb, a.get(), na, t.head);
   ICHK(g, hipGetLastError());
   unsigned n_fresh = 0;
   if (int rc = scan_u32(g, s, t.head, t.scan, nb, &n_fresh)) return rc;
   if (n_fresh == 0) return MALS_OK;
-  int64_t *fresh = nullptr, *merged = nullptr;
-  ICHK(g, hipMalloc(&fresh, sizeof(int64_t) * (size_t)n_fresh));
-  if (hipMalloc(&merged, sizeof(int64_t) * (size_t)(na + n_fresh)) != hipSuccess) {
-    dfree(fresh);
-    return fail(g, MALS_OOM, "item table merge: out of device memory");
-  }
-  hipLaunchKernelGGL(big_compact_fresh_kernel, dim3(blocks_for(nb)), dim3(256), 0, g->stream, b, nb, t.head, t.scan, fresh);
-  hipLaunchKernelGGL(big_merge_place_kernel, dim3(blocks_for(na)), dim3(256), 0, g->stream, a, na, fresh, (int64_t)n_fresh, merged);
-  hipLaunchKernelGGL(big_merge_place_kernel, dim3(blocks_for(n_fresh)), dim3(256), 0, g->stream, fresh, (int64_t)n_fresh, a, na, merged);
+  DeviceBuffer<int64_t> fresh, merged;
+  ICHK(g, fresh.alloc(n_fresh));
+  if (merged.alloc((size_t)(na + n_fresh)) != hipSuccess) return fail(g, MALS_OOM, "item table merge: out of device memory");
+  hipLaunchKernelGGL(big_compact_fresh_kernel, dim3(blocks_for(nb)), dim3(256), 0, g->stream, b, nb, t.head, t.scan, fresh.get());
+  hipLaunchKernelGGL(big_merge_place_kernel, dim3(blocks_for(na)), dim3(256), 0, g->stream, a.get(), na, fresh.get(), (int64_t)n_fresh, merged.get());
+  hipLaunchKernelGGL(big_merge_place_kernel, dim3(blocks_for(n_fresh)), dim3(256), 0, g->stream, fresh.get(), (int64_t)n_fresh, a.get(), na, merged.get());
   const hipError_t e = hipGetLastError();
   const hipError_t e2 = hipStreamSynchronize(g->stream);
-  dfree(fresh);
-  dfree(a);
-  a = merged;
+  fresh.reset();
+  a = std::move(merged);
   na += n_fresh;
   ICHK(g, e);
   ICHK(g, e2);
@@ -383,14 +371,14 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
   FinishTmp t;
   const auto t_ws = std::chrono::steady_clock::now();
   // results that are filled range by range: R by user with room for every record (entries <= records), knownItemIDs likewise
-  ICHK(g, hipMalloc(&B.part, (size_t)n + 8));
-  ICHK(g, hipMalloc(&B.d_split, sizeof(int64_t) * 256));
-  ICHK(g, hipMalloc(&g->col[0], sizeof(int32_t) * (size_t)n));
-  ICHK(g, hipMalloc(&g->val[0], sizeof(float) * (size_t)n));
-  if (g->want_known) ICHK(g, hipMalloc(&g->known_idx, sizeof(int32_t) * (size_t)n));
-  // ... and R by item likewise, now: a 20 GB hipMalloc in the middle of the pipeline is a second of host time on some boxes
-  ICHK(g, hipMalloc(&g->col[1], sizeof(int32_t) * (size_t)n));
-  ICHK(g, hipMalloc(&g->val[1], sizeof(float) * (size_t)n));
+  ICHK(g, B.part.alloc((size_t)n + 8));
+  ICHK(g, B.d_split.alloc(256));
+  ICHK(g, g->col[0].alloc((size_t)n));
+  ICHK(g, g->val[0].alloc((size_t)n));
+  if (g->want_known) ICHK(g, g->known_idx.alloc((size_t)n));
+  // ... and R by item likewise, now: a 20 GB allocation in the middle of the pipeline is a second of host time on some boxes
+  ICHK(g, g->col[1].alloc((size_t)n));
+  ICHK(g, g->val[1].alloc((size_t)n));
   if (part_cap <= 0) {
     // A range costs 76 bytes per record (24 in the partition buffer, 52 of sort workspace).  Of what is free now -- plus the
     // arena an earlier finish left, which is reused -- 70 % go to it: the id tables, the ranges' item tables and the row
@@ -398,7 +386,7 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
     size_t free_b = 0, total_b = 0;
     ICHK(g, hipMemGetInfo(&free_b, &total_b));
     size_t arena = 0;
-    for (int b = 0; b < mals_ingest_s::N_WS; ++b) arena += g->ws_bytes[b];
+    for (int b = 0; b < mals_ingest_s::N_WS; ++b) arena += g->ws[b].capacity();
     const double budget = 0.7 * ((double)free_b + (double)arena);
     part_cap = (int64_t)std::min<double>((double)MALS_INGEST_ONE_SHOT_MAX, std::max<double>((double)MALS_INGEST_MIN_PART, budget / 76.0));
     // (no point in a range larger than the whole input spread over two ranges)
@@ -407,15 +395,15 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
   // the workspace of one partition; the scans over all records run on tiles of 2048 (one count per tile) and the dense item
   // index is a scan over at most 2^31 items: both inside the same tile-sum buffer
   if (int rc = setup_workspace(g, s, t, std::max<int64_t>(part_cap, n_sample), std::max<int64_t>((n + BIG_TILE - 1) / BIG_TILE, (int64_t)1 << 31))) return rc;
-  ICHK(g, hipMalloc(&B.pu, sizeof(int64_t) * (size_t)part_cap));
-  ICHK(g, hipMalloc(&B.pi, sizeof(int64_t) * (size_t)part_cap));
-  ICHK(g, hipMalloc(&B.pv, sizeof(float) * (size_t)part_cap));
+  ICHK(g, B.pu.alloc((size_t)part_cap));
+  ICHK(g, B.pi.alloc((size_t)part_cap));
+  ICHK(g, B.pv.alloc((size_t)part_cap));
   g->last_workspace_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_ws).count();
   ICHK(g, hipEventRecord(e0, g->stream));
 
   ICHK(g, hipMemsetAsync(s.digit_tot, 0, 2 * sizeof(unsigned long long), g->stream));
-  hipLaunchKernelGGL(ids_high_bits_kernel, dim3(blocks_for(n, 256, 8192)), dim3(256), 0, g->stream, g->d_user, n, s.digit_tot);
-  hipLaunchKernelGGL(ids_high_bits_kernel, dim3(blocks_for(n, 256, 8192)), dim3(256), 0, g->stream, g->d_item, n, s.digit_tot + 1);
+  hipLaunchKernelGGL(ids_high_bits_kernel, dim3(blocks_for(n, 256, 8192)), dim3(256), 0, g->stream, g->d_user.get(), n, s.digit_tot);
+  hipLaunchKernelGGL(ids_high_bits_kernel, dim3(blocks_for(n, 256, 8192)), dim3(256), 0, g->stream, g->d_item.get(), n, s.digit_tot + 1);
   unsigned long long high[2] = {1, 1};
   ICHK(g, hipMemcpyAsync(high, s.digit_tot, sizeof(high), hipMemcpyDeviceToHost, g->stream));
   ICHK(g, hipStreamSynchronize(g->stream));
@@ -423,7 +411,7 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
   const bool user32 = high[0] == 0 && narrow, item32 = high[1] == 0 && narrow;
   g->bytes_moved += 16.0 * (double)n;
 
-  hipLaunchKernelGGL(big_sample_kernel, dim3(blocks_for(n_sample)), dim3(256), 0, g->stream, g->d_user, n, n_sample, s.keys[0], s.pay[0]);
+  hipLaunchKernelGGL(big_sample_kernel, dim3(blocks_for(n_sample)), dim3(256), 0, g->stream, g->d_user.get(), n, n_sample, s.keys[0], s.pay[0]);
   ICHK(g, hipGetLastError());
   int rs = 0;
   if (int rc = radix_sort<uint64_t, unsigned>(g, s, s.keys, s.pay, n_sample, &rs)) return rc;
@@ -438,10 +426,10 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
   std::vector<int64_t> splitters;
   for (int attempt = 0;; ++attempt) {
     splitters = big_pick_splitters(sample, n_parts);
-    ICHK(g, hipMemcpyAsync(B.d_split, splitters.data(), sizeof(int64_t) * splitters.size(), hipMemcpyHostToDevice, g->stream));
-    hipLaunchKernelGGL(big_assign_part_kernel, dim3(blocks_for(n, 256, 1 << 16)), dim3(256), 0, g->stream, g->d_user, n, B.d_split, (int)splitters.size(), B.part);
+    ICHK(g, hipMemcpyAsync(B.d_split.get(), splitters.data(), sizeof(int64_t) * splitters.size(), hipMemcpyHostToDevice, g->stream));
+    hipLaunchKernelGGL(big_assign_part_kernel, dim3(blocks_for(n, 256, 1 << 16)), dim3(256), 0, g->stream, g->d_user.get(), n, B.d_split.get(), (int)splitters.size(), B.part.get());
     ICHK(g, hipMemsetAsync(s.digit_tot, 0, 256 * sizeof(unsigned long long), g->stream));
-    hipLaunchKernelGGL(big_part_histogram_kernel, dim3(blocks_for(n, 256, 1 << 14)), dim3(256), 0, g->stream, B.part, n, s.digit_tot);
+    hipLaunchKernelGGL(big_part_histogram_kernel, dim3(blocks_for(n, 256, 1 << 14)), dim3(256), 0, g->stream, B.part.get(), n, s.digit_tot);
     ICHK(g, hipGetLastError());
     ICHK(g, hipMemcpyAsync(hist.data(), s.digit_tot, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
     ICHK(g, hipStreamSynchronize(g->stream));
@@ -470,16 +458,16 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
     const int64_t np = (int64_t)hist[(size_t)p];
     bp.n_records = np;
     if (np == 0) continue;
-    hipLaunchKernelGGL(big_count_part_kernel, dim3(n_tiles), dim3(256), 0, g->stream, B.part, n, (uint8_t)p, t.head);
+    hipLaunchKernelGGL(big_count_part_kernel, dim3(n_tiles), dim3(256), 0, g->stream, B.part.get(), n, (uint8_t)p, t.head);
     ICHK(g, hipGetLastError());
     unsigned counted = 0;
     if (int rc = scan_u32(g, s, t.head, t.head, (int64_t)n_tiles, &counted)) return rc;
     if ((int64_t)counted != np) return fail(g, MALS_HIP_ERROR, "ingest: partition size mismatch");
-    hipLaunchKernelGGL(big_compact_part_kernel, dim3(n_tiles), dim3(256), 0, g->stream, B.part, n, (uint8_t)p, t.head, g->d_user, g->d_item, g->d_value,
-                       B.pu, B.pi, B.pv);
+    hipLaunchKernelGGL(big_compact_part_kernel, dim3(n_tiles), dim3(256), 0, g->stream, B.part.get(), n, (uint8_t)p, t.head, g->d_user.get(), g->d_item.get(), g->d_value.get(),
+                       B.pu.get(), B.pi.get(), B.pv.get());
     ICHK(g, hipGetLastError());
     g->bytes_moved += 2.0 * (double)n + 48.0 * (double)np;
-    const Records rec = {B.pu, B.pi, B.pv, np};
+    const Records rec = {B.pu.get(), B.pi.get(), B.pv.get(), np};
     unsigned n_u_all = 0, n_i_all = 0, n_users = 0, nnz = 0;
     FinishTmp tp;   // the range's temporaries (freed at the end of the iteration), sharing the arena views
     tp.head = t.head; tp.scan = t.scan; tp.ri = t.ri; tp.keep = t.keep; tp.pair_val = t.pair_val; tp.coo_row = t.coo_row; tp.present = t.present;
@@ -487,49 +475,47 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
     if (int rc = item32 ? stage_items<uint32_t>(g, s, tp, rec, user32, &ra, &n_i_all) : stage_items<uint64_t>(g, s, tp, rec, user32, &ra, &n_i_all)) return rc;
     if (int rc = user32 ? stage_users<uint32_t>(g, s, tp, rec, ra, sorted_val, &r, &n_u_all) : stage_users<uint64_t>(g, s, tp, rec, ra, sorted_val, &r, &n_u_all))
       return rc;
-    ICHK(g, hipMalloc(&tp.alive_u, sizeof(unsigned) * (size_t)n_u_all));
-    ICHK(g, hipMalloc(&tp.alive_i, sizeof(unsigned) * (size_t)n_i_all));
-    ICHK(g, hipMalloc(&tp.new_u, sizeof(unsigned) * (size_t)n_u_all));
-    ICHK(g, hipMemsetAsync(tp.alive_u, 0, sizeof(unsigned) * (size_t)n_u_all, g->stream));
-    ICHK(g, hipMemsetAsync(tp.alive_i, 0, sizeof(unsigned) * (size_t)n_i_all, g->stream));
+    ICHK(g, tp.alive_u.alloc(n_u_all));
+    ICHK(g, tp.alive_i.alloc(n_i_all));
+    ICHK(g, tp.new_u.alloc(n_u_all));
+    ICHK(g, hipMemsetAsync(tp.alive_u.get(), 0, sizeof(unsigned) * (size_t)n_u_all, g->stream));
+    ICHK(g, hipMemsetAsync(tp.alive_i.get(), 0, sizeof(unsigned) * (size_t)n_i_all, g->stream));
     hipLaunchKernelGGL(replay_pairs_kernel, dim3(blocks_for(np)), dim3(256), 0, g->stream, s.keys[r], sorted_val, np, g->zero_threshold, tp.keep, tp.pair_val,
-                       tp.alive_u, tp.alive_i, tp.present);
+                       tp.alive_u.get(), tp.alive_i.get(), tp.present);
     ICHK(g, hipGetLastError());
     g->bytes_moved += (8.0 + 4.0 + 8.0 + (tp.present ? 4.0 : 0.0)) * (double)np;
-    if (int rc = scan_u32(g, s, tp.alive_u, tp.new_u, n_u_all, &n_users)) return rc;
+    if (int rc = scan_u32(g, s, tp.alive_u.get(), tp.new_u.get(), n_u_all, &n_users)) return rc;
     if (int rc = scan_u32(g, s, tp.keep, tp.scan, np, &nnz)) return rc;
     bp.n_users = n_users;
     bp.nnz = nnz;
     bp.n_items_local = n_i_all;
-    bp.item_ids = tp.iid_all;     // kept: the range's item table and its liveness
-    tp.iid_all = nullptr;
-    bp.item_alive = tp.alive_i;
-    tp.alive_i = nullptr;
-    ICHK(g, hipMalloc(&bp.user_ids, sizeof(int64_t) * std::max<size_t>(n_users, 1)));
-    ICHK(g, hipMalloc(&bp.ptr_local, sizeof(int64_t) * ((size_t)n_users + 1)));
-    hipLaunchKernelGGL(compact_ids_kernel, dim3(blocks_for(n_u_all)), dim3(256), 0, g->stream, tp.uid_all, tp.alive_u, tp.new_u, (int64_t)n_u_all, bp.user_ids);
-    hipLaunchKernelGGL(big_compact_pairs_kernel, dim3(blocks_for(np)), dim3(256), 0, g->stream, s.keys[r], tp.keep, tp.scan, tp.pair_val, np, tp.new_u,
-                       tp.coo_row, g->col[0] + nnz_base, g->val[0] + nnz_base);
+    bp.item_ids = std::move(tp.iid_all);     // kept: the range's item table and its liveness
+    bp.item_alive = std::move(tp.alive_i);
+    ICHK(g, bp.user_ids.alloc(std::max<size_t>(n_users, 1)));
+    ICHK(g, bp.ptr_local.alloc((size_t)n_users + 1));
+    hipLaunchKernelGGL(compact_ids_kernel, dim3(blocks_for(n_u_all)), dim3(256), 0, g->stream, tp.uid_all.get(), tp.alive_u.get(), tp.new_u.get(), (int64_t)n_u_all, bp.user_ids.get());
+    hipLaunchKernelGGL(big_compact_pairs_kernel, dim3(blocks_for(np)), dim3(256), 0, g->stream, s.keys[r], tp.keep, tp.scan, tp.pair_val, np, tp.new_u.get(),
+                       tp.coo_row, g->col[0].get() + nnz_base, g->val[0].get() + nnz_base);
     hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(blocks_for((int64_t)nnz + 1)), dim3(256), 0, g->stream, tp.coo_row, (int64_t)nnz, (int64_t)n_users,
-                       bp.ptr_local);
+                       bp.ptr_local.get());
     ICHK(g, hipGetLastError());
     g->bytes_moved += 16.0 * (double)np + 16.0 * (double)nnz + 8.0 * (double)n_users;
     if (g->want_known) {
       unsigned n_known = 0;
       if (int rc = scan_u32(g, s, tp.present, tp.scan, np, &n_known)) return rc;
       bp.n_known = n_known;
-      ICHK(g, hipMalloc(&bp.known_ptr_local, sizeof(int64_t) * ((size_t)n_users + 1)));
+      ICHK(g, bp.known_ptr_local.alloc((size_t)n_users + 1));
       int32_t* known_row = (int32_t*)tp.ri;
       hipLaunchKernelGGL(big_compact_pairs_kernel, dim3(blocks_for(np)), dim3(256), 0, g->stream, s.keys[r], tp.present, tp.scan, (const float*)nullptr, np,
-                         tp.new_u, known_row, g->known_idx + known_base, (float*)nullptr);
+                         tp.new_u.get(), known_row, g->known_idx.get() + known_base, (float*)nullptr);
       hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(blocks_for((int64_t)n_known + 1)), dim3(256), 0, g->stream, known_row, (int64_t)n_known,
-                         (int64_t)n_users, bp.known_ptr_local);
+                         (int64_t)n_users, bp.known_ptr_local.get());
       ICHK(g, hipGetLastError());
       g->bytes_moved += (4.0 + 12.0 + 8.0) * (double)np + 12.0 * (double)n_known + 8.0 * (double)n_users;
       known_base += n_known;
     }
     // the merged item table grows by what this range saw for the first time
-    if (int rc = big_merge_tables(g, s, t, B.item_glob, B.n_item_glob, bp.item_ids, bp.n_items_local)) return rc;
+    if (int rc = big_merge_tables(g, s, t, B.item_glob, B.n_item_glob, bp.item_ids.get(), bp.n_items_local)) return rc;
     ICHK(g, hipStreamSynchronize(g->stream));   // tp's allocations go away
     u_base += n_users;
     nnz_base += nnz;
@@ -537,76 +523,74 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
       return fail(g, MALS_INVALID_ARG, "ingest: more than 2^31 distinct users or items (dense indices are 32-bit)");
   }
   const int64_t n_users = u_base, nnz = nnz_base, n_known = known_base;
-  dfree(B.pu); dfree(B.pi); dfree(B.pv); dfree(B.part);
+  B.pu.reset(); B.pi.reset(); B.pv.reset(); B.part.reset();
 
   // ---- 2. items: liveness through the rank maps, dense index, renumbering -------------------------------------------------
   const int64_t n_glob = B.n_item_glob;
-  ICHK(g, hipMalloc(&B.alive_glob, sizeof(unsigned) * std::max<size_t>((size_t)n_glob, 1)));
-  ICHK(g, hipMalloc(&B.new_i, sizeof(unsigned) * std::max<size_t>((size_t)n_glob, 1)));
-  ICHK(g, hipMemsetAsync(B.alive_glob, 0, sizeof(unsigned) * std::max<size_t>((size_t)n_glob, 1), g->stream));
+  ICHK(g, B.alive_glob.alloc(std::max<size_t>((size_t)n_glob, 1)));
+  ICHK(g, B.new_i.alloc(std::max<size_t>((size_t)n_glob, 1)));
+  ICHK(g, hipMemsetAsync(B.alive_glob.get(), 0, sizeof(unsigned) * std::max<size_t>((size_t)n_glob, 1), g->stream));
   // (the maps live in the keys arena: a range's item table is no longer than the range)
   int64_t* map = reinterpret_cast<int64_t*>(s.keys[0]);
   int32_t* final_map = reinterpret_cast<int32_t*>(s.keys[1]);
   for (BigPart& bp : B.parts) {
     if (bp.n_items_local == 0) continue;
-    hipLaunchKernelGGL(index_of_ids_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_ids, bp.n_items_local, B.item_glob, n_glob, map);
-    hipLaunchKernelGGL(big_mark_alive_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_alive, map, bp.n_items_local, B.alive_glob);
+    hipLaunchKernelGGL(index_of_ids_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_ids.get(), bp.n_items_local, B.item_glob.get(), n_glob, map);
+    hipLaunchKernelGGL(big_mark_alive_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_alive.get(), map, bp.n_items_local, B.alive_glob.get());
     ICHK(g, hipGetLastError());
   }
   unsigned n_items_u = 0;
-  if (int rc = scan_u32(g, s, B.alive_glob, B.new_i, n_glob, &n_items_u)) return rc;
+  if (int rc = scan_u32(g, s, B.alive_glob.get(), B.new_i.get(), n_glob, &n_items_u)) return rc;
   const int64_t n_items = n_items_u;
   g->n_users = n_users;
   g->n_items = n_items;
   g->nnz = nnz;
   g->n_known = n_known;
-  ICHK(g, hipMalloc(&g->ids[0], sizeof(int64_t) * std::max<size_t>((size_t)n_users, 1)));
-  ICHK(g, hipMalloc(&g->ids[1], sizeof(int64_t) * std::max<size_t>((size_t)n_items, 1)));
-  ICHK(g, hipMalloc(&g->ptr[0], sizeof(int64_t) * ((size_t)n_users + 1)));
-  ICHK(g, hipMalloc(&g->ptr[1], sizeof(int64_t) * ((size_t)n_items + 1)));
-  if (g->want_known) ICHK(g, hipMalloc(&g->known_ptr, sizeof(int64_t) * ((size_t)n_users + 1)));
-  hipLaunchKernelGGL(compact_ids_kernel, dim3(blocks_for(n_glob)), dim3(256), 0, g->stream, B.item_glob, B.alive_glob, B.new_i, n_glob, g->ids[1]);
+  ICHK(g, g->ids[0].alloc(std::max<size_t>((size_t)n_users, 1)));
+  ICHK(g, g->ids[1].alloc(std::max<size_t>((size_t)n_items, 1)));
+  ICHK(g, g->ptr[0].alloc((size_t)n_users + 1));
+  ICHK(g, g->ptr[1].alloc((size_t)n_items + 1));
+  if (g->want_known) ICHK(g, g->known_ptr.alloc((size_t)n_users + 1));
+  hipLaunchKernelGGL(compact_ids_kernel, dim3(blocks_for(n_glob)), dim3(256), 0, g->stream, B.item_glob.get(), B.alive_glob.get(), B.new_i.get(), n_glob, g->ids[1].get());
   ICHK(g, hipGetLastError());
-  ICHK(g, hipMemsetAsync(g->ptr[0], 0, sizeof(int64_t), g->stream));   // (no range, no user: the one offset there is)
-  if (g->want_known) ICHK(g, hipMemsetAsync(g->known_ptr, 0, sizeof(int64_t), g->stream));
+  ICHK(g, hipMemsetAsync(g->ptr[0].get(), 0, sizeof(int64_t), g->stream));   // (no range, no user: the one offset there is)
+  if (g->want_known) ICHK(g, hipMemsetAsync(g->known_ptr.get(), 0, sizeof(int64_t), g->stream));
   for (BigPart& bp : B.parts) {
     if (bp.n_records == 0) continue;
-    hipLaunchKernelGGL(index_of_ids_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_ids, bp.n_items_local, B.item_glob, n_glob, map);
-    hipLaunchKernelGGL(big_final_map_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, map, bp.n_items_local, B.new_i, final_map);
-    if (bp.nnz) hipLaunchKernelGGL(big_remap_kernel, dim3(blocks_for(bp.nnz)), dim3(256), 0, g->stream, g->col[0] + bp.nnz_base, bp.nnz, final_map);
+    hipLaunchKernelGGL(index_of_ids_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_ids.get(), bp.n_items_local, B.item_glob.get(), n_glob, map);
+    hipLaunchKernelGGL(big_final_map_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, map, bp.n_items_local, B.new_i.get(), final_map);
+    if (bp.nnz) hipLaunchKernelGGL(big_remap_kernel, dim3(blocks_for(bp.nnz)), dim3(256), 0, g->stream, g->col[0].get() + bp.nnz_base, bp.nnz, final_map);
     if (g->want_known && bp.n_known)
-      hipLaunchKernelGGL(big_remap_kernel, dim3(blocks_for(bp.n_known)), dim3(256), 0, g->stream, g->known_idx + bp.known_base, bp.n_known, final_map);
-    if (bp.n_users) ICHK(g, hipMemcpyAsync(g->ids[0] + bp.u_base, bp.user_ids, sizeof(int64_t) * (size_t)bp.n_users, hipMemcpyDeviceToDevice, g->stream));
-    hipLaunchKernelGGL(big_add_base_kernel, dim3(blocks_for(bp.n_users + 1)), dim3(256), 0, g->stream, bp.ptr_local, bp.n_users + 1, bp.nnz_base,
-                       g->ptr[0] + bp.u_base);
+      hipLaunchKernelGGL(big_remap_kernel, dim3(blocks_for(bp.n_known)), dim3(256), 0, g->stream, g->known_idx.get() + bp.known_base, bp.n_known, final_map);
+    if (bp.n_users) ICHK(g, hipMemcpyAsync(g->ids[0].get() + bp.u_base, bp.user_ids.get(), sizeof(int64_t) * (size_t)bp.n_users, hipMemcpyDeviceToDevice, g->stream));
+    hipLaunchKernelGGL(big_add_base_kernel, dim3(blocks_for(bp.n_users + 1)), dim3(256), 0, g->stream, bp.ptr_local.get(), bp.n_users + 1, bp.nnz_base,
+                       g->ptr[0].get() + bp.u_base);
     if (g->want_known)
-      hipLaunchKernelGGL(big_add_base_kernel, dim3(blocks_for(bp.n_users + 1)), dim3(256), 0, g->stream, bp.known_ptr_local, bp.n_users + 1, bp.known_base,
-                         g->known_ptr + bp.u_base);
+      hipLaunchKernelGGL(big_add_base_kernel, dim3(blocks_for(bp.n_users + 1)), dim3(256), 0, g->stream, bp.known_ptr_local.get(), bp.n_users + 1, bp.known_base,
+                         g->known_ptr.get() + bp.u_base);
     ICHK(g, hipGetLastError());
     g->bytes_moved += 8.0 * (double)bp.nnz + 24.0 * (double)bp.n_users;
   }
   ICHK(g, hipStreamSynchronize(g->stream));
-  for (BigPart& bp : B.parts) {
-    dfree(bp.item_ids); dfree(bp.item_alive); dfree(bp.user_ids); dfree(bp.ptr_local); dfree(bp.known_ptr_local);
-  }
-  dfree(B.alive_glob); dfree(B.new_i); dfree(B.item_glob);
+  B.parts.clear();
+  B.alive_glob.reset(); B.new_i.reset(); B.item_glob.reset();
 
   // ---- 3. R^T ---------------------------------------------------------------------------------------------------------------
   // item ranges from a sample of the entries (every 61st), cut at 0.7 of a partition; a range that turns out larger is halved
-  ICHK(g, hipMalloc(&B.cnt, sizeof(unsigned) * ((size_t)n_items + 8)));
+  ICHK(g, B.cnt.alloc((size_t)n_items + 8));
   const int64_t tiles64 = (n_items + SC_TILE - 1) / SC_TILE + 1;
-  ICHK(g, hipMalloc(&B.sums64, sizeof(unsigned long long) * ((size_t)tiles64 + 1)));
-  ICHK(g, hipMemsetAsync(B.cnt, 0, sizeof(unsigned) * ((size_t)n_items + 8), g->stream));
+  ICHK(g, B.sums64.alloc((size_t)tiles64 + 1));
+  ICHK(g, hipMemsetAsync(B.cnt.get(), 0, sizeof(unsigned) * ((size_t)n_items + 8), g->stream));
   const int64_t stride = nnz > ((int64_t)1 << 24) ? 61 : 1;
-  if (nnz) hipLaunchKernelGGL(big_item_sample_kernel, dim3(blocks_for((nnz + stride - 1) / stride, 256, 1 << 16)), dim3(256), 0, g->stream, g->col[0], nnz, stride, B.cnt);
+  if (nnz) hipLaunchKernelGGL(big_item_sample_kernel, dim3(blocks_for((nnz + stride - 1) / stride, 256, 1 << 16)), dim3(256), 0, g->stream, g->col[0].get(), nnz, stride, B.cnt.get());
   const unsigned t64 = (unsigned)std::max<int64_t>(1, (n_items + SC_TILE - 1) / SC_TILE);
-  hipLaunchKernelGGL(big_scan64_reduce_kernel, dim3(t64), dim3(256), 0, g->stream, B.cnt, n_items, B.sums64);
-  hipLaunchKernelGGL(big_scan64_sums_kernel, dim3(1), dim3(64), 0, g->stream, B.sums64, (int64_t)t64, B.sums64 + t64);
-  hipLaunchKernelGGL(big_scan64_apply_kernel, dim3(t64), dim3(256), 0, g->stream, B.cnt, n_items, B.sums64, B.sums64 + t64, g->ptr[1]);
+  hipLaunchKernelGGL(big_scan64_reduce_kernel, dim3(t64), dim3(256), 0, g->stream, B.cnt.get(), n_items, B.sums64.get());
+  hipLaunchKernelGGL(big_scan64_sums_kernel, dim3(1), dim3(64), 0, g->stream, B.sums64.get(), (int64_t)t64, B.sums64.get() + t64);
+  hipLaunchKernelGGL(big_scan64_apply_kernel, dim3(t64), dim3(256), 0, g->stream, B.cnt.get(), n_items, B.sums64.get(), B.sums64.get() + t64, g->ptr[1].get());
   ICHK(g, hipGetLastError());
   g->bytes_moved += 4.0 * (double)nnz / (double)stride + 16.0 * (double)n_items;
   std::vector<int64_t> cp((size_t)n_items + 1);   // estimated offsets, in sampled entries
-  ICHK(g, hipMemcpyAsync(cp.data(), g->ptr[1], sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost, g->stream));
+  ICHK(g, hipMemcpyAsync(cp.data(), g->ptr[1].get(), sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost, g->stream));
   ICHK(g, hipStreamSynchronize(g->stream));
   std::vector<std::pair<int64_t, int64_t>> todo;   // item ranges still to do, the first on top
   {
@@ -621,18 +605,18 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
     todo.assign(ranges.rbegin(), ranges.rend());
   }
   const unsigned e_tiles = big_tiles(nnz);
-  ICHK(g, hipMalloc(&B.tile_row, sizeof(int32_t) * ((size_t)e_tiles + 1)));
-  hipLaunchKernelGGL(big_tile_rows_kernel, dim3(blocks_for((int64_t)e_tiles + 1)), dim3(256), 0, g->stream, g->ptr[0], std::max<int64_t>(n_users, 1), nnz,
-                     (int64_t)e_tiles, B.tile_row);
+  ICHK(g, B.tile_row.alloc((size_t)e_tiles + 1));
+  hipLaunchKernelGGL(big_tile_rows_kernel, dim3(blocks_for((int64_t)e_tiles + 1)), dim3(256), 0, g->stream, g->ptr[0].get(), std::max<int64_t>(n_users, 1), nnz,
+                     (int64_t)e_tiles, B.tile_row.get());
   ICHK(g, hipGetLastError());
   int64_t done_entries = 0;   // R^T's offsets so far: every range starts where the one before it ended
-  ICHK(g, hipMemsetAsync(g->ptr[1], 0, sizeof(int64_t) * ((size_t)n_items + 1), g->stream));
+  ICHK(g, hipMemsetAsync(g->ptr[1].get(), 0, sizeof(int64_t) * ((size_t)n_items + 1), g->stream));
   while (!todo.empty()) {
     const int64_t a = todo.back().first, b = todo.back().second;
     todo.pop_back();
     int64_t nq = 0;
     if (nnz > 0) {
-      hipLaunchKernelGGL(big_count_items_kernel, dim3(e_tiles), dim3(256), 0, g->stream, g->col[0], nnz, (int32_t)a, (int32_t)b, t.head);
+      hipLaunchKernelGGL(big_count_items_kernel, dim3(e_tiles), dim3(256), 0, g->stream, g->col[0].get(), nnz, (int32_t)a, (int32_t)b, t.head);
       ICHK(g, hipGetLastError());
       unsigned counted = 0;
       if (int rc = scan_u32(g, s, t.head, t.head, (int64_t)e_tiles, &counted)) return rc;
@@ -648,19 +632,19 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
     }
     ++g->last_item_ranges;
     if (nq > 0) {
-      hipLaunchKernelGGL(big_select_items_kernel, dim3(e_tiles), dim3(256), 0, g->stream, g->col[0], g->val[0], nnz, g->ptr[0], B.tile_row, (int32_t)a, (int32_t)b,
+      hipLaunchKernelGGL(big_select_items_kernel, dim3(e_tiles), dim3(256), 0, g->stream, g->col[0].get(), g->val[0].get(), nnz, g->ptr[0].get(), B.tile_row.get(), (int32_t)a, (int32_t)b,
                          t.head, s.keys[0], s.pay[0]);
       ICHK(g, hipGetLastError());
       int r2 = 0;
       if (int rc = radix_sort<uint64_t, unsigned>(g, s, s.keys, s.pay, nq, &r2, 4, ((uint64_t)(b - a - 1) << 32) | 0xffffffffull)) return rc;
-      hipLaunchKernelGGL(big_transpose_write_kernel, dim3(blocks_for(nq)), dim3(256), 0, g->stream, s.keys[r2], s.pay[r2], nq, t.coo_row, g->col[1] + done_entries,
-                         g->val[1] + done_entries);
+      hipLaunchKernelGGL(big_transpose_write_kernel, dim3(blocks_for(nq)), dim3(256), 0, g->stream, s.keys[r2], s.pay[r2], nq, t.coo_row, g->col[1].get() + done_entries,
+                         g->val[1].get() + done_entries);
       ICHK(g, hipGetLastError());
       g->bytes_moved += 4.0 * (double)nnz + 40.0 * (double)nq;
     }
     // offsets of the range's items: local from the sorted item column, then shifted behind the ranges before it
-    hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(blocks_for(nq + 1)), dim3(256), 0, g->stream, t.coo_row, nq, b - a, g->ptr[1] + a);
-    hipLaunchKernelGGL(big_add_base_inplace_kernel, dim3(blocks_for(b - a + 1)), dim3(256), 0, g->stream, g->ptr[1] + a, b - a + 1, done_entries);
+    hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(blocks_for(nq + 1)), dim3(256), 0, g->stream, t.coo_row, nq, b - a, g->ptr[1].get() + a);
+    hipLaunchKernelGGL(big_add_base_inplace_kernel, dim3(blocks_for(b - a + 1)), dim3(256), 0, g->stream, g->ptr[1].get() + a, b - a + 1, done_entries);
     ICHK(g, hipGetLastError());
     done_entries += nq;
   }

@@ -20,19 +20,10 @@ struct TextScratch {
   unsigned* block_counts = nullptr;  // line starts per LT_BLOCK_BYTES, then their exclusive scan
 };
 
-template <typename P>
-int grow(mals_ingest g, P*& p, size_t& cap, size_t want, bool keep, size_t used = 0) {
-  if (want <= cap) return MALS_OK;
-  size_t ncap = std::max(want, cap + cap / 2);
-  P* q = nullptr;
-  ICHK(g, hipMalloc(&q, sizeof(P) * ncap));
-  if (keep && used) {
-    ICHK(g, hipMemcpyAsync(q, p, sizeof(P) * used, hipMemcpyDeviceToDevice, g->stream));
-    ICHK(g, hipStreamSynchronize(g->stream));
-  }
-  dfree(p);
-  p = q;
-  cap = ncap;
+// room for `want` elements, by at least half the capacity at a time; the first `used` elements are kept
+template <typename T>
+int reserve_text(mals_ingest g, DeviceBuffer<T>& b, size_t want, size_t used = 0) {
+  if (want > b.capacity()) ICHK(g, b.grow_keep(std::max(want, b.capacity() + b.capacity() / 2), used, g->stream));
   return MALS_OK;
 }
 
@@ -44,27 +35,9 @@ int text_fail(mals_ingest g, int code, const std::string& msg) {
 }
 
 int ensure_record_capacity(mals_ingest g, int64_t extra) {
-  if (g->n + extra <= g->cap) return MALS_OK;
-  const int64_t cap = std::max<int64_t>(g->n + extra, g->cap + g->cap / 2);
-  int64_t *u = nullptr, *it = nullptr;
-  float* v = nullptr;
-  ICHK(g, hipMalloc(&u, sizeof(int64_t) * (size_t)cap));
-  ICHK(g, hipMalloc(&it, sizeof(int64_t) * (size_t)cap));
-  ICHK(g, hipMalloc(&v, sizeof(float) * (size_t)cap));
-  if (g->n) {
-    ICHK(g, hipMemcpyAsync(u, g->d_user, sizeof(int64_t) * (size_t)g->n, hipMemcpyDeviceToDevice, g->stream));
-    ICHK(g, hipMemcpyAsync(it, g->d_item, sizeof(int64_t) * (size_t)g->n, hipMemcpyDeviceToDevice, g->stream));
-    ICHK(g, hipMemcpyAsync(v, g->d_value, sizeof(float) * (size_t)g->n, hipMemcpyDeviceToDevice, g->stream));
-    ICHK(g, hipStreamSynchronize(g->stream));
-  }
-  dfree(g->d_user);
-  dfree(g->d_item);
-  dfree(g->d_value);
-  g->d_user = u;
-  g->d_item = it;
-  g->d_value = v;
-  g->cap = cap;
-  return MALS_OK;
+  const int64_t cap = record_capacity(g);
+  if (g->n + extra <= cap) return MALS_OK;
+  return grow_records(g, std::max<int64_t>(g->n + extra, cap + cap / 2));
 }
 
 // One block: the bytes d_text[0, total) are on the device; lines are taken from [0, region) (region ends right after
@@ -96,68 +69,67 @@ int process_text_region(mals_ingest g, size_t region) {
   // 1. line starts
   const int64_t n_blk = ((int64_t)region + LT_BLOCK_BYTES - 1) / LT_BLOCK_BYTES;
   const int64_t tiles = (n_blk + SC_TILE - 1) / SC_TILE;
-  if (int rc = grow(g, g->t_block_counts, g->t_block_counts_cap, (size_t)n_blk, false)) return rc;
-  if (int rc = grow(g, g->t_tile_sums, g->t_tile_sums_cap, (size_t)tiles + 2, false)) return rc;
+  if (int rc = reserve_text(g, g->t_block_counts, (size_t)n_blk)) return rc;
+  if (int rc = reserve_text(g, g->t_tile_sums, (size_t)tiles + 2)) return rc;
   Scratch s;
-  s.tile_sums = g->t_tile_sums;
-  s.total = g->t_tile_sums + tiles;  // one word behind the tile sums
-  hipLaunchKernelGGL(line_count_kernel, dim3((unsigned)n_blk), dim3(256), 0, g->stream, g->d_text, (int64_t)region, g->t_block_counts);
+  s.tile_sums = g->t_tile_sums.get();
+  s.total = g->t_tile_sums.get() + tiles;  // one word behind the tile sums
+  hipLaunchKernelGGL(line_count_kernel, dim3((unsigned)n_blk), dim3(256), 0, g->stream, g->d_text.get(), (int64_t)region, g->t_block_counts.get());
   ICHK(g, hipGetLastError());
   unsigned n_lines = 0;
-  if (int rc = scan_u32(g, s, g->t_block_counts, g->t_block_counts, n_blk, &n_lines)) return rc;
+  if (int rc = scan_u32(g, s, g->t_block_counts.get(), g->t_block_counts.get(), n_blk, &n_lines)) return rc;
   if (int rc = seg_end()) return rc;
   if (n_lines == 0) return fail(g, MALS_HIP_ERROR, "internal: a non-empty text region without a line");
   // sequential rule IFR:96-98: the line that follows the 101st bad line throws
   if (g->abort_armed) return text_fail(g, MALS_IO_ERROR, "Too many bad lines; aborting");
   // 2. per-line arrays
   const size_t L = n_lines;
-  if (L > g->t_line_cap) {
-    dfree(g->t_starts); dfree(g->t_status); dfree(g->t_user); dfree(g->t_item); dfree(g->t_value);
-    dfree(g->t_flag); dfree(g->t_flag_scan); dfree(g->t_defer);
-    g->t_line_cap = 0;
+  if (L > g->t_starts.capacity()) {
+    g->t_starts.reset(); g->t_status.reset(); g->t_user.reset(); g->t_item.reset(); g->t_value.reset();
+    g->t_flag.reset(); g->t_defer.reset();
     const size_t cap = L + L / 4;
-    ICHK(g, hipMalloc(&g->t_starts, sizeof(unsigned) * cap));
-    ICHK(g, hipMalloc(&g->t_status, cap + 8));
-    ICHK(g, hipMalloc(&g->t_user, sizeof(int64_t) * cap));
-    ICHK(g, hipMalloc(&g->t_item, sizeof(int64_t) * cap));
-    ICHK(g, hipMalloc(&g->t_value, sizeof(uint32_t) * cap));
-    ICHK(g, hipMalloc(&g->t_flag, sizeof(unsigned) * cap));
-    ICHK(g, hipMalloc(&g->t_defer, sizeof(unsigned) * cap));
-    g->t_line_cap = cap;
+    ICHK(g, g->t_status.alloc(cap + 8));
+    ICHK(g, g->t_user.alloc(cap));
+    ICHK(g, g->t_item.alloc(cap));
+    ICHK(g, g->t_value.alloc(cap));
+    ICHK(g, g->t_flag.alloc(cap));
+    ICHK(g, g->t_defer.alloc(cap));
+    ICHK(g, g->t_starts.alloc(cap));  // last: its capacity says that all of them exist
   }
   {
     const int64_t lt = ((int64_t)L + SC_TILE - 1) / SC_TILE;
-    if (int rc = grow(g, g->t_tile_sums, g->t_tile_sums_cap, (size_t)std::max(lt, tiles) + 2, false)) return rc;
-    s.tile_sums = g->t_tile_sums;
-    s.total = g->t_tile_sums + std::max(lt, tiles);
+    if (int rc = reserve_text(g, g->t_tile_sums, (size_t)std::max(lt, tiles) + 2)) return rc;
+    s.tile_sums = g->t_tile_sums.get();
+    s.total = g->t_tile_sums.get() + std::max(lt, tiles);
   }
-  if (!g->t_counters) ICHK(g, hipMalloc(&g->t_counters, sizeof(TextCounters) + 2 * sizeof(unsigned)));
+  if (!g->t_counters) ICHK(g, g->t_counters.alloc(sizeof(TextCounters) + 2 * sizeof(unsigned)));
+  TextCounters* counters = reinterpret_cast<TextCounters*>(g->t_counters.get());
   ICHK(g, hipEventRecord(e0, g->stream));
-  ICHK(g, hipMemsetAsync(g->t_counters, 0, sizeof(TextCounters) + 2 * sizeof(unsigned), g->stream));
-  hipLaunchKernelGGL(line_starts_kernel, dim3((unsigned)n_blk), dim3(256), 0, g->stream, g->d_text, (int64_t)region, g->t_block_counts,
-                     g->t_starts);
+  ICHK(g, hipMemsetAsync(counters, 0, sizeof(TextCounters) + 2 * sizeof(unsigned), g->stream));
+  hipLaunchKernelGGL(line_starts_kernel, dim3((unsigned)n_blk), dim3(256), 0, g->stream, g->d_text.get(), (int64_t)region, g->t_block_counts.get(),
+                     g->t_starts.get());
   const unsigned lgrid = (unsigned)((L + 255) / 256);
   const int first = g->lines == 0 ? 1 : 0;
   // 3. parse: the bulk, then whatever it handed on
-  hipLaunchKernelGGL(parse_lines_kernel, dim3(lgrid), dim3(256), 0, g->stream, g->d_text, g->t_starts, (int64_t)L, (unsigned)region, first,
-                     g->t_status, g->t_user, g->t_item, g->t_value, g->t_defer, g->t_counters);
-  hipLaunchKernelGGL(parse_deferred_kernel, dim3((unsigned)std::min<size_t>((L + 63) / 64, 4096)), dim3(64), 0, g->stream, g->d_text,
-                     g->t_starts, (int64_t)L, (unsigned)region, first, g->t_status, g->t_user, g->t_item, g->t_value, g->t_defer,
-                     g->t_counters);
+  hipLaunchKernelGGL(parse_lines_kernel, dim3(lgrid), dim3(256), 0, g->stream, g->d_text.get(), g->t_starts.get(), (int64_t)L, (unsigned)region, first,
+                     g->t_status.get(), g->t_user.get(), g->t_item.get(), g->t_value.get(), g->t_defer.get(), counters);
+  hipLaunchKernelGGL(parse_deferred_kernel, dim3((unsigned)std::min<size_t>((L + 63) / 64, 4096)), dim3(64), 0, g->stream, g->d_text.get(),
+                     g->t_starts.get(), (int64_t)L, (unsigned)region, first, g->t_status.get(), g->t_user.get(), g->t_item.get(), g->t_value.get(), g->t_defer.get(),
+                     counters);
   const int64_t ct = ((int64_t)L + CT_TILE - 1) / CT_TILE;  // t_flag: records per tile, then their exclusive scan
-  hipLaunchKernelGGL(line_summary_kernel, dim3((unsigned)ct), dim3(256), 0, g->stream, g->t_status, (int64_t)L, g->t_flag, g->t_counters);
+  hipLaunchKernelGGL(line_summary_kernel, dim3((unsigned)ct), dim3(256), 0, g->stream, g->t_status.get(), (int64_t)L, g->t_flag.get(), counters);
   unsigned n_records = 0;
-  if (int rc = scan_u32(g, s, g->t_flag, g->t_flag, ct, nullptr)) return rc;
+  if (int rc = scan_u32(g, s, g->t_flag.get(), g->t_flag.get(), ct, nullptr)) return rc;
   ICHK(g, hipMemcpyAsync(&n_records, s.total, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
   ICHK(g, hipGetLastError());
   TextCounters c;
-  ICHK(g, hipMemcpyAsync(&c, g->t_counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
+  ICHK(g, hipMemcpyAsync(&c, counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
   if (int rc = seg_end()) return rc;
   c.records = n_records;
   // 4. the sequential part of the contract
   if (c.fatal || g->bad_lines + (int64_t)c.bad > 100) {
     std::vector<uint8_t> st(L);
-    ICHK(g, hipMemcpy(st.data(), g->t_status, L, hipMemcpyDeviceToHost));
+    ICHK(g, hipMemcpy(st.data(), g->t_status.get(), L, hipMemcpyDeviceToHost));
     int64_t bad = g->bad_lines;
     for (size_t i = 0; i < L; ++i) {
       if (bad > 100) return text_fail(g, MALS_IO_ERROR, "Too many bad lines; aborting");
@@ -181,18 +153,18 @@ int process_text_region(mals_ingest g, size_t region) {
     if (g->n + (int64_t)c.records >= MALS_INGEST_MAX_RECORDS) return text_fail(g, MALS_INVALID_ARG, "at most 2^36 records per ingest");
     if (int rc = ensure_record_capacity(g, c.records)) return rc;
     ICHK(g, hipEventRecord(e0, g->stream));
-    hipLaunchKernelGGL(compact_records_kernel, dim3((unsigned)ct), dim3(256), 0, g->stream, g->t_status, g->t_flag, (int64_t)L, g->t_user,
-                       g->t_item, g->t_value, g->d_user + g->n, g->d_item + g->n, g->d_value + g->n);
+    hipLaunchKernelGGL(compact_records_kernel, dim3((unsigned)ct), dim3(256), 0, g->stream, g->t_status.get(), g->t_flag.get(), (int64_t)L, g->t_user.get(),
+                       g->t_item.get(), g->t_value.get(), g->d_user.get() + g->n, g->d_item.get() + g->n, g->d_value.get() + g->n);
     ICHK(g, hipGetLastError());
     if (int rc = seg_end()) return rc;
     g->n += c.records;
   }
   if (c.user_tags || c.item_tags) {
-    if (int rc = grow(g, g->d_tags[0], g->tag_cap[0], g->n_tags_raw[0] + c.user_tags, true, g->n_tags_raw[0])) return rc;
-    if (int rc = grow(g, g->d_tags[1], g->tag_cap[1], g->n_tags_raw[1] + c.item_tags, true, g->n_tags_raw[1])) return rc;
-    unsigned* cursors = reinterpret_cast<unsigned*>(g->t_counters + 1);
-    hipLaunchKernelGGL(collect_tags_kernel, dim3(blocks_for((int64_t)L)), dim3(256), 0, g->stream, g->t_status, (int64_t)L, g->t_user, g->t_item,
-                       g->d_tags[0] + g->n_tags_raw[0], g->d_tags[1] + g->n_tags_raw[1], cursors);
+    if (int rc = reserve_text(g, g->d_tags[0], g->n_tags_raw[0] + c.user_tags, g->n_tags_raw[0])) return rc;
+    if (int rc = reserve_text(g, g->d_tags[1], g->n_tags_raw[1] + c.item_tags, g->n_tags_raw[1])) return rc;
+    unsigned* cursors = reinterpret_cast<unsigned*>(counters + 1);
+    hipLaunchKernelGGL(collect_tags_kernel, dim3(blocks_for((int64_t)L)), dim3(256), 0, g->stream, g->t_status.get(), (int64_t)L, g->t_user.get(), g->t_item.get(),
+                       g->d_tags[0].get() + g->n_tags_raw[0], g->d_tags[1].get() + g->n_tags_raw[1], cursors);
     ICHK(g, hipGetLastError());
     g->n_tags_raw[0] += c.user_tags;
     g->n_tags_raw[1] += c.item_tags;
@@ -219,23 +191,17 @@ int append_text_impl(mals_ingest g, const uint8_t* bytes, int64_t n_bytes, int m
     const size_t m = (size_t)std::min<int64_t>(n_bytes - off, (int64_t)block);
     const bool last = eof && off + (int64_t)m == n_bytes;
     const size_t total = g->carry_len + m;
-    if (total + TEXT_PAD > g->text_cap) {
-      dfree(g->d_text);
-      g->text_cap = 0;
-      const size_t cap = ((std::max(total, block) + TEXT_PAD + 4095) / 4096) * 4096;
-      ICHK(g, hipMalloc(&g->d_text, cap));
-      g->text_cap = cap;
-    }
+    if (total + TEXT_PAD > g->d_text.capacity()) ICHK(g, g->d_text.alloc(((std::max(total, block) + TEXT_PAD + 4095) / 4096) * 4096));
     if (!g->t_ev[0]) {
       ICHK(g, hipEventCreate(&g->t_ev[0]));
       ICHK(g, hipEventCreate(&g->t_ev[1]));
     }
     ICHK(g, hipEventRecord(g->t_ev[0], g->stream));
-    if (g->carry_len) ICHK(g, hipMemcpyAsync(g->d_text, g->d_carry, g->carry_len, hipMemcpyDeviceToDevice, g->stream));
+    if (g->carry_len) ICHK(g, hipMemcpyAsync(g->d_text.get(), g->d_carry.get(), g->carry_len, hipMemcpyDeviceToDevice, g->stream));
     if (m)
-      ICHK(g, hipMemcpyAsync(g->d_text + g->carry_len, bytes + off, m, mem_kind == MALS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+      ICHK(g, hipMemcpyAsync(g->d_text.get() + g->carry_len, bytes + off, m, mem_kind == MALS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                              g->stream));
-    ICHK(g, hipMemsetAsync(g->d_text + total, 0, TEXT_PAD, g->stream));
+    ICHK(g, hipMemsetAsync(g->d_text.get() + total, 0, TEXT_PAD, g->stream));
     ICHK(g, hipEventRecord(g->t_ev[1], g->stream));
     // where the complete lines end
     size_t region;
@@ -275,13 +241,8 @@ int append_text_impl(mals_ingest g, const uint8_t* bytes, int64_t n_bytes, int m
     // the tail waits for the next block
     const size_t rest = total - region;
     if (rest) {
-      if (rest > g->carry_cap) {
-        dfree(g->d_carry);
-        g->carry_cap = 0;
-        ICHK(g, hipMalloc(&g->d_carry, rest + rest / 2 + 4096));
-        g->carry_cap = rest + rest / 2 + 4096;
-      }
-      ICHK(g, hipMemcpyAsync(g->d_carry, g->d_text + region, rest, hipMemcpyDeviceToDevice, g->stream));
+      if (rest > g->d_carry.capacity()) ICHK(g, g->d_carry.alloc(rest + rest / 2 + 4096));
+      ICHK(g, hipMemcpyAsync(g->d_carry.get(), g->d_text.get() + region, rest, hipMemcpyDeviceToDevice, g->stream));
       ICHK(g, hipStreamSynchronize(g->stream));
     } else {
       ICHK(g, hipStreamSynchronize(g->stream));
@@ -362,14 +323,8 @@ int mals_ingest_read_file(mals_ingest g, const char* path) {
     return append_text_impl(g, nullptr, 0, MALS_MEM_HOST, true);
   }
   const size_t buf_bytes = std::min<size_t>(g->text_block_bytes, (size_t)64 << 20);
-  if (buf_bytes > g->pinned_cap) {
-    if (g->h_pinned) (void)hipHostFree(g->h_pinned);
-    g->h_pinned = nullptr;
-    g->pinned_cap = 0;
-    ICHK(g, hipHostMalloc(&g->h_pinned, buf_bytes, hipHostMallocDefault));
-    g->pinned_cap = buf_bytes;
-  }
-  uint8_t* buf = static_cast<uint8_t*>(g->h_pinned);
+  if (buf_bytes > g->h_pinned.capacity()) ICHK(g, g->h_pinned.alloc(buf_bytes));
+  uint8_t* buf = g->h_pinned.get();
   if (ends_with(p, ".gz")) {
     gzFile f = gzopen(path, "rb");
     if (!f) return text_fail(g, MALS_IO_ERROR, std::string("cannot open ") + path);
@@ -458,7 +413,7 @@ int mals_ingest_text_info(mals_ingest g, mals_ingest_text_info_t* out) {
   out->stage_ms = g->stage_ms;
   out->n_item_tag_ids = g->finished ? g->n_tag_ids[0] : -1;
   out->n_user_tag_ids = g->finished ? g->n_tag_ids[1] : -1;
-  out->n_known_items = (g->finished && g->known_ptr) ? g->n_known : -1;
+  out->n_known_items = (g->finished && g->known_ptr.get()) ? g->n_known : -1;
   return MALS_OK;
 }
 
@@ -469,25 +424,25 @@ int mals_ingest_get_tag_ids(mals_ingest g, int32_t which, int64_t* host_ids_out)
   if (g->n_tag_ids[which] && !host_ids_out) return MALS_INVALID_ARG;
   ICHK(g, hipSetDevice(g->device));
   if (g->n_tag_ids[which])
-    ICHK(g, hipMemcpy(host_ids_out, g->tag_ids[which], sizeof(int64_t) * (size_t)g->n_tag_ids[which], hipMemcpyDeviceToHost));
+    ICHK(g, hipMemcpy(host_ids_out, g->tag_ids[which].get(), sizeof(int64_t) * (size_t)g->n_tag_ids[which], hipMemcpyDeviceToHost));
   return MALS_OK;
 }
 
 int mals_ingest_get_known_items(mals_ingest g, int64_t* host_ptr, int32_t* host_item_idx) {
   if (!g) return MALS_INVALID_ARG;
-  if (!g->finished || !g->known_ptr) return fail(g, MALS_INVALID_ARG, "no known items: set MALS_INGEST_OPT_KNOWN_ITEMS before mals_ingest_finish");
+  if (!g->finished || !g->known_ptr.get()) return fail(g, MALS_INVALID_ARG, "no known items: set MALS_INGEST_OPT_KNOWN_ITEMS before mals_ingest_finish");
   ICHK(g, hipSetDevice(g->device));
-  if (host_ptr) ICHK(g, hipMemcpy(host_ptr, g->known_ptr, sizeof(int64_t) * (size_t)(g->n_users + 1), hipMemcpyDeviceToHost));
+  if (host_ptr) ICHK(g, hipMemcpy(host_ptr, g->known_ptr.get(), sizeof(int64_t) * (size_t)(g->n_users + 1), hipMemcpyDeviceToHost));
   if (host_item_idx && g->n_known)
-    ICHK(g, hipMemcpy(host_item_idx, g->known_idx, sizeof(int32_t) * (size_t)g->n_known, hipMemcpyDeviceToHost));
+    ICHK(g, hipMemcpy(host_item_idx, g->known_idx.get(), sizeof(int32_t) * (size_t)g->n_known, hipMemcpyDeviceToHost));
   return MALS_OK;
 }
 
 int mals_ingest_device_known_items(mals_ingest g, const int64_t** ptr, const int32_t** item_idx, int64_t* n_known) {
   if (!g) return MALS_INVALID_ARG;
-  if (!g->finished || !g->known_ptr) return fail(g, MALS_INVALID_ARG, "no known items: set MALS_INGEST_OPT_KNOWN_ITEMS before mals_ingest_finish");
-  if (ptr) *ptr = g->known_ptr;
-  if (item_idx) *item_idx = g->known_idx;
+  if (!g->finished || !g->known_ptr.get()) return fail(g, MALS_INVALID_ARG, "no known items: set MALS_INGEST_OPT_KNOWN_ITEMS before mals_ingest_finish");
+  if (ptr) *ptr = g->known_ptr.get();
+  if (item_idx) *item_idx = g->known_idx.get();
   if (n_known) *n_known = g->n_known;
   return MALS_OK;
 }

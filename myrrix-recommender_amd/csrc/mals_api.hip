@@ -11,6 +11,7 @@
 #include "host_solver.h"
 #include "topn_kernels.h"
 #include "mals_internal.h"
+#include "hip_buffer.h"
 
 #include <hip/hip_runtime.h>
 
@@ -41,29 +42,30 @@ namespace {
 struct SideState {
   // factor replica
   int64_t n_total = 0;
-  float* F = nullptr;
-  bool F_owned = false;
+  float* F = nullptr;           // F_own, or the caller's block (mals_bind_factors)
+  DeviceBuffer<float> F_own;
   // local matrix shard
   int64_t row_offset = 0, n_local = 0, nnz = 0;
-  int64_t* row_ptr = nullptr;
+  int64_t* row_ptr = nullptr;   // the *_own blocks, or the caller's (mals_set_matrix from device memory)
   int32_t* col = nullptr;
   float* val = nullptr;
-  bool m_owned = false;
+  DeviceBuffer<int64_t> row_ptr_own;
+  DeviceBuffer<int32_t> col_own;
+  DeviceBuffer<float> val_own;
   bool has_matrix = false;
   std::vector<int64_t> h_row_ptr;  // host copy (work-list construction, chunked upload)
   int64_t append_rows = 0, append_nnz = 0;
   bool appending = false;
   // work lists
-  WorkItem* itemsA = nullptr;  // rows no longer than segment_nnz, longest first
+  DeviceBuffer<WorkItem> itemsA;  // rows no longer than segment_nnz, longest first
   int64_t nA = 0;
   int64_t nnzA = 0, nnzB = 0;  // entries handled by the rows kernel / the segments kernel
-  WorkItem* itemsB = nullptr;  // segments of the long rows, longest first
+  DeviceBuffer<WorkItem> itemsB;  // segments of the long rows, longest first
   int64_t nB = 0;
-  RowC* rowsC = nullptr;
+  DeviceBuffer<RowC> rowsC;
   int64_t nC = 0;
-  float* scratch = nullptr;
-  uint8_t* refine = nullptr;   // per local row: marked for als_refine_kernel by the kernel that solved it
-  size_t refine_cap = 0;
+  DeviceBuffer<float> scratch;
+  DeviceBuffer<uint8_t> refine;   // per local row: marked for als_refine_kernel by the kernel that solved it
   int32_t col_min = 0, col_max = -1;  // range of the column indices (checked against the opposite replica)
   float max_abs_val = 0.f;  // bound on |value| used for the operand scale (>= local_max_abs_val)
   float local_max_abs_val = 0.f;  // largest |value| of the shard
@@ -86,13 +88,12 @@ struct SideState {
   int64_t chunk_rows_override = -1;  // mals_set_chunk_rows: per-side value of cfg.chunk_rows (-1 = use cfg)
   std::vector<ChunkRange> chunks;
   // Gramian of THIS side's factors (consumed when solving the other side)
-  double* G = nullptr;
-  float* Gf = nullptr;
-  double* partials = nullptr;   // wave / slab partials of K1 (doubles, or floats for the split kernel)
-  size_t partial_bytes = 0;
+  DeviceBuffer<double> G;
+  DeviceBuffer<float> Gf;
+  DeviceBuffer<uint8_t> partials;   // wave / slab partials of K1 (doubles, or floats for the split kernel)
   bool G_valid = false;
   uint64_t G_version = 0;  // bumped whenever G changes (cached operand scale of the split-precision gather)
-  unsigned* d_ymax = nullptr;  // bit pattern of max |element| over the rows G was formed from, recorded by the Gramian kernels
+  DeviceBuffer<unsigned> d_ymax;  // bit pattern of max |element| over the rows G was formed from, recorded by the Gramian kernels
   uint64_t ymax_version = 0;   // the G_version d_ymax belongs to (0 = none: G came from outside, gather_scale_kernel then
                                // bounds |y| by sqrt(max_f G_ff))
   uint64_t F_epoch = 0;    // bumped whenever the library itself writes the replica (uploads, solves, rebinding)
@@ -113,25 +114,23 @@ struct mals_handle_s {
   bool split3 = false;     // MALS_GRAMIAN_SPLIT3_F16: three f16 terms per operand (features 49..64)
   int dual_blocks = 0;     // cfg.solve_mode resolved: rows up to 16*dual_blocks entries go to the dual lists (0 = none)
   // dual path state (dual_kernels.h): rotated copy of the gathered factor matrix, Q / Q^T / eigenvalues
-  float* d_Mr = nullptr;
-  size_t Mr_cap = 0;          // floats
+  DeviceBuffer<float> d_Mr;
   // gather table of the direct kernels when features % 16 != 0: zero-padded copy of the gathered factor matrix
   // (pad_rows_kernel), rebuilt once per half-iteration
-  float* d_Mp = nullptr;
-  size_t Mp_cap = 0;          // floats
+  DeviceBuffer<float> d_Mp;
   // mixed-precision refinement of ill-conditioned rows (als_refine_kernel): estimate above which a row is re-solved
   // (MALS_REFINE_LIMIT / mals_set_refine_limit; 0 = off), rows refined so far (device counter)
   float refine_limit = 64.f;
   bool exact_ready = false;   // als_exact_kernel's dynamic LDS limit raised
-  int* d_gref_state = nullptr;   // {a row was marked in this half-iteration, Gref is valid, arrival ticket}
-  double* d_Gref = nullptr;      // the reference-rounded Gramian of the gathered side (gramian_ref_kernel), on demand
-  double* d_gref_part = nullptr;
-  unsigned long long* d_refined = nullptr;
+  DeviceBuffer<int> d_gref_state;   // {a row was marked in this half-iteration, Gref is valid, arrival ticket}
+  DeviceBuffer<double> d_Gref;      // the reference-rounded Gramian of the gathered side (gramian_ref_kernel), on demand
+  DeviceBuffer<double> d_gref_part;
+  DeviceBuffer<unsigned long long> d_refined;
   int pad_side = -1;          // solved side whose opposite matrix the copy holds, version of that side's G and
   uint64_t pad_version = 0;   // factor-upload count at the time of the copy
   uint64_t pad_epoch = 0;
   std::vector<uint8_t> pad_done;  // chunks solved from the current copy: solving one again starts a new half-iteration
-  char* d_eig = nullptr;      // device image of eig_stage; the four pointers below are views into it
+  DeviceBuffer<char> d_eig;   // device image of eig_stage; the four pointers below are views into it
   double* d_Q = nullptr;      // [2][16T][16T]: Q (k x 16T, zero padded) and Q^T
   float* d_Qf = nullptr;      // the same in fp32
   bool rotate_f64 = false;    // this half-iteration's forward rotation runs on the fp64 matrix cores
@@ -139,14 +138,13 @@ struct mals_handle_s {
   int32_t* d_Bs = nullptr;    // [2][KC][T][2][64][4]: Q and Q^T as split-f16 B operands
   size_t Bs_stride = 0;
   float* d_lam = nullptr;     // [2][16T]: eigenvalues, 1/sqrt(L + lambda alpha)
-  unsigned* d_zbound = nullptr;
-  double* h_G = nullptr;      // pinned k x k
+  DeviceBuffer<unsigned> d_zbound;
+  PinnedBuffer<double> h_G;   // k x k
   hipEvent_t ev_G = nullptr;
   // host half of the dual preparation: the eigendecomposition of G turned into what the device half uploads, in ONE
   // pinned block (asynchronous copies straight out of it, no stream synchronisation): Q | Q^T (doubles), the same in
   // fp32, eigenvalues | 1/sqrt(L + lambda alpha), and Q / Q^T as split-f16 B operands
-  char* eig_stage = nullptr;
-  size_t eig_stage_bytes = 0;
+  PinnedBuffer<char> eig_stage;
   bool eig_ok = false;        // the staged decomposition qualifies for the dual path
   double eig_gmax = 0.0;      // max_f G_ff of the decomposed Gramian
   bool dual_pending = false;  // a chunk's direct kernels are enqueued, its dual part waits for the eigendecomposition
@@ -167,16 +165,16 @@ struct mals_handle_s {
   mals_iteration_fn iter_fn = nullptr;   // mals_set_iteration_callback
   void* iter_user = nullptr;
   bool lds_gather = false;
-  float* d_Gperm = nullptr;
+  DeviceBuffer<float> d_Gperm;
   int gperm_side = -1;
   uint64_t gperm_version = 0;
-  float* d_zscale = nullptr;  // {S, 1/S^2} of the split-precision gather (gather_scale_kernel)
+  DeviceBuffer<float> d_zscale;  // {S, 1/S^2} of the split-precision gather (gather_scale_kernel)
   int zs_side = -1;           // what d_zscale currently holds: solved side, version of the opposite G, value bound
   uint64_t zs_version = 0;
   float zs_bound = -1.f;
   double zs_mean = -1.0;
-  unsigned* d_maxabs = nullptr;
-  int* d_colrange = nullptr;
+  DeviceBuffer<unsigned> d_maxabs;
+  DeviceBuffer<int> d_colrange;
   int n_cu = 256;
   SideState side[2];
   hipStream_t stream = nullptr;
@@ -192,8 +190,8 @@ struct mals_handle_s {
   bool overlap = false;
   bool forked[2] = {false, false};
   std::string err;
-  unsigned long long* d_bad = nullptr;   // [4]: first non-PD row per side, then the smallest-pivot suspect per side
-  unsigned long long* h_bad = nullptr;   // pinned
+  DeviceBuffer<unsigned long long> d_bad;   // [4]: first non-PD row per side, then the smallest-pivot suspect per side
+  PinnedBuffer<unsigned long long> h_bad;
   int32_t sing_side = -1;
   int64_t sing_row = -1;
   int32_t sing_rank = 0;
@@ -201,24 +199,22 @@ struct mals_handle_s {
   bool timing = false;
   mals_stats stats;
   std::vector<PendingEvent> pending;
-  unsigned long long* d_trace = nullptr;  // MALS_DEBUG_TRACE
+  DeviceBuffer<unsigned long long> d_trace;  // MALS_DEBUG_TRACE
   void* tn_ws = nullptr;  // top-N workspace (topn_host.h), grow-only
   void* tn_front = nullptr;  // the serving front of mals_recommend*: queue, leader, passes in flight (topn_host.h)
   // userTagIDs as one bit per item (mals_set_tag_items): never recommended (RecommendIterator.java:72)
-  uint32_t* tag_bits = nullptr;
+  DeviceBuffer<uint32_t> tag_bits;
   int64_t tag_bits_items = 0, n_tag_items = 0;
   // knownItemIDs (mals_set_known_items): what mals_recommend skips instead of the rows of R when present
-  const int64_t* known_ptr = nullptr;
+  const int64_t* known_ptr = nullptr;   // the *_copy blocks, or the caller's (device memory)
   const int32_t* known_idx = nullptr;
   int64_t known_rows = 0;
-  int64_t* known_ptr_own = nullptr;   // copies of host arrays
-  int32_t* known_idx_own = nullptr;
-  double* d_sd = nullptr;       // mals_sample_dots: estimates, indices
-  int64_t* d_sd_idx = nullptr;
-  size_t sd_cap = 0, sd_idx_cap = 0;
-  int64_t* d_idx = nullptr;  // gather scratch
-  float* d_rows = nullptr;
-  int32_t idx_cap = 0;
+  DeviceBuffer<int64_t> known_ptr_copy;   // copies of host arrays
+  DeviceBuffer<int32_t> known_idx_copy;
+  DeviceBuffer<double> d_sd;       // mals_sample_dots: estimates, indices
+  DeviceBuffer<int64_t> d_sd_idx;
+  DeviceBuffer<int64_t> d_idx;  // gather scratch
+  DeviceBuffer<float> d_rows;
 };
 
 namespace {
@@ -249,42 +245,43 @@ int use_device(mals_handle h) {
   return MALS_OK;
 }
 
-template <typename P>
-void free_dev(P*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 void clear_known_items(mals_handle h) {
-  free_dev(h->known_ptr_own);
-  free_dev(h->known_idx_own);
+  h->known_ptr_copy.reset();
+  h->known_idx_copy.reset();
   h->known_ptr = nullptr;
   h->known_idx = nullptr;
   h->known_rows = 0;
 }
 
 void free_matrix(SideState& s) {
-  if (s.m_owned) {
-    free_dev(s.row_ptr);
-    free_dev(s.col);
-    free_dev(s.val);
-  }
+  s.row_ptr_own.reset();
+  s.col_own.reset();
+  s.val_own.reset();
   s.row_ptr = nullptr;
   s.col = nullptr;
   s.val = nullptr;
-  s.m_owned = false;
   s.has_matrix = false;
-  free_dev(s.itemsA);
-  free_dev(s.itemsB);
-  free_dev(s.rowsC);
-  free_dev(s.scratch);
-  free_dev(s.refine);
-  s.refine_cap = 0;
+  s.itemsA.reset();
+  s.itemsB.reset();
+  s.rowsC.reset();
+  s.scratch.reset();
+  s.refine.reset();
   s.nA = s.nB = s.nC = 0;
   s.nnzA = s.nnzB = 0;
   s.chunks.clear();
   s.h_row_ptr.clear();
   s.h_row_ptr.shrink_to_fit();
+}
+
+// the shard's own device copy: s.n_local rows, s.nnz entries
+int alloc_matrix(mals_handle h, SideState& s) {
+  HIPCHK(h, s.row_ptr_own.alloc((size_t)(s.n_local + 1)));
+  HIPCHK(h, s.col_own.alloc((size_t)std::max<int64_t>(s.nnz, 1)));
+  HIPCHK(h, s.val_own.alloc((size_t)std::max<int64_t>(s.nnz, 1)));
+  s.row_ptr = s.row_ptr_own.get();
+  s.col = s.col_own.get();
+  s.val = s.val_own.get();
+  return MALS_OK;
 }
 
 int64_t slot_floats(int T) { return (int64_t)(tri(T) * 4 + T) * 64; }
@@ -296,13 +293,13 @@ int build_work_lists(mals_handle h, SideState& s) {
   s.local_mean_abs_val = 0.0;
   s.n_dual_rows = 0;
   if (s.nnz > 0) {  // one pass over the values: bounds the Gramian weights (gather_scale_kernel)
-    HIPCHK(h, hipMemsetAsync(h->d_maxabs, 0, 4 * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_maxabs.get(), 0, 4 * sizeof(unsigned), h->stream));
     const unsigned blocks = (unsigned)std::min<int64_t>(4096, (s.nnz + 255) / 256);
-    hipLaunchKernelGGL(max_abs_kernel, dim3(blocks), dim3(256), 0, h->stream, s.val, s.nnz, h->d_maxabs,
-                       reinterpret_cast<double*>(h->d_maxabs + 2));
+    hipLaunchKernelGGL(max_abs_kernel, dim3(blocks), dim3(256), 0, h->stream, s.val, s.nnz, h->d_maxabs.get(),
+                       reinterpret_cast<double*>(h->d_maxabs.get() + 2));
     HIPCHK(h, hipGetLastError());
     unsigned raw[4];
-    HIPCHK(h, hipMemcpyAsync(raw, h->d_maxabs, sizeof(raw), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(raw, h->d_maxabs.get(), sizeof(raw), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::memcpy(&s.max_abs_val, &raw[0], sizeof(float));
     double sum = 0.0;
@@ -316,12 +313,12 @@ int build_work_lists(mals_handle h, SideState& s) {
   if (s.nnz > 0) {  // the same pass over the column indices: an index outside the opposite replica would be an
                     // out-of-bounds device access in the gather (and a write in the top-N mask)
     const int init[2] = {std::numeric_limits<int>::max(), std::numeric_limits<int>::min()};
-    HIPCHK(h, hipMemcpyAsync(h->d_colrange, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_colrange.get(), init, sizeof(init), hipMemcpyHostToDevice, h->stream));
     const unsigned blocks = (unsigned)std::min<int64_t>(4096, (s.nnz + 255) / 256);
-    hipLaunchKernelGGL(col_range_kernel, dim3(blocks), dim3(256), 0, h->stream, s.col, s.nnz, h->d_colrange);
+    hipLaunchKernelGGL(col_range_kernel, dim3(blocks), dim3(256), 0, h->stream, s.col, s.nnz, h->d_colrange.get());
     HIPCHK(h, hipGetLastError());
     int range[2];
-    HIPCHK(h, hipMemcpyAsync(range, h->d_colrange, sizeof(range), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(range, h->d_colrange.get(), sizeof(range), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     s.col_min = range[0];
     s.col_max = range[1];
@@ -478,15 +475,15 @@ int build_work_lists(mals_handle h, SideState& s) {
                  (long long)ed[2], (long long)nd[3], (long long)ed[3], (long long)nz, (long long)s.nB, (long long)n_long, (long long)s.nnzB);
   }
   if (s.nA) {
-    HIPCHK(h, hipMalloc(&s.itemsA, sizeof(WorkItem) * order.size()));
-    HIPCHK(h, hipMemcpy(s.itemsA, order.data(), sizeof(WorkItem) * order.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, s.itemsA.alloc(order.size()));
+    HIPCHK(h, hipMemcpy(s.itemsA.get(), order.data(), sizeof(WorkItem) * order.size(), hipMemcpyHostToDevice));
   }
   if (s.nB) {
-    HIPCHK(h, hipMalloc(&s.itemsB, sizeof(WorkItem) * segs.size()));
-    HIPCHK(h, hipMemcpy(s.itemsB, segs.data(), sizeof(WorkItem) * segs.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMalloc(&s.rowsC, sizeof(RowC) * rowsC.size()));
-    HIPCHK(h, hipMemcpy(s.rowsC, rowsC.data(), sizeof(RowC) * rowsC.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMalloc(&s.scratch, sizeof(float) * (size_t)(slot * slot_floats(h->T))));
+    HIPCHK(h, s.itemsB.alloc(segs.size()));
+    HIPCHK(h, hipMemcpy(s.itemsB.get(), segs.data(), sizeof(WorkItem) * segs.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, s.rowsC.alloc(rowsC.size()));
+    HIPCHK(h, hipMemcpy(s.rowsC.get(), rowsC.data(), sizeof(RowC) * rowsC.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, s.scratch.alloc((size_t)(slot * slot_floats(h->T))));
   }
   return MALS_OK;
 }
@@ -575,16 +572,9 @@ int launch_gramian_T(mals_handle h, SideState& s, const float* M, int64_t n_rows
     constexpr int GROUPS = 64;              // first-stage sums (doubles) behind the slab partials (floats)
     const size_t slab_bytes = sizeof(float) * (size_t)n_slabs * tri(T) * 256;
     const size_t bytes = slab_bytes + sizeof(double) * (size_t)GROUPS * tri(T) * 256;
-    if (s.partial_bytes < bytes) {
-      free_dev(s.partials);
-      s.partial_bytes = 0;
-      void* pbuf = nullptr;
-      HIPCHK(h, hipMalloc(&pbuf, bytes));
-      s.partials = static_cast<double*>(pbuf);
-      s.partial_bytes = bytes;
-    }
-    float* pf = reinterpret_cast<float*>(s.partials);
-    double* pd = reinterpret_cast<double*>(reinterpret_cast<char*>(s.partials) + slab_bytes);  // slab_bytes is a multiple of 1024
+    if (s.partials.capacity() < bytes) HIPCHK(h, s.partials.alloc(bytes));
+    float* pf = reinterpret_cast<float*>(s.partials.get());
+    double* pd = reinterpret_cast<double*>(s.partials.get() + slab_bytes);  // slab_bytes is a multiple of 1024
     hipLaunchKernelGGL((gramian_split_kernel<T>), dim3((unsigned)(n_slabs / 4)), dim3(256), 0, h->stream, M, n_rows, k,
                        slab_rows, pf, ymax);
     hipLaunchKernelGGL(gramian_reduce_slabs_kernel, dim3((unsigned)((elems + 255) / 256), GROUPS), dim3(256), 0, h->stream, pf, n_slabs,
@@ -600,18 +590,14 @@ int launch_gramian_T(mals_handle h, SideState& s, const float* M, int64_t n_rows
   int64_t rows_per_wave = (n_rows + n_waves - 1) / n_waves;
   rows_per_wave = std::max<int64_t>(4, (rows_per_wave + 3) & ~(int64_t)3);
   const size_t bytes = sizeof(double) * (size_t)n_waves * tri(T) * 256;
-  if (s.partial_bytes < bytes) {
-    free_dev(s.partials);
-    s.partial_bytes = 0;
-    HIPCHK(h, hipMalloc(&s.partials, bytes));
-    s.partial_bytes = bytes;
-  }
+  if (s.partials.capacity() < bytes) HIPCHK(h, s.partials.alloc(bytes));
+  double* partials = reinterpret_cast<double*>(s.partials.get());
   // the fp64 kernel (small matrices: the diagonal's bound is at most 9 binades loose there) records no maximum; tracking
   // it cost the latency-bound kernel 20-40 % (measured on C2).  "Unknown" = a word above 3e38 that survives every max.
   if (ymax) HIPCHK(h, hipMemsetAsync(ymax, 0x7f, sizeof(unsigned), h->stream));
   hipLaunchKernelGGL((gramian_partial_kernel<T>), dim3((unsigned)(n_waves / 4)), dim3(256), 0, h->stream, M, n_rows, k,
-                     rows_per_wave, s.partials);
-  hipLaunchKernelGGL((gramian_finalize_kernel<T, true, 16>), dim3(elems / 16), dim3(256), 0, h->stream, s.partials, n_waves,
+                     rows_per_wave, partials);
+  hipLaunchKernelGGL((gramian_finalize_kernel<T, true, 16>), dim3(elems / 16), dim3(256), 0, h->stream, partials, n_waves,
                      k, G_out, Gf_out);
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
@@ -683,34 +669,34 @@ int launch_lists(mals_handle h, SideState& s, SolveParams p, int chunk, int whic
   const bool own = which & LISTS_ROWS, longs = which & LISTS_LONG, dual_rows_too = which & LISTS_DUAL_ROWS;
   if (longs && cr.nB) {
     p.n_work = cr.nB;
-    p.items = s.itemsB + cr.offB;
+    p.items = s.itemsB.get() + cr.offB;
     if (int rc = launch_persistent(h, segments_kernel, segments_fallback, p, 1, (double)cr.nnzB * per)) return rc;
   }
   if (own && cr.nA) {
     p.n_work = cr.nA;
-    p.items = s.itemsA + cr.offA;
+    p.items = s.itemsA.get() + cr.offA;
     if (int rc = launch_persistent(h, rows_kernel, rows_fallback, p, 0, (double)cr.nnzA * per + (double)cr.nA * per)) return rc;
   }
   if (dual_rows_too && cr.n_dual()) {  // the dual lists through the direct kernel (the half-iteration does not qualify)
     p.n_work = cr.n_dual();
-    p.items = s.itemsA + cr.offA + cr.nA;
+    p.items = s.itemsA.get() + cr.offA + cr.nA;
     if (int rc = launch_persistent(h, rows_kernel, rows_fallback, p, 0, (double)cr.nnz_dual() * per + (double)cr.n_dual() * per)) return rc;
   }
   if (longs && cr.nC) {
     if (int rc = begin_timed(h, 2, (double)cr.nC * per, pe)) return rc;
     if (cr.nP) {
       p.n_work = cr.nP;
-      p.rowsC = s.rowsC + cr.offP;
+      p.rowsC = s.rowsC.get() + cr.offP;
       hipLaunchKernelGGL(prereduce_kernel, dim3((unsigned)((cr.nP + 3) / 4)), dim3(256), 0, h->stream, p);
     }
     p.n_work = cr.nC;
-    p.rowsC = s.rowsC + cr.offC;
+    p.rowsC = s.rowsC.get() + cr.offC;
     hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((cr.nC + 3) / 4)), dim3(256), 0, h->stream, p);
     if (int rc = end_timed(h, pe)) return rc;
   }
   if (own && cr.nZ) {
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((cr.nZ + 31) / 32)), dim3(256), 0, h->stream,  // 8 rows per wave
-                       s.itemsA + cr.offA + cr.nA + cr.n_dual(), cr.nZ, p.k, p.out);
+                       s.itemsA.get() + cr.offA + cr.nA + cr.n_dual(), cr.nZ, p.k, p.out);
   }
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
@@ -745,17 +731,17 @@ int launch_lists_lds(mals_handle h, SideState& s, SolveParams p, int chunk, int 
   const bool own = which & LISTS_ROWS, longs = which & LISTS_LONG, dual_rows_too = which & LISTS_DUAL_ROWS;
   if (longs && cr.nB) {
     p.n_work = cr.nB;
-    p.items = s.itemsB + cr.offB;
+    p.items = s.itemsB.get() + cr.offB;
     if (int rc = launch_persistent_lds(h, als_lds_kernel_h<1>, als_persistent_kernel<T, D, 1, true>, p, 1, (double)cr.nnzB * per)) return rc;
   }
   if (own && cr.nA) {
     p.n_work = cr.nA;
-    p.items = s.itemsA + cr.offA;
+    p.items = s.itemsA.get() + cr.offA;
     if (int rc = launch_persistent_lds(h, als_lds_kernel_h<0>, als_persistent_kernel<T, D, 0, true>, p, 0, (double)cr.nnzA * per + (double)cr.nA * per)) return rc;
   }
   if (dual_rows_too && cr.n_dual()) {
     p.n_work = cr.n_dual();
-    p.items = s.itemsA + cr.offA + cr.nA;
+    p.items = s.itemsA.get() + cr.offA + cr.nA;
     if (int rc = launch_persistent_lds(h, als_lds_kernel_h<0>, als_persistent_kernel<T, D, 0, true>, p, 0,
                                        (double)cr.nnz_dual() * per + (double)cr.n_dual() * per)) return rc;
   }
@@ -763,11 +749,11 @@ int launch_lists_lds(mals_handle h, SideState& s, SolveParams p, int chunk, int 
     if (int rc = begin_timed(h, 2, (double)cr.nC * per, pe)) return rc;
     if (cr.nP) {
       p.n_work = cr.nP;
-      p.rowsC = s.rowsC + cr.offP;
+      p.rowsC = s.rowsC.get() + cr.offP;
       hipLaunchKernelGGL(als_prereduce_kernel<T>, dim3((unsigned)((cr.nP + 3) / 4)), dim3(256), 0, h->stream, p);
     }
     p.n_work = cr.nC;
-    p.rowsC = s.rowsC + cr.offC;
+    p.rowsC = s.rowsC.get() + cr.offC;
     hipLaunchKernelGGL((als_finish_kernel<T, true>), dim3((unsigned)((cr.nC + 3) / 4)), dim3(256), 0, h->stream, p);
     SolveParams pf = p;
     pf.flags |= 8;
@@ -776,7 +762,7 @@ int launch_lists_lds(mals_handle h, SideState& s, SolveParams p, int chunk, int 
   }
   if (own && cr.nZ) {
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((cr.nZ + 31) / 32)), dim3(256), 0, h->stream,
-                       s.itemsA + cr.offA + cr.nA + cr.n_dual(), cr.nZ, p.k, p.out);
+                       s.itemsA.get() + cr.offA + cr.nA + cr.n_dual(), cr.nZ, p.k, p.out);
   }
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
@@ -851,9 +837,9 @@ int launch_refine(mals_handle h, const RefineParams& q) {
 template <int T>
 int launch_gramian_ref_T(mals_handle h, const SideState& o) {
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((o.n_total + 63) / 64, (int64_t)h->n_cu * 2));
-  hipLaunchKernelGGL(gramian_ref_latch_kernel, dim3(1), dim3(1), 0, h->stream, h->d_gref_state);
-  hipLaunchKernelGGL((gramian_ref_kernel<T>), dim3(grid), dim3(256), 0, h->stream, o.F, o.n_total, h->cfg.features, h->d_gref_state,
-                     h->d_gref_part, h->d_Gref);
+  hipLaunchKernelGGL(gramian_ref_latch_kernel, dim3(1), dim3(1), 0, h->stream, h->d_gref_state.get());
+  hipLaunchKernelGGL((gramian_ref_kernel<T>), dim3(grid), dim3(256), 0, h->stream, o.F, o.n_total, h->cfg.features, h->d_gref_state.get(),
+                     h->d_gref_part.get(), h->d_Gref.get());
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
 }
@@ -1028,7 +1014,7 @@ EigStage eig_views(mals_handle h) {
   e.nQ = 2 * KP * KP;
   e.nLam = 2 * KP;
   e.nBs = KC * h->T * 2 * 64 * 4;
-  char* b = h->eig_stage;
+  char* b = h->eig_stage.get();
   e.Q = reinterpret_cast<double*>(b);
   e.Qf = reinterpret_cast<float*>(b + sizeof(double) * e.nQ);
   e.lam = e.Qf + e.nQ;
@@ -1039,8 +1025,7 @@ int ensure_eig_stage(mals_handle h) {
   if (h->eig_stage) return MALS_OK;
   const size_t KP = (size_t)16 * h->T, KC = (size_t)(h->T + 1) / 2;
   const size_t bytes = sizeof(double) * 2 * KP * KP + sizeof(float) * (2 * KP * KP + 2 * KP) + sizeof(int32_t) * 2 * KC * h->T * 2 * 64 * 4;
-  HIPCHK(h, hipHostMalloc(&h->eig_stage, bytes));
-  h->eig_stage_bytes = bytes;
+  HIPCHK(h, h->eig_stage.alloc(bytes));
   return MALS_OK;
 }
 
@@ -1057,8 +1042,8 @@ int prepare_dual_host(mals_handle h, int side, mals_handle from) {
   HIPCHK(h, hipEventSynchronize(h->ev_G));
   h->tl[1] = now_us();
   if (from && from != h) {  // the same G, decomposed by another member of the group
-    if (from->eig_stage_bytes != h->eig_stage_bytes) return fail(h, MALS_INVALID_ARG, "members of a group must share features");
-    std::memcpy(h->eig_stage, from->eig_stage, h->eig_stage_bytes);
+    if (from->eig_stage.capacity() != h->eig_stage.capacity()) return fail(h, MALS_INVALID_ARG, "members of a group must share features");
+    std::memcpy(h->eig_stage.get(), from->eig_stage.get(), h->eig_stage.capacity());
     h->eig_ok = from->eig_ok;
     h->eig_gmax = from->eig_gmax;
     h->rotate_f64 = from->rotate_f64;
@@ -1068,7 +1053,7 @@ int prepare_dual_host(mals_handle h, int side, mals_handle from) {
   }
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<double> evals((size_t)k), V((size_t)k * k);
-  const bool ok = mals::symmetric_eigen(h->h_G, k, evals.data(), V.data());
+  const bool ok = mals::symmetric_eigen(h->h_G.get(), k, evals.data(), V.data());
   h->stats.eigen_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   h->tl[2] = now_us();
   if (!ok) return MALS_OK;
@@ -1108,7 +1093,7 @@ int prepare_dual_host(mals_handle h, int side, mals_handle from) {
     }
   }
   double gmax = 0.0;   // max |y_f| <= sqrt(max_f G_ff)
-  for (int f = 0; f < k; ++f) gmax = std::max(gmax, h->h_G[(size_t)f * k + f]);
+  for (int f = 0; f < k; ++f) gmax = std::max(gmax, h->h_G.get()[(size_t)f * k + f]);
   h->eig_gmax = gmax;
   h->eig_ok = true;
   return MALS_OK;
@@ -1121,36 +1106,30 @@ int prepare_dual_device(mals_handle h, int side) {
   if (!h->eig_ok) return MALS_OK;
   const EigStage e = eig_views(h);
   if (!h->d_eig) {  // one device block with the layout of the pinned one: ONE upload per half-iteration instead of four
-    HIPCHK(h, hipMalloc(&h->d_eig, h->eig_stage_bytes));
-    h->d_Q = reinterpret_cast<double*>(h->d_eig);
-    h->d_Qf = reinterpret_cast<float*>(h->d_eig + (reinterpret_cast<char*>(e.Qf) - h->eig_stage));
-    h->d_lam = reinterpret_cast<float*>(h->d_eig + (reinterpret_cast<char*>(e.lam) - h->eig_stage));
-    h->d_Bs = reinterpret_cast<int32_t*>(h->d_eig + (reinterpret_cast<char*>(e.Bs) - h->eig_stage));
+    HIPCHK(h, h->d_eig.alloc(h->eig_stage.capacity()));
+    char* d = h->d_eig.get();
+    h->d_Q = reinterpret_cast<double*>(d);
+    h->d_Qf = reinterpret_cast<float*>(d + (reinterpret_cast<char*>(e.Qf) - h->eig_stage.get()));
+    h->d_lam = reinterpret_cast<float*>(d + (reinterpret_cast<char*>(e.lam) - h->eig_stage.get()));
+    h->d_Bs = reinterpret_cast<int32_t*>(d + (reinterpret_cast<char*>(e.Bs) - h->eig_stage.get()));
   }
   // {z bound of the dual kernels, x' bound of the un-rotation of the even chunks, of the odd chunks}: a chunk's un-rotation
   // picks its operand scale from the bound its OWN dual kernels left -- with the chunks on two alternating streams a
   // shared slot made the scale (hence the f16 split of small components) depend on how far the other stream had got
-  if (!h->d_zbound) HIPCHK(h, hipMalloc(&h->d_zbound, 3 * sizeof(unsigned)));
-  const size_t need = (size_t)o.n_total * KP;
-  if (h->Mr_cap < need) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    free_dev(h->d_Mr);
-    h->Mr_cap = 0;
-    HIPCHK(h, hipMalloc(&h->d_Mr, sizeof(float) * need));
-    h->Mr_cap = need;
-  }
+  if (!h->d_zbound) HIPCHK(h, h->d_zbound.alloc(3));
+  HIPCHK(h, h->d_Mr.reserve((size_t)o.n_total * KP, h->stream));
   // pinned source, rewritten no earlier than the next half-iteration's prepare_dual_host (which waits for this stream)
-  HIPCHK(h, hipMemcpyAsync(h->d_eig, h->eig_stage, h->eig_stage_bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_eig.get(), h->eig_stage.get(), h->eig_stage.capacity(), hipMemcpyHostToDevice, h->stream));
   h->Bs_stride = e.nBs;
-  HIPCHK(h, hipMemsetAsync(h->d_zbound, 0, 3 * sizeof(unsigned), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->d_zbound.get(), 0, 3 * sizeof(unsigned), h->stream));
   RotateParams rp;
   rp.src = o.F;
-  rp.dst = h->d_Mr;
+  rp.dst = h->d_Mr.get();
   rp.B = h->d_Q;
   rp.Bf = h->d_Qf;
   rp.items = nullptr;
   rp.dmax = h->d_lam + KP;
-  rp.zbound = h->d_zbound;
+  rp.zbound = h->d_zbound.get();
   rp.n_rows = o.n_total;
   rp.k = k;
   rp.src_stride = k;
@@ -1183,21 +1162,21 @@ int launch_dual_chunk(mals_handle h, int side, int chunk) {
   DualParams dp;
   dp.col = s.col;
   dp.val = s.val;
-  dp.Mr = h->d_Mr;
+  dp.Mr = h->d_Mr.get();
   dp.lam = h->d_lam;
-  dp.zbound = h->d_zbound;
+  dp.zbound = h->d_zbound.get();
   dp.out = s.F + s.row_offset * k;
-  dp.bad_row = h->d_bad + side;
+  dp.bad_row = h->d_bad.get() + side;
   dp.k = k;
   dp.alpha = (float)h->cfg.alpha;
   dp.lambda_alpha = (float)(h->cfg.lambda * h->cfg.alpha);
   dp.sqrt_w_max = (float)std::sqrt(std::fabs(h->cfg.alpha) * (double)s.max_abs_val);
-  dp.xbound = h->d_zbound + 1 + (chunk & 1);
+  dp.xbound = h->d_zbound.get() + 1 + (chunk & 1);
   HIPCHK(h, hipMemsetAsync(dp.xbound, 0, sizeof(unsigned), h->stream));  // same stream as the chunk two back, whose un-rotation is done
-  dp.any_marked = h->d_gref_state;
-  dp.refine_flag = h->refine_limit > 0.f ? s.refine : nullptr;
+  dp.any_marked = h->d_gref_state.get();
+  dp.refine_flag = h->refine_limit > 0.f ? s.refine.get() : nullptr;
   dp.refine_limit = h->refine_limit;
-  const WorkItem* base = s.itemsA + cr.offA + cr.nA;
+  const WorkItem* base = s.itemsA.get() + cr.offA + cr.nA;
   int64_t off = 0;
   PendingEvent pe;
   // (Two classes in flight at a time on two streams -- one class's tail under the next one's head -- was built in round 4
@@ -1241,9 +1220,9 @@ int launch_dual_chunk(mals_handle h, int side, int chunk) {
 
 int ensure_gramian_buffers(mals_handle h, SideState& s) {
   const int k = h->cfg.features;
-  if (!s.G) HIPCHK(h, hipMalloc(&s.G, sizeof(double) * (size_t)k * k));
-  if (!s.Gf) HIPCHK(h, hipMalloc(&s.Gf, sizeof(float) * (size_t)tri(h->T) * 256));
-  if (!s.d_ymax) HIPCHK(h, hipMalloc(&s.d_ymax, sizeof(unsigned) * YMAX_SLOTS));
+  if (!s.G) HIPCHK(h, s.G.alloc((size_t)k * k));
+  if (!s.Gf) HIPCHK(h, s.Gf.alloc((size_t)tri(h->T) * 256));
+  if (!s.d_ymax) HIPCHK(h, s.d_ymax.alloc(YMAX_SLOTS));
   return MALS_OK;
 }
 
@@ -1373,18 +1352,21 @@ int mals_create(const mals_config* cfg, mals_handle* out) {
   }
   std::memset(&h->stats, 0, sizeof(h->stats));
   h->stats.struct_size = (int32_t)sizeof(mals_stats);
-  if (hipSetDevice(cfg->device) != hipSuccess || hipMalloc(&h->d_bad, 4 * sizeof(unsigned long long)) != hipSuccess ||
-      hipHostMalloc(&h->h_bad, 4 * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc(&h->d_zscale, 4 * sizeof(float)) != hipSuccess || hipMalloc(&h->d_maxabs, 4 * sizeof(unsigned)) != hipSuccess ||
-      hipMalloc(&h->d_colrange, 2 * sizeof(int)) != hipSuccess ||
-      hipMalloc(&h->d_refined, sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc(&h->d_gref_state, 4 * sizeof(int)) != hipSuccess || hipMemset(h->d_gref_state, 0, 4 * sizeof(int)) != hipSuccess ||
-      hipMemset(h->d_refined, 0, sizeof(unsigned long long)) != hipSuccess ||
-      hipMemset(h->d_zscale, 0, 4 * sizeof(float)) != hipSuccess ||   // (mals_get_gather_scale before any split-precision gather: zeros)
-      hipMemset(h->d_bad, 0xff, 4 * sizeof(unsigned long long)) != hipSuccess) {
-    const hipError_t e = hipGetLastError();
-    delete h;
-    return create_fail(MALS_HIP_ERROR, "mals_create: device " + std::to_string(cfg->device) + ": " + hipGetErrorString(e));
+  hipError_t st = hipSetDevice(cfg->device);
+  if (st == hipSuccess) st = h->d_bad.alloc(4);
+  if (st == hipSuccess) st = h->h_bad.alloc(4);
+  if (st == hipSuccess) st = h->d_zscale.alloc(4);
+  if (st == hipSuccess) st = h->d_maxabs.alloc(4);
+  if (st == hipSuccess) st = h->d_colrange.alloc(2);
+  if (st == hipSuccess) st = h->d_refined.alloc(1);
+  if (st == hipSuccess) st = h->d_gref_state.alloc(4);
+  if (st == hipSuccess) st = hipMemset(h->d_gref_state.get(), 0, 4 * sizeof(int));
+  if (st == hipSuccess) st = hipMemset(h->d_refined.get(), 0, sizeof(unsigned long long));
+  if (st == hipSuccess) st = hipMemset(h->d_zscale.get(), 0, 4 * sizeof(float));   // (mals_get_gather_scale before any split-precision gather: zeros)
+  if (st == hipSuccess) st = hipMemset(h->d_bad.get(), 0xff, 4 * sizeof(unsigned long long));
+  if (st != hipSuccess) {
+    delete h;   // and whatever it allocated
+    return create_fail(MALS_HIP_ERROR, "mals_create: device " + std::to_string(cfg->device) + ": " + hipGetErrorString(st));
   }
   if (const char* e = std::getenv("MALS_REFINE_LIMIT")) h->refine_limit = std::max(0.f, (float)std::atof(e));
   if (hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming) != hipSuccess ||
@@ -1404,8 +1386,8 @@ int mals_create(const mals_config* cfg, mals_handle* out) {
   }
 #ifdef MALS_PROFILING
   if (std::getenv("MALS_DEBUG_TRACE")) {
-    (void)hipMalloc(&h->d_trace, 64 * 64 * 6 * sizeof(unsigned long long));
-    (void)hipMemset(h->d_trace, 0, 64 * 64 * 6 * sizeof(unsigned long long));
+    (void)h->d_trace.alloc(64 * 64 * 6);
+    (void)hipMemset(h->d_trace.get(), 0, 64 * 64 * 6 * sizeof(unsigned long long));
   }
 #endif
   t_create_error.clear();
@@ -1421,11 +1403,10 @@ int mals_destroy(mals_handle h) {
   (void)hipSetDevice(h->cfg.device);
   delete topn_front(h);
   h->tn_front = nullptr;
-  free_dev(h->tag_bits);
   (void)hipStreamSynchronize(h->stream);
   if (h->d_trace) {  // dump the last launch's per-phase cycle stamps (profiling aid)
     std::vector<unsigned long long> t(64 * 64 * 6);
-    (void)hipMemcpy(t.data(), h->d_trace, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(t.data(), h->d_trace.get(), t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     for (int r = 0; r < 64; r += 21)
       for (int w = 0; w < 4; w += 1) {
         const unsigned long long* o = &t[(size_t)(r * 64 + w) * 6];
@@ -1437,38 +1418,13 @@ int mals_destroy(mals_handle h) {
       const unsigned long long* b = &t[(size_t)(63 * 64 + w) * 6];
       if (b[5] > a[5]) std::fprintf(stderr, "[trace] wave %d: %llu cycles in %llu wall ticks (100 MHz) = %.0f MHz; %.0f cycles per row\n", w, b[3] - a[3], b[5] - a[5], 100.0 * (double)(b[3] - a[3]) / (double)(b[5] - a[5]), (double)(b[3] - a[3]) / 63.0);
     }
-    free_dev(h->d_trace);
   }
   for (PendingEvent& pe : h->pending) {
     (void)hipEventDestroy(pe.a);
     (void)hipEventDestroy(pe.b);
   }
-  for (int sd = 0; sd < 2; ++sd) {
-    SideState& s = h->side[sd];
-    free_matrix(s);
-    if (s.F_owned) free_dev(s.F);
-    free_dev(s.G);
-    free_dev(s.Gf);
-    free_dev(s.d_ymax);
-    free_dev(s.partials);
-  }
-  free_dev(h->d_bad);
-  free_dev(h->d_refined);
-  free_dev(h->d_gref_state);
-  free_dev(h->d_Gref);
-  free_dev(h->d_gref_part);
-  free_dev(h->d_zscale);
-  free_dev(h->d_Gperm);
   if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
   if (h->ev_refine) (void)hipEventDestroy(h->ev_refine);
-  free_dev(h->d_maxabs);
-  free_dev(h->d_colrange);
-  free_dev(h->d_Mr);
-  free_dev(h->d_Mp);
-  free_dev(h->d_eig);  // d_Q, d_Qf, d_lam, d_Bs are views into it
-  free_dev(h->d_zbound);
-  if (h->h_G) (void)hipHostFree(h->h_G);
-  if (h->eig_stage) (void)hipHostFree(h->eig_stage);
   for (int i = 0; i < 2; ++i) {
     if (h->aux[i]) (void)hipStreamSynchronize(h->aux[i]);
     if (h->aux[i]) (void)hipStreamDestroy(h->aux[i]);
@@ -1476,15 +1432,9 @@ int mals_destroy(mals_handle h) {
   }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_G) (void)hipEventDestroy(h->ev_G);
-  if (h->h_bad) (void)hipHostFree(h->h_bad);
-  free_dev(h->d_idx);
-  free_dev(h->d_rows);
-  free_dev(h->d_sd);
-  free_dev(h->d_sd_idx);
   topn_free(h);
-  free_dev(h->known_ptr_own);
-  free_dev(h->known_idx_own);
-  delete h;
+  delete h;   // every buffer the handle owns, with its device current
+
   return MALS_OK;
 }
 
@@ -1503,12 +1453,11 @@ int mals_set_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
   if (n_rows_total <= 0) return fail(h, MALS_INVALID_ARG, "n_rows_total must be positive");
   if (int rc = use_device(h)) return rc;
   SideState& s = h->side[side];
-  if (s.F_owned) free_dev(s.F);
   s.F = nullptr;
-  const size_t bytes = sizeof(float) * (size_t)n_rows_total * (size_t)h->cfg.features;
-  HIPCHK(h, hipMalloc(&s.F, bytes));
-  HIPCHK(h, hipMemsetAsync(s.F, 0, bytes, h->stream));
-  s.F_owned = true;
+  const size_t n = (size_t)n_rows_total * (size_t)h->cfg.features;
+  HIPCHK(h, s.F_own.alloc(n));
+  s.F = s.F_own.get();
+  HIPCHK(h, hipMemsetAsync(s.F, 0, sizeof(float) * n, h->stream));
   s.n_total = n_rows_total;
   s.G_valid = false;
   ++s.F_epoch;
@@ -1520,9 +1469,8 @@ int mals_bind_factors(mals_handle h, int side, float* device_ptr, int64_t n_rows
   if (!device_ptr || n_rows_total <= 0) return fail(h, MALS_INVALID_ARG, "null buffer or non-positive row count");
   if (int rc = use_device(h)) return rc;
   SideState& s = h->side[side];
-  if (s.F_owned) free_dev(s.F);
+  s.F_own.reset();
   s.F = device_ptr;
-  s.F_owned = false;
   s.n_total = n_rows_total;
   s.G_valid = false;
   ++s.F_epoch;
@@ -1557,14 +1505,10 @@ int mals_set_matrix(mals_handle h, int side, int64_t row_offset, int64_t n_rows_
     s.row_ptr = const_cast<int64_t*>(row_ptr);
     s.col = const_cast<int32_t*>(col_idx);
     s.val = const_cast<float*>(val);
-    s.m_owned = false;
   } else if (mem_kind == MALS_MEM_HOST) {
     std::memcpy(s.h_row_ptr.data(), row_ptr, sizeof(int64_t) * (size_t)(n_rows_local + 1));
-    s.m_owned = true;
-    HIPCHK(h, hipMalloc(&s.row_ptr, sizeof(int64_t) * (size_t)(n_rows_local + 1)));
+    if (int rc = alloc_matrix(h, s)) return rc;
     HIPCHK(h, hipMemcpy(s.row_ptr, row_ptr, sizeof(int64_t) * (size_t)(n_rows_local + 1), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMalloc(&s.col, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)));
-    HIPCHK(h, hipMalloc(&s.val, sizeof(float) * (size_t)std::max<int64_t>(nnz, 1)));
     if (nnz) {
       HIPCHK(h, hipMemcpy(s.col, col_idx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
       HIPCHK(h, hipMemcpy(s.val, val, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice));
@@ -1602,10 +1546,7 @@ int mals_begin_matrix(mals_handle h, int side, int64_t row_offset, int64_t n_row
   s.n_local = n_rows_local;
   s.nnz = nnz;
   s.h_row_ptr.assign((size_t)n_rows_local + 1, 0);
-  s.m_owned = true;
-  HIPCHK(h, hipMalloc(&s.row_ptr, sizeof(int64_t) * (size_t)(n_rows_local + 1)));
-  HIPCHK(h, hipMalloc(&s.col, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)));
-  HIPCHK(h, hipMalloc(&s.val, sizeof(float) * (size_t)std::max<int64_t>(nnz, 1)));
+  if (int rc = alloc_matrix(h, s)) return rc;
   s.append_rows = 0;
   s.append_nnz = 0;
   s.appending = true;
@@ -1732,18 +1673,17 @@ int mals_get_rows(mals_handle h, int side, const int64_t* row_idx, int32_t n, fl
     if (row_idx[i] < 0 || row_idx[i] >= s.n_total) return fail(h, MALS_INVALID_ARG, "row index outside the factor replica");
   if (int rc = use_device(h)) return rc;
   const int k = h->cfg.features;
-  if (h->idx_cap < n) {
-    free_dev(h->d_idx);
-    free_dev(h->d_rows);
-    HIPCHK(h, hipMalloc(&h->d_idx, sizeof(int64_t) * (size_t)n));
-    HIPCHK(h, hipMalloc(&h->d_rows, sizeof(float) * (size_t)n * k));
-    h->idx_cap = n;
+  if (h->d_idx.capacity() < (size_t)n || h->d_rows.capacity() < (size_t)n * k) {
+    h->d_idx.reset();
+    h->d_rows.reset();
+    HIPCHK(h, h->d_idx.alloc((size_t)n));
+    HIPCHK(h, h->d_rows.alloc((size_t)n * k));
   }
-  HIPCHK(h, hipMemcpyAsync(h->d_idx, row_idx, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, h->stream, s.F, h->d_idx, n, k,
-                     h->d_rows);
+  HIPCHK(h, hipMemcpyAsync(h->d_idx.get(), row_idx, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, h->stream, s.F, h->d_idx.get(), n, k,
+                     h->d_rows.get());
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(host_out, h->d_rows, sizeof(float) * (size_t)n * k, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(host_out, h->d_rows.get(), sizeof(float) * (size_t)n * k, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MALS_OK;
 }
@@ -1758,16 +1698,16 @@ int mals_gramian(mals_handle h, int side, double* host_G) {
   // only the split-f16 kernel (large matrices) records the maximum; below its threshold not even the two memsets are
   // spent (C2 is 50 launches of a few microseconds each)
   const bool with_max = s.n_total >= GRAMIAN_SPLIT_MIN_ROWS;
-  if (with_max) HIPCHK(h, hipMemsetAsync(s.d_ymax, 0, sizeof(unsigned) * YMAX_SLOTS, h->stream));
+  if (with_max) HIPCHK(h, hipMemsetAsync(s.d_ymax.get(), 0, sizeof(unsigned) * YMAX_SLOTS, h->stream));
   if (int rc = begin_timed(h, 3, (double)s.n_total * 4.0 * h->cfg.features, pe)) return rc;
-  if (int rc = launch_gramian(h, s, s.F, s.n_total, s.G, s.Gf, with_max ? s.d_ymax : nullptr)) return rc;
+  if (int rc = launch_gramian(h, s, s.F, s.n_total, s.G.get(), s.Gf.get(), with_max ? s.d_ymax.get() : nullptr)) return rc;
   if (int rc = end_timed(h, pe)) return rc;
   s.G_valid = true;
   ++s.G_version;
   s.ymax_version = with_max ? s.G_version : 0;   // every element of the replica went through the kernel: its maximum is exact
   if (host_G) {
     const int k = h->cfg.features;
-    HIPCHK(h, hipMemcpyAsync(host_G, s.G, sizeof(double) * (size_t)k * k, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(host_G, s.G.get(), sizeof(double) * (size_t)k * k, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   return MALS_OK;
@@ -1799,11 +1739,11 @@ int malsi_set_gramian(mals_handle h, int side, const double* G, int mem_kind, co
   if (int rc = use_device(h)) return rc;
   if (int rc = ensure_gramian_buffers(h, s)) return rc;
   const int k = h->cfg.features;
-  HIPCHK(h, hipMemcpyAsync(s.G, G, sizeof(double) * (size_t)k * k,
+  HIPCHK(h, hipMemcpyAsync(s.G.get(), G, sizeof(double) * (size_t)k * k,
                            mem_kind == MALS_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(gramian_pack_kernel, dim3((unsigned)tri(h->T)), dim3(256), 0, h->stream, s.G, k, h->T, s.Gf);
+  hipLaunchKernelGGL(gramian_pack_kernel, dim3((unsigned)tri(h->T)), dim3(256), 0, h->stream, s.G.get(), k, h->T, s.Gf.get());
   HIPCHK(h, hipGetLastError());
-  if (device_max) HIPCHK(h, hipMemcpyAsync(s.d_ymax, device_max, sizeof(unsigned) * YMAX_SLOTS, hipMemcpyDeviceToDevice, h->stream));
+  if (device_max) HIPCHK(h, hipMemcpyAsync(s.d_ymax.get(), device_max, sizeof(unsigned) * YMAX_SLOTS, hipMemcpyDeviceToDevice, h->stream));
   if (mem_kind != MALS_MEM_DEVICE) HIPCHK(h, hipStreamSynchronize(h->stream));
   s.G_valid = true;
   ++s.G_version;
@@ -1893,58 +1833,54 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
       h->tl[0] = now_us();
       h->tl[1] = h->tl[2] = 0.0;
       // nothing marked yet, no reference-rounded Gramian yet, no arrival counted (gramian_ref_kernel)
-      HIPCHK(h, hipMemsetAsync(h->d_gref_state, 0, 3 * sizeof(int), h->stream));
+      HIPCHK(h, hipMemsetAsync(h->d_gref_state.get(), 0, 3 * sizeof(int), h->stream));
     }
     for (int c = chunk_begin; c < chunk_end; ++c) h->pad_done[(size_t)c] = 1;
     if (k % 16 != 0) {
       const int ld = 16 * h->T;
       const size_t need = (size_t)o.n_total * (size_t)ld;
-      if (need > h->Mp_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        free_dev(h->d_Mp);
-        h->Mp_cap = 0;
+      if (need > h->d_Mp.capacity()) {
         new_half = true;   // the copy is gone
-        HIPCHK(h, hipMalloc(&h->d_Mp, sizeof(float) * need));
-        h->Mp_cap = need;
+        HIPCHK(h, h->d_Mp.reserve(need, h->stream));
       }
       if (new_half) {
         PendingEvent pe;
         if (int rc = begin_timed(h, 5, (double)o.n_total * 4.0 * (k + ld), pe)) return rc;
         const int64_t n4 = o.n_total * (ld / 4);
         const unsigned blocks = (unsigned)std::min<int64_t>((n4 + 255) / 256, (int64_t)h->n_cu * 32);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, h->stream, o.F, o.n_total, k, ld, h->d_Mp);
+        hipLaunchKernelGGL(pad_rows_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, h->stream, o.F, o.n_total, k, ld, h->d_Mp.get());
         HIPCHK(h, hipGetLastError());
         if (int rc = end_timed(h, pe)) return rc;
       }
     }
   }
   if (k % 16 != 0) {
-    p.M = h->d_Mp;
+    p.M = h->d_Mp.get();
     p.ldm = 16 * h->T;
   }
-  p.Gf = o.Gf;
+  p.Gf = o.Gf.get();
   p.Gperm = nullptr;
   if (h->lds_gather && h->split_f16 && k == 128) {
-    if (!h->d_Gperm) HIPCHK(h, hipMalloc(&h->d_Gperm, sizeof(float) * (size_t)tri(8) * 256));
+    if (!h->d_Gperm) HIPCHK(h, h->d_Gperm.alloc((size_t)tri(8) * 256));
     if (!resume && (h->gperm_side != side || h->gperm_version != o.G_version)) {
       if (h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED) {  // W does not start from G (ALS:524-539): an image of zeros
-        HIPCHK(h, hipMemsetAsync(h->d_Gperm, 0, sizeof(float) * (size_t)tri(8) * 256, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->d_Gperm.get(), 0, sizeof(float) * (size_t)tri(8) * 256, h->stream));
       } else {
-        hipLaunchKernelGGL(gramian_perm_kernel, dim3((unsigned)tri(8)), dim3(256), 0, h->stream, o.G, k, h->d_Gperm);
+        hipLaunchKernelGGL(gramian_perm_kernel, dim3((unsigned)tri(8)), dim3(256), 0, h->stream, o.G.get(), k, h->d_Gperm.get());
         HIPCHK(h, hipGetLastError());
       }
       h->gperm_side = side;
       h->gperm_version = o.G_version;
     }
-    p.Gperm = h->d_Gperm;
+    p.Gperm = h->d_Gperm.get();
   }
   p.out = s.F + s.row_offset * k;
   p.items = nullptr;
-  p.rowsC = s.rowsC;
-  p.scratch = s.scratch;
-  p.bad_row = h->d_bad + side;
-  p.suspect = h->d_bad + 2 + side;
-  p.any_marked = h->d_gref_state;
+  p.rowsC = s.rowsC.get();
+  p.scratch = s.scratch.get();
+  p.bad_row = h->d_bad.get() + side;
+  p.suspect = h->d_bad.get() + 2 + side;
+  p.any_marked = h->d_gref_state.get();
   p.refine_flag = nullptr;
   // under lossIgnoresUnspecified W has no Gramian under it and every marked row goes to the fp64 restatement, which
   // also reproduces that mode's fp32-rounded products: the estimate is at its weakest there (measured 100x and more
@@ -1956,17 +1892,11 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
     p.refine_limit *= 0.25f;
   }
   {
-    if (s.refine_cap < (size_t)s.n_local) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      free_dev(s.refine);
-      s.refine_cap = 0;
-      HIPCHK(h, hipMalloc(&s.refine, (size_t)s.n_local));
-      s.refine_cap = (size_t)s.n_local;
-    }
-    p.refine_flag = s.refine;
+    HIPCHK(h, s.refine.reserve((size_t)s.n_local, h->stream));
+    p.refine_flag = s.refine.get();
   }
   p.n_work = 0;
-  p.trace = h->d_trace;
+  p.trace = h->d_trace.get();
   p.trace_start = 0;
   if (const char* ts = std::getenv("MALS_DEBUG_TRACE")) p.trace_start = std::atoi(ts);
   if (const char* ts = std::getenv("MALS_DEBUG_TRACE_SIDE")) if (std::atoi(ts) != side) p.trace = nullptr;
@@ -1975,7 +1905,7 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
   p.alpha = (float)h->cfg.alpha;
   p.lambda_alpha = (float)(h->cfg.lambda * h->cfg.alpha);  // ALS:435
   p.sing_threshold = (float)h->cfg.singularity_threshold;
-  p.zscale = h->d_zscale;
+  p.zscale = h->d_zscale.get();
   if (!resume && h->split_f16 && (h->zs_side != side || h->zs_version != o.G_version || h->zs_bound != s.max_abs_val || h->zs_mean != s.mean_abs_val)) {
     // once per half-iteration, not per chunk: the scale only depends on G and on the value bound
     const double base_w = (h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED) ? 1.0 : 0.0;
@@ -1983,8 +1913,8 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
     const double w_mean = base_w + ((h->cfg.flags & MALS_FLAG_RECONSTRUCT_R) ? 0.0 : std::fabs(h->cfg.alpha) * s.mean_abs_val);
     int force = -1;  // MALS_FORCE_RANGE_FLAG=0/1 (tests): override the range decision
     if (const char* e = std::getenv("MALS_FORCE_RANGE_FLAG")) force = std::atoi(e) != 0;
-    hipLaunchKernelGGL(gather_scale_kernel, dim3(1), dim3(64), 0, h->stream, o.G, k, (float)std::sqrt(w_max), (float)std::sqrt(w_mean),
-                       (double)o.n_total, force, (o.ymax_version != 0 && o.ymax_version == o.G_version) ? o.d_ymax : nullptr, h->d_zscale);
+    hipLaunchKernelGGL(gather_scale_kernel, dim3(1), dim3(64), 0, h->stream, o.G.get(), k, (float)std::sqrt(w_max), (float)std::sqrt(w_mean),
+                       (double)o.n_total, force, (o.ymax_version != 0 && o.ymax_version == o.G_version) ? o.d_ymax.get() : nullptr, h->d_zscale.get());
     HIPCHK(h, hipGetLastError());
     h->zs_side = side;
     h->zs_version = o.G_version;
@@ -2000,9 +1930,9 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
   const bool want_dual = s.n_dual_rows > 0 && dual_pays && h->cfg.flags == 0 && h->cfg.alpha > 0.0 && o.G_valid;
   const bool dual_stale = resume || (want_dual && (h->dual_side != side || h->dual_version != o.G_version));
   if (dual_stale && !resume) {
-    if (!h->h_G) HIPCHK(h, hipHostMalloc(&h->h_G, sizeof(double) * (size_t)k * k));
+    if (!h->h_G) HIPCHK(h, h->h_G.alloc((size_t)k * k));
     if (!h->ev_G) HIPCHK(h, hipEventCreateWithFlags(&h->ev_G, hipEventDisableTiming));
-    HIPCHK(h, hipMemcpyAsync(h->h_G, o.G, sizeof(double) * (size_t)k * k, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_G.get(), o.G.get(), sizeof(double) * (size_t)k * k, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipEventRecord(h->ev_G, h->stream));
   }
   if (phase == SOLVE_BEGIN && chunk_end != chunk_begin + 1) return fail(h, MALS_INVALID_ARG, "solve BEGIN takes one chunk");
@@ -2014,7 +1944,7 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
     const SideState::ChunkRange& cr = s.chunks[(size_t)c];
     const int64_t row0 = std::min<int64_t>(s.n_local, (int64_t)c * rows_per_chunk);
     const int64_t row1 = std::min<int64_t>(s.n_local, (int64_t)(c + 1) * rows_per_chunk);
-    if (!resume && p.refine_flag && row1 > row0) HIPCHK(h, hipMemsetAsync(s.refine + row0, 0, (size_t)(row1 - row0), h->stream));
+    if (!resume && p.refine_flag && row1 > row0) HIPCHK(h, hipMemsetAsync(s.refine.get() + row0, 0, (size_t)(row1 - row0), h->stream));
     // (per chunk, not per call: once the first chunk of a multi-chunk call has prepared the dual path the later ones use it)
     bool dual_now = want_dual && h->dual_ok && h->dual_side == side && h->dual_version == o.G_version;
     if (!resume)
@@ -2064,15 +1994,15 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
       if (h->refine_recorded) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_refine, 0));   // one chunk's block at a time
       if (!h->d_Gref) {   // before the parameter block below takes the pointers
         const size_t kp2 = (size_t)(16 * h->T) * (size_t)(16 * h->T);
-        HIPCHK(h, hipMalloc(&h->d_Gref, sizeof(double) * kp2));
-        HIPCHK(h, hipMalloc(&h->d_gref_part, sizeof(double) * kp2 * (size_t)h->n_cu * 2));
+        HIPCHK(h, h->d_Gref.alloc(kp2));
+        HIPCHK(h, h->d_gref_part.alloc(kp2 * (size_t)h->n_cu * 2));
       }
       RefineParams q;
       q.p = p;
-      q.G = o.G;
-      q.Gref = h->d_Gref;
-      q.gref_state = h->d_gref_state;
-      q.n_refined = h->d_refined;
+      q.G = o.G.get();
+      q.Gref = h->d_Gref.get();
+      q.gref_state = h->d_gref_state.get();
+      q.n_refined = h->d_refined.get();
       q.row_begin = row0;
       q.row_end = row1;
       q.alpha = h->cfg.alpha;
@@ -2129,7 +2059,7 @@ int malsi_dual_host(mals_handle h, int side, mals_handle from) {
 int mals_get_gather_scale(mals_handle h, float* out4) {
   if (!h || !out4) return MALS_INVALID_ARG;
   if (int rc = use_device(h)) return rc;
-  HIPCHK(h, hipMemcpyAsync(out4, h->d_zscale, 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out4, h->d_zscale.get(), 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MALS_OK;
 }
@@ -2180,7 +2110,7 @@ bool build_row_system(mals_handle h, int side, int64_t local_row, std::vector<do
   }
   const bool reconstruct = h->cfg.flags & MALS_FLAG_RECONSTRUCT_R;
   if (!(h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED)) {
-    if (!o.G || hipMemcpy(W.data(), o.G, sizeof(double) * W.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (!o.G.get() || hipMemcpy(W.data(), o.G.get(), sizeof(double) * W.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
   }
   for (int64_t e = 0; e < n_u; ++e) {
     const float* y = rows.data() + (size_t)e * k;
@@ -2205,30 +2135,30 @@ int apparent_rank_of_row(mals_handle h, int side, int64_t local_row) {
 int mals_check(mals_handle h) {
   if (!h) return MALS_INVALID_ARG;
   if (int rc = use_device(h)) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->h_bad, h->d_bad, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->h_bad.get(), h->d_bad.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   // The kernels' verdict is "a Cholesky pivot <= threshold"; the reference's is "a diagonal element of R of the
   // column-pivoted QR <= threshold" (CMLSS:43-54), which can already hold when the smallest (unpivoted) Cholesky
   // pivot is still 100x the threshold (measured: 63 x 63 Gramian of 63 rows, pivot 5e-5, |R_dd| 2e-6).  So the row with
   // the smallest pivot within 1024x of the threshold is put to the reference's own test here, in fp64 on the host.
   for (int sd = 0; sd < 2; ++sd) {
-    const unsigned long long key = h->h_bad[2 + sd];
-    if (h->h_bad[sd] != ~0ull || key == ~0ull) continue;
+    const unsigned long long key = h->h_bad.get()[2 + sd];
+    if (h->h_bad.get()[sd] != ~0ull || key == ~0ull) continue;
     const int64_t row = (int64_t)(key & 0xffffffffull);
     SideState& s = h->side[sd];
     std::vector<double> W;
     if (row < s.n_local && s.h_row_ptr[(size_t)row + 1] - s.h_row_ptr[(size_t)row] <= 200000 && build_row_system(h, sd, row, W) &&
         !mals::PivotedQR(W.data(), h->cfg.features, h->cfg.singularity_threshold).non_singular())
-      h->h_bad[sd] = (unsigned long long)row;
+      h->h_bad.get()[sd] = (unsigned long long)row;
   }
-  if (h->h_bad[2] != ~0ull || h->h_bad[3] != ~0ull)
-    HIPCHK(h, hipMemsetAsync(h->d_bad + 2, 0xff, 2 * sizeof(unsigned long long), h->stream));
+  if (h->h_bad.get()[2] != ~0ull || h->h_bad.get()[3] != ~0ull)
+    HIPCHK(h, hipMemsetAsync(h->d_bad.get() + 2, 0xff, 2 * sizeof(unsigned long long), h->stream));
   for (int sd = 0; sd < 2; ++sd) {
-    if (h->h_bad[sd] != ~0ull) {
+    if (h->h_bad.get()[sd] != ~0ull) {
       h->sing_side = sd;
-      h->sing_row = h->side[sd].row_offset + (int64_t)h->h_bad[sd];
-      h->sing_rank = apparent_rank_of_row(h, sd, (int64_t)h->h_bad[sd]);
-      HIPCHK(h, hipMemsetAsync(h->d_bad, 0xff, 2 * sizeof(unsigned long long), h->stream));
+      h->sing_row = h->side[sd].row_offset + (int64_t)h->h_bad.get()[sd];
+      h->sing_rank = apparent_rank_of_row(h, sd, (int64_t)h->h_bad.get()[sd]);
+      HIPCHK(h, hipMemsetAsync(h->d_bad.get(), 0xff, 2 * sizeof(unsigned long long), h->stream));
       char buf[160];
       std::snprintf(buf, sizeof(buf), "near-singular system (pivot <= %g) for row %lld of side %c", h->cfg.singularity_threshold,
                     (long long)h->sing_row, sd == MALS_SIDE_X ? 'X' : 'Y');
@@ -2323,7 +2253,7 @@ int mals_half_iteration(mals_handle h, int side) {
     if (int rc = mals_gramian(h, 1 - side, nullptr)) return rc;  // ALS:342 / ALS:369
   }
   if (int rc = mals_solve_side(h, side)) return rc;                // ALS:344 / ALS:371
-  return mals_check(h);                                            // ALS:346-361 f.get()
+  return mals_check(h);                                            // ALS:346-361 f
 }
 
 int mals_sample_dots(mals_handle h, const int64_t* test_users, int32_t n_test_users, const int64_t* test_items, int32_t n_test_items,
@@ -2343,21 +2273,19 @@ int mals_sample_dots(mals_handle h, const int64_t* test_users, int32_t n_test_us
   for (int j = 0; j < n_test_items; ++j)
     if (test_items[j] < 0 || test_items[j] >= y.n_total) return fail(h, MALS_INVALID_ARG, "test item outside the factor replica");
   if (int rc = use_device(h)) return rc;
-  const size_t idx_bytes = sizeof(int64_t) * (size_t)(n_test_users + n_test_items);
-  if (h->sd_cap < (size_t)n || h->sd_idx_cap < idx_bytes) {
-    free_dev(h->d_sd);
-    free_dev(h->d_sd_idx);
-    HIPCHK(h, hipMalloc(&h->d_sd, sizeof(double) * (size_t)n));
-    HIPCHK(h, hipMalloc(&h->d_sd_idx, idx_bytes));
-    h->sd_cap = (size_t)n;
-    h->sd_idx_cap = idx_bytes;
+  const size_t n_idx = (size_t)(n_test_users + n_test_items);
+  if (h->d_sd.capacity() < (size_t)n || h->d_sd_idx.capacity() < n_idx) {
+    h->d_sd.reset();
+    h->d_sd_idx.reset();
+    HIPCHK(h, h->d_sd.alloc((size_t)n));
+    HIPCHK(h, h->d_sd_idx.alloc(n_idx));
   }
-  HIPCHK(h, hipMemcpyAsync(h->d_sd_idx, test_users, sizeof(int64_t) * (size_t)n_test_users, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_sd_idx + n_test_users, test_items, sizeof(int64_t) * (size_t)n_test_items, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(sample_dots_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, x.F, y.F, h->d_sd_idx,
-                     h->d_sd_idx + n_test_users, n_test_users, n_test_items, h->cfg.features, h->d_sd);
+  HIPCHK(h, hipMemcpyAsync(h->d_sd_idx.get(), test_users, sizeof(int64_t) * (size_t)n_test_users, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_sd_idx.get() + n_test_users, test_items, sizeof(int64_t) * (size_t)n_test_items, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(sample_dots_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, x.F, y.F, h->d_sd_idx.get(),
+                     h->d_sd_idx.get() + n_test_users, n_test_users, n_test_items, h->cfg.features, h->d_sd.get());
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(host_out, h->d_sd, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(host_out, h->d_sd.get(), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MALS_OK;
 }
@@ -2432,10 +2360,12 @@ int mals_reconstruction_error(mals_handle h, double* sum_out, int64_t* count_out
   if (s.n_local == 0) return MALS_OK;
   const unsigned grid = (unsigned)std::min<int64_t>((s.n_local + 3) / 4, (int64_t)h->n_cu * 32);
   const size_t n_waves = (size_t)grid * 4;
-  double* d_sum = nullptr;
-  unsigned long long* d_cnt = nullptr;
-  HIPCHK(h, hipMalloc(&d_sum, sizeof(double) * n_waves));
-  HIPCHK(h, hipMalloc(&d_cnt, sizeof(unsigned long long) * n_waves));
+  DeviceBuffer<double> sums;
+  DeviceBuffer<unsigned long long> counts;
+  HIPCHK(h, sums.alloc(n_waves));
+  HIPCHK(h, counts.alloc(n_waves));
+  double* d_sum = sums.get();
+  unsigned long long* d_cnt = counts.get();
   int rc = MALS_INVALID_ARG;
   switch (h->T) {
     case 1: rc = launch_reconstruction<1>(h, s, o, grid, d_sum, d_cnt); break;
@@ -2455,8 +2385,8 @@ int mals_reconstruction_error(mals_handle h, double* sum_out, int64_t* count_out
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) rc = fail(h, MALS_HIP_ERROR, hipGetErrorString(e));
   }
-  (void)hipFree(d_sum);
-  (void)hipFree(d_cnt);
+  sums.reset();
+  counts.reset();
   if (rc != MALS_OK) return rc;
   double sum = 0.0;
   unsigned long long cnt = 0;
@@ -2495,7 +2425,7 @@ int mals_recommend(mals_handle h, const int64_t* user_idx, int32_t n_queries, in
       return topn_fail(h, MALS_INVALID_ARG, "known items of this user are not on this handle (row outside the local shard)");
   }
   if (n_queries == 0) return MALS_OK;
-  if (h->tag_bits && h->tag_bits_items != y.n_total)
+  if (h->tag_bits.get() && h->tag_bits_items != y.n_total)
     return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
   if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
   TopnTicket t;
@@ -2537,12 +2467,12 @@ int mals_set_known_items(mals_handle h, int64_t n_rows, const int64_t* row_ptr, 
   } else {
     const int64_t n = row_ptr[n_rows];
     if (n < 0 || (n > 0 && !item_idx)) return fail(h, MALS_INVALID_ARG, "bad known-item arrays");
-    HIPCHK(h, hipMalloc(&h->known_ptr_own, sizeof(int64_t) * (size_t)(n_rows + 1)));
-    HIPCHK(h, hipMalloc(&h->known_idx_own, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)));
-    HIPCHK(h, hipMemcpy(h->known_ptr_own, row_ptr, sizeof(int64_t) * (size_t)(n_rows + 1), hipMemcpyHostToDevice));
-    if (n) HIPCHK(h, hipMemcpy(h->known_idx_own, item_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-    h->known_ptr = h->known_ptr_own;
-    h->known_idx = h->known_idx_own;
+    HIPCHK(h, h->known_ptr_copy.alloc((size_t)(n_rows + 1)));
+    HIPCHK(h, h->known_idx_copy.alloc((size_t)std::max<int64_t>(n, 1)));
+    HIPCHK(h, hipMemcpy(h->known_ptr_copy.get(), row_ptr, sizeof(int64_t) * (size_t)(n_rows + 1), hipMemcpyHostToDevice));
+    if (n) HIPCHK(h, hipMemcpy(h->known_idx_copy.get(), item_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    h->known_ptr = h->known_ptr_copy.get();
+    h->known_idx = h->known_idx_copy.get();
   }
   h->known_rows = n_rows;
   return MALS_OK;
@@ -2554,38 +2484,32 @@ int mals_set_tag_items(mals_handle h, int64_t n, const int64_t* item_idx, int me
   if (n < 0 || (n > 0 && !item_idx)) return fail(h, MALS_INVALID_ARG, "bad tag item list");
   if (int rc = use_device(h)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  free_dev(h->tag_bits);
+  h->tag_bits.reset();
   h->tag_bits_items = h->n_tag_items = 0;
   if (n == 0) return MALS_OK;
   const int64_t n_items = h->side[MALS_SIDE_Y].n_total;
   if (n_items <= 0) return fail(h, MALS_INVALID_ARG, "tag items: the item factor replica comes first (mals_set_factor_rows)");
   const size_t words = ((size_t)((n_items + 31) / 32) + 1) & ~(size_t)1;   // even: the counter behind them is 8-byte aligned
-  uint32_t* bits = nullptr;
-  HIPCHK(h, hipMalloc(&bits, sizeof(uint32_t) * words + sizeof(unsigned long long)));
-  unsigned long long* d_n = reinterpret_cast<unsigned long long*>(bits + words);
-  HIPCHK(h, hipMemsetAsync(bits, 0, sizeof(uint32_t) * words + sizeof(unsigned long long), h->stream));
-  int64_t* d_idx = nullptr;
+  DeviceBuffer<uint32_t> bits;   // the words, then the counter
+  HIPCHK(h, bits.alloc(words + sizeof(unsigned long long) / sizeof(uint32_t)));
+  unsigned long long* d_n = reinterpret_cast<unsigned long long*>(bits.get() + words);
+  HIPCHK(h, hipMemsetAsync(bits.get(), 0, sizeof(uint32_t) * words + sizeof(unsigned long long), h->stream));
+  DeviceBuffer<int64_t> d_idx;
   const int64_t* src = item_idx;
   if (mem_kind == MALS_MEM_HOST) {
-    HIPCHK(h, hipMalloc(&d_idx, sizeof(int64_t) * (size_t)n));
-    HIPCHK(h, hipMemcpyAsync(d_idx, item_idx, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    src = d_idx;
+    HIPCHK(h, d_idx.alloc((size_t)n));
+    HIPCHK(h, hipMemcpyAsync(d_idx.get(), item_idx, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    src = d_idx.get();
   }
-  hipLaunchKernelGGL(topn_tag_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, src, n, n_items, bits, d_n);
+  hipLaunchKernelGGL(topn_tag_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, src, n, n_items, bits.get(), d_n);
   unsigned long long n_set = 0;
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(&n_set, d_n, sizeof(n_set), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  free_dev(d_idx);
-  if (e != hipSuccess) {
-    free_dev(bits);
-    return fail(h, MALS_HIP_ERROR, std::string("mals_set_tag_items: ") + hipGetErrorString(e));
-  }
-  if (n_set == 0) {  // none of them owns a row of Y: nothing to strike
-    free_dev(bits);
-    return MALS_OK;
-  }
-  h->tag_bits = bits;
+  d_idx.reset();
+  if (e != hipSuccess) return fail(h, MALS_HIP_ERROR, std::string("mals_set_tag_items: ") + hipGetErrorString(e));
+  if (n_set == 0) return MALS_OK;  // none of them owns a row of Y: nothing to strike
+  h->tag_bits = std::move(bits);
   h->tag_bits_items = n_items;
   h->n_tag_items = (int64_t)n_set;
   return MALS_OK;
@@ -2616,7 +2540,7 @@ int mals_recommend_to_many(mals_handle h, const float* vectors, const int64_t* v
     }
   }
   if (n_queries == 0) return MALS_OK;
-  if (h->tag_bits && h->tag_bits_items != y.n_total)
+  if (h->tag_bits.get() && h->tag_bits_items != y.n_total)
     return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
   if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
   TopnRequest rq;
@@ -2715,7 +2639,7 @@ int mals_reset_stats(mals_handle h) {
   if (int rc = drain_events(h)) return rc;
   std::memset(&h->stats, 0, sizeof(h->stats));
   h->stats.struct_size = (int32_t)sizeof(mals_stats);
-  HIPCHK(h, hipMemsetAsync(h->d_refined, 0, sizeof(unsigned long long), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->d_refined.get(), 0, sizeof(unsigned long long), h->stream));
   return MALS_OK;
 }
 
@@ -2724,7 +2648,7 @@ int mals_get_stats(mals_handle h, mals_stats* out) {
   if (int rc = use_device(h)) return rc;
   if (int rc = drain_events(h)) return rc;
   unsigned long long refined = 0;
-  HIPCHK(h, hipMemcpyAsync(&refined, h->d_refined, sizeof(refined), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&refined, h->d_refined.get(), sizeof(refined), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->stats.rows_refined = (int64_t)refined;
   *out = h->stats;

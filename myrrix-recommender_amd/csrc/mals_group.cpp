@@ -13,6 +13,7 @@
 // of a rank is issued on that rank's comm stream -- a communicator is never used from two streams at once.
 #include "../../include/myrrix_als.h"
 #include "mals_internal.h"
+#include "hip_buffer.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -116,18 +117,18 @@ struct Member {
   hipEvent_t ev_solved = nullptr, ev_exchanged = nullptr;
   hipEvent_t ev_half = nullptr, ev_join = nullptr;
   ncclComm_t nccl = nullptr;
-  double* d_gp = nullptr;    // k*k: partial Gramian / all-reduce buffer
-  double* d_stat = nullptr;  // 4 doubles: value statistics, status
-  float* d_ymax = nullptr;   // max |element| of the rows of this member's partial Gramian (bit pattern = non-negative float)
+  mals::DeviceBuffer<double> d_gp;    // k*k: partial Gramian / all-reduce buffer
+  mals::DeviceBuffer<double> d_stat;  // 4 doubles: value statistics, status
+  mals::DeviceBuffer<float> d_ymax;   // max |element| of the rows of this member's partial Gramian (bit pattern = non-negative float)
   float* F[2] = {nullptr, nullptr};
-  int64_t* d_row_ptr[2] = {nullptr, nullptr};  // rebased row pointers of borrowed device matrices
+  mals::DeviceBuffer<int64_t> d_row_ptr[2];  // rebased row pointers of borrowed device matrices
   // mals_ingest_install_group: the member's slices when the ingest lives on ANOTHER device (peer copies), and its slice of
   // knownItemIDs (rebased offsets always; the indices only when copied)
-  int32_t* own_col[2] = {nullptr, nullptr};
-  float* own_val[2] = {nullptr, nullptr};
-  int64_t* own_known_ptr = nullptr;
-  int32_t* own_known_idx = nullptr;
-  int64_t* own_tag_idx = nullptr;
+  mals::DeviceBuffer<int32_t> own_col[2];
+  mals::DeviceBuffer<float> own_val[2];
+  mals::DeviceBuffer<int64_t> own_known_ptr;
+  mals::DeviceBuffer<int32_t> own_known_idx;
+  mals::DeviceBuffer<int64_t> own_tag_idx;
   // chunked upload
   int64_t up_rows = 0;
 };
@@ -223,9 +224,9 @@ int init_member(mals_group g, Member& mb, const mals_config& cfg, int device, in
   GHIP(g, hipEventCreateWithFlags(&mb.ev_exchanged, hipEventDisableTiming));
   GHIP(g, hipEventRecord(mb.ev_exchanged, mb.comm));
   const size_t kk = (size_t)cfg.features * cfg.features;
-  GHIP(g, hipMalloc(&mb.d_gp, sizeof(double) * kk));
-  GHIP(g, hipMalloc(&mb.d_stat, sizeof(double) * 4));
-  GHIP(g, hipMalloc(&mb.d_ymax, sizeof(float) * (size_t)malsi_ymax_slots()));
+  GHIP(g, mb.d_gp.alloc(kk));
+  GHIP(g, mb.d_stat.alloc(4));
+  GHIP(g, mb.d_ymax.alloc((size_t)malsi_ymax_slots()));
   if (int rc = mals_set_stream(mb.h, mb.compute)) return mfail(g, mb, rc);
   return MALS_OK;
 }
@@ -237,17 +238,6 @@ void destroy_member(Member& mb) {
   if (mb.comm) (void)hipStreamSynchronize(mb.comm);
   if (mb.nccl && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(mb.nccl);
   if (mb.h) (void)mals_destroy(mb.h);
-  for (int sd = 0; sd < 2; ++sd) {
-    if (mb.d_row_ptr[sd]) (void)hipFree(mb.d_row_ptr[sd]);
-    if (mb.own_col[sd]) (void)hipFree(mb.own_col[sd]);
-    if (mb.own_val[sd]) (void)hipFree(mb.own_val[sd]);
-  }
-  if (mb.own_known_ptr) (void)hipFree(mb.own_known_ptr);
-  if (mb.own_known_idx) (void)hipFree(mb.own_known_idx);
-  if (mb.own_tag_idx) (void)hipFree(mb.own_tag_idx);
-  if (mb.d_gp) (void)hipFree(mb.d_gp);
-  if (mb.d_stat) (void)hipFree(mb.d_stat);
-  if (mb.d_ymax) (void)hipFree(mb.d_ymax);
   if (mb.ev_solved) (void)hipEventDestroy(mb.ev_solved);
   if (mb.ev_half) (void)hipEventDestroy(mb.ev_half);
   if (mb.ev_join) (void)hipEventDestroy(mb.ev_join);
@@ -255,7 +245,7 @@ void destroy_member(Member& mb) {
   if (mb.ev_exchanged) (void)hipEventDestroy(mb.ev_exchanged);
   if (mb.comm) (void)hipStreamDestroy(mb.comm);
   if (mb.compute) (void)hipStreamDestroy(mb.compute);
-  mb = Member();
+  mb = Member();   // and the member's buffers, with its device current
 }
 
 // out[i] = op over all ranks of the members' d_stat[0..n) (op: 0 = sum, 1 = max); result in every d_stat
@@ -265,13 +255,13 @@ int allreduce_stat(mals_group g, int n, int op) {
     std::vector<double> acc((size_t)n, op ? -std::numeric_limits<double>::infinity() : 0.0), tmp((size_t)n);
     for (Member& mb : g->m) {
       GHIP(g, hipSetDevice(mb.device));
-      GHIP(g, hipMemcpyAsync(tmp.data(), mb.d_stat, sizeof(double) * n, hipMemcpyDeviceToHost, mb.compute));
+      GHIP(g, hipMemcpyAsync(tmp.data(), mb.d_stat.get(), sizeof(double) * n, hipMemcpyDeviceToHost, mb.compute));
       GHIP(g, hipStreamSynchronize(mb.compute));
       for (int i = 0; i < n; ++i) acc[(size_t)i] = op ? std::max(acc[(size_t)i], tmp[(size_t)i]) : acc[(size_t)i] + tmp[(size_t)i];
     }
     for (Member& mb : g->m) {
       GHIP(g, hipSetDevice(mb.device));
-      GHIP(g, hipMemcpyAsync(mb.d_stat, acc.data(), sizeof(double) * n, hipMemcpyHostToDevice, mb.compute));
+      GHIP(g, hipMemcpyAsync(mb.d_stat.get(), acc.data(), sizeof(double) * n, hipMemcpyHostToDevice, mb.compute));
       GHIP(g, hipStreamSynchronize(mb.compute));
     }
     return MALS_OK;
@@ -279,7 +269,7 @@ int allreduce_stat(mals_group g, int n, int op) {
   // every RCCL call of a rank goes to ITS comm stream: one communicator is never used from two streams at once
   GNCCL(g, g_rccl.GroupStart());
   for (Member& mb : g->m) {
-    const ncclResult_t r = g_rccl.AllReduce(mb.d_stat, mb.d_stat, (size_t)n, ncclDouble, op ? ncclMax : ncclSum, mb.nccl, mb.comm);
+    const ncclResult_t r = g_rccl.AllReduce(mb.d_stat.get(), mb.d_stat.get(), (size_t)n, ncclDouble, op ? ncclMax : ncclSum, mb.nccl, mb.comm);
     if (r != ncclSuccess) {
       (void)g_rccl.GroupEnd();
       return gfail(g, MALS_COMM_ERROR, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
@@ -298,13 +288,13 @@ int allreduce_host(mals_group g, const std::vector<std::vector<double>>& per_mem
   for (size_t i = 0; i < g->m.size(); ++i) {
     Member& mb = g->m[i];
     GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipMemcpyAsync(mb.d_stat, per_member[i].data(), sizeof(double) * n, hipMemcpyHostToDevice, mb.compute));
+    GHIP(g, hipMemcpyAsync(mb.d_stat.get(), per_member[i].data(), sizeof(double) * n, hipMemcpyHostToDevice, mb.compute));
     GHIP(g, hipStreamSynchronize(mb.compute));  // the source is a pageable temporary
   }
   if (int rc = allreduce_stat(g, n, op)) return rc;
   Member& m0 = g->m[0];
   GHIP(g, hipSetDevice(m0.device));
-  GHIP(g, hipMemcpyAsync(out, m0.d_stat, sizeof(double) * n, hipMemcpyDeviceToHost, m0.compute));
+  GHIP(g, hipMemcpyAsync(out, m0.d_stat.get(), sizeof(double) * n, hipMemcpyDeviceToHost, m0.compute));
   GHIP(g, hipStreamSynchronize(m0.compute));
   return MALS_OK;
 }
@@ -428,14 +418,14 @@ int group_gramian(mals_group g, int side, int* local_rc, std::string* local_msg)
     // the kernels that form the partial Gramian also record the largest |element| of their rows: summed Gramian + the
     // maximum over all ranks give every member the exact operand bound of the split-precision gather (instead of
     // sqrt(max_f G_ff), which at 1e8 rows is 13 binades loose)
-    GHIP(g, hipMemsetAsync(mb.d_ymax, 0, sizeof(float) * (size_t)malsi_ymax_slots(), mb.compute));
+    GHIP(g, hipMemsetAsync(mb.d_ymax.get(), 0, sizeof(float) * (size_t)malsi_ymax_slots(), mb.compute));
     int prc = MALS_OK;
     if (r1 > r0) {
-      prc = malsi_gramian_partial(mb.h, side, r0, r1 - r0, mb.d_gp, reinterpret_cast<unsigned*>(mb.d_ymax));
+      prc = malsi_gramian_partial(mb.h, side, r0, r1 - r0, mb.d_gp.get(), reinterpret_cast<unsigned*>(mb.d_ymax.get()));
       if (prc == MALS_HIP_ERROR) return mfail(g, mb, prc);
       if (prc != MALS_OK) member_failed(mb, prc);
     }
-    if (r1 <= r0 || prc != MALS_OK) GHIP(g, hipMemsetAsync(mb.d_gp, 0, sizeof(double) * kk, mb.compute));
+    if (r1 <= r0 || prc != MALS_OK) GHIP(g, hipMemsetAsync(mb.d_gp.get(), 0, sizeof(double) * kk, mb.compute));
   }
   if (g->world > 1 || g->m[0].nccl) {
     if (g->backend == MALS_GROUP_PEER_COPY) {  // fixed summation order (rank 0, 1, ...): deterministic
@@ -444,8 +434,8 @@ int group_gramian(mals_group g, int side, int* local_rc, std::string* local_msg)
       std::vector<float> ymax(ns, 0.f), ytmp(ns, 0.f);
       for (Member& mb : g->m) {
         GHIP(g, hipSetDevice(mb.device));
-        GHIP(g, hipMemcpyAsync(tmp.data(), mb.d_gp, sizeof(double) * kk, hipMemcpyDeviceToHost, mb.compute));
-        GHIP(g, hipMemcpyAsync(ytmp.data(), mb.d_ymax, sizeof(float) * ns, hipMemcpyDeviceToHost, mb.compute));
+        GHIP(g, hipMemcpyAsync(tmp.data(), mb.d_gp.get(), sizeof(double) * kk, hipMemcpyDeviceToHost, mb.compute));
+        GHIP(g, hipMemcpyAsync(ytmp.data(), mb.d_ymax.get(), sizeof(float) * ns, hipMemcpyDeviceToHost, mb.compute));
         GHIP(g, hipStreamSynchronize(mb.compute));
         for (size_t i = 0; i < kk; ++i) acc[i] += tmp[i];
         for (size_t i = 0; i < ns; ++i)
@@ -453,8 +443,8 @@ int group_gramian(mals_group g, int side, int* local_rc, std::string* local_msg)
       }
       for (Member& mb : g->m) {
         GHIP(g, hipSetDevice(mb.device));
-        GHIP(g, hipMemcpyAsync(mb.d_gp, acc.data(), sizeof(double) * kk, hipMemcpyHostToDevice, mb.compute));
-        GHIP(g, hipMemcpyAsync(mb.d_ymax, ymax.data(), sizeof(float) * ns, hipMemcpyHostToDevice, mb.compute));
+        GHIP(g, hipMemcpyAsync(mb.d_gp.get(), acc.data(), sizeof(double) * kk, hipMemcpyHostToDevice, mb.compute));
+        GHIP(g, hipMemcpyAsync(mb.d_ymax.get(), ymax.data(), sizeof(float) * ns, hipMemcpyHostToDevice, mb.compute));
         GHIP(g, hipStreamSynchronize(mb.compute));
       }
     } else {
@@ -466,8 +456,8 @@ int group_gramian(mals_group g, int side, int* local_rc, std::string* local_msg)
       }
       GNCCL(g, g_rccl.GroupStart());
       for (Member& mb : g->m) {
-        ncclResult_t r = g_rccl.AllReduce(mb.d_gp, mb.d_gp, kk, ncclDouble, ncclSum, mb.nccl, mb.comm);
-        if (r == ncclSuccess) r = g_rccl.AllReduce(mb.d_ymax, mb.d_ymax, (size_t)malsi_ymax_slots(), ncclFloat, ncclMax, mb.nccl, mb.comm);
+        ncclResult_t r = g_rccl.AllReduce(mb.d_gp.get(), mb.d_gp.get(), kk, ncclDouble, ncclSum, mb.nccl, mb.comm);
+        if (r == ncclSuccess) r = g_rccl.AllReduce(mb.d_ymax.get(), mb.d_ymax.get(), (size_t)malsi_ymax_slots(), ncclFloat, ncclMax, mb.nccl, mb.comm);
         if (r != ncclSuccess) {
           (void)g_rccl.GroupEnd();
           return gfail(g, MALS_COMM_ERROR, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
@@ -483,7 +473,7 @@ int group_gramian(mals_group g, int side, int* local_rc, std::string* local_msg)
   }
   for (Member& mb : g->m) {
     GHIP(g, hipSetDevice(mb.device));
-    if (int rc = malsi_set_gramian(mb.h, side, mb.d_gp, MALS_MEM_DEVICE, reinterpret_cast<const unsigned*>(mb.d_ymax))) {
+    if (int rc = malsi_set_gramian(mb.h, side, mb.d_gp.get(), MALS_MEM_DEVICE, reinterpret_cast<const unsigned*>(mb.d_ymax.get()))) {
       if (rc == MALS_HIP_ERROR) return mfail(g, mb, rc);
       member_failed(mb, rc);
     }
@@ -787,19 +777,15 @@ int mals_group_set_matrix(mals_group g, int side, int64_t n_rows, int64_t nnz, c
     if (mem_kind == MALS_MEM_HOST) {
       rc = mals_set_matrix(mb.h, side, r0, r1 - r0, e1 - e0, local.data(), col_idx + e0, val + e0, MALS_MEM_HOST);
     } else {
-      if (mb.d_row_ptr[side]) (void)hipFree(mb.d_row_ptr[side]);
-      mb.d_row_ptr[side] = nullptr;
       // (slices an earlier mals_ingest_install_group copied for this member are not this matrix: let them go once the handle
       // has taken the new arrays below -- mals_set_matrix synchronises the member's stream before it drops the old ones)
-      GHIP(g, hipMalloc(&mb.d_row_ptr[side], sizeof(int64_t) * local.size()));
-      GHIP(g, hipMemcpy(mb.d_row_ptr[side], local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
-      rc = mals_set_matrix(mb.h, side, r0, r1 - r0, e1 - e0, mb.d_row_ptr[side], col_idx + e0, val + e0, MALS_MEM_DEVICE);
+      GHIP(g, mb.d_row_ptr[side].alloc(local.size()));
+      GHIP(g, hipMemcpy(mb.d_row_ptr[side].get(), local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
+      rc = mals_set_matrix(mb.h, side, r0, r1 - r0, e1 - e0, mb.d_row_ptr[side].get(), col_idx + e0, val + e0, MALS_MEM_DEVICE);
     }
     if (rc) return mfail(g, mb, rc);
-    if (mb.own_col[side]) (void)hipFree(mb.own_col[side]);
-    if (mb.own_val[side]) (void)hipFree(mb.own_val[side]);
-    mb.own_col[side] = nullptr;
-    mb.own_val[side] = nullptr;
+    mb.own_col[side].reset();
+    mb.own_val[side].reset();
   }
   return finish_matrix(g, side);
 }
@@ -814,10 +800,6 @@ int mals_ingest_install_group(mals_ingest in, mals_group g, int32_t flags) {
   if (int rc = mals_ingest_device(in, &in_dev)) return gfail(g, rc, "mals_ingest_device failed");
   if (flags & ~MALS_INSTALL_COPY) return gfail(g, MALS_INVALID_ARG, "unknown install flag");
   const bool force_copy = (flags & MALS_INSTALL_COPY) != 0;   // members on the ingest's own device copy too: the ingest may go
-  auto free_p = [](auto*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  };
   // replicas first: validate_columns of the matrix upload checks the column indices against the opposite replica
   for (int sd = 0; sd < 2; ++sd)
     if (g->n_total[sd] < n_rows[sd])
@@ -839,23 +821,22 @@ int mals_ingest_install_group(mals_ingest in, mals_group g, int32_t flags) {
       std::vector<int64_t> local((size_t)(r1 - r0) + 1);
       for (int64_t r = r0; r <= r1; ++r) local[(size_t)(r - r0)] = rp[(size_t)r] - e0;
       GHIP(g, hipSetDevice(mb.device));
-      free_p(mb.d_row_ptr[sd]);
-      free_p(mb.own_col[sd]);
-      free_p(mb.own_val[sd]);
-      GHIP(g, hipMalloc(&mb.d_row_ptr[sd], sizeof(int64_t) * local.size()));
-      GHIP(g, hipMemcpy(mb.d_row_ptr[sd], local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
+      mb.own_col[sd].reset();
+      mb.own_val[sd].reset();
+      GHIP(g, mb.d_row_ptr[sd].alloc(local.size()));
+      GHIP(g, hipMemcpy(mb.d_row_ptr[sd].get(), local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
       const int32_t* col = d_col + e0;
       const float* val = d_val + e0;
       if ((mb.device != in_dev || force_copy) && e1 > e0) {
-        GHIP(g, hipMalloc(&mb.own_col[sd], sizeof(int32_t) * (size_t)(e1 - e0)));
-        GHIP(g, hipMalloc(&mb.own_val[sd], sizeof(float) * (size_t)(e1 - e0)));
-        GHIP(g, hipMemcpyPeerAsync(mb.own_col[sd], mb.device, col, in_dev, sizeof(int32_t) * (size_t)(e1 - e0), mb.compute));
-        GHIP(g, hipMemcpyPeerAsync(mb.own_val[sd], mb.device, val, in_dev, sizeof(float) * (size_t)(e1 - e0), mb.compute));
+        GHIP(g, mb.own_col[sd].alloc((size_t)(e1 - e0)));
+        GHIP(g, mb.own_val[sd].alloc((size_t)(e1 - e0)));
+        GHIP(g, hipMemcpyPeerAsync(mb.own_col[sd].get(), mb.device, col, in_dev, sizeof(int32_t) * (size_t)(e1 - e0), mb.compute));
+        GHIP(g, hipMemcpyPeerAsync(mb.own_val[sd].get(), mb.device, val, in_dev, sizeof(float) * (size_t)(e1 - e0), mb.compute));
         GHIP(g, hipStreamSynchronize(mb.compute));
-        col = mb.own_col[sd];
-        val = mb.own_val[sd];
+        col = mb.own_col[sd].get();
+        val = mb.own_val[sd].get();
       }
-      if (int rc = mals_set_matrix(mb.h, sd, r0, r1 - r0, e1 - e0, mb.d_row_ptr[sd], col, val, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
+      if (int rc = mals_set_matrix(mb.h, sd, r0, r1 - r0, e1 - e0, mb.d_row_ptr[sd].get(), col, val, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
     }
     if (int rc = finish_matrix(g, sd)) return rc;
   }
@@ -874,31 +855,31 @@ int mals_ingest_install_group(mals_ingest in, mals_group g, int32_t flags) {
   }
   for (Member& mb : g->m) {
     GHIP(g, hipSetDevice(mb.device));
-    free_p(mb.own_known_ptr);
-    free_p(mb.own_known_idx);
-    free_p(mb.own_tag_idx);
+    mb.own_known_ptr.reset();
+    mb.own_known_idx.reset();
+    mb.own_tag_idx.reset();
     if (k_ptr) {
       const int64_t r0 = g->bounds[0][(size_t)mb.rank], r1 = g->bounds[0][(size_t)mb.rank + 1];
       const int64_t e0 = kp[(size_t)r0], e1 = kp[(size_t)r1];
       std::vector<int64_t> local((size_t)(r1 - r0) + 1);
       for (int64_t r = r0; r <= r1; ++r) local[(size_t)(r - r0)] = kp[(size_t)r] - e0;
-      GHIP(g, hipMalloc(&mb.own_known_ptr, sizeof(int64_t) * local.size()));
-      GHIP(g, hipMemcpy(mb.own_known_ptr, local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
+      GHIP(g, mb.own_known_ptr.alloc(local.size()));
+      GHIP(g, hipMemcpy(mb.own_known_ptr.get(), local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
       const int32_t* idx = k_idx + e0;
       if ((mb.device != in_dev || force_copy) && e1 > e0) {
-        GHIP(g, hipMalloc(&mb.own_known_idx, sizeof(int32_t) * (size_t)(e1 - e0)));
-        GHIP(g, hipMemcpyPeerAsync(mb.own_known_idx, mb.device, idx, in_dev, sizeof(int32_t) * (size_t)(e1 - e0), mb.compute));
+        GHIP(g, mb.own_known_idx.alloc((size_t)(e1 - e0)));
+        GHIP(g, hipMemcpyPeerAsync(mb.own_known_idx.get(), mb.device, idx, in_dev, sizeof(int32_t) * (size_t)(e1 - e0), mb.compute));
         GHIP(g, hipStreamSynchronize(mb.compute));
-        idx = mb.own_known_idx;
+        idx = mb.own_known_idx.get();
       }
-      if (int rc = mals_set_known_items(mb.h, r1 - r0, mb.own_known_ptr, idx, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
+      if (int rc = mals_set_known_items(mb.h, r1 - r0, mb.own_known_ptr.get(), idx, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
     }
     const int64_t* tags = t_idx;
     if (n_tags > 0 && (mb.device != in_dev || force_copy)) {
-      GHIP(g, hipMalloc(&mb.own_tag_idx, sizeof(int64_t) * (size_t)n_tags));
-      GHIP(g, hipMemcpyPeerAsync(mb.own_tag_idx, mb.device, t_idx, in_dev, sizeof(int64_t) * (size_t)n_tags, mb.compute));
+      GHIP(g, mb.own_tag_idx.alloc((size_t)n_tags));
+      GHIP(g, hipMemcpyPeerAsync(mb.own_tag_idx.get(), mb.device, t_idx, in_dev, sizeof(int64_t) * (size_t)n_tags, mb.compute));
       GHIP(g, hipStreamSynchronize(mb.compute));
-      tags = mb.own_tag_idx;
+      tags = mb.own_tag_idx.get();
     }
     if (int rc = mals_set_tag_items(mb.h, n_tags, tags, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
   }

@@ -14,40 +14,34 @@ struct TopnSlot {
   hipEvent_t ev = nullptr;
   // inputs of the pass: ONE device block, the image of the slot's pinned block (one copy); the pointers below are views
   // into it
-  uint8_t* d_in = nullptr;
-  size_t din_cap = 0;
-  uint8_t* h_in = nullptr;            // pinned input block (offsets, rows, vectors, exclusion lists)
-  size_t in_cap = 0;
+  DeviceBuffer<uint8_t> d_in;
+  PinnedBuffer<uint8_t> h_in;         // input block (offsets, rows, vectors, exclusion lists)
   const float* d_vecs = nullptr;      // [n_vecs][k] (caller's vectors) or X itself (model users: rows d_vrow)
   const int64_t* d_vrow = nullptr;    // vector v = row d_vrow[v] of d_vecs; NULL: row v
   const int32_t* d_vptr = nullptr;    // [nq + 1]
   const int64_t* d_rows = nullptr;    // [nq]: local row of the query's user (known items), -1 = none
   const int64_t* d_excl_ptr = nullptr;
   const int64_t* d_excl_idx = nullptr;
-  float *d_tau = nullptr, *d_bmax = nullptr;  // thresholds; the sample's bucket maxima [queries][16 x TOPN_SAMPLE_GROUPS] ...
-  uint32_t* d_bidx = nullptr;                 // ... and the items that attain them
-  unsigned* d_count = nullptr;
-  uint32_t* d_cand = nullptr;
-  uint64_t* d_pairs = nullptr;
-  void* d_img = nullptr;        // the pass's queries as split bf16 MFMA operands (topn_prepare_kernel)
-  unsigned* d_wcount = nullptr; // hits per wave of the filter kernel, [n_waves] + one overflow word
-  uint2* d_whits = nullptr;     // [n_waves][TOPN_WAVE_CAP] (item, query)
-  size_t wh_cap = 0;
-  size_t cand_cap = 0, pairs_cap = 0;
-  uint8_t* h_stage = nullptr;   // pinned: the pass's results, [nq][how_many] pairs | counts | taus | overflow word (topn_final_kernel
-                                // writes them there), decoded while later passes run
-  size_t stage_cap = 0;
+  DeviceBuffer<float> d_tau, d_bmax;  // thresholds; the sample's bucket maxima [queries][16 x TOPN_SAMPLE_GROUPS] ...
+  DeviceBuffer<uint32_t> d_bidx;      // ... and the items that attain them
+  DeviceBuffer<unsigned> d_count;
+  DeviceBuffer<uint32_t> d_cand;
+  DeviceBuffer<uint64_t> d_pairs;
+  DeviceBuffer<bf16x8> d_img;         // the pass's queries as split bf16 MFMA operands (topn_prepare_kernel)
+  DeviceBuffer<unsigned> d_wcount;    // hits per wave of the filter kernel, [n_waves] + one overflow word
+  DeviceBuffer<uint2> d_whits;        // [n_waves][TOPN_WAVE_CAP] (item, query)
+  PinnedBuffer<uint8_t> h_stage;      // the pass's results, [nq][how_many] pairs | counts | taus | overflow word (topn_final_kernel
+                                      // writes them there), decoded while later passes run
 };
 
 struct TopnWorkspace {
   TopnSlot slot[TOPN_SLOTS];
   hipEvent_t ev_begin = nullptr;  // the caller's stream at the start of the call: every slot stream waits for it
   // dense path
-  float* d_scores = nullptr;
-  uint32_t* d_sel = nullptr;
-  TopnState* d_state = nullptr;
-  unsigned* d_hist = nullptr;
-  size_t scores_cap = 0, sel_cap = 0;
+  DeviceBuffer<float> d_scores;
+  DeviceBuffer<uint32_t> d_sel;
+  DeviceBuffer<TopnState> d_state;
+  DeviceBuffer<unsigned> d_hist;
 };
 
 void topn_free(mals_handle h) {
@@ -55,30 +49,12 @@ void topn_free(mals_handle h) {
   if (!w) return;
   for (TopnSlot& s : w->slot) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
-    free_dev(s.d_in);
-    free_dev(s.d_tau); free_dev(s.d_bmax); free_dev(s.d_bidx); free_dev(s.d_count); free_dev(s.d_cand);
-    free_dev(s.d_pairs); free_dev(s.d_img); free_dev(s.d_wcount); free_dev(s.d_whits);
-    if (s.h_stage) (void)hipHostFree(s.h_stage);
-    if (s.h_in) (void)hipHostFree(s.h_in);
     if (s.ev) (void)hipEventDestroy(s.ev);
     if (s.stream) (void)hipStreamDestroy(s.stream);
   }
   if (w->ev_begin) (void)hipEventDestroy(w->ev_begin);
-  free_dev(w->d_scores); free_dev(w->d_sel); free_dev(w->d_state); free_dev(w->d_hist);
-  delete w;
+  delete w;   // and its buffers
   h->tn_ws = nullptr;
-}
-
-// grow a buffer only `stream` uses
-template <typename P>
-int topn_grow(mals_handle h, hipStream_t stream, P*& p, size_t& cap, size_t want) {
-  if (want <= cap) return MALS_OK;
-  HIPCHK(h, hipStreamSynchronize(stream));  // a pass still in flight may use the old buffer
-  free_dev(p);
-  cap = 0;
-  HIPCHK(h, hipMalloc(&p, sizeof(P) * want));
-  cap = want;
-  return MALS_OK;
 }
 
 struct TopnOut {
@@ -158,27 +134,20 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
                o_eptr = o_uidx + 8 * TOPN_FILTER_QUERIES, o_vecs = o_eptr + 8 * (TOPN_FILTER_QUERIES + 1),
                o_eidx = o_vecs + ((own_vectors ? sizeof(float) * (size_t)ps.n_vecs * (size_t)k : 0) + 15) / 16 * 16,
                total = o_eidx + 8 * (size_t)n_ex;
-  if (total > sl.in_cap) {
-    HIPCHK(h, hipStreamSynchronize(stream));  // an earlier copy may still be reading the old block
-    if (sl.h_in) (void)hipHostFree(sl.h_in);
-    sl.h_in = nullptr;
-    sl.in_cap = 0;
-    HIPCHK(h, hipHostMalloc(&sl.h_in, total + total / 2, hipHostMallocDefault));
-    sl.in_cap = total + total / 2;
-  }
-  if (int rc = topn_grow(h, stream, sl.d_in, sl.din_cap, total + total / 2)) return rc;
-  uint8_t* in = sl.h_in;
+  if (total > sl.h_in.capacity()) HIPCHK(h, sl.h_in.reserve(total + total / 2, stream));  // an earlier copy may still be reading the old block
+  HIPCHK(h, sl.d_in.reserve(total + total / 2, stream));
+  uint8_t* in = sl.h_in.get();
   int32_t* vptr = reinterpret_cast<int32_t*>(in + o_vptr);
   for (int q = 0; q <= ps.nq; ++q) vptr[q] = (rq.user_idx || !rq.vec_ptr) ? q : (int32_t)(rq.vec_ptr[ps.q0 + q] - ps.v0);
   ps.have_rows = ps.have_excl = false;
-  sl.d_vptr = reinterpret_cast<const int32_t*>(sl.d_in + o_vptr);
-  sl.d_rows = reinterpret_cast<const int64_t*>(sl.d_in + o_rows);
-  sl.d_excl_ptr = reinterpret_cast<const int64_t*>(sl.d_in + o_eptr);
-  sl.d_excl_idx = reinterpret_cast<const int64_t*>(sl.d_in + o_eidx);
+  sl.d_vptr = reinterpret_cast<const int32_t*>(sl.d_in.get() + o_vptr);
+  sl.d_rows = reinterpret_cast<const int64_t*>(sl.d_in.get() + o_rows);
+  sl.d_excl_ptr = reinterpret_cast<const int64_t*>(sl.d_in.get() + o_eptr);
+  sl.d_excl_idx = reinterpret_cast<const int64_t*>(sl.d_in.get() + o_eidx);
   if (rq.user_idx) {
     std::memcpy(in + o_uidx, rq.user_idx + ps.q0, sizeof(int64_t) * (size_t)ps.nq);
     sl.d_vecs = x.F;
-    sl.d_vrow = reinterpret_cast<const int64_t*>(sl.d_in + o_uidx);
+    sl.d_vrow = reinterpret_cast<const int64_t*>(sl.d_in.get() + o_uidx);
     if (rq.skip_known || rq.skip_known_q) {
       int64_t* rows = reinterpret_cast<int64_t*>(in + o_rows);
       for (int q = 0; q < ps.nq; ++q)
@@ -187,7 +156,7 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
     }
   } else {
     std::memcpy(in + o_vecs, rq.vectors + ps.v0 * k, sizeof(float) * (size_t)ps.n_vecs * (size_t)k);
-    sl.d_vecs = reinterpret_cast<const float*>(sl.d_in + o_vecs);
+    sl.d_vecs = reinterpret_cast<const float*>(sl.d_in.get() + o_vecs);
     sl.d_vrow = nullptr;
   }
   if (n_ex > 0) {
@@ -196,7 +165,7 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
     std::memcpy(in + o_eidx, rq.excl_idx + rq.excl_ptr[ps.q0], sizeof(int64_t) * (size_t)n_ex);
     ps.have_excl = true;
   }
-  HIPCHK(h, hipMemcpyAsync(sl.d_in, in, total, hipMemcpyHostToDevice, stream));
+  HIPCHK(h, hipMemcpyAsync(sl.d_in.get(), in, total, hipMemcpyHostToDevice, stream));
   return MALS_OK;
 }
 
@@ -222,31 +191,31 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
   const int64_t n_items = y.n_total;
   const int cap_ties = 1024;
   const size_t per_q = 2 * ((size_t)how_many + cap_ties);
-  if (int rc = topn_grow(h, h->stream, w->d_scores, w->scores_cap, (size_t)TOPN_MAX_QUERIES * (size_t)n_items)) return rc;
-  if (int rc = topn_grow(h, h->stream, w->d_sel, w->sel_cap, (size_t)TOPN_MAX_QUERIES * per_q)) return rc;
-  if (!w->d_state) HIPCHK(h, hipMalloc(&w->d_state, sizeof(TopnState) * TOPN_MAX_QUERIES));
-  if (!w->d_hist) HIPCHK(h, hipMalloc(&w->d_hist, sizeof(unsigned) * 256 * TOPN_MAX_QUERIES));
+  HIPCHK(h, w->d_scores.reserve((size_t)TOPN_MAX_QUERIES * (size_t)n_items, h->stream));
+  HIPCHK(h, w->d_sel.reserve((size_t)TOPN_MAX_QUERIES * per_q, h->stream));
+  if (!w->d_state.get()) HIPCHK(h, w->d_state.alloc(TOPN_MAX_QUERIES));
+  if (!w->d_hist.get()) HIPCHK(h, w->d_hist.alloc(256 * TOPN_MAX_QUERIES));
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_items + 63) / 64, (int64_t)h->n_cu * 8));
   hipLaunchKernelGGL(topn_exact_dense_kernel, dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k, sl.d_vecs,
-                     sl.d_vrow, sl.d_vptr, nq, w->d_scores);
+                     sl.d_vrow, sl.d_vptr, nq, w->d_scores.get());
   if (ps.have_rows)
     hipLaunchKernelGGL(topn_mask_kernel, dim3(64, (unsigned)nq), dim3(256), 0, h->stream, h->known_ptr ? h->known_ptr : x.row_ptr,
-                       h->known_ptr ? h->known_idx : x.col, sl.d_rows, nq, 1, n_items, w->d_scores);
+                       h->known_ptr ? h->known_idx : x.col, sl.d_rows, nq, 1, n_items, w->d_scores.get());
   if (ps.have_excl)
     hipLaunchKernelGGL(topn_exclude_kernel, dim3(64, (unsigned)nq), dim3(256), 0, h->stream, sl.d_excl_ptr, sl.d_excl_idx, nq, n_items, 1, n_items,
-                       w->d_scores);
+                       w->d_scores.get());
   if (h->tag_bits)
-    hipLaunchKernelGGL(topn_mask_tags_kernel, dim3((unsigned)(((n_items + 31) / 32 + 255) / 256)), dim3(256), 0, h->stream, h->tag_bits, nq, n_items,
-                       w->d_scores);
+    hipLaunchKernelGGL(topn_mask_tags_kernel, dim3((unsigned)(((n_items + 31) / 32 + 255) / 256)), dim3(256), 0, h->stream, h->tag_bits.get(), nq, n_items,
+                       w->d_scores.get());
   unsigned slabs = 1;
-  if (int rc = topn_select_threshold(h, w->d_scores, n_items, nq, how_many, w->d_state, w->d_hist, &slabs)) return rc;
-  hipLaunchKernelGGL(topn_collect_kernel, dim3(slabs, (unsigned)nq), dim3(256), 0, h->stream, w->d_scores, n_items, w->d_state, how_many, cap_ties,
-                     w->d_sel);
+  if (int rc = topn_select_threshold(h, w->d_scores.get(), n_items, nq, how_many, w->d_state.get(), w->d_hist.get(), &slabs)) return rc;
+  hipLaunchKernelGGL(topn_collect_kernel, dim3(slabs, (unsigned)nq), dim3(256), 0, h->stream, w->d_scores.get(), n_items, w->d_state.get(), how_many, cap_ties,
+                     w->d_sel.get());
   HIPCHK(h, hipGetLastError());
   std::vector<uint32_t> out((size_t)nq * per_q);
   std::vector<TopnState> st((size_t)nq);
-  HIPCHK(h, hipMemcpyAsync(out.data(), w->d_sel, sizeof(uint32_t) * out.size(), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(st.data(), w->d_state, sizeof(TopnState) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out.data(), w->d_sel.get(), sizeof(uint32_t) * out.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(st.data(), w->d_state.get(), sizeof(TopnState) * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   std::vector<float> row;
   std::vector<TopnCand> cand;
@@ -260,7 +229,7 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
       // more ties at the N-th score than the selection buffer holds (e.g. a block of identical items): which of
       // them have the lowest indices is not known from an unordered subset -- resolve this query from its score row
       row.resize((size_t)n_items);
-      HIPCHK(h, hipMemcpy(row.data(), w->d_scores + (size_t)q * (size_t)n_items, sizeof(float) * (size_t)n_items, hipMemcpyDeviceToHost));
+      HIPCHK(h, hipMemcpy(row.data(), w->d_scores.get() + (size_t)q * (size_t)n_items, sizeof(float) * (size_t)n_items, hipMemcpyDeviceToHost));
       const uint32_t ninf = score_key(-std::numeric_limits<float>::infinity());
       for (int64_t i = 0; i < n_items; ++i) {
         const uint32_t kk = score_key(row[(size_t)i]);
@@ -307,14 +276,12 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(stages, MODE == 0 ? TOPN_SAMPLE_GROUPS : (int64_t)h->n_cu * per_cu));
   if (MODE == 1) {
     const size_t nw = (size_t)grid * 4;
-    if (nw * TOPN_WAVE_CAP > sl.wh_cap) {
+    if (nw * TOPN_WAVE_CAP > sl.d_whits.capacity() || nw + 1 > sl.d_wcount.capacity()) {
       HIPCHK(h, hipStreamSynchronize(sl.stream));
-      free_dev(sl.d_whits);
-      free_dev(sl.d_wcount);
-      sl.wh_cap = 0;
-      HIPCHK(h, hipMalloc(&sl.d_whits, sizeof(uint2) * nw * TOPN_WAVE_CAP));
-      HIPCHK(h, hipMalloc(&sl.d_wcount, sizeof(unsigned) * (nw + 1)));
-      sl.wh_cap = nw * TOPN_WAVE_CAP;
+      sl.d_whits.reset();
+      sl.d_wcount.reset();
+      HIPCHK(h, sl.d_whits.alloc(nw * TOPN_WAVE_CAP));
+      HIPCHK(h, sl.d_wcount.alloc(nw + 1));
     }
     *n_out = (int)nw;
   } else {
@@ -322,8 +289,8 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   }
 #define MALS_TOPN_GO(LM)                                                                                                              \
   hipLaunchKernelGGL((topn_stream_kernel<S, QT, MODE, LM>), dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k,                           \
-                     static_cast<const bf16x8*>(sl.d_img), nq, tile_stride, sl.d_bmax, sl.d_bidx, sl.d_tau, TOPN_WAVE_CAP, sl.d_wcount,   \
-                     sl.d_whits, cap, sl.d_count, sl.d_cand, sl.d_count + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE)
+                     sl.d_img.get(), nq, tile_stride, sl.d_bmax.get(), sl.d_bidx.get(), sl.d_tau.get(), TOPN_WAVE_CAP, sl.d_wcount.get(),   \
+                     sl.d_whits.get(), cap, sl.d_count.get(), sl.d_cand.get(), sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE)
   if (lm == 1) MALS_TOPN_GO(1);
   else if (lm == 2) MALS_TOPN_GO(2);
   else if (lm == 3) MALS_TOPN_GO(3);
@@ -389,7 +356,7 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
   const int64_t n_items = y.n_total;
   const int nt = (nq + 15) / 16;
   hipStream_t st = sl.stream;
-  unsigned* d_overflow = sl.d_count + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE;
+  unsigned* d_overflow = sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE;
   const int64_t* d_rows = ps.have_rows ? sl.d_rows : nullptr;
   const int64_t* k_ptr = h->known_ptr ? h->known_ptr : x.row_ptr;   // knownItemIDs if the caller installed them, else the rows of R
   const int32_t* k_idx = h->known_ptr ? h->known_idx : x.col;
@@ -397,23 +364,23 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
   const int64_t* d_eidx = ps.have_excl ? sl.d_excl_idx : nullptr;
   // 0. the queries as matrix operands (every tile an instantiation may touch: padding queries never produce a hit)
   hipLaunchKernelGGL(topn_prepare_kernel, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
-                     static_cast<bf16x8*>(sl.d_img), sl.d_count, d_overflow);
+                     sl.d_img.get(), sl.d_count.get(), d_overflow);
   // 1. sample: bucket maxima of the lower bounds of every tile_stride-th tile; 2. threshold (buckets won by known items dropped)
   int n_groups = 0, n_fw = 0;
   if (int rc = topn_launch_stream<0>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)) return rc;
-  hipLaunchKernelGGL(topn_threshold_kernel, dim3((unsigned)nq), dim3(1024), 0, st, sl.d_bmax, sl.d_bidx, n_groups, how_many, k_ptr, k_idx, d_rows,
-                     d_eptr, d_eidx, n_items, p.tile_stride, h->tag_bits, sl.d_tau);
+  hipLaunchKernelGGL(topn_threshold_kernel, dim3((unsigned)nq), dim3(1024), 0, st, sl.d_bmax.get(), sl.d_bidx.get(), n_groups, how_many, k_ptr, k_idx, d_rows,
+                     d_eptr, d_eidx, n_items, p.tile_stride, h->tag_bits.get(), sl.d_tau.get());
   // 3. filter, 4. exact scores of the hits (known items dropped), 5. the N best -- written straight into the slot's pinned
   // block (device-visible host memory: no copy kernel, no copy call)
   // (the filter's waves scatter their own hits into the per-query candidate lists: no kernel in between)
   if (int rc = topn_launch_stream<1>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)) return rc;
-  hipLaunchKernelGGL(topn_rescore_kernel, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr, sl.d_count, p.cap,
-                     sl.d_cand, k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits, sl.d_pairs, d_overflow);
-  uint8_t* o = sl.h_stage;
+  hipLaunchKernelGGL(topn_rescore_kernel, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr, sl.d_count.get(), p.cap,
+                     sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow);
+  uint8_t* o = sl.h_stage.get();
   const size_t o_cnt = sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many, o_tau = o_cnt + sizeof(unsigned) * TOPN_FILTER_QUERIES,
                o_ovf = o_tau + sizeof(float) * TOPN_FILTER_QUERIES;
-  hipLaunchKernelGGL(topn_final_kernel, dim3((unsigned)nq), dim3(256), sizeof(uint64_t) * (size_t)p.cap, st, sl.d_pairs, sl.d_count, p.cap,
-                     how_many, reinterpret_cast<uint64_t*>(o), reinterpret_cast<unsigned*>(o + o_cnt), sl.d_tau, reinterpret_cast<float*>(o + o_tau),
+  hipLaunchKernelGGL(topn_final_kernel, dim3((unsigned)nq), dim3(256), sizeof(uint64_t) * (size_t)p.cap, st, sl.d_pairs.get(), sl.d_count.get(), p.cap,
+                     how_many, reinterpret_cast<uint64_t*>(o), reinterpret_cast<unsigned*>(o + o_cnt), sl.d_tau.get(), reinterpret_cast<float*>(o + o_tau),
                      d_overflow, reinterpret_cast<unsigned*>(o + o_ovf));
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
@@ -422,15 +389,15 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
 // enqueue one pass on its slot's stream; its results land in the slot's pinned block behind the slot's event
 int topn_pass_filter_enqueue(mals_handle h, TopnSlot& sl, const TopnRequest& rq, const TopnPass& ps, const TopnFilterPlan& p) {
   hipStream_t st = sl.stream;
-  if (!sl.d_tau) {
-    HIPCHK(h, hipMalloc(&sl.d_tau, sizeof(float) * TOPN_FILTER_QUERIES));
-    HIPCHK(h, hipMalloc(&sl.d_count, sizeof(unsigned) * (TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE + 1)));  // padded counters, then the overflow word
-    HIPCHK(h, hipMalloc(&sl.d_img, (size_t)16 * 5 * 64 * 16));
-    HIPCHK(h, hipMalloc(&sl.d_bmax, sizeof(float) * TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
-    HIPCHK(h, hipMalloc(&sl.d_bidx, sizeof(uint32_t) * TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
+  if (!sl.d_bidx.get()) {   // (the last of them: all five exist)
+    HIPCHK(h, sl.d_tau.alloc(TOPN_FILTER_QUERIES));
+    HIPCHK(h, sl.d_count.alloc(TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE + 1));  // padded counters, then the overflow word
+    HIPCHK(h, sl.d_img.alloc((size_t)16 * 5 * 64));
+    HIPCHK(h, sl.d_bmax.alloc(TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
+    HIPCHK(h, sl.d_bidx.alloc(TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
   }
-  if (int rc = topn_grow(h, st, sl.d_pairs, sl.pairs_cap, (size_t)TOPN_FILTER_QUERIES * (size_t)p.cap)) return rc;
-  if (int rc = topn_grow(h, st, sl.d_cand, sl.cand_cap, (size_t)TOPN_FILTER_QUERIES * (size_t)p.cap)) return rc;
+  HIPCHK(h, sl.d_pairs.reserve((size_t)TOPN_FILTER_QUERIES * (size_t)p.cap, st));
+  HIPCHK(h, sl.d_cand.reserve((size_t)TOPN_FILTER_QUERIES * (size_t)p.cap, st));
   // (one graph launch per pass instead of nine kernel launches was tried: no faster -- the device, not the host's launch
   // calls, sets the pace even at 64 queries per pass)
   if (int rc = topn_pass_filter_launch(h, sl, rq, ps, p)) return rc;
@@ -444,7 +411,7 @@ int topn_pass_filter_finish(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
                             std::vector<uint8_t>& failed, bool* any_failed) {
   HIPCHK(h, hipEventSynchronize(sl.ev));
   const int how_many = rq.how_many;
-  const uint8_t* st = sl.h_stage;
+  const uint8_t* st = sl.h_stage.get();
   const uint64_t* outp = reinterpret_cast<const uint64_t*>(st);
   const unsigned* count = reinterpret_cast<const unsigned*>(st + sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many);
   const float* tau = reinterpret_cast<const float*>(st + sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many + sizeof(unsigned) * TOPN_FILTER_QUERIES);
@@ -488,14 +455,7 @@ int topn_prepare_slots(mals_handle h, TopnWorkspace* w, const TopnFilterPlan& p)
   for (TopnSlot& sl : w->slot) {
     if (!sl.stream) HIPCHK(h, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
     if (!sl.ev) HIPCHK(h, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    if (sl.stage_cap < p.stage_bytes) {
-      HIPCHK(h, hipStreamSynchronize(sl.stream));
-      if (sl.h_stage) (void)hipHostFree(sl.h_stage);
-      sl.h_stage = nullptr;
-      sl.stage_cap = 0;
-      HIPCHK(h, hipHostMalloc(&sl.h_stage, p.stage_bytes, hipHostMallocDefault));
-      sl.stage_cap = p.stage_bytes;
-    }
+    HIPCHK(h, sl.h_stage.reserve(p.stage_bytes, sl.stream));
   }
   if (!w->ev_begin) HIPCHK(h, hipEventCreateWithFlags(&w->ev_begin, hipEventDisableTiming));
   return MALS_OK;

@@ -1,0 +1,107 @@
+"""Device memory the native library allocates is released: on an error return (an allocation that fails halfway through
+a growth leaves nothing behind) and at the end of every object's life (create / use / destroy cycles of a handle, an
+ingest and a group come back to the free memory they started from).  Free memory is read with torch.cuda.mem_get_info
+while no torch tensor is alive; the tolerance is 1 GiB because the device may be shared."""
+import numpy as np
+import pytest
+import torch
+
+import myrrix_recommender_amd as pkg
+from myrrix_recommender_amd import _lib, ingest, synth
+from myrrix_recommender_amd.core import MalsError
+
+pytestmark = pytest.mark.gpu
+
+GiB = 1 << 30
+TOL = 1 * GiB
+CYCLES = 3
+
+
+def free_bytes(devices):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    return {d: torch.cuda.mem_get_info(d)[0] for d in devices}
+
+
+def assert_back_at(base, what):
+    now = free_bytes(base.keys())
+    for d, b in base.items():
+        assert b - now[d] < TOL, "%s: %.2f GiB of device %d not released" % (what, (b - now[d]) / GiB, d)
+
+
+def small_text(seed):
+    rng = np.random.default_rng(seed)
+    u, i = rng.integers(0, 300, 4000), rng.integers(0, 200, 4000)
+    return "".join("%d,%d,%d\n" % (a, b, c) for a, b, c in zip(u, i, rng.integers(1, 4, 4000))).encode()
+
+
+def ingest_text_cycle(g, seed):
+    g.append_text(small_text(seed), True)
+    g.finish()
+    c = g.counts()
+    assert c["records"] > 0 and c["nnz"] > 0
+
+
+def test_record_growth_out_of_memory_leaves_nothing_behind():
+    with ingest.Ingest(0) as g:   # the ingest's first use below: warm up the runtime outside the measured window
+        ingest_text_cycle(g, 0)
+    base = free_bytes([0])
+    n = int(0.6 * base[0] / 8)   # the first int64 record array fits, the second does not
+    with ingest.Ingest(0) as g:
+        with pytest.raises(MalsError) as e:
+            g.set_option(_lib.INGEST_OPT_RESERVE_RECORDS, n)
+        assert e.value.status == _lib.OOM, e.value
+        assert_back_at(base, "failed record growth")
+        ingest_text_cycle(g, 1)   # the same ingest still works
+    assert_back_at(base, "ingest after a failed record growth")
+
+
+def handle_cycle(seed):
+    k, n_users, n_items = 64, 600, 140000   # enough items for the filter path of top-N
+    r_csr, c_csr, Y0 = synth.numpy_problem(n_users, n_items, 20000, k, seed=seed)
+    rng = np.random.default_rng(seed)
+    with pkg.ALSCore(k, solve_mode=_lib.SOLVE_DUAL) as core:
+        core.set_factor_rows(pkg.SIDE_X, n_users)
+        core.set_factor_rows(pkg.SIDE_Y, n_items)
+        core.set_matrix(pkg.SIDE_X, *r_csr)
+        core.set_matrix(pkg.SIDE_Y, *c_csr)
+        core.set_factors(pkg.SIDE_Y, Y0)
+        tu = rng.choice(n_users, 50, replace=False).astype(np.int64)
+        ti = rng.choice(n_items, 50, replace=False).astype(np.int64)
+        iters, _ = core.factorize(0.001, 3, False, tu, ti)
+        assert iters >= 1
+        core.set_known_items(*r_csr[:2])
+        X = core.get_factors(pkg.SIDE_X)
+        idx, _, cnt = core.recommend_to_many([X[q:q + 2] for q in range(0, 40, 2)], 10)
+        assert np.all(cnt == 10) and np.all(idx >= 0)
+        core.set_known_items(None, None)
+
+
+def group_cycle(devices, seed):
+    k, n_users, n_items = 64, 2500, 700
+    r_csr, c_csr, Y0 = synth.numpy_problem(n_users, n_items, 30000, k, seed=seed)
+    with pkg.GroupALS.single_process(k, devices, backend=_lib.GROUP_PEER_COPY) as g:
+        g.set_factor_rows(pkg.SIDE_X, n_users)
+        g.set_factor_rows(pkg.SIDE_Y, n_items)
+        g.set_matrix(pkg.SIDE_X, *r_csr)
+        g.set_matrix(pkg.SIDE_Y, *c_csr)
+        g.set_factors(pkg.SIDE_Y, Y0)
+        g.iterate(2)
+
+
+def test_create_use_destroy_cycles_return_to_the_baseline():
+    devices = [0, 1] if torch.cuda.device_count() > 1 else [0, 0]
+    used = sorted(set(devices))
+    handle_cycle(10)   # warm-up: code objects, runtime state
+    with ingest.Ingest(0) as g:
+        ingest_text_cycle(g, 10)
+    group_cycle(devices, 10)
+    base = free_bytes(used)
+    for c in range(CYCLES):
+        handle_cycle(11 + c)
+        assert_back_at(base, "handle cycle %d" % c)
+        with ingest.Ingest(0) as g:
+            ingest_text_cycle(g, 11 + c)
+        assert_back_at(base, "ingest cycle %d" % c)
+        group_cycle(devices, 11 + c)
+        assert_back_at(base, "group cycle %d" % c)
