@@ -449,7 +449,11 @@ int mals_ingest_partitions(mals_ingest g, int32_t* user_ranges, int32_t* item_ra
  * 2^31 - 256 records; beyond, ranges as large as 70 % of the device's free memory hold at 76 bytes per record (at least
  * 2^26) -- which is how C5's 5e9 lines fit one 288 GB device next to their 120 GB of records.  (Tests set a few hundred
  * to run the oracle suites through the partitioned path.) */
-enum { MALS_INGEST_OPT_KNOWN_ITEMS = 1, MALS_INGEST_OPT_TEXT_BLOCK_BYTES = 2, MALS_INGEST_OPT_RESERVE_RECORDS = 3, MALS_INGEST_OPT_PARTITION_RECORDS = 4 };
+/* SHARE (set before the first append): which piece of a stream ingested by a group this ingest holds (0 = default = the
+ * stream's start; mals_group_ingest_finish).  A share > 0 takes an unparseable first line as a header CANDIDATE: the group
+ * finish counts it as the header when every earlier share is empty, as a bad line otherwise. */
+enum { MALS_INGEST_OPT_KNOWN_ITEMS = 1, MALS_INGEST_OPT_TEXT_BLOCK_BYTES = 2, MALS_INGEST_OPT_RESERVE_RECORDS = 3, MALS_INGEST_OPT_PARTITION_RECORDS = 4,
+       MALS_INGEST_OPT_SHARE = 5 };
 enum { MALS_ITEM_TAG_IDS = 0, MALS_USER_TAG_IDS = 1 };
 int mals_ingest_set_option(mals_ingest g, int32_t option, int64_t value);
 int mals_ingest_append_text(mals_ingest g, const void* bytes, int64_t n_bytes, int mem_kind, int32_t end_of_file);
@@ -460,6 +464,11 @@ int mals_ingest_read_file(mals_ingest g, const char* path);
 /* IFR:71-86: the files of input_dir matching .+\.csv(\.(zip|gz))? in ascending last-modified order (equal
  * timestamps: by name; the reference leaves that order to File.listFiles()).  A missing directory reads nothing. */
 int mals_ingest_read_dir(mals_ingest g, const char* input_dir, int32_t* n_files_read);
+/* Share `share` of n_shares (<= 256) of the stream mals_ingest_read_dir reads (same files, same order), cut into pieces of
+ * about equal on-disk bytes: the shares concatenated in index order are that stream.  A cut moves forward to the next line
+ * start of a plain file (byte 0, after '\n', after a '\r' no '\n' follows); a .gz / .zip file goes whole to the share in
+ * which its first byte falls.  A share may be empty.  Sets MALS_INGEST_OPT_SHARE. */
+int mals_ingest_read_dir_share(mals_ingest g, const char* input_dir, int32_t share, int32_t n_shares, int32_t* n_files_read);
 typedef struct mals_ingest_text_info_t {
   int32_t struct_size; /* sizeof(mals_ingest_text_info_t) */
   int32_t reserved;
@@ -633,11 +642,33 @@ int mals_group_pending_entries(mals_group g, int side, int64_t n_rows, int64_t* 
  * hipMemcpyPeerAsync into arrays the group owns otherwise -- together with its slice of knownItemIDs (when the ingest built
  * them) and the userTagIDs item mask.  Factor rows of both sides are declared from the ingest's counts (n_users, n_items)
  * unless already declared at least that large.  In a one-process-per-GPU group every rank calls this with its OWN ingest of
- * the same input (collective like mals_group_set_matrix).  flags = 0: the ingest must outlive the group's use of the
+ * the same input (collective like mals_group_set_matrix); mals_group_ingest_finish is the other way, in which every rank
+ * ingests only its share of the input.  flags = 0: the ingest must outlive the group's use of the
  * borrowed slices; MALS_INSTALL_COPY: members on the ingest's device copy their slices too (8 bytes per entry and side more
  * on that device) and the ingest -- its records and its 52 bytes per record of workspace -- can be destroyed right away. */
 enum { MALS_INSTALL_COPY = 1 };
 int mals_ingest_install_group(mals_ingest g, mals_group grp, int32_t flags);
+/* The sharded ingest, the path that never holds the whole input on one device: ingests[i] holds share `rank of local member
+ * i` of the stream (MALS_INGEST_OPT_SHARE / mals_ingest_read_dir_share) on that member's device; n_local = the group's local
+ * members.  Collective (RCCL: all-reduces and grouped send/recv only; or MALS_GROUP_PEER_COPY), every rank returns the same
+ * status: the text counters are combined in share order (header, bad lines, the abort after the 101st bad line, the
+ * lone-quote error), the records go to the rank that owns their user (user-id ranges from a sample of every share), every rank
+ * finishes its users like mals_ingest_finish would, the item and id tables are merged, and R^T's rows go to the rank that owns
+ * their item (mals_plan_shards on the global entry counts).  The X bounds of the group are the user ranges, the Y bounds the
+ * item ranges.  Records and workspace are released before the factor replicas are declared; each ingest then holds its
+ * member's slices of R, R^T (global column indices) and knownItemIDs, the userTagIDs mask and both full id tables, which the
+ * members borrow (the ingests must outlive their use).  Afterwards mals_ingest_counts reports the global counts (n_records:
+ * the records this rank finished), mals_ingest_get_ids / mals_ingest_text_info the global tables and counters, and
+ * mals_ingest_get_csr / _device_csr / _get_known_items this member's slice (mals_ingest_slice).  flags: reserved, 0. */
+int mals_group_ingest_finish(mals_group grp, mals_ingest* ingests, int32_t n_local, int32_t flags);
+/* Which rows of `side` the ingest's CSR holds: [*row_begin, *row_begin + *n_rows) -- all of them after mals_ingest_finish,
+ * the member's slice after mals_group_ingest_finish. */
+int mals_ingest_slice(mals_ingest g, int side, int64_t* row_begin, int64_t* n_rows);
+/* Device bytes the ingest holds: work (records, text buffers, workspace) and results (CSRs, tables, knownItemIDs); the work
+ * bytes it still held when mals_group_ingest_finish declared the factor replicas (-1: not through a group finish); and the
+ * time and memory traffic of the split kernels (count + scatter: 50 B per record moved) of the last group finish. */
+int mals_ingest_memory(mals_ingest g, int64_t* work_bytes, int64_t* result_bytes, int64_t* work_bytes_at_replicas, double* split_ms,
+                       double* split_bytes);
 /* ServerRecommender.recommend for model users on a group (arguments as mals_recommend): every member holds complete replicas
  * of X and Y but only ITS users' rows of R / knownItemIDs, so a query is answered by the local member whose slice holds the
  * user's row (consider_known_items: by any local member).  Callable from any number of request threads like mals_recommend:

@@ -16,7 +16,7 @@ GRAMIAN_AUTO, GRAMIAN_FP32, GRAMIAN_SPLIT_F16, GRAMIAN_SPLIT3_F16 = 0, 1, 2, 3
 SOLVE_AUTO, SOLVE_DIRECT, SOLVE_DUAL = 0, 1, 2
 ABI_VERSION = 5
 GROUP_RCCL, GROUP_PEER_COPY = 0, 1
-INGEST_OPT_KNOWN_ITEMS, INGEST_OPT_TEXT_BLOCK_BYTES, INGEST_OPT_RESERVE_RECORDS, INGEST_OPT_PARTITION_RECORDS = 1, 2, 3, 4
+INGEST_OPT_KNOWN_ITEMS, INGEST_OPT_TEXT_BLOCK_BYTES, INGEST_OPT_RESERVE_RECORDS, INGEST_OPT_PARTITION_RECORDS, INGEST_OPT_SHARE = 1, 2, 3, 4, 5
 ITEM_TAG_IDS, USER_TAG_IDS = 0, 1
 INSTALL_COPY = 1
 
@@ -175,6 +175,11 @@ SYMBOLS = {
     "mals_ingest_append_text": (ctypes.c_int, [_H, _P, _I64, ctypes.c_int, _I32]),
     "mals_ingest_read_file": (ctypes.c_int, [_H, ctypes.c_char_p]),
     "mals_ingest_read_dir": (ctypes.c_int, [_H, ctypes.c_char_p, ctypes.POINTER(_I32)]),
+    "mals_ingest_read_dir_share": (ctypes.c_int, [_H, ctypes.c_char_p, _I32, _I32, ctypes.POINTER(_I32)]),
+    "mals_group_ingest_finish": (ctypes.c_int, [_H, _P, _I32, _I32]),
+    "mals_ingest_slice": (ctypes.c_int, [_H, ctypes.c_int, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "mals_ingest_memory": (ctypes.c_int, [_H, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(ctypes.c_double)]),
     "mals_ingest_text_info": (ctypes.c_int, [_H, ctypes.POINTER(IngestTextInfo)]),
     "mals_ingest_get_tag_ids": (ctypes.c_int, [_H, _I32, _P]),
     "mals_ingest_get_known_items": (ctypes.c_int, [_H, _P, _P]),

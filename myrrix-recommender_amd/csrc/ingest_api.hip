@@ -5,6 +5,7 @@
 #include "ingest_kernels.h"
 #include "ingest_text_kernels.h"
 #include "hip_buffer.h"
+#include "mals_internal.h"
 
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
+#include <limits>
 #include <new>
 #include <string>
 #include <vector>
@@ -22,6 +25,7 @@ using namespace mals;
 
 constexpr int64_t MALS_INGEST_MAX_RECORDS = (int64_t)1 << 36;       // (the record arrays alone are 1.6 TB there)
 constexpr int64_t MALS_INGEST_ONE_SHOT_MAX = (int64_t)0x7fffff00;   // what one sort pipeline holds (32-bit positions)
+constexpr int64_t MALS_SPLIT_MAX_SHARES = 256;                      // the split kernel's byte-wide destination (split_kernels.h)
 constexpr int64_t MALS_INGEST_MIN_PART = (int64_t)1 << 26;          // smallest user range the automatic choice makes (ingest_big_host.h)
 
 struct mals_ingest_s {
@@ -81,6 +85,16 @@ struct mals_ingest_s {
   DeviceBuffer<int64_t> tag_item_idx;  // dense item index of every userTagID (ascending ids), -1: the tag owns no row of R^T
   int64_t part_cap = 0;       // MALS_INGEST_OPT_PARTITION_RECORDS (0: default) -- ingest_big_host.h
   int32_t last_partitions = 0, last_item_ranges = 0;
+  // ---- one share of a stream ingested by a group (MALS_INGEST_OPT_SHARE, ingest_group_host.h) ----
+  int32_t share = 0;
+  std::vector<int64_t> bad_pos;   // line number (1-based, in this share) of each of the first 101 bad lines
+  int64_t fatal_line = 0;         // line (1-based, in this share) of a lone-quote token, 0: none
+  bool sharded = false;           // the results are this member's slices (mals_group_ingest_finish)
+  int64_t shard_records = 0;     // records this member finished in the group finish (its records are released afterwards)
+  bool spent = false;             // its records went into a group finish (which then failed, or left slices): no append / finish
+  int64_t work_at_replicas = -1;  // work bytes held when the group declared its factor replicas (-1: not in a group finish)
+  int64_t slice_begin[2] = {0, 0}, slice_rows[2] = {0, 0}, slice_nnz[2] = {0, 0};
+  double split_ms = 0.0, split_bytes = 0.0;   // the split kernels of the last group finish
 };
 
 namespace {
@@ -193,6 +207,7 @@ void free_results(mals_ingest g) {
   g->tag_item_idx.reset();
   g->n_known = 0;
   g->finished = false;
+  g->sharded = false;
   g->n_users = g->n_items = g->nnz = 0;
 }
 
@@ -253,6 +268,7 @@ int mals_ingest_append(mals_ingest g, int64_t n, const int64_t* user_ids, const 
   if (!g) return MALS_INVALID_ARG;
   if (n < 0 || (n > 0 && (!user_ids || !item_ids || !values))) return fail(g, MALS_INVALID_ARG, "bad record arrays");
   if (mem_kind != MALS_MEM_HOST && mem_kind != MALS_MEM_DEVICE) return fail(g, MALS_INVALID_ARG, "mem_kind must be MALS_MEM_HOST or MALS_MEM_DEVICE");
+  if (g->spent) return fail(g, MALS_INVALID_ARG, "the ingest's records went into mals_group_ingest_finish: create a new ingest");
   if (g->n + n >= MALS_INGEST_MAX_RECORDS) return fail(g, MALS_INVALID_ARG, "at most 2^36 records per ingest");
   if (n == 0) return MALS_OK;
   ICHK(g, hipSetDevice(g->device));
@@ -533,6 +549,7 @@ extern "C" {
 
 int mals_ingest_finish(mals_ingest g) {
   if (!g) return MALS_INVALID_ARG;
+  if (g->spent) return fail(g, MALS_INVALID_ARG, "the ingest's records went into mals_group_ingest_finish: create a new ingest");
   if (g->text_failed) return fail(g, g->text_fail_code, g->text_fail_msg);
   if (g->carry_len) return fail(g, MALS_INVALID_ARG, "text pending: the last mals_ingest_append_text of a file must say end_of_file");
   ICHK(g, hipSetDevice(g->device));
@@ -563,7 +580,7 @@ int mals_ingest_finish(mals_ingest g) {
 
 int mals_ingest_counts(mals_ingest g, int64_t* n_records, int64_t* n_users, int64_t* n_items, int64_t* nnz) {
   if (!g) return MALS_INVALID_ARG;
-  if (n_records) *n_records = g->n;
+  if (n_records) *n_records = g->sharded ? g->shard_records : g->n;
   if (!g->finished && (n_users || n_items || nnz)) return fail(g, MALS_INVALID_ARG, "mals_ingest_finish has not run");
   if (n_users) *n_users = g->n_users;
   if (n_items) *n_items = g->n_items;
@@ -586,10 +603,11 @@ int mals_ingest_get_csr(mals_ingest g, int side, int64_t* host_row_ptr, int32_t*
   if (side != MALS_SIDE_X && side != MALS_SIDE_Y) return fail(g, MALS_INVALID_ARG, "side must be MALS_SIDE_X or _Y");
   if (!g->finished) return fail(g, MALS_INVALID_ARG, "mals_ingest_finish has not run");
   ICHK(g, hipSetDevice(g->device));
-  const int64_t rows = side == MALS_SIDE_X ? g->n_users : g->n_items;
+  const int64_t rows = g->sharded ? g->slice_rows[side] : side == MALS_SIDE_X ? g->n_users : g->n_items;
+  const int64_t nnz = g->sharded ? g->slice_nnz[side] : g->nnz;
   if (host_row_ptr) ICHK(g, hipMemcpy(host_row_ptr, g->ptr[side].get(), sizeof(int64_t) * (size_t)(rows + 1), hipMemcpyDeviceToHost));
-  if (host_col_idx && g->nnz) ICHK(g, hipMemcpy(host_col_idx, g->col[side].get(), sizeof(int32_t) * (size_t)g->nnz, hipMemcpyDeviceToHost));
-  if (host_val && g->nnz) ICHK(g, hipMemcpy(host_val, g->val[side].get(), sizeof(float) * (size_t)g->nnz, hipMemcpyDeviceToHost));
+  if (host_col_idx && nnz) ICHK(g, hipMemcpy(host_col_idx, g->col[side].get(), sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
+  if (host_val && nnz) ICHK(g, hipMemcpy(host_val, g->val[side].get(), sizeof(float) * (size_t)nnz, hipMemcpyDeviceToHost));
   return MALS_OK;
 }
 
@@ -606,6 +624,7 @@ int mals_ingest_device_csr(mals_ingest g, int side, const int64_t** row_ptr, con
 int mals_ingest_install(mals_ingest g, mals_handle h) {
   if (!g || !h) return MALS_INVALID_ARG;
   if (!g->finished) return fail(g, MALS_INVALID_ARG, "mals_ingest_finish has not run");
+  if (g->sharded || g->spent) return fail(g, MALS_INVALID_ARG, "the ingest holds one member's slices (mals_group_ingest_finish)");
   if (int rc = mals_set_matrix(h, MALS_SIDE_X, 0, g->n_users, g->nnz, g->ptr[0].get(), g->col[0].get(), g->val[0].get(), MALS_MEM_DEVICE))
     return fail(g, rc, mals_last_error(h));
   if (int rc = mals_set_matrix(h, MALS_SIDE_Y, 0, g->n_items, g->nnz, g->ptr[1].get(), g->col[1].get(), g->val[1].get(), MALS_MEM_DEVICE))
@@ -667,3 +686,4 @@ int mals_ingest_stats(mals_ingest g, double* finish_ms, double* workspace_ms, do
 }  // extern "C"
 
 #include "ingest_text_host.h"
+#include "ingest_group_host.h"

@@ -127,17 +127,25 @@ int process_text_region(mals_ingest g, size_t region) {
   if (int rc = seg_end()) return rc;
   c.records = n_records;
   // 4. the sequential part of the contract
-  if (c.fatal || g->bad_lines + (int64_t)c.bad > 100) {
+  //    (the line numbers of the first 101 bad lines are kept: a group finish places the abort in the whole stream.  Any ingest
+  //    may be share 0 of a group, so every one keeps them: one copy of the block's status bytes to the host per block with a
+  //    bad line, until 101 bad lines are seen -- at most 101 copies of L bytes per ingest)
+  const bool want_pos = c.bad && g->bad_pos.size() < 101;
+  if (c.fatal || g->bad_lines + (int64_t)c.bad > 100 || want_pos) {
     std::vector<uint8_t> st(L);
     ICHK(g, hipMemcpy(st.data(), g->t_status.get(), L, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < L && g->bad_pos.size() < 101; ++i)
+      if ((st[i] & 15) == text::ST_BAD) g->bad_pos.push_back(g->lines + (int64_t)i + 1);
     int64_t bad = g->bad_lines;
-    for (size_t i = 0; i < L; ++i) {
+    for (size_t i = 0; i < L && (c.fatal || g->bad_lines + (int64_t)c.bad > 100); ++i) {
       if (bad > 100) return text_fail(g, MALS_IO_ERROR, "Too many bad lines; aborting");
       const int k = st[i] & 15;
-      if (k == text::ST_FATAL)
+      if (k == text::ST_FATAL) {
+        g->fatal_line = g->lines + (int64_t)i + 1;
         return text_fail(g, MALS_INVALID_ARG,
                          "line " + std::to_string(g->lines + (int64_t)i + 1) +
                              ": a token that is a lone '\"' (the reference throws StringIndexOutOfBoundsException here)");
+      }
       if (k == text::ST_BAD) ++bad;
     }
   }
@@ -278,6 +286,7 @@ extern "C" {
 
 int mals_ingest_set_option(mals_ingest g, int32_t option, int64_t value) {
   if (!g) return MALS_INVALID_ARG;
+  if (g->spent) return fail(g, MALS_INVALID_ARG, "the ingest's records went into mals_group_ingest_finish: create a new ingest");
   switch (option) {
     case MALS_INGEST_OPT_KNOWN_ITEMS:
       g->want_known = value != 0;
@@ -291,6 +300,11 @@ int mals_ingest_set_option(mals_ingest g, int32_t option, int64_t value) {
       if (value != 0 && (value < 64 || value > MALS_INGEST_ONE_SHOT_MAX)) return fail(g, MALS_INVALID_ARG, "partition records: 0 (default) or 64 .. 2^31 - 256");
       g->part_cap = value;
       return MALS_OK;
+    case MALS_INGEST_OPT_SHARE:
+      if (value < 0 || value >= MALS_SPLIT_MAX_SHARES) return fail(g, MALS_INVALID_ARG, "share: 0 .. 255");
+      if (g->n || g->lines || g->text_bytes || g->carry_len) return fail(g, MALS_INVALID_ARG, "the share is set before the first append");
+      g->share = (int32_t)value;
+      return MALS_OK;
     case MALS_INGEST_OPT_TEXT_BLOCK_BYTES:
       if (value < 1 || value > (int64_t)1 << 31) return fail(g, MALS_INVALID_ARG, "text block: 1 byte .. 2 GiB");
       g->text_block_bytes = (size_t)value;
@@ -302,6 +316,7 @@ int mals_ingest_set_option(mals_ingest g, int32_t option, int64_t value) {
 
 int mals_ingest_append_text(mals_ingest g, const void* bytes, int64_t n_bytes, int mem_kind, int32_t end_of_file) {
   if (!g) return MALS_INVALID_ARG;
+  if (g->spent) return fail(g, MALS_INVALID_ARG, "the ingest's records went into mals_group_ingest_finish: create a new ingest");
   if (g->text_failed) return fail(g, g->text_fail_code, g->text_fail_msg);
   if (n_bytes < 0 || (n_bytes > 0 && !bytes)) return fail(g, MALS_INVALID_ARG, "bad text block");
   if (mem_kind != MALS_MEM_HOST && mem_kind != MALS_MEM_DEVICE) return fail(g, MALS_INVALID_ARG, "mem_kind must be MALS_MEM_HOST or MALS_MEM_DEVICE");
@@ -311,6 +326,7 @@ int mals_ingest_append_text(mals_ingest g, const void* bytes, int64_t n_bytes, i
 
 int mals_ingest_read_file(mals_ingest g, const char* path) {
   if (!g || !path) return MALS_INVALID_ARG;
+  if (g->spent) return fail(g, MALS_INVALID_ARG, "the ingest's records went into mals_group_ingest_finish: create a new ingest");
   if (g->text_failed) return fail(g, g->text_fail_code, g->text_fail_msg);
   ICHK(g, hipSetDevice(g->device));
   const std::string p(path);
@@ -366,35 +382,152 @@ int mals_ingest_read_file(mals_ingest g, const char* path) {
   return MALS_OK;
 }
 
-int mals_ingest_read_dir(mals_ingest g, const char* input_dir, int32_t* n_files_read) {
-  if (!g || !input_dir) return MALS_INVALID_ARG;
-  if (n_files_read) *n_files_read = 0;
-  if (g->text_failed) return fail(g, g->text_fail_code, g->text_fail_msg);
+}  // extern "C"
+
+namespace {
+
+struct InputFile {
+  std::string path;
+  int64_t mtime_ms, bytes;
+};
+
+// InputFilesReader.java:71-86: the input files of a directory in the order they are read; 1 when one is not a readable file
+int list_input_files(mals_ingest g, const char* input_dir, std::vector<InputFile>* out) {
   DIR* d = opendir(input_dir);
   if (!d) return MALS_OK;  // listFiles() == null: "No input files", not an error (IFR:80-83)
-  struct Entry {
-    std::string name;
-    int64_t mtime_ms;
-  };
-  std::vector<Entry> files;
+  std::vector<InputFile> files;
   while (dirent* e = readdir(d)) {
     const std::string name(e->d_name);
     if (name == "." || name == ".." || !is_input_file_name(name)) continue;
     struct stat st;
     const std::string full = std::string(input_dir) + "/" + name;
     if (stat(full.c_str(), &st) != 0) continue;
-    files.push_back({name, (int64_t)st.st_mtim.tv_sec * 1000 + st.st_mtim.tv_nsec / 1000000});  // File.lastModified(): ms
+    files.push_back({full, (int64_t)st.st_mtim.tv_sec * 1000 + st.st_mtim.tv_nsec / 1000000, (int64_t)st.st_size});  // File.lastModified(): ms
   }
   closedir(d);
   // ByLastModifiedComparator (ascending); Arrays.sort is stable over listFiles()'s unspecified order: by name here
-  std::sort(files.begin(), files.end(), [](const Entry& a, const Entry& b) { return a.name < b.name; });
-  std::stable_sort(files.begin(), files.end(), [](const Entry& a, const Entry& b) { return a.mtime_ms < b.mtime_ms; });
-  for (const Entry& f : files) {
-    const std::string full = std::string(input_dir) + "/" + f.name;
+  std::sort(files.begin(), files.end(), [](const InputFile& a, const InputFile& b) { return a.path < b.path; });
+  std::stable_sort(files.begin(), files.end(), [](const InputFile& a, const InputFile& b) { return a.mtime_ms < b.mtime_ms; });
+  for (const InputFile& f : files) {
     struct stat st;
-    if (stat(full.c_str(), &st) != 0 || !S_ISREG(st.st_mode))
-      return text_fail(g, MALS_IO_ERROR, full + " is not a readable file (FileInputStream would throw)");
-    if (int rc = mals_ingest_read_file(g, full.c_str())) return rc;
+    if (stat(f.path.c_str(), &st) != 0 || !S_ISREG(st.st_mode))
+      return text_fail(g, MALS_IO_ERROR, f.path + " is not a readable file (FileInputStream would throw)");
+  }
+  *out = std::move(files);
+  return MALS_OK;
+}
+
+bool splittable(const std::string& path) { return !ends_with(path, ".gz") && !ends_with(path, ".zip"); }
+
+// the first line start at or after byte `at` of a plain file: byte 0, the byte after '\n', the byte after a '\r' that no
+// '\n' follows (java.io.BufferedReader.readLine); `size` when no line starts there
+int64_t next_line_start(const std::string& path, int64_t at, int64_t size) {
+  if (at <= 0) return 0;
+  if (at >= size) return size;
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f || fseeko(f, (off_t)(at - 1), SEEK_SET) != 0) {
+    if (f) fclose(f);
+    return size;   // the read of the piece reports the error
+  }
+  int prev = fgetc(f);
+  int64_t p = at;
+  for (; p < size; ++p) {
+    const int c = fgetc(f);
+    if (c == EOF) break;
+    if (prev == '\n' || (prev == '\r' && c != '\n')) break;
+    prev = c;
+  }
+  fclose(f);
+  return std::min(p, size);
+}
+
+// bytes [b, e) of a plain file, the last block with end_of_file
+int read_file_piece(mals_ingest g, const std::string& path, int64_t b, int64_t e) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return text_fail(g, MALS_IO_ERROR, std::string("cannot open ") + path);
+  if (fseeko(f, (off_t)b, SEEK_SET) != 0) {
+    fclose(f);
+    return text_fail(g, MALS_IO_ERROR, std::string("read error: ") + path);
+  }
+  const size_t buf_bytes = std::min<size_t>(g->text_block_bytes, (size_t)64 << 20);
+  if (buf_bytes > g->h_pinned.capacity()) ICHK(g, g->h_pinned.alloc(buf_bytes));
+  uint8_t* buf = g->h_pinned.get();
+  for (int64_t at = b;;) {
+    const size_t want = (size_t)std::min<int64_t>((int64_t)buf_bytes, e - at);
+    const size_t got = want ? fread(buf, 1, want, f) : 0;
+    if (got != want) {
+      fclose(f);
+      return text_fail(g, MALS_IO_ERROR, std::string("read error: ") + path);
+    }
+    at += (int64_t)got;
+    if (int rc = append_text_impl(g, buf, (int64_t)got, MALS_MEM_HOST, at == e)) {
+      fclose(f);
+      return rc;
+    }
+    if (at == e) break;
+  }
+  fclose(f);
+  return MALS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mals_ingest_read_dir(mals_ingest g, const char* input_dir, int32_t* n_files_read) {
+  if (!g || !input_dir) return MALS_INVALID_ARG;
+  if (n_files_read) *n_files_read = 0;
+  if (g->spent) return fail(g, MALS_INVALID_ARG, "the ingest's records went into mals_group_ingest_finish: create a new ingest");
+  if (g->text_failed) return fail(g, g->text_fail_code, g->text_fail_msg);
+  std::vector<InputFile> files;
+  if (int rc = list_input_files(g, input_dir, &files)) return rc;
+  for (const InputFile& f : files) {
+    if (int rc = mals_ingest_read_file(g, f.path.c_str())) return rc;
+    if (n_files_read) ++*n_files_read;
+  }
+  return MALS_OK;
+}
+
+// The stream of mals_ingest_read_dir (files in its order, bytes in order) cut into n_shares pieces of about equal on-disk
+// bytes.  A cut moves forward to the next line start of a plain file; a .gz / .zip file goes whole to the share in which its
+// first byte falls.  Every share computes the same cuts from the same listing.
+int mals_ingest_read_dir_share(mals_ingest g, const char* input_dir, int32_t share, int32_t n_shares, int32_t* n_files_read) {
+  if (!g || !input_dir) return MALS_INVALID_ARG;
+  if (n_files_read) *n_files_read = 0;
+  if (n_shares < 1 || n_shares > MALS_SPLIT_MAX_SHARES || share < 0 || share >= n_shares) return fail(g, MALS_INVALID_ARG, "share: 0 <= share < n_shares <= 256");
+  if (g->spent) return fail(g, MALS_INVALID_ARG, "the ingest's records went into mals_group_ingest_finish: create a new ingest");
+  if (g->text_failed) return fail(g, g->text_fail_code, g->text_fail_msg);
+  if (g->share != share) {
+    if (int rc = mals_ingest_set_option(g, MALS_INGEST_OPT_SHARE, share)) return rc;
+  }
+  std::vector<InputFile> files;
+  if (int rc = list_input_files(g, input_dir, &files)) return rc;
+  std::vector<int64_t> start(files.size() + 1, 0);
+  for (size_t i = 0; i < files.size(); ++i) start[i + 1] = start[i] + files[i].bytes;
+  const int64_t total = start.back();
+  // cut c (global byte offset) -> the line start at or after it
+  auto adjust = [&](int64_t c) -> int64_t {
+    if (c <= 0) return 0;
+    if (c >= total) return total;
+    const size_t i = (size_t)(std::upper_bound(start.begin(), start.end(), c) - start.begin()) - 1;   // start[i] <= c < start[i + 1]
+    if (c == start[i]) return c;
+    if (!splittable(files[i].path)) return start[i + 1];
+    return start[i] + next_line_start(files[i].path, c - start[i], files[i].bytes);
+  };
+  const int64_t lo = adjust((int64_t)((__int128)total * share / n_shares));
+  const int64_t hi = adjust((int64_t)((__int128)total * (share + 1) / n_shares));
+  for (size_t i = 0; i < files.size(); ++i) {
+    const int64_t fb = start[i], fe = start[i + 1];
+    if (splittable(files[i].path)) {
+      const int64_t b = std::max(lo, fb), e = std::min(hi, fe);
+      if (e <= b) continue;
+      ICHK(g, hipSetDevice(g->device));
+      if (int rc = read_file_piece(g, files[i].path, b - fb, e - fb)) return rc;
+    } else {
+      // whole, in the share of its first byte (an empty file: the share whose range holds its offset)
+      if (!(fb >= lo && (fb < hi || (fb == total && hi == total && share == n_shares - 1)))) continue;
+      if (int rc = mals_ingest_read_file(g, files[i].path.c_str())) return rc;
+    }
     if (n_files_read) ++*n_files_read;
   }
   return MALS_OK;
@@ -408,7 +541,7 @@ int mals_ingest_text_info(mals_ingest g, mals_ingest_text_info_t* out) {
   out->skipped_lines = g->skipped_lines;
   out->full_parser_lines = g->slow_lines;
   out->text_bytes = g->text_bytes;
-  out->records = g->n;
+  out->records = g->sharded ? g->shard_records : g->n;
   out->parse_ms = g->parse_ms;
   out->stage_ms = g->stage_ms;
   out->n_item_tag_ids = g->finished ? g->n_tag_ids[0] : -1;
@@ -432,7 +565,8 @@ int mals_ingest_get_known_items(mals_ingest g, int64_t* host_ptr, int32_t* host_
   if (!g) return MALS_INVALID_ARG;
   if (!g->finished || !g->known_ptr.get()) return fail(g, MALS_INVALID_ARG, "no known items: set MALS_INGEST_OPT_KNOWN_ITEMS before mals_ingest_finish");
   ICHK(g, hipSetDevice(g->device));
-  if (host_ptr) ICHK(g, hipMemcpy(host_ptr, g->known_ptr.get(), sizeof(int64_t) * (size_t)(g->n_users + 1), hipMemcpyDeviceToHost));
+  const int64_t rows = g->sharded ? g->slice_rows[0] : g->n_users;
+  if (host_ptr) ICHK(g, hipMemcpy(host_ptr, g->known_ptr.get(), sizeof(int64_t) * (size_t)(rows + 1), hipMemcpyDeviceToHost));
   if (host_item_idx && g->n_known)
     ICHK(g, hipMemcpy(host_item_idx, g->known_idx.get(), sizeof(int32_t) * (size_t)g->n_known, hipMemcpyDeviceToHost));
   return MALS_OK;

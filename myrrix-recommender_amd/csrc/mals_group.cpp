@@ -794,6 +794,7 @@ int mals_group_set_matrix(mals_group g, int side, int64_t n_rows, int64_t nnz, c
 int mals_ingest_install_group(mals_ingest in, mals_group g, int32_t flags) {
   if (!g) return MALS_INVALID_ARG;
   if (!in) return gfail(g, MALS_INVALID_ARG, "null ingest handle");
+  if (malsi_ingest_spent(in)) return gfail(g, MALS_INVALID_ARG, "the ingest holds one member's slices (mals_group_ingest_finish), not the whole input");
   int64_t n_rows[2] = {0, 0}, nnz = 0;
   if (int rc = mals_ingest_counts(in, nullptr, &n_rows[0], &n_rows[1], &nnz)) return gfail(g, rc, mals_ingest_last_error(in));
   int32_t in_dev = 0;
@@ -885,6 +886,186 @@ int mals_ingest_install_group(mals_ingest in, mals_group g, int32_t flags) {
   }
   return MALS_OK;
 }
+
+}  // extern "C"
+
+// ---- mals_group_ingest_finish: the group's transport for the ingest side (ingest_group_host.h) ----
+namespace {
+
+const char* shard_ops_error(void* ctx) { return static_cast<mals_group>(ctx)->err.c_str(); }
+
+int shard_ops_allreduce(void* ctx, int64_t* const* dev, int64_t n, int op_max) {
+  mals_group g = static_cast<mals_group>(ctx);
+  if (g->world == 1 && !g->m[0].nccl) return MALS_OK;
+  if (g->backend == MALS_GROUP_PEER_COPY) {
+    std::vector<int64_t> acc((size_t)n), tmp((size_t)n);
+    for (size_t i = 0; i < g->m.size(); ++i) {
+      GHIP(g, hipSetDevice(g->m[i].device));
+      GHIP(g, hipMemcpy(i == 0 ? acc.data() : tmp.data(), dev[i], sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
+      if (i > 0)
+        for (int64_t k = 0; k < n; ++k) acc[(size_t)k] = op_max ? std::max(acc[(size_t)k], tmp[(size_t)k]) : acc[(size_t)k] + tmp[(size_t)k];
+    }
+    for (size_t i = 0; i < g->m.size(); ++i) {
+      GHIP(g, hipSetDevice(g->m[i].device));
+      GHIP(g, hipMemcpy(dev[i], acc.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    return MALS_OK;
+  }
+  GNCCL(g, g_rccl.GroupStart());
+  for (size_t i = 0; i < g->m.size(); ++i) {
+    Member& mb = g->m[i];
+    const ncclResult_t r = g_rccl.AllReduce(dev[i], dev[i], (size_t)n, ncclInt64, op_max ? ncclMax : ncclSum, mb.nccl, mb.comm);
+    if (r != ncclSuccess) {
+      (void)g_rccl.GroupEnd();
+      return gfail(g, MALS_COMM_ERROR, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
+    }
+  }
+  GNCCL(g, g_rccl.GroupEnd());
+  for (Member& mb : g->m) {
+    GHIP(g, hipSetDevice(mb.device));
+    GHIP(g, hipStreamSynchronize(mb.comm));
+  }
+  return MALS_OK;
+}
+
+// every member's run for rank q (send_off row of the member) into q's receive buffer at q's offset for the sender
+int shard_ops_exchange(void* ctx, const uint8_t* const* send, const int64_t* send_off, uint8_t* const* recv, const int64_t* recv_off) {
+  mals_group g = static_cast<mals_group>(ctx);
+  const int W = g->world;
+  const size_t nl = g->m.size();
+  if (g->backend == MALS_GROUP_PEER_COPY || (W == 1 && !g->m[0].nccl)) {
+    for (size_t i = 0; i < nl; ++i) {
+      const Member& src = g->m[i];
+      GHIP(g, hipSetDevice(src.device));
+      for (size_t j = 0; j < nl; ++j) {
+        const Member& dst = g->m[j];
+        const int64_t b = send_off[i * (W + 1) + dst.rank], e = send_off[i * (W + 1) + dst.rank + 1];
+        if (e > b)
+          GHIP(g, hipMemcpyPeerAsync(recv[j] + recv_off[j * (W + 1) + src.rank], dst.device, send[i] + b, src.device, (size_t)(e - b), src.comm));
+      }
+    }
+    for (Member& mb : g->m) {
+      GHIP(g, hipSetDevice(mb.device));
+      GHIP(g, hipStreamSynchronize(mb.comm));
+    }
+    return MALS_OK;
+  }
+  GNCCL(g, g_rccl.GroupStart());
+  for (size_t i = 0; i < nl; ++i) {
+    Member& mb = g->m[i];
+    for (int q = 0; q < W; ++q) {
+      const int64_t sb = send_off[i * (W + 1) + q], se = send_off[i * (W + 1) + q + 1];
+      const int64_t rb = recv_off[i * (W + 1) + q], re = recv_off[i * (W + 1) + q + 1];
+      ncclResult_t r = ncclSuccess;
+      if (q == mb.rank) {
+        if (se > sb && hipSetDevice(mb.device) == hipSuccess &&
+            hipMemcpyAsync(recv[i] + rb, send[i] + sb, (size_t)(se - sb), hipMemcpyDeviceToDevice, mb.comm) != hipSuccess)
+          r = ncclUnhandledCudaError;
+      } else {
+        if (se > sb) r = g_rccl.Send(send[i] + sb, (size_t)(se - sb), ncclUint8, q, mb.nccl, mb.comm);
+        if (r == ncclSuccess && re > rb) r = g_rccl.Recv(recv[i] + rb, (size_t)(re - rb), ncclUint8, q, mb.nccl, mb.comm);
+      }
+      if (r != ncclSuccess) {
+        (void)g_rccl.GroupEnd();
+        return gfail(g, MALS_COMM_ERROR, std::string("ncclSend/ncclRecv: ") + g_rccl.GetErrorString(r));
+      }
+    }
+  }
+  GNCCL(g, g_rccl.GroupEnd());
+  for (Member& mb : g->m) {
+    GHIP(g, hipSetDevice(mb.device));
+    GHIP(g, hipStreamSynchronize(mb.comm));
+  }
+  return MALS_OK;
+}
+
+int shard_ops_agree(void* ctx, const int* local_rc) {
+  mals_group g = static_cast<mals_group>(ctx);
+  int worst = MALS_OK;
+  for (size_t i = 0; i < g->m.size(); ++i) worst = std::max(worst, local_rc[i]);
+  if (g->single_process) return worst;
+  // multi-process: the group's status words (allocated with the group), max over every rank
+  std::vector<std::vector<double>> v(g->m.size(), std::vector<double>(1, 0.0));
+  for (size_t i = 0; i < g->m.size(); ++i) v[i][0] = (double)local_rc[i];
+  double agreed = 0.0;
+  if (int rc = allreduce_host(g, v, 1, 1, &agreed)) return rc == MALS_COMM_ERROR ? MALS_COMM_ERROR : -1;
+  return (int)agreed;
+}
+
+// slices at given bounds (plan_side without the plan)
+int set_side_bounds(mals_group g, int side, const std::vector<int64_t>& bounds) {
+  g->n_rows[side] = bounds.back();
+  g->side_chunks[side] = g->exchange_chunks;
+  g->bounds[side] = bounds;
+  for (Member& mb : g->m)
+    if (int rc = mals_set_chunk_rows(mb.h, side, chunk_rows_of(g, side, mb.rank))) return mfail(g, mb, rc);
+  return MALS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mals_group_ingest_finish(mals_group g, mals_ingest* ingests, int32_t n_local, int32_t flags) {
+  if (!g) return MALS_INVALID_ARG;
+  if (!ingests || n_local != (int32_t)g->m.size()) return gfail(g, MALS_INVALID_ARG, "one ingest per local member");
+  if (flags != 0) return gfail(g, MALS_INVALID_ARG, "flags: reserved, must be 0");
+  for (int32_t i = 0; i < n_local; ++i) {
+    int32_t dev = -1;
+    if (!ingests[i] || mals_ingest_device(ingests[i], &dev) != MALS_OK) return gfail(g, MALS_INVALID_ARG, "null ingest handle");
+    if (dev != g->m[(size_t)i].device) return gfail(g, MALS_INVALID_ARG, "ingest " + std::to_string(i) + " is not on its member's device");
+  }
+  std::vector<int32_t> ranks((size_t)n_local);
+  for (int32_t i = 0; i < n_local; ++i) ranks[(size_t)i] = g->m[(size_t)i].rank;
+  malsi_group_ops ops{g, g->world, n_local, g->cfg.features, ranks.data(), shard_ops_allreduce, shard_ops_exchange, shard_ops_agree, shard_ops_error};
+  std::vector<int64_t> bounds[2] = {std::vector<int64_t>((size_t)g->world + 1, 0), std::vector<int64_t>((size_t)g->world + 1, 0)};
+  if (int rc = malsi_ingest_shard_finish(ingests, &ops, bounds[0].data(), bounds[1].data())) return gfail(g, rc, mals_ingest_last_error(ingests[0]));
+  // the ingests hold their slices only: records, workspace and exchange buffers are gone before the replicas are declared
+  int64_t n_rows[2] = {0, 0};
+  if (int rc = mals_ingest_counts(ingests[0], nullptr, &n_rows[0], &n_rows[1], nullptr)) return gfail(g, rc, mals_ingest_last_error(ingests[0]));
+  for (int32_t i = 0; i < n_local; ++i) malsi_ingest_note_replicas(ingests[i]);
+  for (int sd = 0; sd < 2; ++sd)
+    if (g->n_total[sd] < n_rows[sd])
+      if (int rc = mals_group_set_factor_rows(g, sd, n_rows[sd])) return rc;
+  for (int sd = 0; sd < 2; ++sd) {
+    if (int rc = set_side_bounds(g, sd, bounds[sd])) return rc;
+    for (int32_t i = 0; i < n_local; ++i) {
+      Member& mb = g->m[(size_t)i];
+      const int64_t *d_ptr = nullptr;
+      const int32_t* d_col = nullptr;
+      const float* d_val = nullptr;
+      if (int rc = mals_ingest_device_csr(ingests[i], sd, &d_ptr, &d_col, &d_val)) return gfail(g, rc, mals_ingest_last_error(ingests[i]));
+      const int64_t r0 = bounds[sd][(size_t)mb.rank], r1 = bounds[sd][(size_t)mb.rank + 1];
+      int64_t nnz = 0;
+      GHIP(g, hipSetDevice(mb.device));
+      GHIP(g, hipMemcpy(&nnz, d_ptr + (r1 - r0), sizeof(int64_t), hipMemcpyDeviceToHost));
+      mb.own_col[sd].reset();
+      mb.own_val[sd].reset();
+      if (int rc = mals_set_matrix(mb.h, sd, r0, r1 - r0, nnz, d_ptr, d_col, d_val, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
+    }
+    if (int rc = finish_matrix(g, sd)) return rc;
+  }
+  for (int32_t i = 0; i < n_local; ++i) {
+    Member& mb = g->m[(size_t)i];
+    GHIP(g, hipSetDevice(mb.device));
+    mb.own_known_ptr.reset();
+    mb.own_known_idx.reset();
+    mb.own_tag_idx.reset();
+    const int64_t *k_ptr = nullptr, *t_idx = nullptr;
+    const int32_t* k_idx = nullptr;
+    int64_t n_known = 0, n_tags = 0;
+    (void)mals_ingest_device_known_items(ingests[i], &k_ptr, &k_idx, &n_known);
+    if (k_ptr)
+      if (int rc = mals_set_known_items(mb.h, bounds[0][(size_t)mb.rank + 1] - bounds[0][(size_t)mb.rank], k_ptr, k_idx, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
+    if (int rc = mals_ingest_device_tag_items(ingests[i], &t_idx, &n_tags)) return gfail(g, rc, mals_ingest_last_error(ingests[i]));
+    if (int rc = mals_set_tag_items(mb.h, n_tags, t_idx, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
+  }
+  return MALS_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // ServerRecommender.recommend(userID, ...) on a group: every member holds full replicas of X and Y but only its own users' rows
 // of R / knownItemIDs, so a user is answered by the member whose slice holds its row.

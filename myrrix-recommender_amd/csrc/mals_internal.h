@@ -27,3 +27,26 @@ __attribute__((visibility("hidden"))) void* malsi_ready_event(mals_handle h);
 // the thread's "why did create fail" text (mals_create_error): set by whichever create call fails, cleared by one that succeeds
 __attribute__((visibility("hidden"))) void malsi_set_create_error(const char* text);
 }
+
+// mals_group_ingest_finish (mals_group.cpp) hands the ingest side (ingest_group_host.h) the group's transport: collectives over
+// every rank, called with one device buffer per LOCAL member (on that member's device), returning once they are complete.
+struct malsi_group_ops {
+  void* ctx;
+  int32_t world, n_local, features;
+  const int32_t* ranks;                                                          // rank of local member i
+  int (*allreduce_i64)(void* ctx, int64_t* const* dev, int64_t n, int op_max);   // in place: sum (0) / max (1)
+  // send / recv: byte buffers; send_off / recv_off: n_local rows of world + 1 byte offsets (row i: member i's run per peer rank)
+  int (*exchange)(void* ctx, const uint8_t* const* send, const int64_t* send_off, uint8_t* const* recv, const int64_t* recv_off);
+  // the worst of every rank's status (local_rc: one per local member), through buffers the group already holds (no allocation)
+  int (*agree)(void* ctx, const int* local_rc);
+  const char* (*last_error)(void* ctx);
+};
+// the ingest half of mals_group_ingest_finish: every rank returns the same status; on success bounds_x / bounds_y (world + 1)
+// are the group's slices and every ingest holds its member's
+// the ingest holds a member's slices (mals_group_ingest_finish) or gave its records to one that failed: install / finish refuse it
+__attribute__((visibility("hidden"))) int malsi_ingest_spent(mals_ingest g);
+// called by mals_group_ingest_finish right before it declares the factor replicas (mals_ingest_memory reports what it saw)
+__attribute__((visibility("hidden"))) void malsi_ingest_note_replicas(mals_ingest g);
+__attribute__((visibility("hidden"))) int malsi_ingest_shard_finish(mals_ingest* ingests, const malsi_group_ops* ops, int64_t* bounds_x,
+                                                                  int64_t* bounds_y);
+

@@ -231,6 +231,14 @@ class GroupALS:
             self._chk(self._L.mals_group_append_rows(self._g, side, r1 - r0, cc.ctypes.data_as(ctypes.c_void_p), vv.ctypes.data_as(ctypes.c_void_p)))
         self._chk(self._L.mals_group_end_matrix(self._g, side))
 
+    def ingest_finish(self, ingests):
+        """mals_group_ingest_finish: ingests[i] holds share `rank of local member i` of the input on that member's device;
+        collective.  Afterwards every ingest holds its member's slices, which the members borrow: the ingests are kept alive
+        here."""
+        arr = (ctypes.c_void_p * len(ingests))(*[g._g.value for g in ingests])
+        self._chk(self._L.mals_group_ingest_finish(self._g, arr, len(ingests), 0))
+        self._keep_ingest = list(ingests)
+
     def recommend(self, user_idx, how_many, consider_known_items=False):
         """ServerRecommender.recommend on the group: every query answered by the member that holds the user's row."""
         u = np.ascontiguousarray(user_idx, dtype=np.int64)

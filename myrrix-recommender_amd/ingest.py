@@ -85,6 +85,38 @@ class Ingest:
         self._chk(self._L.mals_ingest_read_dir(self._g, str(path).encode(), ctypes.byref(n)))
         return n.value
 
+    def set_share(self, share):
+        """MALS_INGEST_OPT_SHARE: which piece of a stream ingested by a group this is (before the first append)."""
+        self.set_option(_lib.INGEST_OPT_SHARE, share)
+
+    def read_dir_share(self, path, share, n_shares):
+        """Share `share` of `n_shares` of what read_dir(path) reads, cut by on-disk bytes at line starts; the number of
+        files (or pieces of files) read."""
+        n = ctypes.c_int32()
+        self._chk(self._L.mals_ingest_read_dir_share(self._g, str(path).encode(), int(share), int(n_shares), ctypes.byref(n)))
+        return n.value
+
+    def slice(self, side):
+        """(row_begin, n_rows): the rows of `side` this ingest's CSR holds (a member's slice after GroupALS.ingest_finish)."""
+        b, n = ctypes.c_int64(), ctypes.c_int64()
+        self._chk(self._L.mals_ingest_slice(self._g, side, ctypes.byref(b), ctypes.byref(n)))
+        return b.value, n.value
+
+    def slice_entries(self, side):
+        """entries of this ingest's CSR slice of `side` (its last row pointer)"""
+        rp = np.empty(self.slice(side)[1] + 1, dtype=np.int64)
+        self._chk(self._L.mals_ingest_get_csr(self._g, side, rp.ctypes.data_as(ctypes.c_void_p), None, None))
+        return int(rp[-1])
+
+    def memory(self):
+        """Device bytes held: work (records, text buffers, workspace) and results; the work bytes held when a group finish
+        declared the factor replicas; the split kernels' ms and memory traffic (50 B per record)."""
+        w, r, wr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        ms, by = ctypes.c_double(), ctypes.c_double()
+        self._chk(self._L.mals_ingest_memory(self._g, ctypes.byref(w), ctypes.byref(r), ctypes.byref(wr), ctypes.byref(ms), ctypes.byref(by)))
+        return {"work_bytes": w.value, "result_bytes": r.value, "work_bytes_at_replicas": wr.value, "split_ms": ms.value,
+                "split_bytes": by.value}
+
     def text_info(self):
         info = _lib.IngestTextInfo()
         info.struct_size = ctypes.sizeof(info)
@@ -98,10 +130,9 @@ class Ingest:
         return out
 
     def known_items(self):
-        """knownItemIDs as (row_ptr over the dense users, dense item indices)."""
-        c = self.counts()
+        """knownItemIDs as (row_ptr over the dense users of this ingest's slice, dense item indices)."""
         n = self.text_info()["n_known_items"]
-        ptr = np.empty(c["users"] + 1, dtype=np.int64)
+        ptr = np.empty(self.slice(SIDE_X)[1] + 1, dtype=np.int64)
         idx = np.empty(max(n, 0), dtype=np.int32)
         self._chk(self._L.mals_ingest_get_known_items(self._g, ptr.ctypes.data_as(ctypes.c_void_p), idx.ctypes.data_as(ctypes.c_void_p)))
         return ptr, idx
@@ -121,11 +152,11 @@ class Ingest:
         return out
 
     def csr(self, side):
-        c = self.counts()
-        rows = c["users"] if side == SIDE_X else c["items"]
+        rows = self.slice(side)[1]
         rp = np.empty(rows + 1, dtype=np.int64)
-        col = np.empty(c["nnz"], dtype=np.int32)
-        val = np.empty(c["nnz"], dtype=np.float32)
+        self._chk(self._L.mals_ingest_get_csr(self._g, side, rp.ctypes.data_as(ctypes.c_void_p), None, None))
+        col = np.empty(int(rp[-1]), dtype=np.int32)
+        val = np.empty(int(rp[-1]), dtype=np.float32)
         self._chk(self._L.mals_ingest_get_csr(self._g, side, rp.ctypes.data_as(ctypes.c_void_p),
                                               col.ctypes.data_as(ctypes.c_void_p), val.ctypes.data_as(ctypes.c_void_p)))
         return rp, col, val

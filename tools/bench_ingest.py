@@ -5,7 +5,11 @@ synthetic record stream already resident in HBM, the algorithmic bytes all passe
 usage: python tools/bench_ingest.py [--records N] [--users U] [--items I] [--removes P]
        python tools/bench_ingest.py --from-text [...]   the same stream as TEXT ("user,item,value\\n" lines, resident in
            HBM) through mals_ingest_append_text + mals_ingest_finish: lines/s of the whole path, the text kernels'
-           own rate, and the end-to-end roofline on the bytes that must move (text in + both CSR matrices out)"""
+           own rate, and the end-to-end roofline on the bytes that must move (text in + both CSR matrices out)
+       python tools/bench_ingest.py --ranks 1,2,4 [--records N]   the same text cut into N shares, one single-process group of N
+           members on device 0 (MALS_GROUP_PEER_COPY) and mals_group_ingest_finish: one JSON line per N with the split kernels'
+           time, traffic and rate, the device bytes every member's ingest holds afterwards next to one whole-input ingest plus
+           mals_ingest_install_group, and the entry imbalance of the X slices"""
 import argparse
 import json
 import os
@@ -31,7 +35,11 @@ def main():
                          "generated in HBM, handed to mals_ingest_append_text and dropped; times are the library's HIP-event times of its "
                          "kernels (text_info, stats), so the generator between the pieces is not in them; one run, no repeats")
     ap.add_argument("--partition-records", type=int, default=0, help="MALS_INGEST_OPT_PARTITION_RECORDS (0: the library's default)")
+    ap.add_argument("--ranks", type=str, default="", help="comma-separated member counts: the sharded ingest (mals_group_ingest_finish)")
+    ap.add_argument("--features", type=int, default=32, help="--ranks: k of the group (its factor replicas are declared by the finish)")
     a = ap.parse_args()
+    if a.ranks:
+        return ranks(a)
     if a.from_text:
         return from_text(a)
     import numpy as np
@@ -209,6 +217,101 @@ def from_text(a):
                                "sample": "first %d lines, oracle/ingest_text_oracle.py + ingest_oracle.py (pure Python restatement of "
                                          "InputFilesReader.readInputFiles)" % len(lines)}
     print(json.dumps(out))
+
+
+def ranks(a):
+    """--ranks: the stream of --from-text generated piece by piece; piece p goes to share p * N // pieces (shares in stream
+    order, every piece ends at a line end); one single-process group of N members on device 0 finishes it collectively."""
+    import torch
+    import myrrix_recommender_amd as pkg
+    from myrrix_recommender_amd import _lib, ingest
+    n, k = a.records, a.features
+
+    def pieces():
+        gen = torch.Generator(device="cuda").manual_seed(1234567890)
+        n_pieces = (n + a.text_chunk - 1) // a.text_chunk
+        for p, lo in enumerate(range(0, n, a.text_chunk)):
+            m = min(a.text_chunk, n - lo)
+            u = torch.randint(0, a.users, (m,), device="cuda", generator=gen)
+            i = (torch.rand(m, device="cuda", generator=gen).pow_(3.0) * a.items).long().clamp_(max=a.items - 1)
+            v = torch.randint(1, 6, (m,), device="cuda", generator=gen).float()
+            if a.removes > 0:
+                v[torch.rand(m, device="cuda", generator=gen) < a.removes] = float("nan")
+            t = format_lines(torch, u, i, v)
+            del u, i, v
+            yield p, n_pieces, t
+
+    def hbm_in_use():
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        f, t = torch.cuda.mem_get_info()
+        return t - f
+    # the whole-input path: one ingest of everything + mals_ingest_install_group (what every rank holds today)
+    base0 = hbm_in_use()
+    with ingest.Ingest(0) as g, pkg.GroupALS.single_process(k, [0], backend=_lib.GROUP_PEER_COPY) as grp:
+        g.set_option(_lib.INGEST_OPT_RESERVE_RECORDS, n)
+        for p, n_p, t in pieces():
+            g.append_text(t, p == n_p - 1)
+            del t
+        g.finish()
+        g.install_group(grp)
+        mem = g.memory()
+        c = g.counts()
+        whole = {"ingest_bytes_held": mem["work_bytes"] + mem["result_bytes"], "work_bytes": mem["work_bytes"],
+                 "result_bytes": mem["result_bytes"], "finish_ms": g.stats()["finish_ms"],
+                 "hbm_bytes_in_use_after_install": hbm_in_use() - base0}
+    replica_bytes = 4.0 * k * (c["users"] + c["items"])
+    for N in [int(x) for x in a.ranks.split(",")]:
+        base = hbm_in_use()
+        ings = [ingest.Ingest(0) for _ in range(N)]
+        with pkg.GroupALS.single_process(k, [0] * N, backend=_lib.GROUP_PEER_COPY) as grp:
+            for s, g in enumerate(ings):
+                g.set_share(s)
+                g.set_option(_lib.INGEST_OPT_RESERVE_RECORDS, (n + N - 1) // N)
+            for p, n_p, t in pieces():
+                s = p * N // n_p
+                last = (p + 1) * N // n_p != s or p == n_p - 1
+                ings[s].append_text(t, last)
+                del t
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            grp.ingest_finish(ings)
+            wall_ms = (time.perf_counter() - t0) * 1e3
+            in_use = hbm_in_use() - base
+            mems = [g.memory() for g in ings]
+            x_entries = [g.slice_entries(pkg.SIDE_X) for g in ings]    # entries of every member's X slice
+            split_ms = [m["split_ms"] for m in mems]
+            split_bytes = [m["split_bytes"] for m in mems]
+            held = [m["work_bytes"] + m["result_bytes"] for m in mems]
+            cc = ings[0].counts()
+            rec = [g.counts()["records"] for g in ings]
+            out = {"metric": "sharded ingest (mals_group_ingest_finish), %d members of one single-process group on one MI355X" % N,
+                   "ranks": N, "lines": n, "users": cc["users"], "items": cc["items"], "nnz": cc["nnz"],
+                   "group_finish_wall_ms": wall_ms,
+                   "group_finish_wall_ms_per_member": wall_ms / N,
+                   "note": "the members share one device and are finished one after another by one thread: the wall time is the "
+                           "sum over members (plus the host merges), not what N devices would take in parallel; the exchange is "
+                           "hipMemcpyPeerAsync inside one device, not xGMI",
+                   "split": {"ms_per_member": split_ms, "bytes_per_member": split_bytes,
+                             "GBps_per_member": [b / t / 1e6 if t > 0 else None for b, t in zip(split_bytes, split_ms)],
+                             "what": "count + scatter kernels of both splits (records by user owner, entries by item owner) and their "
+                                     "scan; bytes = 50 per record moved (8 B key + 1 B destination in the count pass, 1 + 20 B read and "
+                                     "20 B written in the scatter)",
+                             "frac_of_6290_GBps_copy": [b / t / 1e6 / 6290.0 if t > 0 else None for b, t in zip(split_bytes, split_ms)]},
+                   "records_finished_per_member": rec,
+                   "hbm_per_member": {"ingest_bytes_held": held, "work_bytes": [m["work_bytes"] for m in mems],
+                                      "work_bytes_at_replicas": [m["work_bytes_at_replicas"] for m in mems],
+                                      "replica_bytes_k": replica_bytes,
+                                      "bytes_held_incl_replicas_max": max(held) + replica_bytes},
+                   "hbm_whole_input_per_rank": dict(whole, replica_bytes_k=replica_bytes,
+                                                    bytes_held_incl_replicas=whole["ingest_bytes_held"] + replica_bytes),
+                   "hbm_bytes_in_use_after_group_finish_all_members": in_use,
+                   "x_slice_entries": x_entries,
+                   "x_entry_imbalance_max_over_mean": max(x_entries) / (sum(x_entries) / N) if sum(x_entries) else None,
+                   "features": k}
+        for g in ings:
+            g.close()
+        print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
