@@ -366,6 +366,32 @@ int mals_recommend_to_many(mals_handle h, const float* vectors, const int64_t* v
                            const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out, float* score_out,
                            int32_t* n_out);
 
+/* ---- item-to-item similarity on the device ------------------------------------------------------------
+ * ServerRecommender.mostSimilarItems (online/src/net/myrrix/online/ServerRecommender.java:1171-1266, scored by
+ * MostSimilarItemIterator.java:73-120): for query q of items i_1..i_n (dense item indices; item_ptr NULL: one item per
+ * query, else query q owns item_idx[item_ptr[q] .. item_ptr[q+1]), at least one) the score of item i is
+ * (float)((s_1 + ... + s_n) / n), s_j = dot(Y_i, Y_ij) / (norm(Y_i) * norm(Y_ij)) in fp64 (SimpleVectorMath.dot and .norm:
+ * fp32 products / squares, fp64 sums in feature order; the product of the norms first, then the division) -- bit-identical;
+ * n counts duplicates.  Skipped: tag items (:77), the query's own items (:81-85), items with a non-finite s_j (:104: a
+ * zero or NaN row, or a query item of zero norm, gives fewer results, never an error).  The how_many best come back best
+ * first, ties in ascending item index; padding -1 / -inf; n_out (may be NULL): results per query.  Rescorers and mapping IDs
+ * to indices stay with the caller.  An index outside [0, rows of Y) is MALS_INVALID_ARG; how_many in 1..4096.  The same
+ * filter as mals_recommend (a bf16 MFMA pass with a proven cosine margin, then the exact rescore; csrc/topn_kernels.h)
+ * over the resident Y.  Threads: as mals_recommend* (any number of request threads, together with recommend calls); calls
+ * of fewer than 64 queries are folded into passes of their own kind, larger ones run exclusively. */
+int mals_most_similar_items(mals_handle h, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
+                            int64_t* item_idx_out, float* score_out, int32_t* n_out);
+/* ServerRecommender.similarityToItem (ServerRecommender.java:1268-1304): out[j] = (float)(dot(Y_ij, Y_to) / (norm(Y_ij) *
+ * norm(Y_to))) for the n items item_idx[j]; NaN is returned as NaN (no skip, no exclusion). */
+int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_idx, int32_t n, float* out);
+/* ServerRecommender.recommendedBecause (ServerRecommender.java:1324-1376, scored by RecommendedBecauseIterator.java:61-75):
+ * for query q the candidates are the known items of user user_idx[q] (global row of X in this handle's local shard):
+ * mals_set_known_items if installed, else the user's row of R -- the lists mals_recommend skips.  Score (float)(dot(Y_c,
+ * Y_item) / (norm(Y_c) * norm(Y_item))) with item = item_idx[q]; tag items and non-finite scores skipped; item itself is
+ * NOT excluded.  Outputs and order as mals_most_similar_items; exact for lists of any length. */
+int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
+                             int64_t* item_idx_out, float* score_out, int32_t* n_out);
+
 /* ---- ingest -> CSR ------------------------------------------------------
  * What InputFilesReader.readInputFiles (online-local/src/net/myrrix/online/generation/
  * InputFilesReader.java:64-211) does to the parsed records of the input files, on the device: the
@@ -676,6 +702,15 @@ int mals_ingest_memory(mals_ingest g, int64_t* work_bytes, int64_t* result_bytes
  * another process (a one-process-per-GPU deployment routes the request to that process). */
 int mals_group_recommend(mals_group g, const int64_t* user_idx, int32_t n_queries, int32_t how_many, int32_t consider_known_items,
                          int64_t* item_idx_out, float* score_out, int32_t* n_out);
+/* The similarity calls on a group (arguments as mals_most_similar_items / mals_similarity_to_item /
+ * mals_recommended_because): the Y replicas are complete on every member, so any local member answers the first two;
+ * recommendedBecause goes to the local member that owns the user's row (MALS_INVALID_ARG if a rank of another process owns
+ * it), as mals_group_recommend does. */
+int mals_group_most_similar_items(mals_group g, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
+                                  int64_t* item_idx_out, float* score_out, int32_t* n_out);
+int mals_group_similarity_to_item(mals_group g, int64_t to_item, const int64_t* item_idx, int32_t n, float* out);
+int mals_group_recommended_because(mals_group g, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
+                                   int64_t* item_idx_out, float* score_out, int32_t* n_out);
 /* slice bounds of a side after its matrix was set: bounds_out[world+1] */
 int mals_group_bounds(mals_group g, int side, int64_t* bounds_out);
 

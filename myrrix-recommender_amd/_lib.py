@@ -152,6 +152,9 @@ SYMBOLS = {
     "mals_recommend_front_stats": (ctypes.c_int, [_H, _P]),
     "mals_recommend_set_depth": (ctypes.c_int, [_H, _I32]),
     "mals_recommend_set_spin_us": (ctypes.c_int, [_H, _I32]),
+    "mals_most_similar_items": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
+    "mals_similarity_to_item": (ctypes.c_int, [_H, ctypes.c_int64, _P, _I32, _P]),
+    "mals_recommended_because": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
     "mals_set_tag_items": (ctypes.c_int, [_H, _I64, _P, ctypes.c_int]),
     "mals_get_tag_item_count": (ctypes.c_int, [_H, ctypes.POINTER(_I64)]),
     "mals_ingest_device": (ctypes.c_int, [_H, ctypes.POINTER(_I32)]),
@@ -211,6 +214,9 @@ SYMBOLS = {
     "mals_group_end_matrix": (ctypes.c_int, [_H, ctypes.c_int]),
     "mals_group_bounds": (ctypes.c_int, [_H, ctypes.c_int, _P]),
     "mals_group_recommend": (ctypes.c_int, [_H, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "mals_group_most_similar_items": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
+    "mals_group_similarity_to_item": (ctypes.c_int, [_H, ctypes.c_int64, _P, _I32, _P]),
+    "mals_group_recommended_because": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
     "mals_group_half_iteration": (ctypes.c_int, [_H, ctypes.c_int]),
     "mals_group_factorize": (ctypes.c_int, [_H, ctypes.c_double, _I32, _I32, _I32, _P, _I32, _P, _I32,
                                             ctypes.POINTER(_I32), ctypes.POINTER(ctypes.c_double)]),

@@ -99,6 +99,19 @@ def _host(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def _item_queries(items):
+    """mostSimilarItems queries as CSR: a sequence of ints is one item per query, a list of sequences several per query."""
+    items = list(items)
+    if items and all(np.ndim(q) == 0 for q in items):
+        flat = np.ascontiguousarray(np.asarray(items, dtype=np.int64))
+        return flat, np.arange(len(flat) + 1, dtype=np.int64)
+    qs = [np.asarray(q, dtype=np.int64).ravel() for q in items]
+    ptr = np.zeros(len(qs) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([len(q) for q in qs])
+    flat = np.ascontiguousarray(np.concatenate(qs)) if ptr[-1] else np.zeros(0, np.int64)
+    return flat, ptr
+
+
 class ALSCore:
     def __init__(self, features, alpha=1.0, lam=0.1, flags=0, device=0, segment_nnz=0,
                  singularity_threshold=1e-5, chunk_rows=0, gramian_mode=0, solve_mode=0):
@@ -409,6 +422,41 @@ class ALSCore:
         self._chk(self._L.mals_recommend_to_many(self._h, flatv.ctypes.data_as(ctypes.c_void_p), vptr.ctypes.data_as(ctypes.c_void_p),
                                                  len(qs), int(how_many), ep, ei, idx.ctypes.data_as(ctypes.c_void_p),
                                                  sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        return idx, sc, cnt
+
+    def most_similar_items(self, items, how_many):
+        """mostSimilarItems (ServerRecommender.java:1171-1266): items = a sequence of item indices (one item per query) or a
+        list of sequences (several items per query); the score is the mean cosine to the query's items
+        (MostSimilarItemIterator.java:73-120).  Returns (item_idx [q][how_many] int64, scores float32, counts)."""
+        flat, ptr = _item_queries(items)
+        idx = np.empty((len(ptr) - 1, how_many), dtype=np.int64)
+        sc = np.empty((len(ptr) - 1, how_many), dtype=np.float32)
+        cnt = np.empty(len(ptr) - 1, dtype=np.int32)
+        self._chk(self._L.mals_most_similar_items(self._h, flat.ctypes.data_as(ctypes.c_void_p), ptr.ctypes.data_as(ctypes.c_void_p),
+                                                  len(ptr) - 1, int(how_many), idx.ctypes.data_as(ctypes.c_void_p),
+                                                  sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        return idx, sc, cnt
+
+    def similarity_to_item(self, to_item, items):
+        """similarityToItem (ServerRecommender.java:1268-1304): the cosine of every item to to_item, NaN as NaN."""
+        ii = _host(items, np.int64)
+        out = np.empty(len(ii), dtype=np.float32)
+        self._chk(self._L.mals_similarity_to_item(self._h, int(to_item), ii.ctypes.data_as(ctypes.c_void_p), len(ii),
+                                                  out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def recommended_because(self, users, items, how_many):
+        """recommendedBecause (ServerRecommender.java:1324-1376): per query (users[q], items[q]) the user's known items most
+        similar to the item, best first.  Returns (item_idx, scores, counts)."""
+        u = _host(users, np.int64)
+        ii = _host(items, np.int64)
+        assert len(u) == len(ii)
+        idx = np.empty((len(u), how_many), dtype=np.int64)
+        sc = np.empty((len(u), how_many), dtype=np.float32)
+        cnt = np.empty(len(u), dtype=np.int32)
+        self._chk(self._L.mals_recommended_because(self._h, u.ctypes.data_as(ctypes.c_void_p), ii.ctypes.data_as(ctypes.c_void_p), len(u),
+                                                   int(how_many), idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+                                                   cnt.ctypes.data_as(ctypes.c_void_p)))
         return idx, sc, cnt
 
     def reconstruction_error(self):

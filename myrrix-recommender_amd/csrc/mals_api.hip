@@ -2580,6 +2580,126 @@ int mals_recommend_vectors(mals_handle h, const float* query_vectors, int32_t n_
   return mals_recommend_to_many(h, query_vectors, nullptr, n_queries, how_many, exclude_ptr, exclude_idx, item_idx_out, score_out, n_out);
 }
 
+// ---- item-to-item similarity (topn_kernels.h, cosine mode): through the same serving front as mals_recommend* ----------
+static int topn_check_items(mals_handle h, const int64_t* idx, int64_t n) {
+  const int64_t n_items = h->side[MALS_SIDE_Y].n_total;
+  for (int64_t i = 0; i < n; ++i)
+    if (idx[i] < 0 || idx[i] >= n_items) return topn_fail(h, MALS_INVALID_ARG, "item index outside the item factor replica");
+  return MALS_OK;
+}
+
+int mals_most_similar_items(mals_handle h, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
+                            int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  if (!h) return MALS_INVALID_ARG;
+  SideState& y = h->side[MALS_SIDE_Y];
+  if (!y.F || y.n_total == 0) return topn_fail(h, MALS_INVALID_ARG, "item factor replica not available");
+  if (n_queries < 0 || how_many <= 0 || how_many > 4096 || (n_queries > 0 && (!item_idx || !item_idx_out || !score_out)))
+    return topn_fail(h, MALS_INVALID_ARG, "bad mostSimilarItems arguments (how_many in 1..4096)");
+  std::vector<int64_t> one_each;
+  if (item_ptr) {
+    if (n_queries > 0 && item_ptr[0] != 0) return topn_fail(h, MALS_INVALID_ARG, "item_ptr[0] must be 0");
+    for (int q = 0; q < n_queries; ++q) {
+      const int64_t n = item_ptr[q + 1] - item_ptr[q];
+      if (n < 1) return topn_fail(h, MALS_INVALID_ARG, "every query needs at least one item");
+      if (n > (1 << 20)) return topn_fail(h, MALS_INVALID_ARG, "too many items in one query");
+    }
+  } else {
+    one_each.resize((size_t)n_queries + 1);
+    for (int q = 0; q <= n_queries; ++q) one_each[(size_t)q] = q;
+    item_ptr = one_each.data();
+  }
+  if (n_queries == 0) return MALS_OK;
+  if (int rc = topn_check_items(h, item_idx, item_ptr[n_queries])) return rc;
+  if (h->tag_bits.get() && h->tag_bits_items != y.n_total)
+    return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
+  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  TopnRequest rq;
+  TopnTicket t;
+  t.how_many = how_many;
+  if (n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N && item_ptr[n_queries] <= 4 * TOPN_FRONT_BULK) {
+    // a small call: folded into a pass with other callers' mostSimilarItems calls
+    t.items = item_idx;
+    t.item_ptr = item_ptr;
+    t.n = n_queries;
+    t.item_out = item_idx_out;
+    t.score_out = score_out;
+    t.n_out = n_out;
+  } else {
+    rq.n_queries = n_queries;
+    rq.how_many = how_many;
+    rq.item_rows = item_idx;
+    rq.vec_ptr = item_ptr;
+    rq.excl_ptr = item_ptr;   // the query items are never returned (MostSimilarItemIterator.java:81-85)
+    rq.excl_idx = item_idx;
+    rq.cosine = true;
+    rq.item_idx_out = item_idx_out;
+    rq.score_out = score_out;
+    rq.n_out = n_out;
+    t.bulk = &rq;
+  }
+  return topn_front_submit(h, t);
+}
+
+int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_idx, int32_t n, float* out) {
+  if (!h) return MALS_INVALID_ARG;
+  SideState& y = h->side[MALS_SIDE_Y];
+  if (!y.F || y.n_total == 0) return topn_fail(h, MALS_INVALID_ARG, "item factor replica not available");
+  if (n < 0 || (n > 0 && (!item_idx || !out))) return topn_fail(h, MALS_INVALID_ARG, "bad similarityToItem arguments");
+  if (to_item < 0 || to_item >= y.n_total) return topn_fail(h, MALS_INVALID_ARG, "item index outside the item factor replica");
+  if (int rc = topn_check_items(h, item_idx, n)) return rc;
+  if (n == 0) return MALS_OK;
+  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  TopnRequest rq;
+  TopnTicket t;
+  rq.kind = TOPN_KIND_SIMILARITY_TO;
+  rq.n_queries = n;
+  rq.how_many = 1;
+  rq.item_rows = item_idx;
+  rq.to_item = to_item;
+  rq.sim_out = out;
+  t.bulk = &rq;
+  t.how_many = 1;
+  return topn_front_submit(h, t);
+}
+
+int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
+                             int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  if (!h) return MALS_INVALID_ARG;
+  SideState& x = h->side[MALS_SIDE_X];
+  SideState& y = h->side[MALS_SIDE_Y];
+  if (!y.F || y.n_total == 0) return topn_fail(h, MALS_INVALID_ARG, "item factor replica not available");
+  if (n_queries < 0 || how_many <= 0 || how_many > 4096 || (n_queries > 0 && (!user_idx || !item_idx || !item_idx_out || !score_out)))
+    return topn_fail(h, MALS_INVALID_ARG, "bad recommendedBecause arguments (how_many in 1..4096)");
+  if (!x.has_matrix && !h->known_ptr)
+    return topn_fail(h, MALS_INVALID_ARG, "the user-side matrix (or mals_set_known_items) is needed for the known items");
+  if (h->known_ptr && h->known_rows != x.n_local)
+    return topn_fail(h, MALS_INVALID_ARG, "the installed known items do not match the local user rows");
+  for (int q = 0; q < n_queries; ++q) {
+    if (user_idx[q] < 0 || user_idx[q] >= x.n_total) return topn_fail(h, MALS_INVALID_ARG, "user index outside the factor replica");
+    if (user_idx[q] < x.row_offset || user_idx[q] >= x.row_offset + x.n_local)
+      return topn_fail(h, MALS_INVALID_ARG, "known items of this user are not on this handle (row outside the local shard)");
+  }
+  if (n_queries == 0) return MALS_OK;
+  if (int rc = topn_check_items(h, item_idx, n_queries)) return rc;
+  if (h->tag_bits.get() && h->tag_bits_items != y.n_total)
+    return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
+  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  TopnRequest rq;
+  TopnTicket t;
+  rq.kind = TOPN_KIND_BECAUSE;
+  rq.n_queries = n_queries;
+  rq.how_many = how_many;
+  rq.item_rows = item_idx;
+  rq.because_user = user_idx;
+  rq.cosine = true;
+  rq.item_idx_out = item_idx_out;
+  rq.score_out = score_out;
+  rq.n_out = n_out;
+  t.bulk = &rq;
+  t.how_many = how_many;
+  return topn_front_submit(h, t);
+}
+
 int mals_recommend_front_stats(mals_handle h, int64_t* out4) {
   if (!h || !out4) return MALS_INVALID_ARG;
   TopnFront* f = topn_front(h);

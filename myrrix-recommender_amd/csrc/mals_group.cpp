@@ -1096,6 +1096,43 @@ int mals_group_recommend(mals_group g, const int64_t* user_idx, int32_t n_querie
   return MALS_OK;
 }
 
+// mostSimilarItems / similarityToItem on a group: the Y replicas are complete on every member, any local member answers
+int mals_group_most_similar_items(mals_group g, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
+                                  int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  if (!g || g->m.empty()) return MALS_INVALID_ARG;
+  return mals_most_similar_items(g->m[0].h, item_idx, item_ptr, n_queries, how_many, item_idx_out, score_out, n_out);
+}
+
+int mals_group_similarity_to_item(mals_group g, int64_t to_item, const int64_t* item_idx, int32_t n, float* out) {
+  if (!g || g->m.empty()) return MALS_INVALID_ARG;
+  return mals_similarity_to_item(g->m[0].h, to_item, item_idx, n, out);
+}
+
+// recommendedBecause on a group: the user's known items live on the member whose slice holds its row
+int mals_group_recommended_because(mals_group g, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
+                                   int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  if (!g) return MALS_INVALID_ARG;
+  if (n_queries < 0 || how_many <= 0 || (n_queries > 0 && (!user_idx || !item_idx || !item_idx_out || !score_out))) return MALS_INVALID_ARG;
+  if (g->bounds[MALS_SIDE_X].empty()) return MALS_INVALID_ARG;
+  const std::vector<int64_t>& b = g->bounds[MALS_SIDE_X];
+  for (int32_t q0 = 0; q0 < n_queries;) {
+    const int64_t u = user_idx[q0];
+    if (u < 0 || u >= b.back()) return MALS_INVALID_ARG;
+    const int owner = (int)(std::upper_bound(b.begin(), b.end(), u) - b.begin()) - 1;
+    int32_t q1 = q0 + 1;
+    while (q1 < n_queries && user_idx[q1] >= b[(size_t)owner] && user_idx[q1] < b[(size_t)owner + 1]) ++q1;
+    const Member* mb = nullptr;
+    for (const Member& m : g->m)
+      if (m.rank == owner) mb = &m;
+    if (!mb) return MALS_INVALID_ARG;   // the owner is another process's rank
+    if (int rc = mals_recommended_because(mb->h, user_idx + q0, item_idx + q0, q1 - q0, how_many, item_idx_out + (size_t)q0 * how_many,
+                                          score_out + (size_t)q0 * how_many, n_out ? n_out + q0 : nullptr))
+      return rc;
+    q0 = q1;
+  }
+  return MALS_OK;
+}
+
 int mals_group_begin_matrix(mals_group g, int side, int64_t n_rows, const int64_t* row_ptr) {
   GSIDE(g, side);
   if (n_rows < 0 || !row_ptr || row_ptr[0] != 0) return gfail(g, MALS_INVALID_ARG, "bad matrix arguments");

@@ -30,6 +30,8 @@ struct TopnSlot {
   DeviceBuffer<bf16x8> d_img;         // the pass's queries as split bf16 MFMA operands (topn_prepare_kernel)
   DeviceBuffer<unsigned> d_wcount;    // hits per wave of the filter kernel, [n_waves] + one overflow word
   DeviceBuffer<uint2> d_whits;        // [n_waves][TOPN_WAVE_CAP] (item, query)
+  DeviceBuffer<double> d_qn;          // cosine mode: the exact norms of the pass's query vectors ...
+  DeviceBuffer<uint32_t> d_qflag;     // ... and per query 0 / 1 (answered empty) / 2 (dense path), topn_prepare_kernel<true>
   PinnedBuffer<uint8_t> h_stage;      // the pass's results, [nq][how_many] pairs | counts | taus | overflow word (topn_final_kernel
                                       // writes them there), decoded while later passes run
 };
@@ -78,7 +80,19 @@ struct TopnRequest {
   // its own "skip the known items" flag
   const TopnOut* out_q = nullptr;
   const uint8_t* skip_known_q = nullptr;
+  // mostSimilarItems (kind TOPN_KIND_SCORE, cosine): the query vectors are rows of Y, vector v = Y[item_rows[v]] (grouped by
+  // vec_ptr); the caller passes the query items as the exclusion lists (MostSimilarItemIterator.java:81-85)
+  const int64_t* item_rows = nullptr;
+  bool cosine = false;
+  int kind = 0;                          // TOPN_KIND_*
+  // recommendedBecause (TOPN_KIND_BECAUSE): query q = (user because_user[q], item item_rows[q]), candidates = the user's
+  // known items
+  const int64_t* because_user = nullptr;
+  // similarityToItem (TOPN_KIND_SIMILARITY_TO): n_queries items item_rows[], against to_item, into sim_out
+  int64_t to_item = 0;
+  float* sim_out = nullptr;
 };
+enum { TOPN_KIND_SCORE = 0, TOPN_KIND_BECAUSE = 1, TOPN_KIND_SIMILARITY_TO = 2 };
 
 inline TopnOut topn_out(const TopnRequest& rq, size_t qq) {
   if (rq.out_q) return rq.out_q[qq];
@@ -120,7 +134,7 @@ bool topn_emit(std::vector<TopnCand>& cand, int how_many, int64_t* item_idx_out,
 int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const TopnRequest& rq, TopnPass& ps) {
   const int k = h->cfg.features;
   SideState& x = h->side[MALS_SIDE_X];
-  const bool own_vectors = !rq.user_idx;
+  const bool own_vectors = !rq.user_idx && !rq.item_rows;
   if (rq.user_idx || !rq.vec_ptr) {
     ps.v0 = ps.q0;
     ps.n_vecs = ps.nq;
@@ -132,7 +146,8 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
   // layout of the block (8-byte aligned pieces)
   const size_t o_vptr = 0, o_rows = o_vptr + 8 * ((TOPN_FILTER_QUERIES + 2) / 2), o_uidx = o_rows + 8 * TOPN_FILTER_QUERIES,
                o_eptr = o_uidx + 8 * TOPN_FILTER_QUERIES, o_vecs = o_eptr + 8 * (TOPN_FILTER_QUERIES + 1),
-               o_eidx = o_vecs + ((own_vectors ? sizeof(float) * (size_t)ps.n_vecs * (size_t)k : 0) + 15) / 16 * 16,
+               o_eidx = o_vecs + ((own_vectors ? sizeof(float) * (size_t)ps.n_vecs * (size_t)k
+                                               : rq.item_rows ? sizeof(int64_t) * (size_t)ps.n_vecs : 0) + 15) / 16 * 16,
                total = o_eidx + 8 * (size_t)n_ex;
   if (total > sl.h_in.capacity()) HIPCHK(h, sl.h_in.reserve(total + total / 2, stream));  // an earlier copy may still be reading the old block
   HIPCHK(h, sl.d_in.reserve(total + total / 2, stream));
@@ -152,6 +167,15 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
       int64_t* rows = reinterpret_cast<int64_t*>(in + o_rows);
       for (int q = 0; q < ps.nq; ++q)
         rows[q] = (!rq.skip_known_q || rq.skip_known_q[ps.q0 + q]) ? rq.user_idx[ps.q0 + q] - x.row_offset : -1;
+      ps.have_rows = true;
+    }
+  } else if (rq.item_rows) {   // rows of Y (the replica is complete on every handle)
+    std::memcpy(in + o_vecs, rq.item_rows + ps.v0, sizeof(int64_t) * (size_t)ps.n_vecs);
+    sl.d_vecs = h->side[MALS_SIDE_Y].F;
+    sl.d_vrow = reinterpret_cast<const int64_t*>(sl.d_in.get() + o_vecs);
+    if (rq.because_user) {
+      int64_t* rows = reinterpret_cast<int64_t*>(in + o_rows);
+      for (int q = 0; q < ps.nq; ++q) rows[q] = rq.because_user[ps.q0 + q] - x.row_offset;
       ps.have_rows = true;
     }
   } else {
@@ -196,8 +220,16 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
   if (!w->d_state.get()) HIPCHK(h, w->d_state.alloc(TOPN_MAX_QUERIES));
   if (!w->d_hist.get()) HIPCHK(h, w->d_hist.alloc(256 * TOPN_MAX_QUERIES));
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_items + 63) / 64, (int64_t)h->n_cu * 8));
-  hipLaunchKernelGGL(topn_exact_dense_kernel, dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k, sl.d_vecs,
-                     sl.d_vrow, sl.d_vptr, nq, w->d_scores.get());
+  if (rq.cosine) {
+    HIPCHK(h, sl.d_qn.reserve((size_t)std::max<int64_t>(ps.n_vecs, 1), h->stream));
+    hipLaunchKernelGGL(topn_qnorm_kernel, dim3((unsigned)((ps.n_vecs + 63) / 64)), dim3(64), 0, h->stream, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs, k,
+                       sl.d_qn.get());
+    hipLaunchKernelGGL(topn_exact_dense_kernel<true>, dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k,
+                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), sl.d_qn.get());
+  } else {
+    hipLaunchKernelGGL(topn_exact_dense_kernel<false>, dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k,
+                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), nullptr);
+  }
   if (ps.have_rows)
     hipLaunchKernelGGL(topn_mask_kernel, dim3(64, (unsigned)nq), dim3(256), 0, h->stream, h->known_ptr ? h->known_ptr : x.row_ptr,
                        h->known_ptr ? h->known_idx : x.col, sl.d_rows, nq, 1, n_items, w->d_scores.get());
@@ -254,7 +286,7 @@ constexpr int TOPN_WAVE_CAP = 2048;  // hits a wave of the filter kernel can rec
 
 // topn_stream_kernel: QT = query tiles per wave, 4 QT per workgroup.  MODE 0: *n_out = workgroups of the sample (16
 // buckets each); MODE 1: *n_out = waves of the filter (one hit list each).
-template <int S, int QT, int MODE>
+template <int S, int QT, int MODE, bool COS>
 int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
   const int64_t tiles = (n_items + 16 * (int64_t)tile_stride - 1) / (16 * (int64_t)tile_stride);
   const int64_t stages = (tiles + 3) / 4;
@@ -264,10 +296,10 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   int& per_cu_cached = cached[lm];
   if (!per_cu_cached) {
     int nb = 0;
-    const hipError_t e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1>, 256, 0)
-                         : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2>, 256, 0)
-                         : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3>, 256, 0)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0>, 256, 0);
+    const hipError_t e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1, COS>, 256, 0)
+                         : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2, COS>, 256, 0)
+                         : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3, COS>, 256, 0)
+                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0, COS>, 256, 0);
     per_cu_cached = (e == hipSuccess && nb > 0) ? std::min(nb, 6) : 2;
   }
   int per_cu = per_cu_cached;
@@ -288,7 +320,7 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
     *n_out = (int)grid;
   }
 #define MALS_TOPN_GO(LM)                                                                                                              \
-  hipLaunchKernelGGL((topn_stream_kernel<S, QT, MODE, LM>), dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k,                           \
+  hipLaunchKernelGGL((topn_stream_kernel<S, QT, MODE, LM, COS>), dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k,                           \
                      sl.d_img.get(), nq, tile_stride, sl.d_bmax.get(), sl.d_bidx.get(), sl.d_tau.get(), TOPN_WAVE_CAP, sl.d_wcount.get(),   \
                      sl.d_whits.get(), cap, sl.d_count.get(), sl.d_cand.get(), sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE)
   if (lm == 1) MALS_TOPN_GO(1);
@@ -299,10 +331,10 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
 }
-template <int MODE>
+template <int MODE, bool COS>
 int topn_launch_stream(mals_handle h, TopnSlot& sl, int S, int nt, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
   const int qt = (nt + 3) / 4;
-#define MALS_TOPN_STREAM(SS, QQ) return topn_launch_stream_QT<SS, QQ, MODE>(h, sl, Y, n_items, k, nq, tile_stride, cap, n_out)
+#define MALS_TOPN_STREAM(SS, QQ) return topn_launch_stream_QT<SS, QQ, MODE, COS>(h, sl, Y, n_items, k, nq, tile_stride, cap, n_out)
   switch (S) {
     case 1:
       if (qt <= 1) MALS_TOPN_STREAM(1, 1);
@@ -362,20 +394,38 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
   const int32_t* k_idx = h->known_ptr ? h->known_idx : x.col;
   const int64_t* d_eptr = ps.have_excl ? sl.d_excl_ptr : nullptr;
   const int64_t* d_eidx = ps.have_excl ? sl.d_excl_idx : nullptr;
-  // 0. the queries as matrix operands (every tile an instantiation may touch: padding queries never produce a hit)
-  hipLaunchKernelGGL(topn_prepare_kernel, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
-                     sl.d_img.get(), sl.d_count.get(), d_overflow);
+  const bool cos = rq.cosine;
+  // 0. the queries as matrix operands (every tile an instantiation may touch: padding queries never produce a hit); in
+  // cosine mode first the exact norms of the query vectors
+  if (cos) {
+    hipLaunchKernelGGL(topn_qnorm_kernel, dim3((unsigned)((ps.n_vecs + 63) / 64)), dim3(64), 0, st, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs, k, sl.d_qn.get());
+    hipLaunchKernelGGL(topn_prepare_kernel<true>, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
+                       sl.d_img.get(), sl.d_count.get(), d_overflow, sl.d_qn.get(), sl.d_qflag.get());
+  } else {
+    hipLaunchKernelGGL(topn_prepare_kernel<false>, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
+                       sl.d_img.get(), sl.d_count.get(), d_overflow, nullptr, nullptr);
+  }
   // 1. sample: bucket maxima of the lower bounds of every tile_stride-th tile; 2. threshold (buckets won by known items dropped)
   int n_groups = 0, n_fw = 0;
-  if (int rc = topn_launch_stream<0>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)) return rc;
+  if (int rc = cos ? topn_launch_stream<0, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
+                   : topn_launch_stream<0, false>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups))
+    return rc;
   hipLaunchKernelGGL(topn_threshold_kernel, dim3((unsigned)nq), dim3(1024), 0, st, sl.d_bmax.get(), sl.d_bidx.get(), n_groups, how_many, k_ptr, k_idx, d_rows,
-                     d_eptr, d_eidx, n_items, p.tile_stride, h->tag_bits.get(), sl.d_tau.get());
+                     d_eptr, d_eidx, n_items, p.tile_stride, h->tag_bits.get(), sl.d_tau.get(), cos ? sl.d_qflag.get() : nullptr);
   // 3. filter, 4. exact scores of the hits (known items dropped), 5. the N best -- written straight into the slot's pinned
   // block (device-visible host memory: no copy kernel, no copy call)
   // (the filter's waves scatter their own hits into the per-query candidate lists: no kernel in between)
-  if (int rc = topn_launch_stream<1>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)) return rc;
-  hipLaunchKernelGGL(topn_rescore_kernel, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr, sl.d_count.get(), p.cap,
-                     sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow);
+  if (int rc = cos ? topn_launch_stream<1, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
+                   : topn_launch_stream<1, false>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw))
+    return rc;
+  if (cos)
+    hipLaunchKernelGGL(topn_rescore_kernel<true>, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr,
+                       sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow,
+                       sl.d_qn.get(), n_items);
+  else
+    hipLaunchKernelGGL(topn_rescore_kernel<false>, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr,
+                       sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow,
+                       nullptr, n_items);
   uint8_t* o = sl.h_stage.get();
   const size_t o_cnt = sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many, o_tau = o_cnt + sizeof(unsigned) * TOPN_FILTER_QUERIES,
                o_ovf = o_tau + sizeof(float) * TOPN_FILTER_QUERIES;
@@ -387,17 +437,27 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
 }
 
 // enqueue one pass on its slot's stream; its results land in the slot's pinned block behind the slot's event
-int topn_pass_filter_enqueue(mals_handle h, TopnSlot& sl, const TopnRequest& rq, const TopnPass& ps, const TopnFilterPlan& p) {
-  hipStream_t st = sl.stream;
-  if (!sl.d_bidx.get()) {   // (the last of them: all five exist)
+// the slot's fixed buffers, once
+int topn_slot_alloc(mals_handle h, TopnSlot& sl) {
+  if (!sl.d_bidx.get()) {   // (the last of them: all six exist)
     HIPCHK(h, sl.d_tau.alloc(TOPN_FILTER_QUERIES));
     HIPCHK(h, sl.d_count.alloc(TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE + 1));  // padded counters, then the overflow word
     HIPCHK(h, sl.d_img.alloc((size_t)16 * 5 * 64));
+    HIPCHK(h, sl.d_qflag.alloc(TOPN_FILTER_QUERIES));
     HIPCHK(h, sl.d_bmax.alloc(TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
     HIPCHK(h, sl.d_bidx.alloc(TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
   }
+  return MALS_OK;
+}
+
+int topn_pass_filter_enqueue(mals_handle h, TopnSlot& sl, const TopnRequest& rq, const TopnPass& ps, const TopnFilterPlan& p) {
+  hipStream_t st = sl.stream;
+  if (int rc = topn_slot_alloc(h, sl)) return rc;
   HIPCHK(h, sl.d_pairs.reserve((size_t)TOPN_FILTER_QUERIES * (size_t)p.cap, st));
   HIPCHK(h, sl.d_cand.reserve((size_t)TOPN_FILTER_QUERIES * (size_t)p.cap, st));
+  if (rq.cosine) HIPCHK(h, sl.d_qn.reserve((size_t)std::max<int64_t>(ps.n_vecs, 1), st));
+  // the result block of THIS slot only: another slot may hold a finished pass that has not been decoded yet
+  HIPCHK(h, sl.h_stage.reserve(p.stage_bytes, st));
   // (one graph launch per pass instead of nine kernel launches was tried: no faster -- the device, not the host's launch
   // calls, sets the pace even at 64 queries per pass)
   if (int rc = topn_pass_filter_launch(h, sl, rq, ps, p)) return rc;
@@ -455,7 +515,6 @@ int topn_prepare_slots(mals_handle h, TopnWorkspace* w, const TopnFilterPlan& p)
   for (TopnSlot& sl : w->slot) {
     if (!sl.stream) HIPCHK(h, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
     if (!sl.ev) HIPCHK(h, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    HIPCHK(h, sl.h_stage.reserve(p.stage_bytes, sl.stream));
   }
   if (!w->ev_begin) HIPCHK(h, hipEventCreateWithFlags(&w->ev_begin, hipEventDisableTiming));
   return MALS_OK;
@@ -492,9 +551,91 @@ int topn_finish_slot(mals_handle h, TopnWorkspace* w, int s, const TopnRequest& 
   return MALS_OK;
 }
 
+// ---- recommendedBecause: the rescore and final kernels on a given candidate list -------------------------------------
+// RecommendedBecauseIterator.java:61-75 over the user's known items (ServerRecommender.java:1324-1376): no sample, no filter.
+// Up to TOPN_MAX_QUERIES queries per pass, the lists in chunks of TOPN_BECAUSE_CAP candidates; the N best of every chunk
+// come back, and the N best of those are the N best of the list (ties by ascending index, topn_emit).  On the caller's
+// stream with slot 0's buffers (the call runs alone on the workspace).
+constexpr int TOPN_BECAUSE_CAP = 4096;
+
+int topn_because_run(mals_handle h, TopnWorkspace* w, const TopnRequest& rq) {
+  SideState& y = h->side[MALS_SIDE_Y];
+  SideState& x = h->side[MALS_SIDE_X];
+  const int k = h->cfg.features, how_many = rq.how_many, cap = TOPN_BECAUSE_CAP;
+  const int64_t n_items = y.n_total;
+  const int64_t* k_ptr = h->known_ptr ? h->known_ptr : x.row_ptr;
+  const int32_t* k_idx = h->known_ptr ? h->known_idx : x.col;
+  TopnSlot& sl = w->slot[0];
+  if (int rc = topn_slot_alloc(h, sl)) return rc;
+  HIPCHK(h, sl.d_pairs.reserve((size_t)TOPN_MAX_QUERIES * (size_t)cap, h->stream));
+  HIPCHK(h, sl.d_cand.reserve((size_t)TOPN_MAX_QUERIES * (size_t)cap, h->stream));
+  HIPCHK(h, sl.d_qn.reserve((size_t)TOPN_MAX_QUERIES, h->stream));
+  const size_t o_cnt = sizeof(uint64_t) * (size_t)TOPN_MAX_QUERIES * (size_t)how_many, o_tau = o_cnt + sizeof(unsigned) * TOPN_MAX_QUERIES,
+               o_ovf = o_tau + sizeof(float) * TOPN_MAX_QUERIES;
+  HIPCHK(h, sl.h_stage.reserve(o_ovf + 16, h->stream));
+  unsigned* d_overflow = sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE;
+  std::vector<std::vector<TopnCand>> cand;
+  for (int q0 = 0; q0 < rq.n_queries; q0 += TOPN_MAX_QUERIES) {
+    TopnPass ps;
+    ps.q0 = q0;
+    ps.nq = std::min(TOPN_MAX_QUERIES, rq.n_queries - q0);
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (the input block is reused pass by pass)
+    if (int rc = topn_upload_pass(h, sl, h->stream, rq, ps)) return rc;
+    hipLaunchKernelGGL(topn_qnorm_kernel, dim3(1), dim3(64), 0, h->stream, sl.d_vecs, sl.d_vrow, ps.nq, k, sl.d_qn.get());
+    cand.assign((size_t)ps.nq, {});
+    for (int64_t off = 0;; off += cap) {
+      hipLaunchKernelGGL(topn_known_cand_kernel, dim3((unsigned)ps.nq), dim3(256), 0, h->stream, k_ptr, k_idx, sl.d_rows, off, cap, sl.d_cand.get(),
+                         sl.d_count.get());
+      hipLaunchKernelGGL(topn_rescore_kernel<true>, dim3(8, (unsigned)ps.nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, k, sl.d_vecs,
+                         sl.d_vrow, sl.d_vptr, sl.d_count.get(), cap, sl.d_cand.get(), nullptr, nullptr, nullptr, nullptr, nullptr, h->tag_bits.get(),
+                         sl.d_pairs.get(), d_overflow, sl.d_qn.get(), n_items);
+      uint8_t* o = sl.h_stage.get();
+      hipLaunchKernelGGL(topn_final_kernel, dim3((unsigned)ps.nq), dim3(256), sizeof(uint64_t) * (size_t)cap, h->stream, sl.d_pairs.get(), sl.d_count.get(), cap,
+                         how_many, reinterpret_cast<uint64_t*>(o), reinterpret_cast<unsigned*>(o + o_cnt), sl.d_tau.get(), reinterpret_cast<float*>(o + o_tau),
+                         d_overflow, reinterpret_cast<unsigned*>(o + o_ovf));
+      HIPCHK(h, hipGetLastError());
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      const uint64_t* outp = reinterpret_cast<const uint64_t*>(o);
+      const unsigned* count = reinterpret_cast<const unsigned*>(o + o_cnt);
+      bool more = false;
+      for (int q = 0; q < ps.nq; ++q) {
+        for (int j = 0; j < how_many; ++j) {
+          const uint64_t pr = outp[(size_t)q * how_many + j];
+          if (pr != 0) cand[(size_t)q].push_back({(uint32_t)(pr >> 32), (int64_t)(0xffffffffu - (uint32_t)pr)});
+        }
+        more = more || count[q] > (unsigned)cap;
+      }
+      if (!more) break;
+    }
+    for (int q = 0; q < ps.nq; ++q) {
+      const TopnOut o_q = topn_out(rq, (size_t)(ps.q0 + q));
+      (void)topn_emit(cand[(size_t)q], how_many, o_q.items, o_q.scores, o_q.n);   // (finite scores only: the rescore struck the rest)
+    }
+  }
+  return MALS_OK;
+}
+
+// similarityToItem: one small kernel on the caller's stream
+int topn_similarity_to_run(mals_handle h, const TopnRequest& rq) {
+  const int n = rq.n_queries;
+  DeviceBuffer<int64_t> d_idx;
+  DeviceBuffer<float> d_out;
+  HIPCHK(h, d_idx.alloc((size_t)n));
+  HIPCHK(h, d_out.alloc((size_t)n));
+  HIPCHK(h, hipMemcpyAsync(d_idx.get(), rq.item_rows, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(topn_similarity_to_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->side[MALS_SIDE_Y].F, h->cfg.features,
+                     rq.to_item, d_idx.get(), n, d_out.get());
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(rq.sim_out, d_out.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MALS_OK;
+}
+
 int topn_run(mals_handle h, const TopnRequest& rq) {
   if (!h->tn_ws) h->tn_ws = new TopnWorkspace();
   TopnWorkspace* w = static_cast<TopnWorkspace*>(h->tn_ws);
+  if (rq.kind == TOPN_KIND_BECAUSE) return topn_because_run(h, w, rq);
+  if (rq.kind == TOPN_KIND_SIMILARITY_TO) return topn_similarity_to_run(h, rq);
   if (topn_dense_only(h, rq.how_many)) {
     for (int q0 = 0; q0 < rq.n_queries; q0 += TOPN_MAX_QUERIES) {
       TopnPass ps;
@@ -576,6 +717,10 @@ struct TopnTicket {
   const int64_t* vec_ptr = nullptr;
   const int64_t* excl_ptr = nullptr;
   const int64_t* excl_idx = nullptr;
+  // ... or a small mostSimilarItems call (MostSimilarItemIterator.java:73-120): n queries, query q owns the items
+  // items[item_ptr[q] .. item_ptr[q+1]) (never NULL here), which are also its exclusions
+  const int64_t* items = nullptr;
+  const int64_t* item_ptr = nullptr;
   // ... or a whole request of its own
   const TopnRequest* bulk = nullptr;
   int rc = MALS_OK;
@@ -633,7 +778,8 @@ struct TopnFrontPass {
   std::vector<int64_t> users;
   std::vector<uint8_t> skip;
   std::vector<TopnOut> outs;
-  // a pass of by-vector calls: the callers' vectors and exclusion lists back to back
+  // a pass of by-vector calls: the callers' vectors and exclusion lists back to back (of mostSimilarItems calls: their items)
+  std::vector<int64_t> items;
   std::vector<float> vecs;
   std::vector<int64_t> vptr, eptr, eidx;
   TopnRequest rq;
@@ -754,6 +900,12 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
           one.rq.vec_ptr = head->vec_ptr;
           one.rq.excl_ptr = head->excl_ptr;
           one.rq.excl_idx = head->excl_idx;
+        } else if (head->items) {
+          one.rq.item_rows = head->items;
+          one.rq.vec_ptr = head->item_ptr;
+          one.rq.excl_ptr = head->item_ptr;
+          one.rq.excl_idx = head->items;
+          one.rq.cosine = true;
         } else {
           one.rq.user_idx = head->user_idx;
           one.rq.skip_known = head->skip_known;
@@ -776,18 +928,26 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
       const int cap = 16 * k_tiles;
       const int kf = h->cfg.features;
       fp.tickets.clear(); fp.users.clear(); fp.skip.clear(); fp.outs.clear();
-      fp.vecs.clear(); fp.vptr.assign(1, 0); fp.eptr.assign(1, 0); fp.eidx.clear();
+      fp.items.clear(); fp.vecs.clear(); fp.vptr.assign(1, 0); fp.eptr.assign(1, 0); fp.eidx.clear();
       const int how_many = head->how_many;
-      const bool by_vector = head->vectors != nullptr;   // a pass holds by-user calls or by-vector calls, not both (where its
-                                                         // query vectors come from -- X on the device or an uploaded block -- is per pass)
+      // a pass holds by-user calls, by-vector calls or mostSimilarItems calls, never two kinds (where its query vectors come
+      // from -- X on the device, an uploaded block, rows of Y -- and how they score is per pass)
+      auto kind_of = [](const TopnTicket* t) { return t->vectors ? 1 : t->items ? 2 : 0; };
+      const int kind = kind_of(head);
+      const bool by_vector = kind == 1;
       bool any_excl = false;
       while (!f->queue.empty()) {
         TopnTicket* t = f->queue.front();
-        if (t->bulk || t->how_many != how_many || (t->vectors != nullptr) != by_vector || (int)fp.outs.size() + t->n > cap) break;
+        if (t->bulk || t->how_many != how_many || kind_of(t) != kind || (int)fp.outs.size() + t->n > cap) break;
         f->queue.pop_front();
         fp.tickets.push_back(t);
         for (int q = 0; q < t->n; ++q) {
-          if (by_vector) {
+          if (kind == 2) {
+            const int64_t v0 = t->item_ptr[q], v1 = t->item_ptr[q + 1];
+            fp.items.insert(fp.items.end(), t->items + v0, t->items + v1);
+            fp.vptr.push_back(fp.vptr.back() + (v1 - v0));
+            fp.eptr.push_back(fp.vptr.back());
+          } else if (by_vector) {
             const int64_t v0 = t->vec_ptr ? t->vec_ptr[q] : q, v1 = t->vec_ptr ? t->vec_ptr[q + 1] : q + 1;
             fp.vecs.insert(fp.vecs.end(), t->vectors + v0 * kf, t->vectors + v1 * kf);
             fp.vptr.push_back(fp.vptr.back() + (v1 - v0));
@@ -806,7 +966,13 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
       fp.rq = TopnRequest();
       fp.rq.n_queries = (int)fp.outs.size();
       fp.rq.how_many = how_many;
-      if (by_vector) {
+      if (kind == 2) {
+        fp.rq.item_rows = fp.items.data();
+        fp.rq.vec_ptr = fp.vptr.data();
+        fp.rq.excl_ptr = fp.eptr.data();
+        fp.rq.excl_idx = fp.items.data();
+        fp.rq.cosine = true;
+      } else if (by_vector) {
         fp.rq.vectors = fp.vecs.data();
         fp.rq.vec_ptr = fp.vptr.data();
         if (any_excl) {

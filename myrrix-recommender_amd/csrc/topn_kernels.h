@@ -35,6 +35,36 @@
 // instructions per element for 20 % fewer candidates -- not worth it: the filter is bound by instruction issue.)  For a
 // query of n vectors the filter vector is their mean and |x| is the mean of their norms (an upper bound of the norm of
 // the mean, and of the per-vector error sum).
+//
+// COSINE MODE (template flag COS: mostSimilarItems, MostSimilarItemIterator.java:73-120; recommendedBecause,
+// RecommendedBecauseIterator.java:61-75).  The exact score of item i for a query of items q_1..q_n is
+//     (float)( (s_1 + ... + s_n) / n ),   s_j = dot(Y_i, Y_qj) / (norm(Y_i) * norm(Y_qj))      (fp64, product first)
+// with norm = SimpleVectorMath.norm (SVM:46-52: sqrt of the fp64 sum of fp32 squares); an item with a non-finite s_j is
+// skipped (:104), never an error.  topn_cos_score computes exactly that in the rescore and the dense path.  The filter
+// runs on the same sample / threshold / filter passes with
+//   x = (1/n) sum_j Y_qj / norm(Y_qj)   (fp64, rounded once to fp32: |x| <= 1 + 2^-23; the margin uses |x| <= 1.000001)
+// and item i passes iff  approx + |y_i|' M_c + floor - tau |y_i|'' >= 0, which is the cosine test approx/|y_i| + M_c - tau
+// >= -floor/|y_i| with the item's norm folded in, no per-element work added.  Bound, with |y| = norm(Y_i) exactly:
+//   (a) bf16 rounding of both operands + fp32 accumulation, as above: |approx - y.x| <= 1.01 * 2^-8 |y| |x|;
+//   (b) the reference's own roundings (fp32 products, the fp64 sums, divisions and the final cast): |score - y.x/|y||
+//       <= 2^-22 (|s_j| <= 1 + 2^-20 per vector; the cast adds <= 2^-24);
+//   (c) |x_fp32 - x| <= 2^-24 |x| (one rounding of the fp64 mean): covered by the 1.000001 in |x|;
+//   (d) the kernel's |y_i|' = fp32 sqrt of an fp32 FMA sum of squares, times 1.0000005, rounded UP to bf16 for the margin
+//       slot: >= |y| (1 - k 2^-25) (k <= 128 terms);
+//   (e) tau |y_i|'' in the margin step: A slots 2-5 = {hi, lo, hi, lo} of the bf16 split of the fp32 |y_i|, B slots 2-5 =
+//       {hi, hi, lo, lo} of the split of -tau (lo rounded up): the four products are exact and differ from -tau |y| by at
+//       most (2^-16 + 2^-16 + k 2^-25) |tau| |y| <= 2^-14 |y| (|tau| <= 1 + 2^-7: tau is a lower bound of a cosine's
+//       approximation);
+// in total  |approx - score |y|| <= (1.01 * 2^-8 + 2^-22 + 2^-14 + k 2^-25) |y| < (1.25 * 2^-8 + 2^-13) |y| = M_c |y|
+// (TOPN_COS_MARGIN; recommend's TOPN_MARGIN is unchanged).  So exact score >= tau implies a non-negative accumulator:
+// every item of the exact top N, with all its ties, is a candidate.  The sample (MODE 0) keeps (approx - |y_i|' M_c -
+// floor) / |y_i| per bucket, a lower bound of the score by the same bound (the fp32 division by the kernel's |y_i|
+// moves it by <= 2^-21, inside the slack of M_c), so at least N unmasked items score >= tau exactly, as for recommend.
+// Items whose |y_i| is zero or not finite (every s_j of theirs is non-finite: skipped) never become candidates: a zero
+// row's margin slot 1 is -1 (accumulator -floor < 0), a NaN / infinite row is struck in the hit test.  (A row whose
+// fp32 squares overflow, |y_f| >= 2^64, is treated as non-finite; outside the supported range.)  A query item of zero or
+// non-finite norm makes every s_j of its query non-finite: the query is answered empty from the exact norms
+// (topn_qnorm_kernel) before its x is formed; a query item whose norm overflows goes to the dense path.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,6 +77,8 @@ constexpr int TOPN_FILTER_MAX_N = 64;     // largest how_many the filter path ta
 constexpr int TOPN_SAMPLE_GROUPS = 512;   // most workgroups of the sample kernel: 16 buckets per workgroup and query
 constexpr float TOPN_MARGIN = 0.0048828125f;  // 1.25 * 2^-8
 constexpr float TOPN_MARGIN_FLOOR = 1e-30f;
+constexpr float TOPN_COS_MARGIN = 0.0050048828125f;  // 1.25 * 2^-8 + 2^-13: the cosine bound (header)
+constexpr float TOPN_COS_DEAD_TAU = 1e30f;           // threshold of a query answered empty (a query item of norm 0 / NaN)
 constexpr int TOPN_COUNT_STRIDE = 32;  // candidate counters one per 128-byte line: atomics on one LINE serialise in L2 (97 us per pass when packed)
 
 // fp32 -> uint32 with the same order (NaN sorts above +inf; the scores here are finite or -inf)
@@ -80,6 +112,53 @@ __device__ __forceinline__ float topn_ref_score(const float* __restrict__ y, con
   }
   return (float)(sum / (double)count);
 }
+// SimpleVectorMath.norm (SVM:46-52): sqrt of the fp64 sum of the fp32 squares
+__device__ __forceinline__ double topn_ref_norm(const float* __restrict__ y, int k) {
+  double d = 0.0;
+  for (int f = 0; f < k; ++f) d += (double)__fmul_rn(y[f], y[f]);
+  return sqrt(d);
+}
+// MostSimilarItemIterator.java:88-115 / RecommendedBecauseIterator.java:70-74 for the vectors [v0, v1) of the pass (qn[v]:
+// their norms): false if any similarity is not finite (the item is skipped)
+__device__ __forceinline__ bool topn_cos_score(const float* __restrict__ y, const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
+                                               const double* __restrict__ qn, int v0, int v1, int k, float* out) {
+  const double ny = topn_ref_norm(y, k);
+  double total = 0.0;
+  for (int v = v0; v < v1; ++v) {
+    const double s = topn_ref_dot(y, vecs + (vrow ? vrow[v] : (int64_t)v) * k, k) / (ny * qn[v]);
+    if (!(fabs(s) < __builtin_huge_val())) return false;
+    total += s;
+  }
+  *out = (float)(total / (double)(v1 - v0));
+  return true;
+}
+// the exact norms of the pass's query vectors, one thread per vector
+__global__ void topn_qnorm_kernel(const float* __restrict__ vecs, const int64_t* __restrict__ vrow, int n_vecs, int k, double* __restrict__ qn) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n_vecs) qn[v] = topn_ref_norm(vecs + (vrow ? vrow[v] : (int64_t)v) * k, k);
+}
+// similarityToItem (ServerRecommender.java:1268-1304): out[j] = (float)(dot(Y_ij, Y_to) / (norm(Y_ij) * norm(Y_to))), NaN
+// as NaN; one thread per item
+__global__ void topn_similarity_to_kernel(const float* __restrict__ Y, int k, int64_t to, const int64_t* __restrict__ idx, int n,
+                                          float* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const float* yt = Y + to * k;
+  const float* yi = Y + idx[j] * k;
+  out[j] = (float)(topn_ref_dot(yi, yt, k) / (topn_ref_norm(yi, k) * topn_ref_norm(yt, k)));
+}
+// recommendedBecause (ServerRecommender.java:1324-1376): the candidates of query q are its user's known items (row
+// rows[q] of the CSR), chunk [off, off + cap) of them; count[q] = the items from `off` on (may exceed cap: more chunks)
+__global__ __launch_bounds__(256) void topn_known_cand_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                              const int64_t* __restrict__ rows, int64_t off, int cap,
+                                                              uint32_t* __restrict__ cand, unsigned* __restrict__ count) {
+  const int q = blockIdx.x;
+  const int64_t r = rows[q];
+  const int64_t b = row_ptr[r] + off, e = row_ptr[r + 1];
+  const int64_t n = e > b ? e - b : 0;
+  if (threadIdx.x == 0) count[(size_t)q * TOPN_COUNT_STRIDE] = (unsigned)(n < 0x7fffffff ? n : 0x7fffffff);
+  for (int64_t i = threadIdx.x; i < n && i < cap; i += 256) cand[(int64_t)q * cap + i] = (uint32_t)col[b + i];
+}
 
 // ---- approximate scores on the bf16 matrix pipe -----------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -110,10 +189,14 @@ __device__ __forceinline__ __bf16 bf16_up(float v) {
 //                 to every accumulator.
 // One workgroup per query tile (16 queries), once per pass: gathers the vectors (row vrow[v] of vecs; vrow NULL: row
 // v), builds the tile's image, and clears the pass's counters.
+// COS: x = the mean of the query's unit vectors (qn: their exact norms), |x| <= 1; qflag[q] = 1: a vector of zero or NaN
+// norm (the query is answered empty), 2: a vector whose norm overflows (the dense path answers), else 0.
+template <bool COS>
 __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
                                                            const int32_t* __restrict__ vptr, int n_queries, int k, int S,
                                                            bf16x8* __restrict__ img, unsigned* __restrict__ count,
-                                                           unsigned* __restrict__ overflow) {
+                                                           unsigned* __restrict__ overflow, const double* __restrict__ qn,
+                                                           uint32_t* __restrict__ qflag) {
   __shared__ float xb[16][129];
   __shared__ float nrm[16];
   const int t = blockIdx.x, qi = threadIdx.x >> 4, sub = threadIdx.x & 15;  // 16 threads per query
@@ -126,22 +209,41 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
     v1 = vptr[q + 1];
   }
   const int n = v1 - v0;
-  for (int f = sub; f < 128; f += 16) {
-    double mean = 0.0;
-    if (f < k)
-      for (int v = v0; v < v1; ++v) mean += (double)vecs[(vrow ? vrow[v] : (int64_t)v) * k + f];
-    xb[qi][f] = n ? (float)(mean / n) : 0.f;
-  }
-  double norms = 0.0;
-  for (int v = v0; v < v1; ++v) {
-    const float* x = vecs + (vrow ? vrow[v] : (int64_t)v) * k;
-    double ss = 0.0;
-    for (int f = sub; f < k; f += 16) ss += (double)x[f] * (double)x[f];
+  if (COS) {
+    uint32_t flag = 0;
+    for (int v = v0; v < v1; ++v) {
+      const double s = qn[v];
+      if (!(s > 0.0)) flag = 1;
+      else if (!(s < __builtin_huge_val()) && flag == 0) flag = 2;
+    }
+    for (int f = sub; f < 128; f += 16) {
+      double mean = 0.0;
+      if (f < k && flag == 0)
+        for (int v = v0; v < v1; ++v) mean += (double)vecs[(vrow ? vrow[v] : (int64_t)v) * k + f] / qn[v];
+      xb[qi][f] = (n && flag == 0) ? (float)(mean / n) : 0.f;
+    }
+    if (sub == 0) {
+      nrm[qi] = n ? 1.000001f : 0.f;
+      if (q < n_queries) qflag[q] = flag;
+    }
+  } else {
+    for (int f = sub; f < 128; f += 16) {
+      double mean = 0.0;
+      if (f < k)
+        for (int v = v0; v < v1; ++v) mean += (double)vecs[(vrow ? vrow[v] : (int64_t)v) * k + f];
+      xb[qi][f] = n ? (float)(mean / n) : 0.f;
+    }
+    double norms = 0.0;
+    for (int v = v0; v < v1; ++v) {
+      const float* x = vecs + (vrow ? vrow[v] : (int64_t)v) * k;
+      double ss = 0.0;
+      for (int f = sub; f < k; f += 16) ss += (double)x[f] * (double)x[f];
 #pragma unroll
-    for (int off = 8; off > 0; off >>= 1) ss += __shfl_xor(ss, off);  // the 16 lanes of this query
-    norms += sqrt(ss);
+      for (int off = 8; off > 0; off >>= 1) ss += __shfl_xor(ss, off);  // the 16 lanes of this query
+      norms += sqrt(ss);
+    }
+    if (sub == 0) nrm[qi] = n ? (float)(norms / n * 1.000001) : 0.f;
   }
-  if (sub == 0) nrm[qi] = n ? (float)(norms / n * 1.000001) : 0.f;
   __syncthreads();
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
@@ -156,7 +258,7 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
     for (int j = 0; j < 8; ++j) m[j] = (__bf16)0.f;
     if (g == 0) {
       if (16 * t + c < n_queries) {
-        m[0] = bf16_up(TOPN_MARGIN * nrm[c]);
+        m[0] = bf16_up((COS ? TOPN_COS_MARGIN : TOPN_MARGIN) * nrm[c]);
         m[1] = bf16_up(TOPN_MARGIN_FLOOR);
       } else {
         m[2] = (__bf16)(-1e30f);  // a padding query never has a candidate
@@ -190,7 +292,10 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
 //         positions come from a ballot, not from an atomic -- a returning atomic in this loop waits on the same counter as
 //         the prefetched rows.  When a wave has run out of item tiles it sorts its own hits into the per-query candidate lists.
 // The filter's grid is persistent (as many workgroups as fit the chip at once).
-template <int S, int QT, int MODE, int LM>
+// COS (cosine mode, header): the margin step's A operand is {|y_i| up, +-1, |y_i| hi, lo, hi, lo, 0, 0} against the query's
+// {M_c, floor, -tau hi, hi, lo, lo}; the sample keeps lower bounds divided by the item's |y_i| (the stage's norms pass
+// through LDS, 256 B); items of zero / non-finite norm never win a bucket and are never hits.
+template <int S, int QT, int MODE, int LM, bool COS = false>
 __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __restrict__ Y, int64_t n_items, int k,
                                                           const bf16x8* __restrict__ img, int n_queries, int tile_stride,
                                                           float* __restrict__ bmax, uint32_t* __restrict__ bidx,
@@ -200,6 +305,7 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
   constexpr int CH = 8 * S;  // features per lane
   constexpr int E = S + 1;   // A operands per item tile: S contraction steps + the margin step
   __shared__ __attribute__((aligned(16))) bf16x8 sa2[2][4 * E * 64];  // two stages x [item tile of the stage][operand][lane]
+  __shared__ float sny[COS ? 2 : 1][4][16];                            // COS: |y| of the stage's items, per buffer
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   // this wave's query tiles, once
   bf16x8 bq[QT][S], bm[QT];
@@ -216,8 +322,16 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
         float v = -tq;
         if (!(tq > -__builtin_huge_valf())) v = 1e30f;  // no threshold: everything is a candidate (the pass falls back)
         const __bf16 hi = (__bf16)v;
-        m[2] = hi;
-        m[3] = bf16_up(v - (float)hi);
+        if (COS) {  // against {|y| hi, lo, hi, lo} in slots 2-5
+          const __bf16 lo = bf16_up(v - (float)hi);
+          m[2] = hi;
+          m[3] = hi;
+          m[4] = lo;
+          m[5] = lo;
+        } else {
+          m[2] = hi;
+          m[3] = bf16_up(v - (float)hi);
+        }
       }
     }
     bm[j] = m;
@@ -295,7 +409,23 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
       const float ny = __builtin_sqrtf(nsq) * 1.0000005f;  // |y_c| of the tile's 16 items
 #pragma unroll
       for (int j = 0; j < 8; ++j) am[j] = (__bf16)0.f;
-      if (g == 0) {
+      if (COS) {
+        const float n0 = __builtin_sqrtf(nsq);
+        const bool finite = n0 > 0.f && n0 < __builtin_huge_valf();
+        if (g == 0) {
+          sny[buf][w][c] = n0;
+          am[0] = MODE == 0 ? (__bf16)(-(float)bf16_up(ny)) : bf16_up(ny);
+          am[1] = (__bf16)(MODE == 0 || !finite ? -1.f : 1.f);  // a zero row: -floor, never a hit
+          if (MODE == 1) {
+            const __bf16 hi = (__bf16)n0;
+            const __bf16 lo = (__bf16)(n0 - (float)hi);
+            am[2] = hi;
+            am[3] = lo;
+            am[4] = hi;
+            am[5] = lo;
+          }
+        }
+      } else if (g == 0) {
         am[0] = MODE == 0 ? (__bf16)(-(float)bf16_up(ny)) : bf16_up(ny);  // the sample wants approx - margin
         am[1] = (__bf16)(MODE == 0 ? -1.f : 1.f);
         am[2] = (__bf16)1.f;
@@ -309,6 +439,7 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
     // two LDS buffers, one barrier per stage: a wave writes buffer b again only after the barrier of the stage in between,
     // which every wave reaches after it has finished reading b (the second barrier per stage cost a quarter of the kernel)
     bf16x8* sa = sa2[buf];
+    const int cb = buf;  // (COS: this stage's norms in sny[cb])
     buf ^= 1;
 #pragma unroll
     for (int s = 0; s < S; ++s) sa[(w * E + s) * 64 + lane] = ah[s];
@@ -331,7 +462,23 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
       for (int j = 0; j < QT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[S], bm[j], acc[j], 0, 0, 0);
       if (i0 >= n_items) continue;  // uniform
       // D layout: lane (g, c) register r = D[row 4 g + r][col c]: item 4 g + r of the tile, query 16 (4 j + w) + c
-      if (MODE == 0) {
+      if (MODE == 0 && COS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t it = i0 + 4 * g + r;
+          const float nr = sny[cb][jt][4 * g + r];
+          const bool in = it < n_items && nr > 0.f && nr < __builtin_huge_valf();
+          const float rn = 1.f / nr;
+#pragma unroll
+          for (int j = 0; j < QT; ++j) {
+            const float lb = acc[j][r] * rn;
+            if (in && lb > best[j][r]) {  // a NaN never wins
+              best[j][r] = lb;
+              besti[j][r] = (uint32_t)it;
+            }
+          }
+        }
+      } else if (MODE == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t it = i0 + 4 * g + r;
@@ -367,7 +514,11 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int64_t it = i0 + 4 * g + r;
-              const bool hit = (int32_t)__float_as_uint(acc[j][r]) > TOPN_HIT && it < n_items && q < n_queries;
+              bool hit = (int32_t)__float_as_uint(acc[j][r]) > TOPN_HIT && it < n_items && q < n_queries;
+              if (COS) {  // a NaN / infinite row (its accumulators are NaN): every similarity of it is skipped
+                const float nr = sny[cb][jt][4 * g + r];
+                hit = hit && nr > 0.f && nr < __builtin_huge_valf();
+              }
               const uint64_t hm = __ballot(hit);
               if (hm) {
                 const unsigned at = n_hits + (unsigned)__popcll(hm & ((1ull << lane) - 1ull));
@@ -478,7 +629,8 @@ __global__ __launch_bounds__(1024) void topn_threshold_kernel(float* __restrict_
                                                               int how_many, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                               const int64_t* __restrict__ query_row, const int64_t* __restrict__ excl_ptr,
                                                               const int64_t* __restrict__ excl_idx, int64_t n_items, int tile_stride,
-                                                              const uint32_t* __restrict__ tag_bits, float* __restrict__ tau) {
+                                                              const uint32_t* __restrict__ tag_bits, float* __restrict__ tau,
+                                                              const uint32_t* __restrict__ qflag) {
   __shared__ unsigned h[256], sfx[256];
   __shared__ uint32_t s_prefix, s_rem;
   const int q = blockIdx.x;
@@ -557,7 +709,14 @@ __global__ __launch_bounds__(1024) void topn_threshold_kernel(float* __restrict_
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) tau[q] = (s_rem >= 0x80000000u || s_prefix <= ninf_key) ? -__builtin_huge_valf() : key_score(s_prefix);
+  if (threadIdx.x == 0) {
+    float t = (s_rem >= 0x80000000u || s_prefix <= ninf_key) ? -__builtin_huge_valf() : key_score(s_prefix);
+    // cosine mode (topn_prepare_kernel<true>): a query item of norm 0 / NaN -- no candidates, answered empty; of norm +inf --
+    // no threshold, the dense path answers
+    if (qflag && qflag[q] == 1u) t = TOPN_COS_DEAD_TAU;
+    if (qflag && qflag[q] == 2u) t = -__builtin_huge_valf();
+    tau[q] = t;
+  }
 }
 
 // ---- exact rescoring of the candidates --------------------------------------------------------------------------------
@@ -566,13 +725,16 @@ __global__ __launch_bounds__(1024) void topn_threshold_kernel(float* __restrict_
 // LDS with coalesced loads (16 lanes per row), then lane l computes candidate l's score from LDS in the reference's
 // order.  (A lane walking its own row in global memory is 64 loads that each touch 64 different lines: 60 us per pass of
 // 240 queries.)  The query's known and excluded items pass through LDS a thousand at a time.
+// COS: the cosine score (topn_cos_score) with the query norms qn; a candidate with a non-finite similarity is struck (never
+// the overflow word), as is an index outside [0, n_items) (a known-item list entry of recommendedBecause)
+template <bool COS>
 __global__ __launch_bounds__(64) void topn_rescore_kernel(const float* __restrict__ Y, int k, const float* __restrict__ vecs,
                                                           const int64_t* __restrict__ vrow, const int32_t* __restrict__ vptr, const unsigned* __restrict__ count, int cap,
                                                           const uint32_t* __restrict__ cand, const int64_t* __restrict__ row_ptr,
                                                           const int32_t* __restrict__ col, const int64_t* __restrict__ query_row,
                                                           const int64_t* __restrict__ excl_ptr, const int64_t* __restrict__ excl_idx,
                                                           const uint32_t* __restrict__ tag_bits, uint64_t* __restrict__ pairs,
-                                                          unsigned* __restrict__ overflow) {
+                                                          unsigned* __restrict__ overflow, const double* __restrict__ qn, int64_t n_items) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   float* ys = reinterpret_cast<float*>(smem);  // [64][k + 1]
   __shared__ uint32_t sk[1024];
@@ -596,8 +758,13 @@ __global__ __launch_bounds__(64) void topn_rescore_kernel(const float* __restric
   for (unsigned base = blockIdx.x * 64; base < n; base += gridDim.x * 64) {
     const unsigned p = base + lane;
     const bool valid = p < n;
-    const uint32_t it = valid ? cand[(int64_t)q * cap + p] : 0u;
-    bool struck = valid && topn_tagged(tag_bits, (int64_t)it);
+    uint32_t it = valid ? cand[(int64_t)q * cap + p] : 0u;
+    bool struck = false;
+    if (COS && (int64_t)it >= n_items) {
+      struck = true;
+      it = 0u;  // (row 0 is staged in its place)
+    }
+    struck = struck || (valid && topn_tagged(tag_bits, (int64_t)it));
     for (int64_t c0 = 0; c0 < n_list; c0 += 1024) {
       __syncthreads();
       for (int i = lane; i < 1024 && c0 + i < n_list; i += 64) {
@@ -653,7 +820,11 @@ __global__ __launch_bounds__(64) void topn_rescore_kernel(const float* __restric
     __syncthreads();
     if (valid) {
       uint64_t out = 0;
-      if (!struck) {
+      if (COS) {
+        float sc;
+        if (!struck && topn_cos_score(ys + lane * pitch, vecs, vrow, qn, v0, v1, k, &sc))
+          out = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xffffffffu - it);
+      } else if (!struck) {
         const float sc = topn_ref_score(ys + lane * pitch, vecs, vrow, v0, v1, k);
         if (!(fabsf(sc) < __builtin_huge_valf())) atomicAdd(overflow, 1u);   // NaN / infinite: the dense path decides and reports
         out = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xffffffffu - it);
@@ -728,10 +899,13 @@ __global__ __launch_bounds__(256) void topn_final_kernel(const uint64_t* __restr
 
 // ---- the dense path: exact scores of every item -----------------------------------------------------------------------
 // scores[q][i] for a 64-item tile per workgroup: the tile's rows are staged in LDS (coalesced), wave w takes the queries
-// w, w + 4, ...: lane = item, the query's vectors are read with wave-uniform addresses.
+// w, w + 4, ...: lane = item, the query's vectors are read with wave-uniform addresses.  COS: the cosine score (qn: the query
+// norms); a skipped item (non-finite similarity) scores -inf.
+template <bool COS>
 __global__ __launch_bounds__(256) void topn_exact_dense_kernel(const float* __restrict__ Y, int64_t n_items, int k,
                                                                const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
-                                                               const int32_t* __restrict__ vptr, int n_queries, float* __restrict__ scores) {
+                                                               const int32_t* __restrict__ vptr, int n_queries, float* __restrict__ scores,
+                                                               const double* __restrict__ qn) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   float* ys = reinterpret_cast<float*>(smem);  // [64][k + 1]
   const int pitch = k + 1;
@@ -745,6 +919,12 @@ __global__ __launch_bounds__(256) void topn_exact_dense_kernel(const float* __re
       const float* y = ys + lane * pitch;
       for (int q = w; q < n_queries; q += 4) {
         const int v0 = __builtin_amdgcn_readfirstlane(vptr[q]), v1 = __builtin_amdgcn_readfirstlane(vptr[q + 1]);
+        if (COS) {
+          float sc;
+          if (!topn_cos_score(y, vecs, vrow, qn, v0, v1, k, &sc)) sc = -__builtin_huge_valf();
+          scores[(int64_t)q * n_items + i0 + lane] = sc;
+          continue;
+        }
         const float sc = topn_ref_score(y, vecs, vrow, v0, v1, k);
         // (a NaN of either sign as THE NaN that score_key sorts above +inf: a non-finite score is then the first result of its
         // query, where topn_emit looks for it -- RecommendIterator.java:105)

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import MEM_DEVICE, MEM_HOST, SIDE_X, SIDE_Y
-from .core import ALSCore, Cancelled, MalsError, SingularSystem
+from .core import ALSCore, Cancelled, MalsError, SingularSystem, _item_queries
 
 
 def plan_shards(row_ptr, world, features, row_cost=-1.0):
@@ -247,6 +247,37 @@ class GroupALS:
         cnt = np.empty(len(u), dtype=np.int32)
         self._chk(self._L.mals_group_recommend(self._g, u.ctypes.data_as(ctypes.c_void_p), len(u), int(how_many), 1 if consider_known_items else 0,
                                                idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        return idx, sc, cnt
+
+    def most_similar_items(self, items, how_many):
+        """mostSimilarItems on the group (any local member: the Y replicas are complete)."""
+        flat, ptr = _item_queries(items)
+        idx = np.empty((len(ptr) - 1, how_many), dtype=np.int64)
+        sc = np.empty((len(ptr) - 1, how_many), dtype=np.float32)
+        cnt = np.empty(len(ptr) - 1, dtype=np.int32)
+        self._chk(self._L.mals_group_most_similar_items(self._g, flat.ctypes.data_as(ctypes.c_void_p), ptr.ctypes.data_as(ctypes.c_void_p),
+                                                        len(ptr) - 1, int(how_many), idx.ctypes.data_as(ctypes.c_void_p),
+                                                        sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        return idx, sc, cnt
+
+    def similarity_to_item(self, to_item, items):
+        ii = np.ascontiguousarray(items, dtype=np.int64)
+        out = np.empty(len(ii), dtype=np.float32)
+        self._chk(self._L.mals_group_similarity_to_item(self._g, int(to_item), ii.ctypes.data_as(ctypes.c_void_p), len(ii),
+                                                        out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def recommended_because(self, users, items, how_many):
+        """recommendedBecause on the group: every query answered by the member that holds the user's row."""
+        u = np.ascontiguousarray(users, dtype=np.int64)
+        ii = np.ascontiguousarray(items, dtype=np.int64)
+        assert len(u) == len(ii)
+        idx = np.empty((len(u), how_many), dtype=np.int64)
+        sc = np.empty((len(u), how_many), dtype=np.float32)
+        cnt = np.empty(len(u), dtype=np.int32)
+        self._chk(self._L.mals_group_recommended_because(self._g, u.ctypes.data_as(ctypes.c_void_p), ii.ctypes.data_as(ctypes.c_void_p), len(u),
+                                                         int(how_many), idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+                                                         cnt.ctypes.data_as(ctypes.c_void_p)))
         return idx, sc, cnt
 
     def bounds(self, side):

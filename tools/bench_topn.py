@@ -2,7 +2,10 @@
 """Top-N scoring on one MI355X: queries/s of mals_recommend for model users
 against n_items item vectors resident in HBM, per batch size, + the oracle (numpy restatement of
 RecommendIterator + TopN, 1 core) on a few queries.
-usage: python tools/bench_topn.py [--items N] [--users U] [--features K] [--how-many N]"""
+usage: python tools/bench_topn.py [--items N] [--users U] [--features K] [--how-many N]
+       python tools/bench_topn.py --similar [--lib-root DIR]: mostSimilarItems (mals_most_similar_items, one item per
+       query) next to recommend in the same run, per batch size; --lib-root imports the package (and its library) from
+       another checkout, whose recommend leg alone then runs (an A/B of recommend against an older build)"""
 import argparse
 import json
 import os
@@ -20,7 +23,12 @@ def main():
     ap.add_argument("--features", type=int, default=64)
     ap.add_argument("--how-many", type=int, default=10)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--similar", action="store_true")
+    ap.add_argument("--lib-root", default=None)
+    ap.add_argument("--reps", type=int, default=3)
     a = ap.parse_args()
+    if a.similar:
+        return similar(a)
     import numpy as np
     import myrrix_recommender_amd as pkg
     rng = np.random.default_rng(1234567890)
@@ -129,6 +137,56 @@ def main():
             to.recommend(Y, X[u], a.how_many, col[rp[u]:rp[u + 1]])
         out["cpu_baseline"] = {"value": nq / (time.perf_counter() - t0), "unit": "queries/s", "cores": 1, "kind": "port",
                                "sample": "%d queries, oracle/topn_oracle.py (numpy)" % nq}
+    print(json.dumps(out))
+
+
+def similar(a):
+    """mostSimilarItems against recommend, the same batches in the same run: queries/s and Y_stream_frac (Y read once
+    per pass of up to per_pass queries, over 8 TB/s)"""
+    if a.lib_root:
+        sys.path.insert(0, os.path.abspath(a.lib_root))
+    import numpy as np
+    import myrrix_recommender_amd as pkg
+    rng = np.random.default_rng(1234567890)
+    k = a.features
+    Y = (rng.standard_normal((a.items, k)) / np.sqrt(k)).astype(np.float32)
+    X = (rng.standard_normal((a.users, k)) / np.sqrt(k)).astype(np.float32)
+    deg = 100
+    rp = np.arange(a.users + 1, dtype=np.int64) * deg
+    col = rng.integers(0, a.items, a.users * deg).astype(np.int32)
+    per_pass = 16 * {1: 16, 2: 15, 3: 10, 4: 7}[(k + 31) // 32]
+    out = {"metric": "mostSimilarItems and recommend queries/s, same run", "unit": "queries/s", "items": a.items, "features": k,
+           "how_many": a.how_many, "queries_per_pass": per_pass, "lib": pkg._lib.LIB_PATH, "recommend": {}, "similar": {}}
+    with pkg.ALSCore(k) as core:
+        core.set_factor_rows(pkg.SIDE_X, a.users)
+        core.set_factor_rows(pkg.SIDE_Y, a.items)
+        core.set_factors(pkg.SIDE_X, X)
+        core.set_factors(pkg.SIDE_Y, Y)
+        core.set_matrix(pkg.SIDE_X, rp, col, np.ones(len(col), np.float32))
+        legs = {"recommend": lambda q: core.recommend(q, a.how_many)}
+        if hasattr(core, "most_similar_items"):
+            legs["similar"] = lambda q: core.most_similar_items(q, a.how_many)
+        else:
+            del out["similar"]
+        for batch in (1, 64, per_pass, 4096):
+            qs = {"recommend": rng.integers(0, a.users, batch).astype(np.int64), "similar": rng.integers(0, a.items, batch).astype(np.int64)}
+            for name, fn in legs.items():
+                fn(qs[name])                                            # warm
+                reps = max(10, 4096 // batch)
+                runs = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    for _ in range(reps):
+                        fn(qs[name])
+                    runs.append((time.perf_counter() - t0) / reps)
+                dt = min(runs)
+                passes = (batch + per_pass - 1) // per_pass
+                y_bytes = passes * a.items * k * 4
+                out[name][str(batch)] = {"ms_per_call": dt * 1e3, "ms_per_call_runs": [r * 1e3 for r in runs], "queries_per_s": batch / dt,
+                                         "passes": passes, "Y_stream_frac": y_bytes / dt / 8e12}
+        if "similar" in out:
+            out["similar_over_recommend"] = {b: out["similar"][b]["queries_per_s"] / out["recommend"][b]["queries_per_s"] for b in out["similar"]}
+    out["value"] = out["similar"]["4096"]["queries_per_s"] if "similar" in out else out["recommend"]["4096"]["queries_per_s"]
     print(json.dumps(out))
 
 
