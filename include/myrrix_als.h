@@ -392,6 +392,80 @@ int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_
 int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
                              int64_t* item_idx_out, float* score_out, int32_t* n_out);
 
+/* ---- the online write path: setPreference / removePreference and the fold-in reads -------------------------------
+ * ServerRecommender (online/src/net/myrrix/online/ServerRecommender.java) changes the model on every write between two
+ * generations; these calls do it to the X, Y and known items resident on the device, in the reference's arithmetic (every
+ * result bit-identical to the CPU restatement tests/foldin_oracle.py).  For handles OUTSIDE a group: a member's handle is
+ * refused (MALS_INVALID_ARG; the mals_group_* twins are a later addition).  Rows are dense indices (user = row of X,
+ * item = row of Y); mapping ids, the candidate filter, clustering, tags and generationManager.append stay with the caller.
+ * THREADS: every call below may be made from any thread while mals_recommend* / similarity calls run on the same handle.
+ * Each (but mals_foldin_stats) is an exclusive ticket in the serving front's queue -- mals_recommend_to_anonymous is two,
+ * see there: passes formed before it see the old model, passes formed after it the new one; concurrent writes are
+ * applied one after another in queue order.
+ *
+ * The generation's solvers (Generation.getXTXSolver / getYTYSolver) on the device: s from mals_recompute_solver or
+ * mals_solver_create (its factors are copied; s stays the caller's).  side X = the solver of X^T X, side Y = of Y^T Y;
+ * s = NULL clears that side.  The writes never recompute them (the reference keeps them until the next generation). */
+int mals_set_foldin_solver(mals_handle h, int side, mals_solver s);
+/* FOLDIN_LEARN_RATE (ServerRecommender.java:98-99), default 1.0. */
+int mals_set_foldin_learn_rate(mals_handle h, double rate);
+/* out6 = {updates applied, updates failed, "fold in vector is large" warnings the reference would have logged (norm of
+ * userFoldIn > BIG_FOLDIN_THRESHOLD = 1e4, counted once per branch that reads it, :889 and :899), levels run, device
+ * nanoseconds of the level kernels (HIP events around them) over all calls, the same for the last call} of
+ * mals_set_preferences since mals_create.  Read without a ticket: it never waits for a pass. */
+int mals_foldin_stats(mals_handle h, int64_t* out6);
+/* Solver.solveFToD on the device (the solve every write uses): x_out[q] = A^-1 (double) b[q] for n_rhs vectors of
+ * features floats, with the solver of `side` -- bit-identical to mals_solver_solve_ftod. */
+int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, double* x_out);
+/* setPreference (:770-836, updateFeatures :865-912) for n updates: the result is exactly what n calls in array order
+ * leave.  Update t, from the rows as they stand after the earlier updates:
+ *   estimate = dot(x_u, y_i) (fp32 products, fp64 sum); not finite: the update fails before anything changes (:982);
+ *   w = foldInWeight(estimate, value) (:981-994); w == 0: only the known items change (:870-872);
+ *   itemFoldIn = solveFToD_XTX(x_u), userFoldIn = solveFToD_YTY(y_i), both from the rows before the update;
+ *   y_i[f] += (float)(w * itemFoldIn[f]) (XTX solver set), then x_u[f] += (float)(w * userFoldIn[f]) (YTY solver set);
+ *   a non-finite delta stops that update at that element (:893 / :903): the elements before it keep their new values;
+ *   in the item loop x_u is not touched; the known items do not change;
+ *   the user's known items gain i.
+ * Solvers: no XTX solver: only x_u moves.  An XTX solver WITHOUT a YTY solver: the reference's item branch reads
+ * norm(userFoldIn) of a null vector and throws before anything changes -- every update with w != 0 fails so, and adds no
+ * known item.  status_out (n, nullable): MALS_OK or the code of each update; the other updates of the batch go on.
+ * Returns the code of the first failed update (array order), else MALS_OK.  Every row must be inside the replicas
+ * (new users / items: mals_grow_factor_rows first) and every user inside this handle's local shard.  Every write makes
+ * the next half-iteration recompute its Gramian.  Updates that touch disjoint rows run side by side on the device; an
+ * update waits for the last earlier update of its user and of its item (a hot item updated m times is m levels). */
+int mals_set_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out);
+/* removePreference (:1001-1074) for n pairs in order: a user without known items, or an item the user does not know, is
+ * ignored; otherwise the item leaves the user's known items, and when that empties them the user is removed: its row of
+ * X is zeroed (a later setPreference recreates it from zeros, getFeatures :838-863) and reported in removed_users_out
+ * (capacity n; *n_removed_out of them) -- the caller drops the id (NoSuchUserException from then on). */
+int mals_remove_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,
+                            int64_t* n_removed_out);
+/* getFeatures (:838-863) for unseen users / items: grow a replica the library owns to n_rows_total rows (content kept, new
+ * rows zero; capacity doubles, so a stream of new rows does not copy the replica each time).  A bound replica
+ * (mals_bind_factors) is MALS_INVALID_ARG.  Side Y extends the userTagIDs with zeros; new users (side X) have no known
+ * items and are valid users of mals_recommend / mals_recommended_because on this handle.  Iterations afterwards run on
+ * the grown shapes.  The known-item changes of the writes (kept beside the installed known items / the rows of R, which
+ * are never written) are dropped by mals_set_known_items, mals_set_matrix of side X and mals_ingest_install*. */
+int mals_grow_factor_rows(mals_handle h, int side, int64_t n_rows_total);
+/* estimatePreferences (:690-727): out[t] = (float)dot(x_u, y_i); a row of -1 (unknown user or item) gives 0.0f.  A
+ * non-finite estimate is MALS_INVALID_ARG (checkState, :718); out still holds every value (the bad ones not finite). */
+int mals_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out);
+/* buildAnonymousUserFeatures (:561-609): query q owns the items item_row[item_ptr[q] .. item_ptr[q+1]) with values (NULL:
+ * 1.0 each); rows -1 are skipped; out[q] = sum over the items in order of (float)(foldInWeight(0, value) *
+ * solveFToD_YTY(y_item)[f]), accumulated in fp32 (n_queries x features).  A query without an item that has a row, or a
+ * handle without a YTY solver, fails (status_out[q], nullable; the first failure's code is returned). */
+int mals_anonymous_features(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                            float* out, int32_t* status_out);
+/* recommendToAnonymous (:511-559): the vectors of mals_anonymous_features through mals_recommend_to_many, each query's
+ * items excluded (and userTagIDs struck as always).  Failed queries (status_out) come back empty (-1 / -inf, n_out 0).
+ * TWO tickets, the vectors and then the top-N: a write may land between them (the reference holds no lock across the
+ * two steps either). */
+int mals_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                                int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out);
+/* estimateForAnonymous (:734-759): out[q] = (float)dot(anonymous features of query q, y_to_item[q]). */
+int mals_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
+                                const float* values, float* out, int32_t* status_out);
+
 /* ---- ingest -> CSR ------------------------------------------------------
  * What InputFilesReader.readInputFiles (online-local/src/net/myrrix/online/generation/
  * InputFilesReader.java:64-211) does to the parsed records of the input files, on the device: the

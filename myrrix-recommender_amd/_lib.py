@@ -155,6 +155,17 @@ SYMBOLS = {
     "mals_most_similar_items": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
     "mals_similarity_to_item": (ctypes.c_int, [_H, ctypes.c_int64, _P, _I32, _P]),
     "mals_recommended_because": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
+    "mals_set_foldin_solver": (ctypes.c_int, [_H, ctypes.c_int, _H]),
+    "mals_set_foldin_learn_rate": (ctypes.c_int, [_H, ctypes.c_double]),
+    "mals_foldin_stats": (ctypes.c_int, [_H, _P]),
+    "mals_foldin_solve": (ctypes.c_int, [_H, ctypes.c_int, _P, _I32, _P]),
+    "mals_set_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P, _P]),
+    "mals_remove_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "mals_grow_factor_rows": (ctypes.c_int, [_H, ctypes.c_int, _I64]),
+    "mals_estimate_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P]),
+    "mals_anonymous_features": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P]),
+    "mals_recommend_to_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "mals_estimate_for_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P, _P]),
     "mals_set_tag_items": (ctypes.c_int, [_H, _I64, _P, ctypes.c_int]),
     "mals_get_tag_item_count": (ctypes.c_int, [_H, ctypes.POINTER(_I64)]),
     "mals_ingest_device": (ctypes.c_int, [_H, ctypes.POINTER(_I32)]),

@@ -459,6 +459,114 @@ class ALSCore:
                                                    cnt.ctypes.data_as(ctypes.c_void_p)))
         return idx, sc, cnt
 
+    # -- the online write path (setPreference / removePreference and the fold-in reads) ---------------------------
+    def set_foldin_solver(self, side, solver):
+        """The generation's solver of side's M^T M (HostSolver, or None to clear) for the writes and fold-in reads."""
+        self._chk(self._L.mals_set_foldin_solver(self._h, side, solver._s if solver is not None else None))
+
+    def set_foldin_learn_rate(self, rate):
+        self._chk(self._L.mals_set_foldin_learn_rate(self._h, float(rate)))
+
+    def foldin_stats(self):
+        """Counters of mals_set_preferences since the handle was created; device_ms: HIP-event time of the level kernels (all
+        calls / the last call)."""
+        o = np.zeros(6, dtype=np.int64)
+        self._chk(self._L.mals_foldin_stats(self._h, o.ctypes.data_as(ctypes.c_void_p)))
+        return {"applied": int(o[0]), "failed": int(o[1]), "big_foldin": int(o[2]), "levels": int(o[3]),
+                "device_ms_total": o[4] * 1e-6, "device_ms_last": o[5] * 1e-6}
+
+    def foldin_solve(self, side, b):
+        """Solver.solveFToD on the device with side's fold-in solver, for the rows of b (n x features float32)."""
+        b = np.ascontiguousarray(np.atleast_2d(_host(b, np.float32)))
+        x = np.empty(b.shape, dtype=np.float64)
+        self._chk(self._L.mals_foldin_solve(self._h, side, b.ctypes.data_as(ctypes.c_void_p), len(b), x.ctypes.data_as(ctypes.c_void_p)))
+        return x
+
+    def set_preferences(self, users, items, values, raise_on_error=True):
+        """setPreference for each (users[t], items[t], values[t]) in order.  Returns the per-update status array; raises on
+        the first failed update unless raise_on_error is False."""
+        u, i, v = _host(users, np.int64), _host(items, np.int64), _host(values, np.float32)
+        assert len(u) == len(i) == len(v)
+        st = np.zeros(len(u), dtype=np.int32)
+        rc = self._L.mals_set_preferences(self._h, len(u), u.ctypes.data_as(ctypes.c_void_p), i.ctypes.data_as(ctypes.c_void_p),
+                                          v.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if raise_on_error or rc not in (_lib.OK, _lib.INVALID_ARG) or not st.any():
+            self._chk(rc)
+        return st
+
+    def remove_preferences(self, users, items):
+        """removePreference for each pair in order.  Returns the user rows that lost their last known item (zeroed)."""
+        u, i = _host(users, np.int64), _host(items, np.int64)
+        assert len(u) == len(i)
+        out = np.zeros(max(len(u), 1), dtype=np.int64)
+        n = ctypes.c_int64(0)
+        self._chk(self._L.mals_remove_preferences(self._h, len(u), u.ctypes.data_as(ctypes.c_void_p), i.ctypes.data_as(ctypes.c_void_p),
+                                                  out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n)))
+        return out[:n.value].copy()
+
+    def grow_factor_rows(self, side, n_rows_total):
+        self._chk(self._L.mals_grow_factor_rows(self._h, side, int(n_rows_total)))
+
+    def estimate_preferences(self, users, items):
+        u, i = _host(users, np.int64), _host(items, np.int64)
+        out = np.empty(len(u), dtype=np.float32)
+        self._chk(self._L.mals_estimate_preferences(self._h, len(u), u.ctypes.data_as(ctypes.c_void_p), i.ctypes.data_as(ctypes.c_void_p),
+                                                    out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    @staticmethod
+    def _anon_args(queries, values):
+        flat, ptr = _item_queries(queries)
+        vals = None
+        if values is not None:
+            vals = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float32).ravel() for v in values]) if len(flat) else np.zeros(0, np.float32))
+            assert len(vals) == len(flat)
+        return flat, ptr, vals
+
+    def anonymous_features(self, queries, values=None, raise_on_error=True):
+        """buildAnonymousUserFeatures per query (a list of item-row lists, -1 = unknown item): (features [q][k], status)."""
+        flat, ptr, vals = self._anon_args(queries, values)
+        nq = len(ptr) - 1
+        out = np.zeros((nq, self.features), dtype=np.float32)
+        st = np.zeros(nq, dtype=np.int32)
+        rc = self._L.mals_anonymous_features(self._h, nq, ptr.ctypes.data_as(ctypes.c_void_p), flat.ctypes.data_as(ctypes.c_void_p),
+                                             vals.ctypes.data_as(ctypes.c_void_p) if vals is not None else None,
+                                             out.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if raise_on_error or not st.any():
+            self._chk(rc)
+        return out, st
+
+    def recommend_to_anonymous(self, queries, how_many, values=None):
+        """recommendToAnonymous: (item_idx, scores, counts, status) per query."""
+        flat, ptr, vals = self._anon_args(queries, values)
+        nq = len(ptr) - 1
+        idx = np.empty((nq, how_many), dtype=np.int64)
+        sc = np.empty((nq, how_many), dtype=np.float32)
+        cnt = np.empty(nq, dtype=np.int32)
+        st = np.zeros(nq, dtype=np.int32)
+        rc = self._L.mals_recommend_to_anonymous(self._h, nq, ptr.ctypes.data_as(ctypes.c_void_p), flat.ctypes.data_as(ctypes.c_void_p),
+                                                 vals.ctypes.data_as(ctypes.c_void_p) if vals is not None else None, int(how_many),
+                                                 idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+                                                 cnt.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if not st.any():
+            self._chk(rc)
+        return idx, sc, cnt, st
+
+    def estimate_for_anonymous(self, to_items, queries, values=None):
+        """estimateForAnonymous per query: (float32 estimates, status)."""
+        flat, ptr, vals = self._anon_args(queries, values)
+        nq = len(ptr) - 1
+        to = _host(to_items, np.int64)
+        assert len(to) == nq
+        out = np.zeros(nq, dtype=np.float32)
+        st = np.zeros(nq, dtype=np.int32)
+        rc = self._L.mals_estimate_for_anonymous(self._h, nq, to.ctypes.data_as(ctypes.c_void_p), ptr.ctypes.data_as(ctypes.c_void_p),
+                                                 flat.ctypes.data_as(ctypes.c_void_p), vals.ctypes.data_as(ctypes.c_void_p) if vals is not None else None,
+                                                 out.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if not st.any():
+            self._chk(rc)
+        return out, st
+
     def reconstruction_error(self):
         """ReconstructionEvaluator's sum and count over the local user rows (mean = sum / count)."""
         sm, cnt = ctypes.c_double(0.0), ctypes.c_int64(0)

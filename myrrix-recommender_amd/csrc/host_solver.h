@@ -33,6 +33,11 @@ class PivotedQR {
   }
 
   int dim() const { return n_; }
+  // the factorization as solve() reads it (the device fold-in of foldin_kernels.h restates solve() on these):
+  // column-major n x n (R on and above the diagonal, reflector tails below), tau, the column pivots
+  const double* factors() const { return a_.data(); }
+  const double* taus() const { return tau_.data(); }
+  const int* pivots() const { return piv_.data(); }
 
   bool non_singular() const {
     for (int j = 0; j < n_; ++j)

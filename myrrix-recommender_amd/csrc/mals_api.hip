@@ -10,6 +10,7 @@
 #include "host_eigen.h"
 #include "host_solver.h"
 #include "topn_kernels.h"
+#include "foldin_kernels.h"
 #include "mals_internal.h"
 #include "hip_buffer.h"
 
@@ -24,12 +25,15 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <functional>
+#include <iterator>
 #include <limits>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #ifndef MALS_D4
@@ -215,6 +219,13 @@ struct mals_handle_s {
   DeviceBuffer<int64_t> d_sd_idx;
   DeviceBuffer<int64_t> d_idx;  // gather scratch
   DeviceBuffer<float> d_rows;
+  void* fo = nullptr;           // the online write path (foldin_host.h): device solvers, known-item overlay, levels
+  bool group_member = false;    // a member of a mals_group (malsi_mark_group_member): the write path refuses it
+  // mals_foldin_stats: applied, failed, large fold-ins, levels, device ns (all calls), device ns (last call) -- atomics,
+  // read without a ticket
+  std::atomic<int64_t> foldin_counters[6] = {};
+  // one past the last user row mals_grow_factor_rows added to this handle's users (-1: none); read by request threads
+  std::atomic<int64_t> grown_users_end{-1};
 };
 
 namespace {
@@ -245,7 +256,15 @@ int use_device(mals_handle h) {
   return MALS_OK;
 }
 
+// foldin_host.h (included after topn_host.h, which needs these)
+void foldin_drop_overlay(mals_handle h);
+bool foldin_known_view(mals_handle h, int64_t local_row, std::vector<int64_t>& out);
+bool foldin_has_overlay(mals_handle h);
+int foldin_known_full(mals_handle h, const std::vector<int64_t>& rows, std::vector<std::vector<int32_t>>& outs, std::string& msg);
+int64_t foldin_user_rows_end(mals_handle h);
+
 void clear_known_items(mals_handle h) {
+  foldin_drop_overlay(h);   // a new generation's known items: the writes of the old one are gone with it
   h->known_ptr_copy.reset();
   h->known_idx_copy.reset();
   h->known_ptr = nullptr;
@@ -1252,6 +1271,7 @@ int launch_reconstruction(mals_handle h, SideState& s, SideState& o, unsigned gr
 
 namespace {
 #include "topn_host.h"
+#include "foldin_host.h"
 }  // namespace
 
 // ================================================================================================
@@ -1433,6 +1453,7 @@ int mals_destroy(mals_handle h) {
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_G) (void)hipEventDestroy(h->ev_G);
   topn_free(h);
+  foldin_free(h);
   delete h;   // every buffer the handle owns, with its device current
 
   return MALS_OK;
@@ -1461,6 +1482,7 @@ int mals_set_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
   s.n_total = n_rows_total;
   s.G_valid = false;
   ++s.F_epoch;
+  if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
   return MALS_OK;
 }
 
@@ -1474,6 +1496,7 @@ int mals_bind_factors(mals_handle h, int side, float* device_ptr, int64_t n_rows
   s.n_total = n_rows_total;
   s.G_valid = false;
   ++s.F_epoch;
+  if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
   return MALS_OK;
 }
 
@@ -2421,7 +2444,7 @@ int mals_recommend(mals_handle h, const int64_t* user_idx, int32_t n_queries, in
     return topn_fail(h, MALS_INVALID_ARG, "the installed known items do not match the local user rows");
   for (int q = 0; q < n_queries; ++q) {
     if (user_idx[q] < 0 || user_idx[q] >= x.n_total) return topn_fail(h, MALS_INVALID_ARG, "user index outside the factor replica");
-    if (!consider_known_items && (user_idx[q] < x.row_offset || user_idx[q] >= x.row_offset + x.n_local))
+    if (!consider_known_items && (user_idx[q] < x.row_offset || user_idx[q] >= foldin_user_rows_end(h)))
       return topn_fail(h, MALS_INVALID_ARG, "known items of this user are not on this handle (row outside the local shard)");
   }
   if (n_queries == 0) return MALS_OK;
@@ -2676,7 +2699,7 @@ int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64
     return topn_fail(h, MALS_INVALID_ARG, "the installed known items do not match the local user rows");
   for (int q = 0; q < n_queries; ++q) {
     if (user_idx[q] < 0 || user_idx[q] >= x.n_total) return topn_fail(h, MALS_INVALID_ARG, "user index outside the factor replica");
-    if (user_idx[q] < x.row_offset || user_idx[q] >= x.row_offset + x.n_local)
+    if (user_idx[q] < x.row_offset || user_idx[q] >= foldin_user_rows_end(h))
       return topn_fail(h, MALS_INVALID_ARG, "known items of this user are not on this handle (row outside the local shard)");
   }
   if (n_queries == 0) return MALS_OK;
@@ -2781,4 +2804,294 @@ int mals_set_refine_limit(mals_handle h, double limit) {
   return MALS_OK;
 }
 
+// ---- the online write path (foldin_host.h, foldin_kernels.h) ---------------------------------------------------------
+void malsi_mark_group_member(mals_handle h) {
+  if (h) h->group_member = true;
+}
+
+static int foldin_refuse(mals_handle h, const char* call) {
+  if (h->group_member)
+    return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": not for a member of a group (the mals_group_* twins are not there yet)").c_str());
+  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  return MALS_OK;
+}
+
+int mals_set_foldin_solver(mals_handle h, int side, mals_solver s) {
+  CHECK_SIDE(h, side);
+  if (int rc = foldin_refuse(h, "mals_set_foldin_solver")) return rc;
+  const int k = h->cfg.features;
+  if (s && s->qr.dim() != k) return topn_fail(h, MALS_INVALID_ARG, "mals_set_foldin_solver: the solver's dimension is not the handle's features");
+  std::vector<int32_t> ipiv((size_t)k);
+  if (s)
+    for (int j = 0; j < k; ++j) ipiv[(size_t)s->qr.pivots()[j]] = j;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    FoldinSide& fs = foldin_state(h)->solver[side];
+    fs.present = false;
+    if (!s) return MALS_OK;
+    if (!fs.a.get()) {
+      FCHK(msg, fs.a.alloc((size_t)k * k));
+      FCHK(msg, fs.tau.alloc((size_t)k));
+      FCHK(msg, fs.ipiv.alloc((size_t)k));
+    }
+    FCHK(msg, hipMemcpyAsync(fs.a.get(), s->qr.factors(), sizeof(double) * (size_t)k * k, hipMemcpyHostToDevice, h->stream));
+    FCHK(msg, hipMemcpyAsync(fs.tau.get(), s->qr.taus(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, h->stream));
+    FCHK(msg, hipMemcpyAsync(fs.ipiv.get(), ipiv.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, h->stream));
+    FCHK(msg, hipStreamSynchronize(h->stream));
+    fs.present = true;
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_set_foldin_solver");
+}
+
+int mals_set_foldin_learn_rate(mals_handle h, double rate) {
+  if (!h) return MALS_INVALID_ARG;
+  if (!std::isfinite(rate)) return topn_fail(h, MALS_INVALID_ARG, "the fold-in learning rate must be finite");
+  if (int rc = foldin_refuse(h, "mals_set_foldin_learn_rate")) return rc;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    foldin_state(h)->rate = rate;
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_set_foldin_learn_rate");
+}
+
+int mals_foldin_stats(mals_handle h, int64_t* out6) {
+  if (!h || !out6) return MALS_INVALID_ARG;
+  for (int i = 0; i < 6; ++i) out6[i] = h->foldin_counters[i].load();
+  return MALS_OK;
+}
+
+// the pairs against the replicas as they stand inside the ticket (a concurrent grow is ordered before or after it)
+static int foldin_check_pairs(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, bool allow_unknown, bool local_users,
+                              std::string& msg) {
+  const SideState& x = h->side[MALS_SIDE_X];
+  const SideState& y = h->side[MALS_SIDE_Y];
+  if (!x.F || !y.F) {
+    msg = "factor replicas not available";
+    return MALS_INVALID_ARG;
+  }
+  const int64_t u_lo = local_users ? x.row_offset : 0, u_hi = local_users ? std::min(foldin_user_rows_end(h), x.n_total) : x.n_total;
+  for (int64_t t = 0; t < n; ++t) {
+    const bool u_ok = (user_row[t] >= u_lo && user_row[t] < u_hi) || (allow_unknown && user_row[t] == -1);
+    const bool i_ok = (item_row[t] >= 0 && item_row[t] < y.n_total) || (allow_unknown && item_row[t] == -1);
+    if (!u_ok || !i_ok) {
+      msg = "pair " + std::to_string(t) + ": row outside the factor replicas (or the user's known items are not on this handle)";
+      return MALS_INVALID_ARG;
+    }
+  }
+  return MALS_OK;
+}
+
+int mals_set_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, "mals_set_preferences")) return rc;
+  if (n < 0 || (n > 0 && (!user_row || !item_row || !value))) return topn_fail(h, MALS_INVALID_ARG, "mals_set_preferences: bad arguments");
+  if (n > (int64_t)1 << 30) return topn_fail(h, MALS_INVALID_ARG, "mals_set_preferences: at most 2^30 updates per call");
+  if (n == 0) return MALS_OK;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    if (int rc = foldin_check_pairs(h, n, user_row, item_row, false, true, msg)) return rc;
+    return foldin_set_run(h, n, user_row, item_row, value, status_out, msg);
+  };
+  return foldin_exclusive(h, fn, msg, "mals_set_preferences");
+}
+
+int mals_remove_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,
+                            int64_t* n_removed_out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (n_removed_out) *n_removed_out = 0;
+  if (int rc = foldin_refuse(h, "mals_remove_preferences")) return rc;
+  if (n < 0 || (n > 0 && (!user_row || !item_row))) return topn_fail(h, MALS_INVALID_ARG, "mals_remove_preferences: bad arguments");
+  if (n == 0) return MALS_OK;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    if (!h->side[MALS_SIDE_X].has_matrix && !h->known_ptr) {
+      msg = "the user-side matrix (or mals_set_known_items) holds the known items";
+      return MALS_INVALID_ARG;
+    }
+    if (int rc = foldin_check_pairs(h, n, user_row, item_row, false, true, msg)) return rc;
+    return foldin_remove_run(h, n, user_row, item_row, removed_users_out, n_removed_out, msg);
+  };
+  return foldin_exclusive(h, fn, msg, "mals_remove_preferences");
+}
+
+int mals_grow_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
+  CHECK_SIDE(h, side);
+  if (int rc = foldin_refuse(h, "mals_grow_factor_rows")) return rc;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    if (!h->side[side].F) {
+      msg = "the replica is not declared (mals_set_factor_rows)";
+      return MALS_INVALID_ARG;
+    }
+    return foldin_grow_run(h, side, n_rows_total, msg);
+  };
+  return foldin_exclusive(h, fn, msg, "mals_grow_factor_rows");
+}
+
+int mals_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, "mals_estimate_preferences")) return rc;
+  if (n < 0 || (n > 0 && (!user_row || !item_row || !out))) return topn_fail(h, MALS_INVALID_ARG, "mals_estimate_preferences: bad arguments");
+  if (n == 0) return MALS_OK;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    if (int rc = foldin_check_pairs(h, n, user_row, item_row, true, false, msg)) return rc;
+    DeviceBuffer<int64_t> d_rows;
+    DeviceBuffer<float> d_out;
+    FCHK(msg, d_rows.alloc(2 * (size_t)n));
+    FCHK(msg, d_out.alloc((size_t)n));
+    FCHK(msg, hipMemcpyAsync(d_rows.get(), user_row, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    FCHK(msg, hipMemcpyAsync(d_rows.get() + n, item_row, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(foldin_estimate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->side[MALS_SIDE_X].F, h->side[MALS_SIDE_Y].F,
+                       h->cfg.features, d_rows.get(), d_rows.get() + n, n, d_out.get());
+    FCHK(msg, hipGetLastError());
+    FCHK(msg, hipMemcpyAsync(out, d_out.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    FCHK(msg, hipStreamSynchronize(h->stream));
+    for (int64_t t = 0; t < n; ++t)   // Preconditions.checkState(isFinite(value), "Bad estimate") (:718)
+      if (!std::isfinite(out[t])) {
+        msg = "bad estimate (not finite) for pair " + std::to_string(t);
+        return MALS_INVALID_ARG;
+      }
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_estimate_preferences");
+}
+
+static int foldin_anonymous(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values, float* out,
+                            int32_t* status_out, const int64_t* to_item, float* dot_out, const char* call) {
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, call)) return rc;
+  if (n_queries < 0 || (n_queries > 0 && (!item_ptr || !out || (item_ptr[n_queries] > 0 && !item_row))) || (n_queries > 0 && item_ptr[0] != 0))
+    return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": bad arguments").c_str());
+  for (int32_t q = 0; q < n_queries; ++q)
+    if (item_ptr[q + 1] < item_ptr[q] || item_ptr[q + 1] - item_ptr[q] > (1 << 20))
+      return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": bad item_ptr").c_str());
+  if (n_queries == 0) return MALS_OK;
+  std::vector<int32_t> found((size_t)n_queries, 0);
+  bool no_solver = false;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    const SideState& y = h->side[MALS_SIDE_Y];
+    if (!y.F) {
+      msg = "item factor replica not available";
+      return MALS_INVALID_ARG;
+    }
+    for (int64_t j = 0; j < item_ptr[n_queries]; ++j)
+      if (item_row[j] < -1 || item_row[j] >= y.n_total) {
+        msg = "item row outside the item factor replica";
+        return MALS_INVALID_ARG;
+      }
+    for (int32_t q = 0; to_item && q < n_queries; ++q)
+      if (to_item[q] < 0 || to_item[q] >= y.n_total) {
+        msg = "item row outside the item factor replica";
+        return MALS_INVALID_ARG;
+      }
+    no_solver = !foldin_state(h)->solver[MALS_SIDE_Y].present;
+    if (no_solver) return MALS_OK;
+    return foldin_anonymous_run(h, n_queries, item_ptr, item_row, values, out, found.data(), to_item, dot_out, msg);
+  };
+  if (int rc = foldin_exclusive(h, fn, msg, call)) return rc;
+  int first = MALS_OK;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    // no Y^T Y solver: NotReadyException (:570-573); no item of the query has a row: NoSuchItemException (:603-605)
+    const int st = (no_solver || !found[(size_t)q]) ? MALS_INVALID_ARG : MALS_OK;
+    if (status_out) status_out[q] = st;
+    if (st != MALS_OK && first == MALS_OK) first = st;
+  }
+  if (first != MALS_OK)
+    return topn_fail(h, first, (std::string(call) + (no_solver ? ": no Y^T Y solver (mals_set_foldin_solver)" : ": a query has no item with a row")).c_str());
+  return MALS_OK;
+}
+
+int mals_anonymous_features(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values, float* out,
+                            int32_t* status_out) {
+  return foldin_anonymous(h, n_queries, item_ptr, item_row, values, out, status_out, nullptr, nullptr, "mals_anonymous_features");
+}
+
+int mals_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
+                                const float* values, float* out, int32_t* status_out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (n_queries > 0 && (!to_item || !out)) return topn_fail(h, MALS_INVALID_ARG, "mals_estimate_for_anonymous: bad arguments");
+  std::vector<float> feats((size_t)std::max(n_queries, 0) * h->cfg.features);
+  return foldin_anonymous(h, n_queries, item_ptr, item_row, values, feats.data(), status_out, to_item, out, "mals_estimate_for_anonymous");
+}
+
+// two tickets: the vectors, then the top-N (like the reference, which holds no lock across the two, a write may land between)
+int mals_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                                int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (n_queries > 0 && (how_many <= 0 || how_many > 4096 || !item_idx_out || !score_out))
+    return topn_fail(h, MALS_INVALID_ARG, "mals_recommend_to_anonymous: bad arguments (how_many in 1..4096)");
+  const int k = h->cfg.features;
+  std::vector<float> feats((size_t)std::max(n_queries, 0) * k);
+  std::vector<int32_t> st((size_t)std::max(n_queries, 0), MALS_OK);
+  const int rc_f = foldin_anonymous(h, n_queries, item_ptr, item_row, values, feats.data(), st.data(), nullptr, nullptr, "mals_recommend_to_anonymous");
+  if (rc_f != MALS_OK && rc_f != MALS_INVALID_ARG) return rc_f;
+  if (n_queries <= 0) return rc_f;
+  if (rc_f == MALS_INVALID_ARG && std::all_of(st.begin(), st.end(), [](int32_t v) { return v == MALS_OK; })) return rc_f;   // (an argument error)
+  // the queries that have a vector, their items as exclusions (rows -1 are no items)
+  std::vector<int32_t> qs;
+  std::vector<float> vecs;
+  std::vector<int64_t> eptr(1, 0), eidx;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    if (status_out) status_out[q] = st[(size_t)q];
+    for (int j = 0; j < how_many; ++j) {
+      item_idx_out[(size_t)q * how_many + j] = -1;
+      score_out[(size_t)q * how_many + j] = -std::numeric_limits<float>::infinity();
+    }
+    if (n_out) n_out[q] = 0;
+    if (st[(size_t)q] != MALS_OK) continue;
+    qs.push_back(q);
+    vecs.insert(vecs.end(), feats.begin() + (size_t)q * k, feats.begin() + (size_t)(q + 1) * k);
+    for (int64_t j = item_ptr[q]; j < item_ptr[q + 1]; ++j)
+      if (item_row[j] >= 0) eidx.push_back(item_row[j]);
+    eptr.push_back((int64_t)eidx.size());
+  }
+  if (!qs.empty()) {
+    std::vector<int64_t> idx(qs.size() * (size_t)how_many);
+    std::vector<float> sc(qs.size() * (size_t)how_many);
+    std::vector<int32_t> cnt(qs.size());
+    if (int rc = mals_recommend_to_many(h, vecs.data(), nullptr, (int32_t)qs.size(), how_many, eptr.data(), eidx.data(), idx.data(), sc.data(), cnt.data()))
+      return rc;
+    for (size_t i = 0; i < qs.size(); ++i) {
+      std::copy(idx.begin() + i * how_many, idx.begin() + (i + 1) * how_many, item_idx_out + (size_t)qs[i] * how_many);
+      std::copy(sc.begin() + i * how_many, sc.begin() + (i + 1) * how_many, score_out + (size_t)qs[i] * how_many);
+      if (n_out) n_out[qs[i]] = cnt[i];
+    }
+  }
+  return rc_f;
+}
+
+int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, double* x_out) {
+  CHECK_SIDE(h, side);
+  if (int rc = foldin_refuse(h, "mals_foldin_solve")) return rc;
+  if (n_rhs < 0 || (n_rhs > 0 && (!b || !x_out))) return topn_fail(h, MALS_INVALID_ARG, "mals_foldin_solve: bad arguments");
+  if (n_rhs == 0) return MALS_OK;
+  const int k = h->cfg.features;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    FoldinState& fs = *foldin_state(h);
+    if (!fs.solver[side].present) {
+      msg = "no solver on that side (mals_set_foldin_solver)";
+      return MALS_INVALID_ARG;
+    }
+    if (int rc = foldin_lds_limit(msg)) return rc;
+    DeviceBuffer<float> d_b;
+    DeviceBuffer<double> d_x;
+    FCHK(msg, d_b.alloc((size_t)n_rhs * k));
+    FCHK(msg, d_x.alloc((size_t)n_rhs * k));
+    FCHK(msg, hipMemcpyAsync(d_b.get(), b, sizeof(float) * (size_t)n_rhs * k, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(foldin_solve_kernel, dim3((unsigned)((n_rhs + FOLDIN_LANES - 1) / FOLDIN_LANES)), dim3(FOLDIN_LANES),
+                       (size_t)k * FOLDIN_LANES * sizeof(double), h->stream, foldin_view(fs.solver[side]), k, d_b.get(), n_rhs, d_x.get());
+    FCHK(msg, hipGetLastError());
+    FCHK(msg, hipMemcpyAsync(x_out, d_x.get(), sizeof(double) * (size_t)n_rhs * k, hipMemcpyDeviceToHost, h->stream));
+    FCHK(msg, hipStreamSynchronize(h->stream));
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_foldin_solve");
+}
+
 }  // extern "C"
+

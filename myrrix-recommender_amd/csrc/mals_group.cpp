@@ -213,6 +213,7 @@ int init_member(mals_group g, Member& mb, const mals_config& cfg, int device, in
     (void)mals_create_error(why, sizeof(why));
     return gfail(g, rc, std::string(why[0] ? why : "mals_create failed") + " (group member " + std::to_string(rank) + ", device " + std::to_string(device) + ")");
   }
+  malsi_mark_group_member(mb.h);
   mb.device = device;
   GHIP(g, hipSetDevice(device));
   GHIP(g, hipStreamCreateWithFlags(&mb.compute, hipStreamNonBlocking));

@@ -26,6 +26,8 @@ __attribute__((visibility("hidden"))) int malsi_set_gramian(mals_handle h, int s
 __attribute__((visibility("hidden"))) void* malsi_ready_event(mals_handle h);
 // the thread's "why did create fail" text (mals_create_error): set by whichever create call fails, cleared by one that succeeds
 __attribute__((visibility("hidden"))) void malsi_set_create_error(const char* text);
+// a handle that mals_group_create made for a member: the online write path (mals_set_preferences ...) refuses it
+__attribute__((visibility("hidden"))) void malsi_mark_group_member(mals_handle h);
 }
 
 // mals_group_ingest_finish (mals_group.cpp) hands the ingest side (ingest_group_host.h) the group's transport: collectives over

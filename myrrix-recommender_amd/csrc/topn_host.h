@@ -91,8 +91,10 @@ struct TopnRequest {
   // similarityToItem (TOPN_KIND_SIMILARITY_TO): n_queries items item_rows[], against to_item, into sim_out
   int64_t to_item = 0;
   float* sim_out = nullptr;
+  // a write or fold-in read of foldin_host.h (TOPN_KIND_CALL): runs alone on the handle, in queue order
+  const std::function<int()>* call = nullptr;
 };
-enum { TOPN_KIND_SCORE = 0, TOPN_KIND_BECAUSE = 1, TOPN_KIND_SIMILARITY_TO = 2 };
+enum { TOPN_KIND_SCORE = 0, TOPN_KIND_BECAUSE = 1, TOPN_KIND_SIMILARITY_TO = 2, TOPN_KIND_CALL = 3 };
 
 inline TopnOut topn_out(const TopnRequest& rq, size_t qq) {
   if (rq.out_q) return rq.out_q[qq];
@@ -142,7 +144,25 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
     ps.v0 = rq.vec_ptr[ps.q0];
     ps.n_vecs = rq.vec_ptr[ps.q0 + ps.nq] - ps.v0;
   }
-  const int64_t n_ex = (rq.excl_ptr && rq.excl_idx) ? rq.excl_ptr[ps.q0 + ps.nq] - rq.excl_ptr[ps.q0] : 0;
+  // by-user queries whose known items the writes changed (foldin_host.h): the additions as exclusion lists beside the base
+  // row; users with removals (or grown rows) drop the base row (rows[q] = -1) and exclude their whole list instead
+  std::vector<int64_t> ov_ptr, ov_idx;
+  std::vector<uint8_t> ov_drop;
+  if (rq.user_idx && (rq.skip_known || rq.skip_known_q) && foldin_has_overlay(h)) {
+    ov_ptr.assign(1, 0);
+    ov_drop.assign((size_t)ps.nq, 0);
+    for (int q = 0; q < ps.nq; ++q) {
+      if (!rq.skip_known_q || rq.skip_known_q[ps.q0 + q]) {
+        const size_t b = ov_idx.size();
+        ov_drop[(size_t)q] = foldin_known_view(h, rq.user_idx[ps.q0 + q] - x.row_offset, ov_idx) ? 1 : 0;
+        std::sort(ov_idx.begin() + (ptrdiff_t)b, ov_idx.end());
+        ov_idx.erase(std::unique(ov_idx.begin() + (ptrdiff_t)b, ov_idx.end()), ov_idx.end());
+      }
+      ov_ptr.push_back((int64_t)ov_idx.size());
+    }
+  }
+  const bool overlay = !ov_ptr.empty();
+  const int64_t n_ex = overlay ? (int64_t)ov_idx.size() : (rq.excl_ptr && rq.excl_idx) ? rq.excl_ptr[ps.q0 + ps.nq] - rq.excl_ptr[ps.q0] : 0;
   // layout of the block (8-byte aligned pieces)
   const size_t o_vptr = 0, o_rows = o_vptr + 8 * ((TOPN_FILTER_QUERIES + 2) / 2), o_uidx = o_rows + 8 * TOPN_FILTER_QUERIES,
                o_eptr = o_uidx + 8 * TOPN_FILTER_QUERIES, o_vecs = o_eptr + 8 * (TOPN_FILTER_QUERIES + 1),
@@ -166,7 +186,7 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
     if (rq.skip_known || rq.skip_known_q) {
       int64_t* rows = reinterpret_cast<int64_t*>(in + o_rows);
       for (int q = 0; q < ps.nq; ++q)
-        rows[q] = (!rq.skip_known_q || rq.skip_known_q[ps.q0 + q]) ? rq.user_idx[ps.q0 + q] - x.row_offset : -1;
+        rows[q] = (!rq.skip_known_q || rq.skip_known_q[ps.q0 + q]) && !(overlay && ov_drop[(size_t)q]) ? rq.user_idx[ps.q0 + q] - x.row_offset : -1;
       ps.have_rows = true;
     }
   } else if (rq.item_rows) {   // rows of Y (the replica is complete on every handle)
@@ -183,7 +203,11 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
     sl.d_vecs = reinterpret_cast<const float*>(sl.d_in.get() + o_vecs);
     sl.d_vrow = nullptr;
   }
-  if (n_ex > 0) {
+  if (n_ex > 0 && overlay) {
+    std::memcpy(in + o_eptr, ov_ptr.data(), sizeof(int64_t) * (size_t)(ps.nq + 1));
+    std::memcpy(in + o_eidx, ov_idx.data(), sizeof(int64_t) * (size_t)n_ex);
+    ps.have_excl = true;
+  } else if (n_ex > 0) {
     int64_t* eptr = reinterpret_cast<int64_t*>(in + o_eptr);
     for (int q = 0; q <= ps.nq; ++q) eptr[q] = rq.excl_ptr[ps.q0 + q] - rq.excl_ptr[ps.q0];
     std::memcpy(in + o_eidx, rq.excl_idx + rq.excl_ptr[ps.q0], sizeof(int64_t) * (size_t)n_ex);
@@ -558,13 +582,39 @@ int topn_finish_slot(mals_handle h, TopnWorkspace* w, int s, const TopnRequest& 
 // stream with slot 0's buffers (the call runs alone on the workspace).
 constexpr int TOPN_BECAUSE_CAP = 4096;
 
-int topn_because_run(mals_handle h, TopnWorkspace* w, const TopnRequest& rq) {
+int topn_because_run(mals_handle h, TopnWorkspace* w, const TopnRequest& rq_in) {
   SideState& y = h->side[MALS_SIDE_Y];
   SideState& x = h->side[MALS_SIDE_X];
-  const int k = h->cfg.features, how_many = rq.how_many, cap = TOPN_BECAUSE_CAP;
+  const int k = h->cfg.features, how_many = rq_in.how_many, cap = TOPN_BECAUSE_CAP;
   const int64_t n_items = y.n_total;
   const int64_t* k_ptr = h->known_ptr ? h->known_ptr : x.row_ptr;
   const int32_t* k_idx = h->known_ptr ? h->known_idx : x.col;
+  // known items changed by writes (foldin_host.h): the queries' current sets as a CSR of their own, query q = its row q
+  TopnRequest rq = rq_in;
+  std::vector<int64_t> own_user, own_ptr, rows;
+  std::vector<int32_t> own_idx;
+  std::vector<std::vector<int32_t>> sets;
+  DeviceBuffer<int64_t> d_own_ptr;
+  DeviceBuffer<int32_t> d_own_idx;
+  if (foldin_has_overlay(h)) {
+    for (int q = 0; q < rq.n_queries; ++q) rows.push_back(rq.because_user[q] - x.row_offset);
+    std::string msg;
+    if (int rc = foldin_known_full(h, rows, sets, msg)) return fail(h, rc, msg);
+    own_ptr.assign(1, 0);
+    for (int q = 0; q < rq.n_queries; ++q) {
+      own_idx.insert(own_idx.end(), sets[(size_t)q].begin(), sets[(size_t)q].end());
+      own_ptr.push_back((int64_t)own_idx.size());
+      own_user.push_back(x.row_offset + q);
+    }
+    HIPCHK(h, d_own_ptr.alloc(own_ptr.size()));
+    HIPCHK(h, d_own_idx.alloc(std::max<size_t>(own_idx.size(), 1)));
+    HIPCHK(h, hipMemcpyAsync(d_own_ptr.get(), own_ptr.data(), sizeof(int64_t) * own_ptr.size(), hipMemcpyHostToDevice, h->stream));
+    if (!own_idx.empty())
+      HIPCHK(h, hipMemcpyAsync(d_own_idx.get(), own_idx.data(), sizeof(int32_t) * own_idx.size(), hipMemcpyHostToDevice, h->stream));
+    k_ptr = d_own_ptr.get();
+    k_idx = d_own_idx.get();
+    rq.because_user = own_user.data();
+  }
   TopnSlot& sl = w->slot[0];
   if (int rc = topn_slot_alloc(h, sl)) return rc;
   HIPCHK(h, sl.d_pairs.reserve((size_t)TOPN_MAX_QUERIES * (size_t)cap, h->stream));
@@ -636,6 +686,7 @@ int topn_run(mals_handle h, const TopnRequest& rq) {
   TopnWorkspace* w = static_cast<TopnWorkspace*>(h->tn_ws);
   if (rq.kind == TOPN_KIND_BECAUSE) return topn_because_run(h, w, rq);
   if (rq.kind == TOPN_KIND_SIMILARITY_TO) return topn_similarity_to_run(h, rq);
+  if (rq.kind == TOPN_KIND_CALL) return (*rq.call)();
   if (topn_dense_only(h, rq.how_many)) {
     for (int q0 = 0; q0 < rq.n_queries; q0 += TOPN_MAX_QUERIES) {
       TopnPass ps;
@@ -891,7 +942,7 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
       one.tickets.push_back(head);
       if (head->bulk) {
         one.rq = *head->bulk;
-        ++f->bulk_calls;
+        if (one.rq.kind != TOPN_KIND_CALL) ++f->bulk_calls;   // (the writes of foldin_host.h are no recommend calls)
       } else {
         one.rq.n_queries = head->n;
         one.rq.how_many = head->how_many;
