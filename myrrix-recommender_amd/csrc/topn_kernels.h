@@ -10,7 +10,7 @@
 // indices are bit-identical to the oracle's.  What makes that affordable on a million items is a FILTER in front:
 //   1. sample     every `stride`-th 16-item tile is scored approximately against all queries of the pass on
 //                 v_mfma_f32_16x16x32_bf16 (item rows and query vectors one bf16 each), fp32 accumulate.
-//                 |approx - exact| <= margin_i = 1.25 * 2^-8 |x| |y_i| (bound below), so lb_i = approx - margin_i is a
+//                 |approx - exact| <= margin_i = 2.25 * 2^-8 |x| |y_i| (bound below), so lb_i = approx - margin_i is a
 //                 LOWER bound of the exact score.  The sample is reduced on the fly to a few thousand BUCKET maxima per
 //                 query (bucket = a fixed subset of the sample's items) with the item that attains each.
 //   2. threshold  buckets whose best item is a known / excluded item of the query are dropped; tau = (a lower estimate
@@ -25,14 +25,19 @@
 // N unmasked buckets, that query is answered by the dense path (all queries of the pass if a wave's hit list overflowed): exact scores of every item (topn_exact_dense_kernel), known
 // items masked, 4-pass radix select of the N-th best, everything above it plus the ties sorted on the host.
 //
-// Error bound of the approximate score.  Both operands enter as ONE bf16: y = yh + ey, |ey| <= 2^-9 |y|; x = xh + ex,
-// |ex| <= 2^-9 |x|.  approx = sum yh xh on v_mfma_f32_16x16x32_bf16 (exact products, fp32 accumulate):
-// |approx - sum x y| <= sum |x| |ey| + |ex| |yh| <= 2^-8 (1 + 2^-10) sum |x_f y_f|, plus the accumulation of <= 128 terms
+// Error bound of the approximate score.  Both operands enter as ONE bf16, rounded to nearest (v_cvt_pk_bf16_f32): bf16
+// has 8 significant bits, so u = 2^-8 is its unit roundoff -- y = yh + ey, |ey| <= u |y|; x = xh + ex, |ex| <= u |x|
+// (e.g. bf16(1 + 2^-8 - 2^-20) = 1).  approx = sum yh xh on v_mfma_f32_16x16x32_bf16 (exact products, fp32 accumulate):
+// |approx - sum x y| <= sum |x| |ey| + |ex| |yh| <= (2u + u^2) sum |x_f y_f|, plus the accumulation of <= 128 terms
 // (< 2^-16 of it) and the reference's own roundings (fp32 products, final cast: <= 2^-23 of it): in total
-// < 1.01 * 2^-8 sum |x_f y_f| <= 1.01 * 2^-8 |x|_2 |y_i|_2 (Cauchy-Schwarz).  The kernels use 1.25 * 2^-8, round both
-// factors of the margin UP to bf16, and add an absolute floor for the subnormal range.  (Until the middle of round 5 the item
-// rows entered split into two bf16 halves with a 2^-8 margin: one more matrix instruction and three more vector
-// instructions per element for 20 % fewer candidates -- not worth it: the filter is bound by instruction issue.)  For a
+// < 2.01 * 2^-8 sum |x_f y_f| <= 2.01 * 2^-8 |x|_2 |y_i|_2 (Cauchy-Schwarz).  The bound is reached: when the roundings of
+// every term point the same way (x and y_i just off bf16 midpoints, all on one side) the error is ~2u |x| |y_i|; one item
+// too high and another too low on disjoint halves of x differ by 2 sqrt(2) u |x| |y| (tests/test_topn_margin.py).  The
+// kernels use 2.25 * 2^-8, round both factors of the margin UP to bf16, and add an absolute floor for the subnormal range.
+// (Until the middle of round 5 the item rows entered split into two bf16 halves, x alone was rounded once and 2^-8 was the
+// bound; dropping the lo half doubled the bound, but the margin was only raised to 1.25 * 2^-8 -- fixed here.  The split
+// costs one more matrix instruction and three more vector instructions per element: the filter is bound by instruction
+// issue.)  For a
 // query of n vectors the filter vector is their mean and |x| is the mean of their norms (an upper bound of the norm of
 // the mean, and of the per-vector error sum).
 //
@@ -45,7 +50,7 @@
 //   x = (1/n) sum_j Y_qj / norm(Y_qj)   (fp64, rounded once to fp32: |x| <= 1 + 2^-23; the margin uses |x| <= 1.000001)
 // and item i passes iff  approx + |y_i|' M_c + floor - tau |y_i|'' >= 0, which is the cosine test approx/|y_i| + M_c - tau
 // >= -floor/|y_i| with the item's norm folded in, no per-element work added.  Bound, with |y| = norm(Y_i) exactly:
-//   (a) bf16 rounding of both operands + fp32 accumulation, as above: |approx - y.x| <= 1.01 * 2^-8 |y| |x|;
+//   (a) bf16 rounding of both operands + fp32 accumulation, as above: |approx - y.x| <= 2.01 * 2^-8 |y| |x|;
 //   (b) the reference's own roundings (fp32 products, the fp64 sums, divisions and the final cast): |score - y.x/|y||
 //       <= 2^-22 (|s_j| <= 1 + 2^-20 per vector; the cast adds <= 2^-24);
 //   (c) |x_fp32 - x| <= 2^-24 |x| (one rounding of the fp64 mean): covered by the 1.000001 in |x|;
@@ -53,10 +58,13 @@
 //       slot: >= |y| (1 - k 2^-25) (k <= 128 terms);
 //   (e) tau |y_i|'' in the margin step: A slots 2-5 = {hi, lo, hi, lo} of the bf16 split of the fp32 |y_i|, B slots 2-5 =
 //       {hi, hi, lo, lo} of the split of -tau (lo rounded up): the four products are exact and differ from -tau |y| by at
-//       most (2^-16 + 2^-16 + k 2^-25) |tau| |y| <= 2^-14 |y| (|tau| <= 1 + 2^-7: tau is a lower bound of a cosine's
-//       approximation);
-// in total  |approx - score |y|| <= (1.01 * 2^-8 + 2^-22 + 2^-14 + k 2^-25) |y| < (1.25 * 2^-8 + 2^-13) |y| = M_c |y|
-// (TOPN_COS_MARGIN; recommend's TOPN_MARGIN is unchanged).  So exact score >= tau implies a non-negative accumulator:
+//       most (2^-16 + 2^-15 + k 2^-25) |tau| |y| <= 1.7 * 2^-15 |y| at k <= 128 (the |y| lo rounded to nearest: 2^-16; the
+//       -tau lo rounded up: < 2^-15, only ever adding; the kernel's |y_i|: (d); |tau| <= 1 + 2^-5: tau is the bucket
+//       maximum of a lower bound approx/|y| - M_c |y|'/|y| of a cosine, and |approx/|y|| <= (1 + 2.01 * 2^-8) |x|, so
+//       |tau| <= 1 + 4.3 * 2^-8 < 1 + 2^-5);
+// in total  |approx - score |y|| <= (2.01 * 2^-8 + 2^-22 + 1.7 * 2^-15 + k 2^-25) |y| < 2.03 * 2^-8 |y|
+// < (2.25 * 2^-8 + 2^-13) |y| = M_c |y|
+// (TOPN_COS_MARGIN; recommend's TOPN_MARGIN = 2.25 * 2^-8).  So exact score >= tau implies a non-negative accumulator:
 // every item of the exact top N, with all its ties, is a candidate.  The sample (MODE 0) keeps (approx - |y_i|' M_c -
 // floor) / |y_i| per bucket, a lower bound of the score by the same bound (the fp32 division by the kernel's |y_i|
 // moves it by <= 2^-21, inside the slack of M_c), so at least N unmasked items score >= tau exactly, as for recommend.
@@ -75,9 +83,9 @@ constexpr int TOPN_MAX_QUERIES = 64;      // dense path: queries per pass
 constexpr int TOPN_FILTER_QUERIES = 256;  // filter path: queries scored per read of Y
 constexpr int TOPN_FILTER_MAX_N = 64;     // largest how_many the filter path takes (the candidates of a query sit in LDS)
 constexpr int TOPN_SAMPLE_GROUPS = 512;   // most workgroups of the sample kernel: 16 buckets per workgroup and query
-constexpr float TOPN_MARGIN = 0.0048828125f;  // 1.25 * 2^-8
+constexpr float TOPN_MARGIN = 0.0087890625f;  // 2.25 * 2^-8: the bound (header)
 constexpr float TOPN_MARGIN_FLOOR = 1e-30f;
-constexpr float TOPN_COS_MARGIN = 0.0050048828125f;  // 1.25 * 2^-8 + 2^-13: the cosine bound (header)
+constexpr float TOPN_COS_MARGIN = 0.0089111328125f;  // 2.25 * 2^-8 + 2^-13: the cosine bound (header)
 constexpr float TOPN_COS_DEAD_TAU = 1e30f;           // threshold of a query answered empty (a query item of norm 0 / NaN)
 constexpr int TOPN_COUNT_STRIDE = 32;  // candidate counters one per 128-byte line: atomics on one LINE serialise in L2 (97 us per pass when packed)
 
