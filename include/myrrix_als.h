@@ -366,6 +366,48 @@ int mals_recommend_to_many(mals_handle h, const float* vectors, const int64_t* v
                            const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out, float* score_out,
                            int32_t* n_out);
 
+/* ---- rescorers: RecommendIterator's IDRescorer on the device ----------------------------------------------------
+ * RecommendIterator.next (online/src/net/myrrix/online/RecommendIterator.java:62-109) with an IDRescorer of the shape the
+ * reference's own FilterHalfRescorerProvider has -- a filter set and an affine rescore -- as a native object:
+ *     isFiltered(i) = i is in the filter set;   rescore(i, sum) = fl(fl(scale_i * sum) + offset_i)   (fp64, no contraction)
+ * Per candidate item, in the reference's order: userTagIDs, known / excluded items and filtered items are skipped; sum = the
+ * fp64 sum of the dots over the query's n vectors (unchanged); r = rescore(i, sum) -- on the SUM, before the division; an
+ * r that is not finite skips the item (never an error); the score is (float)(r / n), and a score that is not finite fails
+ * THAT CALL with MALS_INVALID_ARG, "Bad recommendation value" (checkState, :105) -- the other calls folded into the same
+ * pass are answered as if alone.  Scores and indices are bit-identical to the reference running a Java IDRescorer that
+ * computes the same formula (java/.../NativeIDRescorer.java); ties in ascending item index.
+ * A rescorer is bound to one handle; it starts as the identity (nothing filtered, scale 1, offset 0).
+ *   mals_rescorer_set_filter(r, n, item_idx, mem_kind): the filter set, n dense item indices in [0, rows of Y) (host or
+ *     device); n = 0 clears it.
+ *   mals_rescorer_set_weights(r, scale, offset, n_rows, mem_kind): per-item fp64 weights of rows [0, n_rows) (host or
+ *     device); either array may be NULL (scale 1 / offset 0).  Every scale must be finite and > 0, every offset finite
+ *     (an item a Java rescorer scores NaN belongs in the filter set): else MALS_INVALID_ARG and nothing changes.  Replaces
+ *     the uniform weights (back to 1, 0).
+ *   mals_rescorer_set_uniform(r, scale, offset): the same weights for every item, no arrays; replaces the per-item weights.
+ * Rows of Y the arrays do not cover (rows added by mals_grow_factor_rows among them) are unfiltered, with scale 1 and
+ * offset 0 -- or the uniform weights.  Every set_* is an exclusive ticket of the serving front (as the fold-in writes): a
+ * call sees the rescorer as it was when the call was queued.  mals_rescorer_destroy: not while a call that names it is in
+ * flight; before the handle is destroyed.
+ * The rescored twins of mals_recommend, mals_recommend_to_many (which covers mals_recommend_vectors: vector_ptr NULL) and
+ * mals_recommend_to_anonymous take the rescorer as their second argument (NULL: exactly the plain call).  Calls with the
+ * same rescorer (or none), kind and how_many are folded into one pass; different rescorers never share one.  The filter
+ * path runs on rescorers whose unfiltered weights lie in scale [2^-20, 2^20], |offset| <= 2^64 (csrc/topn_kernels.h,
+ * RESCORED MODE: the bound); the calls of any other rescorer are answered exactly by the dense path, one call at a time. */
+typedef struct mals_rescorer_s* mals_rescorer;
+int mals_rescorer_create(mals_handle h, mals_rescorer* out);
+int mals_rescorer_destroy(mals_rescorer r);
+int mals_rescorer_set_filter(mals_rescorer r, int64_t n, const int64_t* item_idx, int mem_kind);
+int mals_rescorer_set_weights(mals_rescorer r, const double* scale, const double* offset, int64_t n_rows, int mem_kind);
+int mals_rescorer_set_uniform(mals_rescorer r, double scale, double offset);
+int mals_recommend_rescored(mals_handle h, mals_rescorer r, const int64_t* user_idx, int32_t n_queries, int32_t how_many,
+                            int32_t consider_known_items, int64_t* item_idx_out, float* score_out, int32_t* n_out);
+int mals_recommend_to_many_rescored(mals_handle h, mals_rescorer r, const float* vectors, const int64_t* vector_ptr, int32_t n_queries,
+                                    int32_t how_many, const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out,
+                                    float* score_out, int32_t* n_out);
+int mals_recommend_to_anonymous_rescored(mals_handle h, mals_rescorer r, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row,
+                                         const float* values, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out,
+                                         int32_t* status_out);
+
 /* ---- item-to-item similarity on the device ------------------------------------------------------------
  * ServerRecommender.mostSimilarItems (online/src/net/myrrix/online/ServerRecommender.java:1171-1266, scored by
  * MostSimilarItemIterator.java:73-120): for query q of items i_1..i_n (dense item indices; item_ptr NULL: one item per

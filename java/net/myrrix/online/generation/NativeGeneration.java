@@ -55,6 +55,16 @@ public final class NativeGeneration implements AutoCloseable {
                                             long[] items, float[] scores, int[] counts);
   private static native int nativeRecommendToMany(long handle, float[] vectors, long[] vectorPtr, int nQueries, int howMany,
                                                   long[] excludePtr, long[] excludeIdx, long[] items, float[] scores, int[] counts);
+  private static native long nativeRescorerCreate(long handle);
+  private static native void nativeRescorerDestroy(long rescorer);
+  private static native int nativeRescorerSetFilter(long rescorer, long[] itemIdx);
+  private static native int nativeRescorerSetWeights(long rescorer, long[] scaleBits, long[] offsetBits, long nRows);
+  private static native int nativeRescorerSetUniform(long rescorer, long scaleBits, long offsetBits);
+  private static native int nativeRecommendRescored(long handle, long rescorer, long[] userIdx, int howMany, boolean considerKnownItems,
+                                                    long[] items, float[] scores, int[] counts);
+  private static native int nativeRecommendToManyRescored(long handle, long rescorer, float[] vectors, long[] vectorPtr, int nQueries,
+                                                          int howMany, long[] excludePtr, long[] excludeIdx, long[] items, float[] scores,
+                                                          int[] counts);
   private static native String nativeLastError(long handle);
 
   /** The reference's own six arguments (InputFilesReader.java:64-69; call site DelegateGenerationManager.java:336): a switch by
@@ -216,6 +226,54 @@ public final class NativeGeneration implements AutoCloseable {
   public static void recommendToMany(long handle, float[] vectors, long[] vectorPtr, int nQueries, int howMany,
                                      long[] excludePtr, long[] excludeIdx, long[] items, float[] scores, int[] counts) {
     checkHandle(handle, nativeRecommendToMany(handle, vectors, vectorPtr, nQueries, howMany, excludePtr, excludeIdx, items, scores, counts));
+  }
+
+  /** recommend with a rescorer that the device runs (NativeIDRescorer; null = the plain call): the same answer as the Java
+   *  path with the same object as its IDRescorer, bit for bit. */
+  public static void recommend(long handle, long[] userIdx, int howMany, boolean considerKnownItems, NativeIDRescorer rescorer,
+                               long[] items, float[] scores, int[] counts) {
+    if (rescorer == null) {
+      recommend(handle, userIdx, howMany, considerKnownItems, items, scores, counts);
+      return;
+    }
+    checkHandle(handle, nativeRecommendRescored(handle, rescorer.nativeRescorer(handle), userIdx, howMany, considerKnownItems, items, scores,
+                                                counts));
+  }
+
+  /** recommendToMany / recommendToAnonymous with a rescorer that the device runs (null = the plain call). */
+  public static void recommendToMany(long handle, float[] vectors, long[] vectorPtr, int nQueries, int howMany, long[] excludePtr,
+                                     long[] excludeIdx, NativeIDRescorer rescorer, long[] items, float[] scores, int[] counts) {
+    if (rescorer == null) {
+      recommendToMany(handle, vectors, vectorPtr, nQueries, howMany, excludePtr, excludeIdx, items, scores, counts);
+      return;
+    }
+    checkHandle(handle, nativeRecommendToManyRescored(handle, rescorer.nativeRescorer(handle), vectors, vectorPtr, nQueries, howMany, excludePtr,
+                                                      excludeIdx, items, scores, counts));
+  }
+
+  // NativeIDRescorer's way to its device object
+  static long rescorerCreate(long handle) {
+    return nativeRescorerCreate(handle);
+  }
+
+  static void rescorerDestroy(long rescorer) {
+    nativeRescorerDestroy(rescorer);
+  }
+
+  static int rescorerSetFilter(long rescorer, long[] itemIdx) {
+    return nativeRescorerSetFilter(rescorer, itemIdx);
+  }
+
+  static int rescorerSetWeights(long rescorer, long[] scaleBits, long[] offsetBits, long nRows) {
+    return nativeRescorerSetWeights(rescorer, scaleBits, offsetBits, nRows);
+  }
+
+  static int rescorerSetUniform(long rescorer, long scaleBits, long offsetBits) {
+    return nativeRescorerSetUniform(rescorer, scaleBits, offsetBits);
+  }
+
+  static String lastError(long handle) {
+    return nativeLastError(handle);
   }
 
   private static void checkHandle(long handle, int status) {

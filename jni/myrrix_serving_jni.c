@@ -18,6 +18,7 @@
 #include <jni.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "myrrix_als.h"
 
@@ -278,6 +279,137 @@ JNIEXPORT jint JNICALL JNI_FN(nativeRecommendToMany)(JNIEnv* env, jclass cls, jl
     else
     rc = mals_recommend_to_many(as_handle(handle), (const float*)v, (const int64_t*)vp, (int32_t)n_queries, (int32_t)how_many, (const int64_t*)ep,
                                 (const int64_t*)ei, (int64_t*)it, (float*)sc, (int32_t*)cn);
+  }
+  const jint mode = rc == MALS_OK ? 0 : JNI_ABORT;
+  if (cn) (*env)->ReleaseIntArrayElements(env, counts, cn, mode);
+  if (sc) (*env)->ReleaseFloatArrayElements(env, scores, sc, mode);
+  if (it) (*env)->ReleaseLongArrayElements(env, items, it, mode);
+  if (ei) (*env)->ReleaseLongArrayElements(env, exclude_idx, ei, JNI_ABORT);
+  if (ep) (*env)->ReleaseLongArrayElements(env, exclude_ptr, ep, JNI_ABORT);
+  if (vp) (*env)->ReleaseLongArrayElements(env, vector_ptr, vp, JNI_ABORT);
+  if (v) (*env)->ReleaseFloatArrayElements(env, vectors, v, JNI_ABORT);
+  return rc;
+}
+
+/* ---- rescorers (include/myrrix_als.h): NativeIDRescorer's device side.  fp64 weights travel as their raw bits
+ * (Double.doubleToRawLongBits) in long arrays and are handed to the library as they are. ---- */
+static mals_rescorer as_rescorer(jlong r) { return (mals_rescorer)(intptr_t)r; }
+
+JNIEXPORT jlong JNICALL JNI_FN(nativeRescorerCreate)(JNIEnv* env, jclass cls, jlong handle) {
+  (void)env;
+  (void)cls;
+  mals_rescorer r = NULL;
+  if (mals_rescorer_create(as_handle(handle), &r) != MALS_OK) return 0;
+  return (jlong)(intptr_t)r;
+}
+
+JNIEXPORT void JNICALL JNI_FN(nativeRescorerDestroy)(JNIEnv* env, jclass cls, jlong rescorer) {
+  (void)env;
+  (void)cls;
+  if (rescorer) mals_rescorer_destroy(as_rescorer(rescorer));
+}
+
+JNIEXPORT jint JNICALL JNI_FN(nativeRescorerSetFilter)(JNIEnv* env, jclass cls, jlong rescorer, jlongArray item_idx) {
+  (void)cls;
+  if (!rescorer) return MALS_INVALID_ARG;
+  const jsize n = item_idx ? (*env)->GetArrayLength(env, item_idx) : 0;
+  if (n == 0) return mals_rescorer_set_filter(as_rescorer(rescorer), 0, NULL, MALS_MEM_HOST);
+  jlong* ii = (*env)->GetLongArrayElements(env, item_idx, NULL);
+  int rc = MALS_OOM;
+  if (ii) rc = mals_rescorer_set_filter(as_rescorer(rescorer), (int64_t)n, (const int64_t*)ii, MALS_MEM_HOST);
+  if (ii) (*env)->ReleaseLongArrayElements(env, item_idx, ii, JNI_ABORT);
+  return rc;
+}
+
+/* scale_bits / offset_bits: n_rows fp64 bit patterns each (either may be null) */
+JNIEXPORT jint JNICALL JNI_FN(nativeRescorerSetWeights)(JNIEnv* env, jclass cls, jlong rescorer, jlongArray scale_bits, jlongArray offset_bits,
+                                                       jlong n_rows) {
+  (void)cls;
+  if (!rescorer || n_rows < 0 || (scale_bits && (*env)->GetArrayLength(env, scale_bits) < n_rows) ||
+      (offset_bits && (*env)->GetArrayLength(env, offset_bits) < n_rows))
+    return MALS_INVALID_ARG;
+  jlong* sb = scale_bits ? (*env)->GetLongArrayElements(env, scale_bits, NULL) : NULL;
+  jlong* ob = offset_bits ? (*env)->GetLongArrayElements(env, offset_bits, NULL) : NULL;
+  double* sc = sb ? (double*)malloc(sizeof(double) * (size_t)(n_rows > 0 ? n_rows : 1)) : NULL;
+  double* of = ob ? (double*)malloc(sizeof(double) * (size_t)(n_rows > 0 ? n_rows : 1)) : NULL;
+  int rc = MALS_OOM;
+  if ((sb || !scale_bits) && (ob || !offset_bits) && (sc || !sb) && (of || !ob)) {
+    if (sc) memcpy(sc, sb, sizeof(double) * (size_t)n_rows);
+    if (of) memcpy(of, ob, sizeof(double) * (size_t)n_rows);
+    rc = mals_rescorer_set_weights(as_rescorer(rescorer), sc, of, (int64_t)n_rows, MALS_MEM_HOST);
+  }
+  free(of);
+  free(sc);
+  if (ob) (*env)->ReleaseLongArrayElements(env, offset_bits, ob, JNI_ABORT);
+  if (sb) (*env)->ReleaseLongArrayElements(env, scale_bits, sb, JNI_ABORT);
+  return rc;
+}
+
+JNIEXPORT jint JNICALL JNI_FN(nativeRescorerSetUniform)(JNIEnv* env, jclass cls, jlong rescorer, jlong scale_bits, jlong offset_bits) {
+  (void)env;
+  (void)cls;
+  if (!rescorer) return MALS_INVALID_ARG;
+  double s, o;
+  memcpy(&s, &scale_bits, sizeof(double));
+  memcpy(&o, &offset_bits, sizeof(double));
+  return mals_rescorer_set_uniform(as_rescorer(rescorer), s, o);
+}
+
+/* nativeRecommend with a rescorer (0: none) */
+JNIEXPORT jint JNICALL JNI_FN(nativeRecommendRescored)(JNIEnv* env, jclass cls, jlong handle, jlong rescorer, jlongArray user_idx, jint how_many,
+                                                      jboolean consider_known_items, jlongArray items, jfloatArray scores, jintArray counts) {
+  (void)cls;
+  const jsize nq = (*env)->GetArrayLength(env, user_idx);
+  if (how_many < 1 || (int64_t)(*env)->GetArrayLength(env, items) < (int64_t)nq * how_many ||
+      (int64_t)(*env)->GetArrayLength(env, scores) < (int64_t)nq * how_many || (counts && (*env)->GetArrayLength(env, counts) < nq))
+    return MALS_INVALID_ARG;
+  jlong* u = (*env)->GetLongArrayElements(env, user_idx, NULL);
+  jlong* it = (*env)->GetLongArrayElements(env, items, NULL);
+  jfloat* sc = (*env)->GetFloatArrayElements(env, scores, NULL);
+  jint* cn = counts ? (*env)->GetIntArrayElements(env, counts, NULL) : NULL;
+  int rc = MALS_OOM;
+  if (u && it && sc && (cn || !counts))
+    rc = mals_recommend_rescored(as_handle(handle), as_rescorer(rescorer), (const int64_t*)u, (int32_t)nq, (int32_t)how_many, consider_known_items ? 1 : 0,
+                                 (int64_t*)it, (float*)sc, (int32_t*)cn);
+  const jint mode = rc == MALS_OK ? 0 : JNI_ABORT;
+  if (cn) (*env)->ReleaseIntArrayElements(env, counts, cn, mode);
+  if (sc) (*env)->ReleaseFloatArrayElements(env, scores, sc, mode);
+  if (it) (*env)->ReleaseLongArrayElements(env, items, it, mode);
+  if (u) (*env)->ReleaseLongArrayElements(env, user_idx, u, JNI_ABORT);
+  return rc;
+}
+
+/* nativeRecommendToMany with a rescorer (0: none).  An exclusion offset array without its index array is refused before
+ * any length is read from either. */
+JNIEXPORT jint JNICALL JNI_FN(nativeRecommendToManyRescored)(JNIEnv* env, jclass cls, jlong handle, jlong rescorer, jfloatArray vectors,
+                                                            jlongArray vector_ptr, jint n_queries, jint how_many, jlongArray exclude_ptr,
+                                                            jlongArray exclude_idx, jlongArray items, jfloatArray scores, jintArray counts) {
+  (void)cls;
+  if ((!exclude_ptr) != (!exclude_idx)) return MALS_INVALID_ARG;
+  if (n_queries < 0 || how_many < 1 || !vectors || (vector_ptr && (*env)->GetArrayLength(env, vector_ptr) < n_queries + 1) ||
+      (exclude_ptr && (*env)->GetArrayLength(env, exclude_ptr) < n_queries + 1) ||
+      (int64_t)(*env)->GetArrayLength(env, items) < (int64_t)n_queries * how_many ||
+      (int64_t)(*env)->GetArrayLength(env, scores) < (int64_t)n_queries * how_many || (counts && (*env)->GetArrayLength(env, counts) < n_queries))
+    return MALS_INVALID_ARG;
+  jfloat* v = (*env)->GetFloatArrayElements(env, vectors, NULL);
+  jlong* vp = vector_ptr ? (*env)->GetLongArrayElements(env, vector_ptr, NULL) : NULL;
+  jlong* ep = exclude_ptr ? (*env)->GetLongArrayElements(env, exclude_ptr, NULL) : NULL;
+  jlong* ei = exclude_idx ? (*env)->GetLongArrayElements(env, exclude_idx, NULL) : NULL;
+  jlong* it = (*env)->GetLongArrayElements(env, items, NULL);
+  jfloat* sc = (*env)->GetFloatArrayElements(env, scores, NULL);
+  jint* cn = counts ? (*env)->GetIntArrayElements(env, counts, NULL) : NULL;
+  int rc = MALS_OOM;
+  if (v && it && sc && (vp || !vector_ptr) && (ep || !exclude_ptr) && (ei || !exclude_idx) && (cn || !counts)) {
+    /* what the offsets promise must be inside the arrays they index */
+    mals_handle hh = as_handle(handle);
+    const int64_t n_vec = vp ? (int64_t)vp[n_queries] : (int64_t)n_queries;
+    const int64_t features = (int64_t)mals_features(hh);
+    if (n_vec < 0 || features <= 0 || (int64_t)(*env)->GetArrayLength(env, vectors) < n_vec * features ||
+        (ep && (ep[0] < 0 || ep[n_queries] < ep[0] || (int64_t)(*env)->GetArrayLength(env, exclude_idx) < (int64_t)ep[n_queries])))
+      rc = MALS_INVALID_ARG;
+    else
+      rc = mals_recommend_to_many_rescored(hh, as_rescorer(rescorer), (const float*)v, (const int64_t*)vp, (int32_t)n_queries, (int32_t)how_many,
+                                           (const int64_t*)ep, (const int64_t*)ei, (int64_t*)it, (float*)sc, (int32_t*)cn);
   }
   const jint mode = rc == MALS_OK ? 0 : JNI_ABORT;
   if (cn) (*env)->ReleaseIntArrayElements(env, counts, cn, mode);

@@ -165,6 +165,14 @@ SYMBOLS = {
     "mals_estimate_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P]),
     "mals_anonymous_features": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P]),
     "mals_recommend_to_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "mals_rescorer_create": (ctypes.c_int, [_H, ctypes.POINTER(_H)]),
+    "mals_rescorer_destroy": (ctypes.c_int, [_H]),
+    "mals_rescorer_set_filter": (ctypes.c_int, [_H, _I64, _P, ctypes.c_int]),
+    "mals_rescorer_set_weights": (ctypes.c_int, [_H, _P, _P, _I64, ctypes.c_int]),
+    "mals_rescorer_set_uniform": (ctypes.c_int, [_H, ctypes.c_double, ctypes.c_double]),
+    "mals_recommend_rescored": (ctypes.c_int, [_H, _H, _P, _I32, _I32, _I32, _P, _P, _P]),
+    "mals_recommend_to_many_rescored": (ctypes.c_int, [_H, _H, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "mals_recommend_to_anonymous_rescored": (ctypes.c_int, [_H, _H, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "mals_estimate_for_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P, _P]),
     "mals_set_tag_items": (ctypes.c_int, [_H, _I64, _P, ctypes.c_int]),
     "mals_get_tag_item_count": (ctypes.c_int, [_H, ctypes.POINTER(_I64)]),

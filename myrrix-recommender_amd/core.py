@@ -112,6 +112,53 @@ def _item_queries(items):
     return flat, ptr
 
 
+class Rescorer:
+    """RecommendIterator's IDRescorer in the form the device runs (include/myrrix_als.h, "rescorers"): a filter set of
+    item indices and rescore(i, sum) = fl(fl(scale_i * sum) + offset_i) in fp64, applied to the sum of the dots before the
+    division by the query's vector count.  Made by ALSCore.rescorer(); bound to that handle."""
+
+    def __init__(self, core):
+        self._core = core
+        self._h = ctypes.c_void_p()
+        core._chk(core._L.mals_rescorer_create(core._h, ctypes.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set_filter(self, items):
+        """isFiltered: these dense item indices are skipped; None or empty clears."""
+        ii = _host(items if items is not None else [], np.int64)
+        self._core._chk(self._core._L.mals_rescorer_set_filter(self._h, len(ii), ii.ctypes.data_as(ctypes.c_void_p) if len(ii) else None, MEM_HOST))
+
+    def set_weights(self, scale=None, offset=None):
+        """Per-item fp64 weights of rows [0, len): scale_i > 0 and finite, offset_i finite; either may be None (1 / 0).
+        Rows past the arrays have scale 1 and offset 0."""
+        sc = None if scale is None else _host(scale, np.float64)
+        of = None if offset is None else _host(offset, np.float64)
+        n = len(sc) if sc is not None else len(of) if of is not None else 0
+        if sc is not None and of is not None and len(sc) != len(of):
+            raise ValueError("scale and offset cover different rows (%d, %d)" % (len(sc), len(of)))
+        self._core._chk(self._core._L.mals_rescorer_set_weights(
+            self._h, sc.ctypes.data_as(ctypes.c_void_p) if sc is not None and n else None,
+            of.ctypes.data_as(ctypes.c_void_p) if of is not None and n else None, n, MEM_HOST))
+
+    def set_uniform(self, scale=1.0, offset=0.0):
+        """The same weights for every item (replaces per-item weights)."""
+        self._core._chk(self._core._L.mals_rescorer_set_uniform(self._h, float(scale), float(offset)))
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            self._core._L.mals_rescorer_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class ALSCore:
     def __init__(self, features, alpha=1.0, lam=0.1, flags=0, device=0, segment_nnz=0,
                  singularity_threshold=1e-5, chunk_rows=0, gramian_mode=0, solve_mode=0):
@@ -338,20 +385,27 @@ class ALSCore:
     def cancel(self):
         self._chk(self._L.mals_cancel(self._h))
 
-    def recommend(self, user_idx, how_many, consider_known_items=False):
+    def rescorer(self):
+        """A new Rescorer bound to this handle (the identity until it is set)."""
+        return Rescorer(self)
+
+    def recommend(self, user_idx, how_many, consider_known_items=False, rescorer=None):
         """ServerRecommender.recommend for model users (dense indices): (item_idx [q][how_many] int64,
-        scores float32, counts)."""
+        scores float32, counts).  rescorer: a Rescorer of this handle (None: none)."""
         u = _host(user_idx, np.int64)
         idx = np.empty((len(u), how_many), dtype=np.int64)
         sc = np.empty((len(u), how_many), dtype=np.float32)
         cnt = np.empty(len(u), dtype=np.int32)
-        self._chk(self._L.mals_recommend(self._h, u.ctypes.data_as(ctypes.c_void_p), len(u), int(how_many),
-                                         1 if consider_known_items else 0, idx.ctypes.data_as(ctypes.c_void_p),
-                                         sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        args = (u.ctypes.data_as(ctypes.c_void_p), len(u), int(how_many), 1 if consider_known_items else 0,
+                idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p))
+        if rescorer is None:
+            self._chk(self._L.mals_recommend(self._h, *args))
+        else:
+            self._chk(self._L.mals_recommend_rescored(self._h, rescorer.handle, *args))
         return idx, sc, cnt
 
-    def recommend_vectors(self, vectors, how_many, exclude=None):
-        """Top-N for caller-supplied query vectors; exclude: optional list of item-index lists."""
+    def recommend_vectors(self, vectors, how_many, exclude=None, rescorer=None):
+        """Top-N for caller-supplied query vectors; exclude: optional list of item-index lists; rescorer: a Rescorer."""
         v = _host(vectors, np.float32)
         assert v.ndim == 2 and v.shape[1] == self.features
         idx = np.empty((len(v), how_many), dtype=np.int64)
@@ -364,9 +418,14 @@ class ALSCore:
             flat = np.ascontiguousarray(np.concatenate([np.asarray(e, np.int64) for e in exclude]) if ptr[-1] else np.zeros(0, np.int64))
             ep, ei = ptr.ctypes.data_as(ctypes.c_void_p), flat.ctypes.data_as(ctypes.c_void_p)
             self._keep[("excl",)] = (ptr, flat)
-        self._chk(self._L.mals_recommend_vectors(self._h, v.ctypes.data_as(ctypes.c_void_p), len(v), int(how_many), ep, ei,
-                                                 idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
-                                                 cnt.ctypes.data_as(ctypes.c_void_p)))
+        if rescorer is None:
+            self._chk(self._L.mals_recommend_vectors(self._h, v.ctypes.data_as(ctypes.c_void_p), len(v), int(how_many), ep, ei,
+                                                     idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+                                                     cnt.ctypes.data_as(ctypes.c_void_p)))
+        else:
+            self._chk(self._L.mals_recommend_to_many_rescored(self._h, rescorer.handle, v.ctypes.data_as(ctypes.c_void_p), None, len(v),
+                                                              int(how_many), ep, ei, idx.ctypes.data_as(ctypes.c_void_p),
+                                                              sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
         return idx, sc, cnt
 
     def set_known_items(self, row_ptr, item_idx):
@@ -401,7 +460,7 @@ class ALSCore:
     def recommend_set_spin_us(self, spin_us):
         self._chk(self._L.mals_recommend_set_spin_us(self._h, int(spin_us)))
 
-    def recommend_to_many(self, queries, how_many, exclude=None):
+    def recommend_to_many(self, queries, how_many, exclude=None, rescorer=None):
         """recommendToMany (ServerRecommender.java:366-441): queries = list of (n_j x features) arrays, one per query; the
         score of an item is the mean of its dots with the query's vectors (RecommendIterator.java:93-104)."""
         qs = [np.ascontiguousarray(np.atleast_2d(_host(q, np.float32))) for q in queries]
@@ -419,9 +478,12 @@ class ALSCore:
             flat = np.ascontiguousarray(np.concatenate([np.asarray(e, np.int64) for e in exclude]) if ptr[-1] else np.zeros(0, np.int64))
             ep, ei = ptr.ctypes.data_as(ctypes.c_void_p), flat.ctypes.data_as(ctypes.c_void_p)
             self._keep[("excl",)] = (ptr, flat)
-        self._chk(self._L.mals_recommend_to_many(self._h, flatv.ctypes.data_as(ctypes.c_void_p), vptr.ctypes.data_as(ctypes.c_void_p),
-                                                 len(qs), int(how_many), ep, ei, idx.ctypes.data_as(ctypes.c_void_p),
-                                                 sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        args = (flatv.ctypes.data_as(ctypes.c_void_p), vptr.ctypes.data_as(ctypes.c_void_p), len(qs), int(how_many), ep, ei,
+                idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p))
+        if rescorer is None:
+            self._chk(self._L.mals_recommend_to_many(self._h, *args))
+        else:
+            self._chk(self._L.mals_recommend_to_many_rescored(self._h, rescorer.handle, *args))
         return idx, sc, cnt
 
     def most_similar_items(self, items, how_many):
@@ -536,18 +598,22 @@ class ALSCore:
             self._chk(rc)
         return out, st
 
-    def recommend_to_anonymous(self, queries, how_many, values=None):
-        """recommendToAnonymous: (item_idx, scores, counts, status) per query."""
+    def recommend_to_anonymous(self, queries, how_many, values=None, rescorer=None):
+        """recommendToAnonymous: (item_idx, scores, counts, status) per query; rescorer: a Rescorer."""
         flat, ptr, vals = self._anon_args(queries, values)
         nq = len(ptr) - 1
         idx = np.empty((nq, how_many), dtype=np.int64)
         sc = np.empty((nq, how_many), dtype=np.float32)
         cnt = np.empty(nq, dtype=np.int32)
         st = np.zeros(nq, dtype=np.int32)
-        rc = self._L.mals_recommend_to_anonymous(self._h, nq, ptr.ctypes.data_as(ctypes.c_void_p), flat.ctypes.data_as(ctypes.c_void_p),
-                                                 vals.ctypes.data_as(ctypes.c_void_p) if vals is not None else None, int(how_many),
-                                                 idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
-                                                 cnt.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        args = (nq, ptr.ctypes.data_as(ctypes.c_void_p), flat.ctypes.data_as(ctypes.c_void_p),
+                vals.ctypes.data_as(ctypes.c_void_p) if vals is not None else None, int(how_many),
+                idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+                cnt.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if rescorer is None:
+            rc = self._L.mals_recommend_to_anonymous(self._h, *args)
+        else:
+            rc = self._L.mals_recommend_to_anonymous_rescored(self._h, rescorer.handle, *args)
         if not st.any():
             self._chk(rc)
         return idx, sc, cnt, st

@@ -28,6 +28,7 @@
 #include <functional>
 #include <iterator>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -1269,6 +1270,35 @@ int launch_reconstruction(mals_handle h, SideState& s, SideState& o, unsigned gr
 }  // namespace
 
 
+// ---- rescorers (mals_rescorer_*, include/myrrix_als.h; the kernels' side in topn_kernels.h, RESCORED MODE) ---------------
+// What a pass reads is an immutable snapshot: mals_rescorer_set_* builds a new one (an exclusive ticket of the serving front,
+// so every call sees the rescorer as it was when the call was queued) and passes in flight keep the one they were formed with.
+struct RescorerState {
+  // the caller's definition (host copies: the next set_* rebuilds from them)
+  std::vector<int64_t> filt_idx;         // sorted, unique
+  std::vector<double> scale, offset;     // per-item weights (either may be empty), rows [0, n_rows)
+  int64_t n_rows = 0;
+  double us = 1.0, uo = 0.0;             // the uniform weights of every other row (mals_rescorer_set_uniform)
+  // on the device
+  DeviceBuffer<uint32_t> d_filt;
+  DeviceBuffer<double> d_scale, d_offset;
+  DeviceBuffer<uint4> d_fdata;
+  TopnRescore args;
+  bool filter_ok = true;                 // every weight inside the filter's range (topn_kernels.h), else the dense path answers
+};
+struct mals_rescorer_s {
+  mals_handle h = nullptr;
+  std::shared_ptr<const RescorerState> st;
+};
+
+namespace {
+bool rescorer_filter_ok(const mals_rescorer_s* r) { return r->st->filter_ok; }
+void rescorer_bind(const mals_rescorer_s* r, std::shared_ptr<const RescorerState>& keep, TopnRescore& args) {
+  keep = r->st;
+  args = keep->args;
+}
+}  // namespace
+
 namespace {
 #include "topn_host.h"
 #include "foldin_host.h"
@@ -2430,9 +2460,10 @@ static int topn_fail(mals_handle h, int code, const char* msg) {
   return code;
 }
 
-int mals_recommend(mals_handle h, const int64_t* user_idx, int32_t n_queries, int32_t how_many, int32_t consider_known_items,
-                   int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+static int topn_recommend_impl(mals_handle h, mals_rescorer r, const int64_t* user_idx, int32_t n_queries, int32_t how_many,
+                               int32_t consider_known_items, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
   if (!h) return MALS_INVALID_ARG;
+  if (r && r->h != h) return topn_fail(h, MALS_INVALID_ARG, "the rescorer belongs to another handle");
   SideState& x = h->side[MALS_SIDE_X];
   SideState& y = h->side[MALS_SIDE_Y];
   if (!x.F || !y.F || y.n_total == 0) return topn_fail(h, MALS_INVALID_ARG, "factor replicas not available");
@@ -2472,7 +2503,14 @@ int mals_recommend(mals_handle h, const int64_t* user_idx, int32_t n_queries, in
     t.bulk = &rq;
     t.how_many = how_many;
   }
+  t.rescorer = r;
+  rq.rescorer = r;
   return topn_front_submit(h, t);
+}
+
+int mals_recommend(mals_handle h, const int64_t* user_idx, int32_t n_queries, int32_t how_many, int32_t consider_known_items,
+                   int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  return topn_recommend_impl(h, nullptr, user_idx, n_queries, how_many, consider_known_items, item_idx_out, score_out, n_out);
 }
 
 int mals_set_known_items(mals_handle h, int64_t n_rows, const int64_t* row_ptr, const int32_t* item_idx, int mem_kind) {
@@ -2544,10 +2582,11 @@ int mals_get_tag_item_count(mals_handle h, int64_t* n_out) {
   return MALS_OK;
 }
 
-int mals_recommend_to_many(mals_handle h, const float* vectors, const int64_t* vector_ptr, int32_t n_queries, int32_t how_many,
-                           const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out, float* score_out,
-                           int32_t* n_out) {
+static int topn_to_many_impl(mals_handle h, mals_rescorer r, const float* vectors, const int64_t* vector_ptr, int32_t n_queries, int32_t how_many,
+                             const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out, float* score_out,
+                             int32_t* n_out) {
   if (!h) return MALS_INVALID_ARG;
+  if (r && r->h != h) return topn_fail(h, MALS_INVALID_ARG, "the rescorer belongs to another handle");
   SideState& y = h->side[MALS_SIDE_Y];
   if (!y.F || y.n_total == 0) return topn_fail(h, MALS_INVALID_ARG, "item factor replica not available");
   if (n_queries < 0 || how_many <= 0 || how_many > 4096 || (n_queries > 0 && (!vectors || !item_idx_out || !score_out)))
@@ -2594,7 +2633,15 @@ int mals_recommend_to_many(mals_handle h, const float* vectors, const int64_t* v
     rq.n_out = n_out;
     t.bulk = &rq;
   }
+  t.rescorer = r;
+  rq.rescorer = r;
   return topn_front_submit(h, t);
+}
+
+int mals_recommend_to_many(mals_handle h, const float* vectors, const int64_t* vector_ptr, int32_t n_queries, int32_t how_many,
+                           const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out, float* score_out,
+                           int32_t* n_out) {
+  return topn_to_many_impl(h, nullptr, vectors, vector_ptr, n_queries, how_many, exclude_ptr, exclude_idx, item_idx_out, score_out, n_out);
 }
 
 int mals_recommend_vectors(mals_handle h, const float* query_vectors, int32_t n_queries, int32_t how_many,
@@ -3019,9 +3066,10 @@ int mals_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t*
 }
 
 // two tickets: the vectors, then the top-N (like the reference, which holds no lock across the two, a write may land between)
-int mals_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
-                                int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out) {
+static int topn_anonymous_impl(mals_handle h, mals_rescorer r, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row,
+                               const float* values, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out) {
   if (!h) return MALS_INVALID_ARG;
+  if (r && r->h != h) return topn_fail(h, MALS_INVALID_ARG, "the rescorer belongs to another handle");
   if (n_queries > 0 && (how_many <= 0 || how_many > 4096 || !item_idx_out || !score_out))
     return topn_fail(h, MALS_INVALID_ARG, "mals_recommend_to_anonymous: bad arguments (how_many in 1..4096)");
   const int k = h->cfg.features;
@@ -3053,7 +3101,7 @@ int mals_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t*
     std::vector<int64_t> idx(qs.size() * (size_t)how_many);
     std::vector<float> sc(qs.size() * (size_t)how_many);
     std::vector<int32_t> cnt(qs.size());
-    if (int rc = mals_recommend_to_many(h, vecs.data(), nullptr, (int32_t)qs.size(), how_many, eptr.data(), eidx.data(), idx.data(), sc.data(), cnt.data()))
+    if (int rc = topn_to_many_impl(h, r, vecs.data(), nullptr, (int32_t)qs.size(), how_many, eptr.data(), eidx.data(), idx.data(), sc.data(), cnt.data()))
       return rc;
     for (size_t i = 0; i < qs.size(); ++i) {
       std::copy(idx.begin() + i * how_many, idx.begin() + (i + 1) * how_many, item_idx_out + (size_t)qs[i] * how_many);
@@ -3062,6 +3110,11 @@ int mals_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t*
     }
   }
   return rc_f;
+}
+
+int mals_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                                int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out) {
+  return topn_anonymous_impl(h, nullptr, n_queries, item_ptr, item_row, values, how_many, item_idx_out, score_out, n_out, status_out);
 }
 
 int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, double* x_out) {
@@ -3095,3 +3148,211 @@ int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, do
 
 }  // extern "C"
 
+
+// ---- rescorers: RecommendIterator's IDRescorer in the form the device runs (topn_kernels.h, RESCORED MODE) ------------
+namespace {
+uint16_t rescorer_bf16(float v) {   // round to nearest even (finite v)
+  uint32_t u;
+  std::memcpy(&u, &v, 4);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+float rescorer_bf16_value(uint16_t b) {
+  const uint32_t u = (uint32_t)b << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+// the filter's 16 bytes of one item (topn_kernels.h)
+uint4 rescorer_fdata(double s, double o, bool filtered) {
+  if (filtered) {
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    uint32_t z;
+    std::memcpy(&z, &nan, 4);
+    return make_uint4(0u, (uint32_t)rescorer_bf16(-0x1p120f), z, 0u);
+  }
+  const double rs = 1.0 / s, os = o / s;
+  const uint16_t rh = rescorer_bf16((float)rs), rl = rescorer_bf16((float)(rs - (double)rescorer_bf16_value(rh)));
+  const uint16_t oh = rescorer_bf16((float)os), ol = rescorer_bf16((float)(os - (double)rescorer_bf16_value(oh)));
+  const float sf = (float)s;
+  uint32_t z;
+  std::memcpy(&z, &sf, 4);
+  return make_uint4((uint32_t)rh | ((uint32_t)rl << 16), (uint32_t)oh | ((uint32_t)ol << 16), z, 0u);
+}
+bool rescorer_in_range(double s, double o) {
+  return s >= 1.0 / TOPN_RS_MAX_SCALE && s <= TOPN_RS_MAX_SCALE && std::fabs(o) <= TOPN_RS_MAX_OFFSET;
+}
+// the device side of a new definition (runs as an exclusive ticket: nothing else is on the handle's stream)
+int rescorer_upload(mals_handle h, RescorerState& st) {
+  const int64_t n_filt = st.filt_idx.empty() ? 0 : st.filt_idx.back() + 1;
+  const int64_t n_f = std::max<int64_t>(n_filt, (st.scale.empty() && st.offset.empty()) ? 0 : st.n_rows);
+  std::vector<uint32_t> bits((size_t)((n_filt + 31) / 32), 0u);
+  for (int64_t i : st.filt_idx) bits[(size_t)(i >> 5)] |= 1u << (i & 31);
+  st.filter_ok = rescorer_in_range(st.us, st.uo);
+  std::vector<uint4> fd((size_t)n_f);
+  for (int64_t i = 0; i < n_f; ++i) {
+    const bool arr = i < st.n_rows;
+    const double s = arr && !st.scale.empty() ? st.scale[(size_t)i] : st.us, o = arr && !st.offset.empty() ? st.offset[(size_t)i] : st.uo;
+    const bool f = i < n_filt && ((bits[(size_t)(i >> 5)] >> (i & 31)) & 1u);
+    if (!f && !rescorer_in_range(s, o)) st.filter_ok = false;
+    fd[(size_t)i] = rescorer_fdata(s, o, f);
+  }
+  TopnRescore& a = st.args;
+  a = TopnRescore();
+  if (n_filt) {
+    HIPCHK(h, st.d_filt.alloc(bits.size()));
+    HIPCHK(h, hipMemcpyAsync(st.d_filt.get(), bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice, h->stream));
+    a.filt = st.d_filt.get();
+    a.filt_items = n_filt;
+  }
+  if (!st.scale.empty()) {
+    HIPCHK(h, st.d_scale.alloc(st.scale.size()));
+    HIPCHK(h, hipMemcpyAsync(st.d_scale.get(), st.scale.data(), sizeof(double) * st.scale.size(), hipMemcpyHostToDevice, h->stream));
+    a.scale = st.d_scale.get();
+  }
+  if (!st.offset.empty()) {
+    HIPCHK(h, st.d_offset.alloc(st.offset.size()));
+    HIPCHK(h, hipMemcpyAsync(st.d_offset.get(), st.offset.data(), sizeof(double) * st.offset.size(), hipMemcpyHostToDevice, h->stream));
+    a.offset = st.d_offset.get();
+  }
+  a.n_rows = (st.scale.empty() && st.offset.empty()) ? 0 : st.n_rows;
+  a.us = st.us;
+  a.uo = st.uo;
+  if (n_f) {
+    HIPCHK(h, st.d_fdata.alloc((size_t)n_f));
+    HIPCHK(h, hipMemcpyAsync(st.d_fdata.get(), fd.data(), sizeof(uint4) * (size_t)n_f, hipMemcpyHostToDevice, h->stream));
+    a.fdata = st.d_fdata.get();
+    a.n_fdata = n_f;
+  }
+  a.fdef = rescorer_fdata(st.us, st.uo, false);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MALS_OK;
+}
+// a new definition = the current one changed by `edit`, swapped in as an exclusive ticket of the front
+int rescorer_replace(mals_rescorer r, const char* call, const std::function<std::string(RescorerState&)>& edit) {
+  mals_handle h = r->h;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    auto st = std::make_shared<RescorerState>();
+    st->filt_idx = r->st->filt_idx;
+    st->scale = r->st->scale;
+    st->offset = r->st->offset;
+    st->n_rows = r->st->n_rows;
+    st->us = r->st->us;
+    st->uo = r->st->uo;
+    msg = edit(*st);
+    if (!msg.empty()) return MALS_INVALID_ARG;
+    if (int rc = use_device(h)) {
+      msg = h->err;
+      return rc;
+    }
+    if (int rc = rescorer_upload(h, *st)) {
+      msg = h->err;
+      return rc;
+    }
+    r->st = std::move(st);
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, call);
+}
+template <typename T>
+bool rescorer_host_copy(mals_handle h, const T* p, int64_t n, int mem_kind, std::vector<T>& out) {
+  out.resize((size_t)n);
+  if (n == 0) return true;
+  if (mem_kind == MALS_MEM_HOST) {
+    std::memcpy(out.data(), p, sizeof(T) * (size_t)n);
+    return true;
+  }
+  return hipMemcpy(out.data(), p, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
+}
+}  // namespace
+
+int mals_rescorer_create(mals_handle h, mals_rescorer* out) {
+  if (!h || !out) return MALS_INVALID_ARG;
+  mals_rescorer r = new (std::nothrow) mals_rescorer_s();
+  if (!r) return fail(h, MALS_OOM, "mals_rescorer_create: out of host memory");
+  r->h = h;
+  auto st = std::make_shared<RescorerState>();
+  st->args.fdef = rescorer_fdata(1.0, 0.0, false);
+  r->st = std::move(st);
+  *out = r;
+  return MALS_OK;
+}
+
+int mals_rescorer_destroy(mals_rescorer r) {
+  delete r;   // (passes formed with it keep their snapshot)
+  return MALS_OK;
+}
+
+int mals_rescorer_set_filter(mals_rescorer r, int64_t n, const int64_t* item_idx, int mem_kind) {
+  if (!r) return MALS_INVALID_ARG;
+  mals_handle h = r->h;
+  if (mem_kind != MALS_MEM_HOST && mem_kind != MALS_MEM_DEVICE) return topn_fail(h, MALS_INVALID_ARG, "mals_rescorer_set_filter: bad mem_kind");
+  if (n < 0 || (n > 0 && !item_idx)) return topn_fail(h, MALS_INVALID_ARG, "mals_rescorer_set_filter: bad item list");
+  std::vector<int64_t> idx;
+  if (n > 0 && (mem_kind == MALS_MEM_DEVICE && use_device(h) != MALS_OK)) return MALS_HIP_ERROR;
+  if (!rescorer_host_copy(h, item_idx, n, mem_kind, idx)) return topn_fail(h, MALS_HIP_ERROR, "mals_rescorer_set_filter: copy failed");
+  return rescorer_replace(r, "mals_rescorer_set_filter", [&](RescorerState& st) -> std::string {
+    const int64_t n_items = h->side[MALS_SIDE_Y].n_total;
+    for (int64_t i : idx)
+      if (i < 0 || i >= n_items) return "item index outside the item factor replica";
+    std::sort(idx.begin(), idx.end());
+    idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+    st.filt_idx = std::move(idx);
+    return std::string();
+  });
+}
+
+int mals_rescorer_set_weights(mals_rescorer r, const double* scale, const double* offset, int64_t n_rows, int mem_kind) {
+  if (!r) return MALS_INVALID_ARG;
+  mals_handle h = r->h;
+  if (mem_kind != MALS_MEM_HOST && mem_kind != MALS_MEM_DEVICE) return topn_fail(h, MALS_INVALID_ARG, "mals_rescorer_set_weights: bad mem_kind");
+  if (n_rows < 0) return topn_fail(h, MALS_INVALID_ARG, "mals_rescorer_set_weights: n_rows < 0");
+  std::vector<double> sc, of;
+  if (n_rows > 0 && (scale || offset) && mem_kind == MALS_MEM_DEVICE && use_device(h) != MALS_OK) return MALS_HIP_ERROR;
+  if ((scale && !rescorer_host_copy(h, scale, n_rows, mem_kind, sc)) || (offset && !rescorer_host_copy(h, offset, n_rows, mem_kind, of)))
+    return topn_fail(h, MALS_HIP_ERROR, "mals_rescorer_set_weights: copy failed");
+  for (double v : sc)
+    if (!(v > 0.0 && v < std::numeric_limits<double>::infinity())) return topn_fail(h, MALS_INVALID_ARG, "mals_rescorer_set_weights: every scale must be finite and > 0");
+  for (double v : of)
+    if (!std::isfinite(v)) return topn_fail(h, MALS_INVALID_ARG, "mals_rescorer_set_weights: every offset must be finite");
+  return rescorer_replace(r, "mals_rescorer_set_weights", [&](RescorerState& st) -> std::string {
+    st.scale = std::move(sc);
+    st.offset = std::move(of);
+    st.n_rows = (st.scale.empty() && st.offset.empty()) ? 0 : n_rows;
+    st.us = 1.0;
+    st.uo = 0.0;
+    return std::string();
+  });
+}
+
+int mals_rescorer_set_uniform(mals_rescorer r, double scale, double offset) {
+  if (!r) return MALS_INVALID_ARG;
+  if (!(scale > 0.0 && scale < std::numeric_limits<double>::infinity()) || !std::isfinite(offset))
+    return topn_fail(r->h, MALS_INVALID_ARG, "mals_rescorer_set_uniform: scale must be finite and > 0, offset finite");
+  return rescorer_replace(r, "mals_rescorer_set_uniform", [&](RescorerState& st) -> std::string {
+    st.scale.clear();
+    st.offset.clear();
+    st.n_rows = 0;
+    st.us = scale;
+    st.uo = offset;
+    return std::string();
+  });
+}
+
+int mals_recommend_rescored(mals_handle h, mals_rescorer r, const int64_t* user_idx, int32_t n_queries, int32_t how_many,
+                            int32_t consider_known_items, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  return topn_recommend_impl(h, r, user_idx, n_queries, how_many, consider_known_items, item_idx_out, score_out, n_out);
+}
+
+int mals_recommend_to_many_rescored(mals_handle h, mals_rescorer r, const float* vectors, const int64_t* vector_ptr, int32_t n_queries,
+                                    int32_t how_many, const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out,
+                                    float* score_out, int32_t* n_out) {
+  return topn_to_many_impl(h, r, vectors, vector_ptr, n_queries, how_many, exclude_ptr, exclude_idx, item_idx_out, score_out, n_out);
+}
+
+int mals_recommend_to_anonymous_rescored(mals_handle h, mals_rescorer r, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row,
+                                         const float* values, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out,
+                                         int32_t* status_out) {
+  return topn_anonymous_impl(h, r, n_queries, item_ptr, item_row, values, how_many, item_idx_out, score_out, n_out, status_out);
+}

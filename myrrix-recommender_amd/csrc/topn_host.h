@@ -93,7 +93,15 @@ struct TopnRequest {
   float* sim_out = nullptr;
   // a write or fold-in read of foldin_host.h (TOPN_KIND_CALL): runs alone on the handle, in queue order
   const std::function<int()>* call = nullptr;
+  // a rescored call (kind TOPN_KIND_SCORE, not cosine): the rescorer named by the caller, and what the pass reads of it (the
+  // state it had when the call's turn came: a mals_rescorer_set_* is an exclusive ticket of the front)
+  const mals_rescorer_s* rescorer = nullptr;
+  const TopnRescore* rs = nullptr;
+  // per query: 1 = its result is not finite (RecommendIterator.java:105) -- the query's caller fails, the others are answered.
+  // NULL: the whole request fails
+  uint8_t* bad_q = nullptr;
 };
+constexpr const char* TOPN_BAD_VALUE = "Bad recommendation value: a non-finite score (non-finite factors; RecommendIterator.java:105 throws IllegalStateException)";
 enum { TOPN_KIND_SCORE = 0, TOPN_KIND_BECAUSE = 1, TOPN_KIND_SIMILARITY_TO = 2, TOPN_KIND_CALL = 3 };
 
 inline TopnOut topn_out(const TopnRequest& rq, size_t qq) {
@@ -249,10 +257,13 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
     hipLaunchKernelGGL(topn_qnorm_kernel, dim3((unsigned)((ps.n_vecs + 63) / 64)), dim3(64), 0, h->stream, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs, k,
                        sl.d_qn.get());
     hipLaunchKernelGGL(topn_exact_dense_kernel<true>, dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k,
-                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), sl.d_qn.get());
+                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), sl.d_qn.get(), TopnRescore());
+  } else if (rq.rs) {
+    hipLaunchKernelGGL((topn_exact_dense_kernel<false, true>), dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k,
+                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), nullptr, *rq.rs);
   } else {
     hipLaunchKernelGGL(topn_exact_dense_kernel<false>, dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k,
-                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), nullptr);
+                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), nullptr, TopnRescore());
   }
   if (ps.have_rows)
     hipLaunchKernelGGL(topn_mask_kernel, dim3(64, (unsigned)nq), dim3(256), 0, h->stream, h->known_ptr ? h->known_ptr : x.row_ptr,
@@ -296,8 +307,10 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
       for (uint32_t p = 0; p < ties_stored; ++p) cand.push_back({o[2 * (how_many + p) + 1], (int64_t)o[2 * (how_many + p)]});
     }
     const TopnOut o_q = topn_out(rq, (size_t)(ps.q0 + q));
-    if (!topn_emit(cand, how_many, o_q.items, o_q.scores, o_q.n))
-      return fail(h, MALS_INVALID_ARG, "Bad recommendation value: a non-finite score (non-finite factors; RecommendIterator.java:105 throws IllegalStateException)");
+    if (!topn_emit(cand, how_many, o_q.items, o_q.scores, o_q.n)) {
+      if (!rq.bad_q) return fail(h, MALS_INVALID_ARG, TOPN_BAD_VALUE);
+      rq.bad_q[ps.q0 + q] = 1;   // this query's caller fails; the rest of the pass is answered
+    }
   }
   return MALS_OK;
 }
@@ -310,7 +323,8 @@ constexpr int TOPN_WAVE_CAP = 2048;  // hits a wave of the filter kernel can rec
 
 // topn_stream_kernel: QT = query tiles per wave, 4 QT per workgroup.  MODE 0: *n_out = workgroups of the sample (16
 // buckets each); MODE 1: *n_out = waves of the filter (one hit list each).
-template <int S, int QT, int MODE, bool COS>
+// RS: the rescored instantiations (the rescorer's per-item data: behind the query image, topn_prepare_kernel<false, true>)
+template <int S, int QT, int MODE, bool COS, bool RS = false>
 int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
   const int64_t tiles = (n_items + 16 * (int64_t)tile_stride - 1) / (16 * (int64_t)tile_stride);
   const int64_t stages = (tiles + 3) / 4;
@@ -320,10 +334,17 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   int& per_cu_cached = cached[lm];
   if (!per_cu_cached) {
     int nb = 0;
-    const hipError_t e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1, COS>, 256, 0)
-                         : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2, COS>, 256, 0)
-                         : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3, COS>, 256, 0)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0, COS>, 256, 0);
+    hipError_t e;
+    if (RS)
+      e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1, false, true>, 256, 0)
+          : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2, false, true>, 256, 0)
+          : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3, false, true>, 256, 0)
+                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0, false, true>, 256, 0);
+    else
+      e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1, COS>, 256, 0)
+          : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2, COS>, 256, 0)
+          : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3, COS>, 256, 0)
+                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0, COS>, 256, 0);
     per_cu_cached = (e == hipSuccess && nb > 0) ? std::min(nb, 6) : 2;
   }
   int per_cu = per_cu_cached;
@@ -344,7 +365,7 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
     *n_out = (int)grid;
   }
 #define MALS_TOPN_GO(LM)                                                                                                              \
-  hipLaunchKernelGGL((topn_stream_kernel<S, QT, MODE, LM, COS>), dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k,                           \
+  hipLaunchKernelGGL((topn_stream_kernel<S, QT, MODE, LM, COS, RS>), dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k,                       \
                      sl.d_img.get(), nq, tile_stride, sl.d_bmax.get(), sl.d_bidx.get(), sl.d_tau.get(), TOPN_WAVE_CAP, sl.d_wcount.get(),   \
                      sl.d_whits.get(), cap, sl.d_count.get(), sl.d_cand.get(), sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE)
   if (lm == 1) MALS_TOPN_GO(1);
@@ -355,10 +376,10 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
 }
-template <int MODE, bool COS>
+template <int MODE, bool COS, bool RS = false>
 int topn_launch_stream(mals_handle h, TopnSlot& sl, int S, int nt, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
   const int qt = (nt + 3) / 4;
-#define MALS_TOPN_STREAM(SS, QQ) return topn_launch_stream_QT<SS, QQ, MODE, COS>(h, sl, Y, n_items, k, nq, tile_stride, cap, n_out)
+#define MALS_TOPN_STREAM(SS, QQ) return topn_launch_stream_QT<SS, QQ, MODE, COS, RS>(h, sl, Y, n_items, k, nq, tile_stride, cap, n_out)
   switch (S) {
     case 1:
       if (qt <= 1) MALS_TOPN_STREAM(1, 1);
@@ -424,32 +445,41 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
   if (cos) {
     hipLaunchKernelGGL(topn_qnorm_kernel, dim3((unsigned)((ps.n_vecs + 63) / 64)), dim3(64), 0, st, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs, k, sl.d_qn.get());
     hipLaunchKernelGGL(topn_prepare_kernel<true>, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
-                       sl.d_img.get(), sl.d_count.get(), d_overflow, sl.d_qn.get(), sl.d_qflag.get());
+                       sl.d_img.get(), sl.d_count.get(), d_overflow, sl.d_qn.get(), sl.d_qflag.get(), TopnImgTrailer());
+  } else if (rq.rs) {
+    hipLaunchKernelGGL((topn_prepare_kernel<false, true>), dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
+                       sl.d_img.get(), sl.d_count.get(), d_overflow, nullptr, nullptr, TopnImgTrailer{rq.rs->fdata, rq.rs->n_fdata, rq.rs->fdef});
   } else {
     hipLaunchKernelGGL(topn_prepare_kernel<false>, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
-                       sl.d_img.get(), sl.d_count.get(), d_overflow, nullptr, nullptr);
+                       sl.d_img.get(), sl.d_count.get(), d_overflow, nullptr, nullptr, TopnImgTrailer());
   }
   // 1. sample: bucket maxima of the lower bounds of every tile_stride-th tile; 2. threshold (buckets won by known items dropped)
   int n_groups = 0, n_fw = 0;
-  if (int rc = cos ? topn_launch_stream<0, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
-                   : topn_launch_stream<0, false>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups))
+  if (int rc = cos     ? topn_launch_stream<0, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
+               : rq.rs ? topn_launch_stream<0, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
+                       : topn_launch_stream<0, false>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups))
     return rc;
   hipLaunchKernelGGL(topn_threshold_kernel, dim3((unsigned)nq), dim3(1024), 0, st, sl.d_bmax.get(), sl.d_bidx.get(), n_groups, how_many, k_ptr, k_idx, d_rows,
                      d_eptr, d_eidx, n_items, p.tile_stride, h->tag_bits.get(), sl.d_tau.get(), cos ? sl.d_qflag.get() : nullptr);
   // 3. filter, 4. exact scores of the hits (known items dropped), 5. the N best -- written straight into the slot's pinned
   // block (device-visible host memory: no copy kernel, no copy call)
   // (the filter's waves scatter their own hits into the per-query candidate lists: no kernel in between)
-  if (int rc = cos ? topn_launch_stream<1, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
-                   : topn_launch_stream<1, false>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw))
+  if (int rc = cos     ? topn_launch_stream<1, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
+               : rq.rs ? topn_launch_stream<1, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
+                       : topn_launch_stream<1, false>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw))
     return rc;
   if (cos)
     hipLaunchKernelGGL(topn_rescore_kernel<true>, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr,
                        sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow,
-                       sl.d_qn.get(), n_items);
+                       sl.d_qn.get(), n_items, TopnRescore());
+  else if (rq.rs)
+    hipLaunchKernelGGL((topn_rescore_kernel<false, true>), dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow,
+                       sl.d_vptr, sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(),
+                       d_overflow, nullptr, n_items, *rq.rs);
   else
     hipLaunchKernelGGL(topn_rescore_kernel<false>, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr,
                        sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow,
-                       nullptr, n_items);
+                       nullptr, n_items, TopnRescore());
   uint8_t* o = sl.h_stage.get();
   const size_t o_cnt = sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many, o_tau = o_cnt + sizeof(unsigned) * TOPN_FILTER_QUERIES,
                o_ovf = o_tau + sizeof(float) * TOPN_FILTER_QUERIES;
@@ -466,7 +496,7 @@ int topn_slot_alloc(mals_handle h, TopnSlot& sl) {
   if (!sl.d_bidx.get()) {   // (the last of them: all six exist)
     HIPCHK(h, sl.d_tau.alloc(TOPN_FILTER_QUERIES));
     HIPCHK(h, sl.d_count.alloc(TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE + 1));  // padded counters, then the overflow word
-    HIPCHK(h, sl.d_img.alloc((size_t)16 * 5 * 64));
+    HIPCHK(h, sl.d_img.alloc((size_t)TOPN_IMG_ENTRIES + 2));   // (+ the rescored filter's trailer, TopnImgTrailer)
     HIPCHK(h, sl.d_qflag.alloc(TOPN_FILTER_QUERIES));
     HIPCHK(h, sl.d_bmax.alloc(TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
     HIPCHK(h, sl.d_bidx.alloc(TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
@@ -524,14 +554,19 @@ int topn_pass_filter_finish(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
       }
     }
     if (o_q.n) *o_q.n = n;
+    // (rescored mode: a result that is not finite comes back as THE NaN, ranked first -- RecommendIterator.java:105)
+    if (n > 0 && !std::isfinite(o_q.scores[0])) {
+      if (!rq.bad_q) return fail(h, MALS_INVALID_ARG, TOPN_BAD_VALUE);
+      rq.bad_q[ps.q0 + q] = 1;
+    }
   }
   return MALS_OK;
 }
 
-bool topn_dense_only(mals_handle h, int how_many) {
+bool topn_dense_only(mals_handle h, int how_many, const mals_rescorer_s* r = nullptr) {
   const int64_t n_items = h->side[MALS_SIDE_Y].n_total;
   return n_items < 131072 || n_items >= 0xffffffffll || how_many > TOPN_FILTER_MAX_N || n_items / 16 < 64 * (int64_t)how_many ||
-         std::getenv("MALS_TOPN_FULL");
+         std::getenv("MALS_TOPN_FULL") || (r && !rescorer_filter_ok(r));   // (a rescorer outside the filter's range: topn_kernels.h)
 }
 
 // streams, events and pinned result blocks of the slots; every slot stream ordered after the work already on the handle's
@@ -638,7 +673,7 @@ int topn_because_run(mals_handle h, TopnWorkspace* w, const TopnRequest& rq_in) 
                          sl.d_count.get());
       hipLaunchKernelGGL(topn_rescore_kernel<true>, dim3(8, (unsigned)ps.nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, k, sl.d_vecs,
                          sl.d_vrow, sl.d_vptr, sl.d_count.get(), cap, sl.d_cand.get(), nullptr, nullptr, nullptr, nullptr, nullptr, h->tag_bits.get(),
-                         sl.d_pairs.get(), d_overflow, sl.d_qn.get(), n_items);
+                         sl.d_pairs.get(), d_overflow, sl.d_qn.get(), n_items, TopnRescore());
       uint8_t* o = sl.h_stage.get();
       hipLaunchKernelGGL(topn_final_kernel, dim3((unsigned)ps.nq), dim3(256), sizeof(uint64_t) * (size_t)cap, h->stream, sl.d_pairs.get(), sl.d_count.get(), cap,
                          how_many, reinterpret_cast<uint64_t*>(o), reinterpret_cast<unsigned*>(o + o_cnt), sl.d_tau.get(), reinterpret_cast<float*>(o + o_tau),
@@ -687,7 +722,7 @@ int topn_run(mals_handle h, const TopnRequest& rq) {
   if (rq.kind == TOPN_KIND_BECAUSE) return topn_because_run(h, w, rq);
   if (rq.kind == TOPN_KIND_SIMILARITY_TO) return topn_similarity_to_run(h, rq);
   if (rq.kind == TOPN_KIND_CALL) return (*rq.call)();
-  if (topn_dense_only(h, rq.how_many)) {
+  if (topn_dense_only(h, rq.how_many, rq.rescorer)) {
     for (int q0 = 0; q0 < rq.n_queries; q0 += TOPN_MAX_QUERIES) {
       TopnPass ps;
       ps.q0 = q0;
@@ -772,6 +807,8 @@ struct TopnTicket {
   // items[item_ptr[q] .. item_ptr[q+1]) (never NULL here), which are also its exclusions
   const int64_t* items = nullptr;
   const int64_t* item_ptr = nullptr;
+  // ... (by-user and by-vector calls) with the caller's rescorer, NULL: none -- part of the key of a pass
+  const mals_rescorer_s* rescorer = nullptr;
   // ... or a whole request of its own
   const TopnRequest* bulk = nullptr;
   int rc = MALS_OK;
@@ -836,6 +873,10 @@ struct TopnFrontPass {
   TopnRequest rq;
   TopnPass ps;
   TopnFilterPlan plan;
+  // the pass's rescorer as it was when the pass was formed (kept alive until the pass is decoded), and the failed queries
+  std::shared_ptr<const RescorerState> rs_keep;
+  TopnRescore rs_args;
+  std::vector<uint8_t> bad;
 };
 
 struct TopnFront {
@@ -867,12 +908,20 @@ int topn_front_enqueue(mals_handle h, TopnWorkspace* w, int s, TopnFrontPass& fp
 void topn_front_complete(TopnFrontPass& fp, int rc, const std::string& err) {  // mutex held
   TopnTicket* waker = nullptr;
   size_t waiting = 0;
+  size_t q0 = 0;   // a coalesced pass: the tickets' queries back to back; a query that is not finite fails its own ticket only
   for (TopnTicket* t : fp.tickets) {
-    t->rc = rc;
-    if (rc != MALS_OK) t->err = err;
+    int trc = rc;
+    if (rc == MALS_OK && !t->bulk && !fp.bad.empty())
+      for (size_t q = q0; q < q0 + (size_t)t->n && q < fp.bad.size(); ++q)
+        if (fp.bad[q]) trc = MALS_INVALID_ARG;
+    q0 += (size_t)t->n;
+    t->rc = trc;
+    if (trc != MALS_OK) t->err = rc != MALS_OK ? err : std::string(TOPN_BAD_VALUE);
     t->done = true;
     if (!t->is_leader) ++waiting;
   }
+  fp.bad.clear();
+  fp.rs_keep.reset();
   if (waiting >= 16) {
     // groups of 8: the leader wakes the first caller of every group and leaves it the other seven (measured at 128 callers,
     // ~37 per pass: 2.4e5 -> 4.3e5 queries/s, p50 510 -> 260 us; below 16 per pass the leader's own wake-ups cost less than the
@@ -933,7 +982,7 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
   };
   while (!me->done) {
     TopnTicket* head = f->queue.empty() ? nullptr : f->queue.front();
-    if (head && (head->bulk || topn_dense_only(h, head->how_many))) {
+    if (head && (head->bulk || topn_dense_only(h, head->how_many, head->rescorer))) {
       // a request that is passes of its own (or a catalogue the dense path answers): alone on the workspace
       while (f->n_busy > 0) finish_oldest();
       if (me->done && head != me) break;   // (own answer arrived while draining: let the successor run it)
@@ -964,6 +1013,11 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
         one.rq.item_idx_out = head->item_out;
         one.rq.score_out = head->score_out;
         one.rq.n_out = head->n_out;
+        one.rq.rescorer = head->rescorer;
+      }
+      if (one.rq.rescorer) {
+        rescorer_bind(one.rq.rescorer, one.rs_keep, one.rs_args);
+        one.rq.rs = &one.rs_args;
       }
       lk.unlock();
       const int rc = topn_run(h, one.rq);
@@ -989,7 +1043,7 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
       bool any_excl = false;
       while (!f->queue.empty()) {
         TopnTicket* t = f->queue.front();
-        if (t->bulk || t->how_many != how_many || kind_of(t) != kind || (int)fp.outs.size() + t->n > cap) break;
+        if (t->bulk || t->how_many != how_many || kind_of(t) != kind || t->rescorer != head->rescorer || (int)fp.outs.size() + t->n > cap) break;
         f->queue.pop_front();
         fp.tickets.push_back(t);
         for (int q = 0; q < t->n; ++q) {
@@ -1035,6 +1089,13 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
         fp.rq.skip_known_q = fp.skip.data();
       }
       fp.rq.out_q = fp.outs.data();
+      if (head->rescorer) {
+        fp.rq.rescorer = head->rescorer;
+        rescorer_bind(head->rescorer, fp.rs_keep, fp.rs_args);
+        fp.rq.rs = &fp.rs_args;
+      }
+      fp.bad.assign((size_t)fp.rq.n_queries, 0);
+      fp.rq.bad_q = fp.bad.data();
       fp.ps = TopnPass();
       fp.ps.q0 = 0;
       fp.ps.nq = fp.rq.n_queries;

@@ -140,6 +140,82 @@ __device__ __forceinline__ bool topn_cos_score(const float* __restrict__ y, cons
   *out = (float)(total / (double)(v1 - v0));
   return true;
 }
+// RESCORED MODE (template flag RS: mals_recommend_rescored & co., the IDRescorer of RecommendIterator.java:84-101 in the
+// one shape a device can run): isFiltered(i) = bit i of a filter set, rescore(i, s) = fl(fl(scale_i * s) + offset_i) in
+// fp64 (Java evaluates `a * s + b` without contraction).  The exact score of an unfiltered item for a query of n vectors:
+//     r = fl(fl(scale_i * sum) + offset_i),  sum = the fp64 sum of the n dots (topn_ref_sum);  r not finite: SKIPPED;
+//     result = (float)(r / n);  result not finite: the query FAILS (checkState, RecommendIterator.java:105)
+// Per item the kernels read, besides the fp64 scale / offset arrays and the filter bits of the exact path, 16 bytes
+// prepared when the rescorer is set (mals_rescorer_set_*): {bf16 rs_hi, rs_lo, os_hi, os_lo, fp32 scale, 0} with rs = 1 /
+// scale_i and os = offset_i / scale_i (fp64, split into two bf16 rounded to nearest); a filtered item is {0, 0, -2^120, 0,
+// NaN, 0}.  Rows past the arrays read `def` (the uniform scale / offset, unfiltered).
+// Bound of the filter (scale_i in [2^-20, 2^20], |offset_i| <= 2^64: other rescorers are answered by the dense path).
+// With m = sum / n the exact mean and T = scale (m + os / n) the exact rescored mean:
+//   (a) the reference's roundings: two fp64 roundings of the affine step, the fp64 division by n and the cast to fp32:
+//       |result - T| <= (3 * 2^-53 + 2^-24) scale (|m| + |os| / n) < 2^-23.9 scale (|m| + |os| / n);
+//   (b) approx - m: the bound of the unrescored filter (2.01 * 2^-8 |x| |y_i|), unchanged;
+//   (c) the folded terms: rs and os, -tau and 1/n each enter as a bf16 pair (hi + lo): every product of the pairs is exact
+//       and each pair differs from its value by <= 2^-17.8 of it: |rs' (-tau)' - rs (-tau)| <= 2^-15.9 rs |tau| and
+//       |os' n'^-1 - os / n| <= 2^-15.9 |os| / n;
+//   (d) the fp32 accumulation of the margin step (<= 33 terms): <= 2^-18.9 (|approx| + margin + |os| / n + rs |tau|);
+// so the filter adds the COVER terms 2^-14 (1.01 rs_hi |tau| + 1.01 |os_hi| / n) >= the rs |tau| and |os| / n parts of (a),
+// (c) and (d), and the |x| |y_i| parts stay inside the slack of TOPN_MARGIN (2.25 - 2.01 > 2^-10.2 * 2^8).  An item
+// whose exact result reaches tau then has  approx + margin_i + os / n - tau / scale + covers >= 0:  the hit test runs in
+// the DIVIDED domain (acc / scale_i), where the margin of the unrescored filter holds as it is -- in the rescored domain
+// it is margin_i * scale_i, which a margin that ignores scale_i under-estimates by that factor (tests/
+// test_rescorer_margin.py builds a catalogue where it drops a winner).  The sample keeps (approx - margin_i + os/n -
+// cover_o) * scale_f32: a lower bound of the rescored result by the same bound plus the fp32 product (2^-23 of it), so tau
+// is a lower bound of the N-th best RESCORED score; a filtered item's NaN scale never wins a bucket, and its -2^120 / n
+// offset term (|os| / n <= 2^84 for the rest) is never a hit.
+constexpr float TOPN_RS_COVER = 6.103515625e-05f;  // 2^-14 (bound above)
+constexpr double TOPN_RS_MAX_SCALE = 1048576.0;     // 2^20: the filter's range of scale_i (and 2^-20 below) ...
+constexpr double TOPN_RS_MAX_OFFSET = 18446744073709551616.0;  // ... and of |offset_i| (2^64)
+struct TopnRescore {
+  const uint32_t* filt = nullptr;  // filter bits of items [0, filt_items)
+  int64_t filt_items = 0;
+  const double* scale = nullptr;   // per-item weights of rows [0, n_rows) (NULL: us / uo)
+  const double* offset = nullptr;
+  int64_t n_rows = 0;
+  double us = 1.0, uo = 0.0;       // every other row
+  const uint4* fdata = nullptr;    // the filter's 16 bytes of items [0, n_fdata), `def` for the others
+  int64_t n_fdata = 0;
+  uint4 fdef = {0u, 0u, 0u, 0u};
+};
+// where the rescored filter finds the items' 16 bytes: behind the pass's query image (TOPN_IMG_ENTRIES operands, the most
+// an instantiation reads), written by topn_prepare_kernel<false, true>
+constexpr int TOPN_IMG_ENTRIES = 16 * 5 * 64;
+struct TopnImgTrailer {
+  const uint4* fdata;
+  int64_t n_fdata;
+  uint4 fdef;
+};
+__device__ __forceinline__ bool topn_rs_filtered(const TopnRescore& rs, int64_t item) {
+  return item < rs.filt_items && ((rs.filt[item >> 5] >> (item & 31)) & 1u) != 0u;
+}
+// RecommendIterator.java:93-101: the fp64 sum of the dots (unchanged), then the rescore on the SUM, before the division
+__device__ __forceinline__ double topn_ref_sum(const float* __restrict__ y, const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
+                                               int v0, int v1, int k) {
+  double sum = 0.0;
+  for (int v = v0; v < v1; ++v) sum += topn_ref_dot(y, vecs + (vrow ? vrow[v] : (int64_t)v) * k, k);
+  return sum;
+}
+__device__ __forceinline__ double topn_rs_affine(double s, double sum, double o) {
+#pragma clang fp contract(off)
+  const double p = s * sum;  // two roundings, as Java: never a v_fma_f64
+  return p + o;
+}
+// false: the item is skipped (r not finite); else *out = (float)(r / n), THE NaN if that is not finite (the query fails)
+__device__ __forceinline__ bool topn_rs_score(const float* __restrict__ y, const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
+                                              int v0, int v1, int k, const TopnRescore& rs, int64_t item, float* out) {
+  const double sum = topn_ref_sum(y, vecs, vrow, v0, v1, k);
+  const bool arr = item < rs.n_rows;
+  const double s = arr && rs.scale ? rs.scale[item] : rs.us, o = arr && rs.offset ? rs.offset[item] : rs.uo;
+  const double r = topn_rs_affine(s, sum, o);
+  if (!(fabs(r) < __builtin_huge_val())) return false;
+  const float res = (float)(r / (double)(v1 - v0));
+  *out = fabsf(res) < __builtin_huge_valf() ? res : __builtin_nanf("");
+  return true;
+}
 // the exact norms of the pass's query vectors, one thread per vector
 __global__ void topn_qnorm_kernel(const float* __restrict__ vecs, const int64_t* __restrict__ vrow, int n_vecs, int k, double* __restrict__ qn) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,17 +275,22 @@ __device__ __forceinline__ __bf16 bf16_up(float v) {
 // v), builds the tile's image, and clears the pass's counters.
 // COS: x = the mean of the query's unit vectors (qn: their exact norms), |x| <= 1; qflag[q] = 1: a vector of zero or NaN
 // norm (the query is answered empty), 2: a vector whose norm overflows (the dense path answers), else 0.
-template <bool COS>
+// RS (rescored mode): lanes (1, c) also carry {0, 0, 0, 0 (-tau hi, hi, lo, lo: the filter fills them), 1/n hi, hi, lo, lo}
+// and lanes (2, c) {0 (the tau cover: the filter), 2^-14 * 1.01 / n rounded up}, n = the query's vector count.
+template <bool COS, bool RS = false>
 __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
                                                            const int32_t* __restrict__ vptr, int n_queries, int k, int S,
                                                            bf16x8* __restrict__ img, unsigned* __restrict__ count,
                                                            unsigned* __restrict__ overflow, const double* __restrict__ qn,
-                                                           uint32_t* __restrict__ qflag) {
+                                                           uint32_t* __restrict__ qflag, TopnImgTrailer trailer) {
   __shared__ float xb[16][129];
   __shared__ float nrm[16];
   const int t = blockIdx.x, qi = threadIdx.x >> 4, sub = threadIdx.x & 15;  // 16 threads per query
   const int q = 16 * t + qi;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *overflow = 0u;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *overflow = 0u;
+    if (RS) *reinterpret_cast<TopnImgTrailer*>(img + TOPN_IMG_ENTRIES) = trailer;
+  }
   if (sub == 0 && q < n_queries) count[(size_t)q * TOPN_COUNT_STRIDE] = 0u;
   int v0 = 0, v1 = 0;
   if (q < n_queries) {
@@ -272,6 +353,19 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
         m[2] = (__bf16)(-1e30f);  // a padding query never has a candidate
       }
     }
+    if (RS && (g == 1 || g == 2) && 16 * t + c < n_queries) {
+      const int nv = vptr[16 * t + c + 1] - vptr[16 * t + c];
+      const float ninv = (float)(1.0 / (double)nv);
+      if (g == 1) {
+        const __bf16 hi = (__bf16)ninv, lo = (__bf16)(ninv - (float)hi);
+        m[4] = hi;
+        m[5] = hi;
+        m[6] = lo;
+        m[7] = lo;
+      } else {
+        m[1] = bf16_up(TOPN_RS_COVER * 1.01f * ninv);
+      }
+    }
     img[(t * (S + 1) + S) * 64 + lane] = m;
   }
 }
@@ -303,7 +397,11 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
 // COS (cosine mode, header): the margin step's A operand is {|y_i| up, +-1, |y_i| hi, lo, hi, lo, 0, 0} against the query's
 // {M_c, floor, -tau hi, hi, lo, lo}; the sample keeps lower bounds divided by the item's |y_i| (the stage's norms pass
 // through LDS, 256 B); items of zero / non-finite norm never win a bucket and are never hits.
-template <int S, int QT, int MODE, int LM, bool COS = false>
+// RS (rescored mode, above): the margin step's A operand gains lanes (1, c) = {rs hi, lo, hi, lo, os hi, lo, hi, lo} against
+// the query's {-tau hi, hi, lo, lo, 1/n hi, hi, lo, lo}, and lanes (2, c) = {rs hi, +-|os hi|} against the covers {2^-14
+// 1.01 |tau|, 2^-14 1.01 / n}: the item's 16 bytes ride with its row (prefetched a stage ahead), nothing is added per
+// (item, query) pair of the filter; the sample multiplies its accumulators by the items' fp32 scales (through LDS, 256 B).
+template <int S, int QT, int MODE, int LM, bool COS = false, bool RS = false>
 __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __restrict__ Y, int64_t n_items, int k,
                                                           const bf16x8* __restrict__ img, int n_queries, int tile_stride,
                                                           float* __restrict__ bmax, uint32_t* __restrict__ bidx,
@@ -314,6 +412,7 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
   constexpr int E = S + 1;   // A operands per item tile: S contraction steps + the margin step
   __shared__ __attribute__((aligned(16))) bf16x8 sa2[2][4 * E * 64];  // two stages x [item tile of the stage][operand][lane]
   __shared__ float sny[COS ? 2 : 1][4][16];                            // COS: |y| of the stage's items, per buffer
+  __shared__ float ssc[RS ? 2 : 1][4][16];                             // RS: the fp32 scales of the stage's items, per buffer
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   // this wave's query tiles, once
   bf16x8 bq[QT][S], bm[QT];
@@ -323,7 +422,25 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
 #pragma unroll
     for (int s = 0; s < S; ++s) bq[j][s] = img[(t * (S + 1) + s) * 64 + lane];
     bf16x8 m = img[(t * (S + 1) + S) * 64 + lane];
-    if (MODE == 1 && g == 0) {  // -tau_q = hi + lo (lo rounded up) into slots 2, 3 of the margin entry
+    if (MODE == 1 && RS && (g == 1 || g == 2)) {  // -tau_q = hi + lo (lo rounded up) against rs; its cover
+      const int q = 16 * t + c;
+      if (q < n_queries) {
+        const float tq = tau[q];
+        float v = -tq;
+        if (!(tq > -__builtin_huge_valf())) v = 1e30f;  // no threshold: everything is a candidate (the pass falls back)
+        const __bf16 hi = (__bf16)v;
+        if (g == 1) {
+          const __bf16 lo = bf16_up(v - (float)hi);
+          m[0] = hi;
+          m[1] = hi;
+          m[2] = lo;
+          m[3] = lo;
+        } else {
+          m[0] = bf16_up(TOPN_RS_COVER * 1.01f * __builtin_fabsf(v));
+        }
+      }
+    }
+    if (MODE == 1 && g == 0 && !RS) {  // -tau_q = hi + lo (lo rounded up) into slots 2, 3 of the margin entry
       const int q = 16 * t + c;
       if (q < n_queries) {
         const float tq = tau[q];
@@ -397,14 +514,37 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
         besti[j][r] = 0xffffffffu;
       }
   }
+  // RS: the item's 16 bytes (lane (g, c): item c of the wave's tile), loaded beside its row; where they are is in the
+  // trailer of the query image (topn_prepare_kernel<false, true>: the kernel's arguments stay those of the other modes)
+  const uint4* fdata = nullptr;
+  int64_t n_fdata = 0;
+  uint4 fdef = {0u, 0u, 0u, 0u};
+  if (RS) {
+    const TopnImgTrailer* tr = reinterpret_cast<const TopnImgTrailer*>(img + TOPN_IMG_ENTRIES);
+    fdata = tr->fdata;
+    n_fdata = tr->n_fdata;
+    fdef = tr->fdef;
+  }
+  auto load_f16 = [&](int64_t i0, uint4& f) {
+    const int64_t item = i0 + c;
+    f = item < n_fdata ? fdata[item] : fdef;
+  };
   float ynext[CH];
-  if ((int64_t)blockIdx.x < n_stages) load_rows16((4 * (int64_t)blockIdx.x + w) * step, ynext);
+  uint4 fnext = fdef;
+  if ((int64_t)blockIdx.x < n_stages) {
+    load_rows16((4 * (int64_t)blockIdx.x + w) * step, ynext);
+    if (RS) load_f16((4 * (int64_t)blockIdx.x + w) * step, fnext);
+  }
   int buf = 0;
   for (int64_t st = blockIdx.x; st < n_stages; st += gridDim.x) {
     float yv[CH];
 #pragma unroll
     for (int s = 0; s < CH; ++s) yv[s] = ynext[s];
-    if (st + gridDim.x < n_stages) load_rows16((4 * (st + gridDim.x) + w) * step, ynext);  // the next stage's rows fly during this one
+    const uint4 fv = fnext;
+    if (st + gridDim.x < n_stages) {
+      load_rows16((4 * (st + gridDim.x) + w) * step, ynext);  // the next stage's rows fly during this one
+      if (RS) load_f16((4 * (st + gridDim.x) + w) * step, fnext);
+    }
     // this wave's tile of the stage as A operands
     bf16x8 ah[S], am;
     {
@@ -438,6 +578,26 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
         am[1] = (__bf16)(MODE == 0 ? -1.f : 1.f);
         am[2] = (__bf16)1.f;
         am[3] = (__bf16)1.f;
+      }
+      if (RS) {
+        const __bf16 rh = __builtin_bit_cast(__bf16, (uint16_t)(fv.x & 0xffffu)), rl = __builtin_bit_cast(__bf16, (uint16_t)(fv.x >> 16));
+        const __bf16 oh = __builtin_bit_cast(__bf16, (uint16_t)(fv.y & 0xffffu)), ol = __builtin_bit_cast(__bf16, (uint16_t)(fv.y >> 16));
+        if (g == 1) {
+          am[0] = rh;
+          am[1] = rl;
+          am[2] = rh;
+          am[3] = rl;
+          am[4] = oh;
+          am[5] = ol;
+          am[6] = oh;
+          am[7] = ol;
+        } else if (g == 2) {
+          am[0] = rh;  // (MODE 0: against 0)
+          const uint16_t a = (uint16_t)((fv.y & 0x7fffu) | (MODE == 0 ? 0x8000u : 0u));  // the sample subtracts the cover
+          am[1] = __builtin_bit_cast(__bf16, a);
+        } else if (g == 0 && MODE == 0) {
+          ssc[buf][w][c] = __uint_as_float(fv.z);
+        }
       }
 #pragma unroll
       for (int s = 0; s < S; ++s)
@@ -480,6 +640,21 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
 #pragma unroll
           for (int j = 0; j < QT; ++j) {
             const float lb = acc[j][r] * rn;
+            if (in && lb > best[j][r]) {  // a NaN never wins
+              best[j][r] = lb;
+              besti[j][r] = (uint32_t)it;
+            }
+          }
+        }
+      } else if (MODE == 0 && RS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t it = i0 + 4 * g + r;
+          const bool in = it < n_items;
+          const float sc = ssc[cb][jt][4 * g + r];  // NaN: a filtered item
+#pragma unroll
+          for (int j = 0; j < QT; ++j) {
+            const float lb = acc[j][r] * sc;
             if (in && lb > best[j][r]) {  // a NaN never wins
               best[j][r] = lb;
               besti[j][r] = (uint32_t)it;
@@ -572,7 +747,6 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
     }
   }
 }
-
 // known items of the query's user are never recommended (RecommendIterator.java:75-82)
 __global__ void topn_mask_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                  const int64_t* __restrict__ query_row, int n_queries, int tile_stride, int64_t n_out,
@@ -735,14 +909,17 @@ __global__ __launch_bounds__(1024) void topn_threshold_kernel(float* __restrict_
 // 240 queries.)  The query's known and excluded items pass through LDS a thousand at a time.
 // COS: the cosine score (topn_cos_score) with the query norms qn; a candidate with a non-finite similarity is struck (never
 // the overflow word), as is an index outside [0, n_items) (a known-item list entry of recommendedBecause)
-template <bool COS>
+// RS: filtered candidates are struck, the score is topn_rs_score's (a skipped item struck; a result that is not finite
+// becomes THE NaN, which topn_final_kernel ranks first and the host reports as the query's failure -- not the pass's)
+template <bool COS, bool RS = false>
 __global__ __launch_bounds__(64) void topn_rescore_kernel(const float* __restrict__ Y, int k, const float* __restrict__ vecs,
                                                           const int64_t* __restrict__ vrow, const int32_t* __restrict__ vptr, const unsigned* __restrict__ count, int cap,
                                                           const uint32_t* __restrict__ cand, const int64_t* __restrict__ row_ptr,
                                                           const int32_t* __restrict__ col, const int64_t* __restrict__ query_row,
                                                           const int64_t* __restrict__ excl_ptr, const int64_t* __restrict__ excl_idx,
                                                           const uint32_t* __restrict__ tag_bits, uint64_t* __restrict__ pairs,
-                                                          unsigned* __restrict__ overflow, const double* __restrict__ qn, int64_t n_items) {
+                                                          unsigned* __restrict__ overflow, const double* __restrict__ qn, int64_t n_items,
+                                                          TopnRescore rsc) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   float* ys = reinterpret_cast<float*>(smem);  // [64][k + 1]
   __shared__ uint32_t sk[1024];
@@ -832,6 +1009,10 @@ __global__ __launch_bounds__(64) void topn_rescore_kernel(const float* __restric
         float sc;
         if (!struck && topn_cos_score(ys + lane * pitch, vecs, vrow, qn, v0, v1, k, &sc))
           out = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xffffffffu - it);
+      } else if (RS) {
+        float sc;
+        if (!struck && !topn_rs_filtered(rsc, (int64_t)it) && topn_rs_score(ys + lane * pitch, vecs, vrow, v0, v1, k, rsc, (int64_t)it, &sc))
+          out = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xffffffffu - it);
       } else if (!struck) {
         const float sc = topn_ref_score(ys + lane * pitch, vecs, vrow, v0, v1, k);
         if (!(fabsf(sc) < __builtin_huge_valf())) atomicAdd(overflow, 1u);   // NaN / infinite: the dense path decides and reports
@@ -908,12 +1089,13 @@ __global__ __launch_bounds__(256) void topn_final_kernel(const uint64_t* __restr
 // ---- the dense path: exact scores of every item -----------------------------------------------------------------------
 // scores[q][i] for a 64-item tile per workgroup: the tile's rows are staged in LDS (coalesced), wave w takes the queries
 // w, w + 4, ...: lane = item, the query's vectors are read with wave-uniform addresses.  COS: the cosine score (qn: the query
-// norms); a skipped item (non-finite similarity) scores -inf.
-template <bool COS>
+// norms); a skipped item (non-finite similarity) scores -inf.  RS: topn_rs_score, a filtered or skipped item -inf, a result
+// that is not finite THE NaN (first in its query's selection: the query fails)
+template <bool COS, bool RS = false>
 __global__ __launch_bounds__(256) void topn_exact_dense_kernel(const float* __restrict__ Y, int64_t n_items, int k,
                                                                const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
                                                                const int32_t* __restrict__ vptr, int n_queries, float* __restrict__ scores,
-                                                               const double* __restrict__ qn) {
+                                                               const double* __restrict__ qn, TopnRescore rsc) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   float* ys = reinterpret_cast<float*>(smem);  // [64][k + 1]
   const int pitch = k + 1;
@@ -930,6 +1112,12 @@ __global__ __launch_bounds__(256) void topn_exact_dense_kernel(const float* __re
         if (COS) {
           float sc;
           if (!topn_cos_score(y, vecs, vrow, qn, v0, v1, k, &sc)) sc = -__builtin_huge_valf();
+          scores[(int64_t)q * n_items + i0 + lane] = sc;
+          continue;
+        }
+        if (RS) {
+          float sc = -__builtin_huge_valf();
+          if (!topn_rs_filtered(rsc, i0 + lane) && !topn_rs_score(y, vecs, vrow, v0, v1, k, rsc, i0 + lane, &sc)) sc = -__builtin_huge_valf();
           scores[(int64_t)q * n_items + i0 + lane] = sc;
           continue;
         }

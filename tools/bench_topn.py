@@ -5,7 +5,9 @@ RecommendIterator + TopN, 1 core) on a few queries.
 usage: python tools/bench_topn.py [--items N] [--users U] [--features K] [--how-many N]
        python tools/bench_topn.py --similar [--lib-root DIR]: mostSimilarItems (mals_most_similar_items, one item per
        query) next to recommend in the same run, per batch size; --lib-root imports the package (and its library) from
-       another checkout, whose recommend leg alone then runs (an A/B of recommend against an older build)"""
+       another checkout, whose recommend leg alone then runs (an A/B of recommend against an older build)
+       python tools/bench_topn.py --rescorer [--how-many 64]: recommend with a rescorer (a 10 %% filter set plus per-item
+       scale and offset, mals_recommend_rescored) next to the unrescored leg in the same run, 240-query batches"""
 import argparse
 import json
 import os
@@ -26,9 +28,12 @@ def main():
     ap.add_argument("--similar", action="store_true")
     ap.add_argument("--lib-root", default=None)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--rescorer", action="store_true")
     a = ap.parse_args()
     if a.similar:
         return similar(a)
+    if a.rescorer:
+        return rescored(a)
     import numpy as np
     import myrrix_recommender_amd as pkg
     rng = np.random.default_rng(1234567890)
@@ -187,6 +192,52 @@ def similar(a):
         if "similar" in out:
             out["similar_over_recommend"] = {b: out["similar"][b]["queries_per_s"] / out["recommend"][b]["queries_per_s"] for b in out["similar"]}
     out["value"] = out["similar"]["4096"]["queries_per_s"] if "similar" in out else out["recommend"]["4096"]["queries_per_s"]
+    print(json.dumps(out))
+
+
+def rescored(a):
+    """recommend with and without a rescorer (10 % of the items filtered, per-item scale in [0.5, 2], offset ~ 0.1 N(0, 1)),
+    the same users in the same run: queries/s per batch and their ratio; the filter reads 16 bytes per item more than the
+    4k bytes of its row (csrc/topn_kernels.h, RESCORED MODE)"""
+    import numpy as np
+    import myrrix_recommender_amd as pkg
+    rng = np.random.default_rng(1234567890)
+    k = a.features
+    Y = (rng.standard_normal((a.items, k)) / np.sqrt(k)).astype(np.float32)
+    X = (rng.standard_normal((a.users, k)) / np.sqrt(k)).astype(np.float32)
+    deg = 100
+    rp = np.arange(a.users + 1, dtype=np.int64) * deg
+    col = rng.integers(0, a.items, a.users * deg).astype(np.int32)
+    per_pass = 16 * {1: 16, 2: 15, 3: 10, 4: 7}[(k + 31) // 32]
+    out = {"metric": "recommend queries/s with and without a rescorer, same run", "unit": "queries/s", "items": a.items, "features": k,
+           "how_many": a.how_many, "queries_per_pass": per_pass, "filter_bytes_per_item": {"plain": 4 * k, "rescored": 4 * k + 16},
+           "plain": {}, "rescored": {}}
+    with pkg.ALSCore(k) as core:
+        core.set_factor_rows(pkg.SIDE_X, a.users)
+        core.set_factor_rows(pkg.SIDE_Y, a.items)
+        core.set_factors(pkg.SIDE_X, X)
+        core.set_factors(pkg.SIDE_Y, Y)
+        core.set_matrix(pkg.SIDE_X, rp, col, np.ones(len(col), np.float32))
+        r = core.rescorer()
+        r.set_filter(rng.choice(a.items, a.items // 10, replace=False))
+        r.set_weights(rng.uniform(0.5, 2.0, a.items), rng.standard_normal(a.items) * 0.1)
+        legs = {"plain": None, "rescored": r}
+        for batch in (per_pass, 4 * per_pass, 4096):
+            users = rng.integers(0, a.users, batch).astype(np.int64)
+            for name, rs in legs.items():
+                core.recommend(users, a.how_many, rescorer=rs)          # warm
+                reps = max(10, 4096 // batch)
+                runs = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    for _ in range(reps):
+                        core.recommend(users, a.how_many, rescorer=rs)
+                    runs.append((time.perf_counter() - t0) / reps)
+                dt = min(runs)
+                out[name][str(batch)] = {"ms_per_call": dt * 1e3, "ms_per_call_runs": [x * 1e3 for x in runs], "queries_per_s": batch / dt}
+        out["rescored_over_plain"] = {b: out["rescored"][b]["queries_per_s"] / out["plain"][b]["queries_per_s"] for b in out["plain"]}
+        r.close()
+    out["value"] = out["rescored"]["4096"]["queries_per_s"]
     print(json.dumps(out))
 
 
