@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- ALS rows solved / second over one full iteration (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|small] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|small] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, the warm-up steps, the timed steps, --dump-outputs, the result
+line (headline, configuration, and the roofline / per-kernel figures that the HIP events of the timed steps themselves give).
+--full adds everything that takes runs of its own: the same steps again without the per-half status check, the per-half
+kernel pass, the exchange alone (N > 1), the reconstruction error, the un-planted / fp32 / three-term-split legs and the CPU
+baselines (--no-unplanted, --no-fp32-leg and --no-cpu-baseline switch single legs of --full off).
 
 A "step" is one full ALS iteration (X-from-Y half + Y-from-X half, Gramians and -- for N>1 -- the
 all-gathers and k x k all-reduces included) on the synthetic C4 problem of BASELINE.md
@@ -308,7 +314,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything that takes runs of its own: the steps again without the per-half "
+                         "status check, the per-half kernel pass, the exchange alone (N>1), the reconstruction error, the un-planted, "
+                         "fp32 and three-term-split legs and the CPU baselines.  Off by default: a plain run sets up, warms up, times "
+                         "the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines (cpu_baseline, cpu_baseline_reference_jvm)")
     ap.add_argument("--segment-nnz", type=int, default=0)
     ap.add_argument("--gramian-mode", default="auto", choices=["auto", "fp32", "split_f16", "split3_f16"],
                     help="mals_config.gramian_mode (A/B only; the headline number uses the library default)")
@@ -321,10 +332,10 @@ def main():
                     help="fraction of the interactions planted on the 2048 core items (synth.torch_problem); 0 = the plain SURVEY 8(d) workload "
                          "(power-law item popularity, log-normal user activity, values 1..5, nothing planted)")
     ap.add_argument("--no-unplanted", action="store_true",
-                    help="N=1: skip the second, untimed-by-the-headline leg on the un-planted workload (roofline_unplanted)")
+                    help="--full, N=1: skip the second, untimed-by-the-headline leg on the un-planted workload (roofline_unplanted)")
     ap.add_argument("--one-compute-stream", action="store_true",
                     help="group path: solve every chunk on ONE compute stream (A/B against the default, two alternating streams)")
-    ap.add_argument("--no-fp32-leg", action="store_true", help="N=1: skip the leg that re-runs the workload with --gramian-mode fp32 (roofline_fp32)")
+    ap.add_argument("--no-fp32-leg", action="store_true", help="--full, N=1: skip the leg that re-runs the workload with --gramian-mode fp32 (roofline_fp32)")
     ap.add_argument("--exchange-chunks", type=int, default=4,
                     help="N>1: solve each slice in this many row chunks and all-gather a finished chunk while the next is solved")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -486,20 +497,22 @@ def main():
         first = {pkg.SIDE_X: prob["u_off"], pkg.SIDE_Y: prob["i_off"]} if rank_shape else {pkg.SIDE_X: 0, pkg.SIDE_Y: 0}
         dump_outputs(torch, args.dump_outputs, {"X": (als.factors(pkg.SIDE_X), first[pkg.SIDE_X], n_users),
                                                 "Y": (als.factors(pkg.SIDE_Y), first[pkg.SIDE_Y], n_items)}, k)
-    # the same K steps again without the per-half check (a diagnostic: what the check costs)
-    core.reset_stats()       # (st above keeps the timed region's tallies)
-    barrier()
-    t0 = time.perf_counter()
-    als.iterate(args.steps, check=False)
-    barrier()
-    elapsed_chk = time.perf_counter() - t0
-    core.check()
-    add_tally(core.stats())
+    # --full: the same K steps again without the per-half check (a diagnostic: what the check costs)
+    elapsed_chk = None
+    if args.full:
+        core.reset_stats()       # (st above keeps the timed region's tallies)
+        barrier()
+        t0 = time.perf_counter()
+        als.iterate(args.steps, check=False)
+        barrier()
+        elapsed_chk = time.perf_counter() - t0
+        core.check()
+        add_tally(core.stats())
     core.enable_timing(False)
     gscale = core.gather_scale()
-    # untimed diagnostic pass: per-half kernel times (not part of the measured region)
+    # --full: untimed diagnostic pass: per-half kernel times (not part of the measured region)
     halves = {}
-    if os.environ.get("MALS_BENCH_SPLIT", "1") == "1":
+    if args.full and os.environ.get("MALS_BENCH_SPLIT", "1") == "1":
         core.enable_timing(True)
         for side, name in ((pkg.SIDE_X, "x_half"), (pkg.SIDE_Y, "y_half")):
             core.reset_stats()
@@ -516,7 +529,7 @@ def main():
     # untimed: the exchange on its own ("report all-gather time separately") -- the
     # un-pipelined in-place all-gather of each side's freshly solved slices into every replica
     exchange = None
-    if world > 1 or force:
+    if args.full and (world > 1 or force):
         exchange = {}
         for side, name in ((pkg.SIDE_X, "x_ms"), (pkg.SIDE_Y, "y_ms")):
             als._all_gather(side)
@@ -528,15 +541,17 @@ def main():
             exchange[name] = (time.perf_counter() - te) / 3 * 1e3
         exchange["bytes_received_per_rank"] = {"x": (world - 1) * als.per[pkg.SIDE_X] * k * 4, "y": (world - 1) * als.per[pkg.SIDE_Y] * k * 4}
     # untimed quality figure: ReconstructionEvaluator's mean over the observed entries (8(f) row 3)
-    rec_sum, rec_cnt = core.reconstruction_error()
+    rec_sum, rec_cnt = core.reconstruction_error() if args.full else (0.0, 0)
     own_elapsed = elapsed
     if world > 1:
-        t = torch.tensor([elapsed, elapsed_chk], dtype=torch.float64, device=red_device)
+        t = torch.tensor([elapsed, elapsed_chk or 0.0], dtype=torch.float64, device=red_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, elapsed_chk = float(t[0].item()), float(t[1].item())
-        q = torch.tensor([rec_sum, float(rec_cnt)], dtype=torch.float64, device=red_device)
-        dist.all_reduce(q)
-        rec_sum, rec_cnt = float(q[0].item()), int(q[1].item())
+        elapsed = float(t[0].item())
+        if args.full:
+            elapsed_chk = float(t[1].item())
+            q = torch.tensor([rec_sum, float(rec_cnt)], dtype=torch.float64, device=red_device)
+            dist.all_reduce(q)
+            rec_sum, rec_cnt = float(q[0].item()), int(q[1].item())
 
     # N > 1: what every rank saw, so that the line proves itself -- size and rank READ BACK from the RCCL communicator,
     # the HIP device and its PCI bus id, the rows / entries of the rank's two slices, the rank's own clock
@@ -558,7 +573,7 @@ def main():
             gathered = [mine]
         ranks_info = gathered
     planted_err = None
-    if world == 1:
+    if args.full and world == 1:
         planted_err = synth.planted_reconstruction_error(prob, als.factors(pkg.SIDE_X), als.factors(pkg.SIDE_Y))
     out = None
     if rank == 0:
@@ -606,10 +621,11 @@ def main():
             "unit": "rows/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step,
-            # (value / ms_per_step include mals_check after every half-iteration; the same K steps again without it:)
-            "ms_per_step_without_check": 1e3 * elapsed_chk / args.steps,
-            "value_without_check": (n_users + n_items) / (elapsed_chk / args.steps),
+            # (value / ms_per_step include mals_check after every half-iteration; --full: the same K steps again without it)
+            "ms_per_step_without_check": 1e3 * elapsed_chk / args.steps if args.full else None,
+            "value_without_check": (n_users + n_items) / (elapsed_chk / args.steps) if args.full else None,
             "higher_is_better": True,
+            "full": args.full,       # False: a plain run -- the keys of what only --full runs are left out of the line
             "scaling": "strong",
             "vs_baseline": None,
             # the arithmetic type of the path: factors are fp32 like the reference's; above 16 features the per-row Gramian
@@ -669,11 +685,14 @@ def main():
                                              "planted low-rank part (synth.torch_problem), the only part a factor model can predict",
                                      "planted_part": planted_err},
         }
+        if not args.full:            # what only --full runs is not in the line of a plain run
+            for key in ("ms_per_step_without_check", "value_without_check", "half_iteration_kernel_ms", "all_gather_alone_ms", "reconstruction_error"):
+                del out[key]
         if one_device or transport:
             out["INVALID_AS_A_MEASUREMENT"] = ("test run: MALS_BENCH_ONE_DEVICE=%s (all ranks on device 0), MALS_BENCH_TRANSPORT=%s"
                                                % (os.environ.get("MALS_BENCH_ONE_DEVICE", "0"), transport or ""))
         big = args.workload == "c5"    # no second problem / second arithmetic next to 200 GB of resident data
-        if world == 1 and not rank_shape and not force and args.planted > 0 and prob.get("planted") and not args.no_unplanted:
+        if args.full and world == 1 and not rank_shape and not force and args.planted > 0 and prob.get("planted") and not args.no_unplanted:
             out["roofline_unplanted"] = unplanted_leg(torch, pkg, sharded, synth, n_users, n_items, nnz_req, k, args, gmode, smode, local_rank, device)
             out["roofline_unplanted"]["slower_than_planted_by"] = out["roofline_unplanted"]["ms_per_step"] / ms_per_step - 1.0
             if dom == "rows":
@@ -682,12 +701,12 @@ def main():
                 tally["rows"][1] += ums
             out["roofline_unplanted"].pop("_all_rows_launches", None)
         # what a rocprofv3 --kernel-trace --stats run of THIS command averages for the dominant kernel: every launch of the
-        # process (warm-up, timed, the untimed per-half pass, and the un-planted leg -- same kernel, same grid)
+        # process (warm-up, timed and, with --full, the run without the check, the per-half pass and the un-planted leg -- same kernel, same grid)
         out["roofline"]["all_launches_in_process"] = {"launches": tally[dom][0], "avg_ms": tally[dom][1] / max(tally[dom][0], 1),
                                                       "note": "compare with profiles/*_kernel_stats.txt; avg_launch_ms above is the timed region of the headline workload only"}
         # the arithmetic closest to what "dtype": "f32" promises: the same workload with fp32 products in the per-row Gramian
         # (v_mfma_f32_16x16x4_f32), so that the cost of the split-f16 choice is in the record
-        if world == 1 and not rank_shape and not force and split and args.gramian_mode == "auto" and not args.no_fp32_leg and not big:
+        if args.full and world == 1 and not rank_shape and not force and split and args.gramian_mode == "auto" and not args.no_fp32_leg and not big:
             leg = unplanted_leg(torch, pkg, sharded, synth, n_users, n_items, nnz_req, k, args, 1, smode, local_rank, device, prob=prob,
                                 label="the headline workload with --gramian-mode fp32 (per-row Gramian on v_mfma_f32_16x16x4_f32)")
             leg.pop("_all_rows_launches", None)
@@ -703,7 +722,7 @@ def main():
                 leg["kernel"] = "rows kernel (als_persistent_kernel_h<4,0,.,3>, MODE 0)"
                 leg["slower_than_split_f16_by"] = leg["ms_per_step"] / ms_per_step - 1.0
                 out["roofline_split24"] = leg
-        if world == 1 and not args.no_cpu_baseline and not rank_shape and not big:
+        if args.full and world == 1 and not args.no_cpu_baseline and not rank_shape and not big:
             X = als.factors(pkg.SIDE_X)
             Y = als.factors(pkg.SIDE_Y)
             out["cpu_baseline"] = cpu_baseline(torch, pkg, prob, X, Y, n_users, n_items, k)

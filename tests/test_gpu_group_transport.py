@@ -253,19 +253,19 @@ def test_group_through_torch_distributed_two_processes():
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_script_as_the_driver_launches_it(world):
-    """`python bench.py --gpus N` end to end (self-launch through torch.distributed.run, one rank per process, the
+    """`python bench.py --gpus N --full` end to end (self-launch through torch.distributed.run, one rank per process, the
     group API, the timing bracket, ONE JSON line from rank 0 as the last line of stdout) on the stand-in transport."""
     env = dict(os.environ, MALS_BENCH_TRANSPORT=MOCK, MALS_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-                        "--workload", "small"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--workload", "small", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert sum(ln.startswith("{") for ln in lines) == 1, lines[-5:]
     d = json.loads(lines[-1])
     assert d["n_gpus"] == world and d["steps"] == 2 and d["warmup"] == 1
-    assert d["unit"] == "rows/s" and d["value"] > 0 and d["scaling"] == "strong"
+    assert d["unit"] == "rows/s" and d["value"] > 0 and d["scaling"] == "strong" and d["full"] is True
     # the same steps timed once more with the status check of every half-iteration inside the region
     assert d["ms_per_step_without_check"] > 0 and d["value_without_check"] > 0
     assert "INVALID_AS_A_MEASUREMENT" in d          # the line says what it is
@@ -284,18 +284,19 @@ def test_bench_script_as_the_driver_launches_it(world):
 
 
 def test_bench_line_on_one_gpu_says_what_it_leaves_out():
-    """`python bench.py` (N = 1) on the small workload: the line carries the time with the per-half status check inside the
+    """`python bench.py --full` (N = 1) on the small workload: the line carries the time with the per-half status check inside the
     timed region, the CPU baseline sampled by time (work units per thread, CPU model, threads), the fp32-arithmetic leg
     beside the split-f16 headline, and the operand scale / range flag of the last split-precision gather."""
     env = dict(os.environ)
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MALS_BENCH_TRANSPORT", "MALS_BENCH_ONE_DEVICE"):
         env.pop(v, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "small"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "small", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     # the dtype names the arithmetic the path really computes in (k = 64 here: split-f16 operands, f32 accumulate)
     assert d["n_gpus"] == 1 and d["dtype"].startswith("f32 storage; per-row Gramian: f16x2-split") and d["vs_baseline"] is None
+    assert d["full"] is True
     assert d["ms_per_step"] > 0 and d["ms_per_step_without_check"] > 0
     assert 0.33 * d["ms_per_step"] < d["ms_per_step_without_check"] < 2.0 * d["ms_per_step"]
     rf, r32 = d["roofline"], d["roofline_fp32"]
@@ -310,3 +311,61 @@ def test_bench_line_on_one_gpu_says_what_it_leaves_out():
     gs = d["gather_scale"]
     assert len(gs) == 4 and gs[2] == 1.0 and gs[0] > 0          # the split-f16 kernels ran, not their fp32 twins
     assert "roofline_unplanted" in d
+
+
+# what only --full runs: keys of the result line that a plain run leaves out
+FULL_ONLY = ("ms_per_step_without_check", "value_without_check", "half_iteration_kernel_ms", "all_gather_alone_ms",
+             "reconstruction_error", "roofline_unplanted", "roofline_fp32", "roofline_split24", "cpu_baseline",
+             "cpu_baseline_reference_jvm")
+
+
+def test_plain_bench_run_is_lean(tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W` without --full: set-up, warm-up, the timed steps, --dump-outputs and the
+    result line -- the headline keys mean what they do under --full, nothing that takes a run of its own is in the line, the
+    legs' switches change nothing, and the dumped factors are those of the timed steps."""
+    env = dict(os.environ)
+    for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MALS_BENCH_TRANSPORT", "MALS_BENCH_ONE_DEVICE"):
+        env.pop(v, None)
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "small",
+                        "--dump-outputs", str(dump)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert sum(ln.startswith("{") for ln in lines) == 1 and lines[-1].startswith("{"), lines[-5:]
+    d = json.loads(lines[-1])
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["metric"] == "ALS rows solved/sec (full iteration) at k=64" and d["unit"] == "rows/s" and d["higher_is_better"] is True
+    assert d["dtype"].startswith("f32 storage; per-row Gramian: f16x2-split")
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - (d["config"]["users"] + d["config"]["items"]) / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    assert not [key for key in FULL_ONLY if key in d], sorted(d)
+    # the figures that the HIP events of the timed steps give stay in the line: they cost no run of their own
+    rf = d["roofline"]
+    assert rf["bound"] == "hbm" and 0 < rf["frac"] < 1.2 and rf["launches"] > 0
+    assert sum(d["kernels_ms_per_step"].values()) > 0
+    gs = d["gather_scale"]
+    assert len(gs) == 4 and gs[2] == 1.0 and gs[0] > 0
+    X, Y = np.load(dump / "X.npy"), np.load(dump / "Y.npy")
+    # a side too large for its half of the dump is written as a fixed seeded row sample, its row numbers beside it
+    xr, yr = np.load(dump / "X_rows.npy"), np.load(dump / "Y_rows.npy")
+    assert X.shape == (len(xr), 64) and Y.shape == (len(yr), 64) and 0 < len(xr) <= d["config"]["users"] and len(yr) == d["config"]["items"]
+    assert np.isfinite(X).all() and np.isfinite(Y).all() and np.abs(X).max() > 0 and np.abs(Y).max() > 0
+    # the dump of a --full run of the same arguments is the same: what --full adds runs after the timed steps and the dump
+    dump_full = tmp_path / "dump_full"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "small",
+                        "--dump-outputs", str(dump_full), "--full", "--no-cpu-baseline", "--no-unplanted", "--no-fp32-leg"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    f = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert f["full"] is True and f["ms_per_step_without_check"] > 0 and "reconstruction_error" in f and "cpu_baseline" not in f
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert f[key] == d[key], key
+    # ... and launches the dominant kernel more often in its process: the plain run stopped after the timed steps
+    assert rf["all_launches_in_process"]["launches"] > 0
+    if f["roofline"]["kernel"] == rf["kernel"]:      # (the tally is that of the kernel with the most time: the same one in both runs)
+        assert f["roofline"]["all_launches_in_process"]["launches"] > rf["all_launches_in_process"]["launches"]
+    # two runs of the same steps on the same seeded inputs: each within REL_TOL of the oracle's factors, so of each other
+    assert np.array_equal(np.load(dump_full / "X_rows.npy"), xr) and np.array_equal(np.load(dump_full / "Y_rows.npy"), yr)
+    ex, ey = rel(np.load(dump_full / "X.npy"), X), rel(np.load(dump_full / "Y.npy"), Y)
+    print("plain vs --full dump: rel X %.3e  Y %.3e" % (ex, ey))
+    assert ex < REL_TOL and ey < REL_TOL, (ex, ey)
