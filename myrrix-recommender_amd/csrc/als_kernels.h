@@ -43,6 +43,7 @@ __host__ __device__ constexpr int tri(int T) { return T * (T + 1) / 2; }
 // index of upper tile (i <= j), row-major over the upper triangle
 __host__ __device__ constexpr int tidx(int T, int i, int j) { return i * T - (i * (i - 1)) / 2 + (j - i); }
 
+constexpr int GRAMIAN_FLUSH_BINADES = 5;  // gramian_split_kernel: in front of a step this many binades quieter than the slab so far the slab is cut (its rest: a second partial)
 constexpr int YMAX_SLOTS = 64;  // addresses the Gramian kernels spread their max |element| atomics over (power of two)
 
 struct WorkItem {   // one row (list A) or one segment of a long row (list B); 16 bytes, s_load_dwordx4
@@ -1941,7 +1942,9 @@ __global__ __launch_bounds__(256) void gramian_partial_kernel(const float* __res
 // first stage for the many slab partials of gramian_split_kernel: group q of `groups` sums its share of the slabs
 // (fixed order) into one set of doubles, element by element, coalesced -- thousands of workgroups instead of the 144 of
 // the finalize kernel
-__global__ __launch_bounds__(256) void gramian_reduce_slabs_kernel(const float* __restrict__ partial, int64_t n_slabs, int elems,
+// A slab that gramian_split_kernel cut in two (cut_row != 0) brings a second partial, added right behind its first.
+__global__ __launch_bounds__(256) void gramian_reduce_slabs_kernel(const float* __restrict__ partial, const float* __restrict__ partial2,
+                                                                   const int* __restrict__ cut_row, int64_t n_slabs, int elems,
                                                                    int groups, double* __restrict__ out) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   const int q = blockIdx.y;
@@ -1949,7 +1952,10 @@ __global__ __launch_bounds__(256) void gramian_reduce_slabs_kernel(const float* 
   const int64_t per = (n_slabs + groups - 1) / groups;
   const int64_t w0 = q * per, w1 = (q + 1) * per < n_slabs ? (q + 1) * per : n_slabs;
   double acc = 0.0;
-  for (int64_t w = w0; w < w1; ++w) acc += (double)partial[w * (int64_t)elems + e];
+  for (int64_t w = w0; w < w1; ++w) {
+    acc += (double)partial[w * (int64_t)elems + e];
+    if (cut_row[w]) acc += (double)partial2[w * (int64_t)elems + e];   // uniform
+  }
   out[(int64_t)q * elems + e] = acc;
 }
 
@@ -2074,20 +2080,37 @@ __global__ __launch_bounds__(256) void gramian_ref_kernel(const float* __restric
 // accumulates in fp32 only over its slab of rows_per_slab rows (512 .. 2048: gramian_slab_rows in mals_api.hip), the slab partials
 // are summed in fp64 in a fixed order by gramian_finalize_kernel.  Per slab the fp32 sum carries <= 6e-8 x sqrt(roundings) relative (random; 48 .. 192 roundings);
 // over the hundreds of slabs this kernel is used for that averages far below the reference's own product rounding
-// (MU:232 rounds every product to fp32), and stays at 3e-7 even when a handful of rows dominate G.  Small matrices keep the fp64 kernel (launch_gramian).
+// (MU:232 rounds every product to fp32), and stays at 3e-7 of |G| (Frobenius) even when a handful of rows dominate G.  Small matrices keep the fp64 kernel (launch_gramian).
+// Per ELEMENT, |dG_ij| / sqrt(G_ii G_jj), a G that one step dominates shows the arithmetic itself: a split product drops lo.lo (2^-22)
+// and carries two 22-bit operands (2 x 2^-23), 4.8e-7 at worst and 2.5 .. 4.0e-7 measured.  One set of fp32 sums per slab added to
+// that when the dominating step was NOT the slab's last: the 15 (E = 8) or 31 (E = 4) steps behind it each rounded at up to 2^-24 of
+// the sums it dominates (4.6 .. 8.9e-7 per element).  So a slab may be CUT: in front of the first step that is GRAMIAN_FLUSH_BINADES = 5
+// binades quieter than a step before it (its products 2^10 smaller) the slab ends, and a second launch (REST) sums the rows from there
+// on from zero at their own scale into the slab's second partial -- once per slab; a second such outlier behind the cut is summed as
+// before.  The second partial is written and read only for slabs that were cut (cut_row), the hot loop is the same code as without it.
 // Operand scale: a power of two per wave, lowered (with an exact rescale of the accumulators) whenever a 16-row
 // step brings a larger |value| than any before it -- no bound is needed from outside and an outlier row costs
 // the rows after it a few low bits relative to sums it already dominates.
+// Contract of the scale: a matrix times 2^s gives G times 2^(2s) bit for bit (the operands z = y 2^pw do not depend on s,
+// the rescale of the sums and `back` = 2^(-2 pw) are exact) as long as `back` stays inside its clamp of 2^+-126 and the
+// float32 slab partials stay normal and finite.  With a slab's largest |value| below 2^eb the scale is pw = 14 - eb:
+// |pw| <= 63 and partials below 2^128 mean, for values of 1 .. 2^9 and slab sums up to 2^24 (the integer data of
+// tests/gramian_cases.py), -52 <= s <= 51; rely on |s| <= 49.  Outside that range the partials saturate or flush and
+// G is wrong without a flag.  tests/test_gpu_gramian_edges.py pins |s| <= 40 on the device, tests/test_gramian_cases.py
+// |s| <= 49 on a numpy restatement of this kernel.
 // Layout: lane (g,c) holds, for rows r0 + 4g + s (s = 0..3) and every 16-block v, feature 16v + c -- the A and the B
 // operand of the instruction at once (contraction over the 16 rows of the step).
 // E = rows per lane and step (a step = 4 E rows = one MFMA contraction): 8 -> v_mfma_f32_16x16x32_f16 for T <= 4 (both
 // instructions take 16 cycles, so the x32 one halves the matrix-pipe time, and the per-step maximum / rescale logic runs half
 // as often; round 5), 4 -> v_mfma_f32_16x16x16_f16 where two buffers of 8 raw rows per tile do not fit next to the accumulators
 // (T = 6 spilled 188 bytes with E = 8).
-template <int T>
+// REST = false: the pass over every slab; cut_row[slab] = the row (of the slab) where do_step cut it, 0 = not cut.
+// REST = true: a second launch of the same grid for the rows behind a cut, into the slabs' second partials; a wave whose slab was
+// not cut loads one step, finds no rows and stores nothing.
+template <int T, bool REST>
 __global__ __launch_bounds__(256, 2) void gramian_split_kernel(const float* __restrict__ M, int64_t n_rows, int k,
                                                                int64_t rows_per_slab, float* __restrict__ partial,
-                                                               unsigned* __restrict__ ymax) {
+                                                               int* __restrict__ cut_row, unsigned* __restrict__ ymax) {
   constexpr int E = T <= 4 ? 8 : 4, STEP = 4 * E;
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t slab = uniform64((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -2106,8 +2129,10 @@ __global__ __launch_bounds__(256, 2) void gramian_split_kernel(const float* __re
   // features are clamped / zeroed only in the steps that need it (the last step of a ragged slab; the last 16-block
   // when k < 16 T).  Until the second half of round 5 every load carried a 64-bit row x k multiply and a clamp and every
   // element a select: 550 vector instructions per step against 30 matrix instructions, 4.8 TB/s.
-  const int n_slab = (int)(r1 - r0);            // rows of this slab (uniform; <= 0 for the padding slabs of the last workgroup)
-  const float* __restrict__ base = M + (n_slab > 0 ? r0 : 0) * k;
+  const int n_all = (int)(r1 - r0);             // rows of this slab (uniform; <= 0 for the padding slabs of the last workgroup)
+  const int begin = REST ? (n_all > 0 ? uniform(cut_row[slab]) : 0) : 0;   // REST: the first row behind the cut, 0 = no cut
+  int n_slab = REST ? (begin > 0 ? n_all - begin : 0) : n_all;   // rows to sum (uniform); lowered by do_step where it cuts the slab
+  const float* __restrict__ base = M + ((n_slab > 0 ? r0 : 0) + begin) * k;
   const bool kfull = k == 16 * T;               // uniform
   int fo[T];                                    // this lane's feature of 16-block v, clamped into the row
 #pragma unroll
@@ -2161,6 +2186,7 @@ __global__ __launch_bounds__(256, 2) void gramian_split_kernel(const float* __re
     for (int s4 = 0; s4 < E; ++s4)
 #pragma unroll
       for (int v = 0; v < T; ++v) amax = fmaxf(amax, fabsf(raw[v][s4]));
+    bool dead = false;  // this step is where the slab gets cut: it contributes zeros (operand scale 0)
     int m = __float_as_int(amax);  // non-negative floats order like their bit patterns
     for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off));
     m = uniform(m);
@@ -2168,7 +2194,15 @@ __global__ __launch_bounds__(256, 2) void gramian_split_kernel(const float* __re
     if (m != 0) {
       const int eb = ((m >> 23) & 255) - 126;  // step max < 2^eb
       const int want = 14 - eb;
-      if (want < pw) {  // a larger value than any before: lower the scale, bring the sums along (exact)
+      if (!REST && pw != 100 && want >= pw + GRAMIAN_FLUSH_BINADES) {
+        // uniform: the first step that is 2^5 quieter than a step before it.  Its products (2^10 smaller) would round at the ulp
+        // of sums the loud step dominates, and so would every step after it: the slab ENDS in front of this step (this step and
+        // whatever the loop still runs contribute zeros, like steps past a ragged end) and the rows from here on are summed
+        // as a part of their own, from zero and at their own scale, by the REST launch.  Nothing but the end of the slab
+        // changes in the hot loop (a second pass inside this kernel cost 17 .. 44 spilled registers at T = 4, 6, 8); once per slab.
+        n_slab = rl;
+        dead = true;
+      } else if (want < pw) {  // a larger value than any before: lower the scale, bring the sums along (exact)
         if (pw != 100) {
           int d2 = 2 * (want - pw);
           d2 = d2 < -120 ? -120 : d2;
@@ -2180,7 +2214,7 @@ __global__ __launch_bounds__(256, 2) void gramian_split_kernel(const float* __re
       }
     }
     const int pwc = pw == 100 ? 0 : (pw < -100 ? -100 : (pw > 100 ? 100 : pw));
-    const float sc = __int_as_float((pwc + 127) << 23);
+    const float sc = dead ? 0.f : __int_as_float((pwc + 127) << 23);
     ZOp<E> zh[T], zl[T];
 #pragma unroll
     for (int v = 0; v < T; ++v) {
@@ -2226,11 +2260,14 @@ __global__ __launch_bounds__(256, 2) void gramian_split_kernel(const float* __re
   int d2 = pw == 100 ? 0 : -2 * pw;
   d2 = d2 < -126 ? -126 : (d2 > 126 ? 126 : d2);
   const float back = __int_as_float((d2 + 127) << 23);
-  float* o = partial + slab * (int64_t)(tri(T) * 4 * 64) + lane;
+  if (!REST || begin > 0) {  // uniform
+    float* o = partial + slab * (int64_t)(tri(T) * 4 * 64) + lane;
 #pragma unroll
-  for (int t = 0; t < tri(T); ++t)
+    for (int t = 0; t < tri(T); ++t)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) o[(t * 4 + r) * 64] = acc[t][r] * back;
+      for (int r = 0; r < 4; ++r) o[(t * 4 + r) * 64] = acc[t][r] * back;
+  }
+  if (!REST && lane == 0) cut_row[slab] = n_slab < n_all ? n_slab : 0;
   if (ymax) {  // wave-uniform
     // one atomic per workgroup, spread over YMAX_SLOTS addresses: same-address atomics serialise (~0.1 us each) and the
     // waves of a launch finish together; the consumer takes the maximum of the slots

@@ -570,7 +570,7 @@ int drain_events(mals_handle h) {
 constexpr int64_t GRAMIAN_SPLIT_MIN_ROWS = 262144;
 // Rows a wave of gramian_split_kernel sums in fp32 before its partial goes to the fp64 stages.  512 keeps a 262144-row matrix
 // at 128 workgroups; from 4M rows on the 10 KB partial per slab (200 MB written and read again at 10M rows, a sixth of the
-// input) is worth more than the extra waves: 2048 there (10M x 64: 0.67 -> 0.53 ms).  fp32 roundings per accumulator and slab:
+// input; a second one only for the slabs the kernel cuts) is worth more than the extra waves: 2048 there (10M x 64: 0.67 -> 0.53 ms; 0.54 with the second launch for cut slabs).  fp32 roundings per accumulator and slab:
 // 3 per 32-row step, 192 at 2048 rows -- 8e-7 relative at random, averaged over thousands of slabs in fp64.
 inline int64_t gramian_slab_rows(int64_t n_rows) {
   static const int64_t forced = std::getenv("MALS_GRAMIAN_SLAB_ROWS") ? std::atoll(std::getenv("MALS_GRAMIAN_SLAB_ROWS")) : 0;  // tuning override (a multiple of 64)
@@ -590,14 +590,20 @@ int launch_gramian_T(mals_handle h, SideState& s, const float* M, int64_t n_rows
     int64_t n_slabs = (n_rows + slab_rows - 1) / slab_rows;
     n_slabs = (n_slabs + 3) & ~(int64_t)3;  // whole workgroups
     constexpr int GROUPS = 64;              // first-stage sums (doubles) behind the slab partials (floats)
+    // a partial per slab, room for a second one (written and read only for the slabs the kernel cuts in two), the groups' sums, the cut row per slab
     const size_t slab_bytes = sizeof(float) * (size_t)n_slabs * tri(T) * 256;
-    const size_t bytes = slab_bytes + sizeof(double) * (size_t)GROUPS * tri(T) * 256;
+    const size_t bytes = 2 * slab_bytes + sizeof(double) * (size_t)GROUPS * tri(T) * 256 + sizeof(int) * (size_t)n_slabs;
     if (s.partials.capacity() < bytes) HIPCHK(h, s.partials.alloc(bytes));
     float* pf = reinterpret_cast<float*>(s.partials.get());
-    double* pd = reinterpret_cast<double*>(s.partials.get() + slab_bytes);  // slab_bytes is a multiple of 1024
-    hipLaunchKernelGGL((gramian_split_kernel<T>), dim3((unsigned)(n_slabs / 4)), dim3(256), 0, h->stream, M, n_rows, k,
-                       slab_rows, pf, ymax);
-    hipLaunchKernelGGL(gramian_reduce_slabs_kernel, dim3((unsigned)((elems + 255) / 256), GROUPS), dim3(256), 0, h->stream, pf, n_slabs,
+    float* pf2 = reinterpret_cast<float*>(s.partials.get() + slab_bytes);
+    double* pd = reinterpret_cast<double*>(s.partials.get() + 2 * slab_bytes);  // slab_bytes is a multiple of 1024
+    int* has2 = reinterpret_cast<int*>(s.partials.get() + 2 * slab_bytes + sizeof(double) * (size_t)GROUPS * tri(T) * 256);
+    hipLaunchKernelGGL((gramian_split_kernel<T, false>), dim3((unsigned)(n_slabs / 4)), dim3(256), 0, h->stream, M, n_rows, k,
+                       slab_rows, pf, has2, ymax);
+    // the rows behind the cuts of the first pass (a quiet step after a loud one), summed on their own; waves of slabs without one return
+    hipLaunchKernelGGL((gramian_split_kernel<T, true>), dim3((unsigned)(n_slabs / 4)), dim3(256), 0, h->stream, M, n_rows, k,
+                       slab_rows, pf2, has2, ymax);
+    hipLaunchKernelGGL(gramian_reduce_slabs_kernel, dim3((unsigned)((elems + 255) / 256), GROUPS), dim3(256), 0, h->stream, pf, pf2, has2, n_slabs,
                        elems, GROUPS, pd);
     hipLaunchKernelGGL((gramian_finalize_kernel<T, false>), dim3(elems / 64), dim3(256), 0, h->stream, pd, (int64_t)GROUPS, k, G_out, Gf_out);
     HIPCHK(h, hipGetLastError());
