@@ -74,7 +74,9 @@ typedef struct mals_config {
                                    (LinearSystemSolver.java:33-34)                             */
   int32_t flags;                /* MALS_FLAG_*                                                 */
   int32_t device;               /* HIP device ordinal                                          */
-  int32_t segment_nnz;          /* rows longer than this are split across waves; 0 = default   */
+  int32_t segment_nnz;          /* rows longer than this are split across waves; 0 = default.
+                                   Long dense rows with ascending columns are cut by band of the
+                                   gather table instead of by count        */
   int32_t chunk_rows;           /* >0: the shard's rows are cut into contiguous ranges of this many
                                    rows that can be solved one by one (mals_solve_chunk), so that
                                    the caller can exchange a finished range while the next one is

@@ -13,6 +13,7 @@
 #include "foldin_kernels.h"
 #include "mals_internal.h"
 #include "hip_buffer.h"
+#include "band_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -35,6 +36,7 @@
 #include <thread>
 #include <type_traits>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #ifndef MALS_D4
@@ -65,7 +67,8 @@ struct SideState {
   DeviceBuffer<WorkItem> itemsA;  // rows no longer than segment_nnz, longest first
   int64_t nA = 0;
   int64_t nnzA = 0, nnzB = 0;  // entries handled by the rows kernel / the segments kernel
-  DeviceBuffer<WorkItem> itemsB;  // segments of the long rows, longest first
+  DeviceBuffer<WorkItem> itemsB;  // segments of the long rows, longest first; behind them the chunk's banded segments
+                                  // (band_plan.h), band by band
   int64_t nB = 0;
   DeviceBuffer<RowC> rowsC;
   int64_t nC = 0;
@@ -86,10 +89,12 @@ struct SideState {
     int64_t offA = 0, nA = 0, nnzA = 0, offB = 0, nB = 0, nnzB = 0, offC = 0, nC = 0;
     int64_t offP = 0, nP = 0;  // groups of partial slots reduced ahead of the finish kernel (entries of rowsC as well)
     int64_t nD[4] = {0, 0, 0, 0}, nnzD[4] = {0, 0, 0, 0}, nZ = 0;
+    int64_t nBand = 0, nnzBand = 0;  // the tail of list B (included in nB, nnzB): segments cut at the gather table's bands
     int64_t n_dual() const { return nD[0] + nD[1] + nD[2] + nD[3]; }
     int64_t nnz_dual() const { return nnzD[0] + nnzD[1] + nnzD[2] + nnzD[3]; }
   };
   int64_t n_dual_rows = 0;
+  bool band_front = true;  // the banded segments run as one front (one segment per wave) instead of the strided grid
   int64_t chunk_rows_override = -1;  // mals_set_chunk_rows: per-side value of cfg.chunk_rows (-1 = use cfg)
   std::vector<ChunkRange> chunks;
   // Gramian of THIS side's factors (consumed when solving the other side)
@@ -306,6 +311,93 @@ int alloc_matrix(mals_handle h, SideState& s) {
 
 int64_t slot_floats(int T) { return (int64_t)(tri(T) * 4 + T) * 64; }
 
+// ---- banded cuts of long dense rows (band_plan.h) ------------------------------------------------
+// Default size of a band of the gather table; MALS_BAND_BYTES overrides it, 0 = no banding.  Chosen by the sweep of
+// profiles/HISTORY.md, round 7.
+constexpr int64_t BAND_BYTES_DEFAULT = 64ll << 20;
+constexpr int BAND_CHECK_SLICES = 16;
+
+struct BandRow {   // a row long enough to be banded
+  int64_t begin;   // offset of its first entry in col
+  int64_t len;
+};
+
+// Grid (rows, BAND_CHECK_SLICES).  Every workgroup checks its slice of the row's adjacent column pairs (unsorted[row]
+// = 1 where one descends); the first slice's also finds, per band boundary b, the first entry whose column is in band
+// b or later: off[row][b], b = 0 .. n_bands (meaningless for an unsorted row; still inside [0, len]).
+__global__ __launch_bounds__(256) void band_cuts_kernel(const int32_t* __restrict__ col, const BandRow* __restrict__ rows, int n_bands,
+                                                        int64_t band_rows, int64_t* __restrict__ off, int* __restrict__ unsorted) {
+  const BandRow r = rows[blockIdx.x];
+  const int32_t* c = col + r.begin;
+  const int64_t pairs = r.len - 1;
+  const int64_t per = (pairs + gridDim.y - 1) / gridDim.y;
+  const int64_t p0 = (int64_t)blockIdx.y * per < pairs ? (int64_t)blockIdx.y * per : pairs, p1 = p0 + per < pairs ? p0 + per : pairs;
+  bool descends = false;
+  for (int64_t i = p0 + threadIdx.x; i < p1; i += 256) descends |= c[i] > c[i + 1];
+  if (descends) unsorted[blockIdx.x] = 1;  // (every writer stores the same value)
+  if (blockIdx.y != 0) return;
+  for (int b = threadIdx.x; b <= n_bands; b += 256) {
+    const int64_t first_col = (int64_t)b * band_rows;
+    int64_t lo = 0, hi = r.len;
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if ((int64_t)c[mid] < first_col) lo = mid + 1; else hi = mid;
+    }
+    off[(int64_t)blockIdx.x * (n_bands + 1) + b] = b == n_bands ? r.len : lo;
+  }
+}
+
+struct BandCuts {
+  int64_t n_bands = 1, band_rows = 0, min_avg = 0;
+  std::vector<int64_t> row;      // the rows long enough, ascending
+  std::vector<int64_t> off;      // [row.size()][n_bands + 1]
+  std::vector<int> unsorted;     // [row.size()]
+};
+
+// Which rows of the shard are banded and where their columns cross the bands: one kernel and one copy back per list build.
+int find_band_cuts(mals_handle h, const SideState& s, BandCuts& bc) {
+  const char* e = std::getenv("MALS_BAND_BYTES");   // read at every build: the tests switch it between two handles
+  const int64_t band_bytes = e ? std::atoll(e) : BAND_BYTES_DEFAULT;
+  if (band_bytes <= 0 || s.nnz == 0) return MALS_OK;
+  const int k = h->cfg.features;
+  const int64_t ld = k % 16 ? 16 * (int64_t)h->T : k;   // row stride of the table the kernels gather from (solve_chunks)
+  bc.band_rows = std::max<int64_t>(1, band_bytes / (4 * ld));
+  bc.n_bands = std::max<int64_t>(1, ((int64_t)s.col_max + bc.band_rows) / bc.band_rows);  // bands that hold a referenced row
+  if (bc.n_bands > (1 << 20)) bc.n_bands = 1;   // (a band of a few rows: nothing to keep cached)
+  if (bc.n_bands == 1) return MALS_OK;
+  const char* m = std::getenv("MALS_BAND_MIN_ENTRIES");
+  bc.min_avg = std::max<int64_t>(1, m ? std::atoll(m) : band_min_avg(slot_floats(h->T), k));
+  const std::vector<int64_t>& rp = s.h_row_ptr;
+  std::vector<BandRow> rows;
+  for (int64_t r = 0; r < s.n_local; ++r) {
+    const int64_t len = rp[r + 1] - rp[r];
+    if (band_row_eligible(len, h->cfg.segment_nnz, bc.n_bands, bc.min_avg)) {
+      bc.row.push_back(r);
+      rows.push_back(BandRow{rp[r], len});
+    }
+  }
+  if (rows.empty()) return MALS_OK;
+  // (len >= min_avg * n_bands: the offsets are at most 2 nnz / min_avg words)
+  const size_t n_off = rows.size() * (size_t)(bc.n_bands + 1);
+  DeviceBuffer<BandRow> d_rows;
+  DeviceBuffer<int64_t> d_off;
+  DeviceBuffer<int> d_unsorted;
+  HIPCHK(h, d_rows.alloc(rows.size()));
+  HIPCHK(h, d_off.alloc(n_off));
+  HIPCHK(h, d_unsorted.alloc(rows.size()));
+  HIPCHK(h, hipMemcpyAsync(d_rows.get(), rows.data(), sizeof(BandRow) * rows.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_unsorted.get(), 0, sizeof(int) * rows.size(), h->stream));
+  hipLaunchKernelGGL(band_cuts_kernel, dim3((unsigned)rows.size(), BAND_CHECK_SLICES), dim3(256), 0, h->stream, s.col, d_rows.get(),
+                     (int)bc.n_bands, bc.band_rows, d_off.get(), d_unsorted.get());
+  HIPCHK(h, hipGetLastError());
+  bc.off.resize(n_off);
+  bc.unsorted.resize(rows.size());
+  HIPCHK(h, hipMemcpyAsync(bc.off.data(), d_off.get(), sizeof(int64_t) * n_off, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(bc.unsorted.data(), d_unsorted.get(), sizeof(int) * rows.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MALS_OK;
+}
+
 // Split the rows of a shard into the three work lists (DESIGN.md "work decomposition"), chunk by chunk.
 int build_work_lists(mals_handle h, SideState& s) {
   s.max_abs_val = 0.f;
@@ -352,7 +444,17 @@ int build_work_lists(mals_handle h, SideState& s) {
   const std::vector<int64_t>& rp = s.h_row_ptr;
   std::vector<WorkItem> order;
   std::vector<WorkItem> segs;
+  std::vector<std::pair<int32_t, WorkItem>> band_segs;  // (band, segment) of the chunk's banded rows
+  std::vector<BandPiece> pieces;
   std::vector<RowC> rowsC, groups;
+  BandCuts bc;
+  if (int rc = find_band_cuts(h, s, bc)) return rc;
+  {
+    const char* e = std::getenv("MALS_BAND_FRONT");  // A/B: 0 = the strided 16x grid
+    s.band_front = !e || std::atoi(e) != 0;
+  }
+  size_t bc_next = 0;  // cursor into bc.row (the chunks visit the rows in ascending order)
+  int64_t n_banded_rows = 0, n_banded_segs = 0, n_unsorted = 0;
   order.reserve((size_t)n);
   int64_t slot = 0;
   s.chunks.assign((size_t)n_chunks, SideState::ChunkRange());
@@ -425,14 +527,37 @@ int build_work_lists(mals_handle h, SideState& s) {
         rc.nseg = 0;
         rc.stride = 1;
         rc.pad_ = 0;
-        for (int64_t b = 0; b < len; b += per) {
-          if (slot >= std::numeric_limits<int32_t>::max()) return fail(h, MALS_INVALID_ARG, "too many row segments");
-          WorkItem sg;
-          sg.begin = rp[r] + b;
-          sg.len = (int32_t)std::min(per, len - b);
-          sg.id = (int32_t)slot++;
-          segs.push_back(sg);
-          ++rc.nseg;
+        // A row long enough to be cut at the gather table's bands (band_plan.h), with ascending columns: its pieces,
+        // slots in entry order like any other row's.  Everything else: cuts by count.
+        pieces.clear();
+        if (bc_next < bc.row.size() && bc.row[bc_next] == r) {
+          if (bc.unsorted[bc_next]) ++n_unsorted;
+          else if (!band_plan_row(&bc.off[bc_next * (size_t)(bc.n_bands + 1)], bc.n_bands, len, seg, pieces)) pieces.clear();
+          ++bc_next;
+        }
+        if (!pieces.empty()) {
+          ++n_banded_rows;
+          n_banded_segs += (int64_t)pieces.size();
+          cr.nnzBand += len;
+          for (const BandPiece& pc : pieces) {
+            if (slot >= std::numeric_limits<int32_t>::max()) return fail(h, MALS_INVALID_ARG, "too many row segments");
+            WorkItem sg;
+            sg.begin = rp[r] + pc.begin;
+            sg.len = pc.len;
+            sg.id = (int32_t)slot++;
+            band_segs.emplace_back(pc.band, sg);
+            ++rc.nseg;
+          }
+        } else {
+          for (int64_t b = 0; b < len; b += per) {
+            if (slot >= std::numeric_limits<int32_t>::max()) return fail(h, MALS_INVALID_ARG, "too many row segments");
+            WorkItem sg;
+            sg.begin = rp[r] + b;
+            sg.len = (int32_t)std::min(per, len - b);
+            sg.id = (int32_t)slot++;
+            segs.push_back(sg);
+            ++rc.nseg;
+          }
         }
         if (rc.nseg > FINISH_GROUP) {  // group sums first (als_prereduce_kernel), the finish kernel walks the leaders
           // (groups of max(8, sqrt(segments)) slots, more rows grouped: finish + group sums 0.29 -> 0.35 ms on C4 -- every
@@ -464,14 +589,20 @@ int build_work_lists(mals_handle h, SideState& s) {
     cr.nA = n_direct + (n_empty > 0 ? 1 : 0);
     cr.nZ = n_empty > 0 ? n_empty - 1 : 0;
     s.n_dual_rows += n_dual;
-    cr.nB = (int64_t)segs.size() - cr.offB;
+    cr.nBand = (int64_t)band_segs.size();
+    cr.nB = (int64_t)segs.size() - cr.offB + cr.nBand;
     cr.nC = (int64_t)rowsC.size() - cr.offC;
     cr.offP = (int64_t)rowsC.size();  // the chunk's slot groups sit behind its rows in the same array
     cr.nP = (int64_t)groups.size();
     rowsC.insert(rowsC.end(), groups.begin(), groups.end());
     groups.clear();
-    // longest segments first
+    // longest segments first; behind them the banded ones by band, longest first inside a band (both stable in row order)
     std::stable_sort(segs.begin() + cr.offB, segs.end(), [](const WorkItem& a, const WorkItem& b) { return a.len > b.len; });
+    std::stable_sort(band_segs.begin(), band_segs.end(), [](const std::pair<int32_t, WorkItem>& a, const std::pair<int32_t, WorkItem>& b) {
+      return a.first != b.first ? a.first < b.first : a.second.len > b.second.len;
+    });
+    for (const std::pair<int32_t, WorkItem>& bs : band_segs) segs.push_back(bs.second);
+    band_segs.clear();
     s.nnzA += cr.nnzA;
     s.nnzB += cr.nnzB;
   }
@@ -493,6 +624,12 @@ int build_work_lists(mals_handle h, SideState& s) {
                          "zero-filled %lld, segments %lld of %lld long rows (%lld entries)\n",
                  (long long)n, (long long)na, (long long)s.nnzA, (long long)nd[0], (long long)ed[0], (long long)nd[1], (long long)ed[1], (long long)nd[2],
                  (long long)ed[2], (long long)nd[3], (long long)ed[3], (long long)nz, (long long)s.nB, (long long)n_long, (long long)s.nnzB);
+    int64_t e_band = 0;
+    for (const SideState::ChunkRange& cr : s.chunks) e_band += cr.nnzBand;
+    std::fprintf(stderr, "[lists] bands %lld of %lld table rows (at least %lld entries per band): %lld banded rows (%lld entries) in %lld segments, "
+                         "%lld long enough but unsorted\n",
+                 (long long)bc.n_bands, (long long)bc.band_rows, (long long)bc.min_avg, (long long)n_banded_rows, (long long)e_band,
+                 (long long)n_banded_segs, (long long)n_unsorted);
   }
   if (s.nA) {
     HIPCHK(h, s.itemsA.alloc(order.size()));
@@ -650,7 +787,13 @@ int launch_gramian(mals_handle h, SideState& s, const float* M, int64_t n_rows, 
 // assignment), 12-16x oversubscription lets the dispatcher level that out and each wave still
 // walks >100 rows, which keeps the cross-row prefetch effective; beyond 16x nothing changes.
 template <typename K>
-int persistent_grid(mals_handle h, K kernel, int64_t n_work, unsigned* grid) {
+int persistent_grid(mals_handle h, K kernel, int64_t n_work, unsigned* grid, bool front = false) {
+  if (front) {  // banded segments: one item per wave, workgroups dispatched in list order -- the resident waves then work
+                // on one contiguous stretch of the list, i.e. on one or two bands of the table, where the strided
+                // assignment has as many bands in flight as the list is longer than the grid
+    *grid = (unsigned)std::max<int64_t>(1, (n_work + 3) / 4);
+    return MALS_OK;
+  }
   int per_cu = 0;
   HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0));
   if (per_cu < 1) per_cu = 1;
@@ -668,10 +811,10 @@ enum { LISTS_ROWS = 1, LISTS_DUAL_ROWS = 2, LISTS_LONG = 4, LISTS_OWN = LISTS_RO
 // One persistent launch, plus -- for a split-precision kernel -- its fp32-gather twin right behind it with
 // flag bit 3: exactly one of the two does the work (gather_scale_kernel's range flag), the other returns at once.
 template <typename K, typename KF>
-int launch_persistent(mals_handle h, K kernel, KF fallback, const SolveParams& p, int kind, double bytes) {
+int launch_persistent(mals_handle h, K kernel, KF fallback, const SolveParams& p, int kind, double bytes, bool front = false) {
   PendingEvent pe;
   unsigned grid = 1;
-  if (int rc = persistent_grid(h, kernel, p.n_work, &grid)) return rc;
+  if (int rc = persistent_grid(h, kernel, p.n_work, &grid, front)) return rc;
   if (int rc = begin_timed(h, kind, bytes, pe)) return rc;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, h->stream, p);
   if constexpr (!std::is_same<KF, std::nullptr_t>::value) {
@@ -693,10 +836,15 @@ int launch_lists(mals_handle h, SideState& s, SolveParams p, int chunk, int whic
   const SideState::ChunkRange& cr = s.chunks[(size_t)chunk];
   PendingEvent pe;
   const bool own = which & LISTS_ROWS, longs = which & LISTS_LONG, dual_rows_too = which & LISTS_DUAL_ROWS;
-  if (longs && cr.nB) {
-    p.n_work = cr.nB;
+  if (longs && cr.nB > cr.nBand) {
+    p.n_work = cr.nB - cr.nBand;
     p.items = s.itemsB.get() + cr.offB;
-    if (int rc = launch_persistent(h, segments_kernel, segments_fallback, p, 1, (double)cr.nnzB * per)) return rc;
+    if (int rc = launch_persistent(h, segments_kernel, segments_fallback, p, 1, (double)(cr.nnzB - cr.nnzBand) * per)) return rc;
+  }
+  if (longs && cr.nBand) {  // the banded tail of list B, band by band
+    p.n_work = cr.nBand;
+    p.items = s.itemsB.get() + cr.offB + (cr.nB - cr.nBand);
+    if (int rc = launch_persistent(h, segments_kernel, segments_fallback, p, 1, (double)cr.nnzBand * per, s.band_front)) return rc;
   }
   if (own && cr.nA) {
     p.n_work = cr.nA;
@@ -731,11 +879,12 @@ int launch_lists(mals_handle h, SideState& s, SolveParams p, int chunk, int whic
 // the persistent launch of an LDS-staged kernel (lds_kernels.h): one wave per workgroup, LDS-limited to 8 per CU, the same
 // 16x oversubscription as persistent_grid
 template <typename K, typename KF>
-int launch_persistent_lds(mals_handle h, K kernel, KF fallback, const SolveParams& p, int kind, double bytes) {
+int launch_persistent_lds(mals_handle h, K kernel, KF fallback, const SolveParams& p, int kind, double bytes, bool front = false) {
   PendingEvent pe;
   int per_cu = 8 * 16;
   if (const char* e = std::getenv("MALS_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(e)) * 4;  // tuning override (in 256-thread blocks)
   unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(p.n_work, (int64_t)h->n_cu * per_cu));
+  if (front) grid = (unsigned)std::max<int64_t>(1, p.n_work);  // one item per wave, in list order (persistent_grid)
   if (int rc = begin_timed(h, kind, bytes, pe)) return rc;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, h->stream, p);
   SolveParams pf = p;
@@ -755,10 +904,15 @@ int launch_lists_lds(mals_handle h, SideState& s, SolveParams p, int chunk, int 
   const SideState::ChunkRange& cr = s.chunks[(size_t)chunk];
   PendingEvent pe;
   const bool own = which & LISTS_ROWS, longs = which & LISTS_LONG, dual_rows_too = which & LISTS_DUAL_ROWS;
-  if (longs && cr.nB) {
-    p.n_work = cr.nB;
+  if (longs && cr.nB > cr.nBand) {
+    p.n_work = cr.nB - cr.nBand;
     p.items = s.itemsB.get() + cr.offB;
-    if (int rc = launch_persistent_lds(h, als_lds_kernel_h<1>, als_persistent_kernel<T, D, 1, true>, p, 1, (double)cr.nnzB * per)) return rc;
+    if (int rc = launch_persistent_lds(h, als_lds_kernel_h<1>, als_persistent_kernel<T, D, 1, true>, p, 1, (double)(cr.nnzB - cr.nnzBand) * per)) return rc;
+  }
+  if (longs && cr.nBand) {  // the banded tail of list B, band by band
+    p.n_work = cr.nBand;
+    p.items = s.itemsB.get() + cr.offB + (cr.nB - cr.nBand);
+    if (int rc = launch_persistent_lds(h, als_lds_kernel_h<1>, als_persistent_kernel<T, D, 1, true>, p, 1, (double)cr.nnzBand * per, s.band_front)) return rc;
   }
   if (own && cr.nA) {
     p.n_work = cr.nA;
