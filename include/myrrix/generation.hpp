@@ -130,6 +130,68 @@ class Generation {
   std::unique_ptr<Solver> XTXsolver_, YTYsolver_;
 };
 
+// LocationSensitiveHash (online/src/net/myrrix/online/candidate/LocationSensitiveHash.java) on a serving handle: the candidate
+// filter Generation builds when model.lsh.sampleRatio < 1 (CandidateFilterFactory.java:50-71).  Once built, mals_recommend* on
+// the handle only see a query's candidates (LSH:193-216) and the rows of Y grown afterwards (the reference's newItems).
+class LocationSensitiveHash {
+ public:
+  // LSH:98-108; may be -1
+  static int maxBitsDiffering(double sampleRatio, int numHashes) {
+    int32_t out = 0;
+    if (mals_lsh_max_bits_differing(sampleRatio, numHashes, &out) != MALS_OK) throw std::invalid_argument("Bad LSH ratio or # hashes");
+    return out;
+  }
+  // model.lsh.sampleRatio / model.lsh.numHashes (LSH:70-71); the random vectors hash-major from `random`.nextBoolean(), as
+  // LSH:113-119 draws them from RandomManager.getRandom().  false: the ratio is 1, no filter (an earlier one is cleared).
+  template <typename Random>
+  static bool build(mals_handle h, Random& random) {
+    const double ratio = std::stod(System::getProperty("model.lsh.sampleRatio", "1.0"));
+    const int numHashes = std::stoi(System::getProperty("model.lsh.numHashes", "20"));
+    if (!(ratio > 0.0 && ratio <= 1.0)) throw std::invalid_argument("Bad LSH ratio");      // LSH:73-74
+    if (numHashes < 1 || numHashes > 64) throw std::invalid_argument("Bad # hashes");      // LSH:75-76
+    if (ratio >= 1.0) {
+      clear(h);
+      return false;
+    }
+    const int features = mals_features(h);
+    std::vector<uint8_t> rv((size_t)numHashes * (size_t)features);
+    for (auto& b : rv) b = random.nextBoolean() ? 1 : 0;
+    build(h, numHashes, maxBitsDiffering(ratio, numHashes), rv);
+    return true;
+  }
+  // randomVectors: [numHashes][features] 0 / 1; mean: features doubles, or nullptr = the mean of Y's rows (on the device)
+  static void build(mals_handle h, int numHashes, int maxBits, const std::vector<uint8_t>& randomVectors, const double* mean = nullptr) {
+    if (randomVectors.size() != (size_t)numHashes * (size_t)mals_features(h)) throw std::invalid_argument("randomVectors: numHashes x features");
+    ok(h, mals_lsh_build(h, numHashes, maxBits, randomVectors.data(), mean));
+  }
+  static void clear(mals_handle h) { ok(h, mals_lsh_clear(h)); }
+  // {num_hashes (0: none), max_bits_differing, rows signed, rows of Y now, queries by the filter path, by the dense path}
+  static std::vector<int64_t> info(mals_handle h) {
+    std::vector<int64_t> out(6);
+    ok(h, mals_lsh_info(h, out.data()));
+    return out;
+  }
+  // the signatures of rows [rowBegin, rowBegin + nRows) as signed at build time; mean (may be nullptr): features doubles
+  static std::vector<uint64_t> get(mals_handle h, int64_t rowBegin, int64_t nRows, std::vector<double>* mean = nullptr) {
+    std::vector<uint64_t> sig((size_t)nRows);
+    if (mean) mean->resize((size_t)mals_features(h));
+    ok(h, mals_lsh_get(h, mean ? mean->data() : nullptr, rowBegin, nRows, sig.data()));
+    return sig;
+  }
+  // toBitSignature (LSH:169-190) of n vectors (n x features)
+  static std::vector<uint64_t> signatures(mals_handle h, const std::vector<float>& vectors) {
+    const size_t n = vectors.size() / (size_t)mals_features(h);
+    std::vector<uint64_t> sig(n);
+    ok(h, mals_lsh_signatures(h, vectors.data(), (int32_t)n, sig.data()));
+    return sig;
+  }
+
+ private:
+  static void ok(mals_handle h, int rc) {
+    if (rc != MALS_OK) throw std::runtime_error(mals_last_error(h));
+  }
+};
+
 // InputFilesReader.readInputFiles (online-local/.../generation/InputFilesReader.java:64-211) on the device: everything
 // the reference leaves behind after reading `inputDir` -- ids, R by user and by item as CSR over dense indices, the two
 // tag id sets, knownItemIDs (absent under model.noKnownItems) -- through mals_ingest_read_dir / _finish.  Throws

@@ -316,8 +316,8 @@ int mals_reconstruction_error(mals_handle h, double* sum_out, int64_t* count_out
  * RecommendIterator.java:93-104) -- bit-identical; the user's known items (the entries of its row of R on this
  * handle) are skipped unless consider_known_items; the how_many best come back best first, equal scores in
  * ascending item index (the reference leaves ties in hash order).  item_idx_out / score_out: n_queries x
- * how_many, padded with -1 / -inf; n_out (may be NULL): results per query.  Rescorers, candidate filters and
- * tags stay with the caller (tag items: pass them as exclusions).  On large item sets a bf16 MFMA pass with a
+ * how_many, padded with -1 / -inf; n_out (may be NULL): results per query.  Rescorers (mals_rescorer_*), the
+ * candidate filter (mals_lsh_*) and tag items (mals_set_tag_items) run on the device too.  On large item sets a bf16 MFMA pass with a
  * proven error margin only narrows the items down to a few hundred candidates per query, whose scores are then
  * computed exactly (csrc/topn_kernels.h); Y is streamed once per up to 240 queries, the passes of a call overlap
  * on six internal streams (ordered after the work already on the handle's stream; the call returns when all have
@@ -409,6 +409,44 @@ int mals_recommend_to_many_rescored(mals_handle h, mals_rescorer r, const float*
 int mals_recommend_to_anonymous_rescored(mals_handle h, mals_rescorer r, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row,
                                          const float* values, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out,
                                          int32_t* status_out);
+
+/* ---- the candidate filter: LocationSensitiveHash on the device ------------------------------------------------
+ * When model.lsh.sampleRatio < 1 the reference's Generation builds a LocationSensitiveHash over Y (online/src/net/myrrix/
+ * online/candidate/LocationSensitiveHash.java:89-152, chosen by CandidateFilterFactory.java:50-71) and multithreadedTopN
+ * (ServerRecommender.java:443-508) only sees the items it returns for the query's vectors.  Built on a handle, every
+ * mals_recommend, mals_recommend_vectors, mals_recommend_to_many, mals_recommend_to_anonymous call and their rescored twins
+ * behave the same way:
+ *   item i is a candidate of a query iff bitCount(sig_i ^ sig(f_j)) <= max_bits_differing for ANY of the query's vectors f_j
+ *   (LSH:193-216), or i is a new item: a row of Y added by mals_grow_factor_rows after the build (addItem, LSH:219-225).
+ * sig = toBitSignature (LSH:169-190): per hash, in order, the fp64 sum over the features, in order, of +-((double)v[f] -
+ * mean[f]); the bit is sum > 0.0; hash 0 is the most significant of the num_hashes bits -- bit-identical to the reference
+ * given the same mean and random vectors.  Signatures are a snapshot: a fold-in write that moves a row of Y does not change
+ * its signature (the reference buckets once per generation).  Everything after candidacy is unchanged (tag, known, excluded
+ * and rescorer-filtered items, the score arithmetic, ties in ascending item index); a query with fewer candidates than
+ * how_many returns fewer results.  mals_most_similar_items, mals_similarity_to_item, mals_recommended_because and
+ * mals_estimate_* never consult the filter (the reference passes none there).
+ *   mals_lsh_max_bits_differing: LSH:98-108 on the host, no device, no handle: sample_ratio in (0, 1], num_hashes in 1..64;
+ *     the result may be -1 (no bucket matches: only new items are candidates).
+ *   mals_lsh_build: random_vectors = [num_hashes][features] bytes 0 / 1 (host), hash-major as the reference draws them
+ *     (LSH:113-119); mean = features doubles (host), or NULL: computed on the device from the rows of Y (the fp64 sum of
+ *     the rows in a fixed order / rows -- the same bits on every run; the reference's own order is its hash map's).  Signs
+ *     every row of Y present now; replaces an earlier build.  An exclusive ticket of the serving front, like
+ *     mals_rescorer_set_*: calls queued before it see the old filter, calls after it the new one.
+ *   mals_lsh_clear: back to every item a candidate.  Declaring Y's rows anew (mals_set_factor_rows / mals_bind_factors on
+ *     side Y) clears the filter too.  Those two calls are no tickets of the serving front: like every call that changes the
+ *     handle's matrices or factors (THREADS, above) they must not run while mals_recommend* or mals_lsh_* calls are in flight.
+ *   mals_lsh_info: out6 = {num_hashes (0: none), max_bits_differing, rows signed at build, rows of Y now, queries answered
+ *     with the filter on by the bf16 filter path, ... by the dense path}.
+ *   mals_lsh_get: the mean (features doubles; may be NULL) and the signatures of rows [row_begin, row_begin + n_rows) of the
+ *     rows signed at build.
+ *   mals_lsh_signatures: toBitSignature of n caller vectors (n x features, host) with the built mean and random vectors.
+ * Not for members of a group: the mals_group_* twins are out of scope. */
+int mals_lsh_max_bits_differing(double sample_ratio, int32_t num_hashes, int32_t* out);
+int mals_lsh_build(mals_handle h, int32_t num_hashes, int32_t max_bits_differing, const uint8_t* random_vectors, const double* mean);
+int mals_lsh_clear(mals_handle h);
+int mals_lsh_info(mals_handle h, int64_t* out6);
+int mals_lsh_get(mals_handle h, double* mean_out, int64_t row_begin, int64_t n_rows, uint64_t* signatures_out);
+int mals_lsh_signatures(mals_handle h, const float* vectors, int32_t n, uint64_t* out);
 
 /* ---- item-to-item similarity on the device ------------------------------------------------------------
  * ServerRecommender.mostSimilarItems (online/src/net/myrrix/online/ServerRecommender.java:1171-1266, scored by

@@ -8,9 +8,11 @@
  *                         reference's own structures are filled from the resulting CSR -- RbyRow, RbyColumn, itemTagIDs,
  *                         userTagIDs, knownItemIDs -- so DelegateGenerationManager keeps working unchanged; a caller that goes
  *                         on to the native factorizer can skip the maps and call install(handle) instead.
- *   recommend(...) /      ServerRecommender.recommend / recommendToMany / recommendToAnonymous without rescorer or candidate
- *   recommendToMany(...)  filter (online/src/net/myrrix/online/ServerRecommender.java:366-508,561-606) for dense user / item
- *                         indices: the scores are the reference's (RecommendIterator.java:93-104) bit for bit.
+ *   recommend(...) /      ServerRecommender.recommend / recommendToMany / recommendToAnonymous
+ *   recommendToMany(...)  (online/src/net/myrrix/online/ServerRecommender.java:366-508,561-606) for dense user / item indices: the
+ *                         scores are the reference's (RecommendIterator.java:93-104) bit for bit; with a NativeIDRescorer as the
+ *                         rescorer, and -- after buildCandidateFilter(handle, features) -- with the reference's candidate filter
+ *                         (LocationSensitiveHash, chosen when model.lsh.sampleRatio < 1) deciding which items a query sees.
  *
  * NOT BUILT IN THIS REPOSITORY'S IMAGE (no JDK); complete source against the reference's public classes, like
  * HipAlternatingLeastSquares.  Same package as InputFilesReader so that the call site at DelegateGenerationManager.java:336
@@ -25,6 +27,9 @@ import java.nio.charset.Charset;
 import net.myrrix.common.collection.FastByIDFloatMap;
 import net.myrrix.common.collection.FastByIDMap;
 import net.myrrix.common.collection.FastIDSet;
+import net.myrrix.common.random.RandomManager;
+
+import org.apache.commons.math3.random.RandomGenerator;
 
 public final class NativeGeneration implements AutoCloseable {
 
@@ -65,6 +70,9 @@ public final class NativeGeneration implements AutoCloseable {
   private static native int nativeRecommendToManyRescored(long handle, long rescorer, float[] vectors, long[] vectorPtr, int nQueries,
                                                           int howMany, long[] excludePtr, long[] excludeIdx, long[] items, float[] scores,
                                                           int[] counts);
+  private static native int nativeLshMaxBitsDiffering(long ratioBits, int numHashes, int[] out);
+  private static native int nativeLshBuild(long handle, int numHashes, int maxBitsDiffering, int[] randomVectors, long[] meanBits);
+  private static native int nativeLshClear(long handle);
   private static native String nativeLastError(long handle);
 
   /** The reference's own six arguments (InputFilesReader.java:64-69; call site DelegateGenerationManager.java:336): a switch by
@@ -249,6 +257,48 @@ public final class NativeGeneration implements AutoCloseable {
     }
     checkHandle(handle, nativeRecommendToManyRescored(handle, rescorer.nativeRescorer(handle), vectors, vectorPtr, nQueries, howMany, excludePtr,
                                                       excludeIdx, items, scores, counts));
+  }
+
+  /** What Generation does when model.lsh.sampleRatio < 1 (CandidateFilterFactory.java:50-71 -> new LocationSensitiveHash(Y),
+   *  LocationSensitiveHash.java:89-152), on the device: maxBitsDiffering from model.lsh.sampleRatio and model.lsh.numHashes
+   *  (LSH:98-108), the random vectors drawn hash-major from RandomManager.getRandom().nextBoolean() as LSH:113-119 draws them,
+   *  the mean of Y and one signature per row of Y computed on the device.  From then on recommend / recommendToMany on this
+   *  handle only see a query's candidates (LSH:193-216).  Items that setPreference creates later are rows grown with
+   *  mals_grow_factor_rows (the write path does that): they are always candidates, like the reference's newItems (LSH:219-225).
+   *  With model.lsh.sampleRatio >= 1 (the default) no filter is built and an earlier one is cleared.  Returns true if one
+   *  was built. */
+  public static boolean buildCandidateFilter(long handle, int features) {
+    double sampleRatio = Double.parseDouble(System.getProperty("model.lsh.sampleRatio", "1.0"));   // LSH:70
+    int numHashes = Integer.parseInt(System.getProperty("model.lsh.numHashes", "20"));             // LSH:71
+    if (!(sampleRatio > 0.0 && sampleRatio <= 1.0)) {
+      throw new IllegalArgumentException("Bad LSH ratio: " + sampleRatio);                          // LSH:73-74
+    }
+    if (numHashes < 1 || numHashes > 64) {
+      throw new IllegalArgumentException("Bad # hashes: " + numHashes);                             // LSH:75-76
+    }
+    if (sampleRatio >= 1.0) {
+      checkHandle(handle, nativeLshClear(handle));
+      return false;
+    }
+    if (features < 1) {
+      throw new IllegalArgumentException("features must be positive");
+    }
+    int[] maxBits = new int[1];
+    checkHandle(handle, nativeLshMaxBitsDiffering(Double.doubleToRawLongBits(sampleRatio), numHashes, maxBits));
+    RandomGenerator random = RandomManager.getRandom();
+    int[] randomVectors = new int[numHashes * features];
+    for (int h = 0; h < numHashes; h++) {
+      for (int j = 0; j < features; j++) {
+        randomVectors[h * features + j] = random.nextBoolean() ? 1 : 0;
+      }
+    }
+    checkHandle(handle, nativeLshBuild(handle, numHashes, maxBits[0], randomVectors, null));
+    return true;
+  }
+
+  /** Back to every item a candidate. */
+  public static void clearCandidateFilter(long handle) {
+    checkHandle(handle, nativeLshClear(handle));
   }
 
   // NativeIDRescorer's way to its device object

@@ -3,7 +3,8 @@
  *   * input files -> matrices (InputFilesReader.readInputFiles, online-local/src/net/myrrix/online/generation/
  *     InputFilesReader.java:64-211)          -> mals_ingest_* (read_dir / finish / counts / ids / CSR / tags / known items)
  *   * top-N scoring (ServerRecommender.recommend / recommendToMany / recommendToAnonymous,
- *     online/src/net/myrrix/online/ServerRecommender.java:366-508,561-606) -> mals_recommend, _to_many, _set_known_items
+ *     online/src/net/myrrix/online/ServerRecommender.java:366-508,561-606) -> mals_recommend, _to_many, _set_known_items,
+ *     with the candidate filter of model.lsh.sampleRatio < 1 (LocationSensitiveHash.java) -> mals_lsh_build / _clear
  * bound by net.myrrix.online.generation.NativeGeneration (java/net/myrrix/online/generation/NativeGeneration.java).  The
  * reference has no FFI on these paths either; this is the binding a maintainer adds.
  *
@@ -420,6 +421,59 @@ JNIEXPORT jint JNICALL JNI_FN(nativeRecommendToManyRescored)(JNIEnv* env, jclass
   if (vp) (*env)->ReleaseLongArrayElements(env, vector_ptr, vp, JNI_ABORT);
   if (v) (*env)->ReleaseFloatArrayElements(env, vectors, v, JNI_ABORT);
   return rc;
+}
+
+/* ---- the candidate filter (include/myrrix_als.h, mals_lsh_*): LocationSensitiveHash.java on the device ---- */
+
+/* maxBitsDiffering (LocationSensitiveHash.java:98-108) for model.lsh.sampleRatio (its raw fp64 bits) and model.lsh.numHashes
+ * into out[0] */
+JNIEXPORT jint JNICALL JNI_FN(nativeLshMaxBitsDiffering)(JNIEnv* env, jclass cls, jlong ratio_bits, jint num_hashes, jintArray out) {
+  (void)cls;
+  if (!out || (*env)->GetArrayLength(env, out) < 1) return MALS_INVALID_ARG;
+  double ratio;
+  memcpy(&ratio, &ratio_bits, sizeof(double));
+  int32_t mb = 0;
+  const int rc = mals_lsh_max_bits_differing(ratio, (int32_t)num_hashes, &mb);
+  if (rc != MALS_OK) return rc;
+  const jint v = (jint)mb;
+  (*env)->SetIntArrayRegion(env, out, 0, 1, &v);
+  return MALS_OK;
+}
+
+/* random_vectors: numHashes x features entries, 0 / 1, hash-major (LocationSensitiveHash.java:113-119); mean_bits: features
+ * fp64 bit patterns, or null = the mean of Y's rows, computed on the device.  The lengths are checked before an element is
+ * read. */
+JNIEXPORT jint JNICALL JNI_FN(nativeLshBuild)(JNIEnv* env, jclass cls, jlong handle, jint num_hashes, jint max_bits_differing,
+                                             jintArray random_vectors, jlongArray mean_bits) {
+  (void)cls;
+  if (!handle || !random_vectors || num_hashes < 1 || num_hashes > 64) return MALS_INVALID_ARG;
+  const int64_t features = (int64_t)mals_features(as_handle(handle));
+  if (features <= 0 || (int64_t)(*env)->GetArrayLength(env, random_vectors) < (int64_t)num_hashes * features ||
+      (mean_bits && (int64_t)(*env)->GetArrayLength(env, mean_bits) < features))
+    return MALS_INVALID_ARG;
+  const size_t n = (size_t)num_hashes * (size_t)features;
+  jint* rv = (*env)->GetIntArrayElements(env, random_vectors, NULL);
+  jlong* mb = mean_bits ? (*env)->GetLongArrayElements(env, mean_bits, NULL) : NULL;
+  uint8_t* bytes = (uint8_t*)malloc(n);
+  double* mean = mean_bits ? (double*)malloc(sizeof(double) * (size_t)features) : NULL;
+  int rc = MALS_OOM;
+  if (rv && bytes && (mb || !mean_bits) && (mean || !mean_bits)) {
+    for (size_t i = 0; i < n; ++i) bytes[i] = rv[i] ? 1 : 0;
+    if (mean) memcpy(mean, mb, sizeof(double) * (size_t)features);
+    rc = mals_lsh_build(as_handle(handle), (int32_t)num_hashes, (int32_t)max_bits_differing, bytes, mean);
+  }
+  free(mean);
+  free(bytes);
+  if (mb) (*env)->ReleaseLongArrayElements(env, mean_bits, mb, JNI_ABORT);
+  if (rv) (*env)->ReleaseIntArrayElements(env, random_vectors, rv, JNI_ABORT);
+  return rc;
+}
+
+JNIEXPORT jint JNICALL JNI_FN(nativeLshClear)(JNIEnv* env, jclass cls, jlong handle) {
+  (void)env;
+  (void)cls;
+  if (!handle) return MALS_INVALID_ARG;
+  return mals_lsh_clear(as_handle(handle));
 }
 
 JNIEXPORT jstring JNICALL JNI_FN(nativeLastError)(JNIEnv* env, jclass cls, jlong handle) {

@@ -173,6 +173,12 @@ SYMBOLS = {
     "mals_recommend_rescored": (ctypes.c_int, [_H, _H, _P, _I32, _I32, _I32, _P, _P, _P]),
     "mals_recommend_to_many_rescored": (ctypes.c_int, [_H, _H, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     "mals_recommend_to_anonymous_rescored": (ctypes.c_int, [_H, _H, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "mals_lsh_max_bits_differing": (ctypes.c_int, [ctypes.c_double, _I32, ctypes.POINTER(_I32)]),
+    "mals_lsh_build": (ctypes.c_int, [_H, _I32, _I32, _P, _P]),
+    "mals_lsh_clear": (ctypes.c_int, [_H]),
+    "mals_lsh_info": (ctypes.c_int, [_H, _P]),
+    "mals_lsh_get": (ctypes.c_int, [_H, _P, _I64, _I64, _P]),
+    "mals_lsh_signatures": (ctypes.c_int, [_H, _P, _I32, _P]),
     "mals_estimate_for_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P, _P]),
     "mals_set_tag_items": (ctypes.c_int, [_H, _I64, _P, ctypes.c_int]),
     "mals_get_tag_item_count": (ctypes.c_int, [_H, ctypes.POINTER(_I64)]),

@@ -112,6 +112,16 @@ def _item_queries(items):
     return flat, ptr
 
 
+def lsh_max_bits_differing(sample_ratio, num_hashes=20):
+    """maxBitsDiffering of LocationSensitiveHash (LocationSensitiveHash.java:98-108) for model.lsh.sampleRatio and
+    model.lsh.numHashes; may be -1.  Host only: no handle, no device."""
+    out = ctypes.c_int32(0)
+    rc = _lib.load().mals_lsh_max_bits_differing(float(sample_ratio), int(num_hashes), ctypes.byref(out))
+    if rc != _lib.OK:
+        raise MalsError(rc, "lsh_max_bits_differing: sample_ratio in (0, 1], num_hashes in 1..64")
+    return out.value
+
+
 class Rescorer:
     """RecommendIterator's IDRescorer in the form the device runs (include/myrrix_als.h, "rescorers"): a filter set of
     item indices and rescore(i, sum) = fl(fl(scale_i * sum) + offset_i) in fp64, applied to the sum of the dots before the
@@ -427,6 +437,61 @@ class ALSCore:
                                                               int(how_many), ep, ei, idx.ctypes.data_as(ctypes.c_void_p),
                                                               sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
         return idx, sc, cnt
+
+    def lsh_build(self, num_hashes=20, sample_ratio=None, max_bits_differing=None, random_vectors=None, mean=None, seed=None):
+        """Build the reference's candidate filter (LocationSensitiveHash.java:89-152) over the rows of Y: from then on every
+        recommend call only sees a query's LSH candidates and the rows of Y grown later.  sample_ratio
+        (model.lsh.sampleRatio) or max_bits_differing sets the threshold; random_vectors: [num_hashes][features] booleans
+        (None: drawn hash-major with random_mt.MersenneTwister(seed).nextBoolean(), as LSH:113-119 draws them from
+        RandomManager.getRandom()); mean: features doubles (None: the mean of Y's rows, computed on the device).  Returns
+        the random vectors used."""
+        from . import random_mt
+        H = int(num_hashes)
+        if max_bits_differing is None:
+            if sample_ratio is None:
+                raise ValueError("lsh_build: give sample_ratio or max_bits_differing")
+            max_bits_differing = lsh_max_bits_differing(sample_ratio, H)
+        if random_vectors is None:
+            rng = random_mt.MersenneTwister(seed)
+            random_vectors = np.array([[rng.nextBoolean() for _ in range(self.features)] for _ in range(H)], dtype=bool).reshape(H, self.features)
+        rv = np.ascontiguousarray(np.asarray(random_vectors, dtype=bool).astype(np.uint8))
+        if rv.shape != (H, self.features):
+            raise ValueError("lsh_build: random_vectors must be [num_hashes][features], got %s" % (rv.shape,))
+        m = None if mean is None else _host(mean, np.float64)
+        if m is not None and m.shape != (self.features,):
+            raise ValueError("lsh_build: mean must hold features doubles")
+        self._chk(self._L.mals_lsh_build(self._h, H, int(max_bits_differing), rv.ctypes.data_as(ctypes.c_void_p),
+                                         m.ctypes.data_as(ctypes.c_void_p) if m is not None else None))
+        return rv.astype(bool)
+
+    def lsh_clear(self):
+        """Back to every item a candidate."""
+        self._chk(self._L.mals_lsh_clear(self._h))
+
+    def lsh_info(self):
+        o = np.zeros(6, dtype=np.int64)
+        self._chk(self._L.mals_lsh_info(self._h, o.ctypes.data_as(ctypes.c_void_p)))
+        return {"num_hashes": int(o[0]), "max_bits_differing": int(o[1]), "rows_signed": int(o[2]), "rows_now": int(o[3]),
+                "filter_queries": int(o[4]), "dense_queries": int(o[5])}
+
+    def lsh_get(self, row_begin=0, n_rows=None):
+        """(mean float64 [features], signatures uint64 [n_rows]) of the built filter: rows [row_begin, row_begin + n_rows)
+        of the rows signed at build time (None: all from row_begin)."""
+        if n_rows is None:
+            n_rows = self.lsh_info()["rows_signed"] - int(row_begin)
+        mean = np.empty(self.features, dtype=np.float64)
+        sig = np.empty(int(n_rows), dtype=np.uint64)
+        self._chk(self._L.mals_lsh_get(self._h, mean.ctypes.data_as(ctypes.c_void_p), int(row_begin), int(n_rows),
+                                       sig.ctypes.data_as(ctypes.c_void_p) if n_rows else None))
+        return mean, sig
+
+    def lsh_signatures(self, vectors):
+        """toBitSignature (LocationSensitiveHash.java:169-190) of caller vectors with the built mean and random vectors."""
+        v = _host(vectors, np.float32)
+        assert v.ndim == 2 and v.shape[1] == self.features
+        out = np.empty(len(v), dtype=np.uint64)
+        self._chk(self._L.mals_lsh_signatures(self._h, v.ctypes.data_as(ctypes.c_void_p), len(v), out.ctypes.data_as(ctypes.c_void_p) if len(v) else None))
+        return out
 
     def set_known_items(self, row_ptr, item_idx):
         """knownItemIDs as a CSR over the local user rows (generation.getKnownItemIDs()); None, None: back to the rows of R."""

@@ -109,6 +109,27 @@ struct SideState {
   uint64_t F_epoch = 0;    // bumped whenever the library itself writes the replica (uploads, solves, rebinding)
 };
 
+// the candidate filter of mals_recommend* (mals_lsh_build; kernels in lsh_kernels.h): LocationSensitiveHash.java as built
+// for one generation -- the signatures are a snapshot of Y at build time (the reference buckets once per generation)
+struct LshState {
+  int H = 0;              // num_hashes; 0: no filter, every item a candidate
+  int mb = 0;             // maxBitsDiffering (may be -1)
+  int64_t n_signed = 0;   // rows of Y signed at build time; later rows (mals_grow_factor_rows) are new items: always candidates
+  DeviceBuffer<uint64_t> d_sig;    // [n_signed]
+  DeviceBuffer<uint64_t> d_mask;   // [features]: bit h = randomVectors[h][f]
+  DeviceBuffer<double> d_mean;     // [features]
+  // queries answered with the filter on, by the bf16 filter path / by the dense path (mals_lsh_info)
+  std::atomic<int64_t> q_filter{0}, q_dense{0};
+  void clear() {
+    H = 0;
+    mb = 0;
+    n_signed = 0;
+    d_sig.reset();
+    d_mask.reset();
+    d_mean.reset();
+  }
+};
+
 struct PendingEvent {
   hipEvent_t a, b;
   int kind;  // 0 = rows, 1 = segments, 2 = finish, 3 = gramian, 4 = dual, 5 = rotate
@@ -225,6 +246,7 @@ struct mals_handle_s {
   DeviceBuffer<int64_t> d_sd_idx;
   DeviceBuffer<int64_t> d_idx;  // gather scratch
   DeviceBuffer<float> d_rows;
+  LshState lsh;                 // the candidate filter of mals_recommend* (mals_lsh_build)
   void* fo = nullptr;           // the online write path (foldin_host.h): device solvers, known-item overlay, levels
   bool group_member = false;    // a member of a mals_group (malsi_mark_group_member): the write path refuses it
   // mals_foldin_stats: applied, failed, large fold-ins, levels, device ns (all calls), device ns (last call) -- atomics,
@@ -1673,6 +1695,7 @@ int mals_set_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
   s.G_valid = false;
   ++s.F_epoch;
   if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
+  if (side == MALS_SIDE_Y) h->lsh.clear();                 // ... and its rows are not the ones the candidate filter signed
   return MALS_OK;
 }
 
@@ -1687,6 +1710,7 @@ int mals_bind_factors(mals_handle h, int side, float* device_ptr, int64_t n_rows
   s.G_valid = false;
   ++s.F_epoch;
   if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
+  if (side == MALS_SIDE_Y) h->lsh.clear();
   return MALS_OK;
 }
 
@@ -3515,4 +3539,164 @@ int mals_recommend_to_anonymous_rescored(mals_handle h, mals_rescorer r, int32_t
                                          const float* values, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out,
                                          int32_t* status_out) {
   return topn_anonymous_impl(h, r, n_queries, item_ptr, item_row, values, how_many, item_idx_out, score_out, n_out, status_out);
+}
+
+// ---- the candidate filter: LocationSensitiveHash on the device (lsh_kernels.h) --------------------------------------------
+// LSH:98-108: accumulate C(H, b) / 2^H for b = 0, 1, ... while b < H and the sum is below the ratio; the last b minus 1.
+// ArithmeticUtils.binomialCoefficientDouble is the exact binomial for n <= 66, rounded once to fp64.
+int mals_lsh_max_bits_differing(double sample_ratio, int32_t num_hashes, int32_t* out) {
+  if (!out || num_hashes < 1 || num_hashes > 64 || !(sample_ratio > 0.0 && sample_ratio <= 1.0)) return MALS_INVALID_ARG;
+  double cumulative = 0.0;
+  const double denominator = std::ldexp(1.0, num_hashes);
+  int bits = -1;
+  unsigned __int128 binom = 1;   // C(H, 0)
+  while (bits < num_hashes && cumulative < sample_ratio) {
+    ++bits;
+    if (bits > 0) binom = binom * (unsigned __int128)(num_hashes - bits + 1) / (unsigned __int128)bits;
+    cumulative += (double)(uint64_t)binom / denominator;   // (C(64, 32) < 2^61)
+  }
+  *out = bits - 1;
+  return MALS_OK;
+}
+
+namespace {
+// the device side of a build (an exclusive ticket: nothing else is on the handle's stream, no pass is in flight)
+int lsh_build_run(mals_handle h, int H, int mb, const uint8_t* rv, const double* mean, std::string& msg) {
+  SideState& y = h->side[MALS_SIDE_Y];
+  const int k = h->cfg.features;
+  if (!y.F || y.n_total <= 0) {
+    msg = "the item factor replica comes first (mals_set_factor_rows)";
+    return MALS_INVALID_ARG;
+  }
+  const int64_t n = y.n_total;
+  std::vector<uint64_t> mask((size_t)k, 0ull);
+  for (int hh = 0; hh < H; ++hh)
+    for (int f = 0; f < k; ++f)
+      if (rv[(size_t)hh * k + f]) mask[(size_t)f] |= 1ull << hh;
+  LshState nl;
+  FCHK(msg, nl.d_mask.alloc((size_t)k));
+  FCHK(msg, nl.d_mean.alloc((size_t)k));
+  FCHK(msg, nl.d_sig.alloc((size_t)n));
+  FCHK(msg, hipMemcpyAsync(nl.d_mask.get(), mask.data(), sizeof(uint64_t) * (size_t)k, hipMemcpyHostToDevice, h->stream));
+  DeviceBuffer<double> part;
+  if (mean) {
+    FCHK(msg, hipMemcpyAsync(nl.d_mean.get(), mean, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, h->stream));
+  } else {   // LSH:154-167, in a fixed order
+    const int n_part = LSH_MEAN_BLOCKS * lsh_mean_slots(k);
+    FCHK(msg, part.alloc((size_t)n_part * (size_t)k));
+    hipLaunchKernelGGL(lsh_mean_partial_kernel, dim3(LSH_MEAN_BLOCKS), dim3(256), 0, h->stream, y.F, n, k, part.get());
+    hipLaunchKernelGGL(lsh_mean_final_kernel, dim3(1), dim3(128), 0, h->stream, part.get(), n_part, k, n, nl.d_mean.get());
+  }
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, (int64_t)h->n_cu * 4));
+  const size_t lds = sizeof(float) * 64 * (size_t)(k + 1);
+  const int nh = (H + 3) / 4;
+  if (nh <= 5)
+    hipLaunchKernelGGL(lsh_sign_rows_kernel<5>, dim3(grid), dim3(256), lds, h->stream, y.F, n, k, nl.d_mean.get(), nl.d_mask.get(), H, nl.d_sig.get());
+  else if (nh <= 9)
+    hipLaunchKernelGGL(lsh_sign_rows_kernel<9>, dim3(grid), dim3(256), lds, h->stream, y.F, n, k, nl.d_mean.get(), nl.d_mask.get(), H, nl.d_sig.get());
+  else
+    hipLaunchKernelGGL(lsh_sign_rows_kernel<16>, dim3(grid), dim3(256), lds, h->stream, y.F, n, k, nl.d_mean.get(), nl.d_mask.get(), H, nl.d_sig.get());
+  FCHK(msg, hipGetLastError());
+  FCHK(msg, hipStreamSynchronize(h->stream));   // (the host's mask and the caller's mean are read until here)
+  LshState& l = h->lsh;
+  std::lock_guard<std::mutex> lk(topn_front(h)->mu);   // (mals_lsh_info reads under it)
+  l.d_sig = std::move(nl.d_sig);
+  l.d_mask = std::move(nl.d_mask);
+  l.d_mean = std::move(nl.d_mean);
+  l.H = H;
+  l.mb = mb;
+  l.n_signed = n;
+  return MALS_OK;
+}
+}  // namespace
+
+int mals_lsh_build(mals_handle h, int32_t num_hashes, int32_t max_bits_differing, const uint8_t* random_vectors, const double* mean) {
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, "mals_lsh_build")) return rc;
+  if (num_hashes < 1 || num_hashes > 64) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_build: num_hashes in 1..64 (LocationSensitiveHash.java:75)");
+  if (max_bits_differing < -1 || max_bits_differing > num_hashes) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_build: max_bits_differing in -1..num_hashes");
+  if (!random_vectors) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_build: random_vectors is NULL");
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int { return lsh_build_run(h, num_hashes, max_bits_differing, random_vectors, mean, msg); };
+  return foldin_exclusive(h, fn, msg, "mals_lsh_build");
+}
+
+int mals_lsh_clear(mals_handle h) {
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, "mals_lsh_clear")) return rc;
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    FCHK(msg, hipStreamSynchronize(h->stream));
+    std::lock_guard<std::mutex> lk(topn_front(h)->mu);
+    h->lsh.clear();
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_lsh_clear");
+}
+
+// a read of a few words under the front's mutex: no ticket, the serving front is not drained for a statistics query (and
+// a member of a group answers too: it has no filter)
+int mals_lsh_info(mals_handle h, int64_t* out6) {
+  if (!h || !out6) return MALS_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(topn_front(h)->mu);
+  const LshState& l = h->lsh;
+  out6[0] = l.H;
+  out6[1] = l.mb;
+  out6[2] = l.n_signed;
+  out6[3] = h->side[MALS_SIDE_Y].n_total;
+  out6[4] = l.q_filter.load();
+  out6[5] = l.q_dense.load();
+  return MALS_OK;
+}
+
+int mals_lsh_get(mals_handle h, double* mean_out, int64_t row_begin, int64_t n_rows, uint64_t* signatures_out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, "mals_lsh_get")) return rc;
+  if (n_rows < 0 || row_begin < 0 || (n_rows > 0 && !signatures_out)) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_get: bad arguments");
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    const LshState& l = h->lsh;
+    if (l.H == 0) {
+      msg = "no candidate filter is built (mals_lsh_build)";
+      return MALS_INVALID_ARG;
+    }
+    if (row_begin + n_rows > l.n_signed) {
+      msg = "rows outside the rows signed at build time";
+      return MALS_INVALID_ARG;
+    }
+    if (mean_out) FCHK(msg, hipMemcpyAsync(mean_out, l.d_mean.get(), sizeof(double) * (size_t)h->cfg.features, hipMemcpyDeviceToHost, h->stream));
+    if (n_rows > 0)
+      FCHK(msg, hipMemcpyAsync(signatures_out, l.d_sig.get() + row_begin, sizeof(uint64_t) * (size_t)n_rows, hipMemcpyDeviceToHost, h->stream));
+    FCHK(msg, hipStreamSynchronize(h->stream));
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_lsh_get");
+}
+
+int mals_lsh_signatures(mals_handle h, const float* vectors, int32_t n, uint64_t* out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, "mals_lsh_signatures")) return rc;
+  if (n < 0 || (n > 0 && (!vectors || !out))) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_signatures: bad arguments");
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    const LshState& l = h->lsh;
+    if (l.H == 0) {
+      msg = "no candidate filter is built (mals_lsh_build)";
+      return MALS_INVALID_ARG;
+    }
+    if (n == 0) return MALS_OK;
+    const int k = h->cfg.features;
+    DeviceBuffer<float> d_v;
+    DeviceBuffer<uint64_t> d_s;
+    FCHK(msg, d_v.alloc((size_t)n * (size_t)k));
+    FCHK(msg, d_s.alloc((size_t)n));
+    FCHK(msg, hipMemcpyAsync(d_v.get(), vectors, sizeof(float) * (size_t)n * (size_t)k, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(lsh_sign_vectors_kernel, dim3((unsigned)n), dim3(64), 0, h->stream, d_v.get(), nullptr, (int)n, k, l.d_mean.get(), l.d_mask.get(), l.H,
+                       d_s.get(), nullptr, TopnLsh());
+    FCHK(msg, hipGetLastError());
+    FCHK(msg, hipMemcpyAsync(out, d_s.get(), sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    FCHK(msg, hipStreamSynchronize(h->stream));
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_lsh_signatures");
 }

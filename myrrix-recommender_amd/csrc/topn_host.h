@@ -32,6 +32,7 @@ struct TopnSlot {
   DeviceBuffer<uint2> d_whits;        // [n_waves][TOPN_WAVE_CAP] (item, query)
   DeviceBuffer<double> d_qn;          // cosine mode: the exact norms of the pass's query vectors ...
   DeviceBuffer<uint32_t> d_qflag;     // ... and per query 0 / 1 (answered empty) / 2 (dense path), topn_prepare_kernel<true>
+  DeviceBuffer<uint64_t> d_vsig;      // candidate filter: the bit signatures of the pass's query vectors (lsh_sign_vectors_kernel)
   PinnedBuffer<uint8_t> h_stage;      // the pass's results, [nq][how_many] pairs | counts | taus | overflow word (topn_final_kernel
                                       // writes them there), decoded while later passes run
 };
@@ -225,6 +226,30 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
   return MALS_OK;
 }
 
+// ---- the candidate filter (mals_lsh_build; lsh_kernels.h) ---------------------------------------------------------------
+// mals_recommend* and their rescored twins consult it (ServerRecommender.java:431-436, :555); mostSimilarItems,
+// similarityToItem and recommendedBecause never do (the reference passes no candidate filter there).  A build is an exclusive
+// ticket of the front: no pass is in flight while the state changes, so a pass reads it as it is when it is enqueued.
+bool topn_lsh_on(mals_handle h, const TopnRequest& rq) { return h->lsh.H > 0 && rq.kind == TOPN_KIND_SCORE && !rq.cosine; }
+
+// toBitSignature (LSH:169-190) of the pass's query vectors where they already are on the device -- rows of X, the uploaded
+// block -- on `st`, no host round trip; *view = what the pass's kernels read of the filter.  img: the pass's query image (the
+// streaming kernels find the view behind it), NULL for the dense path.
+int topn_lsh_sign_pass(mals_handle h, TopnSlot& sl, hipStream_t st, const TopnPass& ps, bf16x8* img, TopnLsh* view) {
+  LshState& l = h->lsh;
+  HIPCHK(h, sl.d_vsig.reserve((size_t)std::max<int64_t>(ps.n_vecs, 1), st));
+  view->isig = l.d_sig.get();
+  view->n_signed = l.n_signed;
+  view->vsig = sl.d_vsig.get();
+  view->vptr = sl.d_vptr;
+  view->mb = l.mb;
+  hipLaunchKernelGGL(lsh_sign_vectors_kernel, dim3((unsigned)std::max<int64_t>(ps.n_vecs, 1)), dim3(64), 0, st, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs,
+                     h->cfg.features, l.d_mean.get(), l.d_mask.get(), l.H, sl.d_vsig.get(),
+                     img ? reinterpret_cast<TopnLsh*>(img + TOPN_IMG_LSH_AT) : nullptr, *view);
+  HIPCHK(h, hipGetLastError());
+  return MALS_OK;
+}
+
 // ---- dense path: exact scores of every item (on the caller's stream, with slot 0's input block; nothing else of the
 // workspace is in flight when it runs) -------------------------------------------------------------------------------
 int topn_select_threshold(mals_handle h, const float* d_scores, int64_t n_row, int nq, int how_many, TopnState* d_st, unsigned* d_hist,
@@ -274,6 +299,13 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
   if (h->tag_bits)
     hipLaunchKernelGGL(topn_mask_tags_kernel, dim3((unsigned)(((n_items + 31) / 32 + 255) / 256)), dim3(256), 0, h->stream, h->tag_bits.get(), nq, n_items,
                        w->d_scores.get());
+  if (topn_lsh_on(h, rq)) {   // the non-candidates of every query (LSH:193-216)
+    TopnLsh lv;
+    if (int rc = topn_lsh_sign_pass(h, sl, h->stream, ps, nullptr, &lv)) return rc;
+    hipLaunchKernelGGL(lsh_mask_dense_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_items + 255) / 256, 1024)), (unsigned)nq), dim3(256), 0,
+                       h->stream, lv, nq, n_items, w->d_scores.get());
+    h->lsh.q_dense.fetch_add(nq);
+  }
   unsigned slabs = 1;
   if (int rc = topn_select_threshold(h, w->d_scores.get(), n_items, nq, how_many, w->d_state.get(), w->d_hist.get(), &slabs)) return rc;
   hipLaunchKernelGGL(topn_collect_kernel, dim3(slabs, (unsigned)nq), dim3(256), 0, h->stream, w->d_scores.get(), n_items, w->d_state.get(), how_many, cap_ties,
@@ -324,7 +356,7 @@ constexpr int TOPN_WAVE_CAP = 2048;  // hits a wave of the filter kernel can rec
 // topn_stream_kernel: QT = query tiles per wave, 4 QT per workgroup.  MODE 0: *n_out = workgroups of the sample (16
 // buckets each); MODE 1: *n_out = waves of the filter (one hit list each).
 // RS: the rescored instantiations (the rescorer's per-item data: behind the query image, topn_prepare_kernel<false, true>)
-template <int S, int QT, int MODE, bool COS, bool RS = false>
+template <int S, int QT, int MODE, bool COS, bool RS = false, bool LSH = false>
 int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
   const int64_t tiles = (n_items + 16 * (int64_t)tile_stride - 1) / (16 * (int64_t)tile_stride);
   const int64_t stages = (tiles + 3) / 4;
@@ -335,16 +367,10 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   if (!per_cu_cached) {
     int nb = 0;
     hipError_t e;
-    if (RS)
-      e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1, false, true>, 256, 0)
-          : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2, false, true>, 256, 0)
-          : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3, false, true>, 256, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0, false, true>, 256, 0);
-    else
-      e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1, COS>, 256, 0)
-          : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2, COS>, 256, 0)
-          : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3, COS>, 256, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0, COS>, 256, 0);
+    e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1, COS, RS, LSH>, 256, 0)
+        : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2, COS, RS, LSH>, 256, 0)
+        : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3, COS, RS, LSH>, 256, 0)
+                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0, COS, RS, LSH>, 256, 0);
     per_cu_cached = (e == hipSuccess && nb > 0) ? std::min(nb, 6) : 2;
   }
   int per_cu = per_cu_cached;
@@ -365,7 +391,7 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
     *n_out = (int)grid;
   }
 #define MALS_TOPN_GO(LM)                                                                                                              \
-  hipLaunchKernelGGL((topn_stream_kernel<S, QT, MODE, LM, COS, RS>), dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k,                       \
+  hipLaunchKernelGGL((topn_stream_kernel<S, QT, MODE, LM, COS, RS, LSH>), dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k,                       \
                      sl.d_img.get(), nq, tile_stride, sl.d_bmax.get(), sl.d_bidx.get(), sl.d_tau.get(), TOPN_WAVE_CAP, sl.d_wcount.get(),   \
                      sl.d_whits.get(), cap, sl.d_count.get(), sl.d_cand.get(), sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE)
   if (lm == 1) MALS_TOPN_GO(1);
@@ -376,10 +402,10 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
 }
-template <int MODE, bool COS, bool RS = false>
+template <int MODE, bool COS, bool RS = false, bool LSH = false>
 int topn_launch_stream(mals_handle h, TopnSlot& sl, int S, int nt, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
   const int qt = (nt + 3) / 4;
-#define MALS_TOPN_STREAM(SS, QQ) return topn_launch_stream_QT<SS, QQ, MODE, COS, RS>(h, sl, Y, n_items, k, nq, tile_stride, cap, n_out)
+#define MALS_TOPN_STREAM(SS, QQ) return topn_launch_stream_QT<SS, QQ, MODE, COS, RS, LSH>(h, sl, Y, n_items, k, nq, tile_stride, cap, n_out)
   switch (S) {
     case 1:
       if (qt <= 1) MALS_TOPN_STREAM(1, 1);
@@ -453,20 +479,31 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
     hipLaunchKernelGGL(topn_prepare_kernel<false>, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
                        sl.d_img.get(), sl.d_count.get(), d_overflow, nullptr, nullptr, TopnImgTrailer());
   }
+  // the candidate filter: the signatures of the pass's vectors, and the pass's view of the filter behind the query image
+  const bool lsh = topn_lsh_on(h, rq);
+  TopnLsh lv;
+  if (lsh)
+    if (int rc = topn_lsh_sign_pass(h, sl, st, ps, sl.d_img.get(), &lv)) return rc;
   // 1. sample: bucket maxima of the lower bounds of every tile_stride-th tile; 2. threshold (buckets won by known items dropped)
   int n_groups = 0, n_fw = 0;
-  if (int rc = cos     ? topn_launch_stream<0, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
-               : rq.rs ? topn_launch_stream<0, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
-                       : topn_launch_stream<0, false>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups))
+  if (int rc = cos            ? topn_launch_stream<0, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
+               : rq.rs && lsh ? topn_launch_stream<0, false, true, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
+               : rq.rs        ? topn_launch_stream<0, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
+               : lsh          ? topn_launch_stream<0, false, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
+                              : topn_launch_stream<0, false>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups))
     return rc;
+  if (lsh)   // buckets won by non-candidates of the queries of several vectors
+    hipLaunchKernelGGL(lsh_drop_buckets_kernel, dim3(8, (unsigned)nq), dim3(256), 0, st, lv, 16 * (int64_t)n_groups, sl.d_bmax.get(), sl.d_bidx.get());
   hipLaunchKernelGGL(topn_threshold_kernel, dim3((unsigned)nq), dim3(1024), 0, st, sl.d_bmax.get(), sl.d_bidx.get(), n_groups, how_many, k_ptr, k_idx, d_rows,
                      d_eptr, d_eidx, n_items, p.tile_stride, h->tag_bits.get(), sl.d_tau.get(), cos ? sl.d_qflag.get() : nullptr);
   // 3. filter, 4. exact scores of the hits (known items dropped), 5. the N best -- written straight into the slot's pinned
   // block (device-visible host memory: no copy kernel, no copy call)
   // (the filter's waves scatter their own hits into the per-query candidate lists: no kernel in between)
-  if (int rc = cos     ? topn_launch_stream<1, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
-               : rq.rs ? topn_launch_stream<1, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
-                       : topn_launch_stream<1, false>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw))
+  if (int rc = cos            ? topn_launch_stream<1, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
+               : rq.rs && lsh ? topn_launch_stream<1, false, true, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
+               : rq.rs        ? topn_launch_stream<1, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
+               : lsh          ? topn_launch_stream<1, false, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
+                              : topn_launch_stream<1, false>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw))
     return rc;
   if (cos)
     hipLaunchKernelGGL(topn_rescore_kernel<true>, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr,
@@ -480,6 +517,9 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
     hipLaunchKernelGGL(topn_rescore_kernel<false>, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr,
                        sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow,
                        nullptr, n_items, TopnRescore());
+  if (lsh)   // whatever the streaming tests let through
+    hipLaunchKernelGGL(lsh_strike_pairs_kernel, dim3(2, (unsigned)nq), dim3(256), 0, st, lv, sl.d_count.get(), TOPN_COUNT_STRIDE, p.cap, sl.d_cand.get(),
+                       sl.d_pairs.get());
   uint8_t* o = sl.h_stage.get();
   const size_t o_cnt = sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many, o_tau = o_cnt + sizeof(unsigned) * TOPN_FILTER_QUERIES,
                o_ovf = o_tau + sizeof(float) * TOPN_FILTER_QUERIES;
@@ -496,7 +536,7 @@ int topn_slot_alloc(mals_handle h, TopnSlot& sl) {
   if (!sl.d_bidx.get()) {   // (the last of them: all six exist)
     HIPCHK(h, sl.d_tau.alloc(TOPN_FILTER_QUERIES));
     HIPCHK(h, sl.d_count.alloc(TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE + 1));  // padded counters, then the overflow word
-    HIPCHK(h, sl.d_img.alloc((size_t)TOPN_IMG_ENTRIES + 2));   // (+ the rescored filter's trailer, TopnImgTrailer)
+    HIPCHK(h, sl.d_img.alloc((size_t)TOPN_IMG_TOTAL));   // (+ the rescored filter's trailer, TopnImgTrailer, and the candidate filter's, TopnLsh)
     HIPCHK(h, sl.d_qflag.alloc(TOPN_FILTER_QUERIES));
     HIPCHK(h, sl.d_bmax.alloc(TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
     HIPCHK(h, sl.d_bidx.alloc(TOPN_FILTER_QUERIES * 16 * TOPN_SAMPLE_GROUPS));
@@ -554,6 +594,7 @@ int topn_pass_filter_finish(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
       }
     }
     if (o_q.n) *o_q.n = n;
+    if (topn_lsh_on(h, rq)) h->lsh.q_filter.fetch_add(1);
     // (rescored mode: a result that is not finite comes back as THE NaN, ranked first -- RecommendIterator.java:105)
     if (n > 0 && !std::isfinite(o_q.scores[0])) {
       if (!rq.bad_q) return fail(h, MALS_INVALID_ARG, TOPN_BAD_VALUE);

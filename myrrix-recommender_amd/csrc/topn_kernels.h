@@ -77,6 +77,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lsh_kernels.h"
+
 namespace mals {
 
 constexpr int TOPN_MAX_QUERIES = 64;      // dense path: queries per pass
@@ -189,6 +191,11 @@ struct TopnImgTrailer {
   int64_t n_fdata;
   uint4 fdef;
 };
+// ... and behind that the pass's view of the candidate filter (TopnLsh, written by lsh_sign_vectors_kernel), which the LSH
+// instantiations of topn_stream_kernel read
+constexpr int TOPN_IMG_LSH_AT = TOPN_IMG_ENTRIES + 2;
+constexpr int TOPN_IMG_TOTAL = TOPN_IMG_LSH_AT + 3;
+static_assert(sizeof(TopnImgTrailer) <= 32 && sizeof(TopnLsh) <= 48, "the trailers of the query image");
 __device__ __forceinline__ bool topn_rs_filtered(const TopnRescore& rs, int64_t item) {
   return item < rs.filt_items && ((rs.filt[item >> 5] >> (item & 31)) & 1u) != 0u;
 }
@@ -401,7 +408,20 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
 // the query's {-tau hi, hi, lo, lo, 1/n hi, hi, lo, lo}, and lanes (2, c) = {rs hi, +-|os hi|} against the covers {2^-14
 // 1.01 |tau|, 2^-14 1.01 / n}: the item's 16 bytes ride with its row (prefetched a stage ahead), nothing is added per
 // (item, query) pair of the filter; the sample multiplies its accumulators by the items' fp32 scales (through LDS, 256 B).
-template <int S, int QT, int MODE, int LM, bool COS = false, bool RS = false>
+// LSH (candidate filter, lsh_kernels.h; never with COS): the one invariant of the proof the filter can break is that tau must be
+// reached by at least N unmasked CANDIDATE items, so the sample must not let a non-candidate win a bucket: the popcount test
+// bitCount(sig_i ^ sig_q) <= maxBitsDiffering (LSH:201) runs per (item, query) BEFORE the bucket maximum -- dropping the buckets
+// non-candidates won, as for known items, would empty most of them at a 6 % candidate fraction.  The signatures of the stage's
+// items ride with their rows (prefetched a stage ahead, through LDS: 512 B + their new-item biases), the query's signature
+// sits in two registers per query tile.  Per accumulator the sample gains v_xor x2, v_bcnt x2 (the second adds the bias),
+// v_cmp and the mask logic: counted in the ISA at S = 2, QT = 4, 7.3 vector instructions on top of its 3 (527 -> 995 per
+// stage of 64 accumulators).  A query of several vectors is a candidate's query through ANY of them: it is not tested
+// here (threshold 64) -- lsh_drop_buckets_kernel, in front of topn_threshold_kernel, drops the buckets its non-candidates won.
+// MODE 1 tests a hit before it is recorded (inside the rare branch), so that the candidate buffers fill with candidates only;
+// lsh_strike_pairs_kernel, behind topn_rescore_kernel, strikes what is left, so nothing depends on these tests being complete.
+// topn_threshold_kernel, topn_rescore_kernel and their argument lists know nothing of the filter: a pass without one
+// launches exactly the kernels it launched before there was one.
+template <int S, int QT, int MODE, int LM, bool COS = false, bool RS = false, bool LSH = false>
 __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __restrict__ Y, int64_t n_items, int k,
                                                           const bf16x8* __restrict__ img, int n_queries, int tile_stride,
                                                           float* __restrict__ bmax, uint32_t* __restrict__ bidx,
@@ -413,6 +433,8 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
   __shared__ __attribute__((aligned(16))) bf16x8 sa2[2][4 * E * 64];  // two stages x [item tile of the stage][operand][lane]
   __shared__ float sny[COS ? 2 : 1][4][16];                            // COS: |y| of the stage's items, per buffer
   __shared__ float ssc[RS ? 2 : 1][4][16];                             // RS: the fp32 scales of the stage's items, per buffer
+  __shared__ uint64_t ssg[LSH ? 2 : 1][4][16];                         // LSH: the signatures of the stage's items, per buffer ...
+  __shared__ int ssb[LSH ? 2 : 1][4][16];                              // ... and 0, or LSH_NEW_ITEM_BIAS for a row without one
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   // this wave's query tiles, once
   bf16x8 bq[QT][S], bm[QT];
@@ -460,6 +482,27 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
       }
     }
     bm[j] = m;
+  }
+  // LSH: this lane's queries' signatures and thresholds (a query of several vectors: 64, tested later), once
+  uint64_t qs[LSH ? QT : 1];
+  int qb[LSH ? QT : 1];
+  const uint64_t* isig = nullptr;
+  int64_t n_signed = 0;
+  if (LSH) {
+    const TopnLsh* tr = reinterpret_cast<const TopnLsh*>(img + TOPN_IMG_LSH_AT);
+    isig = tr->isig;
+    n_signed = tr->n_signed;
+#pragma unroll
+    for (int j = 0; j < QT; ++j) {
+      const int q = 16 * (4 * j + w) + c;
+      qs[j] = 0ull;
+      qb[j] = 64;
+      if (q < n_queries) {
+        const int v0 = tr->vptr[q];
+        qs[j] = tr->vsig[v0];
+        if (tr->vptr[q + 1] - v0 == 1) qb[j] = tr->mb;
+      }
+    }
   }
   const int64_t step = (int64_t)tile_stride * 16;       // items between consecutive processed tiles
   const int64_t n_proc = (n_items + step - 1) / step;   // processed tiles
@@ -529,11 +572,17 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
     const int64_t item = i0 + c;
     f = item < n_fdata ? fdata[item] : fdef;
   };
+  auto load_sig = [&](int64_t i0, uint64_t& sg) {
+    const int64_t item = i0 + c;
+    sg = item < n_signed ? isig[item] : 0ull;
+  };
   float ynext[CH];
   uint4 fnext = fdef;
+  uint64_t gnext = 0ull;
   if ((int64_t)blockIdx.x < n_stages) {
     load_rows16((4 * (int64_t)blockIdx.x + w) * step, ynext);
     if (RS) load_f16((4 * (int64_t)blockIdx.x + w) * step, fnext);
+    if (LSH) load_sig((4 * (int64_t)blockIdx.x + w) * step, gnext);
   }
   int buf = 0;
   for (int64_t st = blockIdx.x; st < n_stages; st += gridDim.x) {
@@ -541,9 +590,11 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
 #pragma unroll
     for (int s = 0; s < CH; ++s) yv[s] = ynext[s];
     const uint4 fv = fnext;
+    const uint64_t gv = gnext;
     if (st + gridDim.x < n_stages) {
       load_rows16((4 * (st + gridDim.x) + w) * step, ynext);  // the next stage's rows fly during this one
       if (RS) load_f16((4 * (st + gridDim.x) + w) * step, fnext);
+      if (LSH) load_sig((4 * (st + gridDim.x) + w) * step, gnext);
     }
     // this wave's tile of the stage as A operands
     bf16x8 ah[S], am;
@@ -599,6 +650,10 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
           ssc[buf][w][c] = __uint_as_float(fv.z);
         }
       }
+      if (LSH && g == 0) {
+        ssg[buf][w][c] = gv;
+        ssb[buf][w][c] = (4 * st + w) * step + c < n_signed ? 0 : LSH_NEW_ITEM_BIAS;
+      }
 #pragma unroll
       for (int s = 0; s < S; ++s)
 #pragma unroll
@@ -652,10 +707,13 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
           const int64_t it = i0 + 4 * g + r;
           const bool in = it < n_items;
           const float sc = ssc[cb][jt][4 * g + r];  // NaN: a filtered item
+          const uint64_t sg = LSH ? ssg[cb][jt][4 * g + r] : 0ull;
+          const int sb = LSH ? ssb[cb][jt][4 * g + r] : 0;
 #pragma unroll
           for (int j = 0; j < QT; ++j) {
             const float lb = acc[j][r] * sc;
-            if (in && lb > best[j][r]) {  // a NaN never wins
+            const bool cd = !LSH || sb + (int)__popcll(sg ^ qs[j]) <= qb[j];  // LSH:201
+            if (in && cd && lb > best[j][r]) {  // a NaN never wins
               best[j][r] = lb;
               besti[j][r] = (uint32_t)it;
             }
@@ -666,12 +724,16 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
         for (int r = 0; r < 4; ++r) {
           const int64_t it = i0 + 4 * g + r;
           const bool in = it < n_items;
+          const uint64_t sg = LSH ? ssg[cb][jt][4 * g + r] : 0ull;
+          const int sb = LSH ? ssb[cb][jt][4 * g + r] : 0;
 #pragma unroll
-          for (int j = 0; j < QT; ++j)
-            if (in && acc[j][r] > best[j][r]) {  // a NaN never wins
+          for (int j = 0; j < QT; ++j) {
+            const bool cd = !LSH || sb + (int)__popcll(sg ^ qs[j]) <= qb[j];  // LSH:201
+            if (in && cd && acc[j][r] > best[j][r]) {  // a NaN never wins
               best[j][r] = acc[j][r];
               besti[j][r] = (uint32_t)it;
             }
+          }
         }
       } else {
         // A candidate is an accumulator that is not below zero.  As signed integers the non-negative floats (and the
@@ -702,6 +764,7 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
                 const float nr = sny[cb][jt][4 * g + r];
                 hit = hit && nr > 0.f && nr < __builtin_huge_valf();
               }
+              if (LSH) hit = hit && ssb[cb][jt][4 * g + r] + (int)__popcll(ssg[cb][jt][4 * g + r] ^ qs[j]) <= qb[j];  // LSH:201
               const uint64_t hm = __ballot(hit);
               if (hm) {
                 const unsigned at = n_hits + (unsigned)__popcll(hm & ((1ull << lane) - 1ull));

@@ -7,7 +7,11 @@ usage: python tools/bench_topn.py [--items N] [--users U] [--features K] [--how-
        query) next to recommend in the same run, per batch size; --lib-root imports the package (and its library) from
        another checkout, whose recommend leg alone then runs (an A/B of recommend against an older build)
        python tools/bench_topn.py --rescorer [--how-many 64]: recommend with a rescorer (a 10 %% filter set plus per-item
-       scale and offset, mals_recommend_rescored) next to the unrescored leg in the same run, 240-query batches"""
+       scale and offset, mals_recommend_rescored) next to the unrescored leg in the same run, 240-query batches
+       python tools/bench_topn.py --lsh 0.3,0.1 [--lib-root DIR]: recommend with the candidate filter (mals_lsh_build,
+       LocationSensitiveHash) off and at each sample ratio in the same run, the build time next to its bytes bounds (the
+       signatures read Y once, n k 4 bytes; with the mean computed on the device Y is read twice) and how many queries the bf16 filter path / the dense path answered; with --lib-root of a checkout that has
+       no candidate filter only the filter-off leg runs (the A/B of unfiltered passes against an older build)"""
 import argparse
 import json
 import os
@@ -29,7 +33,11 @@ def main():
     ap.add_argument("--lib-root", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rescorer", action="store_true")
+    ap.add_argument("--lsh", default=None, metavar="RATIOS")
+    ap.add_argument("--hashes", type=int, default=20)
     a = ap.parse_args()
+    if a.lsh:
+        return lsh(a)
     if a.similar:
         return similar(a)
     if a.rescorer:
@@ -238,6 +246,68 @@ def rescored(a):
         out["rescored_over_plain"] = {b: out["rescored"][b]["queries_per_s"] / out["plain"][b]["queries_per_s"] for b in out["plain"]}
         r.close()
     out["value"] = out["rescored"]["4096"]["queries_per_s"]
+    print(json.dumps(out))
+
+
+def lsh(a):
+    """recommend with the candidate filter off and at each of the given sample ratios (model.lsh.sampleRatio), the same users
+    in the same run; the build (mean + signatures of Y) against the time its bytes need at 8 TB/s"""
+    if a.lib_root:
+        sys.path.insert(0, os.path.abspath(a.lib_root))
+    import numpy as np
+    import myrrix_recommender_amd as pkg
+    rng = np.random.default_rng(1234567890)
+    k = a.features
+    Y = (rng.standard_normal((a.items, k)) / np.sqrt(k)).astype(np.float32)
+    X = (rng.standard_normal((a.users, k)) / np.sqrt(k)).astype(np.float32)
+    deg = 100
+    rp = np.arange(a.users + 1, dtype=np.int64) * deg
+    col = rng.integers(0, a.items, a.users * deg).astype(np.int32)
+    per_pass = 16 * {1: 16, 2: 15, 3: 10, 4: 7}[(k + 31) // 32]
+    out = {"metric": "recommend queries/s with the candidate filter off and on, same run", "unit": "queries/s", "items": a.items, "features": k,
+           "how_many": a.how_many, "queries_per_pass": per_pass, "num_hashes": a.hashes, "package": os.path.dirname(pkg.__file__), "legs": {}}
+    with pkg.ALSCore(k) as core:
+        core.set_factor_rows(pkg.SIDE_X, a.users)
+        core.set_factor_rows(pkg.SIDE_Y, a.items)
+        core.set_factors(pkg.SIDE_X, X)
+        core.set_factors(pkg.SIDE_Y, Y)
+        core.set_matrix(pkg.SIDE_X, rp, col, np.ones(len(col), np.float32))
+        ratios = [float(r) for r in a.lsh.split(",") if r != "off"] if hasattr(core, "lsh_build") else []   # "--lsh off": the unfiltered leg alone
+        batches = {b: rng.integers(0, a.users, b).astype(np.int64) for b in (per_pass, 4096)}
+        for ratio in [None] + ratios:
+            leg = {}
+            if ratio is not None:
+                rv = rng.integers(0, 2, (a.hashes, k)).astype(bool)
+                core.lsh_build(num_hashes=a.hashes, sample_ratio=ratio, random_vectors=rv)      # warm (allocations, code load)
+                runs = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    core.lsh_build(num_hashes=a.hashes, sample_ratio=ratio, random_vectors=rv)
+                    runs.append(time.perf_counter() - t0)
+                y_bytes = a.items * k * 4              # the signatures read Y once; so does the mean before them
+                leg["build_ms"] = min(runs) * 1e3
+                leg["build_ms_runs"] = [x * 1e3 for x in runs]
+                leg["signatures_bytes_bound_ms"] = y_bytes / 8e12 * 1e3
+                leg["build_bytes_bound_ms"] = 2 * y_bytes / 8e12 * 1e3      # mean + signatures, as timed here
+                leg["max_bits_differing"] = core.lsh_info()["max_bits_differing"]
+                before = core.lsh_info()
+            for batch, users in batches.items():
+                core.recommend(users, a.how_many)                          # warm
+                reps = max(10, 4096 // batch)
+                runs = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    for _ in range(reps):
+                        core.recommend(users, a.how_many)
+                    runs.append((time.perf_counter() - t0) / reps)
+                dt = min(runs)
+                leg[str(batch)] = {"ms_per_call": dt * 1e3, "ms_per_call_runs": [x * 1e3 for x in runs], "queries_per_s": batch / dt}
+            if ratio is not None:
+                after = core.lsh_info()
+                leg["filter_queries"] = after["filter_queries"] - before["filter_queries"]
+                leg["dense_queries"] = after["dense_queries"] - before["dense_queries"]
+            out["legs"]["off" if ratio is None else str(ratio)] = leg
+    out["value"] = out["legs"]["off"]["4096"]["queries_per_s"]
     print(json.dumps(out))
 
 
