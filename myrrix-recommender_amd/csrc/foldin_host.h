@@ -177,10 +177,7 @@ int foldin_exclusive(mals_handle h, const std::function<int()>& fn, const std::s
   rq.kind = TOPN_KIND_CALL;
   rq.call = &fn;
   rq.how_many = 1;
-  TopnTicket t;
-  t.bulk = &rq;
-  t.how_many = 1;
-  const int rc = topn_front_submit(h, t);
+  const int rc = topn_front_submit(h, rq, false);
   if (rc == MALS_OK) return rc;
   std::lock_guard<std::mutex> lk(topn_front(h)->mu);   // (as topn_fail: request threads write h->err under this mutex)
   h->err = std::string(call) + ": " + (msg.empty() ? std::string("failed") : msg);

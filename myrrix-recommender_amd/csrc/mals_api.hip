@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -2644,6 +2645,14 @@ static int topn_fail(mals_handle h, int code, const char* msg) {
   return code;
 }
 
+// the last checks of a call that scores items: the tag items fit the catalogue, the calling thread is on the handle's device
+static int topn_serving_ready(mals_handle h) {
+  if (h->tag_bits.get() && h->tag_bits_items != h->side[MALS_SIDE_Y].n_total)
+    return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
+  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  return MALS_OK;
+}
+
 static int topn_recommend_impl(mals_handle h, mals_rescorer r, const int64_t* user_idx, int32_t n_queries, int32_t how_many,
                                int32_t consider_known_items, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
   if (!h) return MALS_INVALID_ARG;
@@ -2663,33 +2672,17 @@ static int topn_recommend_impl(mals_handle h, mals_rescorer r, const int64_t* us
       return topn_fail(h, MALS_INVALID_ARG, "known items of this user are not on this handle (row outside the local shard)");
   }
   if (n_queries == 0) return MALS_OK;
-  if (h->tag_bits.get() && h->tag_bits_items != y.n_total)
-    return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
-  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
-  TopnTicket t;
+  if (int rc = topn_serving_ready(h)) return rc;
   TopnRequest rq;
-  if (n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N) {
-    t.user_idx = user_idx;
-    t.n = n_queries;
-    t.how_many = how_many;
-    t.skip_known = !consider_known_items;
-    t.item_out = item_idx_out;
-    t.score_out = score_out;
-    t.n_out = n_out;
-  } else {
-    rq.n_queries = n_queries;
-    rq.how_many = how_many;
-    rq.user_idx = user_idx;
-    rq.skip_known = !consider_known_items;
-    rq.item_idx_out = item_idx_out;
-    rq.score_out = score_out;
-    rq.n_out = n_out;
-    t.bulk = &rq;
-    t.how_many = how_many;
-  }
-  t.rescorer = r;
+  rq.n_queries = n_queries;
+  rq.how_many = how_many;
+  rq.user_idx = user_idx;
+  rq.skip_known = !consider_known_items;
+  rq.item_idx_out = item_idx_out;
+  rq.score_out = score_out;
+  rq.n_out = n_out;
   rq.rescorer = r;
-  return topn_front_submit(h, t);
+  return topn_front_submit(h, rq, n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N);
 }
 
 int mals_recommend(mals_handle h, const int64_t* user_idx, int32_t n_queries, int32_t how_many, int32_t consider_known_items,
@@ -2786,40 +2779,23 @@ static int topn_to_many_impl(mals_handle h, mals_rescorer r, const float* vector
     }
   }
   if (n_queries == 0) return MALS_OK;
-  if (h->tag_bits.get() && h->tag_bits_items != y.n_total)
-    return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
-  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  if (int rc = topn_serving_ready(h)) return rc;
   TopnRequest rq;
-  TopnTicket t;
-  t.how_many = how_many;
+  rq.n_queries = n_queries;
+  rq.how_many = how_many;
+  rq.vectors = vectors;
+  rq.vec_ptr = vector_ptr;
+  rq.excl_ptr = exclude_ptr;
+  rq.excl_idx = exclude_idx;
+  rq.item_idx_out = item_idx_out;
+  rq.score_out = score_out;
+  rq.n_out = n_out;
+  rq.rescorer = r;
   const int64_t n_vec = vector_ptr ? vector_ptr[n_queries] : (int64_t)n_queries;
   const int64_t n_ex = (exclude_ptr && exclude_idx) ? exclude_ptr[n_queries] - exclude_ptr[0] : 0;
-  if (n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N && n_vec <= 4 * TOPN_FRONT_BULK && n_ex <= (1 << 16) &&
-      (!exclude_ptr || exclude_ptr[0] == 0)) {
-    // a small call (an anonymous user, recommendToMany for a handful of users): folded into a pass with the other callers'
-    t.vectors = vectors;
-    t.vec_ptr = vector_ptr;
-    t.excl_ptr = exclude_ptr;
-    t.excl_idx = exclude_idx;
-    t.n = n_queries;
-    t.item_out = item_idx_out;
-    t.score_out = score_out;
-    t.n_out = n_out;
-  } else {
-    rq.n_queries = n_queries;
-    rq.how_many = how_many;
-    rq.vectors = vectors;
-    rq.vec_ptr = vector_ptr;
-    rq.excl_ptr = exclude_ptr;
-    rq.excl_idx = exclude_idx;
-    rq.item_idx_out = item_idx_out;
-    rq.score_out = score_out;
-    rq.n_out = n_out;
-    t.bulk = &rq;
-  }
-  t.rescorer = r;
-  rq.rescorer = r;
-  return topn_front_submit(h, t);
+  // a small call (an anonymous user, recommendToMany for a handful of users) is folded into a pass with the other callers'
+  return topn_front_submit(h, rq, n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N && n_vec <= 4 * TOPN_FRONT_BULK && n_ex <= (1 << 16) &&
+                                      (!exclude_ptr || exclude_ptr[0] == 0));
 }
 
 int mals_recommend_to_many(mals_handle h, const float* vectors, const int64_t* vector_ptr, int32_t n_queries, int32_t how_many,
@@ -2864,34 +2840,20 @@ int mals_most_similar_items(mals_handle h, const int64_t* item_idx, const int64_
   }
   if (n_queries == 0) return MALS_OK;
   if (int rc = topn_check_items(h, item_idx, item_ptr[n_queries])) return rc;
-  if (h->tag_bits.get() && h->tag_bits_items != y.n_total)
-    return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
-  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  if (int rc = topn_serving_ready(h)) return rc;
   TopnRequest rq;
-  TopnTicket t;
-  t.how_many = how_many;
-  if (n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N && item_ptr[n_queries] <= 4 * TOPN_FRONT_BULK) {
-    // a small call: folded into a pass with other callers' mostSimilarItems calls
-    t.items = item_idx;
-    t.item_ptr = item_ptr;
-    t.n = n_queries;
-    t.item_out = item_idx_out;
-    t.score_out = score_out;
-    t.n_out = n_out;
-  } else {
-    rq.n_queries = n_queries;
-    rq.how_many = how_many;
-    rq.item_rows = item_idx;
-    rq.vec_ptr = item_ptr;
-    rq.excl_ptr = item_ptr;   // the query items are never returned (MostSimilarItemIterator.java:81-85)
-    rq.excl_idx = item_idx;
-    rq.cosine = true;
-    rq.item_idx_out = item_idx_out;
-    rq.score_out = score_out;
-    rq.n_out = n_out;
-    t.bulk = &rq;
-  }
-  return topn_front_submit(h, t);
+  rq.n_queries = n_queries;
+  rq.how_many = how_many;
+  rq.item_rows = item_idx;
+  rq.vec_ptr = item_ptr;
+  rq.excl_ptr = item_ptr;   // the query items are never returned (MostSimilarItemIterator.java:81-85)
+  rq.excl_idx = item_idx;
+  rq.cosine = true;
+  rq.item_idx_out = item_idx_out;
+  rq.score_out = score_out;
+  rq.n_out = n_out;
+  // a small call is folded into a pass with other callers' mostSimilarItems calls
+  return topn_front_submit(h, rq, n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N && item_ptr[n_queries] <= 4 * TOPN_FRONT_BULK);
 }
 
 int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_idx, int32_t n, float* out) {
@@ -2904,16 +2866,13 @@ int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_
   if (n == 0) return MALS_OK;
   if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
   TopnRequest rq;
-  TopnTicket t;
   rq.kind = TOPN_KIND_SIMILARITY_TO;
   rq.n_queries = n;
   rq.how_many = 1;
   rq.item_rows = item_idx;
   rq.to_item = to_item;
   rq.sim_out = out;
-  t.bulk = &rq;
-  t.how_many = 1;
-  return topn_front_submit(h, t);
+  return topn_front_submit(h, rq, false);
 }
 
 int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
@@ -2935,11 +2894,8 @@ int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64
   }
   if (n_queries == 0) return MALS_OK;
   if (int rc = topn_check_items(h, item_idx, n_queries)) return rc;
-  if (h->tag_bits.get() && h->tag_bits_items != y.n_total)
-    return topn_fail(h, MALS_INVALID_ARG, "the tag items were set for another item count: call mals_set_tag_items again");
-  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  if (int rc = topn_serving_ready(h)) return rc;
   TopnRequest rq;
-  TopnTicket t;
   rq.kind = TOPN_KIND_BECAUSE;
   rq.n_queries = n_queries;
   rq.how_many = how_many;
@@ -2949,9 +2905,7 @@ int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64
   rq.item_idx_out = item_idx_out;
   rq.score_out = score_out;
   rq.n_out = n_out;
-  t.bulk = &rq;
-  t.how_many = how_many;
-  return topn_front_submit(h, t);
+  return topn_front_submit(h, rq, false);
 }
 
 int mals_recommend_front_stats(mals_handle h, int64_t* out4) {

@@ -33,8 +33,8 @@ struct TopnSlot {
   DeviceBuffer<double> d_qn;          // cosine mode: the exact norms of the pass's query vectors ...
   DeviceBuffer<uint32_t> d_qflag;     // ... and per query 0 / 1 (answered empty) / 2 (dense path), topn_prepare_kernel<true>
   DeviceBuffer<uint64_t> d_vsig;      // candidate filter: the bit signatures of the pass's query vectors (lsh_sign_vectors_kernel)
-  PinnedBuffer<uint8_t> h_stage;      // the pass's results, [nq][how_many] pairs | counts | taus | overflow word (topn_final_kernel
-                                      // writes them there), decoded while later passes run
+  PinnedBuffer<uint8_t> h_stage;      // the pass's results (TopnStage: topn_final_kernel writes them there), decoded while later
+                                      // passes run
 };
 
 struct TopnWorkspace {
@@ -226,11 +226,66 @@ int topn_upload_pass(mals_handle h, TopnSlot& sl, hipStream_t stream, const Topn
   return MALS_OK;
 }
 
+// ---- the scoring variant of a pass ------------------------------------------------------------------------------------
+// Which instantiations of the scoring kernels run a pass: derived once from (h, rq), turned into template arguments in one
+// place (topn_dispatch), and the kernel arguments that go with it derived once per pass (topn_variant_args).
+struct TopnVariant {
+  bool cos;   // cosine to rows of Y (mostSimilarItems, recommendedBecause)
+  bool rs;    // the caller's rescorer
+  bool lsh;   // the candidate filter is built and this kind of call consults it
+};
+TopnVariant topn_variant(mals_handle h, const TopnRequest& rq) {
+  return {rq.cosine, rq.rs != nullptr, h->lsh.H > 0 && rq.kind == TOPN_KIND_SCORE && !rq.cosine};
+}
+
+// f(COS, RS, LSH) with the variant as std::bool_constants: the five combinations the library is built for
+template <class F>
+auto topn_dispatch(const TopnVariant& v, F&& f) {
+  assert(!(v.cos && (v.rs || v.lsh)));   // no entry point takes a rescorer for a cosine call, none of them consults the filter
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (v.cos) return f(yes, no, no);
+  if (v.rs && v.lsh) return f(no, yes, yes);
+  if (v.rs) return f(no, yes, no);
+  if (v.lsh) return f(no, no, yes);
+  return f(no, no, no);
+}
+
+struct TopnVariantArgs {
+  const double* qn;         // cosine: the exact norms of the pass's query vectors, else NULL
+  uint32_t* qflag;          // cosine: the per-query flags of topn_prepare_kernel<true>, else NULL
+  TopnRescore rs;           // rescored: what the pass reads of the rescorer, else the identity
+  TopnImgTrailer trailer;   // rescored: the items' filter data behind the query image, else none
+};
+// (after the pass's sl.d_qn has its size: the pointer is taken here)
+TopnVariantArgs topn_variant_args(const TopnVariant& v, const TopnSlot& sl, const TopnRequest& rq) {
+  TopnVariantArgs a{nullptr, nullptr, TopnRescore(), TopnImgTrailer()};
+  if (v.cos) {
+    a.qn = sl.d_qn.get();
+    a.qflag = sl.d_qflag.get();
+  }
+  if (v.rs) {
+    a.rs = *rq.rs;
+    a.trailer = TopnImgTrailer{rq.rs->fdata, rq.rs->n_fdata, rq.rs->fdef};
+  }
+  return a;
+}
+
+// the known-items CSR of a handle: knownItemIDs if the caller installed them, else the rows of R
+struct TopnKnown {
+  const int64_t* ptr;
+  const int32_t* idx;
+};
+TopnKnown topn_known(mals_handle h) {
+  const SideState& x = h->side[MALS_SIDE_X];
+  return h->known_ptr ? TopnKnown{h->known_ptr, h->known_idx} : TopnKnown{x.row_ptr, x.col};
+}
+
 // ---- the candidate filter (mals_lsh_build; lsh_kernels.h) ---------------------------------------------------------------
 // mals_recommend* and their rescored twins consult it (ServerRecommender.java:431-436, :555); mostSimilarItems,
 // similarityToItem and recommendedBecause never do (the reference passes no candidate filter there).  A build is an exclusive
-// ticket of the front: no pass is in flight while the state changes, so a pass reads it as it is when it is enqueued.
-bool topn_lsh_on(mals_handle h, const TopnRequest& rq) { return h->lsh.H > 0 && rq.kind == TOPN_KIND_SCORE && !rq.cosine; }
+// ticket of the front: no pass is in flight while the state changes, so a pass reads it as it is when it is enqueued
+// (TopnVariant::lsh).
 
 // toBitSignature (LSH:169-190) of the pass's query vectors where they already are on the device -- rows of X, the uploaded
 // block -- on `st`, no host round trip; *view = what the pass's kernels read of the filter.  img: the pass's query image (the
@@ -267,7 +322,6 @@ int topn_select_threshold(mals_handle h, const float* d_scores, int64_t n_row, i
 
 int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnRequest& rq, const TopnPass& ps) {
   SideState& y = h->side[MALS_SIDE_Y];
-  SideState& x = h->side[MALS_SIDE_X];
   const int k = h->cfg.features, nq = ps.nq, how_many = rq.how_many;
   const int64_t n_items = y.n_total;
   const int cap_ties = 1024;
@@ -277,29 +331,28 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
   if (!w->d_state.get()) HIPCHK(h, w->d_state.alloc(TOPN_MAX_QUERIES));
   if (!w->d_hist.get()) HIPCHK(h, w->d_hist.alloc(256 * TOPN_MAX_QUERIES));
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_items + 63) / 64, (int64_t)h->n_cu * 8));
-  if (rq.cosine) {
+  const TopnVariant v = topn_variant(h, rq);
+  if (v.cos) {
     HIPCHK(h, sl.d_qn.reserve((size_t)std::max<int64_t>(ps.n_vecs, 1), h->stream));
     hipLaunchKernelGGL(topn_qnorm_kernel, dim3((unsigned)((ps.n_vecs + 63) / 64)), dim3(64), 0, h->stream, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs, k,
                        sl.d_qn.get());
-    hipLaunchKernelGGL(topn_exact_dense_kernel<true>, dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k,
-                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), sl.d_qn.get(), TopnRescore());
-  } else if (rq.rs) {
-    hipLaunchKernelGGL((topn_exact_dense_kernel<false, true>), dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k,
-                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), nullptr, *rq.rs);
-  } else {
-    hipLaunchKernelGGL(topn_exact_dense_kernel<false>, dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, n_items, k,
-                       sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), nullptr, TopnRescore());
   }
-  if (ps.have_rows)
-    hipLaunchKernelGGL(topn_mask_kernel, dim3(64, (unsigned)nq), dim3(256), 0, h->stream, h->known_ptr ? h->known_ptr : x.row_ptr,
-                       h->known_ptr ? h->known_idx : x.col, sl.d_rows, nq, 1, n_items, w->d_scores.get());
+  const TopnVariantArgs va = topn_variant_args(v, sl, rq);
+  topn_dispatch(v, [&](auto COS, auto RS, auto) {
+    hipLaunchKernelGGL((topn_exact_dense_kernel<COS, RS>), dim3(grid), dim3(256), sizeof(float) * 64 * (size_t)(k + 1),
+                       h->stream, y.F, n_items, k, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, w->d_scores.get(), va.qn, va.rs);
+  });
+  if (ps.have_rows) {
+    const TopnKnown kn = topn_known(h);
+    hipLaunchKernelGGL(topn_mask_kernel, dim3(64, (unsigned)nq), dim3(256), 0, h->stream, kn.ptr, kn.idx, sl.d_rows, nq, 1, n_items, w->d_scores.get());
+  }
   if (ps.have_excl)
     hipLaunchKernelGGL(topn_exclude_kernel, dim3(64, (unsigned)nq), dim3(256), 0, h->stream, sl.d_excl_ptr, sl.d_excl_idx, nq, n_items, 1, n_items,
                        w->d_scores.get());
   if (h->tag_bits)
     hipLaunchKernelGGL(topn_mask_tags_kernel, dim3((unsigned)(((n_items + 31) / 32 + 255) / 256)), dim3(256), 0, h->stream, h->tag_bits.get(), nq, n_items,
                        w->d_scores.get());
-  if (topn_lsh_on(h, rq)) {   // the non-candidates of every query (LSH:193-216)
+  if (v.lsh) {   // the non-candidates of every query (LSH:193-216)
     TopnLsh lv;
     if (int rc = topn_lsh_sign_pass(h, sl, h->stream, ps, nullptr, &lv)) return rc;
     hipLaunchKernelGGL(lsh_mask_dense_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_items + 255) / 256, 1024)), (unsigned)nq), dim3(256), 0,
@@ -353,24 +406,22 @@ int topn_max_tiles(int S) { return S == 1 ? 16 : S == 2 ? 15 : S == 3 ? 10 : 7; 
 
 constexpr int TOPN_WAVE_CAP = 2048;  // hits a wave of the filter kernel can record (expected: a hundred)
 
-// topn_stream_kernel: QT = query tiles per wave, 4 QT per workgroup.  MODE 0: *n_out = workgroups of the sample (16
-// buckets each); MODE 1: *n_out = waves of the filter (one hit list each).
+// the slot's overflow word: behind its padded per-query counters
+unsigned* topn_overflow_word(const TopnSlot& sl) { return sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE; }
+
+// topn_stream_kernel: QT = query tiles per wave, 4 QT per workgroup, LM = its load mode.  MODE 0: *n_out = workgroups of the
+// sample (16 buckets each); MODE 1: *n_out = waves of the filter (one hit list each).
 // RS: the rescored instantiations (the rescorer's per-item data: behind the query image, topn_prepare_kernel<false, true>)
-template <int S, int QT, int MODE, bool COS, bool RS = false, bool LSH = false>
-int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
+template <int S, int QT, int MODE, int LM, bool COS, bool RS, bool LSH>
+int topn_launch_stream_LM(mals_handle h, TopnSlot& sl, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
+  constexpr auto kernel = topn_stream_kernel<S, QT, MODE, LM, COS, RS, LSH>;   // asked for its occupancy and launched: the same one
   const int64_t tiles = (n_items + 16 * (int64_t)tile_stride - 1) / (16 * (int64_t)tile_stride);
   const int64_t stages = (tiles + 3) / 4;
   // resident workgroups per CU: what the instantiation's registers and LDS (two buffers of 4 (S + 1) KB) allow, asked once
-  const int lm = k == 32 * S ? 1 : (k & 3) == 0 ? 2 : (k & 1) == 0 ? 3 : 0;  // topn_stream_kernel's load mode
-  static int cached[4] = {0, 0, 0, 0};
-  int& per_cu_cached = cached[lm];
+  static int per_cu_cached = 0;
   if (!per_cu_cached) {
     int nb = 0;
-    hipError_t e;
-    e = lm == 1   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 1, COS, RS, LSH>, 256, 0)
-        : lm == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 2, COS, RS, LSH>, 256, 0)
-        : lm == 3 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 3, COS, RS, LSH>, 256, 0)
-                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, topn_stream_kernel<S, QT, MODE, 0, COS, RS, LSH>, 256, 0);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0);
     per_cu_cached = (e == hipSuccess && nb > 0) ? std::min(nb, 6) : 2;
   }
   int per_cu = per_cu_cached;
@@ -390,42 +441,70 @@ int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n
   } else {
     *n_out = (int)grid;
   }
-#define MALS_TOPN_GO(LM)                                                                                                              \
-  hipLaunchKernelGGL((topn_stream_kernel<S, QT, MODE, LM, COS, RS, LSH>), dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k,                       \
-                     sl.d_img.get(), nq, tile_stride, sl.d_bmax.get(), sl.d_bidx.get(), sl.d_tau.get(), TOPN_WAVE_CAP, sl.d_wcount.get(),   \
-                     sl.d_whits.get(), cap, sl.d_count.get(), sl.d_cand.get(), sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE)
-  if (lm == 1) MALS_TOPN_GO(1);
-  else if (lm == 2) MALS_TOPN_GO(2);
-  else if (lm == 3) MALS_TOPN_GO(3);
-  else MALS_TOPN_GO(0);
-#undef MALS_TOPN_GO
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, sl.stream, Y, n_items, k, sl.d_img.get(), nq, tile_stride, sl.d_bmax.get(), sl.d_bidx.get(),
+                     sl.d_tau.get(), TOPN_WAVE_CAP, sl.d_wcount.get(), sl.d_whits.get(), cap, sl.d_count.get(), sl.d_cand.get(), topn_overflow_word(sl));
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
 }
-template <int MODE, bool COS, bool RS = false, bool LSH = false>
-int topn_launch_stream(mals_handle h, TopnSlot& sl, int S, int nt, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
+// topn_stream_kernel's load mode: what the feature count allows
+template <int S, int QT, int MODE, bool COS, bool RS, bool LSH>
+int topn_launch_stream_QT(mals_handle h, TopnSlot& sl, const float* Y, int64_t n_items, int k, int nq, int tile_stride, int cap, int* n_out) {
+#define MALS_TOPN_LM(LM) return topn_launch_stream_LM<S, QT, MODE, LM, COS, RS, LSH>(h, sl, Y, n_items, k, nq, tile_stride, cap, n_out)
+  if (k == 32 * S) MALS_TOPN_LM(1);
+  if ((k & 3) == 0) MALS_TOPN_LM(2);
+  if ((k & 1) == 0) MALS_TOPN_LM(3);
+  MALS_TOPN_LM(0);
+#undef MALS_TOPN_LM
+}
+// the pass's variant, features and query tiles -> the instantiation
+template <int MODE>
+int topn_launch_stream(mals_handle h, TopnSlot& sl, const TopnVariant& v, int S, int nt, const float* Y, int64_t n_items, int k, int nq, int tile_stride,
+                       int cap, int* n_out) {
   const int qt = (nt + 3) / 4;
+  return topn_dispatch(v, [&](auto COS, auto RS, auto LSH) -> int {
 #define MALS_TOPN_STREAM(SS, QQ) return topn_launch_stream_QT<SS, QQ, MODE, COS, RS, LSH>(h, sl, Y, n_items, k, nq, tile_stride, cap, n_out)
-  switch (S) {
-    case 1:
-      if (qt <= 1) MALS_TOPN_STREAM(1, 1);
-      if (qt == 2) MALS_TOPN_STREAM(1, 2);
-      if (qt == 3) MALS_TOPN_STREAM(1, 3);
-      MALS_TOPN_STREAM(1, 4);
-    case 2:
-      if (qt <= 1) MALS_TOPN_STREAM(2, 1);
-      if (qt == 2) MALS_TOPN_STREAM(2, 2);
-      if (qt == 3) MALS_TOPN_STREAM(2, 3);
-      MALS_TOPN_STREAM(2, 4);
-    case 3:  // at most 10 query tiles per pass
-      if (qt <= 1) MALS_TOPN_STREAM(3, 1);
-      if (qt == 2) MALS_TOPN_STREAM(3, 2);
-      MALS_TOPN_STREAM(3, 3);
-    default:  // at most 7
-      if (qt <= 1) MALS_TOPN_STREAM(4, 1);
-      MALS_TOPN_STREAM(4, 2);
-  }
+    switch (S) {
+      case 1:
+        if (qt <= 1) MALS_TOPN_STREAM(1, 1);
+        if (qt == 2) MALS_TOPN_STREAM(1, 2);
+        if (qt == 3) MALS_TOPN_STREAM(1, 3);
+        MALS_TOPN_STREAM(1, 4);
+      case 2:
+        if (qt <= 1) MALS_TOPN_STREAM(2, 1);
+        if (qt == 2) MALS_TOPN_STREAM(2, 2);
+        if (qt == 3) MALS_TOPN_STREAM(2, 3);
+        MALS_TOPN_STREAM(2, 4);
+      case 3:  // at most 10 query tiles per pass
+        if (qt <= 1) MALS_TOPN_STREAM(3, 1);
+        if (qt == 2) MALS_TOPN_STREAM(3, 2);
+        MALS_TOPN_STREAM(3, 3);
+      default:  // at most 7
+        if (qt <= 1) MALS_TOPN_STREAM(4, 1);
+        MALS_TOPN_STREAM(4, 2);
+    }
 #undef MALS_TOPN_STREAM
+  });
+}
+
+// The pinned result block of a pass, [capacity][how_many] (key, ~index) pairs | [capacity] counts | [capacity] taus | an
+// overflow word: topn_final_kernel writes it (topn_launch_final), the host decodes it, and both find the pieces here.
+struct TopnStage {
+  uint8_t* base;
+  size_t o_count, o_tau, o_overflow;
+  TopnStage(uint8_t* block, int capacity, int how_many)
+      : base(block), o_count(sizeof(uint64_t) * (size_t)capacity * (size_t)how_many), o_tau(o_count + sizeof(unsigned) * (size_t)capacity),
+        o_overflow(o_tau + sizeof(float) * (size_t)capacity) {}
+  uint64_t* pairs() const { return reinterpret_cast<uint64_t*>(base); }
+  unsigned* count() const { return reinterpret_cast<unsigned*>(base + o_count); }
+  float* tau() const { return reinterpret_cast<float*>(base + o_tau); }
+  unsigned* overflow() const { return reinterpret_cast<unsigned*>(base + o_overflow); }
+  size_t bytes() const { return o_overflow + 16; }
+};
+// one place of the block's pairs; false: empty (the query has fewer results than how_many)
+inline bool topn_decode_pair(uint64_t pr, TopnCand* c) {
+  if (pr == 0) return false;
+  *c = {(uint32_t)(pr >> 32), (int64_t)(0xffffffffu - (uint32_t)pr)};
+  return true;
 }
 
 struct TopnFilterPlan {
@@ -447,85 +526,67 @@ TopnFilterPlan topn_plan(mals_handle h, int how_many) {
   int64_t target = std::max<int64_t>(512 * (int64_t)how_many, std::max<int64_t>(16384, n_items / 8));
   if (const char* e = std::getenv("MALS_TOPN_SAMPLE_ITEMS")) target = std::max<int64_t>(1024, std::atoll(e));  // tuning override
   p.tile_stride = (int)std::max<int64_t>(1, n_items / target);
-  p.stage_bytes = (size_t)TOPN_FILTER_QUERIES * ((size_t)how_many * 8 + 8) + 16;  // pairs | counts | taus | overflow word
+  p.stage_bytes = TopnStage(nullptr, TOPN_FILTER_QUERIES, how_many).bytes();
   return p;
+}
+
+// exact scores of the candidates in sl.d_cand into sl.d_pairs (the known items `kn` of the rows d_rows, the exclusion lists and
+// the tag items dropped), and from there the N best of every query into the result block `o`
+void topn_launch_rescore(mals_handle h, TopnSlot& sl, hipStream_t st, const TopnVariant& v, const TopnVariantArgs& va, int nq, int cap, const TopnKnown& kn,
+                         const int64_t* d_rows, const int64_t* d_eptr, const int64_t* d_eidx) {
+  const int k = h->cfg.features;
+  topn_dispatch(v, [&](auto COS, auto RS, auto) {
+    hipLaunchKernelGGL((topn_rescore_kernel<COS, RS>), dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, h->side[MALS_SIDE_Y].F, k,
+                       sl.d_vecs, sl.d_vrow, sl.d_vptr, sl.d_count.get(), cap, sl.d_cand.get(), kn.ptr, kn.idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(),
+                       sl.d_pairs.get(), topn_overflow_word(sl), va.qn, h->side[MALS_SIDE_Y].n_total, va.rs);
+  });
+}
+void topn_launch_final(TopnSlot& sl, hipStream_t st, int nq, int cap, int how_many, const TopnStage& o) {
+  hipLaunchKernelGGL(topn_final_kernel, dim3((unsigned)nq), dim3(256), sizeof(uint64_t) * (size_t)cap, st, sl.d_pairs.get(), sl.d_count.get(), cap, how_many,
+                     o.pairs(), o.count(), sl.d_tau.get(), o.tau(), topn_overflow_word(sl), o.overflow());
 }
 
 // the kernels of one pass on the slot's stream (plain launches, or recorded into a graph while the stream is capturing)
 int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, const TopnPass& ps, const TopnFilterPlan& p) {
   SideState& y = h->side[MALS_SIDE_Y];
-  SideState& x = h->side[MALS_SIDE_X];
   const int k = h->cfg.features, nq = ps.nq, how_many = rq.how_many;
   const int64_t n_items = y.n_total;
   const int nt = (nq + 15) / 16;
   hipStream_t st = sl.stream;
-  unsigned* d_overflow = sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE;
+  const TopnVariant v = topn_variant(h, rq);
+  const TopnVariantArgs va = topn_variant_args(v, sl, rq);
+  const TopnKnown kn = topn_known(h);
   const int64_t* d_rows = ps.have_rows ? sl.d_rows : nullptr;
-  const int64_t* k_ptr = h->known_ptr ? h->known_ptr : x.row_ptr;   // knownItemIDs if the caller installed them, else the rows of R
-  const int32_t* k_idx = h->known_ptr ? h->known_idx : x.col;
   const int64_t* d_eptr = ps.have_excl ? sl.d_excl_ptr : nullptr;
   const int64_t* d_eidx = ps.have_excl ? sl.d_excl_idx : nullptr;
-  const bool cos = rq.cosine;
   // 0. the queries as matrix operands (every tile an instantiation may touch: padding queries never produce a hit); in
   // cosine mode first the exact norms of the query vectors
-  if (cos) {
+  if (v.cos)
     hipLaunchKernelGGL(topn_qnorm_kernel, dim3((unsigned)((ps.n_vecs + 63) / 64)), dim3(64), 0, st, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs, k, sl.d_qn.get());
-    hipLaunchKernelGGL(topn_prepare_kernel<true>, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
-                       sl.d_img.get(), sl.d_count.get(), d_overflow, sl.d_qn.get(), sl.d_qflag.get(), TopnImgTrailer());
-  } else if (rq.rs) {
-    hipLaunchKernelGGL((topn_prepare_kernel<false, true>), dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
-                       sl.d_img.get(), sl.d_count.get(), d_overflow, nullptr, nullptr, TopnImgTrailer{rq.rs->fdata, rq.rs->n_fdata, rq.rs->fdef});
-  } else {
-    hipLaunchKernelGGL(topn_prepare_kernel<false>, dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S,
-                       sl.d_img.get(), sl.d_count.get(), d_overflow, nullptr, nullptr, TopnImgTrailer());
-  }
+  topn_dispatch(v, [&](auto COS, auto RS, auto) {
+    hipLaunchKernelGGL((topn_prepare_kernel<COS, RS>), dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S, sl.d_img.get(),
+                       sl.d_count.get(), topn_overflow_word(sl), va.qn, va.qflag, va.trailer);
+  });
   // the candidate filter: the signatures of the pass's vectors, and the pass's view of the filter behind the query image
-  const bool lsh = topn_lsh_on(h, rq);
   TopnLsh lv;
-  if (lsh)
+  if (v.lsh)
     if (int rc = topn_lsh_sign_pass(h, sl, st, ps, sl.d_img.get(), &lv)) return rc;
   // 1. sample: bucket maxima of the lower bounds of every tile_stride-th tile; 2. threshold (buckets won by known items dropped)
   int n_groups = 0, n_fw = 0;
-  if (int rc = cos            ? topn_launch_stream<0, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
-               : rq.rs && lsh ? topn_launch_stream<0, false, true, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
-               : rq.rs        ? topn_launch_stream<0, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
-               : lsh          ? topn_launch_stream<0, false, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)
-                              : topn_launch_stream<0, false>(h, sl, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups))
-    return rc;
-  if (lsh)   // buckets won by non-candidates of the queries of several vectors
+  if (int rc = topn_launch_stream<0>(h, sl, v, p.S, nt, y.F, n_items, k, nq, p.tile_stride, p.cap, &n_groups)) return rc;
+  if (v.lsh)   // buckets won by non-candidates of the queries of several vectors
     hipLaunchKernelGGL(lsh_drop_buckets_kernel, dim3(8, (unsigned)nq), dim3(256), 0, st, lv, 16 * (int64_t)n_groups, sl.d_bmax.get(), sl.d_bidx.get());
-  hipLaunchKernelGGL(topn_threshold_kernel, dim3((unsigned)nq), dim3(1024), 0, st, sl.d_bmax.get(), sl.d_bidx.get(), n_groups, how_many, k_ptr, k_idx, d_rows,
-                     d_eptr, d_eidx, n_items, p.tile_stride, h->tag_bits.get(), sl.d_tau.get(), cos ? sl.d_qflag.get() : nullptr);
+  hipLaunchKernelGGL(topn_threshold_kernel, dim3((unsigned)nq), dim3(1024), 0, st, sl.d_bmax.get(), sl.d_bidx.get(), n_groups, how_many, kn.ptr, kn.idx, d_rows,
+                     d_eptr, d_eidx, n_items, p.tile_stride, h->tag_bits.get(), sl.d_tau.get(), va.qflag);
   // 3. filter, 4. exact scores of the hits (known items dropped), 5. the N best -- written straight into the slot's pinned
   // block (device-visible host memory: no copy kernel, no copy call)
   // (the filter's waves scatter their own hits into the per-query candidate lists: no kernel in between)
-  if (int rc = cos            ? topn_launch_stream<1, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
-               : rq.rs && lsh ? topn_launch_stream<1, false, true, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
-               : rq.rs        ? topn_launch_stream<1, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
-               : lsh          ? topn_launch_stream<1, false, false, true>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)
-                              : topn_launch_stream<1, false>(h, sl, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw))
-    return rc;
-  if (cos)
-    hipLaunchKernelGGL(topn_rescore_kernel<true>, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr,
-                       sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow,
-                       sl.d_qn.get(), n_items, TopnRescore());
-  else if (rq.rs)
-    hipLaunchKernelGGL((topn_rescore_kernel<false, true>), dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow,
-                       sl.d_vptr, sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(),
-                       d_overflow, nullptr, n_items, *rq.rs);
-  else
-    hipLaunchKernelGGL(topn_rescore_kernel<false>, dim3(8, (unsigned)nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), st, y.F, k, sl.d_vecs, sl.d_vrow, sl.d_vptr,
-                       sl.d_count.get(), p.cap, sl.d_cand.get(), k_ptr, k_idx, d_rows, d_eptr, d_eidx, h->tag_bits.get(), sl.d_pairs.get(), d_overflow,
-                       nullptr, n_items, TopnRescore());
-  if (lsh)   // whatever the streaming tests let through
+  if (int rc = topn_launch_stream<1>(h, sl, v, p.S, nt, y.F, n_items, k, nq, 1, p.cap, &n_fw)) return rc;
+  topn_launch_rescore(h, sl, st, v, va, nq, p.cap, kn, d_rows, d_eptr, d_eidx);
+  if (v.lsh)   // whatever the streaming tests let through
     hipLaunchKernelGGL(lsh_strike_pairs_kernel, dim3(2, (unsigned)nq), dim3(256), 0, st, lv, sl.d_count.get(), TOPN_COUNT_STRIDE, p.cap, sl.d_cand.get(),
                        sl.d_pairs.get());
-  uint8_t* o = sl.h_stage.get();
-  const size_t o_cnt = sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many, o_tau = o_cnt + sizeof(unsigned) * TOPN_FILTER_QUERIES,
-               o_ovf = o_tau + sizeof(float) * TOPN_FILTER_QUERIES;
-  hipLaunchKernelGGL(topn_final_kernel, dim3((unsigned)nq), dim3(256), sizeof(uint64_t) * (size_t)p.cap, st, sl.d_pairs.get(), sl.d_count.get(), p.cap,
-                     how_many, reinterpret_cast<uint64_t*>(o), reinterpret_cast<unsigned*>(o + o_cnt), sl.d_tau.get(), reinterpret_cast<float*>(o + o_tau),
-                     d_overflow, reinterpret_cast<unsigned*>(o + o_ovf));
+  topn_launch_final(sl, st, nq, p.cap, how_many, TopnStage(sl.h_stage.get(), TOPN_FILTER_QUERIES, how_many));
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
 }
@@ -565,12 +626,12 @@ int topn_pass_filter_finish(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
                             std::vector<uint8_t>& failed, bool* any_failed) {
   HIPCHK(h, hipEventSynchronize(sl.ev));
   const int how_many = rq.how_many;
-  const uint8_t* st = sl.h_stage.get();
-  const uint64_t* outp = reinterpret_cast<const uint64_t*>(st);
-  const unsigned* count = reinterpret_cast<const unsigned*>(st + sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many);
-  const float* tau = reinterpret_cast<const float*>(st + sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many + sizeof(unsigned) * TOPN_FILTER_QUERIES);
-  const unsigned wave_overflow = *reinterpret_cast<const unsigned*>(st + sizeof(uint64_t) * (size_t)TOPN_FILTER_QUERIES * (size_t)how_many +
-                                                                    (sizeof(unsigned) + sizeof(float)) * TOPN_FILTER_QUERIES);
+  const TopnStage o(sl.h_stage.get(), TOPN_FILTER_QUERIES, how_many);
+  const uint64_t* outp = o.pairs();
+  const unsigned* count = o.count();
+  const float* tau = o.tau();
+  const unsigned wave_overflow = *o.overflow();
+  const bool lsh = topn_variant(h, rq).lsh;
   failed.assign((size_t)ps.nq, 0);
   *any_failed = false;
   for (int q = 0; q < ps.nq; ++q)
@@ -583,10 +644,10 @@ int topn_pass_filter_finish(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
     const TopnOut o_q = topn_out(rq, (size_t)(ps.q0 + q));
     int n = 0;
     for (int j = 0; j < how_many; ++j) {
-      const uint64_t pr = outp[(size_t)q * how_many + j];
-      if (pr != 0) {
-        o_q.items[j] = (int64_t)(0xffffffffu - (uint32_t)pr);
-        o_q.scores[j] = key_score((uint32_t)(pr >> 32));
+      TopnCand c;
+      if (topn_decode_pair(outp[(size_t)q * how_many + j], &c)) {
+        o_q.items[j] = c.idx;
+        o_q.scores[j] = key_score(c.key);
         ++n;
       } else {
         o_q.items[j] = -1;
@@ -594,7 +655,7 @@ int topn_pass_filter_finish(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
       }
     }
     if (o_q.n) *o_q.n = n;
-    if (topn_lsh_on(h, rq)) h->lsh.q_filter.fetch_add(1);
+    if (lsh) h->lsh.q_filter.fetch_add(1);
     // (rescored mode: a result that is not finite comes back as THE NaN, ranked first -- RecommendIterator.java:105)
     if (n > 0 && !std::isfinite(o_q.scores[0])) {
       if (!rq.bad_q) return fail(h, MALS_INVALID_ARG, TOPN_BAD_VALUE);
@@ -611,7 +672,7 @@ bool topn_dense_only(mals_handle h, int how_many, const mals_rescorer_s* r = nul
 }
 
 // streams, events and pinned result blocks of the slots; every slot stream ordered after the work already on the handle's
-int topn_prepare_slots(mals_handle h, TopnWorkspace* w, const TopnFilterPlan& p) {
+int topn_prepare_slots(mals_handle h, TopnWorkspace* w) {
   for (TopnSlot& sl : w->slot) {
     if (!sl.stream) HIPCHK(h, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
     if (!sl.ev) HIPCHK(h, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
@@ -659,12 +720,9 @@ int topn_finish_slot(mals_handle h, TopnWorkspace* w, int s, const TopnRequest& 
 constexpr int TOPN_BECAUSE_CAP = 4096;
 
 int topn_because_run(mals_handle h, TopnWorkspace* w, const TopnRequest& rq_in) {
-  SideState& y = h->side[MALS_SIDE_Y];
   SideState& x = h->side[MALS_SIDE_X];
   const int k = h->cfg.features, how_many = rq_in.how_many, cap = TOPN_BECAUSE_CAP;
-  const int64_t n_items = y.n_total;
-  const int64_t* k_ptr = h->known_ptr ? h->known_ptr : x.row_ptr;
-  const int32_t* k_idx = h->known_ptr ? h->known_idx : x.col;
+  TopnKnown kn = topn_known(h);
   // known items changed by writes (foldin_host.h): the queries' current sets as a CSR of their own, query q = its row q
   TopnRequest rq = rq_in;
   std::vector<int64_t> own_user, own_ptr, rows;
@@ -687,8 +745,7 @@ int topn_because_run(mals_handle h, TopnWorkspace* w, const TopnRequest& rq_in) 
     HIPCHK(h, hipMemcpyAsync(d_own_ptr.get(), own_ptr.data(), sizeof(int64_t) * own_ptr.size(), hipMemcpyHostToDevice, h->stream));
     if (!own_idx.empty())
       HIPCHK(h, hipMemcpyAsync(d_own_idx.get(), own_idx.data(), sizeof(int32_t) * own_idx.size(), hipMemcpyHostToDevice, h->stream));
-    k_ptr = d_own_ptr.get();
-    k_idx = d_own_idx.get();
+    kn = {d_own_ptr.get(), d_own_idx.get()};
     rq.because_user = own_user.data();
   }
   TopnSlot& sl = w->slot[0];
@@ -696,10 +753,10 @@ int topn_because_run(mals_handle h, TopnWorkspace* w, const TopnRequest& rq_in) 
   HIPCHK(h, sl.d_pairs.reserve((size_t)TOPN_MAX_QUERIES * (size_t)cap, h->stream));
   HIPCHK(h, sl.d_cand.reserve((size_t)TOPN_MAX_QUERIES * (size_t)cap, h->stream));
   HIPCHK(h, sl.d_qn.reserve((size_t)TOPN_MAX_QUERIES, h->stream));
-  const size_t o_cnt = sizeof(uint64_t) * (size_t)TOPN_MAX_QUERIES * (size_t)how_many, o_tau = o_cnt + sizeof(unsigned) * TOPN_MAX_QUERIES,
-               o_ovf = o_tau + sizeof(float) * TOPN_MAX_QUERIES;
-  HIPCHK(h, sl.h_stage.reserve(o_ovf + 16, h->stream));
-  unsigned* d_overflow = sl.d_count.get() + (size_t)TOPN_FILTER_QUERIES * TOPN_COUNT_STRIDE;
+  HIPCHK(h, sl.h_stage.reserve(TopnStage(nullptr, TOPN_MAX_QUERIES, how_many).bytes(), h->stream));
+  const TopnStage o(sl.h_stage.get(), TOPN_MAX_QUERIES, how_many);
+  const TopnVariant v = topn_variant(h, rq);   // cosine
+  const TopnVariantArgs va = topn_variant_args(v, sl, rq);
   std::vector<std::vector<TopnCand>> cand;
   for (int q0 = 0; q0 < rq.n_queries; q0 += TOPN_MAX_QUERIES) {
     TopnPass ps;
@@ -710,26 +767,20 @@ int topn_because_run(mals_handle h, TopnWorkspace* w, const TopnRequest& rq_in) 
     hipLaunchKernelGGL(topn_qnorm_kernel, dim3(1), dim3(64), 0, h->stream, sl.d_vecs, sl.d_vrow, ps.nq, k, sl.d_qn.get());
     cand.assign((size_t)ps.nq, {});
     for (int64_t off = 0;; off += cap) {
-      hipLaunchKernelGGL(topn_known_cand_kernel, dim3((unsigned)ps.nq), dim3(256), 0, h->stream, k_ptr, k_idx, sl.d_rows, off, cap, sl.d_cand.get(),
+      hipLaunchKernelGGL(topn_known_cand_kernel, dim3((unsigned)ps.nq), dim3(256), 0, h->stream, kn.ptr, kn.idx, sl.d_rows, off, cap, sl.d_cand.get(),
                          sl.d_count.get());
-      hipLaunchKernelGGL(topn_rescore_kernel<true>, dim3(8, (unsigned)ps.nq), dim3(64), sizeof(float) * 64 * (size_t)(k + 1), h->stream, y.F, k, sl.d_vecs,
-                         sl.d_vrow, sl.d_vptr, sl.d_count.get(), cap, sl.d_cand.get(), nullptr, nullptr, nullptr, nullptr, nullptr, h->tag_bits.get(),
-                         sl.d_pairs.get(), d_overflow, sl.d_qn.get(), n_items, TopnRescore());
-      uint8_t* o = sl.h_stage.get();
-      hipLaunchKernelGGL(topn_final_kernel, dim3((unsigned)ps.nq), dim3(256), sizeof(uint64_t) * (size_t)cap, h->stream, sl.d_pairs.get(), sl.d_count.get(), cap,
-                         how_many, reinterpret_cast<uint64_t*>(o), reinterpret_cast<unsigned*>(o + o_cnt), sl.d_tau.get(), reinterpret_cast<float*>(o + o_tau),
-                         d_overflow, reinterpret_cast<unsigned*>(o + o_ovf));
+      // (the candidates ARE the known items: nothing to drop but the tag items)
+      topn_launch_rescore(h, sl, h->stream, v, va, ps.nq, cap, TopnKnown{nullptr, nullptr}, nullptr, nullptr, nullptr);
+      topn_launch_final(sl, h->stream, ps.nq, cap, how_many, o);
       HIPCHK(h, hipGetLastError());
       HIPCHK(h, hipStreamSynchronize(h->stream));
-      const uint64_t* outp = reinterpret_cast<const uint64_t*>(o);
-      const unsigned* count = reinterpret_cast<const unsigned*>(o + o_cnt);
       bool more = false;
       for (int q = 0; q < ps.nq; ++q) {
         for (int j = 0; j < how_many; ++j) {
-          const uint64_t pr = outp[(size_t)q * how_many + j];
-          if (pr != 0) cand[(size_t)q].push_back({(uint32_t)(pr >> 32), (int64_t)(0xffffffffu - (uint32_t)pr)});
+          TopnCand c;
+          if (topn_decode_pair(o.pairs()[(size_t)q * how_many + j], &c)) cand[(size_t)q].push_back(c);
         }
-        more = more || count[q] > (unsigned)cap;
+        more = more || o.count()[q] > (unsigned)cap;
       }
       if (!more) break;
     }
@@ -774,7 +825,7 @@ int topn_run(mals_handle h, const TopnRequest& rq) {
     return MALS_OK;
   }
   const TopnFilterPlan p = topn_plan(h, rq.how_many);
-  if (int rc = topn_prepare_slots(h, w, p)) return rc;
+  if (int rc = topn_prepare_slots(h, w)) return rc;
   // whatever the caller's stream still has to do (an iteration, a factor upload) comes first
   HIPCHK(h, hipEventRecord(w->ev_begin, h->stream));
   for (TopnSlot& sl : w->slot) HIPCHK(h, hipStreamWaitEvent(sl.stream, w->ev_begin, 0));
@@ -831,27 +882,9 @@ int topn_run(mals_handle h, const TopnRequest& rq) {
 constexpr int TOPN_FRONT_BULK = 64;
 
 struct TopnTicket {
-  // a small by-user call ...
-  const int64_t* user_idx = nullptr;
-  int n = 0, how_many = 0;
-  bool skip_known = false;
-  int64_t* item_out = nullptr;
-  float* score_out = nullptr;
-  int32_t* n_out = nullptr;
-  // ... or a small call with the caller's own vectors (recommendToAnonymous, recommendToMany: SR:366-441,561-606): n queries,
-  // query q owns vectors [vec_ptr[q], vec_ptr[q+1]) (NULL: one each), optional exclusion lists
-  const float* vectors = nullptr;
-  const int64_t* vec_ptr = nullptr;
-  const int64_t* excl_ptr = nullptr;
-  const int64_t* excl_idx = nullptr;
-  // ... or a small mostSimilarItems call (MostSimilarItemIterator.java:73-120): n queries, query q owns the items
-  // items[item_ptr[q] .. item_ptr[q+1]) (never NULL here), which are also its exclusions
-  const int64_t* items = nullptr;
-  const int64_t* item_ptr = nullptr;
-  // ... (by-user and by-vector calls) with the caller's rescorer, NULL: none -- part of the key of a pass
-  const mals_rescorer_s* rescorer = nullptr;
-  // ... or a whole request of its own
-  const TopnRequest* bulk = nullptr;
+  TopnRequest rq;      // what the call asks for, as its entry point built it
+  bool fold = false;   // small enough to share a pass with other callers' calls (the entry point's size tests); false: the
+                       // call is passes of its own, or no top-N at all, and runs alone in queue order
   int rc = MALS_OK;
   std::string err;
   bool done = false;          // under the front's mutex
@@ -939,7 +972,7 @@ TopnFront* topn_front(mals_handle h) { return static_cast<TopnFront*>(h->tn_fron
 
 // leader only, mutex NOT held: the pass in `fp` (already filled) onto slot s
 int topn_front_enqueue(mals_handle h, TopnWorkspace* w, int s, TopnFrontPass& fp) {
-  if (int rc = topn_prepare_slots(h, w, fp.plan)) return rc;
+  if (int rc = topn_prepare_slots(h, w)) return rc;
   HIPCHK(h, hipEventRecord(w->ev_begin, h->stream));
   HIPCHK(h, hipStreamWaitEvent(w->slot[s].stream, w->ev_begin, 0));
   if (int rc = topn_upload_pass(h, w->slot[s], w->slot[s].stream, fp.rq, fp.ps)) return rc;
@@ -952,10 +985,10 @@ void topn_front_complete(TopnFrontPass& fp, int rc, const std::string& err) {  /
   size_t q0 = 0;   // a coalesced pass: the tickets' queries back to back; a query that is not finite fails its own ticket only
   for (TopnTicket* t : fp.tickets) {
     int trc = rc;
-    if (rc == MALS_OK && !t->bulk && !fp.bad.empty())
-      for (size_t q = q0; q < q0 + (size_t)t->n && q < fp.bad.size(); ++q)
+    if (rc == MALS_OK && !fp.bad.empty())
+      for (size_t q = q0; q < q0 + (size_t)t->rq.n_queries && q < fp.bad.size(); ++q)
         if (fp.bad[q]) trc = MALS_INVALID_ARG;
-    q0 += (size_t)t->n;
+    q0 += (size_t)t->rq.n_queries;
     t->rc = trc;
     if (trc != MALS_OK) t->err = rc != MALS_OK ? err : std::string(TOPN_BAD_VALUE);
     t->done = true;
@@ -1023,39 +1056,15 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
   };
   while (!me->done) {
     TopnTicket* head = f->queue.empty() ? nullptr : f->queue.front();
-    if (head && (head->bulk || topn_dense_only(h, head->how_many, head->rescorer))) {
-      // a request that is passes of its own (or a catalogue the dense path answers): alone on the workspace
+    if (head && (!head->fold || topn_dense_only(h, head->rq.how_many, head->rq.rescorer))) {
+      // a request that is passes of its own (or a catalogue the dense path answers): alone on the workspace, as it is
       while (f->n_busy > 0) finish_oldest();
       if (me->done && head != me) break;   // (own answer arrived while draining: let the successor run it)
       f->queue.pop_front();
       TopnFrontPass one;
       one.tickets.push_back(head);
-      if (head->bulk) {
-        one.rq = *head->bulk;
-        if (one.rq.kind != TOPN_KIND_CALL) ++f->bulk_calls;   // (the writes of foldin_host.h are no recommend calls)
-      } else {
-        one.rq.n_queries = head->n;
-        one.rq.how_many = head->how_many;
-        if (head->vectors) {
-          one.rq.vectors = head->vectors;
-          one.rq.vec_ptr = head->vec_ptr;
-          one.rq.excl_ptr = head->excl_ptr;
-          one.rq.excl_idx = head->excl_idx;
-        } else if (head->items) {
-          one.rq.item_rows = head->items;
-          one.rq.vec_ptr = head->item_ptr;
-          one.rq.excl_ptr = head->item_ptr;
-          one.rq.excl_idx = head->items;
-          one.rq.cosine = true;
-        } else {
-          one.rq.user_idx = head->user_idx;
-          one.rq.skip_known = head->skip_known;
-        }
-        one.rq.item_idx_out = head->item_out;
-        one.rq.score_out = head->score_out;
-        one.rq.n_out = head->n_out;
-        one.rq.rescorer = head->rescorer;
-      }
+      one.rq = head->rq;
+      if (!head->fold && one.rq.kind != TOPN_KIND_CALL) ++f->bulk_calls;   // (the writes of foldin_host.h are no recommend calls)
       if (one.rq.rescorer) {
         rescorer_bind(one.rq.rescorer, one.rs_keep, one.rs_args);
         one.rq.rs = &one.rs_args;
@@ -1075,38 +1084,39 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
       const int kf = h->cfg.features;
       fp.tickets.clear(); fp.users.clear(); fp.skip.clear(); fp.outs.clear();
       fp.items.clear(); fp.vecs.clear(); fp.vptr.assign(1, 0); fp.eptr.assign(1, 0); fp.eidx.clear();
-      const int how_many = head->how_many;
+      const int how_many = head->rq.how_many;
       // a pass holds by-user calls, by-vector calls or mostSimilarItems calls, never two kinds (where its query vectors come
       // from -- X on the device, an uploaded block, rows of Y -- and how they score is per pass)
-      auto kind_of = [](const TopnTicket* t) { return t->vectors ? 1 : t->items ? 2 : 0; };
+      auto kind_of = [](const TopnTicket* t) { return t->rq.vectors ? 1 : t->rq.item_rows ? 2 : 0; };
       const int kind = kind_of(head);
       const bool by_vector = kind == 1;
       bool any_excl = false;
       while (!f->queue.empty()) {
         TopnTicket* t = f->queue.front();
-        if (t->bulk || t->how_many != how_many || kind_of(t) != kind || t->rescorer != head->rescorer || (int)fp.outs.size() + t->n > cap) break;
+        const TopnRequest& r = t->rq;
+        if (!t->fold || r.how_many != how_many || kind_of(t) != kind || r.rescorer != head->rq.rescorer || (int)fp.outs.size() + r.n_queries > cap) break;
         f->queue.pop_front();
         fp.tickets.push_back(t);
-        for (int q = 0; q < t->n; ++q) {
-          if (kind == 2) {
-            const int64_t v0 = t->item_ptr[q], v1 = t->item_ptr[q + 1];
-            fp.items.insert(fp.items.end(), t->items + v0, t->items + v1);
+        for (int q = 0; q < r.n_queries; ++q) {
+          if (kind == 2) {   // (vec_ptr is never NULL here; the query's items are also its exclusions)
+            const int64_t v0 = r.vec_ptr[q], v1 = r.vec_ptr[q + 1];
+            fp.items.insert(fp.items.end(), r.item_rows + v0, r.item_rows + v1);
             fp.vptr.push_back(fp.vptr.back() + (v1 - v0));
             fp.eptr.push_back(fp.vptr.back());
           } else if (by_vector) {
-            const int64_t v0 = t->vec_ptr ? t->vec_ptr[q] : q, v1 = t->vec_ptr ? t->vec_ptr[q + 1] : q + 1;
-            fp.vecs.insert(fp.vecs.end(), t->vectors + v0 * kf, t->vectors + v1 * kf);
+            const int64_t v0 = r.vec_ptr ? r.vec_ptr[q] : q, v1 = r.vec_ptr ? r.vec_ptr[q + 1] : q + 1;
+            fp.vecs.insert(fp.vecs.end(), r.vectors + v0 * kf, r.vectors + v1 * kf);
             fp.vptr.push_back(fp.vptr.back() + (v1 - v0));
-            if (t->excl_ptr && t->excl_idx) {
-              fp.eidx.insert(fp.eidx.end(), t->excl_idx + t->excl_ptr[q], t->excl_idx + t->excl_ptr[q + 1]);
-              any_excl = any_excl || t->excl_ptr[q + 1] > t->excl_ptr[q];
+            if (r.excl_ptr && r.excl_idx) {
+              fp.eidx.insert(fp.eidx.end(), r.excl_idx + r.excl_ptr[q], r.excl_idx + r.excl_ptr[q + 1]);
+              any_excl = any_excl || r.excl_ptr[q + 1] > r.excl_ptr[q];
             }
             fp.eptr.push_back((int64_t)fp.eidx.size());
           } else {
-            fp.users.push_back(t->user_idx[q]);
-            fp.skip.push_back(t->skip_known ? 1 : 0);
+            fp.users.push_back(r.user_idx[q]);
+            fp.skip.push_back(r.skip_known ? 1 : 0);
           }
-          fp.outs.push_back({t->item_out + (size_t)q * how_many, t->score_out + (size_t)q * how_many, t->n_out ? t->n_out + q : nullptr});
+          fp.outs.push_back(topn_out(r, (size_t)q));
         }
       }
       fp.rq = TopnRequest();
@@ -1130,9 +1140,9 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
         fp.rq.skip_known_q = fp.skip.data();
       }
       fp.rq.out_q = fp.outs.data();
-      if (head->rescorer) {
-        fp.rq.rescorer = head->rescorer;
-        rescorer_bind(head->rescorer, fp.rs_keep, fp.rs_args);
+      if (head->rq.rescorer) {
+        fp.rq.rescorer = head->rq.rescorer;
+        rescorer_bind(head->rq.rescorer, fp.rs_keep, fp.rs_args);
         fp.rq.rs = &fp.rs_args;
       }
       fp.bad.assign((size_t)fp.rq.n_queries, 0);
@@ -1170,12 +1180,15 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
   }
 }
 
-// every mals_recommend* call ends here
-int topn_front_submit(mals_handle h, TopnTicket& me) {
+// every mals_recommend* call ends here: `rq` as a ticket in the handle's queue; fold: it may share a pass with other callers'
+int topn_front_submit(mals_handle h, const TopnRequest& rq, bool fold) {
+  TopnTicket me;
+  me.rq = rq;
+  me.fold = fold;
   TopnFront* f = topn_front(h);
   std::unique_lock<std::mutex> lk(f->mu);
   ++f->calls;
-  f->queries += (uint64_t)(me.bulk ? me.bulk->n_queries : me.n);
+  f->queries += (uint64_t)rq.n_queries;
   f->queue.push_back(&me);
   for (;;) {
     if (me.done) break;
