@@ -478,7 +478,8 @@ int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64
  * ServerRecommender (online/src/net/myrrix/online/ServerRecommender.java) changes the model on every write between two
  * generations; these calls do it to the X, Y and known items resident on the device, in the reference's arithmetic (every
  * result bit-identical to the CPU restatement tests/foldin_oracle.py).  For handles OUTSIDE a group: a member's handle is
- * refused (MALS_INVALID_ARG; the mals_group_* twins are a later addition).  Rows are dense indices (user = row of X,
+ * refused (MALS_INVALID_ARG); a group is written and read through the mals_group_* twins further down, which route every
+ * user's known items to their owner.  Rows are dense indices (user = row of X,
  * item = row of Y); mapping ids, the candidate filter, clustering, tags and generationManager.append stay with the caller.
  * THREADS: every call below may be made from any thread while mals_recommend* / similarity calls run on the same handle.
  * Each (but mals_foldin_stats) is an exclusive ticket in the serving front's queue -- mals_recommend_to_anonymous is two,
@@ -869,6 +870,71 @@ int mals_group_recommended_because(mals_group g, const int64_t* user_idx, const 
                                    int64_t* item_idx_out, float* score_out, int32_t* n_out);
 /* slice bounds of a side after its matrix was set: bounds_out[world+1] */
 int mals_group_bounds(mals_group g, int side, int64_t* bounds_out);
+
+/* ---- the online write path on a group: the twins of mals_set_preferences ... ---------------------------------------
+ * Semantics, arguments, status_out, return codes and failure texts are the single-handle calls' (above), rows are dense
+ * global indices.  For groups whose ranks all live in this process (mals_group_create with either backend, or
+ * mals_group_create_rank with world 1); on a rank of a multi-process group every call below is MALS_INVALID_ARG -- like
+ * mals_group_recommend, it cannot reach another process's owner.
+ * WRITES (set_foldin_solver, set_foldin_learn_rate, set_preferences, remove_preferences, grow_factor_rows) are a
+ * replicated state machine: every member holds complete replicas of X and Y, the update kernels are deterministic, so
+ * every local member applies the same batch in the same order to its own replicas and nothing is exchanged.  Afterwards
+ * every member's X and Y are bit for bit what ONE handle holding the whole model would hold after the same call.  A
+ * write holds the serving fronts of all members at once (the single-handle call's exclusive ticket, on each), enqueues
+ * every member's kernels and only then waits for each: the devices work side by side.  The group orders its writes with a
+ * lock of its own -- two writes from two threads reach every member in the same order (updates that share a row do not
+ * commute).  Reads take no group-wide lock; a read racing a write sees, per member, the model before it or after it.
+ * KNOWN ITEMS stay with their owner: user u belongs to the member whose slice of X holds its row (mals_group_bounds),
+ * users past the installed matrix (rows of mals_group_grow_factor_rows) to the last rank.  Only the owner records the
+ * items a write adds, only the owner decides whether a removal applies and whether it empties the user; every member
+ * zeroes the rows of the emptied users.  mals_group_recommend and mals_group_recommended_because route grown users to the
+ * last rank's member.  A new generation drops these overlays on every member: mals_group_set_matrix of side X,
+ * mals_ingest_install_group, mals_group_ingest_finish (and mals_group_set_factor_rows of side X forgets the grown users).
+ * ITERATIONS afterwards: a half-iteration of a side solves the rows of that side's installed matrix; rows past it (grown
+ * rows) keep the values the writes gave them, on every member alike, and count in the Gramian of the opposite side's
+ * half-iteration like every other row of the replica.  The replicas stay bitwise equal either way.
+ * mals_group_foldin_stats: out6 as mals_foldin_stats; the counters count each update of a group write once (not once per
+ * member), the two device times are the maximum over the members.
+ * READS (estimate_preferences, anonymous_features, recommend_to_anonymous, estimate_for_anonymous): any member answers
+ * (replicas and solvers are complete everywhere); successive calls rotate over the local members, so W devices serve W
+ * callers.  Every answer is bit-identical to the single handle's.  Rescorers and the candidate filter on groups stay out
+ * of scope. */
+int mals_group_set_foldin_solver(mals_group g, int side, mals_solver s);
+int mals_group_set_foldin_learn_rate(mals_group g, double rate);
+int mals_group_foldin_stats(mals_group g, int64_t* out6);
+int mals_group_set_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value,
+                               int32_t* status_out);
+int mals_group_remove_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,
+                                  int64_t* n_removed_out);
+int mals_group_grow_factor_rows(mals_group g, int side, int64_t n_rows_total);
+int mals_group_estimate_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out);
+int mals_group_anonymous_features(mals_group g, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                                  float* out, int32_t* status_out);
+int mals_group_recommend_to_anonymous(mals_group g, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                                      int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out);
+int mals_group_estimate_for_anonymous(mals_group g, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr,
+                                      const int64_t* item_row, const float* values, float* out, int32_t* status_out);
+
+/* ---- a digest of a factor replica, on the device -------------------------------------------------------------------
+ * The proof that replicas agree without copying them to the host.  The digest of rows [row_begin, row_begin + n_rows) of a
+ * replica with k = features columns is the sum modulo 2^64, over the elements of the range, of term(j, bits): j = the
+ * element's global flat index row * k + f, bits = the 32 bits of the float, and in uint64 arithmetic
+ *     z = j * 0x9E3779B97F4A7C15 + bits;   z ^= z >> 32;   z *= 0xD6E8FEB86659FD93;   z ^= z >> 32;   term = z.
+ * A sum, so any reduction order gives the same number and the digests of adjacent ranges add up (mod 2^64) to the digest
+ * of their union -- a caller checks only the bands it touched.  It sees a value in the wrong row (j enters the mix),
+ * tells -0.0 from 0.0 and one NaN payload from another (the bits enter, not the value); a range of 0 rows has digest 0.
+ * It is a checksum against divergence, not a cryptographic hash.
+ *   mals_factor_digest: one streaming pass on the device (16-byte loads; csrc/factor_digest.h), a ticket of the serving
+ *     front: it sees the model between two writes, never the middle of one.  Members of a group are allowed.
+ *   mals_group_replica_digest: the same range on every local member, taken with all members' fronts held at once, i.e.
+ *     between the same two group writes; out_per_local_member[i] for local member i; *all_equal_out (nullable) = 1 iff
+ *     they are all the same number.  Single-process groups only, like the write path.
+ *   mals_factor_digest_host: the same arithmetic on the host over rows[n_rows][features] (the rows of the range, not the
+ *     whole replica), no device -- what another runtime compares its own copy with. */
+int mals_factor_digest(mals_handle h, int side, int64_t row_begin, int64_t n_rows, uint64_t* out);
+int mals_group_replica_digest(mals_group g, int side, int64_t row_begin, int64_t n_rows, uint64_t* out_per_local_member,
+                              int32_t* all_equal_out);
+int mals_factor_digest_host(const float* rows, int32_t features, int64_t row_begin, int64_t n_rows, uint64_t* out);
 
 /* iterateXFromY / iterateYFromX (ALS:340-389) and call() (ALS:176-262) on the group; arguments as for
  * mals_half_iteration / mals_factorize. */

@@ -16,7 +16,8 @@ Importing the package does not need a GPU; creating an ALSCore does, and fails l
 one.  There is no CPU fallback anywhere in this package.
 """
 from . import _lib
-from .core import ALSCore, Cancelled, HostSolver, IllConditioned, MalsError, Rescorer, SingularSystem, lsh_max_bits_differing
+from .core import (ALSCore, Cancelled, HostSolver, IllConditioned, MalsError, Rescorer, SingularSystem, factor_digest_host,
+                   lsh_max_bits_differing)
 from .factorizer import (AlternatingLeastSquares, ExecutionException, InterruptedException,
                          MatrixFactorizer, MatrixUtils, SingularMatrixSolverException,
                          SolverException, System)
@@ -26,7 +27,7 @@ from .ingest import Ingest, readInputRecords
 from .serializer import GenerationSerializer, SerializedGeneration
 from ._lib import (FLAG_LOSS_IGNORES_UNSPECIFIED, FLAG_RECONSTRUCT_R, SIDE_X, SIDE_Y)
 
-__all__ = ["lsh_max_bits_differing", "GroupALS", "plan_shards", "GenerationSerializer", "SerializedGeneration", "ALSCore", "Rescorer", "HostSolver", "IllConditioned", "Generation", "Solver", "Ingest", "readInputRecords",
+__all__ = ["lsh_max_bits_differing", "factor_digest_host", "GroupALS", "plan_shards", "GenerationSerializer", "SerializedGeneration", "ALSCore", "Rescorer", "HostSolver", "IllConditioned", "Generation", "Solver", "Ingest", "readInputRecords",
            "IllConditionedSolverException", "MalsError", "SingularSystem", "Cancelled", "AlternatingLeastSquares",
            "MatrixFactorizer", "MatrixUtils", "System", "ExecutionException",
            "InterruptedException", "SolverException", "SingularMatrixSolverException",

@@ -242,6 +242,19 @@ SYMBOLS = {
     "mals_group_most_similar_items": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
     "mals_group_similarity_to_item": (ctypes.c_int, [_H, ctypes.c_int64, _P, _I32, _P]),
     "mals_group_recommended_because": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
+    "mals_group_set_foldin_solver": (ctypes.c_int, [_H, ctypes.c_int, _H]),
+    "mals_group_set_foldin_learn_rate": (ctypes.c_int, [_H, ctypes.c_double]),
+    "mals_group_foldin_stats": (ctypes.c_int, [_H, _P]),
+    "mals_group_set_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P, _P]),
+    "mals_group_remove_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
+    "mals_group_grow_factor_rows": (ctypes.c_int, [_H, ctypes.c_int, _I64]),
+    "mals_group_estimate_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P]),
+    "mals_group_anonymous_features": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P]),
+    "mals_group_recommend_to_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "mals_group_estimate_for_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P, _P]),
+    "mals_factor_digest": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, ctypes.POINTER(ctypes.c_uint64)]),
+    "mals_group_replica_digest": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, _P, ctypes.POINTER(_I32)]),
+    "mals_factor_digest_host": (ctypes.c_int, [_P, _I32, _I64, _I64, ctypes.POINTER(ctypes.c_uint64)]),
     "mals_group_half_iteration": (ctypes.c_int, [_H, ctypes.c_int]),
     "mals_group_factorize": (ctypes.c_int, [_H, ctypes.c_double, _I32, _I32, _I32, _P, _I32, _P, _I32,
                                             ctypes.POINTER(_I32), ctypes.POINTER(ctypes.c_double)]),

@@ -112,6 +112,19 @@ def _item_queries(items):
     return flat, ptr
 
 
+def factor_digest_host(rows, row_begin=0):
+    """mals_factor_digest_host: the digest mals_factor_digest gives for rows [row_begin, row_begin + len(rows)) of a replica
+    that holds `rows` (n x features float32) there.  Host only: no handle, no device."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[1] < 1:
+        raise ValueError("rows must be n x features")
+    out = ctypes.c_uint64(0)
+    rc = _lib.load().mals_factor_digest_host(rows.ctypes.data_as(ctypes.c_void_p), rows.shape[1], int(row_begin), rows.shape[0], ctypes.byref(out))
+    if rc != _lib.OK:
+        raise MalsError(rc, "mals_factor_digest_host: bad arguments")
+    return out.value
+
+
 def lsh_max_bits_differing(sample_ratio, num_hashes=20):
     """maxBitsDiffering of LocationSensitiveHash (LocationSensitiveHash.java:98-108) for model.lsh.sampleRatio and
     model.lsh.numHashes; may be -1.  Host only: no handle, no device."""
@@ -698,6 +711,15 @@ class ALSCore:
             self._chk(rc)
         return out, st
 
+    def factor_digest(self, side, row_begin=0, n_rows=None):
+        """mals_factor_digest: the 64-bit digest of rows [row_begin, row_begin + n_rows) of side's replica, computed on the
+        device between two writes (n_rows None: to the end).  Equals factor_digest_host of the same rows."""
+        if n_rows is None:
+            n_rows = self.factor_device_ptr(side)[1] - int(row_begin)
+        out = ctypes.c_uint64(0)
+        self._chk(self._L.mals_factor_digest(self._h, side, int(row_begin), int(n_rows), ctypes.byref(out)))
+        return out.value
+
     def reconstruction_error(self):
         """ReconstructionEvaluator's sum and count over the local user rows (mean = sum / count)."""
         sm, cnt = ctypes.c_double(0.0), ctypes.c_int64(0)
@@ -753,5 +775,5 @@ class ALSCore:
         return {name: getattr(st, name) for name, _ in _lib.Stats._fields_ if name not in ("struct_size", "reserved")}
 
 
-__all__ = ["ALSCore", "HostSolver", "MalsError", "SingularSystem", "Cancelled", "IllConditioned", "SIDE_X", "SIDE_Y",
+__all__ = ["ALSCore", "HostSolver", "factor_digest_host", "MalsError", "SingularSystem", "Cancelled", "IllConditioned", "SIDE_X", "SIDE_Y",
            "FLAG_RECONSTRUCT_R", "FLAG_LOSS_IGNORES_UNSPECIFIED"]

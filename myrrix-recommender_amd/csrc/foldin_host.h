@@ -184,6 +184,24 @@ int foldin_exclusive(mals_handle h, const std::function<int()>& fn, const std::s
   return rc;
 }
 
+// fn with the fronts of ALL the handles held at once (the members of a group): a ticket of hs[0] whose call is a ticket of
+// hs[1], and so on; fn runs innermost, on whichever thread leads the last front.  Nothing else nests tickets and the order
+// is always hs[0] first, so two such calls cannot wait for each other.  A thread that waits in a handle's front may be made
+// its leader and then runs other callers' passes there: it is on that handle's device for as long as it is inside.
+int foldin_exclusive_all(mals_handle* hs, int n, int i, const std::function<int()>& fn) {
+  if (i == n) return fn();
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipSetDevice(hs[i]->cfg.device) != hipSuccess) return MALS_HIP_ERROR;
+  const std::function<int()> inner = [&]() -> int { return foldin_exclusive_all(hs, n, i + 1, fn); };
+  TopnRequest rq;
+  rq.kind = TOPN_KIND_CALL;
+  rq.call = &inner;
+  rq.how_many = 1;
+  const int rc = topn_front_submit(hs[i], rq, false);
+  (void)hipSetDevice(dev);
+  return rc;
+}
+
 int foldin_lds_limit(std::string& msg) {
   static std::once_flag once;
   static hipError_t e = hipSuccess;
@@ -214,13 +232,16 @@ uint32_t& foldin_slot(std::vector<int64_t>& keys, std::vector<uint32_t>& vals, i
 }
 
 // ---- mals_set_preferences -------------------------------------------------------------------------------------------
-int foldin_set_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const float* value, int32_t* status_out,
-                   std::string& msg) {
-  FoldinState& fs = *foldin_state(h);
-  SideState& x = h->side[MALS_SIDE_X];
-  SideState& y = h->side[MALS_SIDE_Y];
-  const int k = h->cfg.features;
-  if (int rc = foldin_lds_limit(msg)) return rc;
+// A batch runs in three steps, so that a group can have every member's kernels enqueued before it waits for any of them
+// (mals_group_set_preferences): the level plan (the same for every replica the batch goes to), the enqueue half (uploads,
+// the level kernels and the status copy on the handle's stream, no wait) and the collect half (the wait and the host-side
+// bookkeeping).  One handle runs the three back to back.
+struct FoldinPlan {
+  std::vector<int64_t> off, order;   // updates of level l: order[off[l] .. off[l + 1])
+  uint32_t n_levels = 0;
+};
+
+void foldin_set_plan(FoldinState& fs, int64_t n, const int64_t* urow, const int64_t* irow, FoldinPlan& p) {
   // levels: 1 + the larger level of the last update of the same X row and of the same Y row
   size_t cap = 16;
   while (cap < 2 * (size_t)n) cap <<= 1;
@@ -237,12 +258,26 @@ int foldin_set_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t*
     level[(size_t)t] = lu = li = l;
     n_levels = std::max(n_levels, l);
   }
-  std::vector<int64_t> off((size_t)n_levels + 2, 0);
+  std::vector<int64_t>& off = p.off;
+  off.assign((size_t)n_levels + 2, 0);
   for (int64_t t = 0; t < n; ++t) ++off[level[(size_t)t] + 1];
   for (uint32_t l = 1; l <= n_levels + 1; ++l) off[l] += off[l - 1];
   std::vector<int64_t> pos(off.begin(), off.end());
-  std::vector<int64_t> order((size_t)n);
-  for (int64_t t = 0; t < n; ++t) order[(size_t)pos[level[(size_t)t]]++] = t;
+  p.order.resize((size_t)n);
+  for (int64_t t = 0; t < n; ++t) p.order[(size_t)pos[level[(size_t)t]]++] = t;
+  p.n_levels = n_levels;
+}
+
+int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const float* value, const FoldinPlan& p,
+                       std::string& msg) {
+  FoldinState& fs = *foldin_state(h);
+  SideState& x = h->side[MALS_SIDE_X];
+  SideState& y = h->side[MALS_SIDE_Y];
+  const int k = h->cfg.features;
+  if (int rc = foldin_lds_limit(msg)) return rc;
+  const std::vector<int64_t>& off = p.off;
+  const std::vector<int64_t>& order = p.order;
+  const uint32_t n_levels = p.n_levels;
   // level order on the device: user rows | item rows | values, one copy
   const size_t bytes = sizeof(int64_t) * 2 * (size_t)n + sizeof(float) * (size_t)n;
   FCHK(msg, fs.h_stage.reserve(std::max(bytes, sizeof(int32_t) * (size_t)n), h->stream));
@@ -277,6 +312,18 @@ int foldin_set_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t*
   FCHK(msg, hipEventRecord(fs.ev[1], h->stream));
   int32_t* hs = reinterpret_cast<int32_t*>(fs.h_stage.get());
   FCHK(msg, hipMemcpyAsync(hs, fs.d_status.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  return MALS_OK;
+}
+
+// the known items of the applied updates are recorded for the users in [own_lo, own_hi) only: on a group the owner of a
+// user keeps its overlay (a single handle owns every user foldin_check_pairs let through)
+int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const FoldinPlan& p, int64_t own_lo, int64_t own_hi,
+                       int32_t* status_out, std::string& msg) {
+  FoldinState& fs = *foldin_state(h);
+  SideState& x = h->side[MALS_SIDE_X];
+  const std::vector<int64_t>& order = p.order;
+  const uint32_t n_levels = p.n_levels;
+  const int32_t* hs = reinterpret_cast<const int32_t*>(fs.h_stage.get());
   FCHK(msg, hipStreamSynchronize(h->stream));
   float dev_ms = 0.f;
   FCHK(msg, hipEventElapsedTime(&dev_ms, fs.ev[0], fs.ev[1]));
@@ -303,7 +350,8 @@ int foldin_set_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t*
       continue;
     }
     ++applied;
-    foldin_overlay_add(fs, urow[t] - x.row_offset, (int32_t)irow[t]);   // knownItemIDs.get(userID).add(itemID) (:813-836)
+    if (urow[t] >= own_lo && urow[t] < own_hi)
+      foldin_overlay_add(fs, urow[t] - x.row_offset, (int32_t)irow[t]);   // knownItemIDs.get(userID).add(itemID) (:813-836)
   }
   std::atomic<int64_t>* c = h->foldin_counters;
   c[0] += applied;
@@ -321,14 +369,28 @@ int foldin_set_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t*
   return first;
 }
 
+int foldin_set_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const float* value, int32_t* status_out,
+                   std::string& msg) {
+  FoldinPlan p;
+  foldin_set_plan(*foldin_state(h), n, urow, irow, p);
+  if (int rc = foldin_set_enqueue(h, n, urow, irow, value, p, msg)) return rc;
+  return foldin_set_collect(h, n, urow, irow, p, std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max(), status_out, msg);
+}
+
 // ---- mals_remove_preferences ----------------------------------------------------------------------------------------
-int foldin_remove_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, int64_t* removed_out, int64_t* n_removed_out,
-                      std::string& msg) {
+// Three steps as well (mals_group_remove_preferences): the decision, which is the known items' holder's alone -- the pairs
+// whose user lies in [own_lo, own_hi) against this handle's sets; (position in the batch, user) of every user a pair
+// empties is appended to `emptied` -- then zeroing those rows of X (enqueue) and the wait (collect), which every replica
+// runs with the same list.
+int foldin_remove_decide(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, int64_t own_lo, int64_t own_hi,
+                         std::vector<std::pair<int64_t, int64_t>>& emptied, std::string& msg) {
   FoldinState& fs = *foldin_state(h);
   SideState& x = h->side[MALS_SIDE_X];
+  auto mine = [&](int64_t t) { return urow[t] >= own_lo && urow[t] < own_hi; };
   // every user of the batch without a replaced set gets one first: its base row and additions, fetched together
   std::vector<int64_t> need;
   for (int64_t t = 0; t < n; ++t) {
+    if (!mine(t)) continue;
     const int64_t lr = urow[t] - x.row_offset;
     if (!fs.replaced.count(lr)) need.push_back(lr);
   }
@@ -340,35 +402,64 @@ int foldin_remove_run(mals_handle h, int64_t n, const int64_t* urow, const int64
     if (need[j] < (int64_t)fs.head.size()) fs.head[(size_t)need[j]] = UINT32_MAX;
     fs.replaced[need[j]].swap(full[j]);   // (an empty set: a user without known items, whose removals are ignored)
   }
-  std::vector<int64_t> removed;
   for (int64_t t = 0; t < n; ++t) {
+    if (!mine(t)) continue;
     std::vector<int32_t>& v = fs.replaced[urow[t] - x.row_offset];
     auto p = std::lower_bound(v.begin(), v.end(), (int32_t)irow[t]);
     if (p == v.end() || *p != (int32_t)irow[t]) continue;  // an unknown user, or an item it does not know: ignored (:1024-1033)
     v.erase(p);
-    if (v.empty()) removed.push_back(urow[t]);  // the user goes (:1040-1058)
+    if (v.empty()) emptied.push_back({t, urow[t]});  // the user goes (:1040-1058)
   }
-  if (!removed.empty()) {
-    DeviceBuffer<int64_t> d;
-    FCHK(msg, d.alloc(removed.size()));
-    FCHK(msg, hipMemcpyAsync(d.get(), removed.data(), sizeof(int64_t) * removed.size(), hipMemcpyHostToDevice, h->stream));
-    const int64_t nk = (int64_t)removed.size() * h->cfg.features;
-    hipLaunchKernelGGL(foldin_zero_rows_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, h->stream, x.F, h->cfg.features, d.get(),
-                       (int64_t)removed.size());
-    FCHK(msg, hipGetLastError());
-    FCHK(msg, hipStreamSynchronize(h->stream));
-  }
+  return MALS_OK;
+}
+
+// `removed` (host) and `d` (its device copy) stay the caller's until foldin_remove_collect has returned
+int foldin_remove_enqueue(mals_handle h, const std::vector<int64_t>& removed, DeviceBuffer<int64_t>& d, std::string& msg) {
+  if (removed.empty()) return MALS_OK;
+  SideState& x = h->side[MALS_SIDE_X];
+  FCHK(msg, d.alloc(removed.size()));
+  FCHK(msg, hipMemcpyAsync(d.get(), removed.data(), sizeof(int64_t) * removed.size(), hipMemcpyHostToDevice, h->stream));
+  const int64_t nk = (int64_t)removed.size() * h->cfg.features;
+  hipLaunchKernelGGL(foldin_zero_rows_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, h->stream, x.F, h->cfg.features, d.get(),
+                     (int64_t)removed.size());
+  FCHK(msg, hipGetLastError());
+  return MALS_OK;
+}
+
+int foldin_remove_collect(mals_handle h, bool any_removed, std::string& msg) {
+  if (any_removed) FCHK(msg, hipStreamSynchronize(h->stream));
   for (int s = 0; s < 2; ++s) {
     h->side[s].G_valid = false;
     ++h->side[s].F_epoch;
   }
+  return MALS_OK;
+}
+
+int foldin_remove_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, int64_t* removed_out, int64_t* n_removed_out,
+                      std::string& msg) {
+  std::vector<std::pair<int64_t, int64_t>> emptied;
+  if (int rc = foldin_remove_decide(h, n, urow, irow, std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max(), emptied, msg))
+    return rc;
+  std::vector<int64_t> removed;
+  for (const auto& e : emptied) removed.push_back(e.second);
+  DeviceBuffer<int64_t> d;
+  if (int rc = foldin_remove_enqueue(h, removed, d, msg)) return rc;
+  if (int rc = foldin_remove_collect(h, !removed.empty(), msg)) return rc;
   if (removed_out) std::copy(removed.begin(), removed.end(), removed_out);
   if (n_removed_out) *n_removed_out = (int64_t)removed.size();
   return MALS_OK;
 }
 
 // ---- mals_grow_factor_rows ------------------------------------------------------------------------------------------
-int foldin_grow_run(mals_handle h, int side, int64_t n_rows, std::string& msg) {
+// Two steps (mals_group_grow_factor_rows enqueues every member's copies before it waits for any): the new blocks and the
+// copies into them on the handle's stream, then the wait and the swap.
+struct FoldinGrow {
+  DeviceBuffer<float> rows;      // the larger replica, when the capacity did not do
+  DeviceBuffer<uint32_t> bits;   // the longer userTagIDs mask (side Y)
+  bool grows = false;
+};
+
+int foldin_grow_enqueue(mals_handle h, int side, int64_t n_rows, FoldinGrow& gw, std::string& msg) {
   SideState& s = h->side[side];
   const int k = h->cfg.features;
   if (s.F != s.F_own.get()) {
@@ -380,36 +471,53 @@ int foldin_grow_run(mals_handle h, int side, int64_t n_rows, std::string& msg) {
     return MALS_INVALID_ARG;
   }
   if (n_rows == s.n_total) return MALS_OK;
+  gw.grows = true;
   const size_t need = (size_t)n_rows * k, have = (size_t)s.n_total * k;
+  float* rows = s.F;
   if (s.F_own.capacity() < need) {  // capacity doubling: a stream of new users does not copy the replica each time
-    DeviceBuffer<float> nb;
-    FCHK(msg, nb.alloc(std::max(need, 2 * s.F_own.capacity())));
-    FCHK(msg, hipMemcpyAsync(nb.get(), s.F, sizeof(float) * have, hipMemcpyDeviceToDevice, h->stream));
-    FCHK(msg, hipStreamSynchronize(h->stream));
-    s.F_own = std::move(nb);
-    s.F = s.F_own.get();
+    FCHK(msg, gw.rows.alloc(std::max(need, 2 * s.F_own.capacity())));
+    FCHK(msg, hipMemcpyAsync(gw.rows.get(), s.F, sizeof(float) * have, hipMemcpyDeviceToDevice, h->stream));
+    rows = gw.rows.get();
   }
-  FCHK(msg, hipMemsetAsync(s.F + have, 0, sizeof(float) * (need - have), h->stream));
+  FCHK(msg, hipMemsetAsync(rows + have, 0, sizeof(float) * (need - have), h->stream));
   if (side == MALS_SIDE_Y && h->tag_bits.get()) {  // userTagIDs: the new items are no tags
     const size_t old_words = ((size_t)((h->tag_bits_items + 31) / 32) + 1) & ~(size_t)1;
     const size_t words = ((size_t)((n_rows + 31) / 32) + 1) & ~(size_t)1;
     const size_t tail = sizeof(unsigned long long) / sizeof(uint32_t);
-    DeviceBuffer<uint32_t> bits;
-    FCHK(msg, bits.alloc(words + tail));
-    FCHK(msg, hipMemsetAsync(bits.get(), 0, sizeof(uint32_t) * (words + tail), h->stream));
-    FCHK(msg, hipMemcpyAsync(bits.get(), h->tag_bits.get(), sizeof(uint32_t) * old_words, hipMemcpyDeviceToDevice, h->stream));
-    FCHK(msg, hipMemcpyAsync(bits.get() + words, h->tag_bits.get() + old_words, sizeof(uint32_t) * tail, hipMemcpyDeviceToDevice, h->stream));
-    FCHK(msg, hipStreamSynchronize(h->stream));
-    h->tag_bits = std::move(bits);
+    FCHK(msg, gw.bits.alloc(words + tail));
+    FCHK(msg, hipMemsetAsync(gw.bits.get(), 0, sizeof(uint32_t) * (words + tail), h->stream));
+    FCHK(msg, hipMemcpyAsync(gw.bits.get(), h->tag_bits.get(), sizeof(uint32_t) * old_words, hipMemcpyDeviceToDevice, h->stream));
+    FCHK(msg, hipMemcpyAsync(gw.bits.get() + words, h->tag_bits.get() + old_words, sizeof(uint32_t) * tail, hipMemcpyDeviceToDevice, h->stream));
+  }
+  return MALS_OK;
+}
+
+// owns_grown_users (side X): the new users' known items are this handle's
+int foldin_grow_finish(mals_handle h, int side, int64_t n_rows, FoldinGrow& gw, bool owns_grown_users, std::string& msg) {
+  if (!gw.grows) return MALS_OK;
+  SideState& s = h->side[side];
+  FCHK(msg, hipStreamSynchronize(h->stream));
+  if (gw.rows) {
+    s.F_own = std::move(gw.rows);
+    s.F = s.F_own.get();
+  }
+  if (gw.bits) {
+    h->tag_bits = std::move(gw.bits);
     h->tag_bits_items = n_rows;
   }
-  FCHK(msg, hipStreamSynchronize(h->stream));
   s.n_total = n_rows;
   s.G_valid = false;
   ++s.F_epoch;
-  // grown users are this handle's when its users already reached the end of the old replica (a single handle)
-  if (side == MALS_SIDE_X && foldin_user_rows_end(h) >= (int64_t)(have / k)) h->grown_users_end.store(n_rows, std::memory_order_release);
+  if (side == MALS_SIDE_X && owns_grown_users) h->grown_users_end.store(n_rows, std::memory_order_release);
   return MALS_OK;
+}
+
+int foldin_grow_run(mals_handle h, int side, int64_t n_rows, std::string& msg) {
+  // grown users are this handle's when its users already reached the end of the old replica (a single handle)
+  const bool owns = foldin_user_rows_end(h) >= h->side[side].n_total;
+  FoldinGrow gw;
+  if (int rc = foldin_grow_enqueue(h, side, n_rows, gw, msg)) return rc;
+  return foldin_grow_finish(h, side, n_rows, gw, owns, msg);
 }
 
 // ---- mals_anonymous_features / mals_estimate_for_anonymous ----------------------------------------------------------

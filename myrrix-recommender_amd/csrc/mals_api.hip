@@ -11,6 +11,8 @@
 #include "host_solver.h"
 #include "topn_kernels.h"
 #include "foldin_kernels.h"
+#define MALS_FACTOR_DIGEST_KERNEL
+#include "factor_digest.h"
 #include "mals_internal.h"
 #include "hip_buffer.h"
 #include "band_plan.h"
@@ -2994,11 +2996,38 @@ void malsi_mark_group_member(mals_handle h) {
   if (h) h->group_member = true;
 }
 
-static int foldin_refuse(mals_handle h, const char* call) {
-  if (h->group_member)
-    return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": not for a member of a group (the mals_group_* twins are not there yet)").c_str());
+// via_group: the call comes from the member's group (a mals_group_* twin), which routes the known items to their owner
+static int foldin_refuse(mals_handle h, const char* call, bool via_group = false) {
+  if (h->group_member && !via_group)
+    return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": not for a member of a group (writes and fold-in reads go through the group: mals_group_set_preferences ...)").c_str());
   if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
   return MALS_OK;
+}
+
+// inside a ticket: the solver's factors onto the handle's device (ipiv: the inverse of its pivot permutation)
+static int foldin_solver_install(mals_handle h, int side, mals_solver s, const std::vector<int32_t>& ipiv, std::string& msg) {
+  const int k = h->cfg.features;
+  FoldinSide& fs = foldin_state(h)->solver[side];
+  fs.present = false;
+  if (!s) return MALS_OK;
+  if (!fs.a.get()) {
+    FCHK(msg, fs.a.alloc((size_t)k * k));
+    FCHK(msg, fs.tau.alloc((size_t)k));
+    FCHK(msg, fs.ipiv.alloc((size_t)k));
+  }
+  FCHK(msg, hipMemcpyAsync(fs.a.get(), s->qr.factors(), sizeof(double) * (size_t)k * k, hipMemcpyHostToDevice, h->stream));
+  FCHK(msg, hipMemcpyAsync(fs.tau.get(), s->qr.taus(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, h->stream));
+  FCHK(msg, hipMemcpyAsync(fs.ipiv.get(), ipiv.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, h->stream));
+  FCHK(msg, hipStreamSynchronize(h->stream));
+  fs.present = true;
+  return MALS_OK;
+}
+
+static std::vector<int32_t> foldin_solver_ipiv(mals_solver s, int k) {
+  std::vector<int32_t> ipiv((size_t)k);
+  if (s)
+    for (int j = 0; j < k; ++j) ipiv[(size_t)s->qr.pivots()[j]] = j;
+  return ipiv;
 }
 
 int mals_set_foldin_solver(mals_handle h, int side, mals_solver s) {
@@ -3006,26 +3035,9 @@ int mals_set_foldin_solver(mals_handle h, int side, mals_solver s) {
   if (int rc = foldin_refuse(h, "mals_set_foldin_solver")) return rc;
   const int k = h->cfg.features;
   if (s && s->qr.dim() != k) return topn_fail(h, MALS_INVALID_ARG, "mals_set_foldin_solver: the solver's dimension is not the handle's features");
-  std::vector<int32_t> ipiv((size_t)k);
-  if (s)
-    for (int j = 0; j < k; ++j) ipiv[(size_t)s->qr.pivots()[j]] = j;
+  const std::vector<int32_t> ipiv = foldin_solver_ipiv(s, k);
   std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    FoldinSide& fs = foldin_state(h)->solver[side];
-    fs.present = false;
-    if (!s) return MALS_OK;
-    if (!fs.a.get()) {
-      FCHK(msg, fs.a.alloc((size_t)k * k));
-      FCHK(msg, fs.tau.alloc((size_t)k));
-      FCHK(msg, fs.ipiv.alloc((size_t)k));
-    }
-    FCHK(msg, hipMemcpyAsync(fs.a.get(), s->qr.factors(), sizeof(double) * (size_t)k * k, hipMemcpyHostToDevice, h->stream));
-    FCHK(msg, hipMemcpyAsync(fs.tau.get(), s->qr.taus(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, h->stream));
-    FCHK(msg, hipMemcpyAsync(fs.ipiv.get(), ipiv.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, h->stream));
-    FCHK(msg, hipStreamSynchronize(h->stream));
-    fs.present = true;
-    return MALS_OK;
-  };
+  const std::function<int()> fn = [&]() -> int { return foldin_solver_install(h, side, s, ipiv, msg); };
   return foldin_exclusive(h, fn, msg, "mals_set_foldin_solver");
 }
 
@@ -3115,9 +3127,9 @@ int mals_grow_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
   return foldin_exclusive(h, fn, msg, "mals_grow_factor_rows");
 }
 
-int mals_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out) {
+static int foldin_estimate_impl(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out, bool via_group) {
   if (!h) return MALS_INVALID_ARG;
-  if (int rc = foldin_refuse(h, "mals_estimate_preferences")) return rc;
+  if (int rc = foldin_refuse(h, "mals_estimate_preferences", via_group)) return rc;
   if (n < 0 || (n > 0 && (!user_row || !item_row || !out))) return topn_fail(h, MALS_INVALID_ARG, "mals_estimate_preferences: bad arguments");
   if (n == 0) return MALS_OK;
   std::string msg;
@@ -3144,10 +3156,14 @@ int mals_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row,
   return foldin_exclusive(h, fn, msg, "mals_estimate_preferences");
 }
 
+int mals_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out) {
+  return foldin_estimate_impl(h, n, user_row, item_row, out, false);
+}
+
 static int foldin_anonymous(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values, float* out,
-                            int32_t* status_out, const int64_t* to_item, float* dot_out, const char* call) {
+                            int32_t* status_out, const int64_t* to_item, float* dot_out, const char* call, bool via_group = false) {
   if (!h) return MALS_INVALID_ARG;
-  if (int rc = foldin_refuse(h, call)) return rc;
+  if (int rc = foldin_refuse(h, call, via_group)) return rc;
   if (n_queries < 0 || (n_queries > 0 && (!item_ptr || !out || (item_ptr[n_queries] > 0 && !item_row))) || (n_queries > 0 && item_ptr[0] != 0))
     return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": bad arguments").c_str());
   for (int32_t q = 0; q < n_queries; ++q)
@@ -3195,17 +3211,23 @@ int mals_anonymous_features(mals_handle h, int32_t n_queries, const int64_t* ite
   return foldin_anonymous(h, n_queries, item_ptr, item_row, values, out, status_out, nullptr, nullptr, "mals_anonymous_features");
 }
 
-int mals_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
-                                const float* values, float* out, int32_t* status_out) {
+static int foldin_estimate_anonymous_impl(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
+                                          const float* values, float* out, int32_t* status_out, bool via_group) {
   if (!h) return MALS_INVALID_ARG;
   if (n_queries > 0 && (!to_item || !out)) return topn_fail(h, MALS_INVALID_ARG, "mals_estimate_for_anonymous: bad arguments");
   std::vector<float> feats((size_t)std::max(n_queries, 0) * h->cfg.features);
-  return foldin_anonymous(h, n_queries, item_ptr, item_row, values, feats.data(), status_out, to_item, out, "mals_estimate_for_anonymous");
+  return foldin_anonymous(h, n_queries, item_ptr, item_row, values, feats.data(), status_out, to_item, out, "mals_estimate_for_anonymous", via_group);
+}
+
+int mals_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
+                                const float* values, float* out, int32_t* status_out) {
+  return foldin_estimate_anonymous_impl(h, n_queries, to_item, item_ptr, item_row, values, out, status_out, false);
 }
 
 // two tickets: the vectors, then the top-N (like the reference, which holds no lock across the two, a write may land between)
 static int topn_anonymous_impl(mals_handle h, mals_rescorer r, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row,
-                               const float* values, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out) {
+                               const float* values, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out,
+                               bool via_group = false) {
   if (!h) return MALS_INVALID_ARG;
   if (r && r->h != h) return topn_fail(h, MALS_INVALID_ARG, "the rescorer belongs to another handle");
   if (n_queries > 0 && (how_many <= 0 || how_many > 4096 || !item_idx_out || !score_out))
@@ -3213,7 +3235,7 @@ static int topn_anonymous_impl(mals_handle h, mals_rescorer r, int32_t n_queries
   const int k = h->cfg.features;
   std::vector<float> feats((size_t)std::max(n_queries, 0) * k);
   std::vector<int32_t> st((size_t)std::max(n_queries, 0), MALS_OK);
-  const int rc_f = foldin_anonymous(h, n_queries, item_ptr, item_row, values, feats.data(), st.data(), nullptr, nullptr, "mals_recommend_to_anonymous");
+  const int rc_f = foldin_anonymous(h, n_queries, item_ptr, item_row, values, feats.data(), st.data(), nullptr, nullptr, "mals_recommend_to_anonymous", via_group);
   if (rc_f != MALS_OK && rc_f != MALS_INVALID_ARG) return rc_f;
   if (n_queries <= 0) return rc_f;
   if (rc_f == MALS_INVALID_ARG && std::all_of(st.begin(), st.end(), [](int32_t v) { return v == MALS_OK; })) return rc_f;   // (an argument error)
@@ -3285,6 +3307,242 @@ int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, do
 }
 
 }  // extern "C"
+
+// ---- the write path on the members of a group (mals_group.cpp: the mals_group_* twins) ---------------------------------
+// A group write is a replicated state machine: every member applies the same batch to its own replicas of X and Y with the
+// same deterministic kernels, nothing is exchanged, and only the owner of a user (own[m] <= user < own[m + 1]) keeps that
+// user's known-item overlay.  Each call below holds the fronts of ALL members (foldin_exclusive_all) while it enqueues
+// every member's device work and only then waits for each: the members work side by side, and a read of any member sees
+// the model before the write or after it.  The caller (the group) orders the writes among themselves.
+namespace {
+
+// on the device of member m for the rest of the scope's iteration
+int group_on_device(mals_handle h, std::string& msg) {
+  FCHK(msg, hipSetDevice(h->cfg.device));
+  return MALS_OK;
+}
+
+// after an enqueue failed: nothing of the call may still run when it returns
+void group_drain(mals_handle* hs, int n) {
+  for (int m = 0; m < n; ++m)
+    if (hipSetDevice(hs[m]->cfg.device) == hipSuccess) (void)hipStreamSynchronize(hs[m]->stream);
+}
+
+int group_finish(int rc, const std::string& msg, std::string* err) {
+  if (rc != MALS_OK && err) *err = msg.empty() ? std::string("failed") : msg;
+  return rc;
+}
+
+}  // namespace
+
+int malsi_group_set_foldin_solver(mals_handle* hs, int n_members, int side, mals_solver s, std::string* err) {
+  const int k = hs[0]->cfg.features;
+  if (s && s->qr.dim() != k) return group_finish(MALS_INVALID_ARG, "the solver's dimension is not the group's features", err);
+  const std::vector<int32_t> ipiv = foldin_solver_ipiv(s, k);
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    for (int m = 0; m < n_members; ++m) {
+      if (int rc = group_on_device(hs[m], msg)) return rc;
+      if (int rc = foldin_solver_install(hs[m], side, s, ipiv, msg)) return rc;
+    }
+    return MALS_OK;
+  };
+  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+}
+
+int malsi_group_set_foldin_learn_rate(mals_handle* hs, int n_members, double rate, std::string* err) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    for (int m = 0; m < n_members; ++m) foldin_state(hs[m])->rate = rate;
+    return MALS_OK;
+  };
+  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+}
+
+int malsi_group_set_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n, const int64_t* user_row, const int64_t* item_row,
+                                const float* value, int32_t* status_out, std::string* err) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    for (int m = 0; m < n_members; ++m)   // (the replicas have one size; each member is asked all the same)
+      if (int rc = foldin_check_pairs(hs[m], n, user_row, item_row, false, false, msg)) return rc;
+    FoldinPlan plan;
+    foldin_set_plan(*foldin_state(hs[0]), n, user_row, item_row, plan);
+    for (int m = 0; m < n_members; ++m) {
+      int rc = group_on_device(hs[m], msg);
+      if (rc == MALS_OK) rc = foldin_set_enqueue(hs[m], n, user_row, item_row, value, plan, msg);
+      if (rc != MALS_OK) {
+        group_drain(hs, m + 1);
+        return rc;
+      }
+    }
+    // every member's kernels are on their way: collect.  The statuses are every replica's own (the same arithmetic on the
+    // same bits); the caller gets member 0's, and a member that answers otherwise is a failure of its own
+    int first = MALS_OK;
+    for (int m = 0; m < n_members; ++m) {
+      std::string mine;
+      int rc = group_on_device(hs[m], mine);
+      if (rc == MALS_OK) rc = foldin_set_collect(hs[m], n, user_row, item_row, plan, own[m], own[m + 1], m == 0 ? status_out : nullptr, mine);
+      if (m == 0) {
+        first = rc;
+        msg = mine;
+      } else if (rc != first) {
+        group_drain(hs, n_members);
+        msg = "member " + std::to_string(m) + " answered " + std::to_string(rc) + " where member 0 answered " + std::to_string(first) + ": " + mine;
+        return rc == MALS_OK ? MALS_HIP_ERROR : rc;
+      }
+    }
+    return first;
+  };
+  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+}
+
+int malsi_group_remove_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n, const int64_t* user_row, const int64_t* item_row,
+                                   int64_t* removed_users_out, int64_t* n_removed_out, std::string* err) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    for (int m = 0; m < n_members; ++m) {
+      if (!hs[m]->side[MALS_SIDE_X].has_matrix && !hs[m]->known_ptr) {
+        msg = "the user-side matrix (or the installed known items) holds the known items";
+        return MALS_INVALID_ARG;
+      }
+      if (int rc = foldin_check_pairs(hs[m], n, user_row, item_row, false, false, msg)) return rc;
+    }
+    // the owners decide (small reads of their own known items), in batch order within each owner; a user has one owner
+    std::vector<std::pair<int64_t, int64_t>> emptied;
+    for (int m = 0; m < n_members; ++m) {
+      if (int rc = group_on_device(hs[m], msg)) return rc;
+      if (int rc = foldin_remove_decide(hs[m], n, user_row, item_row, own[m], own[m + 1], emptied, msg)) return rc;
+    }
+    std::sort(emptied.begin(), emptied.end());
+    std::vector<int64_t> removed;
+    for (const auto& e : emptied) removed.push_back(e.second);
+    // every replica zeroes the same rows
+    std::vector<DeviceBuffer<int64_t>> d((size_t)n_members);
+    int rc = MALS_OK;
+    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
+      rc = group_on_device(hs[m], msg);
+      if (rc == MALS_OK) rc = foldin_remove_enqueue(hs[m], removed, d[(size_t)m], msg);
+    }
+    if (rc != MALS_OK) group_drain(hs, n_members);
+    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
+      rc = group_on_device(hs[m], msg);
+      if (rc == MALS_OK) rc = foldin_remove_collect(hs[m], !removed.empty(), msg);
+    }
+    for (int m = 0; m < n_members; ++m)
+      if (hipSetDevice(hs[m]->cfg.device) == hipSuccess) d[(size_t)m].reset();
+    if (rc != MALS_OK) return rc;
+    if (removed_users_out) std::copy(removed.begin(), removed.end(), removed_users_out);
+    if (n_removed_out) *n_removed_out = (int64_t)removed.size();
+    return MALS_OK;
+  };
+  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+}
+
+// grown_owner: the member that owns the users past the installed matrix (the last rank), or -1
+int malsi_group_grow_factor_rows(mals_handle* hs, int n_members, int side, int64_t n_rows_total, int grown_owner, std::string* err) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    for (int m = 0; m < n_members; ++m)
+      if (!hs[m]->side[side].F) {
+        msg = "the replica is not declared (mals_group_set_factor_rows)";
+        return MALS_INVALID_ARG;
+      }
+    std::vector<FoldinGrow> gw((size_t)n_members);
+    int rc = MALS_OK;
+    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
+      rc = group_on_device(hs[m], msg);
+      if (rc == MALS_OK) rc = foldin_grow_enqueue(hs[m], side, n_rows_total, gw[(size_t)m], msg);
+    }
+    if (rc != MALS_OK) group_drain(hs, n_members);
+    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
+      rc = group_on_device(hs[m], msg);
+      if (rc == MALS_OK) rc = foldin_grow_finish(hs[m], side, n_rows_total, gw[(size_t)m], m == grown_owner, msg);
+    }
+    for (int m = 0; m < n_members; ++m)   // (what a failure left behind goes with its device current)
+      if (hipSetDevice(hs[m]->cfg.device) == hipSuccess) gw[(size_t)m] = FoldinGrow();
+    return rc;
+  };
+  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+}
+
+// the digest of rows [row_begin, row_begin + n_rows) of every handle's replica, all taken between the same two writes
+int malsi_group_factor_digest(mals_handle* hs, int n_members, int side, int64_t row_begin, int64_t n_rows, uint64_t* out, std::string* err) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    for (int m = 0; m < n_members; ++m) {
+      const SideState& s = hs[m]->side[side];
+      if (!s.F) {
+        msg = "the replica is not declared";
+        return MALS_INVALID_ARG;
+      }
+      if (row_begin < 0 || n_rows < 0 || row_begin > s.n_total || n_rows > s.n_total - row_begin) {
+        msg = "rows outside the factor replica";
+        return MALS_INVALID_ARG;
+      }
+      out[m] = 0;
+    }
+    if (n_rows == 0) return MALS_OK;
+    const int k = hs[0]->cfg.features;
+    const int64_t e0 = row_begin * k, e1 = (row_begin + n_rows) * k;
+    // enough workgroups to keep every CU streaming (8 per CU of 256), never more than the float4s ask for
+    const unsigned grid = (unsigned)std::min<int64_t>(2048, std::max<int64_t>(1, ((e1 - e0) / 4 + 255) / 256));
+    std::vector<DeviceBuffer<unsigned long long>> cell((size_t)n_members);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the digest cell is 64 bits");
+    int rc = MALS_OK;
+    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
+      rc = group_on_device(hs[m], msg);
+      if (rc != MALS_OK) break;
+      rc = [&]() -> int {
+        FCHK(msg, cell[(size_t)m].alloc(1));
+        FCHK(msg, hipMemsetAsync(cell[(size_t)m].get(), 0, sizeof(unsigned long long), hs[m]->stream));
+        hipLaunchKernelGGL(factor_digest_kernel, dim3(grid), dim3(256), 0, hs[m]->stream, hs[m]->side[side].F, e0, e1, cell[(size_t)m].get());
+        FCHK(msg, hipGetLastError());
+        FCHK(msg, hipMemcpyAsync(out + m, cell[(size_t)m].get(), sizeof(uint64_t), hipMemcpyDeviceToHost, hs[m]->stream));
+        return MALS_OK;
+      }();
+    }
+    for (int m = 0; m < n_members; ++m) {
+      if (hipSetDevice(hs[m]->cfg.device) != hipSuccess) continue;
+      const hipError_t e = hipStreamSynchronize(hs[m]->stream);
+      if (e != hipSuccess && rc == MALS_OK) {
+        msg = std::string("hipStreamSynchronize: ") + hipGetErrorString(e);
+        rc = MALS_HIP_ERROR;
+      }
+      cell[(size_t)m].reset();
+    }
+    return rc;
+  };
+  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+}
+
+// the fold-in reads on ONE member (any: the replicas and the solvers are complete everywhere)
+int malsi_member_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out) {
+  return foldin_estimate_impl(h, n, user_row, item_row, out, true);
+}
+
+int malsi_member_anonymous_features(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values, float* out,
+                                    int32_t* status_out) {
+  return foldin_anonymous(h, n_queries, item_ptr, item_row, values, out, status_out, nullptr, nullptr, "mals_anonymous_features", true);
+}
+
+int malsi_member_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                                        int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out) {
+  return topn_anonymous_impl(h, nullptr, n_queries, item_ptr, item_row, values, how_many, item_idx_out, score_out, n_out, status_out, true);
+}
+
+int malsi_member_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
+                                        const float* values, float* out, int32_t* status_out) {
+  return foldin_estimate_anonymous_impl(h, n_queries, to_item, item_ptr, item_row, values, out, status_out, true);
+}
+
+extern "C" int mals_factor_digest(mals_handle h, int side, int64_t row_begin, int64_t n_rows, uint64_t* out) {
+  CHECK_SIDE(h, side);
+  if (!out) return topn_fail(h, MALS_INVALID_ARG, "mals_factor_digest: out is NULL");
+  std::string msg;
+  const int rc = malsi_group_factor_digest(&h, 1, side, row_begin, n_rows, out, &msg);
+  if (rc != MALS_OK) return topn_fail(h, rc, ("mals_factor_digest: " + msg).c_str());
+  return MALS_OK;
+}
 
 
 // ---- rescorers: RecommendIterator's IDRescorer in the form the device runs (topn_kernels.h, RESCORED MODE) ------------

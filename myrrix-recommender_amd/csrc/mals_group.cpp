@@ -14,6 +14,7 @@
 #include "../../include/myrrix_als.h"
 #include "mals_internal.h"
 #include "hip_buffer.h"
+#include "factor_digest.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -27,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -156,6 +158,12 @@ struct mals_group_s {
   std::atomic<int> cancelled{0};
   mals_iteration_fn iter_fn = nullptr;   // mals_group_set_iteration_callback
   void* iter_user = nullptr;
+  // the online write path (mals_group_set_preferences ...): two writes reach every member's serving front in the same
+  // order (updates that share a row do not commute); the reads take no lock and rotate over the local members
+  std::mutex write_mu;
+  std::mutex err_mu;                   // the failure text of a read: request threads share the group's string
+  std::atomic<uint32_t> next_reader{0};
+  std::atomic<int64_t> users_end{0};   // rows of the X replicas: users past the installed matrix belong to the last rank
   std::string err;
 };
 
@@ -189,6 +197,13 @@ int mfail(mals_group g, const Member& mb, int rc) {
     if (!(g)) return MALS_INVALID_ARG;                                                    \
     if ((side) != MALS_SIDE_X && (side) != MALS_SIDE_Y) return gfail(g, MALS_INVALID_ARG, "side must be MALS_SIDE_X or _Y"); \
   } while (0)
+
+// the rank that holds user u's known items: the slice with its row; users past the installed matrix (rows the replicas
+// grew by, mals_group_grow_factor_rows) are the last rank's
+int owner_of(const std::vector<int64_t>& bounds, int64_t u) {
+  const int world = (int)bounds.size() - 1;
+  return std::min(world - 1, (int)(std::upper_bound(bounds.begin(), bounds.end(), u) - bounds.begin()) - 1);
+}
 
 int64_t chunk_rows_of(const mals_group g, int side, int rank) {
   const int64_t n = g->bounds[side][(size_t)rank + 1] - g->bounds[side][(size_t)rank];
@@ -728,6 +743,7 @@ int mals_group_set_factor_rows(mals_group g, int side, int64_t n_rows_total) {
   for (Member& mb : g->m)
     if (int rc = mals_set_factor_rows(mb.h, side, n_rows_total)) return mfail(g, mb, rc);
   g->n_total[side] = n_rows_total;
+  if (side == MALS_SIDE_X) g->users_end.store(n_rows_total, std::memory_order_release);
   return refresh_replica_ptrs(g, side);
 }
 
@@ -1079,10 +1095,10 @@ int mals_group_recommend(mals_group g, const int64_t* user_idx, int32_t n_querie
   // runs of consecutive queries with the same owner go to that member in one call (a one-user call is one run)
   for (int32_t q0 = 0; q0 < n_queries;) {
     const int64_t u = user_idx[q0];
-    if (u < 0 || u >= b.back()) return MALS_INVALID_ARG;
-    const int owner = (int)(std::upper_bound(b.begin(), b.end(), u) - b.begin()) - 1;
+    if (u < 0 || u >= std::max(b.back(), g->users_end.load(std::memory_order_acquire))) return MALS_INVALID_ARG;
+    const int owner = owner_of(b, u);
     int32_t q1 = q0 + 1;
-    while (q1 < n_queries && user_idx[q1] >= b[(size_t)owner] && user_idx[q1] < b[(size_t)owner + 1]) ++q1;
+    while (q1 < n_queries && user_idx[q1] >= 0 && owner_of(b, user_idx[q1]) == owner) ++q1;
     const Member* mb = nullptr;
     for (const Member& m : g->m)
       if (m.rank == owner) mb = &m;
@@ -1118,10 +1134,10 @@ int mals_group_recommended_because(mals_group g, const int64_t* user_idx, const 
   const std::vector<int64_t>& b = g->bounds[MALS_SIDE_X];
   for (int32_t q0 = 0; q0 < n_queries;) {
     const int64_t u = user_idx[q0];
-    if (u < 0 || u >= b.back()) return MALS_INVALID_ARG;
-    const int owner = (int)(std::upper_bound(b.begin(), b.end(), u) - b.begin()) - 1;
+    if (u < 0 || u >= std::max(b.back(), g->users_end.load(std::memory_order_acquire))) return MALS_INVALID_ARG;
+    const int owner = owner_of(b, u);
     int32_t q1 = q0 + 1;
-    while (q1 < n_queries && user_idx[q1] >= b[(size_t)owner] && user_idx[q1] < b[(size_t)owner + 1]) ++q1;
+    while (q1 < n_queries && user_idx[q1] >= 0 && owner_of(b, user_idx[q1]) == owner) ++q1;
     const Member* mb = nullptr;
     for (const Member& m : g->m)
       if (m.rank == owner) mb = &m;
@@ -1431,6 +1447,189 @@ int mals_group_factorize(mals_group g, double convergence_threshold, int32_t max
     if (!std::isfinite(mean)) break;                                    // ALS:248-251
     if (!(random_y && it == 1) && mean < convergence_threshold) break;  // ALS:253-256
   }
+  return MALS_OK;
+}
+
+}  // extern "C"
+
+// ---- the online write path and the fold-in reads on a group (include/myrrix_als.h; the members' side: mals_api.hip) ----
+namespace {
+
+// what every twin checks first: a group all of whose ranks live in this process
+int foldin_group_ready(mals_group g, const char* call) {
+  if (!g) return MALS_INVALID_ARG;
+  if (!g->single_process)
+    return gfail(g, MALS_INVALID_ARG, std::string(call) + ": not for a group of several processes (a process cannot reach another process's members)");
+  return MALS_OK;
+}
+
+std::vector<mals_handle> member_handles(mals_group g) {
+  std::vector<mals_handle> hs;
+  for (Member& mb : g->m) hs.push_back(mb.h);
+  return hs;
+}
+
+// member m keeps the known items of the users own[m] <= u < own[m + 1] (the members are the ranks, in order)
+int owned_users(mals_group g, const char* call, std::vector<int64_t>& own) {
+  const std::vector<int64_t>& b = g->bounds[MALS_SIDE_X];
+  if (b.size() != g->m.size() + 1) return gfail(g, MALS_INVALID_ARG, std::string(call) + ": the user-side matrix is not set (it says who owns a user)");
+  own = b;
+  own.back() = std::numeric_limits<int64_t>::max();   // grown users: the last rank's
+  return MALS_OK;
+}
+
+int write_failed(mals_group g, int rc, const char* call, const std::string& msg) {
+  return rc == MALS_OK ? rc : gfail(g, rc, std::string(call) + ": " + msg);
+}
+
+mals_handle next_reader(mals_group g) { return g->m[g->next_reader.fetch_add(1, std::memory_order_relaxed) % g->m.size()].h; }
+
+// a read's failure text is the answering member's (the last failing read wins; no read waits for a write here)
+int read_failed(mals_group g, mals_handle h, int rc) {
+  if (rc != MALS_OK) {
+    std::lock_guard<std::mutex> lk(g->err_mu);
+    g->err = mals_last_error(h);
+  }
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mals_group_set_foldin_solver(mals_group g, int side, mals_solver s) {
+  if (int rc = foldin_group_ready(g, "mals_group_set_foldin_solver")) return rc;
+  GSIDE(g, side);
+  std::vector<mals_handle> hs = member_handles(g);
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  std::string msg;
+  return write_failed(g, malsi_group_set_foldin_solver(hs.data(), (int)hs.size(), side, s, &msg), "mals_group_set_foldin_solver", msg);
+}
+
+int mals_group_set_foldin_learn_rate(mals_group g, double rate) {
+  if (int rc = foldin_group_ready(g, "mals_group_set_foldin_learn_rate")) return rc;
+  if (!std::isfinite(rate)) return gfail(g, MALS_INVALID_ARG, "mals_group_set_foldin_learn_rate: the fold-in learning rate must be finite");
+  std::vector<mals_handle> hs = member_handles(g);
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  std::string msg;
+  return write_failed(g, malsi_group_set_foldin_learn_rate(hs.data(), (int)hs.size(), rate, &msg), "mals_group_set_foldin_learn_rate", msg);
+}
+
+int mals_group_foldin_stats(mals_group g, int64_t* out6) {
+  if (int rc = foldin_group_ready(g, "mals_group_foldin_stats")) return rc;
+  if (!out6) return MALS_INVALID_ARG;
+  // every member counted the group's writes once: the counters are member 0's, the device times the slowest member's
+  for (size_t i = 0; i < g->m.size(); ++i) {
+    int64_t o[6];
+    if (int rc = mals_foldin_stats(g->m[i].h, o)) return rc;
+    for (int j = 0; j < 6; ++j)
+      if (i == 0 || (j >= 4 && o[j] > out6[j])) out6[j] = o[j];
+  }
+  return MALS_OK;
+}
+
+int mals_group_set_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
+  if (int rc = foldin_group_ready(g, "mals_group_set_preferences")) return rc;
+  if (n < 0 || (n > 0 && (!user_row || !item_row || !value))) return gfail(g, MALS_INVALID_ARG, "mals_group_set_preferences: bad arguments");
+  if (n > (int64_t)1 << 30) return gfail(g, MALS_INVALID_ARG, "mals_group_set_preferences: at most 2^30 updates per call");
+  if (n == 0) return MALS_OK;
+  std::vector<mals_handle> hs = member_handles(g);
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  std::vector<int64_t> own;
+  if (int rc = owned_users(g, "mals_group_set_preferences", own)) return rc;
+  std::string msg;
+  return write_failed(g, malsi_group_set_preferences(hs.data(), (int)hs.size(), own.data(), n, user_row, item_row, value, status_out, &msg),
+                      "mals_group_set_preferences", msg);
+}
+
+int mals_group_remove_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,
+                                  int64_t* n_removed_out) {
+  if (n_removed_out) *n_removed_out = 0;
+  if (int rc = foldin_group_ready(g, "mals_group_remove_preferences")) return rc;
+  if (n < 0 || (n > 0 && (!user_row || !item_row))) return gfail(g, MALS_INVALID_ARG, "mals_group_remove_preferences: bad arguments");
+  if (n == 0) return MALS_OK;
+  std::vector<mals_handle> hs = member_handles(g);
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  std::vector<int64_t> own;
+  if (int rc = owned_users(g, "mals_group_remove_preferences", own)) return rc;
+  std::string msg;
+  return write_failed(g, malsi_group_remove_preferences(hs.data(), (int)hs.size(), own.data(), n, user_row, item_row, removed_users_out,
+                                                        n_removed_out, &msg),
+                      "mals_group_remove_preferences", msg);
+}
+
+int mals_group_grow_factor_rows(mals_group g, int side, int64_t n_rows_total) {
+  if (int rc = foldin_group_ready(g, "mals_group_grow_factor_rows")) return rc;
+  GSIDE(g, side);
+  std::vector<mals_handle> hs = member_handles(g);
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  std::string msg;
+  // (single process: local member i is rank i, the last one owns the users past the installed matrix)
+  if (int rc = malsi_group_grow_factor_rows(hs.data(), (int)hs.size(), side, n_rows_total, (int)hs.size() - 1, &msg))
+    return write_failed(g, rc, "mals_group_grow_factor_rows", msg);
+  g->n_total[side] = n_rows_total;
+  if (side == MALS_SIDE_X) g->users_end.store(n_rows_total, std::memory_order_release);
+  return refresh_replica_ptrs(g, side);   // (a capacity doubling moved the replicas)
+}
+
+int mals_group_estimate_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out) {
+  if (int rc = foldin_group_ready(g, "mals_group_estimate_preferences")) return rc;
+  mals_handle h = next_reader(g);
+  return read_failed(g, h, malsi_member_estimate_preferences(h, n, user_row, item_row, out));
+}
+
+int mals_group_anonymous_features(mals_group g, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values, float* out,
+                                  int32_t* status_out) {
+  if (int rc = foldin_group_ready(g, "mals_group_anonymous_features")) return rc;
+  mals_handle h = next_reader(g);
+  return read_failed(g, h, malsi_member_anonymous_features(h, n_queries, item_ptr, item_row, values, out, status_out));
+}
+
+int mals_group_recommend_to_anonymous(mals_group g, int32_t n_queries, const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                                      int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out) {
+  if (int rc = foldin_group_ready(g, "mals_group_recommend_to_anonymous")) return rc;
+  mals_handle h = next_reader(g);
+  return read_failed(g, h, malsi_member_recommend_to_anonymous(h, n_queries, item_ptr, item_row, values, how_many, item_idx_out, score_out, n_out,
+                                                               status_out));
+}
+
+int mals_group_estimate_for_anonymous(mals_group g, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
+                                      const float* values, float* out, int32_t* status_out) {
+  if (int rc = foldin_group_ready(g, "mals_group_estimate_for_anonymous")) return rc;
+  mals_handle h = next_reader(g);
+  return read_failed(g, h, malsi_member_estimate_for_anonymous(h, n_queries, to_item, item_ptr, item_row, values, out, status_out));
+}
+
+int mals_group_replica_digest(mals_group g, int side, int64_t row_begin, int64_t n_rows, uint64_t* out_per_local_member, int32_t* all_equal_out) {
+  if (int rc = foldin_group_ready(g, "mals_group_replica_digest")) return rc;
+  GSIDE(g, side);
+  if (!out_per_local_member) return gfail(g, MALS_INVALID_ARG, "mals_group_replica_digest: out_per_local_member is NULL");
+  std::vector<mals_handle> hs = member_handles(g);
+  std::string msg;
+  const int rc = malsi_group_factor_digest(hs.data(), (int)hs.size(), side, row_begin, n_rows, out_per_local_member, &msg);
+  if (rc != MALS_OK) {
+    std::lock_guard<std::mutex> lk(g->err_mu);
+    return write_failed(g, rc, "mals_group_replica_digest", msg);
+  }
+  if (all_equal_out) {
+    *all_equal_out = 1;
+    for (size_t i = 1; i < hs.size(); ++i)
+      if (out_per_local_member[i] != out_per_local_member[0]) *all_equal_out = 0;
+  }
+  return MALS_OK;
+}
+
+int mals_factor_digest_host(const float* rows, int32_t features, int64_t row_begin, int64_t n_rows, uint64_t* out) {
+  if (!out || features <= 0 || row_begin < 0 || n_rows < 0 || (n_rows > 0 && !rows)) return MALS_INVALID_ARG;
+  uint64_t sum = 0;
+  const uint64_t j0 = (uint64_t)row_begin * (uint64_t)features;
+  const uint64_t n = (uint64_t)n_rows * (uint64_t)features;
+  for (uint64_t e = 0; e < n; ++e) {
+    uint32_t bits;
+    std::memcpy(&bits, rows + e, sizeof(bits));
+    sum += mals::factor_digest_term(j0 + e, bits);
+  }
+  *out = sum;
   return MALS_OK;
 }
 

@@ -30,6 +30,36 @@ __attribute__((visibility("hidden"))) void malsi_set_create_error(const char* te
 __attribute__((visibility("hidden"))) void malsi_mark_group_member(mals_handle h);
 }
 
+// The write path and the fold-in reads of a group (the mals_group_* twins of mals_set_preferences ...; mals_api.hip).  hs =
+// the handles of the local members; every call holds ALL their serving fronts while it enqueues each member's work and
+// then waits for each.  own (n_members + 1): member m keeps the known items of the users own[m] <= u < own[m + 1].  A
+// failure's text goes to *err.  The caller orders the writes among themselves (the group's write lock).
+#include <string>
+__attribute__((visibility("hidden"))) int malsi_group_set_foldin_solver(mals_handle* hs, int n_members, int side, mals_solver s, std::string* err);
+__attribute__((visibility("hidden"))) int malsi_group_set_foldin_learn_rate(mals_handle* hs, int n_members, double rate, std::string* err);
+__attribute__((visibility("hidden"))) int malsi_group_set_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n,
+                                                                    const int64_t* user_row, const int64_t* item_row, const float* value,
+                                                                    int32_t* status_out, std::string* err);
+__attribute__((visibility("hidden"))) int malsi_group_remove_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n,
+                                                                       const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,
+                                                                       int64_t* n_removed_out, std::string* err);
+__attribute__((visibility("hidden"))) int malsi_group_grow_factor_rows(mals_handle* hs, int n_members, int side, int64_t n_rows_total,
+                                                                     int grown_owner, std::string* err);
+__attribute__((visibility("hidden"))) int malsi_group_factor_digest(mals_handle* hs, int n_members, int side, int64_t row_begin, int64_t n_rows,
+                                                                  uint64_t* out, std::string* err);
+// the fold-in reads on one member's handle (any member answers: replicas and solvers are complete everywhere)
+__attribute__((visibility("hidden"))) int malsi_member_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row,
+                                                                          const int64_t* item_row, float* out);
+__attribute__((visibility("hidden"))) int malsi_member_anonymous_features(mals_handle h, int32_t n_queries, const int64_t* item_ptr,
+                                                                        const int64_t* item_row, const float* values, float* out, int32_t* status_out);
+__attribute__((visibility("hidden"))) int malsi_member_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t* item_ptr,
+                                                                            const int64_t* item_row, const float* values, int32_t how_many,
+                                                                            int64_t* item_idx_out, float* score_out, int32_t* n_out,
+                                                                            int32_t* status_out);
+__attribute__((visibility("hidden"))) int malsi_member_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item,
+                                                                            const int64_t* item_ptr, const int64_t* item_row, const float* values,
+                                                                            float* out, int32_t* status_out);
+
 // mals_group_ingest_finish (mals_group.cpp) hands the ingest side (ingest_group_host.h) the group's transport: collectives over
 // every rank, called with one device buffer per LOCAL member (on that member's device), returning once they are complete.
 struct malsi_group_ops {

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import MEM_DEVICE, MEM_HOST, SIDE_X, SIDE_Y
-from .core import ALSCore, Cancelled, MalsError, SingularSystem, _item_queries
+from .core import ALSCore, Cancelled, MalsError, SingularSystem, _host, _item_queries
 
 
 def plan_shards(row_ptr, world, features, row_cost=-1.0):
@@ -279,6 +279,113 @@ class GroupALS:
                                                          int(how_many), idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
                                                          cnt.ctypes.data_as(ctypes.c_void_p)))
         return idx, sc, cnt
+
+    # -- the online write path on the group (the mals_group_* twins of ALSCore's methods of the same names) -------
+    # Writes go to every local member (replicated, in one order); a user's known items stay with the member that owns the
+    # user; the reads rotate over the members.  Signatures and return values are ALSCore's.
+    def set_foldin_solver(self, side, solver):
+        self._chk(self._L.mals_group_set_foldin_solver(self._g, side, solver._s if solver is not None else None))
+
+    def set_foldin_learn_rate(self, rate):
+        self._chk(self._L.mals_group_set_foldin_learn_rate(self._g, float(rate)))
+
+    def foldin_stats(self):
+        """The group's writes counted once (not once per member); the device times are the slowest member's."""
+        o = np.zeros(6, dtype=np.int64)
+        self._chk(self._L.mals_group_foldin_stats(self._g, o.ctypes.data_as(ctypes.c_void_p)))
+        return {"applied": int(o[0]), "failed": int(o[1]), "big_foldin": int(o[2]), "levels": int(o[3]),
+                "device_ms_total": o[4] * 1e-6, "device_ms_last": o[5] * 1e-6}
+
+    def set_preferences(self, users, items, values, raise_on_error=True):
+        u, i, v = _host(users, np.int64), _host(items, np.int64), _host(values, np.float32)
+        assert len(u) == len(i) == len(v)
+        st = np.zeros(len(u), dtype=np.int32)
+        rc = self._L.mals_group_set_preferences(self._g, len(u), u.ctypes.data_as(ctypes.c_void_p), i.ctypes.data_as(ctypes.c_void_p),
+                                                v.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if raise_on_error or rc not in (_lib.OK, _lib.INVALID_ARG) or not st.any():
+            self._chk(rc)
+        return st
+
+    def remove_preferences(self, users, items):
+        u, i = _host(users, np.int64), _host(items, np.int64)
+        assert len(u) == len(i)
+        out = np.zeros(max(len(u), 1), dtype=np.int64)
+        n = ctypes.c_int64(0)
+        self._chk(self._L.mals_group_remove_preferences(self._g, len(u), u.ctypes.data_as(ctypes.c_void_p), i.ctypes.data_as(ctypes.c_void_p),
+                                                        out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n)))
+        return out[:n.value].copy()
+
+    def grow_factor_rows(self, side, n_rows_total):
+        self._chk(self._L.mals_group_grow_factor_rows(self._g, side, int(n_rows_total)))
+
+    def estimate_preferences(self, users, items):
+        u, i = _host(users, np.int64), _host(items, np.int64)
+        out = np.empty(len(u), dtype=np.float32)
+        self._chk(self._L.mals_group_estimate_preferences(self._g, len(u), u.ctypes.data_as(ctypes.c_void_p), i.ctypes.data_as(ctypes.c_void_p),
+                                                          out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def anonymous_features(self, queries, values=None, raise_on_error=True):
+        flat, ptr, vals = ALSCore._anon_args(queries, values)
+        nq = len(ptr) - 1
+        out = np.zeros((nq, self.features), dtype=np.float32)
+        st = np.zeros(nq, dtype=np.int32)
+        rc = self._L.mals_group_anonymous_features(self._g, nq, ptr.ctypes.data_as(ctypes.c_void_p), flat.ctypes.data_as(ctypes.c_void_p),
+                                                   vals.ctypes.data_as(ctypes.c_void_p) if vals is not None else None,
+                                                   out.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if raise_on_error or not st.any():
+            self._chk(rc)
+        return out, st
+
+    def recommend_to_anonymous(self, queries, how_many, values=None):
+        flat, ptr, vals = ALSCore._anon_args(queries, values)
+        nq = len(ptr) - 1
+        idx = np.empty((nq, how_many), dtype=np.int64)
+        sc = np.empty((nq, how_many), dtype=np.float32)
+        cnt = np.empty(nq, dtype=np.int32)
+        st = np.zeros(nq, dtype=np.int32)
+        rc = self._L.mals_group_recommend_to_anonymous(self._g, nq, ptr.ctypes.data_as(ctypes.c_void_p), flat.ctypes.data_as(ctypes.c_void_p),
+                                                       vals.ctypes.data_as(ctypes.c_void_p) if vals is not None else None, int(how_many),
+                                                       idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+                                                       cnt.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if not st.any():
+            self._chk(rc)
+        return idx, sc, cnt, st
+
+    def estimate_for_anonymous(self, to_items, queries, values=None):
+        flat, ptr, vals = ALSCore._anon_args(queries, values)
+        nq = len(ptr) - 1
+        to = _host(to_items, np.int64)
+        assert len(to) == nq
+        out = np.zeros(nq, dtype=np.float32)
+        st = np.zeros(nq, dtype=np.int32)
+        rc = self._L.mals_group_estimate_for_anonymous(self._g, nq, to.ctypes.data_as(ctypes.c_void_p), ptr.ctypes.data_as(ctypes.c_void_p),
+                                                       flat.ctypes.data_as(ctypes.c_void_p),
+                                                       vals.ctypes.data_as(ctypes.c_void_p) if vals is not None else None,
+                                                       out.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p))
+        if not st.any():
+            self._chk(rc)
+        return out, st
+
+    def replica_digest(self, side, row_begin=0, n_rows=None):
+        """mals_group_replica_digest: (uint64 digest of the range on every local member, whether they all agree), taken
+        between the same two group writes on every member.  n_rows None: to the end of the replica."""
+        m, _ = self.local(0)
+        if n_rows is None:
+            n_rows = m.factor_device_ptr(side)[1] - int(row_begin)
+        n_local = self._n_local()
+        out = np.zeros(n_local, dtype=np.uint64)
+        eq = ctypes.c_int32(0)
+        self._chk(self._L.mals_group_replica_digest(self._g, side, int(row_begin), int(n_rows), out.ctypes.data_as(ctypes.c_void_p),
+                                                    ctypes.byref(eq)))
+        return out, bool(eq.value)
+
+    def _n_local(self):
+        n = 0
+        h, r = ctypes.c_void_p(), ctypes.c_int32()
+        while self._L.mals_group_local(self._g, n, ctypes.byref(h), ctypes.byref(r)) == _lib.OK:
+            n += 1
+        return n
 
     def bounds(self, side):
         out = np.zeros(self.world + 1, dtype=np.int64)

@@ -2,9 +2,12 @@
 """The online write path (mals_set_preferences) on one MI355X: updates/s per batch size for uniform and Zipf(1.1) item
 draws, the level count of each batch, single-update latency from 1 and 32 writer threads while 32 threads recommend, and
 a CPU baseline (the same updates through HostSolver in one thread, sampled, labelled as such).  One JSON line per leg.
+--members N: the same writes on a single-process group of N members ON ONE DEVICE (mals_group_set_preferences): a 1-update
+call and a distinct-rows call of --group-batch updates, to price the replication where it cannot spread (N replicas share one
+device, so their work adds up; N devices are not measured here).  --digest: mals_factor_digest over the whole X replica.
 wall_ms: host wall clock around the synchronous call (level assignment, upload, every level's kernel, status copy, known-item
 bookkeeping); device_ms: HIP events around the level kernels (mals_foldin_stats).
-usage: python tools/bench_foldin.py [--items N] [--users U] [--features K ...] [--out FILE]"""
+usage: python tools/bench_foldin.py [--items N] [--users U] [--features K ...] [--members N ...] [--digest] [--out FILE]"""
 import argparse
 import json
 import os
@@ -34,6 +37,47 @@ def zipf_items(rng, n_items, n, s=1.1):
     return r.astype(np.int64)
 
 
+def group_legs(a, k, pkg, np, torch):
+    """mals_group_set_preferences on N members that share device 0: what the replication costs when it cannot spread."""
+    gen = torch.Generator(device="cuda").manual_seed(k)
+    X = (torch.randn(a.users, k, device="cuda", generator=gen) * (0.3 / k ** 0.5)).float().cpu().numpy()
+    Y = (torch.randn(a.items, k, device="cuda", generator=gen) * (0.3 / k ** 0.5)).float().cpu().numpy()
+    torch.cuda.empty_cache()
+    ptr = np.arange(a.users + 1, dtype=np.int64)
+    col = np.random.default_rng(1).integers(0, a.items, a.users).astype(np.int32)
+    for members in a.members:
+        g = pkg.GroupALS.single_process(k, [0] * members, backend=pkg._lib.GROUP_PEER_COPY)
+        g.set_factor_rows(pkg.SIDE_X, a.users)
+        g.set_factor_rows(pkg.SIDE_Y, a.items)
+        g.set_factors(pkg.SIDE_X, X)
+        g.set_factors(pkg.SIDE_Y, Y)
+        g.set_matrix(pkg.SIDE_X, ptr, col, np.ones(a.users, np.float32))
+        m0, _ = g.local(0)
+        sx, _ = m0.recompute_solver(pkg.SIDE_X)
+        sy, _ = m0.recompute_solver(pkg.SIDE_Y)
+        g.set_foldin_solver(pkg.SIDE_X, sx)
+        g.set_foldin_solver(pkg.SIDE_Y, sy)
+        rng = np.random.default_rng(k)
+        for n in (1, a.group_batch):
+            times, dev = [], []
+            for rep in range(a.reps + 1):
+                u = rng.permutation(a.users)[:n]            # distinct rows: one level
+                i = rng.permutation(a.items)[:n]
+                v = rng.choice(np.array([1.0, 2.0, -1.0, 0.5], np.float32), n)
+                t0 = time.perf_counter()
+                g.set_preferences(u, i, v, raise_on_error=False)
+                dt = time.perf_counter() - t0
+                if rep:
+                    times.append(dt)
+                    dev.append(g.foldin_stats()["device_ms_last"])
+            med = float(np.median(times))
+            emit({"leg": "group_set_preferences", "members": members, "devices": 1, "k": k, "items": a.items, "users": a.users,
+                  "dist": "distinct", "batch": n, "wall_ms_median": med * 1e3, "wall_ms_min": min(times) * 1e3, "updates_per_s": n / med,
+                  "device_ms_median_slowest_member": float(np.median(dev)), "replicas_equal": bool(g.replica_digest(pkg.SIDE_Y)[1]),
+                  "reps": a.reps}, a.out)
+        g.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--items", type=int, default=1_000_000)
@@ -43,6 +87,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--latency-calls", type=int, default=300)
     ap.add_argument("--cpu-sample", type=int, default=200)
+    ap.add_argument("--members", type=int, nargs="+", default=[], help="group legs: members on one device (replaces the other legs)")
+    ap.add_argument("--group-batch", type=int, default=4096)
+    ap.add_argument("--digest", action="store_true", help="add the mals_factor_digest leg (single handle)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
@@ -50,6 +97,10 @@ def main():
     import myrrix_recommender_amd as pkg
     from tests import foldin_oracle as fo
 
+    for k in a.features if a.members else []:
+        group_legs(a, k, pkg, np, torch)
+    if a.members:
+        return
     for k in a.features:
         g = torch.Generator(device="cuda").manual_seed(k)
         X = (torch.randn(a.users, k, device="cuda", generator=g) * (0.3 / k ** 0.5)).float()
@@ -87,6 +138,18 @@ def main():
                       "wall_ms_median": med * 1e3, "wall_ms_min": min(times) * 1e3, "updates_per_s": n / med,
                       "device_ms_median": dmed, "device_updates_per_s": n / (dmed * 1e-3),
                       "levels_median": float(np.median(levels)), "levels_max": int(max(levels)), "reps": a.reps}, a.out)
+        if a.digest:
+            # one streaming read of the X replica; wall clock around the synchronous call (ticket, launch, 8-byte copy back)
+            core.factor_digest(pkg.SIDE_X)
+            times = []
+            for _ in range(20):
+                t0 = time.perf_counter()
+                core.factor_digest(pkg.SIDE_X)
+                times.append(time.perf_counter() - t0)
+            nbytes = 4.0 * a.users * k
+            emit({"leg": "factor_digest", "k": k, "rows": a.users, "bytes": nbytes, "wall_ms_min": min(times) * 1e3,
+                  "wall_ms_median": float(np.median(times)) * 1e3, "read_TBps_at_min": nbytes / min(times) / 1e12,
+                  "read_TBps_at_median": nbytes / float(np.median(times)) / 1e12, "calls": 20}, a.out)
         # single-update latency from 1 and 32 writer threads while 32 threads recommend
         for writers in (1, 32):
             stop = threading.Event()
