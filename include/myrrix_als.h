@@ -549,6 +549,49 @@ int mals_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t*
 int mals_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
                                 const float* values, float* out, int32_t* status_out);
 
+/* ---- mostPopularItems on the device -----------------------------------------------------------------------------
+ * ServerRecommender.mostPopularItems(howMany, rescorer) (online/src/net/myrrix/online/ServerRecommender.java:611-673,
+ * scored by MostPopularItemsIterator.java:51-67) over the known items resident on the handle, in the reference's order:
+ *  1. Counted users: every user row this handle holds known items for -- the local shard and, on a handle outside a group,
+ *     the rows mals_grow_factor_rows added -- except the rows named by mals_set_tag_users: the itemTagIDs, "users" that
+ *     are really tags of items (:631-638).  mals_set_tag_users takes n GLOBAL user rows (host or device); rows outside the
+ *     handle's users are ignored; n = 0 clears the set; nothing else reads it.  Like mals_set_tag_items it must not run
+ *     while calls are in flight.  mals_set_matrix / mals_begin_matrix of side X drop the set (it named the old rows).
+ *     mals_ingest_install hands the ingest's itemTagIDs over as user rows; mals_ingest_install_group and
+ *     mals_group_ingest_finish do NOT: their callers use mals_group_set_tag_users.
+ *  2. A user's set is its CURRENT known items: the replaced set after a removal, else the base row (the installed known
+ *     items, or the user's row of R if none were installed) plus the items this generation's writes added.  It is a set:
+ *     an item repeated in a caller-supplied row, or added again by a write, counts once; base rows need not be sorted.  A
+ *     handle with neither a side-X matrix, nor known items, nor written known items is MALS_INVALID_ARG (the reference
+ *     throws UnsupportedOperationException, :622).
+ *  3. count(i) = the number of counted users whose set holds i.  Items with count 0 are no candidates whatever a
+ *     rescorer's offset (they are not in itemCounts), nor are the rows of Y struck by mals_set_tag_items (userTagIDs,
+ *     :657-667).
+ *  4. value(i) = the float that count(i) increments by 1.0f reach (FastByIDFloatMap.increment, :644): (float)min(count(i),
+ *     16777216) -- in fp32 2^24 + 1.0f rounds back to 2^24 (halfway, to even), so the reference's sum stays there.
+ *  5. With a rescorer (r non-NULL, bound to this handle; MostPopularItemsIterator.java:56-63): a filtered item is skipped;
+ *     value = (float) fl(fl(scale_i * (double)value) + offset_i), fp64 without contraction (the formula of
+ *     mals_recommend_rescored); a value that is not finite after the cast to float skips the item -- never an error
+ *     (this iterator has no checkState).  Always exact: the weight range of the bf16 filter does not apply.
+ *  6. The how_many (1..4096) best come back best first, equal values in ascending item index (the library's rule; the
+ *     reference leaves ties in hash order): ONE block of how_many entries in item_idx_out / score_out, padded with -1 /
+ *     -inf; n_out (may be NULL): the results.  Counts are small integers, ties at the cut are the rule: the selection is a
+ *     radix select over 64-bit (value, index) keys on the device, exact for any number of ties (csrc/popular_kernels.h);
+ *     only the result block crosses to the host.  Needs the item factor rows declared (they say how many items there are).
+ *  7. THREADS: an exclusive ticket of the serving front, like the fold-in reads: callable from any request thread while
+ *     mals_recommend* calls are in flight; it sees the known items, the writes and the rescorer as they are when its turn
+ *     comes.  Not for a member of a group (mals_group_most_popular_items).
+ *  8. The per-item counts stay on the device after a call and are recomputed only when something they depend on changed
+ *     since: mals_set_known_items, mals_set_matrix / mals_begin_matrix of side X, mals_set_factor_rows / mals_bind_factors
+ *     of side X, any mals_set_preferences / mals_remove_preferences / mals_grow_factor_rows batch, mals_set_tag_users, or
+ *     another item count.  Rescorer changes and mals_set_tag_items act after the count and never force a recount.
+ *     mals_most_popular_stats: out4 = {calls, recounts, user rows whose set the last recount took from the writes' overlay
+ *     (not their base row), (user, item) pairs counted in the last recount}; read without a ticket. */
+int mals_set_tag_users(mals_handle h, int64_t n, const int64_t* user_idx, int mem_kind);
+int mals_get_tag_user_count(mals_handle h, int64_t* n_out);   /* distinct user rows of this handle currently not counted */
+int mals_most_popular_items(mals_handle h, mals_rescorer r, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out);
+int mals_most_popular_stats(mals_handle h, int64_t* out4);
+
 /* ---- ingest -> CSR ------------------------------------------------------
  * What InputFilesReader.readInputFiles (online-local/src/net/myrrix/online/generation/
  * InputFilesReader.java:64-211) does to the parsed records of the input files, on the device: the
@@ -914,6 +957,19 @@ int mals_group_recommend_to_anonymous(mals_group g, int32_t n_queries, const int
                                       int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out, int32_t* status_out);
 int mals_group_estimate_for_anonymous(mals_group g, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr,
                                       const int64_t* item_row, const float* values, float* out, int32_t* status_out);
+/* mostPopularItems on a group whose ranks all live in this process (else MALS_INVALID_ARG, like the twins above).  The
+ * known items are sharded by owner, so no member can answer alone: every local member counts the users it owns, side by
+ * side on its own device; the partial count arrays are added on one member (peer copies, whichever backend the group was
+ * made with); saturation at 2^24, the tag items and the selection happen after the sum.  The answer is bit for bit what
+ * ONE handle holding the whole model returns from mals_most_popular_items (arguments as there; no rescorer: rescorers on
+ * groups stay out of scope).  It holds every member's serving front while it runs, like a group write, but takes no
+ * group-wide lock.  Each member keeps its own counts and recounts only after a change (point 8 there).
+ * mals_group_set_tag_users: n GLOBAL user rows (host); each member keeps those it owns; n = 0 clears.  The calls that
+ * start a new generation on a group (mals_group_set_matrix / mals_group_begin_matrix of side X, mals_ingest_install_group,
+ * mals_group_ingest_finish) drop the set on every member, as they drop the overlays -- and none of them hands the ingest's
+ * itemTagIDs over: call mals_group_set_tag_users afterwards. */
+int mals_group_set_tag_users(mals_group g, int64_t n, const int64_t* user_idx);
+int mals_group_most_popular_items(mals_group g, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out);
 
 /* ---- a digest of a factor replica, on the device -------------------------------------------------------------------
  * The proof that replicas agree without copying them to the host.  The digest of rows [row_begin, row_begin + n_rows) of a

@@ -182,6 +182,12 @@ SYMBOLS = {
     "mals_estimate_for_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P, _P]),
     "mals_set_tag_items": (ctypes.c_int, [_H, _I64, _P, ctypes.c_int]),
     "mals_get_tag_item_count": (ctypes.c_int, [_H, ctypes.POINTER(_I64)]),
+    "mals_set_tag_users": (ctypes.c_int, [_H, _I64, _P, ctypes.c_int]),
+    "mals_get_tag_user_count": (ctypes.c_int, [_H, ctypes.POINTER(_I64)]),
+    "mals_most_popular_items": (ctypes.c_int, [_H, _H, _I32, _P, _P, ctypes.POINTER(_I32)]),
+    "mals_most_popular_stats": (ctypes.c_int, [_H, _P]),
+    "mals_group_set_tag_users": (ctypes.c_int, [_H, _I64, _P]),
+    "mals_group_most_popular_items": (ctypes.c_int, [_H, _I32, _P, _P, ctypes.POINTER(_I32)]),
     "mals_ingest_device": (ctypes.c_int, [_H, ctypes.POINTER(_I32)]),
     "mals_ingest_device_tag_items": (ctypes.c_int, [_H, ctypes.POINTER(_P), ctypes.POINTER(_I64)]),
     "mals_ingest_get_tag_items": (ctypes.c_int, [_H, _P]),

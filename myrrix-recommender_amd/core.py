@@ -526,6 +526,34 @@ class ALSCore:
         self._chk(self._L.mals_get_tag_item_count(self._h, ctypes.byref(n)))
         return n.value
 
+    def set_tag_users(self, user_idx):
+        """itemTagIDs as global user rows: "users" that are tags of items, which most_popular_items does not count
+        (ServerRecommender.java:631-638); rows outside this handle's users are ignored; None or empty clears."""
+        uu = _host(user_idx if user_idx is not None else [], np.int64)
+        self._chk(self._L.mals_set_tag_users(self._h, len(uu), uu.ctypes.data_as(ctypes.c_void_p) if len(uu) else None, MEM_HOST))
+
+    def tag_user_count(self):
+        n = ctypes.c_int64(0)
+        self._chk(self._L.mals_get_tag_user_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def most_popular_items(self, how_many, rescorer=None):
+        """mostPopularItems (ServerRecommender.java:611-673): the items most users know, best first, ties in ascending item
+        index.  Returns (item_idx [how_many] int64, scores float32 -- the user counts, or their rescored values -- and the
+        number of results); padding -1 / -inf.  rescorer: a Rescorer of this handle (None: none)."""
+        idx = np.empty(int(how_many), dtype=np.int64)
+        sc = np.empty(int(how_many), dtype=np.float32)
+        cnt = ctypes.c_int32(0)
+        self._chk(self._L.mals_most_popular_items(self._h, rescorer.handle if rescorer is not None else None, int(how_many),
+                                                  idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cnt)))
+        return idx, sc, cnt.value
+
+    def most_popular_stats(self):
+        """{calls, recounts, overlay_rows, pairs}: the last two describe the last recount."""
+        o = np.zeros(4, dtype=np.int64)
+        self._chk(self._L.mals_most_popular_stats(self._h, o.ctypes.data_as(ctypes.c_void_p)))
+        return {"calls": int(o[0]), "recounts": int(o[1]), "overlay_rows": int(o[2]), "pairs": int(o[3])}
+
     def recommend_front_stats(self):
         """{calls, queries, passes, exclusive} of the serving front since the handle was created."""
         o = np.zeros(4, dtype=np.int64)

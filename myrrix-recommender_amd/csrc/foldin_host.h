@@ -353,6 +353,7 @@ int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int6
     if (urow[t] >= own_lo && urow[t] < own_hi)
       foldin_overlay_add(fs, urow[t] - x.row_offset, (int32_t)irow[t]);   // knownItemIDs.get(userID).add(itemID) (:813-836)
   }
+  if (applied) popular_touch(h, false);   // known items were added: what mals_most_popular_items counted is stale
   std::atomic<int64_t>* c = h->foldin_counters;
   c[0] += applied;
   c[1] += failed;
@@ -398,6 +399,7 @@ int foldin_remove_decide(mals_handle h, int64_t n, const int64_t* urow, const in
   need.erase(std::unique(need.begin(), need.end()), need.end());
   std::vector<std::vector<int32_t>> full;
   if (int rc = foldin_known_full(h, need, full, msg)) return rc;
+  popular_touch(h, false);   // (conservative: a batch that removes nothing recounts too)
   for (size_t j = 0; j < need.size(); ++j) {
     if (need[j] < (int64_t)fs.head.size()) fs.head[(size_t)need[j]] = UINT32_MAX;
     fs.replaced[need[j]].swap(full[j]);   // (an empty set: a user without known items, whose removals are ignored)
@@ -509,6 +511,7 @@ int foldin_grow_finish(mals_handle h, int side, int64_t n_rows, FoldinGrow& gw, 
   s.G_valid = false;
   ++s.F_epoch;
   if (side == MALS_SIDE_X && owns_grown_users) h->grown_users_end.store(n_rows, std::memory_order_release);
+  popular_touch(h, false);
   return MALS_OK;
 }
 

@@ -642,6 +642,18 @@ int mals_ingest_install(mals_ingest g, mals_handle h) {
   if (g->n_tag_ids[1] > 0 && (!fy || fy_rows < g->n_items))
     if (int rc = mals_set_factor_rows(h, MALS_SIDE_Y, g->n_items)) return fail(g, rc, mals_last_error(h));
   if (int rc = mals_set_tag_items(h, g->n_tag_ids[1], g->tag_item_idx.get(), MALS_MEM_DEVICE)) return fail(g, rc, mals_last_error(h));
+  // itemTagIDs as rows of R: the "users" mals_most_popular_items does not count (ServerRecommender.java:631-638); -1 (a tag
+  // that owns no row) is outside the handle's users and ignored there.  (mals_set_matrix(side X) has dropped an earlier set.)
+  if (g->n_tag_ids[0] > 0) {
+    ICHK(g, hipSetDevice(g->device));
+    DeviceBuffer<int64_t> tag_user_idx;
+    ICHK(g, tag_user_idx.alloc((size_t)g->n_tag_ids[0]));
+    hipLaunchKernelGGL(index_of_ids_kernel, dim3(blocks_for(g->n_tag_ids[0])), dim3(256), 0, g->stream, g->tag_ids[0].get(), g->n_tag_ids[0], g->ids[0].get(),
+                       (int64_t)g->n_users, tag_user_idx.get());
+    ICHK(g, hipGetLastError());
+    ICHK(g, hipStreamSynchronize(g->stream));
+    if (int rc = mals_set_tag_users(h, g->n_tag_ids[0], tag_user_idx.get(), MALS_MEM_DEVICE)) return fail(g, rc, mals_last_error(h));
+  }
   return MALS_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "host_solver.h"
 #include "topn_kernels.h"
 #include "foldin_kernels.h"
+#include "popular_kernels.h"
 #define MALS_FACTOR_DIGEST_KERNEL
 #include "factor_digest.h"
 #include "mals_internal.h"
@@ -257,6 +258,11 @@ struct mals_handle_s {
   std::atomic<int64_t> foldin_counters[6] = {};
   // one past the last user row mals_grow_factor_rows added to this handle's users (-1: none); read by request threads
   std::atomic<int64_t> grown_users_end{-1};
+  // mals_most_popular_items (popular_host.h): the count cache and the tag users; the counter every call that may change a
+  // counted user's set bumps (popular_touch), the same for the base CSR alone, and mals_most_popular_stats
+  void* pop = nullptr;
+  std::atomic<uint64_t> pop_epoch{1}, pop_base_epoch{1};
+  std::atomic<int64_t> popular_counters[4] = {};
 };
 
 namespace {
@@ -294,8 +300,16 @@ bool foldin_has_overlay(mals_handle h);
 int foldin_known_full(mals_handle h, const std::vector<int64_t>& rows, std::vector<std::vector<int32_t>>& outs, std::string& msg);
 int64_t foldin_user_rows_end(mals_handle h);
 
+// popular_host.h: what mals_most_popular_items counted is stale (base: the base CSR itself is another one)
+void popular_touch(mals_handle h, bool base) {
+  h->pop_epoch.fetch_add(1, std::memory_order_acq_rel);
+  if (base) h->pop_base_epoch.fetch_add(1, std::memory_order_acq_rel);
+}
+void popular_new_generation(mals_handle h, bool new_rows);
+
 void clear_known_items(mals_handle h) {
   foldin_drop_overlay(h);   // a new generation's known items: the writes of the old one are gone with it
+  popular_new_generation(h, false);   // ... and so is what mals_most_popular_items counted
   h->known_ptr_copy.reset();
   h->known_idx_copy.reset();
   h->known_ptr = nullptr;
@@ -1487,6 +1501,7 @@ void rescorer_bind(const mals_rescorer_s* r, std::shared_ptr<const RescorerState
 namespace {
 #include "topn_host.h"
 #include "foldin_host.h"
+#include "popular_host.h"
 }  // namespace
 
 // ================================================================================================
@@ -1669,6 +1684,7 @@ int mals_destroy(mals_handle h) {
   if (h->ev_G) (void)hipEventDestroy(h->ev_G);
   topn_free(h);
   foldin_free(h);
+  popular_free(h);
   delete h;   // every buffer the handle owns, with its device current
 
   return MALS_OK;
@@ -1698,6 +1714,7 @@ int mals_set_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
   s.G_valid = false;
   ++s.F_epoch;
   if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
+  if (side == MALS_SIDE_X) popular_touch(h, false);
   if (side == MALS_SIDE_Y) h->lsh.clear();                 // ... and its rows are not the ones the candidate filter signed
   return MALS_OK;
 }
@@ -1713,6 +1730,7 @@ int mals_bind_factors(mals_handle h, int side, float* device_ptr, int64_t n_rows
   s.G_valid = false;
   ++s.F_epoch;
   if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
+  if (side == MALS_SIDE_X) popular_touch(h, false);
   if (side == MALS_SIDE_Y) h->lsh.clear();
   return MALS_OK;
 }
@@ -1736,6 +1754,7 @@ int mals_set_matrix(mals_handle h, int side, int64_t row_offset, int64_t n_rows_
   HIPCHK(h, hipStreamSynchronize(h->stream));
   free_matrix(s);
   if (side == MALS_SIDE_X) clear_known_items(h);  // they were a CSR over the OLD local rows (and maybe borrowed arrays)
+  if (side == MALS_SIDE_X) popular_new_generation(h, true);   // ... and the tag users named the old rows
   s.row_offset = row_offset;
   s.n_local = n_rows_local;
   s.nnz = nnz;
@@ -1782,6 +1801,7 @@ int mals_begin_matrix(mals_handle h, int side, int64_t row_offset, int64_t n_row
   HIPCHK(h, hipStreamSynchronize(h->stream));
   free_matrix(s);
   if (side == MALS_SIDE_X) clear_known_items(h);
+  if (side == MALS_SIDE_X) popular_new_generation(h, true);
   s.row_offset = row_offset;
   s.n_local = n_rows_local;
   s.nnz = nnz;
@@ -1836,6 +1856,7 @@ int mals_end_matrix(mals_handle h, int side) {
     return rc;
   }
   s.has_matrix = true;
+  if (side == MALS_SIDE_X) popular_touch(h, true);   // the rows of R are there now
   return MALS_OK;
 }
 
@@ -3306,6 +3327,45 @@ int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, do
   return foldin_exclusive(h, fn, msg, "mals_foldin_solve");
 }
 
+// ---- mostPopularItems (popular_host.h) ------------------------------------------------------------------------------------
+int mals_set_tag_users(mals_handle h, int64_t n, const int64_t* user_idx, int mem_kind) {
+  if (!h) return MALS_INVALID_ARG;
+  if (mem_kind != MALS_MEM_HOST && mem_kind != MALS_MEM_DEVICE) return fail(h, MALS_INVALID_ARG, "mem_kind must be MALS_MEM_HOST or MALS_MEM_DEVICE");
+  if (n < 0 || (n > 0 && !user_idx)) return fail(h, MALS_INVALID_ARG, "bad tag user list");
+  std::vector<int64_t> host;
+  if (mem_kind == MALS_MEM_DEVICE && n > 0) {
+    if (int rc = use_device(h)) return rc;
+    host.resize((size_t)n);
+    HIPCHK(h, hipMemcpy(host.data(), user_idx, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
+    user_idx = host.data();
+  }
+  popular_set_tag_users(h, n, user_idx);
+  return MALS_OK;
+}
+
+int mals_get_tag_user_count(mals_handle h, int64_t* n_out) {
+  if (!h || !n_out) return MALS_INVALID_ARG;
+  *n_out = h->pop ? (int64_t)popular_state(h)->tag_users.size() : 0;
+  return MALS_OK;
+}
+
+int mals_most_popular_items(mals_handle h, mals_rescorer r, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (r && r->h != h) return topn_fail(h, MALS_INVALID_ARG, "the rescorer belongs to another handle");
+  if (int rc = foldin_refuse(h, "mals_most_popular_items")) return rc;
+  if (how_many <= 0 || how_many > 4096 || !item_idx_out || !score_out)
+    return topn_fail(h, MALS_INVALID_ARG, "mals_most_popular_items: bad arguments (how_many in 1..4096)");
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int { return popular_run(h, r, how_many, item_idx_out, score_out, n_out, msg); };
+  return foldin_exclusive(h, fn, msg, "mals_most_popular_items");
+}
+
+int mals_most_popular_stats(mals_handle h, int64_t* out4) {
+  if (!h || !out4) return MALS_INVALID_ARG;
+  for (int i = 0; i < 4; ++i) out4[i] = h->popular_counters[i].load();
+  return MALS_OK;
+}
+
 }  // extern "C"
 
 // ---- the write path on the members of a group (mals_group.cpp: the mals_group_* twins) ---------------------------------
@@ -3510,6 +3570,86 @@ int malsi_group_factor_digest(mals_handle* hs, int n_members, int side, int64_t 
       }
       cell[(size_t)m].reset();
     }
+    return rc;
+  };
+  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+}
+
+// mals_group_set_tag_users: every member keeps the rows it owns (a handle ignores rows outside its users)
+int malsi_group_set_tag_users(mals_handle* hs, int n_members, int64_t n, const int64_t* user_idx, std::string* err) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    for (int m = 0; m < n_members; ++m) popular_set_tag_users(hs[m], n, user_idx);
+    return MALS_OK;
+  };
+  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+}
+
+// mals_group_most_popular_items: every member counts the users it owns, side by side; the partial arrays are added on
+// member 0 (peer copies), which saturates, strikes the tag items and selects -- after the sum, as one handle would
+int malsi_group_most_popular_items(mals_handle* hs, int n_members, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out,
+                                   std::string* err) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    int64_t n_items = 0;
+    bool any_known = false;
+    for (int m = 0; m < n_members; ++m) {
+      const SideState& y = hs[m]->side[MALS_SIDE_Y];
+      if (!y.F || y.n_total <= 0 || (m > 0 && y.n_total != n_items)) {
+        msg = "the item factor rows are not declared alike on every member";
+        return MALS_INVALID_ARG;
+      }
+      n_items = y.n_total;
+      any_known = any_known || popular_has_known(hs[m]);
+    }
+    if (!any_known) {
+      msg = "no known items: neither a user-side matrix, nor installed known items, nor writes";
+      return MALS_INVALID_ARG;
+    }
+    if (hs[0]->tag_bits.get() && hs[0]->tag_bits_items != n_items) {
+      msg = "the tag items were set for another item count";
+      return MALS_INVALID_ARG;
+    }
+    std::vector<char> rec((size_t)n_members, 0);
+    std::vector<int64_t> n_override((size_t)n_members, 0);
+    int rc = MALS_OK;
+    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
+      rc = group_on_device(hs[m], msg);
+      bool recounted = false;
+      if (rc == MALS_OK) rc = popular_count_enqueue(hs[m], n_items, &recounted, &n_override[(size_t)m], msg);
+      rec[(size_t)m] = recounted ? 1 : 0;
+    }
+    if (rc != MALS_OK) group_drain(hs, n_members);
+    for (int m = 0; m < n_members; ++m) {
+      int64_t pairs = 0;
+      if (rec[(size_t)m]) {
+        std::string mine;
+        int r2 = group_on_device(hs[m], mine);
+        if (r2 == MALS_OK) r2 = popular_count_finish(hs[m], &pairs, mine);
+        if (r2 != MALS_OK && rc == MALS_OK) {
+          rc = r2;
+          msg = mine;
+        }
+      }
+      if (rc == MALS_OK) popular_note(hs[m], rec[(size_t)m] != 0, n_override[(size_t)m], pairs);
+    }
+    if (rc != MALS_OK) return rc;
+    // the sum, on member 0's device and stream (every member's array is complete: the waits above)
+    mals_handle h0 = hs[0];
+    if (int r0 = group_on_device(h0, msg)) return r0;
+    PopularState& p0 = *popular_state(h0);
+    const size_t bytes = sizeof(uint32_t) * (size_t)n_items;
+    FCHK(msg, p0.d_sum.reserve((size_t)n_items, h0->stream));
+    FCHK(msg, hipMemcpyAsync(p0.d_sum.get(), p0.count.get(), bytes, hipMemcpyDeviceToDevice, h0->stream));
+    DeviceBuffer<uint32_t> part;
+    if (n_members > 1) FCHK(msg, part.alloc((size_t)n_items));
+    for (int m = 1; m < n_members; ++m) {
+      FCHK(msg, hipMemcpyPeerAsync(part.get(), h0->cfg.device, popular_state(hs[m])->count.get(), hs[m]->cfg.device, bytes, h0->stream));
+      hipLaunchKernelGGL(popular_add_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, h0->stream, p0.d_sum.get(), part.get(), n_items);
+      FCHK(msg, hipGetLastError());
+    }
+    rc = popular_select_run(h0, p0.d_sum.get(), n_items, nullptr, how_many, item_idx_out, score_out, n_out, msg);
+    if (rc != MALS_OK) (void)hipStreamSynchronize(h0->stream);   // `part` goes: nothing may still read it
     return rc;
   };
   return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);

@@ -1600,6 +1600,31 @@ int mals_group_estimate_for_anonymous(mals_group g, int32_t n_queries, const int
   return read_failed(g, h, malsi_member_estimate_for_anonymous(h, n_queries, to_item, item_ptr, item_row, values, out, status_out));
 }
 
+int mals_group_set_tag_users(mals_group g, int64_t n, const int64_t* user_idx) {
+  if (int rc = foldin_group_ready(g, "mals_group_set_tag_users")) return rc;
+  if (n < 0 || (n > 0 && !user_idx)) return gfail(g, MALS_INVALID_ARG, "mals_group_set_tag_users: bad tag user list");
+  std::vector<mals_handle> hs = member_handles(g);
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  std::string msg;
+  return write_failed(g, malsi_group_set_tag_users(hs.data(), (int)hs.size(), n, user_idx, &msg), "mals_group_set_tag_users", msg);
+}
+
+int mals_group_most_popular_items(mals_group g, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  if (int rc = foldin_group_ready(g, "mals_group_most_popular_items")) return rc;
+  if (how_many <= 0 || how_many > 4096 || !item_idx_out || !score_out) {
+    std::lock_guard<std::mutex> lk(g->err_mu);
+    return gfail(g, MALS_INVALID_ARG, "mals_group_most_popular_items: bad arguments (how_many in 1..4096)");
+  }
+  std::vector<mals_handle> hs = member_handles(g);
+  std::string msg;
+  const int rc = malsi_group_most_popular_items(hs.data(), (int)hs.size(), how_many, item_idx_out, score_out, n_out, &msg);
+  if (rc != MALS_OK) {
+    std::lock_guard<std::mutex> lk(g->err_mu);
+    return write_failed(g, rc, "mals_group_most_popular_items", msg);
+  }
+  return MALS_OK;
+}
+
 int mals_group_replica_digest(mals_group g, int side, int64_t row_begin, int64_t n_rows, uint64_t* out_per_local_member, int32_t* all_equal_out) {
   if (int rc = foldin_group_ready(g, "mals_group_replica_digest")) return rc;
   GSIDE(g, side);

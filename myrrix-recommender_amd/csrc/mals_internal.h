@@ -47,6 +47,11 @@ __attribute__((visibility("hidden"))) int malsi_group_grow_factor_rows(mals_hand
                                                                      int grown_owner, std::string* err);
 __attribute__((visibility("hidden"))) int malsi_group_factor_digest(mals_handle* hs, int n_members, int side, int64_t row_begin, int64_t n_rows,
                                                                   uint64_t* out, std::string* err);
+// mals_group_set_tag_users / mals_group_most_popular_items (popular_host.h): every member counts its own users, member 0 adds
+// the partial arrays and selects
+__attribute__((visibility("hidden"))) int malsi_group_set_tag_users(mals_handle* hs, int n_members, int64_t n, const int64_t* user_idx, std::string* err);
+__attribute__((visibility("hidden"))) int malsi_group_most_popular_items(mals_handle* hs, int n_members, int32_t how_many, int64_t* item_idx_out,
+                                                                       float* score_out, int32_t* n_out, std::string* err);
 // the fold-in reads on one member's handle (any member answers: replicas and solvers are complete everywhere)
 __attribute__((visibility("hidden"))) int malsi_member_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row,
                                                                           const int64_t* item_row, float* out);

@@ -1,0 +1,274 @@
+// popular_host.h -- host side of mals_most_popular_items / mals_set_tag_users (include/myrrix_als.h; kernels in
+// popular_kernels.h).  Included by mals_api.hip inside its anonymous namespace, after foldin_host.h: the read runs as an
+// exclusive ticket of the serving front (foldin_exclusive), so the state below is only ever touched by the front's leader --
+// except the tag users, which follow the rule of mals_set_tag_items (not while calls are in flight).
+//
+// THE COUNT CACHE.  The per-item count array stays on the device.  The handle carries a counter (pop_epoch) that every
+// call which may change a counted user's set bumps (popular_touch: a new generation's known items or user-side matrix, a
+// new X replica, every applied write batch, the tag users); a call recounts when the counter, or the item count, is not
+// the one its array was counted at.  Rescorers and the tag ITEMS act after the count (popular_key_kernel).
+#pragma once
+
+struct PopularState {
+  std::vector<int64_t> tag_users;          // itemTagIDs as local user rows: ascending, unique
+  DeviceBuffer<uint32_t> count;            // [n_items]: this handle's users
+  uint64_t counted_epoch = 0;              // the pop_epoch `count` was counted at (0: never)
+  int64_t counted_items = -1;
+  uint64_t ascending_epoch = 0;            // the pop_base_epoch base_ascending was decided at (0: never)
+  bool base_ascending = false;             // every row of the base CSR is strictly ascending
+  // per recount: the skip bitset over the base rows, the override CSR, the pair counter and the ascending flag
+  std::vector<uint32_t> h_skip;             // (host images: they outlive the asynchronous copies made from them)
+  std::vector<int64_t> h_optr;
+  std::vector<int32_t> h_oidx;
+  DeviceBuffer<uint32_t> d_skip;
+  DeviceBuffer<int64_t> d_optr;
+  DeviceBuffer<int32_t> d_oidx;
+  DeviceBuffer<unsigned long long> d_pairs;   // {pairs, flag}
+  // per call: the keys, the selection state, the histogram and the survivors
+  DeviceBuffer<unsigned long long> d_keys, d_out;
+  DeviceBuffer<PopularSelect> d_sel;
+  DeviceBuffer<unsigned> d_hist;
+  DeviceBuffer<uint32_t> d_sum;            // a group's summed counts (on the member that selects)
+};
+
+PopularState* popular_state(mals_handle h) {
+  if (!h->pop) h->pop = new PopularState();
+  return static_cast<PopularState*>(h->pop);
+}
+
+void popular_free(mals_handle h) {
+  delete static_cast<PopularState*>(h->pop);
+  h->pop = nullptr;
+}
+
+// a new generation: the cache goes (with the overlay, clear_known_items); new_rows: the local user rows are new ones, the
+// tag users named the old
+void popular_new_generation(mals_handle h, bool new_rows) {
+  popular_touch(h, true);
+  PopularState* ps = static_cast<PopularState*>(h->pop);
+  if (!ps) return;
+  ps->count.reset();
+  ps->counted_epoch = 0;
+  if (new_rows) std::vector<int64_t>().swap(ps->tag_users);
+}
+
+// itemTagIDs (ServerRecommender.java:626, :638): global user rows (host); those outside this handle's users are ignored
+void popular_set_tag_users(mals_handle h, int64_t n, const int64_t* user_idx) {
+  PopularState& ps = *popular_state(h);
+  const int64_t lo = h->side[MALS_SIDE_X].row_offset, hi = foldin_user_rows_end(h);
+  std::vector<int64_t> v;
+  for (int64_t j = 0; j < n; ++j)
+    if (user_idx[j] >= lo && user_idx[j] < hi) v.push_back(user_idx[j] - lo);
+  std::sort(v.begin(), v.end());
+  v.erase(std::unique(v.begin(), v.end()), v.end());
+  ps.tag_users.swap(v);
+  popular_touch(h, false);
+}
+
+unsigned popular_grid(mals_handle h, int64_t n_units, int per_block) {
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->n_cu * 8, (n_units + per_block - 1) / per_block));
+}
+
+// whether a call on this handle has anything to count (the reference: knownItemIDs == null -> UnsupportedOperationException, :622)
+bool popular_has_known(mals_handle h) { return h->side[MALS_SIDE_X].has_matrix || h->known_ptr || foldin_has_overlay(h); }
+
+// count[] of this handle's users for n_items items, enqueued on the handle's stream unless the cache holds it; *recounted
+// says which.  The host work of a recount (the override CSR) is done here; the stats of a recount are read back by
+// popular_count_finish, after the wait.
+int popular_count_enqueue(mals_handle h, int64_t n_items, bool* recounted, int64_t* n_override, std::string& msg) {
+  PopularState& ps = *popular_state(h);
+  const uint64_t epoch = h->pop_epoch.load(std::memory_order_acquire);
+  *recounted = false;
+  if (ps.count && ps.counted_epoch == epoch && ps.counted_items == n_items) return MALS_OK;
+  const SideState& x = h->side[MALS_SIDE_X];
+  if (h->known_ptr && h->known_rows != x.n_local) {
+    msg = "the installed known items do not match the local user rows";
+    return MALS_INVALID_ARG;
+  }
+  const int64_t n_base = foldin_base_rows(h);
+  const int64_t* bptr = h->known_ptr ? h->known_ptr : x.row_ptr;
+  const int32_t* bidx = h->known_ptr ? h->known_idx : x.col;
+  // users whose current set is not their base row: an added chain or a replaced set (grown users have nothing else)
+  const FoldinState* fs = static_cast<const FoldinState*>(h->fo);
+  std::vector<int64_t> orows;
+  if (fs) {
+    for (size_t r = 0; r < fs->head.size(); ++r)
+      if (fs->head[r] != UINT32_MAX) orows.push_back((int64_t)r);
+    for (const auto& kv : fs->replaced) orows.push_back(kv.first);
+    std::sort(orows.begin(), orows.end());
+    orows.erase(std::unique(orows.begin(), orows.end()), orows.end());
+  }
+  // the skip bits of the base pass: tag users and the users of the override CSR; the override CSR leaves the tag users out
+  const size_t words = (size_t)((n_base + 31) / 32);
+  std::vector<uint32_t>& skip = ps.h_skip;
+  skip.clear();
+  auto mark = [&](int64_t r) {
+    if (r < n_base) {
+      if (skip.empty()) skip.assign(words, 0u);
+      skip[(size_t)(r >> 5)] |= 1u << (r & 31);
+    }
+  };
+  for (int64_t r : ps.tag_users) mark(r);
+  std::vector<int64_t> counted;
+  for (int64_t r : orows) {
+    mark(r);
+    if (!std::binary_search(ps.tag_users.begin(), ps.tag_users.end(), r)) counted.push_back(r);
+  }
+  std::vector<std::vector<int32_t>> sets;
+  if (!counted.empty())
+    if (int rc = foldin_known_full(h, counted, sets, msg)) return rc;   // sorted, distinct
+  std::vector<int64_t>& optr = ps.h_optr;
+  optr.assign(counted.size() + 1, 0);
+  for (size_t j = 0; j < counted.size(); ++j) optr[j + 1] = optr[j] + (int64_t)sets[j].size();
+  std::vector<int32_t>& oidx = ps.h_oidx;
+  oidx.resize((size_t)optr.back());
+  for (size_t j = 0; j < counted.size(); ++j) std::copy(sets[j].begin(), sets[j].end(), oidx.begin() + optr[j]);
+  *n_override = (int64_t)counted.size();
+
+  ps.counted_epoch = 0;
+  if (ps.count.capacity() != (size_t)n_items) {
+    FCHK(msg, hipStreamSynchronize(h->stream));
+    FCHK(msg, ps.count.alloc((size_t)n_items));
+  }
+  if (!ps.d_pairs) FCHK(msg, ps.d_pairs.alloc(2));
+  FCHK(msg, hipMemsetAsync(ps.count.get(), 0, sizeof(uint32_t) * (size_t)n_items, h->stream));
+  FCHK(msg, hipMemsetAsync(ps.d_pairs.get(), 0, 2 * sizeof(unsigned long long), h->stream));
+  if (n_base > 0) {
+    // once per installed base: are all its rows strictly ascending?
+    const uint64_t base_epoch = h->pop_base_epoch.load(std::memory_order_acquire);
+    if (ps.ascending_epoch != base_epoch) {
+      int* d_flag = reinterpret_cast<int*>(ps.d_pairs.get() + 1);
+      int flag = 0;
+      hipLaunchKernelGGL(popular_ascending_kernel, dim3(popular_grid(h, n_base, 4)), dim3(256), 0, h->stream, bptr, bidx, n_base, d_flag);
+      FCHK(msg, hipGetLastError());
+      FCHK(msg, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      FCHK(msg, hipStreamSynchronize(h->stream));
+      ps.base_ascending = flag == 0;
+      ps.ascending_epoch = base_epoch;
+    }
+    const uint32_t* d_skip = nullptr;
+    if (!skip.empty()) {
+      FCHK(msg, ps.d_skip.reserve(words, h->stream));
+      FCHK(msg, hipMemcpyAsync(ps.d_skip.get(), skip.data(), sizeof(uint32_t) * words, hipMemcpyHostToDevice, h->stream));
+      d_skip = ps.d_skip.get();
+    }
+    const unsigned grid = popular_grid(h, n_base, 4);
+    if (ps.base_ascending)
+      hipLaunchKernelGGL(popular_count_kernel<true>, dim3(grid), dim3(256), 0, h->stream, bptr, bidx, n_base, d_skip, n_items, ps.count.get(),
+                         ps.d_pairs.get());
+    else
+      hipLaunchKernelGGL(popular_count_kernel<false>, dim3(grid), dim3(256), 0, h->stream, bptr, bidx, n_base, d_skip, n_items, ps.count.get(),
+                         ps.d_pairs.get());
+    FCHK(msg, hipGetLastError());
+  }
+  if (!oidx.empty()) {
+    FCHK(msg, ps.d_optr.reserve(optr.size(), h->stream));
+    FCHK(msg, ps.d_oidx.reserve(oidx.size(), h->stream));
+    FCHK(msg, hipMemcpyAsync(ps.d_optr.get(), optr.data(), sizeof(int64_t) * optr.size(), hipMemcpyHostToDevice, h->stream));
+    FCHK(msg, hipMemcpyAsync(ps.d_oidx.get(), oidx.data(), sizeof(int32_t) * oidx.size(), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(popular_count_kernel<true>, dim3(popular_grid(h, (int64_t)counted.size(), 4)), dim3(256), 0, h->stream, ps.d_optr.get(),
+                       ps.d_oidx.get(), (int64_t)counted.size(), (const uint32_t*)nullptr, n_items, ps.count.get(), ps.d_pairs.get());
+    FCHK(msg, hipGetLastError());
+  }
+  *recounted = true;
+  ps.counted_items = n_items;
+  ps.counted_epoch = epoch;   // (withdrawn by popular_count_finish if the recount fails)
+  return MALS_OK;
+}
+
+// after popular_count_enqueue said `recounted`: the wait and the pair count of the recount
+int popular_count_finish(mals_handle h, int64_t* pairs, std::string& msg) {
+  PopularState& ps = *popular_state(h);
+  unsigned long long p = 0;
+  hipError_t e = hipMemcpyAsync(&p, ps.d_pairs.get(), sizeof(p), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    ps.counted_epoch = 0;
+    FCHK(msg, e);
+  }
+  *pairs = (int64_t)p;
+  return MALS_OK;
+}
+
+// count[] -> the how_many best, on the handle's stream; out arrays: one block of how_many entries, padded with -1 / -inf
+int popular_select_run(mals_handle h, const uint32_t* count, int64_t n_items, const mals_rescorer_s* r, int32_t how_many, int64_t* item_idx_out,
+                       float* score_out, int32_t* n_out, std::string& msg) {
+  PopularState& ps = *popular_state(h);
+  FCHK(msg, ps.d_keys.reserve((size_t)n_items, h->stream));
+  FCHK(msg, ps.d_out.reserve(4096, h->stream));
+  if (!ps.d_sel) FCHK(msg, ps.d_sel.alloc(1));
+  if (!ps.d_hist) FCHK(msg, ps.d_hist.alloc(256));
+  const uint32_t* tags = h->tag_bits.get();
+  const unsigned item_blocks = (unsigned)((n_items + 255) / 256);
+  std::shared_ptr<const RescorerState> keep;
+  TopnRescore rs;
+  if (r) {
+    rescorer_bind(r, keep, rs);
+    hipLaunchKernelGGL(popular_key_kernel<true>, dim3(item_blocks), dim3(256), 0, h->stream, count, n_items, tags, rs, ps.d_keys.get());
+  } else {
+    hipLaunchKernelGGL(popular_key_kernel<false>, dim3(item_blocks), dim3(256), 0, h->stream, count, n_items, tags, rs, ps.d_keys.get());
+  }
+  hipLaunchKernelGGL(popular_select_init_kernel, dim3(1), dim3(256), 0, h->stream, ps.d_sel.get(), ps.d_hist.get(), (int)how_many);
+  const unsigned grid = popular_grid(h, n_items, 256 * 8);
+  for (int pass = 0; pass < 8; ++pass) {
+    hipLaunchKernelGGL(popular_hist_kernel, dim3(grid), dim3(256), 0, h->stream, ps.d_keys.get(), n_items, pass, ps.d_sel.get(), ps.d_hist.get());
+    hipLaunchKernelGGL(popular_pick_kernel, dim3(1), dim3(256), 0, h->stream, ps.d_sel.get(), ps.d_hist.get(), pass);
+  }
+  hipLaunchKernelGGL(popular_collect_kernel, dim3(grid), dim3(256), 0, h->stream, ps.d_keys.get(), n_items, ps.d_sel.get(), (int)how_many,
+                     ps.d_out.get());
+  FCHK(msg, hipGetLastError());
+  // only the result block crosses: the selection state and the survivors
+  PopularSelect sel;
+  std::vector<unsigned long long> got((size_t)how_many);
+  FCHK(msg, hipMemcpyAsync(&sel, ps.d_sel.get(), sizeof(sel), hipMemcpyDeviceToHost, h->stream));
+  FCHK(msg, hipMemcpyAsync(got.data(), ps.d_out.get(), sizeof(unsigned long long) * (size_t)how_many, hipMemcpyDeviceToHost, h->stream));
+  FCHK(msg, hipStreamSynchronize(h->stream));
+  const int n = (int)std::min<uint32_t>(sel.taken, (uint32_t)how_many);
+  std::sort(got.begin(), got.begin() + n, std::greater<unsigned long long>());   // best first, equal values in ascending index
+  for (int j = 0; j < how_many; ++j) {
+    item_idx_out[j] = j < n ? (int64_t)(0xffffffffu - (uint32_t)(got[(size_t)j] & 0xffffffffull)) : -1;
+    score_out[j] = j < n ? key_score((uint32_t)(got[(size_t)j] >> 32)) : -std::numeric_limits<float>::infinity();
+  }
+  if (n_out) *n_out = n;
+  return MALS_OK;
+}
+
+// what both the single call and the group twin check inside their ticket
+int popular_ready(mals_handle h, int64_t* n_items, std::string& msg) {
+  *n_items = h->side[MALS_SIDE_Y].n_total;
+  if (!h->side[MALS_SIDE_Y].F || *n_items <= 0) {
+    msg = "the item factor rows are not declared (they say how many items there are)";
+    return MALS_INVALID_ARG;
+  }
+  if (!popular_has_known(h)) {
+    msg = "no known items: neither a user-side matrix, nor mals_set_known_items, nor writes (the reference throws UnsupportedOperationException)";
+    return MALS_INVALID_ARG;
+  }
+  if (h->tag_bits.get() && h->tag_bits_items != *n_items) {
+    msg = "the tag items were set for another item count: call mals_set_tag_items again";
+    return MALS_INVALID_ARG;
+  }
+  return MALS_OK;
+}
+
+void popular_note(mals_handle h, bool recounted, int64_t n_override, int64_t pairs) {
+  std::atomic<int64_t>* c = h->popular_counters;
+  ++c[0];
+  if (recounted) {
+    ++c[1];
+    c[2].store(n_override);
+    c[3].store(pairs);
+  }
+}
+
+int popular_run(mals_handle h, const mals_rescorer_s* r, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out,
+                std::string& msg) {
+  int64_t n_items = 0, n_override = 0, pairs = 0;
+  if (int rc = popular_ready(h, &n_items, msg)) return rc;
+  bool recounted = false;
+  if (int rc = popular_count_enqueue(h, n_items, &recounted, &n_override, msg)) return rc;
+  if (recounted)
+    if (int rc = popular_count_finish(h, &pairs, msg)) return rc;
+  popular_note(h, recounted, n_override, pairs);
+  return popular_select_run(h, popular_state(h)->count.get(), n_items, r, how_many, item_idx_out, score_out, n_out, msg);
+}

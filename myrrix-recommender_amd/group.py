@@ -280,6 +280,21 @@ class GroupALS:
                                                          cnt.ctypes.data_as(ctypes.c_void_p)))
         return idx, sc, cnt
 
+    def set_tag_users(self, user_idx):
+        """itemTagIDs as global user rows: every member keeps those it owns; None or empty clears."""
+        uu = np.ascontiguousarray(user_idx if user_idx is not None else [], dtype=np.int64)
+        self._chk(self._L.mals_group_set_tag_users(self._g, len(uu), uu.ctypes.data_as(ctypes.c_void_p) if len(uu) else None))
+
+    def most_popular_items(self, how_many):
+        """mostPopularItems on the group: every member counts its own users, one member adds the counts and selects.
+        Returns what ALSCore.most_popular_items returns on one handle holding the whole model."""
+        idx = np.empty(int(how_many), dtype=np.int64)
+        sc = np.empty(int(how_many), dtype=np.float32)
+        cnt = ctypes.c_int32(0)
+        self._chk(self._L.mals_group_most_popular_items(self._g, int(how_many), idx.ctypes.data_as(ctypes.c_void_p),
+                                                        sc.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cnt)))
+        return idx, sc, cnt.value
+
     # -- the online write path on the group (the mals_group_* twins of ALSCore's methods of the same names) -------
     # Writes go to every local member (replicated, in one order); a user's known items stay with the member that owns the
     # user; the reads rotate over the members.  Signatures and return values are ALSCore's.

@@ -11,7 +11,10 @@ usage: python tools/bench_topn.py [--items N] [--users U] [--features K] [--how-
        python tools/bench_topn.py --lsh 0.3,0.1 [--lib-root DIR]: recommend with the candidate filter (mals_lsh_build,
        LocationSensitiveHash) off and at each sample ratio in the same run, the build time next to its bytes bounds (the
        signatures read Y once, n k 4 bytes; with the mean computed on the device Y is read twice) and how many queries the bf16 filter path / the dense path answered; with --lib-root of a checkout that has
-       no candidate filter only the filter-off leg runs (the A/B of unfiltered passes against an older build)"""
+       no candidate filter only the filter-off leg runs (the A/B of unfiltered passes against an older build)
+       python tools/bench_topn.py --popular [--items 1000000] [--entries 100000000] [--how-many 100]: mostPopularItems
+       (mals_most_popular_items) over a seeded known-item CSR resident on the device: the first call (the recount), the
+       second (counts cached) and, in the same run, a device-to-device copy of the same index array as the yardstick"""
 import argparse
 import json
 import os
@@ -35,7 +38,11 @@ def main():
     ap.add_argument("--rescorer", action="store_true")
     ap.add_argument("--lsh", default=None, metavar="RATIOS")
     ap.add_argument("--hashes", type=int, default=20)
+    ap.add_argument("--popular", action="store_true")
+    ap.add_argument("--entries", type=int, default=100_000_000)
     a = ap.parse_args()
+    if a.popular:
+        return popular(a)
     if a.lsh:
         return lsh(a)
     if a.similar:
@@ -308,6 +315,54 @@ def lsh(a):
                 leg["dense_queries"] = after["dense_queries"] - before["dense_queries"]
             out["legs"]["off" if ratio is None else str(ratio)] = leg
     out["value"] = out["legs"]["off"]["4096"]["queries_per_s"]
+    print(json.dumps(out))
+
+
+def popular(a):
+    """mostPopularItems: recount and cached call against a device-to-device copy of the index array (4 bytes per entry read
+    and written; the count pass reads them once and adds one atomic per entry)"""
+    import numpy as np
+    import torch
+    import myrrix_recommender_amd as pkg
+    deg = 100
+    n_users = a.entries // deg
+    gen = torch.Generator(device="cuda").manual_seed(1234567890)
+    # strictly ascending rows of `deg` items, popularity skewed towards the low indices
+    first = (torch.rand((n_users, deg), device="cuda", generator=gen).pow_(2.0) * (a.items - deg)).to(torch.int32)
+    col = (torch.sort(first, dim=1).values + torch.arange(deg, device="cuda", dtype=torch.int32)[None, :]).reshape(-1).contiguous()
+    del first
+    rp = torch.arange(n_users + 1, device="cuda", dtype=torch.int64) * deg
+    val = torch.ones(n_users * deg, device="cuda", dtype=torch.float32)
+    out = {"metric": "mostPopularItems: recount / cached call / device-to-device copy of the index array, same run", "unit": "ms",
+           "items": a.items, "users": n_users, "entries": n_users * deg, "how_many": a.how_many}
+    with pkg.ALSCore(4) as core:
+        core.set_factor_rows(pkg.SIDE_Y, a.items)
+        core.set_matrix(pkg.SIDE_X, rp, col, val)
+        t0 = time.perf_counter()
+        first_call = core.most_popular_items(a.how_many)
+        out["first_call_ms"] = (time.perf_counter() - t0) * 1e3            # with the ascending check and the allocations
+        recount, cached, copy = [], [], []
+        for _ in range(a.reps):
+            core.set_tag_users(None)                                       # forces a recount
+            t0 = time.perf_counter()
+            again = core.most_popular_items(a.how_many)
+            recount.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            core.most_popular_items(a.how_many)
+            cached.append((time.perf_counter() - t0) * 1e3)
+            assert np.array_equal(again[0], first_call[0]) and np.array_equal(again[1], first_call[1])
+            dst = torch.empty_like(col)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dst.copy_(col)
+            torch.cuda.synchronize()
+            copy.append((time.perf_counter() - t0) * 1e3)
+            del dst
+        st = core.most_popular_stats()
+        out.update({"recount_ms": min(recount), "recount_ms_runs": recount, "cached_ms": min(cached), "cached_ms_runs": cached,
+                    "d2d_copy_ms": min(copy), "d2d_copy_ms_runs": copy, "recount_over_copy": min(recount) / min(copy),
+                    "pairs": st["pairs"], "recounts": st["recounts"], "top": first_call[0][:5].tolist(), "top_counts": first_call[1][:5].tolist()})
+    out["value"] = out["recount_ms"]
     print(json.dumps(out))
 
 
