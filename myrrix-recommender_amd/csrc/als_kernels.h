@@ -27,6 +27,8 @@
 
 #include <type_traits>
 
+#include "work_plan.h"
+
 namespace mals {
 
 #ifndef MALS_WAVES
@@ -46,23 +48,7 @@ __host__ __device__ constexpr int tidx(int T, int i, int j) { return i * T - (i 
 constexpr int GRAMIAN_FLUSH_BINADES = 5;  // gramian_split_kernel: in front of a step this many binades quieter than the slab so far the slab is cut (its rest: a second partial)
 constexpr int YMAX_SLOTS = 64;  // addresses the Gramian kernels spread their max |element| atomics over (power of two)
 
-struct WorkItem {   // one row (list A) or one segment of a long row (list B); 16 bytes, s_load_dwordx4
-  int64_t begin;    // absolute offset into col/val
-  int32_t len;      // entries
-  int32_t id;       // list A: local row; list B: scratch slot
-};
-struct RowC {       // a long row to be finished from its segment partials: slots first_slot + i * stride, i < nseg
-  int64_t first_slot;
-  int32_t row;
-  int32_t nseg;
-  int32_t stride;   // 1, or the group length once als_prereduce_kernel has summed every group of slots into its first
-  int32_t pad_;
-};
-// A wave sums a row's partial slots one after the other (a dependent chain of ~0.7 us each): the most popular item of
-// C4 (7M entries, 1 700 segments) kept the finish kernel running for 1.15 ms with everything else long done.  Rows with
-// more than FINISH_GROUP segments are first reduced group-wise, one wave per group of FINISH_GROUP consecutive slots,
-// in place (als_prereduce_kernel); the finish kernel then walks the group leaders.
-constexpr int FINISH_GROUP = 32;
+// WorkItem, RowC, FINISH_GROUP: the entries of the work lists, work_plan.h (with the planner that fills them)
 
 struct SolveParams {
   const int64_t* row_ptr;   // local CSR

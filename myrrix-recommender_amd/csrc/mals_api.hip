@@ -16,7 +16,7 @@
 #include "factor_digest.h"
 #include "mals_internal.h"
 #include "hip_buffer.h"
-#include "band_plan.h"
+#include "work_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -69,13 +69,9 @@ struct SideState {
   bool appending = false;
   // work lists
   DeviceBuffer<WorkItem> itemsA;  // rows no longer than segment_nnz, longest first
-  int64_t nA = 0;
-  int64_t nnzA = 0, nnzB = 0;  // entries handled by the rows kernel / the segments kernel
   DeviceBuffer<WorkItem> itemsB;  // segments of the long rows, longest first; behind them the chunk's banded segments
                                   // (band_plan.h), band by band
-  int64_t nB = 0;
   DeviceBuffer<RowC> rowsC;
-  int64_t nC = 0;
   DeviceBuffer<float> scratch;
   DeviceBuffer<uint8_t> refine;   // per local row: marked for als_refine_kernel by the kernel that solved it
   int32_t col_min = 0, col_max = -1;  // range of the column indices (checked against the opposite replica)
@@ -83,20 +79,7 @@ struct SideState {
   float local_max_abs_val = 0.f;  // largest |value| of the shard
   double mean_abs_val = 0.0;      // mean |value| used by the operand-range check (all shards if the caller synced it)
   double local_mean_abs_val = 0.0;  // mean |value| of the shard
-  // the lists are stored chunk-major (contiguous ranges of cfg.chunk_rows rows of the shard), each
-  // chunk sorted by length; a chunk can be solved on its own so that the caller can overlap the
-  // exchange of finished chunks with the solve of the next one
-  // itemsA of a chunk: [nA rows for the direct kernel, longest first, then ONE representative empty
-  // row] [the dual classes: nD[3] rows with 48 < len <= 64, nD[2] ..., nD[0] rows with len <= 16 --
-  // descending length throughout] [nZ further empty rows: x = 0, same verdict as the representative]
-  struct ChunkRange {
-    int64_t offA = 0, nA = 0, nnzA = 0, offB = 0, nB = 0, nnzB = 0, offC = 0, nC = 0;
-    int64_t offP = 0, nP = 0;  // groups of partial slots reduced ahead of the finish kernel (entries of rowsC as well)
-    int64_t nD[4] = {0, 0, 0, 0}, nnzD[4] = {0, 0, 0, 0}, nZ = 0;
-    int64_t nBand = 0, nnzBand = 0;  // the tail of list B (included in nB, nnzB): segments cut at the gather table's bands
-    int64_t n_dual() const { return nD[0] + nD[1] + nD[2] + nD[3]; }
-    int64_t nnz_dual() const { return nnzD[0] + nnzD[1] + nnzD[2] + nnzD[3]; }
-  };
+  // the lists are stored chunk-major, each chunk sorted by length (work_plan.h: ChunkRange)
   int64_t n_dual_rows = 0;
   bool band_front = true;  // the banded segments run as one front (one segment per wave) instead of the strided grid
   int64_t chunk_rows_override = -1;  // mals_set_chunk_rows: per-side value of cfg.chunk_rows (-1 = use cfg)
@@ -134,6 +117,13 @@ struct LshState {
   }
 };
 
+struct HalfStamp {  // what a cache that is rebuilt once per half-iteration holds: the solved side, the OPPOSITE side's G_version
+  int side = -1;
+  uint64_t version = 0;
+  bool operator==(const HalfStamp& o) const { return side == o.side && version == o.version; }
+  bool operator!=(const HalfStamp& o) const { return !(*this == o); }
+};
+
 struct PendingEvent {
   hipEvent_t a, b;
   int kind;  // 0 = rows, 1 = segments, 2 = finish, 3 = gramian, 4 = dual, 5 = rotate
@@ -161,8 +151,7 @@ struct mals_handle_s {
   DeviceBuffer<double> d_Gref;      // the reference-rounded Gramian of the gathered side (gramian_ref_kernel), on demand
   DeviceBuffer<double> d_gref_part;
   DeviceBuffer<unsigned long long> d_refined;
-  int pad_side = -1;          // solved side whose opposite matrix the copy holds, version of that side's G and
-  uint64_t pad_version = 0;   // factor-upload count at the time of the copy
+  HalfStamp pad;              // what the copy holds, and the factor-upload count of the opposite side at the time of the copy
   uint64_t pad_epoch = 0;
   std::vector<uint8_t> pad_done;  // chunks solved from the current copy: solving one again starts a new half-iteration
   DeviceBuffer<char> d_eig;   // device image of eig_stage; the four pointers below are views into it
@@ -185,8 +174,7 @@ struct mals_handle_s {
   bool dual_pending = false;  // a chunk's direct kernels are enqueued, its dual part waits for the eigendecomposition
   int dual_pending_side = -1, dual_pending_chunk = -1;
   double tl[4] = {0.0, 0.0, 0.0, 0.0};  // mals_get_timeline
-  int dual_side = -1;         // what the rotated copy currently holds: solved side, version of the opposite G
-  uint64_t dual_version = 0;
+  HalfStamp dual;             // what the rotated copy currently holds
   bool dual_ok = false;       // the half-iteration's systems qualify for the dual path
   // k = 128 with the split-precision gather: the rows / segments kernels that stage the gather through LDS (lds_kernels.h)
   // and the Gramian image in their feature order (all zeros under lossIgnoresUnspecified), rebuilt when the opposite
@@ -201,11 +189,9 @@ struct mals_handle_s {
   void* iter_user = nullptr;
   bool lds_gather = false;
   DeviceBuffer<float> d_Gperm;
-  int gperm_side = -1;
-  uint64_t gperm_version = 0;
+  HalfStamp gperm;
   DeviceBuffer<float> d_zscale;  // {S, 1/S^2} of the split-precision gather (gather_scale_kernel)
-  int zs_side = -1;           // what d_zscale currently holds: solved side, version of the opposite G, value bound
-  uint64_t zs_version = 0;
+  HalfStamp zs;               // what d_zscale currently holds, with the value bound and mean it was computed from
   float zs_bound = -1.f;
   double zs_mean = -1.0;
   DeviceBuffer<unsigned> d_maxabs;
@@ -330,8 +316,6 @@ void free_matrix(SideState& s) {
   s.rowsC.reset();
   s.scratch.reset();
   s.refine.reset();
-  s.nA = s.nB = s.nC = 0;
-  s.nnzA = s.nnzB = 0;
   s.chunks.clear();
   s.h_row_ptr.clear();
   s.h_row_ptr.shrink_to_fit();
@@ -386,13 +370,6 @@ __global__ __launch_bounds__(256) void band_cuts_kernel(const int32_t* __restric
   }
 }
 
-struct BandCuts {
-  int64_t n_bands = 1, band_rows = 0, min_avg = 0;
-  std::vector<int64_t> row;      // the rows long enough, ascending
-  std::vector<int64_t> off;      // [row.size()][n_bands + 1]
-  std::vector<int> unsorted;     // [row.size()]
-};
-
 // Which rows of the shard are banded and where their columns cross the bands: one kernel and one copy back per list build.
 int find_band_cuts(mals_handle h, const SideState& s, BandCuts& bc) {
   const char* e = std::getenv("MALS_BAND_BYTES");   // read at every build: the tests switch it between two handles
@@ -437,12 +414,12 @@ int find_band_cuts(mals_handle h, const SideState& s, BandCuts& bc) {
   return MALS_OK;
 }
 
-// Split the rows of a shard into the three work lists (DESIGN.md "work decomposition"), chunk by chunk.
-int build_work_lists(mals_handle h, SideState& s) {
+// What the list plan and the solve need to know about a shard's entries, found on the device where they live: the value
+// statistics, the column range and the band cuts of the long rows.
+int scan_shard(mals_handle h, SideState& s, BandCuts& bc) {
   s.max_abs_val = 0.f;
   s.mean_abs_val = 0.0;
   s.local_mean_abs_val = 0.0;
-  s.n_dual_rows = 0;
   if (s.nnz > 0) {  // one pass over the values: bounds the Gramian weights (gather_scale_kernel)
     HIPCHK(h, hipMemsetAsync(h->d_maxabs.get(), 0, 4 * sizeof(unsigned), h->stream));
     const unsigned blocks = (unsigned)std::min<int64_t>(4096, (s.nnz + 255) / 256);
@@ -475,182 +452,21 @@ int build_work_lists(mals_handle h, SideState& s) {
     s.col_max = range[1];
     if (s.col_min < 0) return fail(h, MALS_INVALID_ARG, "negative column index");
   }
-  const int64_t n = s.n_local;
-  const int seg = h->cfg.segment_nnz;
-  const int64_t want_chunk = s.chunk_rows_override >= 0 ? s.chunk_rows_override : h->cfg.chunk_rows;
-  const int64_t chunk_rows = want_chunk > 0 ? want_chunk : std::max<int64_t>(n, 1);
-  const int n_chunks = (int)std::max<int64_t>(1, (n + chunk_rows - 1) / chunk_rows);
-  const std::vector<int64_t>& rp = s.h_row_ptr;
-  std::vector<WorkItem> order;
-  std::vector<WorkItem> segs;
-  std::vector<std::pair<int32_t, WorkItem>> band_segs;  // (band, segment) of the chunk's banded rows
-  std::vector<BandPiece> pieces;
-  std::vector<RowC> rowsC, groups;
-  BandCuts bc;
   if (int rc = find_band_cuts(h, s, bc)) return rc;
   {
     const char* e = std::getenv("MALS_BAND_FRONT");  // A/B: 0 = the strided 16x grid
     s.band_front = !e || std::atoi(e) != 0;
   }
-  size_t bc_next = 0;  // cursor into bc.row (the chunks visit the rows in ascending order)
-  int64_t n_banded_rows = 0, n_banded_segs = 0, n_unsorted = 0;
-  order.reserve((size_t)n);
-  int64_t slot = 0;
-  s.chunks.assign((size_t)n_chunks, SideState::ChunkRange());
-  std::vector<int64_t> count((size_t)seg + 2);
-  for (int c = 0; c < n_chunks; ++c) {
-    const int64_t r0 = std::min(n, c * chunk_rows), r1 = std::min(n, (c + 1) * chunk_rows);
-    SideState::ChunkRange& cr = s.chunks[(size_t)c];
-    cr.offA = (int64_t)order.size();
-    cr.offB = (int64_t)segs.size();
-    cr.offC = (int64_t)rowsC.size();
-    // counting sort of the chunk's short rows by length, longest first (stable: ascending row inside a length)
-    std::fill(count.begin(), count.end(), 0);
-    const int64_t dual_len = 16 * (int64_t)h->dual_blocks;  // rows with 1..dual_len entries: dual lists
-    int64_t n_short = 0, n_direct = 0, n_empty = 0;
-    for (int64_t r = r0; r < r1; ++r) {
-      const int64_t len = rp[r + 1] - rp[r];
-      if (len < 0) return fail(h, MALS_INVALID_ARG, "row_ptr must be non-decreasing");
-      if (len <= seg) {
-        ++count[(size_t)(seg - len)];
-        ++n_short;
-        if (len == 0) {
-          ++n_empty;
-        } else if (len <= dual_len) {
-          const int cls = (int)((len - 1) >> 4);
-          ++cr.nD[cls];
-          cr.nnzD[cls] += len;
-        } else {
-          ++n_direct;
-          cr.nnzA += len;
-        }
-      } else {
-        cr.nnzB += len;
-      }
-    }
-    // How the long rows (more than segment_nnz entries) are cut: segments of up to segment_nnz entries when that gives
-    // at least one per SIMD, shorter ones otherwise -- a wave takes ~20 ns per entry, and the user half of C2 (a handful
-    // of rows above 4 096 entries) ran FOUR waves for 80 us on the critical path (round 3: 80 -> 22 us).  Each segment
-    // costs a partial slot, written and read back one after the other by the finish kernel's one wave per row: with
-    // six times the segments on C2's item half the finish kernel went from 23 to 70 us and ate the gain -- hence only
-    // for lists that cannot even give every SIMD a segment, and never below 512 entries.
-    int64_t seg_b = seg;
-    {
-      const int64_t want_segments = (int64_t)h->n_cu * 4;
-      const int64_t lo = std::min<int64_t>(512, seg);
-      seg_b = std::max<int64_t>(lo, std::min<int64_t>(seg, (cr.nnzB + want_segments - 1) / want_segments));
-      seg_b = (seg_b + 31) & ~(int64_t)31;                   // whole 32-entry super-steps
-      if (seg_b > seg) seg_b = seg;
-    }
-    int64_t acc = cr.offA;
-    for (size_t b = 0; b < count.size(); ++b) {
-      const int64_t cnt = count[b];
-      count[b] = acc;
-      acc += cnt;
-    }
-    order.resize((size_t)(cr.offA + n_short));
-    for (int64_t r = r0; r < r1; ++r) {
-      const int64_t len = rp[r + 1] - rp[r];
-      if (len <= seg) {
-        WorkItem& w = order[(size_t)count[(size_t)(seg - len)]++];
-        w.begin = rp[r];
-        w.len = (int32_t)len;
-        w.id = (int32_t)r;
-      } else {
-        const int64_t nseg = (len + seg_b - 1) / seg_b;
-        int64_t per = (len + nseg - 1) / nseg;
-        per = (per + 3) & ~(int64_t)3;  // whole 4-entry steps
-        RowC rc;
-        rc.first_slot = slot;
-        rc.row = (int32_t)r;
-        rc.nseg = 0;
-        rc.stride = 1;
-        rc.pad_ = 0;
-        // A row long enough to be cut at the gather table's bands (band_plan.h), with ascending columns: its pieces,
-        // slots in entry order like any other row's.  Everything else: cuts by count.
-        pieces.clear();
-        if (bc_next < bc.row.size() && bc.row[bc_next] == r) {
-          if (bc.unsorted[bc_next]) ++n_unsorted;
-          else if (!band_plan_row(&bc.off[bc_next * (size_t)(bc.n_bands + 1)], bc.n_bands, len, seg, pieces)) pieces.clear();
-          ++bc_next;
-        }
-        if (!pieces.empty()) {
-          ++n_banded_rows;
-          n_banded_segs += (int64_t)pieces.size();
-          cr.nnzBand += len;
-          for (const BandPiece& pc : pieces) {
-            if (slot >= std::numeric_limits<int32_t>::max()) return fail(h, MALS_INVALID_ARG, "too many row segments");
-            WorkItem sg;
-            sg.begin = rp[r] + pc.begin;
-            sg.len = pc.len;
-            sg.id = (int32_t)slot++;
-            band_segs.emplace_back(pc.band, sg);
-            ++rc.nseg;
-          }
-        } else {
-          for (int64_t b = 0; b < len; b += per) {
-            if (slot >= std::numeric_limits<int32_t>::max()) return fail(h, MALS_INVALID_ARG, "too many row segments");
-            WorkItem sg;
-            sg.begin = rp[r] + b;
-            sg.len = (int32_t)std::min(per, len - b);
-            sg.id = (int32_t)slot++;
-            segs.push_back(sg);
-            ++rc.nseg;
-          }
-        }
-        if (rc.nseg > FINISH_GROUP) {  // group sums first (als_prereduce_kernel), the finish kernel walks the leaders
-          // (groups of max(8, sqrt(segments)) slots, more rows grouped: finish + group sums 0.29 -> 0.35 ms on C4 -- every
-          // group sum is a slot read and written once more)
-          const int32_t grp_len = FINISH_GROUP;
-          for (int32_t g0 = 0; g0 < rc.nseg; g0 += grp_len) {
-            RowC grp;
-            grp.first_slot = rc.first_slot + g0;
-            grp.row = (int32_t)r;
-            grp.nseg = std::min<int32_t>(grp_len, rc.nseg - g0);
-            grp.stride = 1;
-            grp.pad_ = 0;
-            groups.push_back(grp);
-          }
-          rc.nseg = (rc.nseg + grp_len - 1) / grp_len;
-          rc.stride = grp_len;
-        }
-        rowsC.push_back(rc);
-      }
-    }
-    // Every empty row has the same system (W = G, b = 0: ALS:447-494 with no entries): x = 0, and the
-    // verdict "singular" is shared.  One representative (the smallest row) goes through the kernel, right
-    // behind the direct rows; the others are only zero-filled.
-    const int64_t n_dual = cr.n_dual();
-    if (n_empty > 0 && n_dual > 0) {
-      auto first = order.begin() + (size_t)(cr.offA + n_direct);
-      std::rotate(first, first + (size_t)n_dual, first + (size_t)n_dual + 1);
-    }
-    cr.nA = n_direct + (n_empty > 0 ? 1 : 0);
-    cr.nZ = n_empty > 0 ? n_empty - 1 : 0;
-    s.n_dual_rows += n_dual;
-    cr.nBand = (int64_t)band_segs.size();
-    cr.nB = (int64_t)segs.size() - cr.offB + cr.nBand;
-    cr.nC = (int64_t)rowsC.size() - cr.offC;
-    cr.offP = (int64_t)rowsC.size();  // the chunk's slot groups sit behind its rows in the same array
-    cr.nP = (int64_t)groups.size();
-    rowsC.insert(rowsC.end(), groups.begin(), groups.end());
-    groups.clear();
-    // longest segments first; behind them the banded ones by band, longest first inside a band (both stable in row order)
-    std::stable_sort(segs.begin() + cr.offB, segs.end(), [](const WorkItem& a, const WorkItem& b) { return a.len > b.len; });
-    std::stable_sort(band_segs.begin(), band_segs.end(), [](const std::pair<int32_t, WorkItem>& a, const std::pair<int32_t, WorkItem>& b) {
-      return a.first != b.first ? a.first < b.first : a.second.len > b.second.len;
-    });
-    for (const std::pair<int32_t, WorkItem>& bs : band_segs) segs.push_back(bs.second);
-    band_segs.clear();
-    s.nnzA += cr.nnzA;
-    s.nnzB += cr.nnzB;
-  }
-  s.nA = (int64_t)order.size();
-  s.nB = (int64_t)segs.size();
-  s.nC = (int64_t)rowsC.size();
+  return MALS_OK;
+}
+
+// The planned lists onto the device (and, under MALS_DEBUG_LISTS, what they hold onto stderr).
+int upload_work_lists(mals_handle h, SideState& s, const WorkPlan& plan, const BandCuts& bc) {
+  s.chunks = plan.chunks;
+  s.n_dual_rows = plan.n_dual_rows;
   if (std::getenv("MALS_DEBUG_LISTS")) {  // work decomposition of the upload (tuning aid)
-    int64_t nd[4] = {0, 0, 0, 0}, ed[4] = {0, 0, 0, 0}, na = 0, nz = 0, n_long = 0;   // (s.nC also counts the slot groups)
-    for (const SideState::ChunkRange& cr : s.chunks) {
+    int64_t nd[4] = {0, 0, 0, 0}, ed[4] = {0, 0, 0, 0}, na = 0, nz = 0, n_long = 0;   // (rowsC also holds the slot groups)
+    for (const ChunkRange& cr : s.chunks) {
       n_long += cr.nC;
       for (int c = 0; c < 4; ++c) {
         nd[c] += cr.nD[c];
@@ -661,27 +477,41 @@ int build_work_lists(mals_handle h, SideState& s) {
     }
     std::fprintf(stderr, "[lists] rows %lld: direct %lld (%lld entries), dual 1-16: %lld (%lld) 17-32: %lld (%lld) 33-48: %lld (%lld) 49-64: %lld (%lld), "
                          "zero-filled %lld, segments %lld of %lld long rows (%lld entries)\n",
-                 (long long)n, (long long)na, (long long)s.nnzA, (long long)nd[0], (long long)ed[0], (long long)nd[1], (long long)ed[1], (long long)nd[2],
-                 (long long)ed[2], (long long)nd[3], (long long)ed[3], (long long)nz, (long long)s.nB, (long long)n_long, (long long)s.nnzB);
+                 (long long)s.n_local, (long long)na, (long long)plan.nnzA, (long long)nd[0], (long long)ed[0], (long long)nd[1], (long long)ed[1], (long long)nd[2],
+                 (long long)ed[2], (long long)nd[3], (long long)ed[3], (long long)nz, (long long)plan.itemsB.size(), (long long)n_long, (long long)plan.nnzB);
     int64_t e_band = 0;
-    for (const SideState::ChunkRange& cr : s.chunks) e_band += cr.nnzBand;
+    for (const ChunkRange& cr : s.chunks) e_band += cr.nnzBand;
     std::fprintf(stderr, "[lists] bands %lld of %lld table rows (at least %lld entries per band): %lld banded rows (%lld entries) in %lld segments, "
                          "%lld long enough but unsorted\n",
-                 (long long)bc.n_bands, (long long)bc.band_rows, (long long)bc.min_avg, (long long)n_banded_rows, (long long)e_band,
-                 (long long)n_banded_segs, (long long)n_unsorted);
+                 (long long)bc.n_bands, (long long)bc.band_rows, (long long)bc.min_avg, (long long)plan.n_banded_rows, (long long)e_band,
+                 (long long)plan.n_banded_segs, (long long)plan.n_unsorted);
   }
-  if (s.nA) {
-    HIPCHK(h, s.itemsA.alloc(order.size()));
-    HIPCHK(h, hipMemcpy(s.itemsA.get(), order.data(), sizeof(WorkItem) * order.size(), hipMemcpyHostToDevice));
+  if (!plan.itemsA.empty()) {
+    HIPCHK(h, s.itemsA.alloc(plan.itemsA.size()));
+    HIPCHK(h, hipMemcpy(s.itemsA.get(), plan.itemsA.data(), sizeof(WorkItem) * plan.itemsA.size(), hipMemcpyHostToDevice));
   }
-  if (s.nB) {
-    HIPCHK(h, s.itemsB.alloc(segs.size()));
-    HIPCHK(h, hipMemcpy(s.itemsB.get(), segs.data(), sizeof(WorkItem) * segs.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, s.rowsC.alloc(rowsC.size()));
-    HIPCHK(h, hipMemcpy(s.rowsC.get(), rowsC.data(), sizeof(RowC) * rowsC.size(), hipMemcpyHostToDevice));
-    HIPCHK(h, s.scratch.alloc((size_t)(slot * slot_floats(h->T))));
+  if (!plan.itemsB.empty()) {
+    HIPCHK(h, s.itemsB.alloc(plan.itemsB.size()));
+    HIPCHK(h, hipMemcpy(s.itemsB.get(), plan.itemsB.data(), sizeof(WorkItem) * plan.itemsB.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, s.rowsC.alloc(plan.rowsC.size()));
+    HIPCHK(h, hipMemcpy(s.rowsC.get(), plan.rowsC.data(), sizeof(RowC) * plan.rowsC.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, s.scratch.alloc((size_t)(plan.n_slots * slot_floats(h->T))));
   }
   return MALS_OK;
+}
+
+// mals_set_chunk_rows, or the configuration's (0 = the shard in one chunk)
+int64_t wanted_chunk_rows(mals_handle h, const SideState& s) { return s.chunk_rows_override >= 0 ? s.chunk_rows_override : h->cfg.chunk_rows; }
+
+// Split the rows of a shard into the three work lists (DESIGN.md "work decomposition"), chunk by chunk: work_plan.h.
+int build_work_lists(mals_handle h, SideState& s) {
+  BandCuts bc;
+  WorkPlan plan;
+  s.n_dual_rows = 0;
+  if (int rc = scan_shard(h, s, bc)) return rc;
+  if (const char* why = plan_work_lists(s.h_row_ptr.data(), s.n_local, h->cfg.segment_nnz, wanted_chunk_rows(h, s), h->dual_blocks, h->n_cu, bc, plan))
+    return fail(h, MALS_INVALID_ARG, why);
+  return upload_work_lists(h, s, plan, bc);
 }
 
 int validate_matrix(mals_handle h, int side) {
@@ -740,6 +570,17 @@ int drain_events(mals_handle h) {
 }
 
 // ---- kernel dispatch ---------------------------------------------------------------------------
+// The runtime feature-block count h->T as a compile-time constant: calls f(std::integral_constant<int, T>) for the T in
+// MIN_T .. 8 that it is (the rotations and the dual kernels exist from T = 2 on) and returns what f returns.
+template <int MIN_T = 1, typename F>
+int dispatch_T(mals_handle h, F&& f) {
+  if (h->T == MIN_T) return f(std::integral_constant<int, MIN_T>());
+  if constexpr (MIN_T < 8) return dispatch_T<MIN_T + 1>(h, f);
+  return fail(h, MALS_INVALID_ARG, "unsupported feature count");
+}
+// gather depth D of the fp32 persistent kernels (rows whose gathers are in flight at once) per T
+constexpr int gather_depth(int T) { return T <= 3 ? 4 : T == 4 ? MALS_D4 : 2; }
+
 // fp64 kernel below this many rows, split-f16 kernel (slabs of 512 rows = 32 accumulation steps, fp64 sum over the
 // slabs) from there on: even when a few rows dominate G (no averaging over slabs) the fp32 slab sums stay within
 // 6e-8 x sqrt(32) of it (als_kernels.h, gramian_split_kernel)
@@ -806,17 +647,7 @@ int launch_gramian_T(mals_handle h, SideState& s, const float* M, int64_t n_rows
 }
 
 int launch_gramian(mals_handle h, SideState& s, const float* M, int64_t n_rows, double* G_out, float* Gf_out, unsigned* ymax = nullptr) {
-  switch (h->T) {
-    case 1: return launch_gramian_T<1>(h, s, M, n_rows, G_out, Gf_out, ymax);
-    case 2: return launch_gramian_T<2>(h, s, M, n_rows, G_out, Gf_out, ymax);
-    case 3: return launch_gramian_T<3>(h, s, M, n_rows, G_out, Gf_out, ymax);
-    case 4: return launch_gramian_T<4>(h, s, M, n_rows, G_out, Gf_out, ymax);
-    case 5: return launch_gramian_T<5>(h, s, M, n_rows, G_out, Gf_out, ymax);
-    case 6: return launch_gramian_T<6>(h, s, M, n_rows, G_out, Gf_out, ymax);
-    case 7: return launch_gramian_T<7>(h, s, M, n_rows, G_out, Gf_out, ymax);
-    case 8: return launch_gramian_T<8>(h, s, M, n_rows, G_out, Gf_out, ymax);
-  }
-  return fail(h, MALS_INVALID_ARG, "unsupported feature count");
+  return dispatch_T(h, [&](auto t) { return launch_gramian_T<t()>(h, s, M, n_rows, G_out, Gf_out, ymax); });
 }
 
 // Grid of the persistent kernels.  Work item i goes to wave i mod W of a length-sorted list, so every
@@ -825,37 +656,57 @@ int launch_gramian(mals_handle h, SideState& s, const float* M, int64_t n_rows, 
 // grids lose ~10% to waves that run slower than their peers (nothing rebalances a static
 // assignment), 12-16x oversubscription lets the dispatcher level that out and each wave still
 // walks >100 rows, which keeps the cross-row prefetch effective; beyond 16x nothing changes.
+// block: threads per workgroup, one work item per wave.  resident_per_cu: the workgroups a CU holds where the caller
+// knows (the LDS-staged kernels), 0 = ask the occupancy query.
 template <typename K>
-int persistent_grid(mals_handle h, K kernel, int64_t n_work, unsigned* grid, bool front = false) {
+int persistent_grid(mals_handle h, K kernel, int64_t n_work, unsigned* grid, bool front = false, int block = 256, int resident_per_cu = 0) {
+  const int64_t groups = (n_work + block / 64 - 1) / (block / 64);
   if (front) {  // banded segments: one item per wave, workgroups dispatched in list order -- the resident waves then work
                 // on one contiguous stretch of the list, i.e. on one or two bands of the table, where the strided
                 // assignment has as many bands in flight as the list is longer than the grid
-    *grid = (unsigned)std::max<int64_t>(1, (n_work + 3) / 4);
+    *grid = (unsigned)std::max<int64_t>(1, groups);
     return MALS_OK;
   }
-  int per_cu = 0;
-  HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0));
+  int per_cu = resident_per_cu;
+  if (!per_cu) HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0));
   if (per_cu < 1) per_cu = 1;
   per_cu *= 16;
-  if (const char* e = std::getenv("MALS_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(e));  // tuning override
+  if (const char* e = std::getenv("MALS_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(e)) * (256 / block);  // tuning override (in 256-thread blocks)
   const int64_t cap = (int64_t)h->n_cu * per_cu;
-  *grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_work + 3) / 4, cap));
+  *grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(groups, cap));
   return MALS_OK;
 }
 
 // what one launch_solve call covers: the rows list (+ zero-fill) / the dual lists through the direct kernel / the long
 // rows (segments + finish).  The three are independent of each other (disjoint output rows, read-only inputs).
-enum { LISTS_ROWS = 1, LISTS_DUAL_ROWS = 2, LISTS_LONG = 4, LISTS_OWN = LISTS_ROWS | LISTS_LONG };
+enum { LISTS_ROWS = 1, LISTS_DUAL_ROWS = 2, LISTS_LONG = 4 };
 
-// One persistent launch, plus -- for a split-precision kernel -- its fp32-gather twin right behind it with
-// flag bit 3: exactly one of the two does the work (gather_scale_kernel's range flag), the other returns at once.
+// The kernels that run a chunk's lists, and how they are launched: what differs between the families launch_solve_TF
+// chooses from.  An fp32 twin (std::nullptr_t: none) follows its split-precision kernel with flag bit 3: exactly one of
+// the two does the work (gather_scale_kernel's range flag), the other returns at once.
+template <typename KR, typename KS, typename KRF, typename KSF, typename KC, typename KCF, typename KP>
+struct ListKernels {
+  KR rows;         // list A
+  KS segments;     // list B
+  KRF rows_f32;    // their fp32-gather twins
+  KSF segments_f32;
+  KC finish;       // list C
+  KCF finish_f32;  // the finish kernel of the twins' partial slots where those differ in layout (flag bit 3 again)
+  KP prereduce;
+  int block;            // threads per workgroup of rows / segments
+  int resident_per_cu;  // persistent_grid
+};
+template <typename KR, typename KS, typename KRF, typename KSF, typename KC, typename KCF, typename KP>
+ListKernels(KR, KS, KRF, KSF, KC, KCF, KP, int, int) -> ListKernels<KR, KS, KRF, KSF, KC, KCF, KP>;
+
+// One persistent launch, plus -- for a split-precision kernel -- its fp32-gather twin right behind it.
 template <typename K, typename KF>
-int launch_persistent(mals_handle h, K kernel, KF fallback, const SolveParams& p, int kind, double bytes, bool front = false) {
+int launch_persistent(mals_handle h, K kernel, KF fallback, int block, int resident_per_cu, const SolveParams& p, int kind, double bytes, bool front) {
   PendingEvent pe;
   unsigned grid = 1;
-  if (int rc = persistent_grid(h, kernel, p.n_work, &grid, front)) return rc;
+  if (int rc = persistent_grid(h, kernel, p.n_work, &grid, front, block, resident_per_cu)) return rc;
   if (int rc = begin_timed(h, kind, bytes, pe)) return rc;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, h->stream, p);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, h->stream, p);
   if constexpr (!std::is_same<KF, std::nullptr_t>::value) {
     SolveParams pf = p;
     pf.flags |= 8;
@@ -868,212 +719,117 @@ int launch_persistent(mals_handle h, K kernel, KF fallback, const SolveParams& p
   return end_timed(h, pe);
 }
 
-template <typename KA, typename KB, typename KFA, typename KFB, typename KC, typename KP>
-int launch_lists(mals_handle h, SideState& s, SolveParams p, int chunk, int which, KA rows_kernel, KB segments_kernel, KFA rows_fallback,
-                 KFB segments_fallback, KC finish_kernel, KP prereduce_kernel) {
+template <typename LK>
+int launch_lists(mals_handle h, SideState& s, SolveParams p, int chunk, int which, const LK& fam) {
   const double per = 4.0 * p.k + 8.0;  // gathered row + col idx + value; written row + row_ptr
-  const SideState::ChunkRange& cr = s.chunks[(size_t)chunk];
-  PendingEvent pe;
+  const ChunkRange& cr = s.chunks[(size_t)chunk];
   const bool own = which & LISTS_ROWS, longs = which & LISTS_LONG, dual_rows_too = which & LISTS_DUAL_ROWS;
-  if (longs && cr.nB > cr.nBand) {
-    p.n_work = cr.nB - cr.nBand;
-    p.items = s.itemsB.get() + cr.offB;
-    if (int rc = launch_persistent(h, segments_kernel, segments_fallback, p, 1, (double)(cr.nnzB - cr.nnzBand) * per)) return rc;
-  }
-  if (longs && cr.nBand) {  // the banded tail of list B, band by band
-    p.n_work = cr.nBand;
-    p.items = s.itemsB.get() + cr.offB + (cr.nB - cr.nBand);
-    if (int rc = launch_persistent(h, segments_kernel, segments_fallback, p, 1, (double)cr.nnzBand * per, s.band_front)) return rc;
-  }
-  if (own && cr.nA) {
-    p.n_work = cr.nA;
-    p.items = s.itemsA.get() + cr.offA;
-    if (int rc = launch_persistent(h, rows_kernel, rows_fallback, p, 0, (double)cr.nnzA * per + (double)cr.nA * per)) return rc;
-  }
-  if (dual_rows_too && cr.n_dual()) {  // the dual lists through the direct kernel (the half-iteration does not qualify)
-    p.n_work = cr.n_dual();
-    p.items = s.itemsA.get() + cr.offA + cr.nA;
-    if (int rc = launch_persistent(h, rows_kernel, rows_fallback, p, 0, (double)cr.nnz_dual() * per + (double)cr.n_dual() * per)) return rc;
+  const WorkItem *A = s.itemsA.get() + cr.offA, *B = s.itemsB.get() + cr.offB;
+  const int64_t n_plain = cr.nB - cr.nBand, n_dual = cr.n_dual();
+  struct Run {
+    const WorkItem* items;
+    int64_t n;
+    double bytes;
+    int kind;    // 0 = rows (list A), 1 = segments (list B): kernel and timing kind
+    bool front;
+  };
+  const Run runs[4] = {
+      {B, longs ? n_plain : 0, (double)(cr.nnzB - cr.nnzBand) * per, 1, false},
+      {B + n_plain, longs ? cr.nBand : 0, (double)cr.nnzBand * per, 1, s.band_front},  // the banded tail of list B, band by band
+      {A, own ? cr.nA : 0, (double)cr.nnzA * per + (double)cr.nA * per, 0, false},
+      // the dual lists through the direct kernel (the half-iteration does not qualify)
+      {A + cr.nA, dual_rows_too ? n_dual : 0, (double)cr.nnz_dual() * per + (double)n_dual * per, 0, false}};
+  for (const Run& r : runs) {
+    if (!r.n) continue;
+    p.n_work = r.n;
+    p.items = r.items;
+    if (int rc = r.kind ? launch_persistent(h, fam.segments, fam.segments_f32, fam.block, fam.resident_per_cu, p, 1, r.bytes, r.front)
+                        : launch_persistent(h, fam.rows, fam.rows_f32, fam.block, fam.resident_per_cu, p, 0, r.bytes, r.front))
+      return rc;
   }
   if (longs && cr.nC) {
+    PendingEvent pe;
     if (int rc = begin_timed(h, 2, (double)cr.nC * per, pe)) return rc;
     if (cr.nP) {
       p.n_work = cr.nP;
       p.rowsC = s.rowsC.get() + cr.offP;
-      hipLaunchKernelGGL(prereduce_kernel, dim3((unsigned)((cr.nP + 3) / 4)), dim3(256), 0, h->stream, p);
+      hipLaunchKernelGGL(fam.prereduce, dim3((unsigned)((cr.nP + 3) / 4)), dim3(256), 0, h->stream, p);
     }
     p.n_work = cr.nC;
     p.rowsC = s.rowsC.get() + cr.offC;
-    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((cr.nC + 3) / 4)), dim3(256), 0, h->stream, p);
+    hipLaunchKernelGGL(fam.finish, dim3((unsigned)((cr.nC + 3) / 4)), dim3(256), 0, h->stream, p);
+    if constexpr (!std::is_same<decltype(fam.finish_f32), std::nullptr_t>::value) {
+      SolveParams pf = p;
+      pf.flags |= 8;
+      hipLaunchKernelGGL(fam.finish_f32, dim3((unsigned)((cr.nC + 3) / 4)), dim3(256), 0, h->stream, pf);
+    }
     if (int rc = end_timed(h, pe)) return rc;
   }
   if (own && cr.nZ) {
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((cr.nZ + 31) / 32)), dim3(256), 0, h->stream,  // 8 rows per wave
-                       s.itemsA.get() + cr.offA + cr.nA + cr.n_dual(), cr.nZ, p.k, p.out);
+                       A + cr.nA + n_dual, cr.nZ, p.k, p.out);
   }
   HIPCHK(h, hipGetLastError());
   return MALS_OK;
 }
 
-// the persistent launch of an LDS-staged kernel (lds_kernels.h): one wave per workgroup, LDS-limited to 8 per CU, the same
-// 16x oversubscription as persistent_grid
-template <typename K, typename KF>
-int launch_persistent_lds(mals_handle h, K kernel, KF fallback, const SolveParams& p, int kind, double bytes, bool front = false) {
-  PendingEvent pe;
-  int per_cu = 8 * 16;
-  if (const char* e = std::getenv("MALS_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(e)) * 4;  // tuning override (in 256-thread blocks)
-  unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(p.n_work, (int64_t)h->n_cu * per_cu));
-  if (front) grid = (unsigned)std::max<int64_t>(1, p.n_work);  // one item per wave, in list order (persistent_grid)
-  if (int rc = begin_timed(h, kind, bytes, pe)) return rc;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, h->stream, p);
-  SolveParams pf = p;
-  pf.flags |= 8;
-  if (int rc = persistent_grid(h, fallback, p.n_work, &grid)) return rc;
-  grid = std::min<unsigned>(grid, (unsigned)h->n_cu * 8u);   // (as launch_persistent: the twin almost always returns at once)
-  hipLaunchKernelGGL(fallback, dim3(grid), dim3(256), 0, h->stream, pf);
-  return end_timed(h, pe);
-}
-
-// launch_lists for k = 128 through the LDS-staged kernels.  Their partial slots are in the kernels' own feature order, the
-// fp32 twins' (range flag 0) in the plain one: both finish kernels are enqueued and the range flag decides on the device
-// which of the two runs (bit 3 again: "only if the split-precision launch did not run").
-int launch_lists_lds(mals_handle h, SideState& s, SolveParams p, int chunk, int which) {
-  constexpr int T = 8, D = 2;
-  const double per = 4.0 * p.k + 8.0;
-  const SideState::ChunkRange& cr = s.chunks[(size_t)chunk];
-  PendingEvent pe;
-  const bool own = which & LISTS_ROWS, longs = which & LISTS_LONG, dual_rows_too = which & LISTS_DUAL_ROWS;
-  if (longs && cr.nB > cr.nBand) {
-    p.n_work = cr.nB - cr.nBand;
-    p.items = s.itemsB.get() + cr.offB;
-    if (int rc = launch_persistent_lds(h, als_lds_kernel_h<1>, als_persistent_kernel<T, D, 1, true>, p, 1, (double)(cr.nnzB - cr.nnzBand) * per)) return rc;
-  }
-  if (longs && cr.nBand) {  // the banded tail of list B, band by band
-    p.n_work = cr.nBand;
-    p.items = s.itemsB.get() + cr.offB + (cr.nB - cr.nBand);
-    if (int rc = launch_persistent_lds(h, als_lds_kernel_h<1>, als_persistent_kernel<T, D, 1, true>, p, 1, (double)cr.nnzBand * per, s.band_front)) return rc;
-  }
-  if (own && cr.nA) {
-    p.n_work = cr.nA;
-    p.items = s.itemsA.get() + cr.offA;
-    if (int rc = launch_persistent_lds(h, als_lds_kernel_h<0>, als_persistent_kernel<T, D, 0, true>, p, 0, (double)cr.nnzA * per + (double)cr.nA * per)) return rc;
-  }
-  if (dual_rows_too && cr.n_dual()) {
-    p.n_work = cr.n_dual();
-    p.items = s.itemsA.get() + cr.offA + cr.nA;
-    if (int rc = launch_persistent_lds(h, als_lds_kernel_h<0>, als_persistent_kernel<T, D, 0, true>, p, 0,
-                                       (double)cr.nnz_dual() * per + (double)cr.n_dual() * per)) return rc;
-  }
-  if (longs && cr.nC) {
-    if (int rc = begin_timed(h, 2, (double)cr.nC * per, pe)) return rc;
-    if (cr.nP) {
-      p.n_work = cr.nP;
-      p.rowsC = s.rowsC.get() + cr.offP;
-      hipLaunchKernelGGL(als_prereduce_kernel<T>, dim3((unsigned)((cr.nP + 3) / 4)), dim3(256), 0, h->stream, p);
-    }
-    p.n_work = cr.nC;
-    p.rowsC = s.rowsC.get() + cr.offC;
-    hipLaunchKernelGGL((als_finish_kernel<T, true>), dim3((unsigned)((cr.nC + 3) / 4)), dim3(256), 0, h->stream, p);
-    SolveParams pf = p;
-    pf.flags |= 8;
-    hipLaunchKernelGGL((als_finish_kernel<T, false>), dim3((unsigned)((cr.nC + 3) / 4)), dim3(256), 0, h->stream, pf);
-    if (int rc = end_timed(h, pe)) return rc;
-  }
-  if (own && cr.nZ) {
-    hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((cr.nZ + 31) / 32)), dim3(256), 0, h->stream,
-                       s.itemsA.get() + cr.offA + cr.nA + cr.n_dual(), cr.nZ, p.k, p.out);
-  }
-  HIPCHK(h, hipGetLastError());
-  return MALS_OK;
-}
-
-template <int T, int D, bool FULL>
+template <int T, bool FULL>
 int launch_solve_TF(mals_handle h, SideState& s, const SolveParams& p, int chunk, int which) {
+  constexpr int D = gather_depth(T);
+  constexpr auto rows_f32 = als_persistent_kernel<T, D, 0, FULL>;
+  constexpr auto segments_f32 = als_persistent_kernel<T, D, 1, FULL>;
   if constexpr (T == 8 && FULL) {
-    if (h->split_f16 && h->lds_gather && p.Gperm) return launch_lists_lds(h, s, p, chunk, which);
+    // k = 128 through the LDS-staged kernels (lds_kernels.h): one wave per workgroup, LDS-limited to 8 per CU.  Their
+    // partial slots are in the kernels' own feature order, the fp32 twins' (range flag 0) in the plain one: both finish
+    // kernels are enqueued and the range flag decides on the device which of the two runs (bit 3 again: "only if the
+    // split-precision launch did not run").
+    if (h->split_f16 && h->lds_gather && p.Gperm)
+      return launch_lists(h, s, p, chunk, which, ListKernels{als_lds_kernel_h<0>, als_lds_kernel_h<1>, rows_f32, segments_f32, als_finish_kernel<T, true>,
+                                                             als_finish_kernel<T, false>, als_prereduce_kernel<T>, 64, 8});
   }
   if constexpr (T == 4) {
     if (h->split3)
-      return launch_lists(h, s, p, chunk, which, als_persistent_kernel_h<T, 0, FULL, 3>, als_persistent_kernel_h<T, 1, FULL, 3>,
-                          als_persistent_kernel<T, D, 0, FULL>, als_persistent_kernel<T, D, 1, FULL>, als_finish_kernel<T>,
-                          als_prereduce_kernel<T>);
+      return launch_lists(h, s, p, chunk, which, ListKernels{als_persistent_kernel_h<T, 0, FULL, 3>, als_persistent_kernel_h<T, 1, FULL, 3>, rows_f32,
+                                                             segments_f32, als_finish_kernel<T>, nullptr, als_prereduce_kernel<T>, 256, 0});
   }
   if (h->split_f16)
-    return launch_lists(h, s, p, chunk, which, als_persistent_kernel_h<T, 0, FULL>, als_persistent_kernel_h<T, 1, FULL>,
-                        als_persistent_kernel<T, D, 0, FULL>, als_persistent_kernel<T, D, 1, FULL>, als_finish_kernel<T>,
-                        als_prereduce_kernel<T>);
-  return launch_lists(h, s, p, chunk, which, als_persistent_kernel<T, D, 0, FULL>, als_persistent_kernel<T, D, 1, FULL>,
-                      nullptr, nullptr, als_finish_kernel<T>, als_prereduce_kernel<T>);
-}
-
-template <int T, int D>
-int launch_solve_T(mals_handle h, SideState& s, const SolveParams& p, int chunk, int which) {
-  return p.k == 16 * T ? launch_solve_TF<T, D, true>(h, s, p, chunk, which) : launch_solve_TF<T, D, false>(h, s, p, chunk, which);
+    return launch_lists(h, s, p, chunk, which, ListKernels{als_persistent_kernel_h<T, 0, FULL>, als_persistent_kernel_h<T, 1, FULL>, rows_f32,
+                                                           segments_f32, als_finish_kernel<T>, nullptr, als_prereduce_kernel<T>, 256, 0});
+  return launch_lists(h, s, p, chunk, which,
+                      ListKernels{rows_f32, segments_f32, nullptr, nullptr, als_finish_kernel<T>, nullptr, als_prereduce_kernel<T>, 256, 0});
 }
 
 // the direct kernels over a chunk's lists (LISTS_*)
 int launch_solve(mals_handle h, SideState& s, const SolveParams& p, int chunk, int which) {
-  switch (h->T) {
-    case 1: return launch_solve_T<1, 4>(h, s, p, chunk, which);
-    case 2: return launch_solve_T<2, 4>(h, s, p, chunk, which);
-    case 3: return launch_solve_T<3, 4>(h, s, p, chunk, which);
-    case 4: return launch_solve_T<4, MALS_D4>(h, s, p, chunk, which);
-    case 5: return launch_solve_T<5, 2>(h, s, p, chunk, which);
-    case 6: return launch_solve_T<6, 2>(h, s, p, chunk, which);
-    case 7: return launch_solve_T<7, 2>(h, s, p, chunk, which);
-    case 8: return launch_solve_T<8, 2>(h, s, p, chunk, which);
-  }
-  return fail(h, MALS_INVALID_ARG, "unsupported feature count");
+  return dispatch_T(h, [&](auto t) {
+    return p.k == 16 * t() ? launch_solve_TF<t(), true>(h, s, p, chunk, which) : launch_solve_TF<t(), false>(h, s, p, chunk, which);
+  });
 }
 
 // ---- refinement of the rows the solving kernels marked (als_refine_kernel) -------------------------
-template <int T>
-int launch_refine_T(mals_handle h, const RefineParams& q) {
+int launch_refine(mals_handle h, const RefineParams& q) {
   // reads the marks on the device: no host round trip.  A resident-sized grid; a chunk without marked rows costs
   // one pass over its flag bytes.
   const int64_t rows = q.row_end - q.row_begin;
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, (int64_t)h->n_cu * 8));
-  hipLaunchKernelGGL((als_refine_kernel<T>), dim3(grid), dim3(256), 0, h->stream, q);
-  HIPCHK(h, hipGetLastError());
-  return MALS_OK;
-}
-int launch_refine(mals_handle h, const RefineParams& q) {
-  switch (h->T) {
-    case 1: return launch_refine_T<1>(h, q);
-    case 2: return launch_refine_T<2>(h, q);
-    case 3: return launch_refine_T<3>(h, q);
-    case 4: return launch_refine_T<4>(h, q);
-    case 5: return launch_refine_T<5>(h, q);
-    case 6: return launch_refine_T<6>(h, q);
-    case 7: return launch_refine_T<7>(h, q);
-    case 8: return launch_refine_T<8>(h, q);
-  }
-  return fail(h, MALS_INVALID_ARG, "unsupported feature count");
+  return dispatch_T(h, [&](auto t) -> int {
+    hipLaunchKernelGGL((als_refine_kernel<t()>), dim3(grid), dim3(256), 0, h->stream, q);
+    HIPCHK(h, hipGetLastError());
+    return MALS_OK;
+  });
 }
 
 // The reference's M^T M (MU:219-239 rounds every product to fp32) for the refinement of marked rows; the kernel
 // returns at once unless a row has been marked in this half-iteration and the matrix is not there yet.
-template <int T>
-int launch_gramian_ref_T(mals_handle h, const SideState& o) {
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((o.n_total + 63) / 64, (int64_t)h->n_cu * 2));
-  hipLaunchKernelGGL(gramian_ref_latch_kernel, dim3(1), dim3(1), 0, h->stream, h->d_gref_state.get());
-  hipLaunchKernelGGL((gramian_ref_kernel<T>), dim3(grid), dim3(256), 0, h->stream, o.F, o.n_total, h->cfg.features, h->d_gref_state.get(),
-                     h->d_gref_part.get(), h->d_Gref.get());
-  HIPCHK(h, hipGetLastError());
-  return MALS_OK;
-}
 int launch_gramian_ref(mals_handle h, const SideState& o) {
-  switch (h->T) {
-    case 1: return launch_gramian_ref_T<1>(h, o);
-    case 2: return launch_gramian_ref_T<2>(h, o);
-    case 3: return launch_gramian_ref_T<3>(h, o);
-    case 4: return launch_gramian_ref_T<4>(h, o);
-    case 5: return launch_gramian_ref_T<5>(h, o);
-    case 6: return launch_gramian_ref_T<6>(h, o);
-    case 7: return launch_gramian_ref_T<7>(h, o);
-    case 8: return launch_gramian_ref_T<8>(h, o);
-  }
-  return fail(h, MALS_INVALID_ARG, "unsupported feature count");
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((o.n_total + 63) / 64, (int64_t)h->n_cu * 2));
+  return dispatch_T(h, [&](auto t) -> int {
+    hipLaunchKernelGGL(gramian_ref_latch_kernel, dim3(1), dim3(1), 0, h->stream, h->d_gref_state.get());
+    hipLaunchKernelGGL((gramian_ref_kernel<t()>), dim3(grid), dim3(256), 0, h->stream, o.F, o.n_total, h->cfg.features, h->d_gref_state.get(),
+                       h->d_gref_part.get(), h->d_Gref.get());
+    HIPCHK(h, hipGetLastError());
+    return MALS_OK;
+  });
 }
 
 int launch_exact(mals_handle h, const RefineParams& q, int level) {
@@ -1091,49 +847,47 @@ int launch_exact(mals_handle h, const RefineParams& q, int level) {
 }
 
 // ---- dual path (dual_kernels.h) ------------------------------------------------------------------
-template <int T, bool LISTED, bool F64>
-int launch_rotate_T(mals_handle h, const RotateParams& rp) {
-  const int64_t tiles = (rp.n_rows + (F64 ? 31 : 63)) / (F64 ? 32 : 64);
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, (int64_t)h->n_cu * 16));
-  hipLaunchKernelGGL((rotate_rows_kernel<T, LISTED, F64>), dim3(grid), dim3(256), 0, h->stream, rp);
-  HIPCHK(h, hipGetLastError());
-  return MALS_OK;
-}
 template <bool LISTED, bool F64>
 int launch_rotate(mals_handle h, const RotateParams& rp) {
-  switch (h->T) {
-    case 2: return launch_rotate_T<2, LISTED, F64>(h, rp);
-    case 3: return launch_rotate_T<3, LISTED, F64>(h, rp);
-    case 4: return launch_rotate_T<4, LISTED, F64>(h, rp);
-    case 5: return launch_rotate_T<5, LISTED, F64>(h, rp);
-    case 6: return launch_rotate_T<6, LISTED, F64>(h, rp);
-    case 7: return launch_rotate_T<7, LISTED, F64>(h, rp);
-    case 8: return launch_rotate_T<8, LISTED, F64>(h, rp);
-  }
-  return fail(h, MALS_INVALID_ARG, "unsupported feature count");
+  const int64_t tiles = (rp.n_rows + (F64 ? 31 : 63)) / (F64 ? 32 : 64);
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, (int64_t)h->n_cu * 16));
+  return dispatch_T<2>(h, [&](auto t) -> int {
+    hipLaunchKernelGGL((rotate_rows_kernel<t(), LISTED, F64>), dim3(grid), dim3(256), 0, h->stream, rp);
+    HIPCHK(h, hipGetLastError());
+    return MALS_OK;
+  });
 }
 
-template <int T, bool LISTED>
-int launch_rotate_split_T(mals_handle h, const RotateSplitParams& rp) {
-  const int rows_per_wave = 16 * rotate_split_tiles(T);
-  const int64_t tiles = (rp.n_rows + rows_per_wave - 1) / rows_per_wave;
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, (int64_t)h->n_cu * 16));
-  hipLaunchKernelGGL((rotate_rows_split_kernel<T, LISTED>), dim3(grid), dim3(256), 0, h->stream, rp);
-  HIPCHK(h, hipGetLastError());
-  return MALS_OK;
-}
 template <bool LISTED>
 int launch_rotate_split(mals_handle h, const RotateSplitParams& rp) {
-  switch (h->T) {
-    case 2: return launch_rotate_split_T<2, LISTED>(h, rp);
-    case 3: return launch_rotate_split_T<3, LISTED>(h, rp);
-    case 4: return launch_rotate_split_T<4, LISTED>(h, rp);
-    case 5: return launch_rotate_split_T<5, LISTED>(h, rp);
-    case 6: return launch_rotate_split_T<6, LISTED>(h, rp);
-    case 7: return launch_rotate_split_T<7, LISTED>(h, rp);
-    case 8: return launch_rotate_split_T<8, LISTED>(h, rp);
-  }
-  return fail(h, MALS_INVALID_ARG, "unsupported feature count");
+  return dispatch_T<2>(h, [&](auto t) -> int {
+    const int rows_per_wave = 16 * rotate_split_tiles(t());
+    const int64_t tiles = (rp.n_rows + rows_per_wave - 1) / rows_per_wave;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, (int64_t)h->n_cu * 16));
+    hipLaunchKernelGGL((rotate_rows_split_kernel<t(), LISTED>), dim3(grid), dim3(256), 0, h->stream, rp);
+    HIPCHK(h, hipGetLastError());
+    return MALS_OK;
+  });
+}
+
+// the same rotation on the f16 matrix pipe: Bs = Q (or Q^T) as split operands (split_rotation_operand) in place of B / Bf, and
+// a bound on |src|, on the device (bound_bits) or known to the host
+RotateSplitParams rotate_split_params(const RotateParams& rp, const int32_t* Bs, const unsigned* bound_bits, float bound_host) {
+  RotateSplitParams sp;
+  sp.src = rp.src;
+  sp.dst = rp.dst;
+  sp.Bs = reinterpret_cast<const i32x4*>(Bs);
+  sp.items = rp.items;
+  sp.dmax = rp.dmax;
+  sp.zbound = rp.zbound;
+  sp.bound_bits = bound_bits;
+  sp.bound_host = bound_host;
+  sp.n_rows = rp.n_rows;
+  sp.k = rp.k;
+  sp.src_stride = rp.src_stride;
+  sp.dst_stride = rp.dst_stride;
+  sp.dst_cols = rp.dst_cols;
+  return sp;
 }
 
 // fp32 -> f16 bit pattern, round to nearest even (the compiler's conversion) / toward zero
@@ -1198,16 +952,7 @@ int launch_dual_T(mals_handle h, const DualParams& dp, int tn) {
   return fail(h, MALS_INVALID_ARG, "no dual kernel for this row class");
 }
 int launch_dual(mals_handle h, const DualParams& dp, int tn) {
-  switch (h->T) {
-    case 2: return launch_dual_T<2>(h, dp, tn);
-    case 3: return launch_dual_T<3>(h, dp, tn);
-    case 4: return launch_dual_T<4>(h, dp, tn);
-    case 5: return launch_dual_T<5>(h, dp, tn);
-    case 6: return launch_dual_T<6>(h, dp, tn);
-    case 7: return launch_dual_T<7>(h, dp, tn);
-    case 8: return launch_dual_T<8>(h, dp, tn);
-  }
-  return fail(h, MALS_INVALID_ARG, "unsupported feature count");
+  return dispatch_T<2>(h, [&](auto t) { return launch_dual_T<t()>(h, dp, tn); });
 }
 
 // Once per half-iteration, in two halves.  HOST: G (opposite side, already on its way to h_G) -> eigendecomposition
@@ -1251,8 +996,7 @@ int ensure_eig_stage(mals_handle h) {
 int prepare_dual_host(mals_handle h, int side, mals_handle from) {
   SideState& o = h->side[1 - side];
   const int k = h->cfg.features, KP = 16 * h->T;
-  h->dual_side = side;
-  h->dual_version = o.G_version;
+  h->dual = HalfStamp{side, o.G_version};
   h->dual_ok = false;
   h->eig_ok = false;
   if (int rc = ensure_eig_stage(h)) return rc;
@@ -1357,13 +1101,7 @@ int prepare_dual_device(mals_handle h, int side) {
   PendingEvent pe;
   if (int rc = begin_timed(h, 5, (double)o.n_total * (4.0 * k + 4.0 * KP), pe)) return rc;
   if (h->rotate_split && !h->rotate_f64) {
-    RotateSplitParams sp;
-    sp.src = rp.src; sp.dst = rp.dst; sp.items = nullptr; sp.dmax = rp.dmax; sp.zbound = rp.zbound; sp.n_rows = rp.n_rows; sp.k = k;
-    sp.src_stride = rp.src_stride; sp.dst_stride = rp.dst_stride; sp.dst_cols = rp.dst_cols;
-    sp.Bs = reinterpret_cast<const i32x4*>(h->d_Bs);
-    sp.bound_bits = nullptr;
-    sp.bound_host = (float)std::sqrt(h->eig_gmax);
-    if (int rc = launch_rotate_split<false>(h, sp)) return rc;
+    if (int rc = launch_rotate_split<false>(h, rotate_split_params(rp, h->d_Bs, nullptr, (float)std::sqrt(h->eig_gmax)))) return rc;
   } else if (int rc = h->rotate_f64 ? launch_rotate<false, true>(h, rp) : launch_rotate<false, false>(h, rp)) {
     return rc;
   }
@@ -1375,7 +1113,7 @@ int prepare_dual_device(mals_handle h, int side) {
 // the dual lists of one chunk: als_dual_kernel per row class, then x = Q x' in place
 int launch_dual_chunk(mals_handle h, int side, int chunk) {
   SideState& s = h->side[side];
-  const SideState::ChunkRange& cr = s.chunks[(size_t)chunk];
+  const ChunkRange& cr = s.chunks[(size_t)chunk];
   const int k = h->cfg.features, KP = 16 * h->T;
   const double per = 4.0 * k + 8.0;
   DualParams dp;
@@ -1424,13 +1162,7 @@ int launch_dual_chunk(mals_handle h, int side, int chunk) {
   rp.dst_cols = k;
   if (int rc = begin_timed(h, 5, (double)cr.n_dual() * 8.0 * k, pe)) return rc;
   if (h->rotate_split) {
-    RotateSplitParams sp;
-    sp.src = rp.src; sp.dst = rp.dst; sp.items = rp.items; sp.dmax = nullptr; sp.zbound = nullptr; sp.n_rows = rp.n_rows; sp.k = k;
-    sp.src_stride = k; sp.dst_stride = k; sp.dst_cols = k;
-    sp.Bs = reinterpret_cast<const i32x4*>(h->d_Bs + h->Bs_stride);
-    sp.bound_bits = dp.xbound;
-    sp.bound_host = 0.f;
-    if (int rc = launch_rotate_split<true>(h, sp)) return rc;
+    if (int rc = launch_rotate_split<true>(h, rotate_split_params(rp, h->d_Bs + h->Bs_stride, dp.xbound, 0.f))) return rc;
   } else if (int rc = launch_rotate<true, false>(h, rp)) {
     return rc;
   }
@@ -1457,17 +1189,6 @@ void dwm_increment(double& total_weight, double& mean, double datum, double weig
 }
 
 }  // namespace
-
-namespace {
-template <int T>
-int launch_reconstruction(mals_handle h, SideState& s, SideState& o, unsigned grid, double* d_sum, unsigned long long* d_cnt) {
-  hipLaunchKernelGGL((reconstruction_kernel<T>), dim3(grid), dim3(256), 0, h->stream, s.row_ptr, s.col,
-                     s.F + s.row_offset * h->cfg.features, o.F, h->cfg.features, s.n_local, d_sum, d_cnt);
-  HIPCHK(h, hipGetLastError());
-  return MALS_OK;
-}
-}  // namespace
-
 
 // ---- rescorers (mals_rescorer_*, include/myrrix_als.h; the kernels' side in topn_kernels.h, RESCORED MODE) ---------------
 // What a pass reads is an immutable snapshot: mals_rescorer_set_* builds a new one (an exclusive ticket of the serving front,
@@ -2051,9 +1772,12 @@ static int join_streams(mals_handle h) {
 // once per group), END enqueues the rest.  BEGIN + host + END = ALL.
 enum { SOLVE_ALL = 0, SOLVE_BEGIN = 1, SOLVE_END = 2 };
 
-static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end, int phase = SOLVE_ALL) {
-  SideState& s = h->side[side];
-  SideState& o = h->side[1 - side];
+// ---- solve_chunks in steps: argument checks, the once-per-half-iteration setup, the parameter block, one chunk, the
+// chunk's refinement block; the driver behind them
+
+static int solve_check_args(mals_handle h, int side, int chunk_begin, int chunk_end) {
+  const SideState& s = h->side[side];
+  const SideState& o = h->side[1 - side];
   if (!s.has_matrix) return fail(h, MALS_INVALID_ARG, "matrix of this side not set");
   if (!s.F || !o.F) return fail(h, MALS_INVALID_ARG, "factor replicas not allocated");
   if (s.row_offset + s.n_local > s.n_total) return fail(h, MALS_INVALID_ARG, "matrix rows exceed the factor replica");
@@ -2063,16 +1787,98 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
   if (use_g && !o.G_valid) return fail(h, MALS_INVALID_ARG, "Gramian of the opposite side not computed");
   if (chunk_begin < 0 || chunk_end > (int)s.chunks.size() || chunk_begin >= chunk_end)
     return fail(h, MALS_INVALID_ARG, "chunk index out of range");
-  const bool resume = phase == SOLVE_END;
-  if (resume) {
-    if (!h->dual_pending) return MALS_OK;  // BEGIN did the whole chunk
-    if (h->dual_pending_side != side || h->dual_pending_chunk != chunk_begin || chunk_end != chunk_begin + 1)
-      return fail(h, MALS_INVALID_ARG, "solve END does not match the pending BEGIN");
-  } else {
-    h->dual_pending = false;  // a BEGIN whose END never came belongs to a half-iteration that was abandoned on an error
+  return MALS_OK;
+}
+
+// dual path (dual_kernels.h): the reference's default mode only
+// ... and only when it pays: the rotation of the gathered matrix costs ~1/30 of what a dual row saves
+// (measured, k = 64 and 128), so a side with few short rows against a huge opposite matrix (the item half of
+// C5: 1.25M long rows per rank gathering from 100M users) stays on the direct kernels
+static bool dual_wanted(mals_handle h, const SideState& s, const SideState& o) {
+  const bool dual_pays = h->cfg.solve_mode == MALS_SOLVE_DUAL || s.n_dual_rows * 32 >= o.n_total;
+  return s.n_dual_rows > 0 && dual_pays && h->cfg.flags == 0 && h->cfg.alpha > 0.0 && o.G_valid;
+}
+
+// What a half-iteration sets up once, enqueued by the first call that solves one of its chunks: the padded gather table,
+// the permuted Gramian image, the refinement marks' block, the operand scale and -- g_to_host -- the copy of G that the
+// dual path's eigendecomposition reads.  Marks the call's chunks as solved from this setup.
+static int solve_setup(mals_handle h, int side, int chunk_begin, int chunk_end, bool g_to_host) {
+  SideState& s = h->side[side];
+  SideState& o = h->side[1 - side];
+  const int k = h->cfg.features;
+  // A new half-iteration?  The opposite factors do not change while a half-iteration's chunks are solved (in any
+  // order): "new" = the side, the opposite Gramian or the opposite uploads changed, or a chunk comes round again.
+  const HalfStamp now{side, o.G_version};
+  bool new_half = h->pad != now || h->pad_epoch != o.F_epoch || h->pad_done.size() != s.chunks.size();
+  for (int c = chunk_begin; c < chunk_end && !new_half; ++c) new_half = h->pad_done[(size_t)c] != 0;
+  if (new_half) {
+    h->pad = now;
+    h->pad_epoch = o.F_epoch;
+    h->pad_done.assign(s.chunks.size(), 0);
+    h->tl[0] = now_us();
+    h->tl[1] = h->tl[2] = 0.0;
+    // nothing marked yet, no reference-rounded Gramian yet, no arrival counted (gramian_ref_kernel)
+    HIPCHK(h, hipMemsetAsync(h->d_gref_state.get(), 0, 3 * sizeof(int), h->stream));
   }
-  if (int rc = use_device(h)) return rc;
-  if (s.n_local == 0) return MALS_OK;
+  for (int c = chunk_begin; c < chunk_end; ++c) h->pad_done[(size_t)c] = 1;
+  if (k % 16 != 0) {
+    const int ld = 16 * h->T;
+    const size_t need = (size_t)o.n_total * (size_t)ld;
+    if (need > h->d_Mp.capacity()) {
+      new_half = true;   // the copy is gone
+      HIPCHK(h, h->d_Mp.reserve(need, h->stream));
+    }
+    if (new_half) {
+      PendingEvent pe;
+      if (int rc = begin_timed(h, 5, (double)o.n_total * 4.0 * (k + ld), pe)) return rc;
+      const int64_t n4 = o.n_total * (ld / 4);
+      const unsigned blocks = (unsigned)std::min<int64_t>((n4 + 255) / 256, (int64_t)h->n_cu * 32);
+      hipLaunchKernelGGL(pad_rows_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, h->stream, o.F, o.n_total, k, ld, h->d_Mp.get());
+      HIPCHK(h, hipGetLastError());
+      if (int rc = end_timed(h, pe)) return rc;
+    }
+  }
+  if (h->lds_gather && h->split_f16 && k == 128) {
+    if (!h->d_Gperm) HIPCHK(h, h->d_Gperm.alloc((size_t)tri(8) * 256));
+    if (h->gperm != now) {
+      if (h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED) {  // W does not start from G (ALS:524-539): an image of zeros
+        HIPCHK(h, hipMemsetAsync(h->d_Gperm.get(), 0, sizeof(float) * (size_t)tri(8) * 256, h->stream));
+      } else {
+        hipLaunchKernelGGL(gramian_perm_kernel, dim3((unsigned)tri(8)), dim3(256), 0, h->stream, o.G.get(), k, h->d_Gperm.get());
+        HIPCHK(h, hipGetLastError());
+      }
+      h->gperm = now;
+    }
+  }
+  HIPCHK(h, s.refine.reserve((size_t)s.n_local, h->stream));
+  if (h->split_f16 && (h->zs != now || h->zs_bound != s.max_abs_val || h->zs_mean != s.mean_abs_val)) {
+    // once per half-iteration, not per chunk: the scale only depends on G and on the value bound
+    const double base_w = (h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED) ? 1.0 : 0.0;
+    const double w_max = base_w + ((h->cfg.flags & MALS_FLAG_RECONSTRUCT_R) ? 0.0 : std::fabs(h->cfg.alpha) * (double)s.max_abs_val);
+    const double w_mean = base_w + ((h->cfg.flags & MALS_FLAG_RECONSTRUCT_R) ? 0.0 : std::fabs(h->cfg.alpha) * s.mean_abs_val);
+    int force = -1;  // MALS_FORCE_RANGE_FLAG=0/1 (tests): override the range decision
+    if (const char* e = std::getenv("MALS_FORCE_RANGE_FLAG")) force = std::atoi(e) != 0;
+    hipLaunchKernelGGL(gather_scale_kernel, dim3(1), dim3(64), 0, h->stream, o.G.get(), k, (float)std::sqrt(w_max), (float)std::sqrt(w_mean),
+                       (double)o.n_total, force, (o.ymax_version != 0 && o.ymax_version == o.G_version) ? o.d_ymax.get() : nullptr, h->d_zscale.get());
+    HIPCHK(h, hipGetLastError());
+    h->zs = now;
+    h->zs_bound = s.max_abs_val;
+    h->zs_mean = s.mean_abs_val;
+  }
+  if (g_to_host) {  // the Gramian goes to the host first so that its eigendecomposition runs while the direct kernels of
+                    // the first chunk execute
+    if (!h->h_G) HIPCHK(h, h->h_G.alloc((size_t)k * k));
+    if (!h->ev_G) HIPCHK(h, hipEventCreateWithFlags(&h->ev_G, hipEventDisableTiming));
+    HIPCHK(h, hipMemcpyAsync(h->h_G.get(), o.G.get(), sizeof(double) * (size_t)k * k, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev_G, h->stream));
+  }
+  return MALS_OK;
+}
+
+// The parameter block of the side's direct kernels, from what solve_setup left (no device work); a launch adds its list.
+static SolveParams solve_params(mals_handle h, int side) {
+  SideState& s = h->side[side];
+  SideState& o = h->side[1 - side];
   const int k = h->cfg.features;
   SolveParams p;
   p.row_ptr = s.row_ptr;
@@ -2080,61 +1886,12 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
   p.val = s.val;
   p.M = o.F;
   p.ldm = k;
-  if (!resume) {
-    // A new half-iteration?  The opposite factors do not change while a half-iteration's chunks are solved (in any
-    // order): "new" = the side, the opposite Gramian or the opposite uploads changed, or a chunk comes round again.
-    bool new_half = h->pad_side != side || h->pad_version != o.G_version || h->pad_epoch != o.F_epoch ||
-                    h->pad_done.size() != s.chunks.size();
-    for (int c = chunk_begin; c < chunk_end && !new_half; ++c) new_half = h->pad_done[(size_t)c] != 0;
-    if (new_half) {
-      h->pad_side = side;
-      h->pad_version = o.G_version;
-      h->pad_epoch = o.F_epoch;
-      h->pad_done.assign(s.chunks.size(), 0);
-      h->tl[0] = now_us();
-      h->tl[1] = h->tl[2] = 0.0;
-      // nothing marked yet, no reference-rounded Gramian yet, no arrival counted (gramian_ref_kernel)
-      HIPCHK(h, hipMemsetAsync(h->d_gref_state.get(), 0, 3 * sizeof(int), h->stream));
-    }
-    for (int c = chunk_begin; c < chunk_end; ++c) h->pad_done[(size_t)c] = 1;
-    if (k % 16 != 0) {
-      const int ld = 16 * h->T;
-      const size_t need = (size_t)o.n_total * (size_t)ld;
-      if (need > h->d_Mp.capacity()) {
-        new_half = true;   // the copy is gone
-        HIPCHK(h, h->d_Mp.reserve(need, h->stream));
-      }
-      if (new_half) {
-        PendingEvent pe;
-        if (int rc = begin_timed(h, 5, (double)o.n_total * 4.0 * (k + ld), pe)) return rc;
-        const int64_t n4 = o.n_total * (ld / 4);
-        const unsigned blocks = (unsigned)std::min<int64_t>((n4 + 255) / 256, (int64_t)h->n_cu * 32);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, h->stream, o.F, o.n_total, k, ld, h->d_Mp.get());
-        HIPCHK(h, hipGetLastError());
-        if (int rc = end_timed(h, pe)) return rc;
-      }
-    }
-  }
   if (k % 16 != 0) {
     p.M = h->d_Mp.get();
     p.ldm = 16 * h->T;
   }
   p.Gf = o.Gf.get();
-  p.Gperm = nullptr;
-  if (h->lds_gather && h->split_f16 && k == 128) {
-    if (!h->d_Gperm) HIPCHK(h, h->d_Gperm.alloc((size_t)tri(8) * 256));
-    if (!resume && (h->gperm_side != side || h->gperm_version != o.G_version)) {
-      if (h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED) {  // W does not start from G (ALS:524-539): an image of zeros
-        HIPCHK(h, hipMemsetAsync(h->d_Gperm.get(), 0, sizeof(float) * (size_t)tri(8) * 256, h->stream));
-      } else {
-        hipLaunchKernelGGL(gramian_perm_kernel, dim3((unsigned)tri(8)), dim3(256), 0, h->stream, o.G.get(), k, h->d_Gperm.get());
-        HIPCHK(h, hipGetLastError());
-      }
-      h->gperm_side = side;
-      h->gperm_version = o.G_version;
-    }
-    p.Gperm = h->d_Gperm.get();
-  }
+  p.Gperm = h->lds_gather && h->split_f16 && k == 128 ? h->d_Gperm.get() : nullptr;
   p.out = s.F + s.row_offset * k;
   p.items = nullptr;
   p.rowsC = s.rowsC.get();
@@ -2142,7 +1899,7 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
   p.bad_row = h->d_bad.get() + side;
   p.suspect = h->d_bad.get() + 2 + side;
   p.any_marked = h->d_gref_state.get();
-  p.refine_flag = nullptr;
+  p.refine_flag = s.refine.get();
   // under lossIgnoresUnspecified W has no Gramian under it and every marked row goes to the fp64 restatement, which
   // also reproduces that mode's fp32-rounded products: the estimate is at its weakest there (measured 100x and more
   // below cond(W) for rows with about as many entries as features), so the bar is lower
@@ -2151,10 +1908,6 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
   if (h->cfg.flags & MALS_FLAG_RECONSTRUCT_R) {   // no confidence weights: W = G + rho I (or the plain sum of y y^T)
     p.gramian_weight = 1.f;
     p.refine_limit *= 0.25f;
-  }
-  {
-    HIPCHK(h, s.refine.reserve((size_t)s.n_local, h->stream));
-    p.refine_flag = s.refine.get();
   }
   p.n_work = 0;
   p.trace = h->d_trace.get();
@@ -2167,116 +1920,129 @@ static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end,
   p.lambda_alpha = (float)(h->cfg.lambda * h->cfg.alpha);  // ALS:435
   p.sing_threshold = (float)h->cfg.singularity_threshold;
   p.zscale = h->d_zscale.get();
-  if (!resume && h->split_f16 && (h->zs_side != side || h->zs_version != o.G_version || h->zs_bound != s.max_abs_val || h->zs_mean != s.mean_abs_val)) {
-    // once per half-iteration, not per chunk: the scale only depends on G and on the value bound
-    const double base_w = (h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED) ? 1.0 : 0.0;
-    const double w_max = base_w + ((h->cfg.flags & MALS_FLAG_RECONSTRUCT_R) ? 0.0 : std::fabs(h->cfg.alpha) * (double)s.max_abs_val);
-    const double w_mean = base_w + ((h->cfg.flags & MALS_FLAG_RECONSTRUCT_R) ? 0.0 : std::fabs(h->cfg.alpha) * s.mean_abs_val);
-    int force = -1;  // MALS_FORCE_RANGE_FLAG=0/1 (tests): override the range decision
-    if (const char* e = std::getenv("MALS_FORCE_RANGE_FLAG")) force = std::atoi(e) != 0;
-    hipLaunchKernelGGL(gather_scale_kernel, dim3(1), dim3(64), 0, h->stream, o.G.get(), k, (float)std::sqrt(w_max), (float)std::sqrt(w_mean),
-                       (double)o.n_total, force, (o.ymax_version != 0 && o.ymax_version == o.G_version) ? o.d_ymax.get() : nullptr, h->d_zscale.get());
-    HIPCHK(h, hipGetLastError());
-    h->zs_side = side;
-    h->zs_version = o.G_version;
-    h->zs_bound = s.max_abs_val;
-    h->zs_mean = s.mean_abs_val;
-  }
-  // dual path (dual_kernels.h): the reference's default mode only; the Gramian goes to the host first so
-  // that its eigendecomposition runs while the direct kernels of the first chunk execute
-  // ... and only when it pays: the rotation of the gathered matrix costs ~1/30 of what a dual row saves
-  // (measured, k = 64 and 128), so a side with few short rows against a huge opposite matrix (the item half of
-  // C5: 1.25M long rows per rank gathering from 100M users) stays on the direct kernels
-  const bool dual_pays = h->cfg.solve_mode == MALS_SOLVE_DUAL || s.n_dual_rows * 32 >= o.n_total;
-  const bool want_dual = s.n_dual_rows > 0 && dual_pays && h->cfg.flags == 0 && h->cfg.alpha > 0.0 && o.G_valid;
-  const bool dual_stale = resume || (want_dual && (h->dual_side != side || h->dual_version != o.G_version));
-  if (dual_stale && !resume) {
-    if (!h->h_G) HIPCHK(h, h->h_G.alloc((size_t)k * k));
-    if (!h->ev_G) HIPCHK(h, hipEventCreateWithFlags(&h->ev_G, hipEventDisableTiming));
-    HIPCHK(h, hipMemcpyAsync(h->h_G.get(), o.G.get(), sizeof(double) * (size_t)k * k, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev_G, h->stream));
-  }
-  if (phase == SOLVE_BEGIN && chunk_end != chunk_begin + 1) return fail(h, MALS_INVALID_ARG, "solve BEGIN takes one chunk");
-  // everything a half-iteration sets up once is enqueued by now unless the dual preparation is still to come (below)
-  if (!resume && !(want_dual && dual_stale)) HIPCHK(h, hipEventRecord(h->ev_ready, h->stream));
-  const int64_t want_chunk_rows = s.chunk_rows_override >= 0 ? s.chunk_rows_override : h->cfg.chunk_rows;
-  const int64_t rows_per_chunk = want_chunk_rows > 0 ? want_chunk_rows : std::max<int64_t>(s.n_local, 1);  // as build_work_lists
-  for (int c = chunk_begin; c < chunk_end; ++c) {
-    const SideState::ChunkRange& cr = s.chunks[(size_t)c];
-    const int64_t row0 = std::min<int64_t>(s.n_local, (int64_t)c * rows_per_chunk);
-    const int64_t row1 = std::min<int64_t>(s.n_local, (int64_t)(c + 1) * rows_per_chunk);
-    if (!resume && p.refine_flag && row1 > row0) HIPCHK(h, hipMemsetAsync(s.refine.get() + row0, 0, (size_t)(row1 - row0), h->stream));
-    // (per chunk, not per call: once the first chunk of a multi-chunk call has prepared the dual path the later ones use it)
-    bool dual_now = want_dual && h->dual_ok && h->dual_side == side && h->dual_version == o.G_version;
-    if (!resume)
-      if (int rc = fork_streams(h)) return rc;
-    if (want_dual && dual_stale && c == chunk_begin) {
-      if (!resume) {
-        {
-          SideStream long_rows(h, 0);
-          if (int rc = launch_solve(h, s, p, c, LISTS_LONG)) return rc;
-        }
-        if (int rc = launch_solve(h, s, p, c, LISTS_ROWS)) return rc;   // direct lists first ...
-        if (phase == SOLVE_BEGIN) {                                     // ... the caller decomposes G under them
-          h->dual_pending = true;
-          h->dual_pending_side = side;
-          h->dual_pending_chunk = c;
-          return MALS_OK;
-        }
-        if (int rc = prepare_dual_host(h, side, nullptr)) return rc;    // ... host eigendecomposition under them
-      } else if (h->dual_side != side || h->dual_version != o.G_version) {
-        return fail(h, MALS_INVALID_ARG, "solve END without the eigendecomposition of this half-iteration");
-      }
-      h->dual_pending = false;
-      {
-        SideStream dual_rows(h, 1);
-        if (int rc = prepare_dual_device(h, side)) return rc;
-        HIPCHK(h, hipEventRecord(h->ev_ready, h->stream));   // (with MALS_OVERLAP: the side stream the rotation is on)
-        dual_now = h->dual_ok;
-        if (dual_now) {
-          if (int rc = launch_dual_chunk(h, side, c)) return rc;
-        } else if (cr.n_dual()) {  // does not qualify: the dual lists through the direct kernel after all
-          if (int rc = launch_solve(h, s, p, c, LISTS_DUAL_ROWS)) return rc;
-        }
-      }
-    } else {
+  return p;
+}
+
+// One chunk's kernels, between the fork and the join of the side streams.  prepare_dual: the chunk is the first of a
+// half-iteration whose dual path is still to be prepared -- its direct lists go first, the eigendecomposition of G runs
+// on the host under them (SOLVE_BEGIN: returns there with h->dual_pending set, the caller provides it; SOLVE_END resumes
+// behind it), then the device half of the preparation and the dual lists.  *dual_now: the chunk's dual lists ran on the
+// dual path.
+static int solve_one_chunk(mals_handle h, int side, const SolveParams& p, int c, int phase, bool want_dual, bool prepare_dual, bool* dual_now) {
+  SideState& s = h->side[side];
+  const SideState& o = h->side[1 - side];
+  const ChunkRange& cr = s.chunks[(size_t)c];
+  const bool resume = phase == SOLVE_END;
+  if (!resume && p.refine_flag && cr.row1 > cr.row0)
+    HIPCHK(h, hipMemsetAsync(s.refine.get() + cr.row0, 0, (size_t)(cr.row1 - cr.row0), h->stream));
+  // (per chunk, not per call: once the first chunk of a multi-chunk call has prepared the dual path the later ones use it)
+  const HalfStamp now{side, o.G_version};
+  *dual_now = want_dual && h->dual_ok && h->dual == now;
+  if (!resume)
+    if (int rc = fork_streams(h)) return rc;
+  if (prepare_dual) {
+    if (!resume) {
       {
         SideStream long_rows(h, 0);
         if (int rc = launch_solve(h, s, p, c, LISTS_LONG)) return rc;
       }
-      if (dual_now && cr.n_dual()) {
-        SideStream dual_rows(h, 1);
+      if (int rc = launch_solve(h, s, p, c, LISTS_ROWS)) return rc;   // direct lists first ...
+      if (phase == SOLVE_BEGIN) {                                     // ... the caller decomposes G under them
+        h->dual_pending = true;
+        h->dual_pending_side = side;
+        h->dual_pending_chunk = c;
+        return MALS_OK;
+      }
+      if (int rc = prepare_dual_host(h, side, nullptr)) return rc;    // ... host eigendecomposition under them
+    } else if (h->dual != now) {
+      return fail(h, MALS_INVALID_ARG, "solve END without the eigendecomposition of this half-iteration");
+    }
+    h->dual_pending = false;
+    {
+      SideStream dual_rows(h, 1);
+      if (int rc = prepare_dual_device(h, side)) return rc;
+      HIPCHK(h, hipEventRecord(h->ev_ready, h->stream));   // (with MALS_OVERLAP: the side stream the rotation is on)
+      *dual_now = h->dual_ok;
+      if (*dual_now) {
         if (int rc = launch_dual_chunk(h, side, c)) return rc;
+      } else if (cr.n_dual()) {  // does not qualify: the dual lists through the direct kernel after all
+        if (int rc = launch_solve(h, s, p, c, LISTS_DUAL_ROWS)) return rc;
       }
-      if (int rc = launch_solve(h, s, p, c, dual_now ? LISTS_ROWS : (LISTS_ROWS | LISTS_DUAL_ROWS))) return rc;
     }
-    if (int rc = join_streams(h)) return rc;
-    if (p.refine_flag && row1 > row0) {  // behind every kernel of the chunk (the un-rotation of the dual rows included)
-      if (h->refine_recorded) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_refine, 0));   // one chunk's block at a time
-      if (!h->d_Gref) {   // before the parameter block below takes the pointers
-        const size_t kp2 = (size_t)(16 * h->T) * (size_t)(16 * h->T);
-        HIPCHK(h, h->d_Gref.alloc(kp2));
-        HIPCHK(h, h->d_gref_part.alloc(kp2 * (size_t)h->n_cu * 2));
-      }
-      RefineParams q;
-      q.p = p;
-      q.G = o.G.get();
-      q.Gref = h->d_Gref.get();
-      q.gref_state = h->d_gref_state.get();
-      q.n_refined = h->d_refined.get();
-      q.row_begin = row0;
-      q.row_end = row1;
-      q.alpha = h->cfg.alpha;
-      q.lambda_alpha = h->cfg.lambda * h->cfg.alpha;
-      const bool no_gramian = h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED;
-      if (!no_gramian)   // something marked in this half-iteration: M^T M once more, rounded like the reference's
-        if (int rc = launch_gramian_ref(h, o)) return rc;
-      if (!no_gramian && h->refine_limit > 0.f)
-        if (int rc = launch_refine(h, q)) return rc;      // marks 1; may raise a mark to 2
-      if (int rc = launch_exact(h, q, no_gramian ? 1 : 2)) return rc;
-      HIPCHK(h, hipEventRecord(h->ev_refine, h->stream));
-      h->refine_recorded = true;
+  } else {
+    {
+      SideStream long_rows(h, 0);
+      if (int rc = launch_solve(h, s, p, c, LISTS_LONG)) return rc;
     }
+    if (*dual_now && cr.n_dual()) {
+      SideStream dual_rows(h, 1);
+      if (int rc = launch_dual_chunk(h, side, c)) return rc;
+    }
+    if (int rc = launch_solve(h, s, p, c, *dual_now ? LISTS_ROWS : (LISTS_ROWS | LISTS_DUAL_ROWS))) return rc;
+  }
+  return join_streams(h);
+}
+
+// The chunk's refinement block, behind every kernel of the chunk (the un-rotation of the dual rows included): the rows
+// the solving kernels marked, re-solved.
+static int refine_chunk(mals_handle h, int side, const SolveParams& p, const ChunkRange& cr) {
+  const SideState& o = h->side[1 - side];
+  if (!p.refine_flag || cr.row1 <= cr.row0) return MALS_OK;
+  if (h->refine_recorded) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_refine, 0));   // one chunk's block at a time
+  if (!h->d_Gref) {   // before the parameter block below takes the pointers
+    const size_t kp2 = (size_t)(16 * h->T) * (size_t)(16 * h->T);
+    HIPCHK(h, h->d_Gref.alloc(kp2));
+    HIPCHK(h, h->d_gref_part.alloc(kp2 * (size_t)h->n_cu * 2));
+  }
+  RefineParams q;
+  q.p = p;
+  q.G = o.G.get();
+  q.Gref = h->d_Gref.get();
+  q.gref_state = h->d_gref_state.get();
+  q.n_refined = h->d_refined.get();
+  q.row_begin = cr.row0;
+  q.row_end = cr.row1;
+  q.alpha = h->cfg.alpha;
+  q.lambda_alpha = h->cfg.lambda * h->cfg.alpha;
+  const bool no_gramian = h->cfg.flags & MALS_FLAG_LOSS_IGNORES_UNSPECIFIED;
+  if (!no_gramian)   // something marked in this half-iteration: M^T M once more, rounded like the reference's
+    if (int rc = launch_gramian_ref(h, o)) return rc;
+  if (!no_gramian && h->refine_limit > 0.f)
+    if (int rc = launch_refine(h, q)) return rc;      // marks 1; may raise a mark to 2
+  if (int rc = launch_exact(h, q, no_gramian ? 1 : 2)) return rc;
+  HIPCHK(h, hipEventRecord(h->ev_refine, h->stream));
+  h->refine_recorded = true;
+  return MALS_OK;
+}
+
+static int solve_chunks(mals_handle h, int side, int chunk_begin, int chunk_end, int phase = SOLVE_ALL) {
+  if (int rc = solve_check_args(h, side, chunk_begin, chunk_end)) return rc;
+  SideState& s = h->side[side];
+  SideState& o = h->side[1 - side];
+  const bool resume = phase == SOLVE_END;
+  if (resume) {
+    if (!h->dual_pending) return MALS_OK;  // BEGIN did the whole chunk
+    if (h->dual_pending_side != side || h->dual_pending_chunk != chunk_begin || chunk_end != chunk_begin + 1)
+      return fail(h, MALS_INVALID_ARG, "solve END does not match the pending BEGIN");
+  } else {
+    h->dual_pending = false;  // a BEGIN whose END never came belongs to a half-iteration that was abandoned on an error
+  }
+  if (int rc = use_device(h)) return rc;
+  if (s.n_local == 0) return MALS_OK;
+  const bool want_dual = dual_wanted(h, s, o);
+  const bool dual_stale = resume || (want_dual && h->dual != HalfStamp{side, o.G_version});
+  if (!resume)
+    if (int rc = solve_setup(h, side, chunk_begin, chunk_end, dual_stale)) return rc;
+  const SolveParams p = solve_params(h, side);
+  if (phase == SOLVE_BEGIN && chunk_end != chunk_begin + 1) return fail(h, MALS_INVALID_ARG, "solve BEGIN takes one chunk");
+  // everything a half-iteration sets up once is enqueued by now unless the dual preparation is still to come (solve_one_chunk)
+  if (!resume && !(want_dual && dual_stale)) HIPCHK(h, hipEventRecord(h->ev_ready, h->stream));
+  for (int c = chunk_begin; c < chunk_end; ++c) {
+    const ChunkRange& cr = s.chunks[(size_t)c];
+    bool dual_now = false;
+    if (int rc = solve_one_chunk(h, side, p, c, phase, want_dual, want_dual && dual_stale && c == chunk_begin, &dual_now)) return rc;
+    if (phase == SOLVE_BEGIN && h->dual_pending) return MALS_OK;   // the host's turn; END takes the chunk up again
+    if (int rc = refine_chunk(h, side, p, cr)) return rc;
     h->stats.rows_solved += cr.nA + cr.nC + cr.n_dual() + cr.nZ;
     h->stats.nnz_gathered += cr.nnzA + cr.nnzB + cr.nnz_dual();
     if (dual_now) h->stats.rows_dual += cr.n_dual();
@@ -2627,17 +2393,12 @@ int mals_reconstruction_error(mals_handle h, double* sum_out, int64_t* count_out
   HIPCHK(h, counts.alloc(n_waves));
   double* d_sum = sums.get();
   unsigned long long* d_cnt = counts.get();
-  int rc = MALS_INVALID_ARG;
-  switch (h->T) {
-    case 1: rc = launch_reconstruction<1>(h, s, o, grid, d_sum, d_cnt); break;
-    case 2: rc = launch_reconstruction<2>(h, s, o, grid, d_sum, d_cnt); break;
-    case 3: rc = launch_reconstruction<3>(h, s, o, grid, d_sum, d_cnt); break;
-    case 4: rc = launch_reconstruction<4>(h, s, o, grid, d_sum, d_cnt); break;
-    case 5: rc = launch_reconstruction<5>(h, s, o, grid, d_sum, d_cnt); break;
-    case 6: rc = launch_reconstruction<6>(h, s, o, grid, d_sum, d_cnt); break;
-    case 7: rc = launch_reconstruction<7>(h, s, o, grid, d_sum, d_cnt); break;
-    case 8: rc = launch_reconstruction<8>(h, s, o, grid, d_sum, d_cnt); break;
-  }
+  int rc = dispatch_T(h, [&](auto t) -> int {
+    hipLaunchKernelGGL((reconstruction_kernel<t()>), dim3(grid), dim3(256), 0, h->stream, s.row_ptr, s.col,
+                       s.F + s.row_offset * h->cfg.features, o.F, h->cfg.features, s.n_local, d_sum, d_cnt);
+    HIPCHK(h, hipGetLastError());
+    return MALS_OK;
+  });
   std::vector<double> hs(n_waves);
   std::vector<unsigned long long> hc(n_waves);
   if (rc == MALS_OK) {

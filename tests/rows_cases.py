@@ -30,7 +30,7 @@ FLAG_RECONSTRUCT_R, FLAG_LOSS_IGNORES_UNSPECIFIED = 1, 2
 ALPHA, LAMBDA = 1.0, 0.125
 ORDER_SEEDS = (1, 2)
 ULP = 2.0 ** -23
-FINISH_GROUP = 32        # csrc/als_kernels.h: a row of more segments than this goes through als_prereduce_kernel first
+FINISH_GROUP = 32        # csrc/work_plan.h: a row of more segments than this goes through als_prereduce_kernel first
 
 
 def table_shape(k):
@@ -174,8 +174,9 @@ def gather_scale(G, max_abs_val, flags=0, alpha=ALPHA):
 
 
 def segment_cuts(length, segment_nnz):
-    """First entries of the segments build_work_lists (csrc/mals_api.hip) cuts a row of more than segment_nnz entries into by
-    count, for segment_nnz <= 512 (above, the cut also depends on the device's size): equal parts, whole 4-entry steps."""
+    """First entries of the segments plan_work_lists (csrc/work_plan.h) cuts a row of more than segment_nnz entries into by
+    count, for segment_nnz <= 512 (above, the cut also depends on the device's size): equal parts, whole 4-entry steps.
+    tests/test_work_plan.py holds this against the planner itself."""
     assert segment_nnz <= 512 and segment_nnz % 32 == 0 and length > segment_nnz
     nseg = -(-length // segment_nnz)
     per = (-(-length // nseg) + 3) & ~3

@@ -1,5 +1,5 @@
-"""Long dense rows cut at the bands of the gather table (csrc/band_plan.h, build_work_lists and launch_lists in
-csrc/mals_api.hip): the banded lists must compute what the lists cut by count compute.
+"""Long dense rows cut at the bands of the gather table (csrc/band_plan.h, plan_work_lists in csrc/work_plan.h, launch_lists
+in csrc/mals_api.hip): the banded lists must compute what the lists cut by count compute.
 
 The table has 2048 rows and a band is 256 of them (MALS_BAND_BYTES, read at every list build), segment_nnz = 64 and a row
 is banded from 16 entries per band on (MALS_BAND_MIN_ENTRIES), i.e. from 128 entries.  k = 30 gathers from the padded
