@@ -992,6 +992,102 @@ int mals_group_replica_digest(mals_group g, int side, int64_t row_begin, int64_t
                               int32_t* all_equal_out);
 int mals_factor_digest_host(const float* rows, int32_t features, int64_t row_begin, int64_t n_rows, uint64_t* out);
 
+/* ---- loading a new generation into a live handle -------------------------------------------------------------------
+ * GenerationLoader.loadModel (online-local/src/net/myrrix/online/generation/GenerationLoader.java:49-106), which
+ * DelegateGenerationManager calls after every rebuild (DelegateGenerationManager.java:359): the new X, Y, knownItemIDs and
+ * tag sets are merged into the generation being served BY ID, and what the new model no longer has survives only if it
+ * was written since the last load.  On the device the model is dense rows, so the merge is an id join, a compaction and a
+ * row gather (csrc/generation_kernels.h), run as ONE exclusive ticket of the serving front on the handle's stream: a
+ * concurrent mals_recommend* sees the old generation or the new one, never a mixture.  For handles outside a group
+ * (a member is MALS_INVALID_ARG, like the writes; the mals_group_* twin is not built yet).
+ *
+ * RECENT ROWS (recentlyActiveUsers / recentlyActiveItems, DelegateGenerationManager.java:179-186): the handle records,
+ * per side, the user row and the item row of every datum given to mals_set_preferences and mals_remove_preferences whose
+ * batch passed its argument checks, as doAppend does -- a host bit per written row, set inside the write's ticket; no
+ * other call sees it.  mals_mark_recent adds n rows of `side` (host; rows inside the replica) for writes made elsewhere
+ * (tag writes, an append on the JVM side); mals_get_recent returns them ascending (rows_out: capacity = the replica's
+ * rows, may be NULL to ask for *n_out alone).  A successful load clears both sides (:97-98).
+ *
+ * THE MERGE, per side, with cur_ids[r] = the id of live row r (n_cur = the replica's rows) and new_ids[j] = the id of row
+ * j of the new model:
+ *   - merged rows 0 .. n_new-1 are the new model's rows in its order; behind them come, in live order, the live rows whose
+ *     id is not among new_ids and which are recent -- the KEPT rows, with their live values, fold-in updates included.
+ *     Every other live row is pruned (removeNotUpdated, :137-152).  A live row whose id is among new_ids takes the new
+ *     model's vector even if it was written recently (updateMap is a put, :117-126).
+ *     MALS_GENERATION_KEEP_NOT_UPDATED (model.removeNotUpdatedData=false, :72): every live row not among new_ids is kept.
+ *   - the new rows are a prefix of the merged rows, so the new model's known-item CSR and its dense item indices hold for
+ *     the merged model unchanged.
+ *   - known items: a user of the new model gets the new model's set, whole (a put).  A kept user keeps its effective live
+ *     set -- base row plus the writes' additions, or the set left by removals -- with every item re-indexed to its merged
+ *     row.  DEVIATION: an item of such a set that has no merged row (it was pruned) is dropped and counted in
+ *     n_known_dropped; the reference keeps the bare id there, where only mostPopularItems could still see it.
+ *   - tag sets (updateTagIDs :108-115, removeNotUpdated :88-95): final set = updated set + the live tags whose row is
+ *     recent (with KEEP_NOT_UPDATED: + every live tag).  item_tag_ids (itemTagIDs) are user-side ids and become the set of
+ *     mals_set_tag_users over merged user rows; user_tag_ids (userTagIDs) are item-side ids and become the mask of
+ *     mals_set_tag_items over merged item rows.  Ids without a merged row are ignored and counted
+ *     (n_tag_ids_without_row).
+ *   - state derived from the model (Generation.recomputeState, :101-102): both Gramians and the padded / rotated copies of
+ *     the replicas are invalidated, the counts of mals_most_popular_items are recounted on the next call, and the
+ *     candidate filter is DROPPED -- its signatures were a snapshot of the live Y: call mals_lsh_build again.  With
+ *     MALS_GENERATION_RECOMPUTE_SOLVERS the solvers of X^T X and Y^T Y are recomputed from the merged replicas and set as
+ *     mals_recompute_solver + mals_set_foldin_solver do, still inside the ticket; solver_status = the first code that was
+ *     not MALS_OK (MALS_ILL_CONDITIONED, MALS_SINGULAR: the load itself stands, the solvers of the old generation stay).
+ *     Rescorers name item rows of the generation they were made for: the caller makes them again.
+ *   - the handle's matrices (mals_set_matrix) named live rows and are released: a handle that serves loaded generations
+ *     is not iterated; a builder handle does that beside it ("rebuild beside a serving handle").
+ * The merged replicas are the library's own blocks with room to grow (mals_grow_factor_rows), whatever the live ones were;
+ * the new known items are copied (the new model's arrays stay the caller's and may go once the call returns).
+ *
+ * ALL OR NOTHING: everything is built aside and swapped in last.  Any failure -- MALS_OOM, an id twice within cur_ids or
+ * within new_ids (MALS_INVALID_ARG), features != the handle's, n_cur != the replica's rows, missing known items on a
+ * handle that holds some, a group member -- leaves the handle answering exactly as before.
+ *
+ * THE JOIN is an open-addressing table of the new ids with linear probing: slots = the smallest power of two >= max(64,
+ * 2 n_new), home slot = mals_generation_hash_host(id) & (slots - 1), with in uint64 arithmetic
+ *     z = id * 0x9E3779B97F4A7C15;   z ^= z >> 32;   z *= 0xD6E8FEB86659FD93;   z ^= z >> 32;   hash = z.
+ * Every 64-bit value is a legal id (Long.MIN_VALUE, -1 and 0 included): a slot is claimed through its value word.
+ * mals_generation_join_host is the same join on the host, no device: recent_rows = n_recent live rows (any order, repeats
+ * allowed), flags as above; map_out[n_cur] = live row -> merged row, -1 = pruned; counts_out[4] (nullable) = {n_merged,
+ * n_updated, n_kept, n_pruned}.  MALS_INVALID_ARG for a duplicate id on either side or a recent row outside [0, n_cur). */
+enum { MALS_GENERATION_KEEP_NOT_UPDATED = 1, MALS_GENERATION_RECOMPUTE_SOLVERS = 2 };
+typedef struct mals_generation_load {
+  int32_t struct_size;
+  int32_t flags;                  /* MALS_GENERATION_* */
+  int32_t features;               /* of new_rows: must be the handle's */
+  int32_t cur_mem_kind;           /* of cur_ids */
+  int32_t new_mem_kind;           /* of every array of the new model below (device: what a builder handle and an ingest hold) */
+  int32_t reserved;
+  const int64_t* cur_ids[2];      /* [side]: the id of every live row */
+  int64_t n_cur[2];               /* = the replica's rows (0 for a side without a replica) */
+  const int64_t* new_ids[2];
+  int64_t n_new[2];
+  const float* new_rows[2];       /* n_new x features, dense */
+  const int64_t* new_known_ptr;   /* CSR over the new users: n_new[X] + 1 offsets; NULL only if the handle holds no known items */
+  const int32_t* new_known_idx;   /* dense item rows of the new model */
+  const int64_t* item_tag_ids;    /* updatedItemTagIDs: user-side ids */
+  int64_t n_item_tag_ids;
+  const int64_t* user_tag_ids;    /* updatedUserTagIDs: item-side ids */
+  int64_t n_user_tag_ids;
+} mals_generation_load;
+typedef struct mals_generation_result {
+  int32_t struct_size;
+  int32_t solver_status;          /* MALS_GENERATION_RECOMPUTE_SOLVERS: MALS_OK or the first failure */
+  int64_t n_merged[2], n_updated[2], n_kept[2], n_pruned[2];   /* [side]; n_updated: live rows whose id the new model has */
+  int64_t n_known_dropped, n_tag_ids_without_row;
+  double join_ms[2], scan_ms[2], gather_ms[2];   /* device times (HIP events): tables + probe; scan + map; head copy + tail gather */
+  double sides_ms, known_ms, tags_ms, total_ms;  /* host wall time: both sides (waits included), known items, tag sets, the ticket */
+} mals_generation_result;
+int mals_load_generation(mals_handle h, const mals_generation_load* load, mals_generation_result* result_out);
+/* Of the last successful load, valid until the next: the merged ids in row order (n_merged of them), and live row ->
+ * merged row for the n_cur rows the handle had before it (-1 = pruned) -- what the caller re-keys its id map with. */
+int mals_generation_get_ids(mals_handle h, int side, int64_t* ids_out);
+int mals_generation_get_map(mals_handle h, int side, int64_t* map_out);
+int mals_mark_recent(mals_handle h, int side, int64_t n, const int64_t* rows);
+int mals_get_recent(mals_handle h, int side, int64_t* rows_out, int64_t* n_out);
+uint64_t mals_generation_hash_host(int64_t id);
+int mals_generation_join_host(const int64_t* cur_ids, int64_t n_cur, const int64_t* new_ids, int64_t n_new, const int64_t* recent_rows,
+                              int64_t n_recent, int32_t flags, int64_t* map_out, int64_t* counts_out);
+
 /* iterateXFromY / iterateYFromX (ALS:340-389) and call() (ALS:176-262) on the group; arguments as for
  * mals_half_iteration / mals_factorize. */
 int mals_group_half_iteration(mals_group g, int side);

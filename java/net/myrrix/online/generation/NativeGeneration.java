@@ -74,6 +74,12 @@ public final class NativeGeneration implements AutoCloseable {
   private static native int nativeLshBuild(long handle, int numHashes, int maxBitsDiffering, int[] randomVectors, long[] meanBits);
   private static native int nativeLshClear(long handle);
   private static native String nativeLastError(long handle);
+  private static native int nativeLoadGeneration(long handle, int flags, int features, long[] curUserIds, long[] curItemIds,
+                                                 long[] newUserIds, long[] newItemIds, float[] newX, float[] newY,
+                                                 long[] knownPtr, int[] knownIdx, long[] itemTagIds, long[] userTagIds,
+                                                 long[] counts, long[] userMap, long[] itemMap);
+  private static native int nativeGenerationIds(long handle, int side, long nMerged, long[] ids);
+  private static native int nativeMarkRecent(long handle, int side, long[] rows);
 
   /** The reference's own six arguments (InputFilesReader.java:64-69; call site DelegateGenerationManager.java:336): a switch by
    *  class name only.  The device is the first of -Dmodel.als.gpus (default 0). */
@@ -320,6 +326,52 @@ public final class NativeGeneration implements AutoCloseable {
 
   static int rescorerSetUniform(long rescorer, long scaleBits, long offsetBits) {
     return nativeRescorerSetUniform(rescorer, scaleBits, offsetBits);
+  }
+
+  /** model.removeNotUpdatedData=false (GenerationLoader.java:72): every live row the new model lacks is kept. */
+  public static final int KEEP_NOT_UPDATED = 1;
+  /** Generation.recomputeState: the XTX / YTY solvers are recomputed from the merged model inside the load. */
+  public static final int RECOMPUTE_SOLVERS = 2;
+
+  /** What loadGeneration leaves: the merged ids in row order and, per live row, its merged row (-1 = pruned) -- what the
+   *  caller re-keys its id maps with -- and the counts. */
+  public static final class LoadedGeneration {
+    public long[] userIDs;
+    public long[] itemIDs;
+    public long[] userMap;
+    public long[] itemMap;
+    /** per side merged, updated, kept, pruned (users, then items); known items dropped; tag ids without a row; solver status */
+    public long[] counts;
+  }
+
+  /** GenerationLoader.loadModel (GenerationLoader.java:49-106) on the serving handle, by id: the rebuilt model's rows come
+   *  first in its own order, then the live rows it lacks that were written since the last load (setPreference,
+   *  removePreference, markRecent).  curUserIDs / curItemIDs: the id of every live row; newX / newY: n x features,
+   *  row-major; knownPtr / knownIdx: the new knownItemIDs as a CSR over the new users with dense new item rows (null, null
+   *  only for a handle without known items).  One exclusive step of the serving front: a concurrent recommend sees the old
+   *  generation or the new one.  The candidate filter is dropped: call buildCandidateFilter again.  A kept user's known
+   *  item that was pruned is dropped (counts[8]); the reference keeps the bare id. */
+  public static LoadedGeneration loadGeneration(long handle, int flags, int features, long[] curUserIDs, long[] curItemIDs,
+                                                long[] newUserIDs, long[] newItemIDs, float[] newX, float[] newY,
+                                                long[] knownPtr, int[] knownIdx, long[] itemTagIDs, long[] userTagIDs) {
+    LoadedGeneration g = new LoadedGeneration();
+    g.counts = new long[12];
+    g.userMap = new long[curUserIDs.length];
+    g.itemMap = new long[curItemIDs.length];
+    checkHandle(handle, nativeLoadGeneration(handle, flags, features, curUserIDs, curItemIDs, newUserIDs, newItemIDs, newX, newY,
+                                             knownPtr, knownIdx, itemTagIDs == null ? new long[0] : itemTagIDs,
+                                             userTagIDs == null ? new long[0] : userTagIDs, g.counts, g.userMap, g.itemMap));
+    g.userIDs = new long[(int) g.counts[0]];
+    g.itemIDs = new long[(int) g.counts[4]];
+    checkHandle(handle, nativeGenerationIds(handle, 0, g.counts[0], g.userIDs));
+    checkHandle(handle, nativeGenerationIds(handle, 1, g.counts[4], g.itemIDs));
+    return g;
+  }
+
+  /** recentlyActiveUsers (side 0) / recentlyActiveItems (side 1) for writes made outside the library
+   *  (DelegateGenerationManager.java:179-186): dense rows of the serving handle. */
+  public static void markRecent(long handle, int side, long[] rows) {
+    checkHandle(handle, nativeMarkRecent(handle, side, rows));
   }
 
   static String lastError(long handle) {

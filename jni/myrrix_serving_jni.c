@@ -481,3 +481,126 @@ JNIEXPORT jstring JNICALL JNI_FN(nativeLastError)(JNIEnv* env, jclass cls, jlong
   const char* e = handle ? mals_last_error(as_handle(handle)) : "no handle";
   return (*env)->NewStringUTF(env, e ? e : "");
 }
+
+/* ---- a new generation into the serving handle (GenerationLoader.loadModel, GenerationLoader.java:49-106) -------------- */
+
+/* mals_load_generation with every array of the new model on the host: cur*Ids = the id of every live row, new*Ids / newX /
+ * newY (n x features, row-major) the rebuilt model, knownPtr / knownIdx its knownItemIDs as a CSR over the new users (both
+ * null only for a handle without known items), itemTagIds / userTagIds the updated tag sets (may be empty).  flags: 1 =
+ * model.removeNotUpdatedData=false, 2 = recompute the solvers.  counts (long[12]): per side merged, updated, kept, pruned
+ * (users then items), known items dropped, tag ids without a row, the solvers' status, 0.  userMap / itemMap (one long per
+ * live row): live row -> merged row, -1 = pruned.  The merged ids come from nativeGenerationIds. */
+JNIEXPORT jint JNICALL JNI_FN(nativeLoadGeneration)(JNIEnv* env, jclass cls, jlong handle, jint flags, jint features, jlongArray cur_user_ids,
+                                                    jlongArray cur_item_ids, jlongArray new_user_ids, jlongArray new_item_ids, jfloatArray new_x,
+                                                    jfloatArray new_y, jlongArray known_ptr, jintArray known_idx, jlongArray item_tag_ids,
+                                                    jlongArray user_tag_ids, jlongArray counts, jlongArray user_map, jlongArray item_map) {
+  (void)cls;
+  if (!cur_user_ids || !cur_item_ids || !new_user_ids || !new_item_ids || !new_x || !new_y || !item_tag_ids || !user_tag_ids || !counts ||
+      !user_map || !item_map || features < 1 || (known_ptr == NULL) != (known_idx == NULL))
+    return MALS_INVALID_ARG;
+  const jsize n_cur[2] = {(*env)->GetArrayLength(env, cur_user_ids), (*env)->GetArrayLength(env, cur_item_ids)};
+  const jsize n_new[2] = {(*env)->GetArrayLength(env, new_user_ids), (*env)->GetArrayLength(env, new_item_ids)};
+  /* the native side reads n x features floats and n + 1 offsets, and writes one map entry per live row */
+  if ((int64_t)(*env)->GetArrayLength(env, new_x) < (int64_t)n_new[0] * features || (int64_t)(*env)->GetArrayLength(env, new_y) < (int64_t)n_new[1] * features ||
+      (known_ptr && (*env)->GetArrayLength(env, known_ptr) < n_new[0] + 1) || (*env)->GetArrayLength(env, counts) < 12 ||
+      (*env)->GetArrayLength(env, user_map) < n_cur[0] || (*env)->GetArrayLength(env, item_map) < n_cur[1])
+    return MALS_INVALID_ARG;
+  jlong* cu = (*env)->GetLongArrayElements(env, cur_user_ids, NULL);
+  jlong* ci = (*env)->GetLongArrayElements(env, cur_item_ids, NULL);
+  jlong* nu = (*env)->GetLongArrayElements(env, new_user_ids, NULL);
+  jlong* ni = (*env)->GetLongArrayElements(env, new_item_ids, NULL);
+  jfloat* x = (*env)->GetFloatArrayElements(env, new_x, NULL);
+  jfloat* y = (*env)->GetFloatArrayElements(env, new_y, NULL);
+  jlong* kp = known_ptr ? (*env)->GetLongArrayElements(env, known_ptr, NULL) : NULL;
+  jint* ki = known_idx ? (*env)->GetIntArrayElements(env, known_idx, NULL) : NULL;
+  jlong* it = (*env)->GetLongArrayElements(env, item_tag_ids, NULL);
+  jlong* ut = (*env)->GetLongArrayElements(env, user_tag_ids, NULL);
+  int rc = MALS_OOM;
+  mals_generation_result res;
+  memset(&res, 0, sizeof res);
+  res.struct_size = (int32_t)sizeof res;
+  if (cu && ci && nu && ni && x && y && it && ut && (kp || !known_ptr) && (ki || !known_idx)) {
+    if (kp && (kp[0] != 0 || kp[n_new[0]] < 0 || kp[n_new[0]] > (jlong)(*env)->GetArrayLength(env, known_idx))) {
+      rc = MALS_INVALID_ARG;   /* the offsets index knownIdx: they must stay inside it */
+    } else {
+      mals_generation_load ld;
+      memset(&ld, 0, sizeof ld);
+      ld.struct_size = (int32_t)sizeof ld;
+      ld.flags = (int32_t)flags;
+      ld.features = (int32_t)features;
+      ld.cur_mem_kind = MALS_MEM_HOST;
+      ld.new_mem_kind = MALS_MEM_HOST;
+      ld.cur_ids[0] = (const int64_t*)cu;
+      ld.cur_ids[1] = (const int64_t*)ci;
+      ld.new_ids[0] = (const int64_t*)nu;
+      ld.new_ids[1] = (const int64_t*)ni;
+      ld.new_rows[0] = (const float*)x;
+      ld.new_rows[1] = (const float*)y;
+      for (int s = 0; s < 2; ++s) {
+        ld.n_cur[s] = (int64_t)n_cur[s];
+        ld.n_new[s] = (int64_t)n_new[s];
+      }
+      ld.new_known_ptr = (const int64_t*)kp;
+      ld.new_known_idx = (const int32_t*)ki;
+      ld.item_tag_ids = (const int64_t*)it;
+      ld.n_item_tag_ids = (int64_t)(*env)->GetArrayLength(env, item_tag_ids);
+      ld.user_tag_ids = (const int64_t*)ut;
+      ld.n_user_tag_ids = (int64_t)(*env)->GetArrayLength(env, user_tag_ids);
+      rc = mals_load_generation(as_handle(handle), &ld, &res);
+    }
+  }
+  if (ut) (*env)->ReleaseLongArrayElements(env, user_tag_ids, ut, JNI_ABORT);
+  if (it) (*env)->ReleaseLongArrayElements(env, item_tag_ids, it, JNI_ABORT);
+  if (ki) (*env)->ReleaseIntArrayElements(env, known_idx, ki, JNI_ABORT);
+  if (kp) (*env)->ReleaseLongArrayElements(env, known_ptr, kp, JNI_ABORT);
+  if (y) (*env)->ReleaseFloatArrayElements(env, new_y, y, JNI_ABORT);
+  if (x) (*env)->ReleaseFloatArrayElements(env, new_x, x, JNI_ABORT);
+  if (ni) (*env)->ReleaseLongArrayElements(env, new_item_ids, ni, JNI_ABORT);
+  if (nu) (*env)->ReleaseLongArrayElements(env, new_user_ids, nu, JNI_ABORT);
+  if (ci) (*env)->ReleaseLongArrayElements(env, cur_item_ids, ci, JNI_ABORT);
+  if (cu) (*env)->ReleaseLongArrayElements(env, cur_user_ids, cu, JNI_ABORT);
+  if (rc != MALS_OK) return rc;
+  const jlong out[12] = {(jlong)res.n_merged[0], (jlong)res.n_updated[0], (jlong)res.n_kept[0], (jlong)res.n_pruned[0],
+                         (jlong)res.n_merged[1], (jlong)res.n_updated[1], (jlong)res.n_kept[1], (jlong)res.n_pruned[1],
+                         (jlong)res.n_known_dropped, (jlong)res.n_tag_ids_without_row, (jlong)res.solver_status, 0};
+  (*env)->SetLongArrayRegion(env, counts, 0, 12, out);
+  jlongArray maps[2] = {user_map, item_map};
+  for (int s = 0; s < 2 && rc == MALS_OK; ++s) {
+    if (n_cur[s] == 0) continue;
+    jlong* m = (*env)->GetLongArrayElements(env, maps[s], NULL);
+    if (!m) return MALS_OOM;
+    rc = mals_generation_get_map(as_handle(handle), s, (int64_t*)m);
+    (*env)->ReleaseLongArrayElements(env, maps[s], m, rc == MALS_OK ? 0 : JNI_ABORT);
+  }
+  return rc;
+}
+
+/* the merged ids of the last load in row order: ids must hold the side's merged rows (counts[0] / counts[4] above) */
+JNIEXPORT jint JNICALL JNI_FN(nativeGenerationIds)(JNIEnv* env, jclass cls, jlong handle, jint side, jlong n_merged, jlongArray ids) {
+  (void)cls;
+  int64_t n_rows = 0;
+  void* rows = NULL;
+  if (!ids || (side != 0 && side != 1)) return MALS_INVALID_ARG;
+  /* the native side writes one id per row of the replica: the array must hold them */
+  const int rc0 = mals_factor_device_ptr(as_handle(handle), (int)side, &rows, &n_rows);
+  if (rc0 != MALS_OK) return rc0;
+  if (n_merged != (jlong)n_rows || (int64_t)(*env)->GetArrayLength(env, ids) < n_rows) return MALS_INVALID_ARG;
+  jlong* p = (*env)->GetLongArrayElements(env, ids, NULL);
+  if (!p) return MALS_OOM;
+  const int rc = mals_generation_get_ids(as_handle(handle), (int)side, (int64_t*)p);
+  (*env)->ReleaseLongArrayElements(env, ids, p, rc == MALS_OK ? 0 : JNI_ABORT);
+  return rc;
+}
+
+/* recentlyActiveUsers / recentlyActiveItems for writes the library did not see (tag writes, an append on the JVM side) */
+JNIEXPORT jint JNICALL JNI_FN(nativeMarkRecent)(JNIEnv* env, jclass cls, jlong handle, jint side, jlongArray rows) {
+  (void)cls;
+  if (!rows) return MALS_INVALID_ARG;
+  const jsize n = (*env)->GetArrayLength(env, rows);
+  if (n == 0) return MALS_OK;
+  jlong* r = (*env)->GetLongArrayElements(env, rows, NULL);
+  if (!r) return MALS_OOM;
+  const int rc = mals_mark_recent(as_handle(handle), (int)side, (int64_t)n, (const int64_t*)r);
+  (*env)->ReleaseLongArrayElements(env, rows, r, JNI_ABORT);
+  return rc;
+}

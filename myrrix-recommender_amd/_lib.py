@@ -80,6 +80,27 @@ class IngestTextInfo(ctypes.Structure):   # mals_ingest_text_info_t
                 ("n_item_tag_ids", ctypes.c_int64), ("n_user_tag_ids", ctypes.c_int64), ("n_known_items", ctypes.c_int64)]
 
 
+GENERATION_KEEP_NOT_UPDATED, GENERATION_RECOMPUTE_SOLVERS = 1, 2
+
+
+class GenerationLoad(ctypes.Structure):   # mals_generation_load
+    _fields_ = [("struct_size", ctypes.c_int32), ("flags", ctypes.c_int32), ("features", ctypes.c_int32), ("cur_mem_kind", ctypes.c_int32),
+                ("new_mem_kind", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("cur_ids", ctypes.c_void_p * 2), ("n_cur", ctypes.c_int64 * 2),
+                ("new_ids", ctypes.c_void_p * 2), ("n_new", ctypes.c_int64 * 2), ("new_rows", ctypes.c_void_p * 2),
+                ("new_known_ptr", ctypes.c_void_p), ("new_known_idx", ctypes.c_void_p),
+                ("item_tag_ids", ctypes.c_void_p), ("n_item_tag_ids", ctypes.c_int64),
+                ("user_tag_ids", ctypes.c_void_p), ("n_user_tag_ids", ctypes.c_int64)]
+
+
+class GenerationResult(ctypes.Structure):   # mals_generation_result
+    _fields_ = [("struct_size", ctypes.c_int32), ("solver_status", ctypes.c_int32),
+                ("n_merged", ctypes.c_int64 * 2), ("n_updated", ctypes.c_int64 * 2), ("n_kept", ctypes.c_int64 * 2), ("n_pruned", ctypes.c_int64 * 2),
+                ("n_known_dropped", ctypes.c_int64), ("n_tag_ids_without_row", ctypes.c_int64),
+                ("join_ms", ctypes.c_double * 2), ("scan_ms", ctypes.c_double * 2), ("gather_ms", ctypes.c_double * 2),
+                ("sides_ms", ctypes.c_double), ("known_ms", ctypes.c_double), ("tags_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
+
+
 ITERATION_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(IterationInfo))
 
 
@@ -261,6 +282,13 @@ SYMBOLS = {
     "mals_factor_digest": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, ctypes.POINTER(ctypes.c_uint64)]),
     "mals_group_replica_digest": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, _P, ctypes.POINTER(_I32)]),
     "mals_factor_digest_host": (ctypes.c_int, [_P, _I32, _I64, _I64, ctypes.POINTER(ctypes.c_uint64)]),
+    "mals_load_generation": (ctypes.c_int, [_H, ctypes.POINTER(GenerationLoad), ctypes.POINTER(GenerationResult)]),
+    "mals_generation_get_ids": (ctypes.c_int, [_H, ctypes.c_int, _P]),
+    "mals_generation_get_map": (ctypes.c_int, [_H, ctypes.c_int, _P]),
+    "mals_mark_recent": (ctypes.c_int, [_H, ctypes.c_int, _I64, _P]),
+    "mals_get_recent": (ctypes.c_int, [_H, ctypes.c_int, _P, ctypes.POINTER(_I64)]),
+    "mals_generation_hash_host": (ctypes.c_uint64, [_I64]),
+    "mals_generation_join_host": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _P]),
     "mals_group_half_iteration": (ctypes.c_int, [_H, ctypes.c_int]),
     "mals_group_factorize": (ctypes.c_int, [_H, ctypes.c_double, _I32, _I32, _I32, _P, _I32, _P, _I32,
                                             ctypes.POINTER(_I32), ctypes.POINTER(ctypes.c_double)]),

@@ -125,6 +125,27 @@ def factor_digest_host(rows, row_begin=0):
     return out.value
 
 
+def generation_hash_host(ids):
+    """mals_generation_hash_host of every id (int64) as uint64: the home slot of an id in the join's table is
+    hash & (slots - 1), slots = the smallest power of two >= max(64, 2 * n_new).  Host only."""
+    L = _lib.load()
+    return np.array([L.mals_generation_hash_host(int(i)) for i in np.asarray(ids, dtype=np.int64).ravel()], dtype=np.uint64)
+
+
+def generation_join_host(cur_ids, new_ids, recent_rows=(), flags=0):
+    """mals_generation_join_host: the id join of mals_load_generation on the host.  Returns (map int64 [n_cur]: live row ->
+    merged row, -1 = pruned; counts dict).  Raises MalsError(INVALID_ARG) for a duplicate id.  Host only."""
+    cur, new, rec = _host(cur_ids, np.int64), _host(new_ids, np.int64), _host(recent_rows, np.int64)
+    out = np.empty(len(cur), dtype=np.int64)
+    counts = np.zeros(4, dtype=np.int64)
+    rc = _lib.load().mals_generation_join_host(cur.ctypes.data_as(ctypes.c_void_p), len(cur), new.ctypes.data_as(ctypes.c_void_p), len(new),
+                                               rec.ctypes.data_as(ctypes.c_void_p), len(rec), int(flags),
+                                               out.ctypes.data_as(ctypes.c_void_p), counts.ctypes.data_as(ctypes.c_void_p))
+    if rc != _lib.OK:
+        raise MalsError(rc, "mals_generation_join_host: a duplicate id, or a recent row outside the live rows")
+    return out, {"n_merged": int(counts[0]), "n_updated": int(counts[1]), "n_kept": int(counts[2]), "n_pruned": int(counts[3])}
+
+
 def lsh_max_bits_differing(sample_ratio, num_hashes=20):
     """maxBitsDiffering of LocationSensitiveHash (LocationSensitiveHash.java:98-108) for model.lsh.sampleRatio and
     model.lsh.numHashes; may be -1.  Host only: no handle, no device."""
@@ -739,6 +760,94 @@ class ALSCore:
             self._chk(rc)
         return out, st
 
+    # -- a new generation into the live handle (GenerationLoader.loadModel) -----------------------------------------
+    def mark_recent(self, side, rows):
+        """mals_mark_recent: rows of `side` written elsewhere since the last load (recentlyActiveUsers / Items)."""
+        r = _host(rows, np.int64)
+        self._chk(self._L.mals_mark_recent(self._h, side, len(r), r.ctypes.data_as(ctypes.c_void_p) if len(r) else None))
+
+    def get_recent(self, side):
+        """mals_get_recent: the rows of `side` written since the last load, ascending."""
+        n = ctypes.c_int64(0)
+        self._chk(self._L.mals_get_recent(self._h, side, None, ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.int64)
+        if n.value:
+            self._chk(self._L.mals_get_recent(self._h, side, out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n)))
+        return out[:n.value]
+
+    def load_generation(self, cur_user_ids, cur_item_ids, new_user_ids, new_item_ids, new_X, new_Y, new_known=None,
+                        item_tag_ids=None, user_tag_ids=None, keep_not_updated=False, recompute_solvers=False):
+        """mals_load_generation: merge a new model into the generation this handle serves, by id, keeping the live rows
+        written since the last load.  cur_*_ids: the id of every live row (both numpy, or both torch CUDA int64).  The new model -- ids, X, Y, new_known =
+        (row_ptr, item_idx) over the new users or None, the two updated tag-id sets -- is all numpy or all torch CUDA
+        tensors (int64 ids and offsets, float32 rows, int32 item indices).  Returns (result dict, (merged user ids, merged
+        item ids), (user map, item map)): map[r] = the merged row of live row r, -1 = pruned."""
+        arrays = [new_user_ids, new_item_ids, new_X, new_Y] + (list(new_known) if new_known is not None else []) + \
+                 [a for a in (item_tag_ids, user_tag_ids) if a is not None]
+        device = any(_is_torch(a) for a in arrays)
+        keep = []
+
+        def ptr(a, dtype):
+            if a is None:
+                return None, 0
+            if device:
+                assert _is_torch(a) and a.is_cuda and str(a.dtype) == "torch." + np.dtype(dtype).name, "the new model: all device or all host"
+                a = a.contiguous()
+                keep.append(a)
+                return (ctypes.c_void_p(a.data_ptr()) if a.numel() else None), int(a.shape[0])
+            a = _host(a, dtype)
+            keep.append(a)
+            return (a.ctypes.data_as(ctypes.c_void_p) if a.size else None), int(a.shape[0])
+
+        cur_device = _is_torch(cur_user_ids)
+        if cur_device:     # the live ids on the device too (both)
+            assert _is_torch(cur_item_ids) and cur_user_ids.is_cuda and cur_item_ids.is_cuda and str(cur_user_ids.dtype) == str(cur_item_ids.dtype) == "torch.int64"
+            cur = [cur_user_ids.contiguous(), cur_item_ids.contiguous()]
+        else:
+            cur = [_host(cur_user_ids, np.int64), _host(cur_item_ids, np.int64)]
+        L = _lib.GenerationLoad()
+        L.struct_size = ctypes.sizeof(_lib.GenerationLoad)
+        L.flags = (_lib.GENERATION_KEEP_NOT_UPDATED if keep_not_updated else 0) | (_lib.GENERATION_RECOMPUTE_SOLVERS if recompute_solvers else 0)
+        L.features = self.features
+        L.cur_mem_kind = MEM_DEVICE if cur_device else MEM_HOST
+        L.new_mem_kind = MEM_DEVICE if device else MEM_HOST
+        for s, (ids, rows) in enumerate(((new_user_ids, new_X), (new_item_ids, new_Y))):
+            if not len(cur[s]):
+                L.cur_ids[s] = None
+            else:
+                L.cur_ids[s] = ctypes.c_void_p(cur[s].data_ptr()) if cur_device else cur[s].ctypes.data_as(ctypes.c_void_p)
+            L.n_cur[s] = len(cur[s])
+            L.new_ids[s], L.n_new[s] = ptr(ids, np.int64)
+            p, n = ptr(rows, np.float32)
+            if n != L.n_new[s] or (n and tuple(keep[-1].shape) != (n, self.features)):
+                raise ValueError("load_generation: the new rows must be n_new x features")
+            L.new_rows[s] = p
+        if new_known is not None:
+            L.new_known_ptr, n = ptr(new_known[0], np.int64)
+            if n != L.n_new[0] + 1:
+                raise ValueError("load_generation: new_known[0] holds n_new users + 1 offsets")
+            L.new_known_idx, _ = ptr(new_known[1], np.int32)
+        L.item_tag_ids, L.n_item_tag_ids = ptr(item_tag_ids, np.int64)
+        L.user_tag_ids, L.n_user_tag_ids = ptr(user_tag_ids, np.int64)
+        R = _lib.GenerationResult()
+        R.struct_size = ctypes.sizeof(_lib.GenerationResult)
+        self._chk(self._L.mals_load_generation(self._h, ctypes.byref(L), ctypes.byref(R)))
+        for side in (SIDE_X, SIDE_Y):     # the replicas and matrices are the library's own from here on
+            self._keep.pop(("F", side), None)
+            self._keep.pop(("M", side), None)
+        res = {name: (list(getattr(R, name)) if hasattr(getattr(R, name), "__len__") else getattr(R, name))
+               for name, _ in _lib.GenerationResult._fields_ if name != "struct_size"}
+        ids, maps = [], []
+        for side in (SIDE_X, SIDE_Y):
+            i = np.empty(int(R.n_merged[side]), dtype=np.int64)
+            m = np.empty(len(cur[side]), dtype=np.int64)
+            self._chk(self._L.mals_generation_get_ids(self._h, side, i.ctypes.data_as(ctypes.c_void_p)))
+            if len(m):
+                self._chk(self._L.mals_generation_get_map(self._h, side, m.ctypes.data_as(ctypes.c_void_p)))
+            ids.append(i)
+            maps.append(m)
+        return res, tuple(ids), tuple(maps)
+
     def factor_digest(self, side, row_begin=0, n_rows=None):
         """mals_factor_digest: the 64-bit digest of rows [row_begin, row_begin + n_rows) of side's replica, computed on the
         device between two writes (n_rows None: to the end).  Equals factor_digest_host of the same rows."""
@@ -803,5 +912,5 @@ class ALSCore:
         return {name: getattr(st, name) for name, _ in _lib.Stats._fields_ if name not in ("struct_size", "reserved")}
 
 
-__all__ = ["ALSCore", "HostSolver", "factor_digest_host", "MalsError", "SingularSystem", "Cancelled", "IllConditioned", "SIDE_X", "SIDE_Y",
+__all__ = ["ALSCore", "HostSolver", "factor_digest_host", "generation_hash_host", "generation_join_host", "MalsError", "SingularSystem", "Cancelled", "IllConditioned", "SIDE_X", "SIDE_Y",
            "FLAG_RECONSTRUCT_R", "FLAG_LOSS_IGNORES_UNSPECIFIED"]

@@ -12,6 +12,7 @@
 #include "topn_kernels.h"
 #include "foldin_kernels.h"
 #include "popular_kernels.h"
+#include "generation_kernels.h"
 #define MALS_FACTOR_DIGEST_KERNEL
 #include "factor_digest.h"
 #include "mals_internal.h"
@@ -247,6 +248,7 @@ struct mals_handle_s {
   // mals_most_popular_items (popular_host.h): the count cache and the tag users; the counter every call that may change a
   // counted user's set bumps (popular_touch), the same for the base CSR alone, and mals_most_popular_stats
   void* pop = nullptr;
+  void* gen = nullptr;          // mals_load_generation (generation_host.h): the recent rows, the ids and maps of the last load
   std::atomic<uint64_t> pop_epoch{1}, pop_base_epoch{1};
   std::atomic<int64_t> popular_counters[4] = {};
 };
@@ -1223,6 +1225,7 @@ namespace {
 #include "topn_host.h"
 #include "foldin_host.h"
 #include "popular_host.h"
+#include "generation_host.h"
 }  // namespace
 
 // ================================================================================================
@@ -1406,6 +1409,7 @@ int mals_destroy(mals_handle h) {
   topn_free(h);
   foldin_free(h);
   popular_free(h);
+  generation_free(h);
   delete h;   // every buffer the handle owns, with its device current
 
   return MALS_OK;
@@ -1435,6 +1439,7 @@ int mals_set_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
   s.G_valid = false;
   ++s.F_epoch;
   if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
+  generation_drop_recent(h, side);                         // ... and no rows written since the last load
   if (side == MALS_SIDE_X) popular_touch(h, false);
   if (side == MALS_SIDE_Y) h->lsh.clear();                 // ... and its rows are not the ones the candidate filter signed
   return MALS_OK;
@@ -1451,6 +1456,7 @@ int mals_bind_factors(mals_handle h, int side, float* device_ptr, int64_t n_rows
   s.G_valid = false;
   ++s.F_epoch;
   if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
+  generation_drop_recent(h, side);                         // ... and no rows written since the last load
   if (side == MALS_SIDE_X) popular_touch(h, false);
   if (side == MALS_SIDE_Y) h->lsh.clear();
   return MALS_OK;
@@ -2437,7 +2443,7 @@ static int topn_serving_ready(mals_handle h) {
   return MALS_OK;
 }
 
-static int topn_recommend_impl(mals_handle h, mals_rescorer r, const int64_t* user_idx, int32_t n_queries, int32_t how_many,
+static int topn_recommend_once(mals_handle h, mals_rescorer r, const int64_t* user_idx, int32_t n_queries, int32_t how_many,
                                int32_t consider_known_items, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
   if (!h) return MALS_INVALID_ARG;
   if (r && r->h != h) return topn_fail(h, MALS_INVALID_ARG, "the rescorer belongs to another handle");
@@ -2467,6 +2473,10 @@ static int topn_recommend_impl(mals_handle h, mals_rescorer r, const int64_t* us
   rq.n_out = n_out;
   rq.rescorer = r;
   return topn_front_submit(h, rq, n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N);
+}
+static int topn_recommend_impl(mals_handle h, mals_rescorer r, const int64_t* user_idx, int32_t n_queries, int32_t how_many,
+                               int32_t consider_known_items, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  return topn_generation_guard(h, [&]() -> int { return topn_recommend_once(h, r, user_idx, n_queries, how_many, consider_known_items, item_idx_out, score_out, n_out); });
 }
 
 int mals_recommend(mals_handle h, const int64_t* user_idx, int32_t n_queries, int32_t how_many, int32_t consider_known_items,
@@ -2543,7 +2553,7 @@ int mals_get_tag_item_count(mals_handle h, int64_t* n_out) {
   return MALS_OK;
 }
 
-static int topn_to_many_impl(mals_handle h, mals_rescorer r, const float* vectors, const int64_t* vector_ptr, int32_t n_queries, int32_t how_many,
+static int topn_to_many_once(mals_handle h, mals_rescorer r, const float* vectors, const int64_t* vector_ptr, int32_t n_queries, int32_t how_many,
                              const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out, float* score_out,
                              int32_t* n_out) {
   if (!h) return MALS_INVALID_ARG;
@@ -2581,6 +2591,11 @@ static int topn_to_many_impl(mals_handle h, mals_rescorer r, const float* vector
   return topn_front_submit(h, rq, n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N && n_vec <= 4 * TOPN_FRONT_BULK && n_ex <= (1 << 16) &&
                                       (!exclude_ptr || exclude_ptr[0] == 0));
 }
+static int topn_to_many_impl(mals_handle h, mals_rescorer r, const float* vectors, const int64_t* vector_ptr, int32_t n_queries, int32_t how_many,
+                             const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out, float* score_out,
+                             int32_t* n_out) {
+  return topn_generation_guard(h, [&]() -> int { return topn_to_many_once(h, r, vectors, vector_ptr, n_queries, how_many, exclude_ptr, exclude_idx, item_idx_out, score_out, n_out); });
+}
 
 int mals_recommend_to_many(mals_handle h, const float* vectors, const int64_t* vector_ptr, int32_t n_queries, int32_t how_many,
                            const int64_t* exclude_ptr, const int64_t* exclude_idx, int64_t* item_idx_out, float* score_out,
@@ -2602,7 +2617,7 @@ static int topn_check_items(mals_handle h, const int64_t* idx, int64_t n) {
   return MALS_OK;
 }
 
-int mals_most_similar_items(mals_handle h, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
+static int topn_most_similar_once(mals_handle h, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
                             int64_t* item_idx_out, float* score_out, int32_t* n_out) {
   if (!h) return MALS_INVALID_ARG;
   SideState& y = h->side[MALS_SIDE_Y];
@@ -2639,8 +2654,12 @@ int mals_most_similar_items(mals_handle h, const int64_t* item_idx, const int64_
   // a small call is folded into a pass with other callers' mostSimilarItems calls
   return topn_front_submit(h, rq, n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N && item_ptr[n_queries] <= 4 * TOPN_FRONT_BULK);
 }
+int mals_most_similar_items(mals_handle h, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
+                            int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  return topn_generation_guard(h, [&]() -> int { return topn_most_similar_once(h, item_idx, item_ptr, n_queries, how_many, item_idx_out, score_out, n_out); });
+}
 
-int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_idx, int32_t n, float* out) {
+static int topn_similarity_to_once(mals_handle h, int64_t to_item, const int64_t* item_idx, int32_t n, float* out) {
   if (!h) return MALS_INVALID_ARG;
   SideState& y = h->side[MALS_SIDE_Y];
   if (!y.F || y.n_total == 0) return topn_fail(h, MALS_INVALID_ARG, "item factor replica not available");
@@ -2658,8 +2677,11 @@ int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_
   rq.sim_out = out;
   return topn_front_submit(h, rq, false);
 }
+int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_idx, int32_t n, float* out) {
+  return topn_generation_guard(h, [&]() -> int { return topn_similarity_to_once(h, to_item, item_idx, n, out); });
+}
 
-int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
+static int topn_because_once(mals_handle h, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
                              int64_t* item_idx_out, float* score_out, int32_t* n_out) {
   if (!h) return MALS_INVALID_ARG;
   SideState& x = h->side[MALS_SIDE_X];
@@ -2690,6 +2712,10 @@ int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64
   rq.score_out = score_out;
   rq.n_out = n_out;
   return topn_front_submit(h, rq, false);
+}
+int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64_t* item_idx, int32_t n_queries, int32_t how_many,
+                             int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  return topn_generation_guard(h, [&]() -> int { return topn_because_once(h, user_idx, item_idx, n_queries, how_many, item_idx_out, score_out, n_out); });
 }
 
 int mals_recommend_front_stats(mals_handle h, int64_t* out4) {
@@ -2871,6 +2897,7 @@ int mals_set_preferences(mals_handle h, int64_t n, const int64_t* user_row, cons
   std::string msg;
   const std::function<int()> fn = [&]() -> int {
     if (int rc = foldin_check_pairs(h, n, user_row, item_row, false, true, msg)) return rc;
+    generation_mark_pairs(h, n, user_row, item_row);   // doAppend (DelegateGenerationManager.java:179-186)
     return foldin_set_run(h, n, user_row, item_row, value, status_out, msg);
   };
   return foldin_exclusive(h, fn, msg, "mals_set_preferences");
@@ -2890,6 +2917,7 @@ int mals_remove_preferences(mals_handle h, int64_t n, const int64_t* user_row, c
       return MALS_INVALID_ARG;
     }
     if (int rc = foldin_check_pairs(h, n, user_row, item_row, false, true, msg)) return rc;
+    generation_mark_pairs(h, n, user_row, item_row);
     return foldin_remove_run(h, n, user_row, item_row, removed_users_out, n_removed_out, msg);
   };
   return foldin_exclusive(h, fn, msg, "mals_remove_preferences");
@@ -3125,6 +3153,95 @@ int mals_most_popular_stats(mals_handle h, int64_t* out4) {
   if (!h || !out4) return MALS_INVALID_ARG;
   for (int i = 0; i < 4; ++i) out4[i] = h->popular_counters[i].load();
   return MALS_OK;
+}
+
+// ---- loading a new generation into a live handle (generation_host.h) ------------------------------------------------------
+int mals_load_generation(mals_handle h, const mals_generation_load* load, mals_generation_result* result_out) {
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, "mals_load_generation")) return rc;
+  if (!load || load->struct_size != (int32_t)sizeof(mals_generation_load) || (result_out && result_out->struct_size != (int32_t)sizeof(mals_generation_result)))
+    return topn_fail(h, MALS_INVALID_ARG, "mals_load_generation: null argument or struct_size mismatch");
+  const mals_generation_load& L = *load;
+  bool ok = (L.cur_mem_kind == MALS_MEM_HOST || L.cur_mem_kind == MALS_MEM_DEVICE) && (L.new_mem_kind == MALS_MEM_HOST || L.new_mem_kind == MALS_MEM_DEVICE);
+  for (int sd = 0; sd < 2 && ok; ++sd)
+    ok = L.n_cur[sd] >= 0 && L.n_new[sd] >= 0 && (L.n_cur[sd] == 0 || L.cur_ids[sd]) && (L.n_new[sd] == 0 || (L.new_ids[sd] && L.new_rows[sd])) &&
+         L.n_cur[sd] < ((int64_t)1 << 31) && L.n_new[sd] < ((int64_t)1 << 31);
+  ok = ok && L.n_item_tag_ids >= 0 && L.n_user_tag_ids >= 0 && (L.n_item_tag_ids == 0 || L.item_tag_ids) && (L.n_user_tag_ids == 0 || L.user_tag_ids);
+  if (!ok) return topn_fail(h, MALS_INVALID_ARG, "mals_load_generation: bad arguments (mem kinds, counts in [0, 2^31), null arrays)");
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    if (int rc = generation_load_run(h, L, result_out, msg)) return rc;
+    if (L.flags & MALS_GENERATION_RECOMPUTE_SOLVERS) {   // Generation.recomputeState: the solvers of the merged X and Y
+      int first = MALS_OK;
+      mals_solver sv[2] = {nullptr, nullptr};
+      for (int sd = 0; sd < 2 && first == MALS_OK; ++sd) first = mals_recompute_solver(h, sd, &sv[sd], nullptr);
+      for (int sd = 0; sd < 2 && first == MALS_OK; ++sd) {
+        std::string why;
+        first = foldin_solver_install(h, sd, sv[sd], foldin_solver_ipiv(sv[sd], h->cfg.features), why);
+      }
+      for (mals_solver s : sv)
+        if (s) (void)mals_solver_destroy(s);
+      if (result_out) result_out->solver_status = first;
+    }
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_load_generation");
+}
+
+static int generation_get_impl(mals_handle h, int side, bool ids, int64_t* out, const char* call) {
+  CHECK_SIDE(h, side);
+  if (!out) return topn_fail(h, MALS_INVALID_ARG, "the output array must not be NULL");
+  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int { return generation_get(h, side, ids, out, msg); };
+  return foldin_exclusive(h, fn, msg, call);
+}
+int mals_generation_get_ids(mals_handle h, int side, int64_t* ids_out) { return generation_get_impl(h, side, true, ids_out, "mals_generation_get_ids"); }
+int mals_generation_get_map(mals_handle h, int side, int64_t* map_out) { return generation_get_impl(h, side, false, map_out, "mals_generation_get_map"); }
+
+int mals_mark_recent(mals_handle h, int side, int64_t n, const int64_t* rows) {
+  CHECK_SIDE(h, side);
+  if (n < 0 || (n > 0 && !rows)) return topn_fail(h, MALS_INVALID_ARG, "mals_mark_recent: bad arguments");
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    const int64_t n_rows = h->side[side].F ? h->side[side].n_total : 0;
+    for (int64_t t = 0; t < n; ++t)
+      if (rows[t] < 0 || rows[t] >= n_rows) {
+        msg = "row " + std::to_string(t) + " is outside the replica";
+        return MALS_INVALID_ARG;
+      }
+    for (int64_t t = 0; t < n; ++t) generation_mark(h, side, rows[t]);
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_mark_recent");
+}
+
+int mals_get_recent(mals_handle h, int side, int64_t* rows_out, int64_t* n_out) {
+  CHECK_SIDE(h, side);
+  if (!n_out) return topn_fail(h, MALS_INVALID_ARG, "mals_get_recent: n_out must not be NULL");
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int {
+    const std::vector<uint32_t>& b = generation_state(h)->recent[side];
+    const int64_t n_rows = h->side[side].F ? h->side[side].n_total : 0;   // (rows_out holds the replica's rows: never more)
+    int64_t n = 0;
+    for (size_t w = 0; w < b.size(); ++w)
+      for (uint32_t bits = b[w]; bits; bits &= bits - 1) {
+        const int64_t row = (int64_t)w * 32 + __builtin_ctz(bits);
+        if (row >= n_rows) continue;
+        if (rows_out) rows_out[n] = row;
+        ++n;
+      }
+    *n_out = n;
+    return MALS_OK;
+  };
+  return foldin_exclusive(h, fn, msg, "mals_get_recent");
+}
+
+uint64_t mals_generation_hash_host(int64_t id) { return gen_hash(id); }
+
+int mals_generation_join_host(const int64_t* cur_ids, int64_t n_cur, const int64_t* new_ids, int64_t n_new, const int64_t* recent_rows,
+                              int64_t n_recent, int32_t flags, int64_t* map_out, int64_t* counts_out) {
+  return generation_join_host(cur_ids, n_cur, new_ids, n_new, recent_rows, n_recent, flags, map_out, counts_out);
 }
 
 }  // extern "C"

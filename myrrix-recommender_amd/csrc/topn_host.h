@@ -966,9 +966,59 @@ struct TopnFront {
   std::vector<uint8_t> failed;
   // counters (mals_recommend_front_stats)
   uint64_t calls = 0, queries = 0, passes = 0, bulk_calls = 0;
+  // mals_load_generation replaces the rows a request's indices were checked against (generation_host.h): odd while a swap
+  // writes the handle, two more after every swap.  A request carries the value its entry point read BEFORE its argument
+  // checks (topn_generation_guard); one that reaches the queue with another value, or waits in it across a swap, is handed
+  // back with TOPN_RETRY and its entry point checks it again against the new generation.
+  std::atomic<uint64_t> gen_seq{0};
+  TopnFrontPass stale;   // the requests a swap hands back (topn_generation_swap_end)
 };
+constexpr int TOPN_RETRY = -1000;   // internal: never leaves the library
 
 TopnFront* topn_front(mals_handle h) { return static_cast<TopnFront*>(h->tn_front); }
+
+struct TopnGenStamp {
+  mals_handle h = nullptr;
+  uint64_t seq = 0;
+};
+thread_local TopnGenStamp t_gen_stamp;
+
+// an entry point of the readers: `call` = its argument checks and its topn_front_submit
+template <class F>
+int topn_generation_guard(mals_handle h, F&& call) {
+  if (!h) return call();
+  TopnFront* f = topn_front(h);
+  for (;;) {
+    const uint64_t seq = f->gen_seq.load(std::memory_order_acquire);
+    if (seq & 1) {   // a swap is writing the handle
+      std::this_thread::yield();
+      continue;
+    }
+    t_gen_stamp = {h, seq};
+    const int rc = call();
+    t_gen_stamp = {nullptr, 0};
+    if (rc == TOPN_RETRY) continue;
+    if (rc != MALS_OK && f->gen_seq.load(std::memory_order_acquire) != seq) continue;   // (the checks may have read a handle in mid-swap)
+    return rc;
+  }
+}
+
+// THE CHECKS AND THE SWAP.  The argument checks read plain fields of the handle (SideState::F, n_total, n_local, known_ptr,
+// known_rows, tag_bits_items ...) on the caller's thread while a swap may be writing them: a sequence lock over data that is
+// not atomic, which the language calls a data race.  What makes it sound here: the fields are aligned words, read once each
+// and only compared (no pointer among them is followed before the ticket runs), a check that saw a mixture can only come
+// out wrong in a call whose sequence number no longer matches, and every such call is checked again -- a request is never
+// RUN on the strength of a check that overlapped a swap.  mals_grow_factor_rows has always changed n_total under the same
+// readers.
+// mals_load_generation, leader only, mutex NOT held.  Before the swap, and fallible: room for the list of the requests that
+// topn_generation_swap_end hands back (they are in the queue by now: one that arrives later is refused at the door) ...
+void topn_generation_swap_reserve(mals_handle h) {
+  TopnFront* f = topn_front(h);
+  std::lock_guard<std::mutex> lk(f->mu);
+  f->stale.tickets.reserve(f->queue.size());
+}
+// ... before the first write of the swap ...
+void topn_generation_swap_begin(mals_handle h) { topn_front(h)->gen_seq.fetch_add(1, std::memory_order_acq_rel); }
 
 // leader only, mutex NOT held: the pass in `fp` (already filled) onto slot s
 int topn_front_enqueue(mals_handle h, TopnWorkspace* w, int s, TopnFrontPass& fp) {
@@ -1021,6 +1071,25 @@ void topn_front_complete(TopnFrontPass& fp, int rc, const std::string& err) {  /
       if (!t->is_leader) topn_signal(t, TOPN_SIG_DONE);   // (after this the ticket may be gone)
   }
   fp.tickets.clear();
+}
+
+// ... and after its last: the requests that waited in the queue across the swap were checked against the old generation --
+// each goes back to its entry point (the calls of foldin_host.h check their arguments inside their own ticket and stay)
+void topn_generation_swap_end(mals_handle h) {
+  TopnFront* f = topn_front(h);
+  std::lock_guard<std::mutex> lk(f->mu);
+  f->gen_seq.fetch_add(1, std::memory_order_acq_rel);
+  TopnFrontPass& stale = f->stale;
+  stale.tickets.clear();
+  // (requests that came while the swap ran were refused by topn_front_submit: these all fit what _reserve made room for)
+  auto first_stale = std::stable_partition(f->queue.begin(), f->queue.end(), [](const TopnTicket* t) { return t->rq.kind == TOPN_KIND_CALL; });
+  for (auto it = first_stale; it != f->queue.end(); ++it) {
+    stale.tickets.push_back(*it);
+    --f->calls;   // its entry point submits it again: one call, counted once
+    f->queries -= (uint64_t)(*it)->rq.n_queries;
+  }
+  f->queue.erase(first_stale, f->queue.end());
+  if (!stale.tickets.empty()) topn_front_complete(stale, TOPN_RETRY, "");
 }
 
 // a caller on its way out: the pass-mates the leader left to it, then its own ticket's last visitors
@@ -1187,6 +1256,7 @@ int topn_front_submit(mals_handle h, const TopnRequest& rq, bool fold) {
   me.fold = fold;
   TopnFront* f = topn_front(h);
   std::unique_lock<std::mutex> lk(f->mu);
+  if (rq.kind != TOPN_KIND_CALL && t_gen_stamp.h == h && t_gen_stamp.seq != f->gen_seq.load(std::memory_order_acquire)) return TOPN_RETRY;
   ++f->calls;
   f->queries += (uint64_t)rq.n_queries;
   f->queue.push_back(&me);
@@ -1216,7 +1286,7 @@ int topn_front_submit(mals_handle h, const TopnRequest& rq, bool fold) {
     lk.lock();
   }
   const int rc = me.rc;
-  if (rc != MALS_OK) h->err = me.err;
+  if (rc != MALS_OK && rc != TOPN_RETRY) h->err = me.err;   // (a request handed back is no failure: it is submitted again)
   lk.unlock();
   topn_ticket_leave(me);
   return rc;
