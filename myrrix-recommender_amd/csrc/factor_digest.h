@@ -2,7 +2,7 @@
 // mals_factor_digest_host; defined in include/myrrix_als.h): the sum modulo 2^64 over the elements of the range of
 // factor_digest_term(j, bits), j = the element's global flat index row * features + f, bits = its 32 bits.  A sum: any
 // grid, any reduction tree and any split into ranges give the same number.  The arithmetic lives here once, for the host
-// (mals_group.cpp) and for the device kernel below (mals_api.hip).
+// (mals_group.cpp) and for the device kernel below (mals_serving.hip).
 #pragma once
 #include <stdint.h>
 
@@ -28,7 +28,7 @@ MALS_DIGEST_HD inline uint64_t factor_digest_finish(uint64_t z) {
 
 MALS_DIGEST_HD inline uint64_t factor_digest_term(uint64_t j, uint32_t bits) { return factor_digest_finish(j * DIGEST_MUL_INDEX + bits); }
 
-#if defined(MALS_FACTOR_DIGEST_KERNEL)   // (mals_api.hip: every kernel lives in one translation unit)
+#if defined(MALS_FACTOR_DIGEST_KERNEL)   // (mals_serving.hip: every kernel lives in one translation unit)
 // One streaming pass over the elements [e0, e1) of F (flat indices; F = the replica's first element).  The range is cut at
 // the 16-byte boundaries of the ADDRESS: block 0 takes the elements before the first and after the last whole float4 one by
 // one, every block strides over the float4s in between.  j * DIGEST_MUL_INDEX is carried along by additions (exact modulo

@@ -1,6 +1,6 @@
 // foldin_host.h -- host side of the online write path (mals_set_preferences, mals_remove_preferences,
 // mals_grow_factor_rows, the fold-in reads; include/myrrix_als.h; kernels in foldin_kernels.h).  Included by
-// mals_api.hip inside its anonymous namespace, after topn_host.h: every call here runs as an exclusive ticket of the
+// mals_serving.hip inside its anonymous namespace, after topn_host.h: every call here runs as an exclusive ticket of the
 // serving front (topn_front_submit), so the passes formed before it have finished and the passes formed after it wait
 // for its work on the handle's stream (ev_begin), and the state below is only ever touched by the front's leader.
 #pragma once
@@ -44,29 +44,29 @@ struct FoldinState {
 };
 
 FoldinState* foldin_state(mals_handle h) {
-  if (!h->fo) {
+  if (!h->serving->fo) {
     FoldinState* fs = new FoldinState();
     double t = 1e8;
     while (!(std::sqrt(t) > 1e4)) t = std::nextafter(t, std::numeric_limits<double>::infinity());
     fs->big_total = t;
-    h->fo = fs;
+    h->serving->fo = fs;
   }
-  return static_cast<FoldinState*>(h->fo);
+  return h->serving->fo;
 }
 
 void foldin_free(mals_handle h) {
-  FoldinState* fs = static_cast<FoldinState*>(h->fo);
+  FoldinState* fs = h->serving->fo;
   if (fs)
     for (hipEvent_t e : fs->ev)
       if (e) (void)hipEventDestroy(e);
   delete fs;
-  h->fo = nullptr;
+  h->serving->fo = nullptr;
 }
 
 // a new generation (mals_set_known_items, mals_set_matrix of side X, mals_set_factor_rows / mals_bind_factors of X)
 void foldin_drop_overlay(mals_handle h) {
   h->grown_users_end.store(-1, std::memory_order_release);
-  FoldinState* fs = static_cast<FoldinState*>(h->fo);
+  FoldinState* fs = h->serving->fo;
   if (!fs) return;
   std::vector<uint32_t>().swap(fs->head);
   std::vector<std::pair<int32_t, uint32_t>>().swap(fs->pool);
@@ -88,7 +88,7 @@ int64_t foldin_user_rows_end(mals_handle h) {
 }
 
 bool foldin_has_overlay(mals_handle h) {
-  const FoldinState* fs = static_cast<const FoldinState*>(h->fo);
+  const FoldinState* fs = h->serving->fo;
   return (fs && (!fs->pool.empty() || !fs->replaced.empty())) || h->grown_users_end.load(std::memory_order_acquire) >= 0 ||
          foldin_base_rows(h) < h->side[MALS_SIDE_X].n_local;
 }
@@ -97,7 +97,7 @@ bool foldin_has_overlay(mals_handle h) {
 // possibly repeated) and whether the base row is dropped (a replaced set, or a grown row the base CSR does not have)
 bool foldin_known_view(mals_handle h, int64_t local_row, std::vector<int64_t>& out) {
   bool drop = local_row >= foldin_base_rows(h);
-  const FoldinState* fs = static_cast<const FoldinState*>(h->fo);
+  const FoldinState* fs = h->serving->fo;
   if (!fs) return drop;
   if (!fs->replaced.empty()) {
     auto it = fs->replaced.find(local_row);

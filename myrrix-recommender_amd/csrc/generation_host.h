@@ -1,5 +1,5 @@
 // generation_host.h -- host side of mals_load_generation, mals_mark_recent / mals_get_recent and the mals_generation_*
-// calls (include/myrrix_als.h; kernels in generation_kernels.h).  Included by mals_api.hip inside its anonymous namespace,
+// calls (include/myrrix_als.h; kernels in generation_kernels.h).  Included by mals_serving.hip inside its anonymous namespace,
 // after popular_host.h: the load runs as ONE exclusive ticket of the serving front (foldin_exclusive), so the passes formed
 // before it read the old generation, the passes formed after it the new one, and the state below is only ever touched by
 // the front's leader.
@@ -19,19 +19,19 @@ struct GenerationState {
 };
 
 GenerationState* generation_state(mals_handle h) {
-  if (!h->gen) h->gen = new GenerationState();
-  return static_cast<GenerationState*>(h->gen);
+  if (!h->serving->gen) h->serving->gen = new GenerationState();
+  return h->serving->gen;
 }
 
 void generation_free(mals_handle h) {
-  delete static_cast<GenerationState*>(h->gen);
-  h->gen = nullptr;
+  delete h->serving->gen;
+  h->serving->gen = nullptr;
 }
 
 // the rows of a side were replaced by rows that are not theirs (mals_set_factor_rows, mals_bind_factors): what was written
 // to the old ones says nothing about the new
 void generation_drop_recent(mals_handle h, int side) {
-  if (h->gen) std::vector<uint32_t>().swap(static_cast<GenerationState*>(h->gen)->recent[side]);
+  if (h->serving->gen) std::vector<uint32_t>().swap(h->serving->gen->recent[side]);
 }
 
 // inside a ticket: doAppend's recentlyActiveUsers.add(userID) / recentlyActiveItems.add(itemID)
@@ -389,7 +389,7 @@ void generation_swap(mals_handle h, GenPrepared& p) {
     std::vector<uint32_t>().swap(gs.recent[sd]);   // recentlyActiveUsers.clear() / recentlyActiveItems.clear() (:97-98)
   }
   gs.loaded = true;
-  clear_known_items(h);   // the live base and overlay (the kept users' sets were read from them before)
+  malsi_clear_known_items(h);   // the live base and overlay (the kept users' sets were read from them before)
   popular_new_generation(h, true);
   SideState& x = h->side[MALS_SIDE_X];
   if (p.install_known) {
@@ -401,7 +401,7 @@ void generation_swap(mals_handle h, GenPrepared& p) {
     x.n_local = h->known_rows;
     // the kept users: rows past the base CSR with a whole set of their own, as grown users are after a removal
     if (p.side[MALS_SIDE_X].n_kept > 0) {
-      foldin_state(h)->replaced.swap(p.kept_sets);   // (clear_known_items left it empty)
+      foldin_state(h)->replaced.swap(p.kept_sets);   // (malsi_clear_known_items left it empty)
       h->grown_users_end.store(x.n_total, std::memory_order_release);
     }
   }
@@ -498,7 +498,7 @@ int generation_load_body(mals_handle h, const mals_generation_load& L, mals_gene
     // itemTagIDs: user-side ids -> the tag users of mals_most_popular_items
     const GenerationState& gs = *generation_state(h);
     std::vector<int64_t> live, live_mapped;
-    if (h->pop)
+    if (h->serving->pop)
       for (int64_t r : popular_state(h)->tag_users)
         if (keep_all || generation_is_recent(gs.recent[MALS_SIDE_X], r)) live.push_back(r);
     if (int rc = generation_map_rows(h, gx, live, live_mapped, msg)) return rc;
@@ -587,7 +587,7 @@ int generation_load_run(mals_handle h, const mals_generation_load& L, mals_gener
 
 // the ids / the map of the last load, to the host
 int generation_get(mals_handle h, int side, bool ids, int64_t* out, std::string& msg) {
-  GenerationState* gs = static_cast<GenerationState*>(h->gen);
+  GenerationState* gs = h->serving->gen;
   if (!gs || !gs->loaded) {
     msg = "no generation was loaded into this handle (mals_load_generation)";
     return MALS_INVALID_ARG;

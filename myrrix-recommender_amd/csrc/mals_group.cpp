@@ -1,5 +1,5 @@
 // mals_group.cpp -- the multi-GPU half-iteration of include/myrrix_als.h, built
-// entirely on the per-GPU C-ABI of mals_api.hip plus streams, events and the exchange.
+// entirely on the per-GPU C-ABI of mals_api.hip and mals_serving.hip plus streams, events and the exchange.
 //
 // The reference runs one process with N worker threads, every output row written by exactly one of
 // them (ALS:391-410, ALS:497-499); here the workers are GPUs, a row belongs to the rank whose slice
@@ -1452,7 +1452,7 @@ int mals_group_factorize(mals_group g, double convergence_threshold, int32_t max
 
 }  // extern "C"
 
-// ---- the online write path and the fold-in reads on a group (include/myrrix_als.h; the members' side: mals_api.hip) ----
+// ---- the online write path and the fold-in reads on a group (include/myrrix_als.h; the members' side: mals_serving.hip) ----
 namespace {
 
 // what every twin checks first: a group all of whose ranks live in this process

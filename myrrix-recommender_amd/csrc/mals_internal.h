@@ -30,7 +30,7 @@ __attribute__((visibility("hidden"))) void malsi_set_create_error(const char* te
 __attribute__((visibility("hidden"))) void malsi_mark_group_member(mals_handle h);
 }
 
-// The write path and the fold-in reads of a group (the mals_group_* twins of mals_set_preferences ...; mals_api.hip).  hs =
+// The write path and the fold-in reads of a group (the mals_group_* twins of mals_set_preferences ...; mals_serving.hip).  hs =
 // the handles of the local members; every call holds ALL their serving fronts while it enqueues each member's work and
 // then waits for each.  own (n_members + 1): member m keeps the known items of the users own[m] <= u < own[m + 1].  A
 // failure's text goes to *err.  The caller orders the writes among themselves (the group's write lock).

@@ -1,5 +1,5 @@
 // popular_host.h -- host side of mals_most_popular_items / mals_set_tag_users (include/myrrix_als.h; kernels in
-// popular_kernels.h).  Included by mals_api.hip inside its anonymous namespace, after foldin_host.h: the read runs as an
+// popular_kernels.h).  Included by mals_serving.hip inside its anonymous namespace, after foldin_host.h: the read runs as an
 // exclusive ticket of the serving front (foldin_exclusive), so the state below is only ever touched by the front's leader --
 // except the tag users, which follow the rule of mals_set_tag_items (not while calls are in flight).
 //
@@ -32,20 +32,20 @@ struct PopularState {
 };
 
 PopularState* popular_state(mals_handle h) {
-  if (!h->pop) h->pop = new PopularState();
-  return static_cast<PopularState*>(h->pop);
+  if (!h->serving->pop) h->serving->pop = new PopularState();
+  return h->serving->pop;
 }
 
 void popular_free(mals_handle h) {
-  delete static_cast<PopularState*>(h->pop);
-  h->pop = nullptr;
+  delete h->serving->pop;
+  h->serving->pop = nullptr;
 }
 
-// a new generation: the cache goes (with the overlay, clear_known_items); new_rows: the local user rows are new ones, the
+// a new generation: the cache goes (with the overlay, malsi_clear_known_items); new_rows: the local user rows are new ones, the
 // tag users named the old
 void popular_new_generation(mals_handle h, bool new_rows) {
   popular_touch(h, true);
-  PopularState* ps = static_cast<PopularState*>(h->pop);
+  PopularState* ps = h->serving->pop;
   if (!ps) return;
   ps->count.reset();
   ps->counted_epoch = 0;
@@ -89,7 +89,7 @@ int popular_count_enqueue(mals_handle h, int64_t n_items, bool* recounted, int64
   const int64_t* bptr = h->known_ptr ? h->known_ptr : x.row_ptr;
   const int32_t* bidx = h->known_ptr ? h->known_idx : x.col;
   // users whose current set is not their base row: an added chain or a replaced set (grown users have nothing else)
-  const FoldinState* fs = static_cast<const FoldinState*>(h->fo);
+  const FoldinState* fs = h->serving->fo;
   std::vector<int64_t> orows;
   if (fs) {
     for (size_t r = 0; r < fs->head.size(); ++r)

@@ -14,7 +14,7 @@
 //           eighth pass the prefix IS the how_many-th largest key and the collect pass takes exactly the keys >= it: no tie
 //           cap, nothing of the key row goes to the host.
 //   ADD     the sum of the members' partial count arrays (a group), saturating.
-// Included by mals_api.hip after topn_kernels.h (score_key, TopnRescore, topn_rs_filtered, topn_rs_affine, topn_tagged).
+// Included by mals_serving.hip after topn_kernels.h (score_key, TopnRescore, topn_rs_filtered, topn_rs_affine, topn_tagged).
 #pragma once
 
 namespace mals {

@@ -1,5 +1,5 @@
 // topn_host.h -- host side of top-N scoring (mals_recommend*, include/myrrix_als.h; kernels and the argument for
-// exactness in topn_kernels.h).  Included by mals_api.hip inside its anonymous namespace, after mals_handle_s.
+// exactness in topn_kernels.h).  Included by mals_serving.hip inside its anonymous namespace, after ServingState.
 #pragma once
 
 constexpr int TOPN_SLOTS = 6;  // passes in flight, each on its own stream (3 -> 6: 3-4 % at 64-128 queries per pass, nothing at 240)
@@ -48,7 +48,7 @@ struct TopnWorkspace {
 };
 
 void topn_free(mals_handle h) {
-  TopnWorkspace* w = static_cast<TopnWorkspace*>(h->tn_ws);
+  TopnWorkspace* w = h->serving->tn_ws;
   if (!w) return;
   for (TopnSlot& s : w->slot) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
@@ -57,7 +57,7 @@ void topn_free(mals_handle h) {
   }
   if (w->ev_begin) (void)hipEventDestroy(w->ev_begin);
   delete w;   // and its buffers
-  h->tn_ws = nullptr;
+  h->serving->tn_ws = nullptr;
 }
 
 struct TopnOut {
@@ -809,8 +809,8 @@ int topn_similarity_to_run(mals_handle h, const TopnRequest& rq) {
 }
 
 int topn_run(mals_handle h, const TopnRequest& rq) {
-  if (!h->tn_ws) h->tn_ws = new TopnWorkspace();
-  TopnWorkspace* w = static_cast<TopnWorkspace*>(h->tn_ws);
+  if (!h->serving->tn_ws) h->serving->tn_ws = new TopnWorkspace();
+  TopnWorkspace* w = h->serving->tn_ws;
   if (rq.kind == TOPN_KIND_BECAUSE) return topn_because_run(h, w, rq);
   if (rq.kind == TOPN_KIND_SIMILARITY_TO) return topn_similarity_to_run(h, rq);
   if (rq.kind == TOPN_KIND_CALL) return (*rq.call)();
@@ -975,7 +975,7 @@ struct TopnFront {
 };
 constexpr int TOPN_RETRY = -1000;   // internal: never leaves the library
 
-TopnFront* topn_front(mals_handle h) { return static_cast<TopnFront*>(h->tn_front); }
+TopnFront* topn_front(mals_handle h) { return h->serving->tn_front; }
 
 struct TopnGenStamp {
   mals_handle h = nullptr;
@@ -1108,8 +1108,8 @@ void topn_ticket_leave(TopnTicket& me) {
 
 // The calling thread leads until its own ticket is answered.
 void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& lk, TopnTicket* me) {
-  if (!h->tn_ws) h->tn_ws = new TopnWorkspace();
-  TopnWorkspace* w = static_cast<TopnWorkspace*>(h->tn_ws);
+  if (!h->serving->tn_ws) h->serving->tn_ws = new TopnWorkspace();
+  TopnWorkspace* w = h->serving->tn_ws;
   const int k_tiles = topn_max_tiles((h->cfg.features + 31) / 32);
   auto finish_oldest = [&]() {
     const int s = f->oldest;
