@@ -99,4 +99,20 @@ using DeviceBuffer = HipBuffer<T, DeviceMemory>;
 template <typename T>
 using PinnedBuffer = HipBuffer<T, PinnedMemory>;
 
+// the two events around a timed stretch of a stream, destroyed with their holder on whichever path it is left
+struct EventPair {
+  hipEvent_t begin = nullptr, end = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    if (begin) (void)hipEventDestroy(begin);
+    if (end) (void)hipEventDestroy(end);
+  }
+  hipError_t create() {
+    const hipError_t e = hipEventCreate(&begin);
+    return e != hipSuccess ? e : hipEventCreate(&end);
+  }
+};
+
 }  // namespace mals

@@ -1,17 +1,18 @@
-// ingest_big_host.h -- mals_ingest_finish for more records than ONE sort pipeline holds (included by ingest_api.hip).
+// ingest_big_host.h -- mals_ingest_finish for more records than ONE sort pipeline holds (host code of ingest_api.hip).
+// Expects before it: ingest_host.h (the ingest object, Scratch, finish_range, finish_tags) and ingest_big_kernels.h.
 //
-// The pipeline of ingest_api.hip sorts all records at once: 32-bit positions, 52 bytes of workspace per record -- 2^31
+// The one-shot pipeline sorts all records at once: 32-bit positions, 52 bytes of workspace per record -- 2^31
 // records at most, and 5e9 records (C5: InputFilesReader.readInputFiles, IFR:64-211, is the one entry point of every
 // configuration) would need 260 GB beside 120 GB of records.  Here the same result is assembled from pieces that each fit:
 //
 //   1. the records are cut into P <= 250 ranges of USER id (splitters from a sorted sample of 65536 user ids, exact sizes
 //      counted, P raised until every range fits `part_cap` records); a byte per record says which range it belongs to;
 //   2. range by range, in ascending id order: the range's records are compacted (stable: stream order kept) into a
-//      partition buffer and go through the unchanged stages of the one-shot pipeline -- composite stable sort by (user id,
-//      item id), per-pair replay (MU:64-125, FBIFM:129-138), removeSmall (IFR:200-211).  Users of different ranges are
-//      different users, so the range's user table, row pointers and surviving entries are final up to their offsets, which
-//      are the running totals.  Items are shared between ranges: a range keeps its own ascending item table, its liveness
-//      flags and writes the entries' columns as LOCAL item ranks;
+//      partition buffer and go through the unchanged stages of the one-shot pipeline (finish_range) -- composite stable sort
+//      by (user id, item id), per-pair replay (MU:64-125, FBIFM:129-138), removeSmall (IFR:200-211).  Users of different
+//      ranges are different users, so the range's user table, row pointers and surviving entries are final up to their
+//      offsets, which are the running totals.  Items are shared between ranges: a range keeps its own ascending item table,
+//      its liveness flags and writes the entries' columns as LOCAL item ranks;
 //   3. the ranges' item tables are merged into one ascending table (binary-search merges, no sort), liveness is OR-ed
 //      through the rank maps, the dense item index is the scan of it, and every range's columns are renumbered in place;
 //   4. R^T: entries per item counted with atomics (an item's count is bounded by the users: no overflow), offsets by a
@@ -23,268 +24,6 @@
 // the oracle suites through this path with a partition capacity of a few hundred records).
 #pragma once
 
-namespace mals {
-
-constexpr int BIG_TILE = 2048;  // records (or entries) per workgroup of the selection kernels: 256 threads x 8
-
-// part[i] = number of splitters <= user_ids[i] (splitters ascending and distinct): equal ids share a range, ranges ascend
-__global__ void big_assign_part_kernel(const int64_t* __restrict__ user_ids, int64_t n, const int64_t* __restrict__ splitters, int n_split,
-                                       uint8_t* __restrict__ part) {
-  MALS_GRID_STRIDE(i, n) {
-    const int64_t u = user_ids[i];
-    int lo = 0, hi = n_split;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (splitters[mid] <= u) lo = mid + 1; else hi = mid;
-    }
-    part[i] = (uint8_t)lo;
-  }
-}
-// records per range, all ranges in one read: hist[256] (block-private LDS counts, then global atomics)
-__global__ __launch_bounds__(256) void big_part_histogram_kernel(const uint8_t* __restrict__ part, int64_t n, unsigned long long* __restrict__ hist) {
-  __shared__ unsigned h[256];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  MALS_GRID_STRIDE(i, n) atomicAdd(&h[part[i]], 1u);
-  __syncthreads();
-  if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)h[threadIdx.x]);
-}
-// tile_counts[t] = records of range p in tile t
-// (a thread's 8 range bytes are ONE 8-byte load -- the array is padded past n --, a thread's 8 columns two 16-byte loads:
-// eight strided 1- or 4-byte loads per thread ran these kernels at 0.2-0.9 TB/s)
-__device__ __forceinline__ unsigned big_match8(const uint8_t* __restrict__ part, int64_t b, int64_t n, uint8_t p, bool (&m)[8]) {
-  const uint64_t w = b < n ? *reinterpret_cast<const uint64_t*>(part + b) : 0ull;
-  unsigned c = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    m[j] = b + j < n && (uint8_t)(w >> (8 * j)) == p;
-    c += m[j] ? 1u : 0u;
-  }
-  return c;
-}
-__device__ __forceinline__ void big_load8(const int32_t* __restrict__ col, int64_t e, int64_t nnz, int32_t (&c)[8]) {
-  if (e + 8 <= nnz) {
-    const int4 lo = *reinterpret_cast<const int4*>(col + e), hi = *reinterpret_cast<const int4*>(col + e + 4);
-    c[0] = lo.x, c[1] = lo.y, c[2] = lo.z, c[3] = lo.w, c[4] = hi.x, c[5] = hi.y, c[6] = hi.z, c[7] = hi.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) c[j] = e + j < nnz ? col[e + j] : -1;
-  }
-}
-__global__ __launch_bounds__(256) void big_count_part_kernel(const uint8_t* __restrict__ part, int64_t n, uint8_t p, unsigned* __restrict__ tile_counts) {
-  const int64_t b = (int64_t)blockIdx.x * BIG_TILE + threadIdx.x * 8;
-  bool m[8];
-  const unsigned c = big_match8(part, b, n, p, m);
-  unsigned total;
-  block_exclusive_scan(c, &total);
-  if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
-}
-// the records of range p, in stream order, into the partition buffers (tile_offsets = exclusive scan of the tile counts)
-__global__ __launch_bounds__(256) void big_compact_part_kernel(const uint8_t* __restrict__ part, int64_t n, uint8_t p,
-                                                               const unsigned* __restrict__ tile_offsets, const int64_t* __restrict__ user,
-                                                               const int64_t* __restrict__ item, const float* __restrict__ value,
-                                                               int64_t* __restrict__ pu, int64_t* __restrict__ pi, float* __restrict__ pv) {
-  const int64_t b = (int64_t)blockIdx.x * BIG_TILE + threadIdx.x * 8;
-  bool m[8];
-  const unsigned c = big_match8(part, b, n, p, m);
-  unsigned pos = tile_offsets[blockIdx.x] + block_exclusive_scan(c, nullptr);
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    if (m[j]) {
-      pu[pos] = user[b + j];
-      pi[pos] = item[b + j];
-      pv[pos] = value[b + j];
-      ++pos;
-    }
-}
-// every S-th user id as a sort key
-__global__ void big_sample_kernel(const int64_t* __restrict__ user_ids, int64_t n, int64_t n_sample, uint64_t* __restrict__ keys, unsigned* __restrict__ pay) {
-  MALS_GRID_STRIDE(j, n_sample) {
-    int64_t i = (int64_t)((double)j * ((double)n / (double)n_sample));   // (any spread of positions does: it is a sample)
-    i = i < 0 ? 0 : (i >= n ? n - 1 : i);
-    keys[j] = id_to_key(user_ids[i]);
-    pay[j] = 0u;
-  }
-}
-__global__ void big_keys_to_ids_kernel(const uint64_t* __restrict__ keys, int64_t n, int64_t* __restrict__ ids) {
-  MALS_GRID_STRIDE(i, n) ids[i] = key_to_id(keys[i]);
-}
-// the kept pairs of a partition: local row (dense among the partition's live users), LOCAL item rank as the column
-__global__ void big_compact_pairs_kernel(const uint64_t* __restrict__ keys, const unsigned* __restrict__ keep, const unsigned* __restrict__ keep_scan,
-                                         const float* __restrict__ pair_val, int64_t n, const unsigned* __restrict__ new_u,
-                                         int32_t* __restrict__ row, int32_t* __restrict__ col, float* __restrict__ val) {
-  MALS_GRID_STRIDE(i, n) {
-    if (!keep[i]) continue;
-    const unsigned q = keep_scan[i];
-    row[q] = (int32_t)new_u[(unsigned)(keys[i] >> 32)];
-    col[q] = (int32_t)(unsigned)(keys[i] & 0xffffffffu);
-    if (val) val[q] = pair_val[i];
-  }
-}
-// out[r] = base + local[r]
-__global__ void big_add_base_kernel(const int64_t* __restrict__ local, int64_t n, int64_t base, int64_t* __restrict__ out) {
-  MALS_GRID_STRIDE(i, n) out[i] = base + local[i];
-}
-// ---- merging ascending id tables without a sort ------------------------------------------------------------------------
-// lower_bound of x in the ascending table
-__device__ __forceinline__ int64_t big_lower_bound(const int64_t* __restrict__ table, int64_t n, int64_t x) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (table[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-// fresh[i] = 1 where b[i] is not in a
-__global__ void big_fresh_kernel(const int64_t* __restrict__ b, int64_t nb, const int64_t* __restrict__ a, int64_t na, unsigned* __restrict__ fresh) {
-  MALS_GRID_STRIDE(i, nb) {
-    const int64_t q = big_lower_bound(a, na, b[i]);
-    fresh[i] = (q < na && a[q] == b[i]) ? 0u : 1u;
-  }
-}
-__global__ void big_compact_fresh_kernel(const int64_t* __restrict__ b, int64_t nb, const unsigned* __restrict__ fresh, const unsigned* __restrict__ fresh_scan,
-                                         int64_t* __restrict__ out) {
-  MALS_GRID_STRIDE(i, nb)
-    if (fresh[i]) out[fresh_scan[i]] = b[i];
-}
-// union of two DISJOINT ascending tables: an element's position = its own index + how many of the other table precede it
-__global__ void big_merge_place_kernel(const int64_t* __restrict__ mine, int64_t n_mine, const int64_t* __restrict__ other, int64_t n_other,
-                                       int64_t* __restrict__ out) {
-  MALS_GRID_STRIDE(i, n_mine) out[i + big_lower_bound(other, n_other, mine[i])] = mine[i];
-}
-// alive_glob[map[l]] |= alive_local[l]
-__global__ void big_mark_alive_kernel(const unsigned* __restrict__ alive_local, const int64_t* __restrict__ map, int64_t n_local,
-                                      unsigned* __restrict__ alive_glob) {
-  MALS_GRID_STRIDE(l, n_local)
-    if (alive_local[l] && __atomic_load_n(&alive_glob[map[l]], __ATOMIC_RELAXED) == 0u) alive_glob[map[l]] = 1u;
-}
-// local item rank -> dense item index of the result
-__global__ void big_final_map_kernel(const int64_t* __restrict__ map, int64_t n_local, const unsigned* __restrict__ new_i, int32_t* __restrict__ out) {
-  MALS_GRID_STRIDE(l, n_local) out[l] = (int32_t)new_i[map[l]];
-}
-__global__ void big_remap_kernel(int32_t* __restrict__ col, int64_t n, const int32_t* __restrict__ final_map) {
-  MALS_GRID_STRIDE(i, n) col[i] = final_map[col[i]];
-}
-// ---- R^T ------------------------------------------------------------------------------------------------------------------
-// entries per item, from every `stride`-th entry: the item ranges of R^T are CUT by this estimate (an exact count of all
-// entries is 5e9 atomics, a fifth of them on a few thousand popular items: 324 ms at 2.5e9 entries, a quarter of the whole
-// finish); what a range really holds is counted exactly when it is selected, and R^T's offsets come out of the sorted ranges
-__global__ void big_item_sample_kernel(const int32_t* __restrict__ col, int64_t nnz, int64_t stride, unsigned* __restrict__ cnt) {
-  const int64_t n_s = (nnz + stride - 1) / stride;
-  MALS_GRID_STRIDE(i, n_s) atomicAdd(&cnt[col[i * stride]], 1u);
-}
-// exclusive scan uint32 -> int64 offsets (out has n + 1 entries): tile sums, one block over them, apply
-__global__ __launch_bounds__(256) void big_scan64_reduce_kernel(const unsigned* __restrict__ in, int64_t n, unsigned long long* __restrict__ tile_sums) {
-  const int64_t b = (int64_t)blockIdx.x * SC_TILE + threadIdx.x * 8;
-  unsigned v[8], s = 0;
-  scan_load8(in, b, n, v);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s += v[i];   // a tile holds 2048 counts below 2^31 / 2048 each in every real input; summed in 64 bits below
-  __shared__ unsigned long long acc;
-  if (threadIdx.x == 0) acc = 0;
-  __syncthreads();
-  atomicAdd(&acc, (unsigned long long)s);
-  __syncthreads();
-  if (threadIdx.x == 0) tile_sums[blockIdx.x] = acc;
-}
-__global__ void big_scan64_sums_kernel(unsigned long long* __restrict__ sums, int64_t n_tiles, unsigned long long* __restrict__ grand_total) {
-  // one thread: a few million additions at most (n_items / 2048 tiles)
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  unsigned long long run = 0;
-  for (int64_t t = 0; t < n_tiles; ++t) {
-    const unsigned long long v = sums[t];
-    sums[t] = run;
-    run += v;
-  }
-  *grand_total = run;
-}
-__global__ __launch_bounds__(256) void big_scan64_apply_kernel(const unsigned* __restrict__ in, int64_t n, const unsigned long long* __restrict__ tile_offsets,
-                                                               const unsigned long long* __restrict__ grand_total, int64_t* __restrict__ out) {
-  const int64_t b = (int64_t)blockIdx.x * SC_TILE + threadIdx.x * 8;
-  unsigned v[8], s = 0;
-  scan_load8(in, b, n, v);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s += v[i];
-  unsigned long long pre = tile_offsets[blockIdx.x] + (unsigned long long)block_exclusive_scan(s, nullptr);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    if (b + i < n) out[b + i] = (int64_t)pre;
-    pre += v[i];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = (int64_t)*grand_total;
-}
-// tile_counts[t] = entries of tile t whose item lies in [a, b)
-__global__ __launch_bounds__(256) void big_count_items_kernel(const int32_t* __restrict__ col, int64_t nnz, int32_t a, int32_t b,
-                                                              unsigned* __restrict__ tile_counts) {
-  const int64_t e = (int64_t)blockIdx.x * BIG_TILE + threadIdx.x * 8;
-  int32_t cc[8];
-  big_load8(col, e, nnz, cc);
-  unsigned c = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) c += (cc[j] >= a && cc[j] < b) ? 1u : 0u;
-  unsigned total;
-  block_exclusive_scan(c, &total);
-  if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
-}
-// the row of entry e: the last r with row_ptr[r] <= e, searched in [lo, hi]
-__device__ __forceinline__ int64_t big_row_of(const int64_t* __restrict__ row_ptr, int64_t lo, int64_t hi, int64_t e) {
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo + 1) / 2;
-    if (row_ptr[mid] <= e) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// tile_row[t] = the row of the first entry of entry tile t (tile_row[n_tiles] = the last row): once per finish, one thread per
-// tile.  (Searched inside big_select_items_kernel by one thread per workgroup it was 50 dependent loads in front of a
-// barrier, per tile and per item range: 20 ms per range at 2.5e9 entries, a third of the finish.)
-__global__ void big_tile_rows_kernel(const int64_t* __restrict__ row_ptr, int64_t n_rows, int64_t nnz, int64_t n_tiles, int32_t* __restrict__ tile_row) {
-  MALS_GRID_STRIDE(t, n_tiles + 1)
-    tile_row[t] = (t == n_tiles || t * BIG_TILE >= nnz) ? (int32_t)(n_rows - 1) : (int32_t)big_row_of(row_ptr, 0, n_rows - 1, t * BIG_TILE);
-}
-// the selected entries, in (user, item) order, as sort keys ((item - a) << 32 | user) with the value bits as payload
-__global__ __launch_bounds__(256) void big_select_items_kernel(const int32_t* __restrict__ col, const float* __restrict__ val, int64_t nnz,
-                                                               const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ tile_row, int32_t a, int32_t b,
-                                                               const unsigned* __restrict__ tile_offsets, uint64_t* __restrict__ keys,
-                                                               unsigned* __restrict__ pay) {
-  const int64_t e0 = (int64_t)blockIdx.x * BIG_TILE;
-  const int64_t r_lo = tile_row[blockIdx.x], r_hi = tile_row[blockIdx.x + 1];
-  const int64_t e = e0 + threadIdx.x * 8;
-  int32_t cc[8];
-  big_load8(col, e, nnz, cc);
-  bool m[8];
-  unsigned c = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    m[j] = cc[j] >= a && cc[j] < b;   // (entries past nnz read as -1: outside every range)
-    c += m[j] ? 1u : 0u;
-  }
-  unsigned pos = tile_offsets[blockIdx.x] + block_exclusive_scan(c, nullptr);
-  int64_t row = -1;
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    if (m[j]) {
-      // (a thread's 8 entries are consecutive: the row only moves forward)
-      if (row < 0 || row_ptr[row + 1] <= e + j) row = big_row_of(row_ptr, row < 0 ? r_lo : row, r_hi, e + j);
-      keys[pos] = ((uint64_t)(uint32_t)(cc[j] - a) << 32) | (uint32_t)row;
-      pay[pos] = __float_as_uint(val[e + j]);
-      ++pos;
-    }
-}
-__global__ void big_transpose_write_kernel(const uint64_t* __restrict__ keys, const unsigned* __restrict__ pay, int64_t n, int32_t* __restrict__ t_row,
-                                           int32_t* __restrict__ t_col, float* __restrict__ t_val) {
-  MALS_GRID_STRIDE(i, n) {
-    t_row[i] = (int32_t)(keys[i] >> 32);          // the item, counted from the range's first
-    t_col[i] = (int32_t)(keys[i] & 0xffffffffu);  // the user
-    t_val[i] = __uint_as_float(pay[i]);
-  }
-}
-__global__ void big_add_base_inplace_kernel(int64_t* __restrict__ p, int64_t n, int64_t base) {
-  MALS_GRID_STRIDE(i, n) p[i] += base;
-}
-
-}  // namespace mals
-
-// ---- host ----------------------------------------------------------------------------------------------------------------
 namespace {
 
 struct BigPart {  // what a user range leaves behind until the items are known
@@ -299,7 +38,12 @@ struct BigPart {  // what a user range leaves behind until the items are known
 };
 
 struct BigState {
+  int64_t part_cap = 0;                   // records a user range (entries an item range) holds at most
+  int64_t n_sample = 0;                   // user ids the splitters are picked from
+  IdWidth width = {false, false};
+  std::vector<unsigned long long> hist;   // records per user range
   std::vector<BigPart> parts;
+  int64_t n_users = 0, n_items = 0, nnz = 0, n_known = 0;   // the totals, as the phases settle them
   DeviceBuffer<uint8_t> part;
   DeviceBuffer<int64_t> pu, pi;
   DeviceBuffer<float> pv;
@@ -309,12 +53,13 @@ struct BigState {
   DeviceBuffer<unsigned> alive_glob, new_i, cnt;
   DeviceBuffer<unsigned long long> sums64;
   DeviceBuffer<int32_t> tile_row;
+  int64_t sort_cap() const { return std::max<int64_t>(part_cap, n_sample); }   // what the arena's sort buffers hold
 };
 
-unsigned big_tiles(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + mals::BIG_TILE - 1) / mals::BIG_TILE); }
+Grid big_tiles(int64_t n) { return {(unsigned)std::max<int64_t>(1, (n + BIG_TILE - 1) / BIG_TILE)}; }
 
 // a = a U b for ascending tables (b's duplicates of a dropped); a is reallocated
-int big_merge_tables(mals_ingest g, Scratch& s, FinishTmp& t, DeviceBuffer<int64_t>& a, int64_t& na, const int64_t* b, int64_t nb) {
+int big_merge_tables(mals_ingest g, Scratch& s, DeviceBuffer<int64_t>& a, int64_t& na, const int64_t* b, int64_t nb) {
   if (nb == 0) return MALS_OK;
   if (na == 0) {
     ICHK(g, a.alloc((size_t)nb));
@@ -322,23 +67,21 @@ int big_merge_tables(mals_ingest g, Scratch& s, FinishTmp& t, DeviceBuffer<int64
     na = nb;
     return MALS_OK;
   }
-  hipLaunchKernelGGL(big_fresh_kernel, dim3(blocks_for(nb)), dim3(256), 0, g->stream, b, nb, a.get(), na, t.head);
-  ICHK(g, hipGetLastError());
+  ITRY(launch(g, nb, big_fresh_kernel, b, nb, a.get(), na, s.head));
   unsigned n_fresh = 0;
-  if (int rc = scan_u32(g, s, t.head, t.scan, nb, &n_fresh)) return rc;
+  ITRY(scan_u32(g, s, s.head, s.scan, nb, &n_fresh));
   if (n_fresh == 0) return MALS_OK;
   DeviceBuffer<int64_t> fresh, merged;
   ICHK(g, fresh.alloc(n_fresh));
   if (merged.alloc((size_t)(na + n_fresh)) != hipSuccess) return fail(g, MALS_OOM, "item table merge: out of device memory");
-  hipLaunchKernelGGL(big_compact_fresh_kernel, dim3(blocks_for(nb)), dim3(256), 0, g->stream, b, nb, t.head, t.scan, fresh.get());
-  hipLaunchKernelGGL(big_merge_place_kernel, dim3(blocks_for(na)), dim3(256), 0, g->stream, a.get(), na, fresh.get(), (int64_t)n_fresh, merged.get());
-  hipLaunchKernelGGL(big_merge_place_kernel, dim3(blocks_for(n_fresh)), dim3(256), 0, g->stream, fresh.get(), (int64_t)n_fresh, a.get(), na, merged.get());
-  const hipError_t e = hipGetLastError();
-  const hipError_t e2 = hipStreamSynchronize(g->stream);
+  int rc = launch(g, nb, big_compact_fresh_kernel, b, nb, s.head, s.scan, fresh.get());
+  if (!rc) rc = launch(g, na, big_merge_place_kernel, a.get(), na, fresh.get(), (int64_t)n_fresh, merged.get());
+  if (!rc) rc = launch(g, n_fresh, big_merge_place_kernel, fresh.get(), (int64_t)n_fresh, a.get(), na, merged.get());
+  const hipError_t e2 = hipStreamSynchronize(g->stream);   // (also after a failed launch: the tables below are in use until then)
   fresh.reset();
   a = std::move(merged);
   na += n_fresh;
-  ICHK(g, e);
+  ITRY(rc);
   ICHK(g, e2);
   g->bytes_moved += 24.0 * (double)nb + 16.0 * (double)na;
   return MALS_OK;
@@ -355,20 +98,10 @@ std::vector<int64_t> big_pick_splitters(const std::vector<int64_t>& sample, int 
   return sp;
 }
 
-}  // namespace
-
-static int setup_workspace(mals_ingest g, Scratch& s, FinishTmp& t, int64_t n, int64_t scan_extra);
-static int finish_tags(mals_ingest g, Scratch& s, FinishTmp& t, int64_t sort_cap);
-
-// part_cap = 0: as many records per range as the device's free memory holds (fewer ranges = fewer sweeps over the records)
-static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
-  using namespace mals;
+// The buffers of the whole finish, before the pipeline starts.  part_cap = 0: as many records per range as the device's
+// free memory holds (fewer ranges = fewer sweeps over the records).
+int big_reserve(mals_ingest g, Scratch& s, BigState& B, int64_t part_cap) {
   const int64_t n = g->n;
-  BigState B;
-  // ---- 0. ranges of user id ------------------------------------------------------------------------------------------
-  const int64_t n_sample = std::min<int64_t>(n, 65536);
-  Scratch s;
-  FinishTmp t;
   const auto t_ws = std::chrono::steady_clock::now();
   // results that are filled range by range: R by user with room for every record (entries <= records), knownItemIDs likewise
   ICHK(g, B.part.alloc((size_t)n + 8));
@@ -392,29 +125,24 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
     // (no point in a range larger than the whole input spread over two ranges)
     part_cap = std::min<int64_t>(part_cap, std::max<int64_t>(MALS_INGEST_MIN_PART, n / 2 + n / 8));
   }
+  B.part_cap = part_cap;
+  B.n_sample = std::min<int64_t>(n, 65536);
   // the workspace of one partition; the scans over all records run on tiles of 2048 (one count per tile) and the dense item
   // index is a scan over at most 2^31 items: both inside the same tile-sum buffer
-  if (int rc = setup_workspace(g, s, t, std::max<int64_t>(part_cap, n_sample), std::max<int64_t>((n + BIG_TILE - 1) / BIG_TILE, (int64_t)1 << 31))) return rc;
+  ITRY(setup_workspace(g, s, B.sort_cap(), std::max<int64_t>((n + BIG_TILE - 1) / BIG_TILE, (int64_t)1 << 31)));
   ICHK(g, B.pu.alloc((size_t)part_cap));
   ICHK(g, B.pi.alloc((size_t)part_cap));
   ICHK(g, B.pv.alloc((size_t)part_cap));
   g->last_workspace_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_ws).count();
-  ICHK(g, hipEventRecord(e0, g->stream));
+  return MALS_OK;
+}
 
-  ICHK(g, hipMemsetAsync(s.digit_tot, 0, 2 * sizeof(unsigned long long), g->stream));
-  hipLaunchKernelGGL(ids_high_bits_kernel, dim3(blocks_for(n, 256, 8192)), dim3(256), 0, g->stream, g->d_user.get(), n, s.digit_tot);
-  hipLaunchKernelGGL(ids_high_bits_kernel, dim3(blocks_for(n, 256, 8192)), dim3(256), 0, g->stream, g->d_item.get(), n, s.digit_tot + 1);
-  unsigned long long high[2] = {1, 1};
-  ICHK(g, hipMemcpyAsync(high, s.digit_tot, sizeof(high), hipMemcpyDeviceToHost, g->stream));
-  ICHK(g, hipStreamSynchronize(g->stream));
-  const bool narrow = !std::getenv("MALS_INGEST_WIDE_KEYS");
-  const bool user32 = high[0] == 0 && narrow, item32 = high[1] == 0 && narrow;
-  g->bytes_moved += 16.0 * (double)n;
-
-  hipLaunchKernelGGL(big_sample_kernel, dim3(blocks_for(n_sample)), dim3(256), 0, g->stream, g->d_user.get(), n, n_sample, s.keys[0], s.pay[0]);
-  ICHK(g, hipGetLastError());
+// ---- 0. ranges of user id: B.part says which range a record belongs to, B.hist how many records each holds --------------
+int big_plan_user_ranges(mals_ingest g, Scratch& s, BigState& B) {
+  const int64_t n = g->n, n_sample = B.n_sample, part_cap = B.part_cap;
+  ITRY(launch(g, n_sample, big_sample_kernel, g->d_user.get(), n, n_sample, s.keys[0], s.pay[0]));
   int rs = 0;
-  if (int rc = radix_sort<uint64_t, unsigned>(g, s, s.keys, s.pay, n_sample, &rs)) return rc;
+  ITRY((radix_sort<uint64_t, unsigned>(g, s, s.keys, s.pay, n_sample, &rs)));
   std::vector<int64_t> sample((size_t)n_sample);
   {
     std::vector<uint64_t> sk((size_t)n_sample);
@@ -422,111 +150,75 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
     for (size_t i = 0; i < sk.size(); ++i) sample[i] = key_to_id(sk[i]);
   }
   int n_parts = (int)std::min<int64_t>(250, std::max<int64_t>(2, (n + (part_cap * 3) / 4 - 1) / ((part_cap * 3) / 4)));
-  std::vector<unsigned long long> hist(256);
+  B.hist.assign(256, 0);
   std::vector<int64_t> splitters;
   for (int attempt = 0;; ++attempt) {
     splitters = big_pick_splitters(sample, n_parts);
     ICHK(g, hipMemcpyAsync(B.d_split.get(), splitters.data(), sizeof(int64_t) * splitters.size(), hipMemcpyHostToDevice, g->stream));
-    hipLaunchKernelGGL(big_assign_part_kernel, dim3(blocks_for(n, 256, 1 << 16)), dim3(256), 0, g->stream, g->d_user.get(), n, B.d_split.get(), (int)splitters.size(), B.part.get());
+    ITRY(launch_grid(g, {blocks_for(n, 256, 1 << 16)}, big_assign_part_kernel, g->d_user.get(), n, B.d_split.get(), (int)splitters.size(), B.part.get()));
     ICHK(g, hipMemsetAsync(s.digit_tot, 0, 256 * sizeof(unsigned long long), g->stream));
-    hipLaunchKernelGGL(big_part_histogram_kernel, dim3(blocks_for(n, 256, 1 << 14)), dim3(256), 0, g->stream, B.part.get(), n, s.digit_tot);
-    ICHK(g, hipGetLastError());
-    ICHK(g, hipMemcpyAsync(hist.data(), s.digit_tot, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
+    ITRY(launch_grid(g, {blocks_for(n, 256, 1 << 14)}, big_part_histogram_kernel, B.part.get(), n, s.digit_tot));
+    ICHK(g, hipMemcpyAsync(B.hist.data(), s.digit_tot, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
     ICHK(g, hipStreamSynchronize(g->stream));
     g->bytes_moved += 10.0 * (double)n;
     unsigned long long worst = 0;
-    for (unsigned long long c : hist) worst = std::max(worst, c);
+    for (unsigned long long c : B.hist) worst = std::max(worst, c);
     if ((int64_t)worst <= part_cap) break;
     if (n_parts >= 250 || attempt >= 8)
       return fail(g, MALS_INVALID_ARG, "ingest: the records of one user-id range do not fit a partition (" + std::to_string(worst) + " records, capacity " +
                                            std::to_string(part_cap) + "): one user id owns too many lines, or MALS_INGEST_OPT_PARTITION_RECORDS is too small");
     n_parts = std::min(250, n_parts + std::max(1, n_parts / 2));
   }
-  n_parts = (int)splitters.size() + 1;
-  g->last_partitions = n_parts;
+  g->last_partitions = (int)splitters.size() + 1;
+  B.parts.resize((size_t)g->last_partitions);
+  return MALS_OK;
+}
 
-  // ---- 1. range by range ----------------------------------------------------------------------------------------------
-  B.parts.resize((size_t)n_parts);
-  int64_t u_base = 0, nnz_base = 0, known_base = 0;
-  const unsigned n_tiles = big_tiles(n);
-  float* sorted_val = reinterpret_cast<float*>(s.pay[0]);
-  for (int p = 0; p < n_parts; ++p) {
-    BigPart& bp = B.parts[(size_t)p];
-    bp.u_base = u_base;
-    bp.nnz_base = nnz_base;
-    bp.known_base = known_base;
-    const int64_t np = (int64_t)hist[(size_t)p];
+// ---- 1. range by range: R's rows of the range's users behind those of the ranges before it, columns as local item ranks ---
+int big_finish_user_ranges(mals_ingest g, Scratch& s, BigState& B) {
+  const int64_t n = g->n;
+  const Grid n_tiles = big_tiles(n);
+  for (size_t p = 0; p < B.parts.size(); ++p) {
+    BigPart& bp = B.parts[p];
+    bp.u_base = B.n_users;   // the running totals: the range's users, entries and known items land behind them
+    bp.nnz_base = B.nnz;
+    bp.known_base = B.n_known;
+    const int64_t np = (int64_t)B.hist[p];
     bp.n_records = np;
     if (np == 0) continue;
-    hipLaunchKernelGGL(big_count_part_kernel, dim3(n_tiles), dim3(256), 0, g->stream, B.part.get(), n, (uint8_t)p, t.head);
-    ICHK(g, hipGetLastError());
+    ITRY(launch_grid(g, n_tiles, big_count_part_kernel, B.part.get(), n, (uint8_t)p, s.head));
     unsigned counted = 0;
-    if (int rc = scan_u32(g, s, t.head, t.head, (int64_t)n_tiles, &counted)) return rc;
+    ITRY(scan_u32(g, s, s.head, s.head, (int64_t)n_tiles.blocks, &counted));
     if ((int64_t)counted != np) return fail(g, MALS_HIP_ERROR, "ingest: partition size mismatch");
-    hipLaunchKernelGGL(big_compact_part_kernel, dim3(n_tiles), dim3(256), 0, g->stream, B.part.get(), n, (uint8_t)p, t.head, g->d_user.get(), g->d_item.get(), g->d_value.get(),
-                       B.pu.get(), B.pi.get(), B.pv.get());
-    ICHK(g, hipGetLastError());
+    ITRY(launch_grid(g, n_tiles, big_compact_part_kernel, B.part.get(), n, (uint8_t)p, s.head, g->d_user.get(), g->d_item.get(), g->d_value.get(), B.pu.get(),
+                     B.pi.get(), B.pv.get()));
     g->bytes_moved += 2.0 * (double)n + 48.0 * (double)np;
-    const Records rec = {B.pu.get(), B.pi.get(), B.pv.get(), np};
-    unsigned n_u_all = 0, n_i_all = 0, n_users = 0, nnz = 0;
-    FinishTmp tp;   // the range's temporaries (freed at the end of the iteration), sharing the arena views
-    tp.head = t.head; tp.scan = t.scan; tp.ri = t.ri; tp.keep = t.keep; tp.pair_val = t.pair_val; tp.coo_row = t.coo_row; tp.present = t.present;
-    int ra = 0, r = 0;
-    if (int rc = item32 ? stage_items<uint32_t>(g, s, tp, rec, user32, &ra, &n_i_all) : stage_items<uint64_t>(g, s, tp, rec, user32, &ra, &n_i_all)) return rc;
-    if (int rc = user32 ? stage_users<uint32_t>(g, s, tp, rec, ra, sorted_val, &r, &n_u_all) : stage_users<uint64_t>(g, s, tp, rec, ra, sorted_val, &r, &n_u_all))
-      return rc;
-    ICHK(g, tp.alive_u.alloc(n_u_all));
-    ICHK(g, tp.alive_i.alloc(n_i_all));
-    ICHK(g, tp.new_u.alloc(n_u_all));
-    ICHK(g, hipMemsetAsync(tp.alive_u.get(), 0, sizeof(unsigned) * (size_t)n_u_all, g->stream));
-    ICHK(g, hipMemsetAsync(tp.alive_i.get(), 0, sizeof(unsigned) * (size_t)n_i_all, g->stream));
-    hipLaunchKernelGGL(replay_pairs_kernel, dim3(blocks_for(np)), dim3(256), 0, g->stream, s.keys[r], sorted_val, np, g->zero_threshold, tp.keep, tp.pair_val,
-                       tp.alive_u.get(), tp.alive_i.get(), tp.present);
-    ICHK(g, hipGetLastError());
-    g->bytes_moved += (8.0 + 4.0 + 8.0 + (tp.present ? 4.0 : 0.0)) * (double)np;
-    if (int rc = scan_u32(g, s, tp.alive_u.get(), tp.new_u.get(), n_u_all, &n_users)) return rc;
-    if (int rc = scan_u32(g, s, tp.keep, tp.scan, np, &nnz)) return rc;
-    bp.n_users = n_users;
-    bp.nnz = nnz;
-    bp.n_items_local = n_i_all;
+    RangeTmp tp;   // the range's temporaries (freed at the end of the iteration)
+    RangeCounts c;
+    ITRY(finish_range(g, s, tp, Records{B.pu.get(), B.pi.get(), B.pv.get(), np}, B.width,
+                      RangeOut{false, bp.user_ids, bp.ptr_local, bp.known_ptr_local, bp.nnz_base, bp.known_base}, c));
+    bp.n_users = c.n_users;
+    bp.nnz = c.nnz;
+    bp.n_known = c.n_known;
+    bp.n_items_local = c.n_i_all;
     bp.item_ids = std::move(tp.iid_all);     // kept: the range's item table and its liveness
     bp.item_alive = std::move(tp.alive_i);
-    ICHK(g, bp.user_ids.alloc(std::max<size_t>(n_users, 1)));
-    ICHK(g, bp.ptr_local.alloc((size_t)n_users + 1));
-    hipLaunchKernelGGL(compact_ids_kernel, dim3(blocks_for(n_u_all)), dim3(256), 0, g->stream, tp.uid_all.get(), tp.alive_u.get(), tp.new_u.get(), (int64_t)n_u_all, bp.user_ids.get());
-    hipLaunchKernelGGL(big_compact_pairs_kernel, dim3(blocks_for(np)), dim3(256), 0, g->stream, s.keys[r], tp.keep, tp.scan, tp.pair_val, np, tp.new_u.get(),
-                       tp.coo_row, g->col[0].get() + nnz_base, g->val[0].get() + nnz_base);
-    hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(blocks_for((int64_t)nnz + 1)), dim3(256), 0, g->stream, tp.coo_row, (int64_t)nnz, (int64_t)n_users,
-                       bp.ptr_local.get());
-    ICHK(g, hipGetLastError());
-    g->bytes_moved += 16.0 * (double)np + 16.0 * (double)nnz + 8.0 * (double)n_users;
-    if (g->want_known) {
-      unsigned n_known = 0;
-      if (int rc = scan_u32(g, s, tp.present, tp.scan, np, &n_known)) return rc;
-      bp.n_known = n_known;
-      ICHK(g, bp.known_ptr_local.alloc((size_t)n_users + 1));
-      int32_t* known_row = (int32_t*)tp.ri;
-      hipLaunchKernelGGL(big_compact_pairs_kernel, dim3(blocks_for(np)), dim3(256), 0, g->stream, s.keys[r], tp.present, tp.scan, (const float*)nullptr, np,
-                         tp.new_u.get(), known_row, g->known_idx.get() + known_base, (float*)nullptr);
-      hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(blocks_for((int64_t)n_known + 1)), dim3(256), 0, g->stream, known_row, (int64_t)n_known,
-                         (int64_t)n_users, bp.known_ptr_local.get());
-      ICHK(g, hipGetLastError());
-      g->bytes_moved += (4.0 + 12.0 + 8.0) * (double)np + 12.0 * (double)n_known + 8.0 * (double)n_users;
-      known_base += n_known;
-    }
     // the merged item table grows by what this range saw for the first time
-    if (int rc = big_merge_tables(g, s, t, B.item_glob, B.n_item_glob, bp.item_ids.get(), bp.n_items_local)) return rc;
+    ITRY(big_merge_tables(g, s, B.item_glob, B.n_item_glob, bp.item_ids.get(), bp.n_items_local));
     ICHK(g, hipStreamSynchronize(g->stream));   // tp's allocations go away
-    u_base += n_users;
-    nnz_base += nnz;
-    if (u_base > (int64_t)0x7fffff00 || B.n_item_glob > (int64_t)0x7fffff00)
+    B.n_users += c.n_users;
+    B.nnz += c.nnz;
+    B.n_known += c.n_known;
+    if (B.n_users > (int64_t)0x7fffff00 || B.n_item_glob > (int64_t)0x7fffff00)
       return fail(g, MALS_INVALID_ARG, "ingest: more than 2^31 distinct users or items (dense indices are 32-bit)");
   }
-  const int64_t n_users = u_base, nnz = nnz_base, n_known = known_base;
   B.pu.reset(); B.pi.reset(); B.pv.reset(); B.part.reset();
+  return MALS_OK;
+}
 
-  // ---- 2. items: liveness through the rank maps, dense index, renumbering -------------------------------------------------
-  const int64_t n_glob = B.n_item_glob;
+// ---- 2. items: liveness through the rank maps, dense index, renumbering; the ranges' user tables and offsets into place ---
+int big_settle_items(mals_ingest g, Scratch& s, BigState& B) {
+  const int64_t n_glob = B.n_item_glob, n_users = B.n_users;
   ICHK(g, B.alive_glob.alloc(std::max<size_t>((size_t)n_glob, 1)));
   ICHK(g, B.new_i.alloc(std::max<size_t>((size_t)n_glob, 1)));
   ICHK(g, hipMemsetAsync(B.alive_glob.get(), 0, sizeof(unsigned) * std::max<size_t>((size_t)n_glob, 1), g->stream));
@@ -535,91 +227,94 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
   int32_t* final_map = reinterpret_cast<int32_t*>(s.keys[1]);
   for (BigPart& bp : B.parts) {
     if (bp.n_items_local == 0) continue;
-    hipLaunchKernelGGL(index_of_ids_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_ids.get(), bp.n_items_local, B.item_glob.get(), n_glob, map);
-    hipLaunchKernelGGL(big_mark_alive_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_alive.get(), map, bp.n_items_local, B.alive_glob.get());
-    ICHK(g, hipGetLastError());
+    ITRY(launch(g, bp.n_items_local, index_of_ids_kernel, bp.item_ids.get(), bp.n_items_local, B.item_glob.get(), n_glob, map));
+    ITRY(launch(g, bp.n_items_local, big_mark_alive_kernel, bp.item_alive.get(), map, bp.n_items_local, B.alive_glob.get()));
   }
   unsigned n_items_u = 0;
-  if (int rc = scan_u32(g, s, B.alive_glob.get(), B.new_i.get(), n_glob, &n_items_u)) return rc;
-  const int64_t n_items = n_items_u;
+  ITRY(scan_u32(g, s, B.alive_glob.get(), B.new_i.get(), n_glob, &n_items_u));
+  const int64_t n_items = B.n_items = n_items_u;
   g->n_users = n_users;
   g->n_items = n_items;
-  g->nnz = nnz;
-  g->n_known = n_known;
+  g->nnz = B.nnz;
+  g->n_known = B.n_known;
   ICHK(g, g->ids[0].alloc(std::max<size_t>((size_t)n_users, 1)));
   ICHK(g, g->ids[1].alloc(std::max<size_t>((size_t)n_items, 1)));
   ICHK(g, g->ptr[0].alloc((size_t)n_users + 1));
   ICHK(g, g->ptr[1].alloc((size_t)n_items + 1));
   if (g->want_known) ICHK(g, g->known_ptr.alloc((size_t)n_users + 1));
-  hipLaunchKernelGGL(compact_ids_kernel, dim3(blocks_for(n_glob)), dim3(256), 0, g->stream, B.item_glob.get(), B.alive_glob.get(), B.new_i.get(), n_glob, g->ids[1].get());
-  ICHK(g, hipGetLastError());
+  ITRY(launch(g, n_glob, compact_ids_kernel, B.item_glob.get(), B.alive_glob.get(), B.new_i.get(), n_glob, g->ids[1].get()));
   ICHK(g, hipMemsetAsync(g->ptr[0].get(), 0, sizeof(int64_t), g->stream));   // (no range, no user: the one offset there is)
   if (g->want_known) ICHK(g, hipMemsetAsync(g->known_ptr.get(), 0, sizeof(int64_t), g->stream));
   for (BigPart& bp : B.parts) {
     if (bp.n_records == 0) continue;
-    hipLaunchKernelGGL(index_of_ids_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, bp.item_ids.get(), bp.n_items_local, B.item_glob.get(), n_glob, map);
-    hipLaunchKernelGGL(big_final_map_kernel, dim3(blocks_for(bp.n_items_local)), dim3(256), 0, g->stream, map, bp.n_items_local, B.new_i.get(), final_map);
-    if (bp.nnz) hipLaunchKernelGGL(big_remap_kernel, dim3(blocks_for(bp.nnz)), dim3(256), 0, g->stream, g->col[0].get() + bp.nnz_base, bp.nnz, final_map);
-    if (g->want_known && bp.n_known)
-      hipLaunchKernelGGL(big_remap_kernel, dim3(blocks_for(bp.n_known)), dim3(256), 0, g->stream, g->known_idx.get() + bp.known_base, bp.n_known, final_map);
+    ITRY(launch(g, bp.n_items_local, index_of_ids_kernel, bp.item_ids.get(), bp.n_items_local, B.item_glob.get(), n_glob, map));
+    ITRY(launch(g, bp.n_items_local, big_final_map_kernel, map, bp.n_items_local, B.new_i.get(), final_map));
+    if (bp.nnz) ITRY(launch(g, bp.nnz, big_remap_kernel, g->col[0].get() + bp.nnz_base, bp.nnz, final_map));
+    if (g->want_known && bp.n_known) ITRY(launch(g, bp.n_known, big_remap_kernel, g->known_idx.get() + bp.known_base, bp.n_known, final_map));
     if (bp.n_users) ICHK(g, hipMemcpyAsync(g->ids[0].get() + bp.u_base, bp.user_ids.get(), sizeof(int64_t) * (size_t)bp.n_users, hipMemcpyDeviceToDevice, g->stream));
-    hipLaunchKernelGGL(big_add_base_kernel, dim3(blocks_for(bp.n_users + 1)), dim3(256), 0, g->stream, bp.ptr_local.get(), bp.n_users + 1, bp.nnz_base,
-                       g->ptr[0].get() + bp.u_base);
+    ITRY(launch(g, bp.n_users + 1, big_add_base_kernel, bp.ptr_local.get(), bp.n_users + 1, bp.nnz_base, g->ptr[0].get() + bp.u_base));
     if (g->want_known)
-      hipLaunchKernelGGL(big_add_base_kernel, dim3(blocks_for(bp.n_users + 1)), dim3(256), 0, g->stream, bp.known_ptr_local.get(), bp.n_users + 1, bp.known_base,
-                         g->known_ptr.get() + bp.u_base);
-    ICHK(g, hipGetLastError());
+      ITRY(launch(g, bp.n_users + 1, big_add_base_kernel, bp.known_ptr_local.get(), bp.n_users + 1, bp.known_base, g->known_ptr.get() + bp.u_base));
     g->bytes_moved += 8.0 * (double)bp.nnz + 24.0 * (double)bp.n_users;
   }
   ICHK(g, hipStreamSynchronize(g->stream));
   B.parts.clear();
   B.alive_glob.reset(); B.new_i.reset(); B.item_glob.reset();
+  return MALS_OK;
+}
 
-  // ---- 3. R^T ---------------------------------------------------------------------------------------------------------------
-  // item ranges from a sample of the entries (every 61st), cut at 0.7 of a partition; a range that turns out larger is halved
+// item ranges from a sample of the entries (every 61st), cut at 0.7 of a partition; *todo: the ranges still to do, the first
+// on top.  Leaves R^T's offsets zeroed and B.tile_row filled.
+int big_plan_item_ranges(mals_ingest g, BigState& B, std::vector<std::pair<int64_t, int64_t>>* todo) {
+  const int64_t n_items = B.n_items, nnz = B.nnz;
   ICHK(g, B.cnt.alloc((size_t)n_items + 8));
   const int64_t tiles64 = (n_items + SC_TILE - 1) / SC_TILE + 1;
   ICHK(g, B.sums64.alloc((size_t)tiles64 + 1));
   ICHK(g, hipMemsetAsync(B.cnt.get(), 0, sizeof(unsigned) * ((size_t)n_items + 8), g->stream));
   const int64_t stride = nnz > ((int64_t)1 << 24) ? 61 : 1;
-  if (nnz) hipLaunchKernelGGL(big_item_sample_kernel, dim3(blocks_for((nnz + stride - 1) / stride, 256, 1 << 16)), dim3(256), 0, g->stream, g->col[0].get(), nnz, stride, B.cnt.get());
+  if (nnz) ITRY(launch_grid(g, {blocks_for((nnz + stride - 1) / stride, 256, 1 << 16)}, big_item_sample_kernel, g->col[0].get(), nnz, stride, B.cnt.get()));
   const unsigned t64 = (unsigned)std::max<int64_t>(1, (n_items + SC_TILE - 1) / SC_TILE);
-  hipLaunchKernelGGL(big_scan64_reduce_kernel, dim3(t64), dim3(256), 0, g->stream, B.cnt.get(), n_items, B.sums64.get());
-  hipLaunchKernelGGL(big_scan64_sums_kernel, dim3(1), dim3(64), 0, g->stream, B.sums64.get(), (int64_t)t64, B.sums64.get() + t64);
-  hipLaunchKernelGGL(big_scan64_apply_kernel, dim3(t64), dim3(256), 0, g->stream, B.cnt.get(), n_items, B.sums64.get(), B.sums64.get() + t64, g->ptr[1].get());
-  ICHK(g, hipGetLastError());
+  ITRY(launch_grid(g, {t64}, big_scan64_reduce_kernel, B.cnt.get(), n_items, B.sums64.get()));
+  ITRY(launch_grid(g, {1, 64}, big_scan64_sums_kernel, B.sums64.get(), (int64_t)t64, B.sums64.get() + t64));
+  ITRY(launch_grid(g, {t64}, big_scan64_apply_kernel, B.cnt.get(), n_items, B.sums64.get(), B.sums64.get() + t64, g->ptr[1].get()));
   g->bytes_moved += 4.0 * (double)nnz / (double)stride + 16.0 * (double)n_items;
   std::vector<int64_t> cp((size_t)n_items + 1);   // estimated offsets, in sampled entries
   ICHK(g, hipMemcpyAsync(cp.data(), g->ptr[1].get(), sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost, g->stream));
   ICHK(g, hipStreamSynchronize(g->stream));
-  std::vector<std::pair<int64_t, int64_t>> todo;   // item ranges still to do, the first on top
-  {
-    const int64_t budget = std::max<int64_t>(1, (int64_t)(0.7 * (double)part_cap / (double)stride));
-    std::vector<std::pair<int64_t, int64_t>> ranges;
-    for (int64_t a = 0; a < n_items;) {
-      int64_t b = std::upper_bound(cp.begin() + a + 1, cp.end(), cp[(size_t)a] + budget) - cp.begin() - 1;
-      b = std::min(std::max(b, a + 1), n_items);
-      ranges.emplace_back(a, b);
-      a = b;
-    }
-    todo.assign(ranges.rbegin(), ranges.rend());
+  const int64_t budget = std::max<int64_t>(1, (int64_t)(0.7 * (double)B.part_cap / (double)stride));
+  std::vector<std::pair<int64_t, int64_t>> ranges;
+  for (int64_t a = 0; a < n_items;) {
+    int64_t b = std::upper_bound(cp.begin() + a + 1, cp.end(), cp[(size_t)a] + budget) - cp.begin() - 1;
+    b = std::min(std::max(b, a + 1), n_items);
+    ranges.emplace_back(a, b);
+    a = b;
   }
-  const unsigned e_tiles = big_tiles(nnz);
-  ICHK(g, B.tile_row.alloc((size_t)e_tiles + 1));
-  hipLaunchKernelGGL(big_tile_rows_kernel, dim3(blocks_for((int64_t)e_tiles + 1)), dim3(256), 0, g->stream, g->ptr[0].get(), std::max<int64_t>(n_users, 1), nnz,
-                     (int64_t)e_tiles, B.tile_row.get());
-  ICHK(g, hipGetLastError());
-  int64_t done_entries = 0;   // R^T's offsets so far: every range starts where the one before it ended
+  todo->assign(ranges.rbegin(), ranges.rend());
+  const Grid e_tiles = big_tiles(nnz);
+  ICHK(g, B.tile_row.alloc((size_t)e_tiles.blocks + 1));
+  ITRY(launch(g, (int64_t)e_tiles.blocks + 1, big_tile_rows_kernel, g->ptr[0].get(), std::max<int64_t>(B.n_users, 1), nnz, (int64_t)e_tiles.blocks, B.tile_row.get()));
   ICHK(g, hipMemsetAsync(g->ptr[1].get(), 0, sizeof(int64_t) * ((size_t)n_items + 1), g->stream));
+  return MALS_OK;
+}
+
+// ---- 3. R^T, item range by item range; a range that turns out larger than a partition is halved -----------------------------
+// (Not transpose_by_item: the range's entries are selected out of R and land behind the ranges before it -- the write
+// kernel takes the offset, the pointers of the range get a base added -- where the one-shot transpose gathers into whole
+// arrays; the sort on the item half is all the two have in common.)
+int big_transpose(mals_ingest g, Scratch& s, BigState& B) {
+  const int64_t nnz = B.nnz, part_cap = B.part_cap;
+  std::vector<std::pair<int64_t, int64_t>> todo;
+  ITRY(big_plan_item_ranges(g, B, &todo));
+  const Grid e_tiles = big_tiles(nnz);
+  int64_t done_entries = 0;   // R^T's offsets so far: every range starts where the one before it ended
   while (!todo.empty()) {
     const int64_t a = todo.back().first, b = todo.back().second;
     todo.pop_back();
     int64_t nq = 0;
     if (nnz > 0) {
-      hipLaunchKernelGGL(big_count_items_kernel, dim3(e_tiles), dim3(256), 0, g->stream, g->col[0].get(), nnz, (int32_t)a, (int32_t)b, t.head);
-      ICHK(g, hipGetLastError());
+      ITRY(launch_grid(g, e_tiles, big_count_items_kernel, g->col[0].get(), nnz, (int32_t)a, (int32_t)b, s.head));
       unsigned counted = 0;
-      if (int rc = scan_u32(g, s, t.head, t.head, (int64_t)e_tiles, &counted)) return rc;
+      ITRY(scan_u32(g, s, s.head, s.head, (int64_t)e_tiles.blocks, &counted));
       nq = counted;
       g->bytes_moved += 4.0 * (double)nnz;
     }
@@ -632,25 +327,37 @@ static int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
     }
     ++g->last_item_ranges;
     if (nq > 0) {
-      hipLaunchKernelGGL(big_select_items_kernel, dim3(e_tiles), dim3(256), 0, g->stream, g->col[0].get(), g->val[0].get(), nnz, g->ptr[0].get(), B.tile_row.get(), (int32_t)a, (int32_t)b,
-                         t.head, s.keys[0], s.pay[0]);
-      ICHK(g, hipGetLastError());
+      ITRY(launch_grid(g, e_tiles, big_select_items_kernel, g->col[0].get(), g->val[0].get(), nnz, g->ptr[0].get(), B.tile_row.get(), (int32_t)a, (int32_t)b, s.head,
+                       s.keys[0], s.pay[0]));
       int r2 = 0;
-      if (int rc = radix_sort<uint64_t, unsigned>(g, s, s.keys, s.pay, nq, &r2, 4, ((uint64_t)(b - a - 1) << 32) | 0xffffffffull)) return rc;
-      hipLaunchKernelGGL(big_transpose_write_kernel, dim3(blocks_for(nq)), dim3(256), 0, g->stream, s.keys[r2], s.pay[r2], nq, t.coo_row, g->col[1].get() + done_entries,
-                         g->val[1].get() + done_entries);
-      ICHK(g, hipGetLastError());
+      ITRY((radix_sort<uint64_t, unsigned>(g, s, s.keys, s.pay, nq, &r2, 4, ((uint64_t)(b - a - 1) << 32) | 0xffffffffull)));
+      ITRY(launch(g, nq, big_transpose_write_kernel, s.keys[r2], s.pay[r2], nq, s.coo_row, g->col[1].get() + done_entries, g->val[1].get() + done_entries));
       g->bytes_moved += 4.0 * (double)nnz + 40.0 * (double)nq;
     }
     // offsets of the range's items: local from the sorted item column, then shifted behind the ranges before it
-    hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(blocks_for(nq + 1)), dim3(256), 0, g->stream, t.coo_row, nq, b - a, g->ptr[1].get() + a);
-    hipLaunchKernelGGL(big_add_base_inplace_kernel, dim3(blocks_for(b - a + 1)), dim3(256), 0, g->stream, g->ptr[1].get() + a, b - a + 1, done_entries);
-    ICHK(g, hipGetLastError());
+    ITRY(launch(g, nq + 1, row_ptr_from_sorted_kernel, s.coo_row, nq, b - a, g->ptr[1].get() + a));
+    ITRY(launch(g, b - a + 1, big_add_base_inplace_kernel, g->ptr[1].get() + a, b - a + 1, done_entries));
     done_entries += nq;
   }
   if (done_entries != nnz) return fail(g, MALS_HIP_ERROR, "ingest: the item ranges do not add up to the entries");
+  return MALS_OK;
+}
+
+// the pipeline proper starts at e0, once the buffers exist
+int finish_big(mals_ingest g, hipEvent_t e0, int64_t part_cap) {
+  Scratch s;
+  BigState B;
+  ITRY(big_reserve(g, s, B, part_cap));
+  ICHK(g, hipEventRecord(e0, g->stream));
+  ITRY(probe_id_width(g, s, &B.width));
+  ITRY(big_plan_user_ranges(g, s, B));
+  ITRY(big_finish_user_ranges(g, s, B));
+  ITRY(big_settle_items(g, s, B));
+  ITRY(big_transpose(g, s, B));
   // ---- 4. tag id sets, userTagIDs as rows of R^T ----------------------------------------------------------------------------
-  if (int rc = finish_tags(g, s, t, std::max<int64_t>(part_cap, n_sample))) return rc;
+  ITRY(finish_tags(g, s, B.sort_cap()));
   ICHK(g, hipStreamSynchronize(g->stream));
   return MALS_OK;
 }
+
+}  // namespace

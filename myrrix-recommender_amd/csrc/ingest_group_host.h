@@ -1,6 +1,8 @@
 // ingest_group_host.h -- the ingest half of mals_group_ingest_finish (include/myrrix_als.h): every rank of a group has
 // ingested one SHARE of the input stream (shares in stream order); the finish gives every rank the users of one id range and
-// the items of one bound range, without any rank ever holding the whole input.  Included by ingest_api.hip.
+// the items of one bound range, without any rank ever holding the whole input.  Host code of ingest_api.hip.
+// Expects before it: ingest_host.h (the ingest object, setup_workspace, transpose_by_item), split_kernels.h,
+// ingest_big_kernels.h (the 64-bit scan) and mals_internal.h (malsi_group_ops).
 //
 //   a. status and text counters of every share in one all-reduce; the header candidate of a share and the "line after the
 //      101st bad line" rule are decided on the combined counters, identically on every rank
@@ -12,8 +14,6 @@
 //      sort by item of runs that arrive in ascending user order gives R^T's rows of this rank's items
 //   g. records, workspace and exchange buffers are released before the caller declares the factor replicas
 #pragma once
-
-#include "split_kernels.h"
 
 namespace {
 
@@ -158,25 +158,18 @@ int shard_split(mals_ingest g, const int64_t* key, const std::vector<int64_t>& s
   ICHK(g, offs.alloc((size_t)n_counts + 1));
   ICHK(g, sums.alloc((size_t)scan_tiles + 1));
   if (!splitters.empty()) ICHK(g, hipMemcpy(spl.get(), splitters.data(), sizeof(int64_t) * splitters.size(), hipMemcpyHostToDevice));
-  hipEvent_t e0, e1;
-  ICHK(g, hipEventCreate(&e0));
-  ICHK(g, hipEventCreate(&e1));
-  ICHK(g, hipEventRecord(e0, g->stream));
-  hipLaunchKernelGGL(split_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, g->stream, key, n, spl.get(), nb - 1, n_tiles, dest.get(), counts_d.get());
-  hipLaunchKernelGGL(big_scan64_reduce_kernel, dim3((unsigned)scan_tiles), dim3(256), 0, g->stream, counts_d.get(), n_counts, sums.get());
-  hipLaunchKernelGGL(big_scan64_sums_kernel, dim3(1), dim3(64), 0, g->stream, sums.get(), scan_tiles, sums.get() + scan_tiles);
-  hipLaunchKernelGGL(big_scan64_apply_kernel, dim3((unsigned)scan_tiles), dim3(256), 0, g->stream, counts_d.get(), n_counts, sums.get(), sums.get() + scan_tiles,
-                     offs.get());
-  hipLaunchKernelGGL(split_scatter_kernel, dim3((unsigned)n_tiles), dim3(256), 0, g->stream, dest.get(), n, nb, n_tiles, offs.get(), a, b, v, oa.get(), ob.get(),
-                     ov.get());
-  const hipError_t le = hipGetLastError();
-  ICHK(g, hipEventRecord(e1, g->stream));
-  ICHK(g, hipEventSynchronize(e1));
+  EventPair ev;
+  ICHK(g, ev.create());
+  ICHK(g, hipEventRecord(ev.begin, g->stream));
+  ITRY(launch_grid(g, {(unsigned)n_tiles}, split_count_kernel, key, n, spl.get(), nb - 1, n_tiles, dest.get(), counts_d.get()));
+  ITRY(launch_grid(g, {(unsigned)scan_tiles}, big_scan64_reduce_kernel, counts_d.get(), n_counts, sums.get()));
+  ITRY(launch_grid(g, {1, 64}, big_scan64_sums_kernel, sums.get(), scan_tiles, sums.get() + scan_tiles));
+  ITRY(launch_grid(g, {(unsigned)scan_tiles}, big_scan64_apply_kernel, counts_d.get(), n_counts, sums.get(), sums.get() + scan_tiles, offs.get()));
+  ITRY(launch_grid(g, {(unsigned)n_tiles}, split_scatter_kernel, dest.get(), n, nb, n_tiles, offs.get(), a, b, v, oa.get(), ob.get(), ov.get()));
+  ICHK(g, hipEventRecord(ev.end, g->stream));
+  ICHK(g, hipEventSynchronize(ev.end));
   float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  ICHK(g, le);
+  (void)hipEventElapsedTime(&ms, ev.begin, ev.end);
   g->split_ms += ms;
   // the traffic of the two split kernels: count pass 8 B key read + 1 B destination written, scatter 1 B destination + 20 B
   // record read and 20 B written (the scan over tiles x buckets, 12 B per tile and bucket, is below 1 % at world <= 8)
@@ -326,359 +319,375 @@ std::vector<int64_t> shard_splitters(int world, const std::vector<int64_t>& all)
   return spl;
 }
 
-void shard_release_work(mals_ingest g) {
-  g->d_user.reset();
-  g->d_item.reset();
-  g->d_value.reset();
-  for (int b = 0; b < mals_ingest_s::N_WS; ++b) g->ws[b].reset();
-  g->d_text.reset(); g->d_carry.reset();
-  g->t_block_counts.reset(); g->t_tile_sums.reset(); g->t_starts.reset(); g->t_flag.reset(); g->t_defer.reset();
-  g->t_status.reset(); g->t_user.reset(); g->t_item.reset(); g->t_value.reset(); g->t_counters.reset();
-  g->d_tags[0].reset(); g->d_tags[1].reset();
-  g->n_tags_raw[0] = g->n_tags_raw[1] = 0;
-  g->n = 0;
-  g->carry_len = 0;
+// ---- the steps of the group finish, in the order shard_finish_impl runs them.  A step that talks to the other ranks returns
+// the same status on every rank; its collective calls are part of its contract (ranks in other processes meet them call for call).
+
+// one int64 vector of `len` per local member, for an all-reduce in which every rank fills its own slots
+std::vector<std::vector<int64_t>> shard_slots(const ShardCtx& c, int64_t len) {
+  return std::vector<std::vector<int64_t>>((size_t)c.nl, std::vector<int64_t>((size_t)len, 0));
+}
+
+// a. the text status: status and counters of every share in one all-reduce, decided on the combined counters
+int shard_agree_text(ShardCtx& c) {
+  std::vector<std::vector<int64_t>> per = shard_slots(c, (int64_t)c.world * SC_N);
+  for (int i = 0; i < c.nl; ++i) {
+    mals_ingest g = c.g[i];
+    const int r = c.ops->ranks[i];
+    int64_t* sc = &per[(size_t)i][(size_t)r * SC_N];
+    int rc = g->text_failed ? g->text_fail_code : g->carry_len ? MALS_INVALID_ARG : MALS_OK;
+    if (!rc && g->share != r) rc = fail(g, MALS_INVALID_ARG, "the share of local member " + std::to_string(i) + " is not its rank");
+    sc[SC_RC] = rc;
+    sc[SC_LINES] = g->lines;
+    sc[SC_BAD] = g->bad_lines;
+    sc[SC_HEADER] = g->header_lines;
+    sc[SC_SKIPPED] = g->skipped_lines;
+    sc[SC_SLOW] = g->slow_lines;
+    sc[SC_BYTES] = g->text_bytes;
+    sc[SC_FATAL] = g->fatal_line;
+    sc[SC_NPOS] = (int64_t)std::min<size_t>(g->bad_pos.size(), SHARD_BADPOS);
+    for (int64_t k = 0; k < sc[SC_NPOS]; ++k) sc[SC_POS + k] = g->bad_pos[(size_t)k];
+  }
+  std::vector<int64_t> all;
+  ITRY(shard_allreduce(c, per, 0, &all));
+  std::string why;
+  const int rc = shard_decide_text(c, all, &why);
+  for (int i = 0; i < c.nl && rc; ++i) {
+    mals_ingest g = c.g[i];
+    if (!g->text_failed || g->text_fail_code != rc) g->err = why;
+    else g->err = g->text_fail_msg;
+  }
+  return rc;
+}
+
+// b. the user splitters: a sample of every member's user ids, all-reduced; the same splitters on every rank
+int shard_user_splitters(ShardCtx& c, std::vector<int64_t>* spl) {
+  const int S = SHARD_SAMPLE + 2;
+  std::vector<std::vector<int64_t>> per = shard_slots(c, (int64_t)c.world * S);
+  std::vector<int> rcs((size_t)c.nl, MALS_OK);
+  for (int i = 0; i < c.nl; ++i) {
+    mals_ingest g = c.g[i];
+    const int r = c.ops->ranks[i];
+    const int64_t m = std::min<int64_t>(g->n, SHARD_SAMPLE);
+    per[(size_t)i][(size_t)r * S] = g->n;
+    per[(size_t)i][(size_t)r * S + 1] = m;
+    if (m == 0) continue;
+    DeviceBuffer<int64_t> d;
+    if (hipSetDevice(g->device) != hipSuccess || d.alloc((size_t)m) != hipSuccess) {
+      rcs[(size_t)i] = fail(g, MALS_OOM, "sharded ingest: sample: out of device memory");
+      continue;
+    }
+    if (launch(g, m, shard_sample_kernel, g->d_user.get(), g->n, m, d.get()) != MALS_OK ||
+        hipMemcpyAsync(&per[(size_t)i][(size_t)r * S + 2], d.get(), sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+        hipStreamSynchronize(g->stream) != hipSuccess)
+      rcs[(size_t)i] = fail(g, MALS_HIP_ERROR, "sharded ingest: sample failed");
+  }
+  ITRY(shard_agree(c, rcs));
+  std::vector<int64_t> all;
+  ITRY(shard_allreduce(c, per, 0, &all));
+  *spl = shard_splitters(c.world, all);
+  return MALS_OK;
+}
+
+// c / f. One redistribution of rows (two ids and a value) among the ranks.  split(i, &cnt) splits member i's rows by owner
+// into the send buffers (shard_split) and counts the runs; the world x world count matrix is all-reduced and every run goes
+// to its owner in one exchange.  The receivers hold the runs in source-rank order; the caller adopts them.
+struct ShardRuns {
+  std::vector<DeviceBuffer<int64_t>> sa, sb, ra, rb;
+  std::vector<DeviceBuffer<float>> sv, rv;
+  std::vector<int64_t> n_recv;
+  explicit ShardRuns(int nl) : sa((size_t)nl), sb((size_t)nl), sv((size_t)nl) {}
+  void release_sent(int i) { sa[(size_t)i].reset(); sb[(size_t)i].reset(); sv[(size_t)i].reset(); }
+  void release_received(int i) { ra[(size_t)i].reset(); rb[(size_t)i].reset(); rv[(size_t)i].reset(); }
+};
+template <typename Split>
+int shard_redistribute(ShardCtx& c, ShardRuns& R, bool records_are_source, Split&& split) {
+  const int W = c.world;
+  std::vector<std::vector<int64_t>> per = shard_slots(c, (int64_t)W * W);
+  std::vector<int> rcs((size_t)c.nl, MALS_OK);
+  for (int i = 0; i < c.nl; ++i) {
+    std::vector<int64_t> cnt;
+    rcs[(size_t)i] = split(i, &cnt);
+    if (!rcs[(size_t)i])
+      for (int q = 0; q < W; ++q) per[(size_t)i][(size_t)c.ops->ranks[i] * W + q] = cnt[(size_t)q];
+  }
+  ITRY(shard_agree(c, rcs));
+  std::vector<int64_t> mat;
+  ITRY(shard_allreduce(c, per, 0, &mat));
+  for (int i = 0; i < c.nl && records_are_source; ++i) {   // the split copies hold the records now
+    (void)hipSetDevice(c.g[i]->device);
+    c.g[i]->d_user.reset(); c.g[i]->d_item.reset(); c.g[i]->d_value.reset();
+  }
+  return shard_exchange(c, mat, R.sa, R.sb, R.sv, R.ra, R.rb, R.rv, &R.n_recv);
+}
+
+// c. records to the owners of their users
+int shard_redistribute_records(ShardCtx& c, const std::vector<int64_t>& spl) {
+  ShardRuns R(c.nl);
+  ITRY(shard_redistribute(c, R, true, [&](int i, std::vector<int64_t>* cnt) -> int {
+    mals_ingest g = c.g[i];
+    if (hipSetDevice(g->device) != hipSuccess) return MALS_HIP_ERROR;
+    return shard_split(g, g->d_user.get(), spl, g->d_user.get(), g->d_item.get(), g->d_value.get(), g->n, R.sa[(size_t)i], R.sb[(size_t)i], R.sv[(size_t)i], cnt);
+  }));
+  for (int i = 0; i < c.nl; ++i) {
+    mals_ingest g = c.g[i];
+    (void)hipSetDevice(g->device);
+    R.release_sent(i);
+    g->d_user = std::move(R.ra[(size_t)i]);
+    g->d_item = std::move(R.rb[(size_t)i]);
+    g->d_value = std::move(R.rv[(size_t)i]);
+    g->n = R.n_recv[(size_t)i];
+    g->shard_records = g->n;
+  }
+  return MALS_OK;
+}
+
+// d. the one-device finish on every member's users; records and workspace go: nothing of them is needed afterwards
+int shard_finish_members(ShardCtx& c) {
+  std::vector<int> rcs((size_t)c.nl, MALS_OK);
+  for (int i = 0; i < c.nl; ++i) {
+    mals_ingest g = c.g[i];
+    const double sm = g->split_ms, sbytes = g->split_bytes;
+    rcs[(size_t)i] = mals_ingest_finish(g);
+    g->split_ms = sm;
+    g->split_bytes = sbytes;
+    (void)hipSetDevice(g->device);
+    g->release_work();
+  }
+  return shard_agree(c, rcs);
+}
+
+// e. the group's tables, as every rank knows them after the members' finishes
+struct ShardTables {
+  std::vector<int64_t> sizes;                        // per rank: users, items, tags0, tags1
+  int64_t n_users = 0, n_items = 0;
+  std::vector<int64_t> items_glob;                   // the ranks' item tables merged, ascending (host)
+  std::vector<std::vector<int64_t>> local_items;     // per local member: its own item table (host)
+  std::vector<DeviceBuffer<int64_t>> users_glob;     // per local member: the ranks' user tables in rank order = ascending
+  std::vector<int64_t> tags_glob[2];
+  std::vector<std::vector<int32_t>> maps;            // per local member: its item index -> global item index
+  std::vector<int64_t> column(int world, int k) const {
+    std::vector<int64_t> v((size_t)world);
+    for (int r = 0; r < world; ++r) v[(size_t)r] = sizes[(size_t)r * 4 + k];
+    return v;
+  }
+};
+
+int shard_table_sizes(ShardCtx& c, ShardTables& T) {
+  std::vector<std::vector<int64_t>> per = shard_slots(c, (int64_t)c.world * 4);
+  for (int i = 0; i < c.nl; ++i) {
+    mals_ingest g = c.g[i];
+    const int64_t mine[4] = {g->n_users, g->n_items, g->n_tag_ids[0], g->n_tag_ids[1]};
+    std::copy(mine, mine + 4, &per[(size_t)i][(size_t)c.ops->ranks[i] * 4]);
+  }
+  return shard_allreduce(c, per, 0, &T.sizes);
+}
+
+// one table of every member (table(g): its device pointer, len[rank]: its length) all-gathered in rank order into
+// *gathered (one device copy per member) and, where the host merges it, brought to the host as *cat
+template <typename Table>
+int shard_gather_table(ShardCtx& c, const std::vector<int64_t>& len, Table&& table, std::vector<DeviceBuffer<int64_t>>* gathered,
+                       std::vector<int64_t>* cat = nullptr) {
+  std::vector<const int64_t*> src((size_t)c.nl);
+  for (int i = 0; i < c.nl; ++i) src[(size_t)i] = table(c.g[i]);
+  ITRY(shard_allgather(c, len, src, gathered));
+  if (!cat) return MALS_OK;
+  int64_t tot = 0;
+  for (int64_t v : len) tot += v;
+  cat->assign((size_t)tot, 0);
+  int rc0 = hip_status(c.g[0], hipSetDevice(c.g[0]->device), "hipSetDevice");
+  if (!rc0 && tot) rc0 = hip_status(c.g[0], hipMemcpy(cat->data(), (*gathered)[0].get(), sizeof(int64_t) * (size_t)tot, hipMemcpyDeviceToHost), "hipMemcpy");
+  return shard_agree1(c, 0, rc0);
+}
+
+// item tables: all-gathered, merged on the host (each is ascending: pairwise merges, no sort)
+int shard_merge_item_tables(ShardCtx& c, ShardTables& T) {
+  const std::vector<int64_t> n_items_r = T.column(c.world, 1);
+  std::vector<int64_t> cat;
+  std::vector<DeviceBuffer<int64_t>> gathered;
+  ITRY(shard_gather_table(c, n_items_r, [](mals_ingest g) { return g->ids[1].get(); }, &gathered, &cat));
+  T.local_items.resize((size_t)c.nl);
+  int64_t off = 0;
+  for (int r = 0; r < c.world; ++r) {
+    const auto b = cat.begin() + off, e = b + n_items_r[(size_t)r];
+    std::vector<int64_t> m;
+    m.reserve(T.items_glob.size() + (size_t)n_items_r[(size_t)r]);
+    std::set_union(T.items_glob.begin(), T.items_glob.end(), b, e, std::back_inserter(m));
+    T.items_glob.swap(m);
+    for (int i = 0; i < c.nl; ++i)
+      if (c.ops->ranks[i] == r) T.local_items[(size_t)i].assign(b, e);
+    off += n_items_r[(size_t)r];
+  }
+  T.n_items = (int64_t)T.items_glob.size();
+  return MALS_OK;
+}
+
+// f. per-item entry counts of every rank, all-reduced -> the item bounds of the group (mals_plan_shards)
+int shard_plan_item_bounds(ShardCtx& c, ShardTables& T, int64_t* bounds_y) {
+  const int64_t n_items = T.n_items;
+  T.maps.resize((size_t)c.nl);
+  std::vector<std::vector<int64_t>> per = shard_slots(c, std::max<int64_t>(n_items, 1));
+  std::vector<int> rcs((size_t)c.nl, MALS_OK);
+  for (int i = 0; i < c.nl; ++i) {
+    mals_ingest g = c.g[i];
+    const std::vector<int64_t>& li = T.local_items[(size_t)i];
+    std::vector<int32_t>& map = T.maps[(size_t)i];
+    map.resize(li.size());
+    for (size_t j = 0; j < li.size(); ++j) map[j] = (int32_t)(std::lower_bound(T.items_glob.begin(), T.items_glob.end(), li[j]) - T.items_glob.begin());
+    std::vector<int64_t> cp(li.size() + 1);
+    int rc = hip_status(g, hipSetDevice(g->device), "hipSetDevice");
+    if (!rc) rc = hip_status(g, hipMemcpy(cp.data(), g->ptr[1].get(), sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+    rcs[(size_t)i] = rc;
+    if (!rc)
+      for (size_t j = 0; j < li.size(); ++j) per[(size_t)i][(size_t)map[j]] = cp[j + 1] - cp[j];
+  }
+  ITRY(shard_agree(c, rcs));
+  std::vector<int64_t> cnt;
+  ITRY(shard_allreduce(c, per, 0, &cnt));
+  std::vector<int64_t> rp((size_t)n_items + 1, 0);
+  for (int64_t j = 0; j < n_items; ++j) rp[(size_t)j + 1] = rp[(size_t)j] + cnt[(size_t)j];
+  const int rc = mals_plan_shards(rp.data(), n_items, c.world, -1.0, c.ops->features, bounds_y);
+  for (int i = 0; i < c.nl && rc; ++i) fail(c.g[i], rc, "mals_plan_shards failed");
+  return rc;
+}
+
+// f. member i's entries as (global user, global item, value), split by the owner of the item.  Its columns and knownItemIDs
+// become global item indices on the way; its local R^T is not needed any more.
+int shard_split_entries(ShardCtx& c, int i, const ShardTables& T, const std::vector<int64_t>& yspl, int64_t user_base, ShardRuns& R, std::vector<int64_t>* cnt) {
+  mals_ingest g = c.g[i];
+  const std::vector<int32_t>& host_map = T.maps[(size_t)i];
+  ICHK(g, hipSetDevice(g->device));
+  const int64_t nnz = g->nnz, nu = g->n_users;
+  DeviceBuffer<int32_t> map;
+  ICHK(g, map.alloc(std::max<size_t>(host_map.size(), 1)));
+  if (!host_map.empty()) ICHK(g, hipMemcpy(map.get(), host_map.data(), sizeof(int32_t) * host_map.size(), hipMemcpyHostToDevice));
+  if (nnz) ITRY(launch(g, nnz, shard_remap_kernel, g->col[0].get(), nnz, map.get()));
+  if (g->known_ptr && g->n_known) ITRY(launch(g, g->n_known, shard_remap_kernel, g->known_idx.get(), g->n_known, map.get()));
+  DeviceBuffer<int64_t> eu, ei;
+  ICHK(g, eu.alloc((size_t)std::max<int64_t>(nnz, 1)));
+  ICHK(g, ei.alloc((size_t)std::max<int64_t>(nnz, 1)));
+  if (nnz) {
+    ITRY(launch(g, nu, shard_expand_rows_kernel, g->ptr[0].get(), nu, user_base, eu.get()));
+    ITRY(launch(g, nnz, shard_widen_kernel, g->col[0].get(), nnz, ei.get()));
+  }
+  ICHK(g, hipStreamSynchronize(g->stream));
+  g->ptr[1].reset(); g->col[1].reset(); g->val[1].reset();
+  return shard_split(g, ei.get(), yspl, eu.get(), ei.get(), g->val[0].get(), nnz, R.sa[(size_t)i], R.sb[(size_t)i], R.sv[(size_t)i], cnt);
+}
+
+// f. member i's rows of R^T, items [y0, y0 + ny), from the m entries it received: the runs arrive in ascending user order,
+// so a stable sort on the item half of the key alone does it
+int shard_build_item_slice(ShardCtx& c, int i, ShardRuns& R, int64_t y0, int64_t ny) {
+  mals_ingest g = c.g[i];
+  ICHK(g, hipSetDevice(g->device));
+  R.release_sent(i);
+  const int64_t m = R.n_recv[(size_t)i];
+  ICHK(g, g->ptr[1].alloc((size_t)ny + 1));
+  ICHK(g, g->col[1].alloc((size_t)std::max<int64_t>(m, 1)));
+  ICHK(g, g->val[1].alloc((size_t)std::max<int64_t>(m, 1)));
+  if (m > 0) {
+    Scratch s;
+    ITRY(setup_workspace(g, s, m, 0));
+    ITRY(launch(g, m, shard_transpose_keys_kernel, R.ra[(size_t)i].get(), R.rb[(size_t)i].get(), R.rv[(size_t)i].get(), m, y0, s.keys[0], s.pay[0]));
+    ITRY(transpose_by_item(g, s, m, ny, g->ptr[1].get(), g->col[1].get(), g->val[1].get()));
+    ICHK(g, hipStreamSynchronize(g->stream));
+    for (int b = 0; b < mals_ingest_s::N_WS; ++b) g->ws[b].reset();
+  } else {
+    ICHK(g, hipMemset(g->ptr[1].get(), 0, sizeof(int64_t) * ((size_t)ny + 1)));
+  }
+  R.release_received(i);
+  g->slice_begin[1] = y0;
+  g->slice_rows[1] = ny;
+  g->slice_nnz[1] = m;
+  return MALS_OK;
+}
+
+// the global tables on member i; from here on its counts are the group's and its matrices are slices
+int shard_install_tables(ShardCtx& c, int i, ShardTables& T, int64_t user_base) {
+  mals_ingest g = c.g[i];
+  const int64_t n_users = T.n_users, n_items = T.n_items;
+  const int64_t x_rows = g->n_users, x_nnz = g->nnz;
+  ICHK(g, g->ids[0].alloc((size_t)std::max<int64_t>(n_users, 1)));
+  if (n_users) ICHK(g, hipMemcpy(g->ids[0].get(), T.users_glob[(size_t)i].get(), sizeof(int64_t) * (size_t)n_users, hipMemcpyDeviceToDevice));
+  T.users_glob[(size_t)i].reset();
+  ICHK(g, g->ids[1].alloc((size_t)std::max<int64_t>(n_items, 1)));
+  if (n_items) ICHK(g, hipMemcpy(g->ids[1].get(), T.items_glob.data(), sizeof(int64_t) * (size_t)n_items, hipMemcpyHostToDevice));
+  for (int w = 0; w < 2; ++w) {
+    g->tag_ids[w].reset();
+    g->n_tag_ids[w] = (int64_t)T.tags_glob[w].size();
+    if (!T.tags_glob[w].empty()) {
+      ICHK(g, g->tag_ids[w].alloc(T.tags_glob[w].size()));
+      ICHK(g, hipMemcpy(g->tag_ids[w].get(), T.tags_glob[w].data(), sizeof(int64_t) * T.tags_glob[w].size(), hipMemcpyHostToDevice));
+    }
+  }
+  g->tag_item_idx.reset();
+  if (g->n_tag_ids[1] > 0) {
+    ICHK(g, g->tag_item_idx.alloc((size_t)g->n_tag_ids[1]));
+    ITRY(launch(g, g->n_tag_ids[1], index_of_ids_kernel, g->tag_ids[1].get(), g->n_tag_ids[1], g->ids[1].get(), n_items, g->tag_item_idx.get()));
+  }
+  ICHK(g, hipStreamSynchronize(g->stream));
+  g->sharded = true;
+  g->slice_begin[0] = user_base;
+  g->slice_rows[0] = x_rows;
+  g->slice_nnz[0] = x_nnz;
+  g->n_users = n_users;
+  g->n_items = n_items;
+  return MALS_OK;
+}
+
+// f. entries to the owners of their items; every member's item slice; the global tables in place of its own
+int shard_redistribute_entries(ShardCtx& c, ShardTables& T, const int64_t* bounds_x, const int64_t* bounds_y) {
+  const std::vector<int64_t> yspl(bounds_y + 1, bounds_y + c.world);
+  ShardRuns R(c.nl);
+  ITRY(shard_redistribute(c, R, false, [&](int i, std::vector<int64_t>* cnt) { return shard_split_entries(c, i, T, yspl, bounds_x[c.ops->ranks[i]], R, cnt); }));
+  std::vector<int> rcs((size_t)c.nl, MALS_OK);
+  for (int i = 0; i < c.nl; ++i) {
+    const int r = c.ops->ranks[i];
+    int rc = shard_build_item_slice(c, i, R, bounds_y[r], bounds_y[r + 1] - bounds_y[r]);
+    if (!rc) rc = shard_install_tables(c, i, T, bounds_x[r]);
+    rcs[(size_t)i] = rc;
+  }
+  return shard_agree(c, rcs);
+}
+
+// the global entry count on every member
+int shard_total_entries(ShardCtx& c) {
+  std::vector<std::vector<int64_t>> per = shard_slots(c, 1);
+  for (int i = 0; i < c.nl; ++i) per[(size_t)i][0] = c.g[i]->slice_nnz[0];
+  std::vector<int64_t> tot;
+  ITRY(shard_allreduce(c, per, 0, &tot));
+  for (int i = 0; i < c.nl; ++i) c.g[i]->nnz = tot[0];
+  return MALS_OK;
 }
 
 int shard_finish_impl(ShardCtx& c, int64_t* bounds_x, int64_t* bounds_y) {
-  const int W = c.world, NL = c.nl;
-  std::string why;
-  // ---- a. status and counters
-  {
-    std::vector<std::vector<int64_t>> per((size_t)NL, std::vector<int64_t>((size_t)W * SC_N, 0));
-    for (int i = 0; i < NL; ++i) {
-      mals_ingest g = c.g[i];
-      const int r = c.ops->ranks[i];
-      int64_t* sc = &per[(size_t)i][(size_t)r * SC_N];
-      int rc = g->text_failed ? g->text_fail_code : g->carry_len ? MALS_INVALID_ARG : MALS_OK;
-      if (!rc && g->share != r) rc = fail(g, MALS_INVALID_ARG, "the share of local member " + std::to_string(i) + " is not its rank");
-      sc[SC_RC] = rc;
-      sc[SC_LINES] = g->lines;
-      sc[SC_BAD] = g->bad_lines;
-      sc[SC_HEADER] = g->header_lines;
-      sc[SC_SKIPPED] = g->skipped_lines;
-      sc[SC_SLOW] = g->slow_lines;
-      sc[SC_BYTES] = g->text_bytes;
-      sc[SC_FATAL] = g->fatal_line;
-      sc[SC_NPOS] = (int64_t)std::min<size_t>(g->bad_pos.size(), SHARD_BADPOS);
-      for (int64_t k = 0; k < sc[SC_NPOS]; ++k) sc[SC_POS + k] = g->bad_pos[(size_t)k];
-    }
-    std::vector<int64_t> all;
-    if (int rc = shard_allreduce(c, per, 0, &all)) return rc;
-    if (int rc = shard_decide_text(c, all, &why)) {
-      for (int i = 0; i < NL; ++i) {
-        mals_ingest g = c.g[i];
-        if (!g->text_failed || g->text_fail_code != rc) g->err = why;
-        else g->err = g->text_fail_msg;
-      }
-      return rc;
-    }
-  }
-  for (int i = 0; i < NL; ++i) {
-    free_results(c.g[i]);
+  const int W = c.world;
+  ITRY(shard_agree_text(c));                                   // a
+  for (int i = 0; i < c.nl; ++i) {
+    c.g[i]->free_results();
     c.g[i]->split_ms = c.g[i]->split_bytes = 0.0;
     c.g[i]->work_at_replicas = -1;
   }
-  // ---- b. user-id splitters
   std::vector<int64_t> spl;
-  {
-    const int S = SHARD_SAMPLE + 2;
-    std::vector<std::vector<int64_t>> per((size_t)NL, std::vector<int64_t>((size_t)W * S, 0));
-    std::vector<int> rcs((size_t)NL, MALS_OK);
-    for (int i = 0; i < NL; ++i) {
-      mals_ingest g = c.g[i];
-      const int r = c.ops->ranks[i];
-      const int64_t m = std::min<int64_t>(g->n, SHARD_SAMPLE);
-      per[(size_t)i][(size_t)r * S] = g->n;
-      per[(size_t)i][(size_t)r * S + 1] = m;
-      if (m == 0) continue;
-      DeviceBuffer<int64_t> d;
-      if (hipSetDevice(g->device) != hipSuccess || d.alloc((size_t)m) != hipSuccess) {
-        rcs[(size_t)i] = fail(g, MALS_OOM, "sharded ingest: sample: out of device memory");
-        continue;
-      }
-      hipLaunchKernelGGL(shard_sample_kernel, dim3(blocks_for(m)), dim3(256), 0, g->stream, g->d_user.get(), g->n, m, d.get());
-      if (hipMemcpyAsync(&per[(size_t)i][(size_t)r * S + 2], d.get(), sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
-          hipStreamSynchronize(g->stream) != hipSuccess)
-        rcs[(size_t)i] = fail(g, MALS_HIP_ERROR, "sharded ingest: sample failed");
-    }
-    if (int rc = shard_agree(c, rcs)) return rc;
-    std::vector<int64_t> all;
-    if (int rc = shard_allreduce(c, per, 0, &all)) return rc;
-    spl = shard_splitters(W, all);
-  }
-  // ---- c. records to their owners
-  {
-    std::vector<DeviceBuffer<int64_t>> sa((size_t)NL), sb((size_t)NL), ra, rb;
-    std::vector<DeviceBuffer<float>> sv((size_t)NL), rv;
-    std::vector<std::vector<int64_t>> per((size_t)NL, std::vector<int64_t>((size_t)W * W, 0));
-    std::vector<int> rcs((size_t)NL, MALS_OK);
-    for (int i = 0; i < NL; ++i) {
-      mals_ingest g = c.g[i];
-      const int r = c.ops->ranks[i];
-      std::vector<int64_t> cnt;
-      if (hipSetDevice(g->device) != hipSuccess) { rcs[(size_t)i] = MALS_HIP_ERROR; continue; }
-      rcs[(size_t)i] = shard_split(g, g->d_user.get(), spl, g->d_user.get(), g->d_item.get(), g->d_value.get(), g->n, sa[(size_t)i], sb[(size_t)i], sv[(size_t)i], &cnt);
-      if (!rcs[(size_t)i])
-        for (int q = 0; q < W; ++q) per[(size_t)i][(size_t)r * W + q] = cnt[(size_t)q];
-    }
-    if (int rc = shard_agree(c, rcs)) return rc;
-    std::vector<int64_t> mat;
-    if (int rc = shard_allreduce(c, per, 0, &mat)) return rc;
-    for (int i = 0; i < NL; ++i) {   // the split copies hold the records now
-      (void)hipSetDevice(c.g[i]->device);
-      c.g[i]->d_user.reset();
-      c.g[i]->d_item.reset();
-      c.g[i]->d_value.reset();
-    }
-    std::vector<int64_t> n_recv;
-    if (int rc = shard_exchange(c, mat, sa, sb, sv, ra, rb, rv, &n_recv)) return rc;
-    for (int i = 0; i < NL; ++i) {
-      mals_ingest g = c.g[i];
-      (void)hipSetDevice(g->device);
-      sa[(size_t)i].reset(); sb[(size_t)i].reset(); sv[(size_t)i].reset();
-      g->d_user = std::move(ra[(size_t)i]);
-      g->d_item = std::move(rb[(size_t)i]);
-      g->d_value = std::move(rv[(size_t)i]);
-      g->n = n_recv[(size_t)i];
-      g->shard_records = g->n;
-    }
-  }
-  // ---- d. the one-device finish on this rank's users
-  {
-    std::vector<int> rcs((size_t)NL, MALS_OK);
-    for (int i = 0; i < NL; ++i) {
-      mals_ingest g = c.g[i];
-      const double sm = g->split_ms, sbytes = g->split_bytes;
-      rcs[(size_t)i] = mals_ingest_finish(g);
-      g->split_ms = sm;
-      g->split_bytes = sbytes;
-      (void)hipSetDevice(g->device);
-      shard_release_work(g);   // records and workspace: nothing of them is needed below
-    }
-    if (int rc = shard_agree(c, rcs)) return rc;
-  }
-  // ---- e. global tables
-  std::vector<int64_t> sizes;   // per rank: users, items, tags0, tags1
-  {
-    std::vector<std::vector<int64_t>> per((size_t)NL, std::vector<int64_t>((size_t)W * 4, 0));
-    for (int i = 0; i < NL; ++i) {
-      mals_ingest g = c.g[i];
-      int64_t* p = &per[(size_t)i][(size_t)c.ops->ranks[i] * 4];
-      p[0] = g->n_users;
-      p[1] = g->n_items;
-      p[2] = g->n_tag_ids[0];
-      p[3] = g->n_tag_ids[1];
-    }
-    if (int rc = shard_allreduce(c, per, 0, &sizes)) return rc;
-  }
-  auto col_of = [&](int k) {
-    std::vector<int64_t> v((size_t)W);
-    for (int r = 0; r < W; ++r) v[(size_t)r] = sizes[(size_t)r * 4 + k];
-    return v;
-  };
-  const std::vector<int64_t> n_users_r = col_of(0), n_items_r = col_of(1);
-  bounds_x[0] = 0;
-  for (int r = 0; r < W; ++r) bounds_x[r + 1] = bounds_x[r] + n_users_r[(size_t)r];
-  const int64_t n_users = bounds_x[W];
-  // item tables: all-gathered, merged on the host (each is ascending: pairwise merges, no sort)
-  std::vector<int64_t> items_glob;
-  std::vector<std::vector<int64_t>> local_items((size_t)NL);
-  {
-    std::vector<const int64_t*> src((size_t)NL);
-    for (int i = 0; i < NL; ++i) src[(size_t)i] = c.g[i]->ids[1].get();
+  ITRY(shard_user_splitters(c, &spl));                         // b
+  ITRY(shard_redistribute_records(c, spl));                    // c
+  ITRY(shard_finish_members(c));                               // d
+  ShardTables T;                                               // e
+  ITRY(shard_table_sizes(c, T));
+  bounds_x[0] = 0;   // users: ranks own ascending id ranges, so the concatenation of their tables is the ascending table
+  for (int r = 0; r < W; ++r) bounds_x[r + 1] = bounds_x[r] + T.sizes[(size_t)r * 4];
+  T.n_users = bounds_x[W];
+  ITRY(shard_merge_item_tables(c, T));
+  ITRY(shard_gather_table(c, T.column(W, 0), [](mals_ingest g) { return g->ids[0].get(); }, &T.users_glob));
+  for (int w = 0; w < 2; ++w) {   // tags: union of every rank's sets
+    std::vector<int64_t>& tags = T.tags_glob[w];
     std::vector<DeviceBuffer<int64_t>> gathered;
-    if (int rc = shard_allgather(c, n_items_r, src, &gathered)) return rc;
-    int64_t tot = 0;
-    for (int64_t v : n_items_r) tot += v;
-    std::vector<int64_t> cat((size_t)tot);
-    int rc0 = hip_status(c.g[0], hipSetDevice(c.g[0]->device), "hipSetDevice");
-    if (!rc0 && tot) rc0 = hip_status(c.g[0], hipMemcpy(cat.data(), gathered[0].get(), sizeof(int64_t) * (size_t)tot, hipMemcpyDeviceToHost), "hipMemcpy");
-    if (int rc = shard_agree1(c, 0, rc0)) return rc;
-    int64_t off = 0;
-    for (int r = 0; r < W; ++r) {
-      std::vector<int64_t> m;
-      m.reserve(items_glob.size() + (size_t)n_items_r[(size_t)r]);
-      std::set_union(items_glob.begin(), items_glob.end(), cat.begin() + off, cat.begin() + off + n_items_r[(size_t)r], std::back_inserter(m));
-      items_glob.swap(m);
-      for (int i = 0; i < NL; ++i)
-        if (c.ops->ranks[i] == r) local_items[(size_t)i].assign(cat.begin() + off, cat.begin() + off + n_items_r[(size_t)r]);
-      off += n_items_r[(size_t)r];
-    }
+    ITRY(shard_gather_table(c, T.column(W, 2 + w), [w](mals_ingest g) { return g->tag_ids[w].get(); }, &gathered, &tags));
+    std::sort(tags.begin(), tags.end());
+    tags.erase(std::unique(tags.begin(), tags.end()), tags.end());
   }
-  const int64_t n_items = (int64_t)items_glob.size();
-  // users: ranks own ascending id ranges, so the concatenation is the ascending table
-  std::vector<DeviceBuffer<int64_t>> users_glob;
-  {
-    std::vector<const int64_t*> src((size_t)NL);
-    for (int i = 0; i < NL; ++i) src[(size_t)i] = c.g[i]->ids[0].get();
-    if (int rc = shard_allgather(c, n_users_r, src, &users_glob)) return rc;
-  }
-  // tags: union of every rank's sets
-  std::vector<int64_t> tags_glob[2];
-  for (int w = 0; w < 2; ++w) {
-    std::vector<const int64_t*> src((size_t)NL);
-    for (int i = 0; i < NL; ++i) src[(size_t)i] = c.g[i]->tag_ids[w].get();
-    const std::vector<int64_t> len = col_of(2 + w);
-    std::vector<DeviceBuffer<int64_t>> gathered;
-    if (int rc = shard_allgather(c, len, src, &gathered)) return rc;
-    int64_t tot = 0;
-    for (int64_t v : len) tot += v;
-    std::vector<int64_t> cat((size_t)tot);
-    int rc0 = hip_status(c.g[0], hipSetDevice(c.g[0]->device), "hipSetDevice");
-    if (!rc0 && tot) rc0 = hip_status(c.g[0], hipMemcpy(cat.data(), gathered[0].get(), sizeof(int64_t) * (size_t)tot, hipMemcpyDeviceToHost), "hipMemcpy");
-    if (int rc = shard_agree1(c, 0, rc0)) return rc;
-    std::sort(cat.begin(), cat.end());
-    cat.erase(std::unique(cat.begin(), cat.end()), cat.end());
-    tags_glob[w] = std::move(cat);
-  }
-  // ---- f. per-item entry counts -> item bounds; columns renumbered; R^T by item owner
-  std::vector<std::vector<int32_t>> maps((size_t)NL);
-  {
-    std::vector<std::vector<int64_t>> per((size_t)NL, std::vector<int64_t>((size_t)std::max<int64_t>(n_items, 1), 0));
-    std::vector<int> rcs((size_t)NL, MALS_OK);
-    for (int i = 0; i < NL; ++i) {
-      mals_ingest g = c.g[i];
-      const std::vector<int64_t>& li = local_items[(size_t)i];
-      maps[(size_t)i].resize(li.size());
-      for (size_t j = 0; j < li.size(); ++j) maps[(size_t)i][j] = (int32_t)(std::lower_bound(items_glob.begin(), items_glob.end(), li[j]) - items_glob.begin());
-      std::vector<int64_t> cp(li.size() + 1);
-      int rc = hip_status(g, hipSetDevice(g->device), "hipSetDevice");
-      if (!rc) rc = hip_status(g, hipMemcpy(cp.data(), g->ptr[1].get(), sizeof(int64_t) * cp.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-      rcs[(size_t)i] = rc;
-      if (!rc)
-        for (size_t j = 0; j < li.size(); ++j) per[(size_t)i][(size_t)maps[(size_t)i][j]] = cp[j + 1] - cp[j];
-    }
-    if (int rc = shard_agree(c, rcs)) return rc;
-    std::vector<int64_t> cnt;
-    if (int rc = shard_allreduce(c, per, 0, &cnt)) return rc;
-    std::vector<int64_t> rp((size_t)n_items + 1, 0);
-    for (int64_t j = 0; j < n_items; ++j) rp[(size_t)j + 1] = rp[(size_t)j] + cnt[(size_t)j];
-    if (int rc = mals_plan_shards(rp.data(), n_items, W, -1.0, c.ops->features, bounds_y)) {
-      for (int i = 0; i < NL; ++i) fail(c.g[i], rc, "mals_plan_shards failed");
-      return rc;
-    }
-  }
-  std::vector<int64_t> yspl(bounds_y + 1, bounds_y + W);
-  {
-    std::vector<DeviceBuffer<int64_t>> sa((size_t)NL), sb((size_t)NL), ra, rb;
-    std::vector<DeviceBuffer<float>> sv((size_t)NL), rv;
-    std::vector<std::vector<int64_t>> per((size_t)NL, std::vector<int64_t>((size_t)W * W, 0));
-    std::vector<int> rcs((size_t)NL, MALS_OK);
-    for (int i = 0; i < NL && true; ++i) {
-      mals_ingest g = c.g[i];
-      const int r = c.ops->ranks[i];
-      auto step = [&]() -> int {
-        ICHK(g, hipSetDevice(g->device));
-        const int64_t nnz = g->nnz, nu = g->n_users;
-        // columns and knownItemIDs to global item indices
-        DeviceBuffer<int32_t> map;
-        ICHK(g, map.alloc(std::max<size_t>(maps[(size_t)i].size(), 1)));
-        if (!maps[(size_t)i].empty()) ICHK(g, hipMemcpy(map.get(), maps[(size_t)i].data(), sizeof(int32_t) * maps[(size_t)i].size(), hipMemcpyHostToDevice));
-        if (nnz) hipLaunchKernelGGL(shard_remap_kernel, dim3(blocks_for(nnz)), dim3(256), 0, g->stream, g->col[0].get(), nnz, map.get());
-        if (g->known_ptr && g->n_known)
-          hipLaunchKernelGGL(shard_remap_kernel, dim3(blocks_for(g->n_known)), dim3(256), 0, g->stream, g->known_idx.get(), g->n_known, map.get());
-        ICHK(g, hipGetLastError());
-        // entries as (global user, global item, value)
-        DeviceBuffer<int64_t> eu, ei;
-        ICHK(g, eu.alloc((size_t)std::max<int64_t>(nnz, 1)));
-        ICHK(g, ei.alloc((size_t)std::max<int64_t>(nnz, 1)));
-        if (nnz) {
-          hipLaunchKernelGGL(shard_expand_rows_kernel, dim3(blocks_for(nu)), dim3(256), 0, g->stream, g->ptr[0].get(), nu, bounds_x[r], eu.get());
-          hipLaunchKernelGGL(shard_widen_kernel, dim3(blocks_for(nnz)), dim3(256), 0, g->stream, g->col[0].get(), nnz, ei.get());
-          ICHK(g, hipGetLastError());
-        }
-        ICHK(g, hipStreamSynchronize(g->stream));
-        // the local R^T is not needed any more
-        g->ptr[1].reset(); g->col[1].reset(); g->val[1].reset();
-        std::vector<int64_t> cnt;
-        if (int rc = shard_split(g, ei.get(), yspl, eu.get(), ei.get(), g->val[0].get(), nnz, sa[(size_t)i], sb[(size_t)i], sv[(size_t)i], &cnt)) return rc;
-        for (int q = 0; q < W; ++q) per[(size_t)i][(size_t)r * W + q] = cnt[(size_t)q];
-        return MALS_OK;
-      };
-      rcs[(size_t)i] = step();
-    }
-    if (int rc = shard_agree(c, rcs)) return rc;
-    std::vector<int64_t> mat;
-    if (int rc = shard_allreduce(c, per, 0, &mat)) return rc;
-    std::vector<int64_t> n_recv;
-    if (int rc = shard_exchange(c, mat, sa, sb, sv, ra, rb, rv, &n_recv)) return rc;
-    for (int i = 0; i < NL; ++i) {
-      mals_ingest g = c.g[i];
-      const int r = c.ops->ranks[i];
-      auto step = [&]() -> int {
-        ICHK(g, hipSetDevice(g->device));
-        sa[(size_t)i].reset(); sb[(size_t)i].reset(); sv[(size_t)i].reset();
-        const int64_t m = n_recv[(size_t)i], y0 = bounds_y[r], ny = bounds_y[r + 1] - bounds_y[r];
-        ICHK(g, g->ptr[1].alloc((size_t)ny + 1));
-        ICHK(g, g->col[1].alloc((size_t)std::max<int64_t>(m, 1)));
-        ICHK(g, g->val[1].alloc((size_t)std::max<int64_t>(m, 1)));
-        if (m > 0) {
-          // the runs arrive in ascending user order: a stable sort on the item half of the key alone
-          Scratch s;
-          FinishTmp t;
-          if (int rc = setup_workspace(g, s, t, m, 0)) return rc;
-          hipLaunchKernelGGL(shard_transpose_keys_kernel, dim3(blocks_for(m)), dim3(256), 0, g->stream, ra[(size_t)i].get(), rb[(size_t)i].get(), rv[(size_t)i].get(), m, y0,
-                             s.keys[0], s.pay[0]);
-          ICHK(g, hipGetLastError());
-          int r2 = 0;
-          if (int rc = radix_sort<uint64_t, unsigned>(g, s, s.keys, s.pay, m, &r2, 4, ((uint64_t)(ny > 0 ? ny - 1 : 0) << 32) | 0xffffffffull)) return rc;
-          hipLaunchKernelGGL(transpose_gather_kernel, dim3(blocks_for(m)), dim3(256), 0, g->stream, s.keys[r2], s.pay[r2], m, t.coo_row, g->col[1].get(), g->val[1].get());
-          hipLaunchKernelGGL(row_ptr_from_sorted_kernel, dim3(blocks_for(m + 1)), dim3(256), 0, g->stream, t.coo_row, m, ny, g->ptr[1].get());
-          ICHK(g, hipGetLastError());
-          ICHK(g, hipStreamSynchronize(g->stream));
-          for (int b = 0; b < mals_ingest_s::N_WS; ++b) g->ws[b].reset();
-        } else {
-          ICHK(g, hipMemset(g->ptr[1].get(), 0, sizeof(int64_t) * ((size_t)ny + 1)));
-        }
-        ra[(size_t)i].reset(); rb[(size_t)i].reset(); rv[(size_t)i].reset();
-        // the global tables
-        const int64_t x_rows = g->n_users, x_nnz = g->nnz;
-        ICHK(g, g->ids[0].alloc((size_t)std::max<int64_t>(n_users, 1)));
-        if (n_users) ICHK(g, hipMemcpy(g->ids[0].get(), users_glob[(size_t)i].get(), sizeof(int64_t) * (size_t)n_users, hipMemcpyDeviceToDevice));
-        users_glob[(size_t)i].reset();
-        ICHK(g, g->ids[1].alloc((size_t)std::max<int64_t>(n_items, 1)));
-        if (n_items) ICHK(g, hipMemcpy(g->ids[1].get(), items_glob.data(), sizeof(int64_t) * (size_t)n_items, hipMemcpyHostToDevice));
-        for (int w = 0; w < 2; ++w) {
-          g->tag_ids[w].reset();
-          g->n_tag_ids[w] = (int64_t)tags_glob[w].size();
-          if (!tags_glob[w].empty()) {
-            ICHK(g, g->tag_ids[w].alloc(tags_glob[w].size()));
-            ICHK(g, hipMemcpy(g->tag_ids[w].get(), tags_glob[w].data(), sizeof(int64_t) * tags_glob[w].size(), hipMemcpyHostToDevice));
-          }
-        }
-        g->tag_item_idx.reset();
-        if (g->n_tag_ids[1] > 0) {
-          ICHK(g, g->tag_item_idx.alloc((size_t)g->n_tag_ids[1]));
-          hipLaunchKernelGGL(index_of_ids_kernel, dim3(blocks_for(g->n_tag_ids[1])), dim3(256), 0, g->stream, g->tag_ids[1].get(), g->n_tag_ids[1], g->ids[1].get(),
-                             n_items, g->tag_item_idx.get());
-          ICHK(g, hipGetLastError());
-        }
-        ICHK(g, hipStreamSynchronize(g->stream));
-        g->sharded = true;
-        g->slice_begin[0] = bounds_x[r];
-        g->slice_rows[0] = x_rows;
-        g->slice_nnz[0] = x_nnz;
-        g->slice_begin[1] = y0;
-        g->slice_rows[1] = ny;
-        g->slice_nnz[1] = m;
-        g->n_users = n_users;
-        g->n_items = n_items;
-        return MALS_OK;
-      };
-      rcs[(size_t)i] = step();
-    }
-    if (int rc = shard_agree(c, rcs)) return rc;
-  }
-  // global entry count
-  {
-    std::vector<std::vector<int64_t>> per((size_t)NL, std::vector<int64_t>(1, 0));
-    for (int i = 0; i < NL; ++i) per[(size_t)i][0] = c.g[i]->slice_nnz[0];
-    std::vector<int64_t> tot;
-    if (int rc = shard_allreduce(c, per, 0, &tot)) return rc;
-    for (int i = 0; i < NL; ++i) c.g[i]->nnz = tot[0];
-  }
-  return MALS_OK;
+  ITRY(shard_plan_item_bounds(c, T, bounds_y));                // f
+  ITRY(shard_redistribute_entries(c, T, bounds_x, bounds_y));
+  return shard_total_entries(c);
 }
 
 }  // namespace
@@ -692,8 +701,8 @@ int malsi_ingest_shard_finish(mals_ingest* ingests, const malsi_group_ops* ops, 
       if (!c.comm_msg.empty()) g->err = c.comm_msg;
       else if (g->err.empty()) g->err = "another rank reported status " + std::to_string(rc);
       (void)hipSetDevice(g->device);
-      free_results(g);
-      shard_release_work(g);
+      g->free_results();
+      g->release_work();
       g->spent = true;   // its records are gone: a new ingest starts over
     }
     return rc;

@@ -1,5 +1,6 @@
 // ingest_text_host.h -- host side of the text half of the ingest path (mals_ingest_append_text / _read_file /
-// _read_dir, include/myrrix_als.h).  Included by ingest_api.hip after mals_ingest_s and its helpers.
+// _read_dir, include/myrrix_als.h).  Host code of ingest_api.hip.  Expects before it: ingest_host.h (the ingest object, the
+// launch helpers, scan_u32, grow_records) and ingest_text_kernels.h.
 //
 // The host does what java.io does for the reference -- list the directory (InputFilesReader.java:71-86), open and
 // inflate files (FileLineIterator.java:92-102), hand the bytes on in blocks -- and keeps the two counters whose
@@ -15,10 +16,6 @@
 namespace {
 
 constexpr size_t TEXT_PAD = 128;  // readable bytes behind the text (16-byte and 8-byte aligned window loads)
-
-struct TextScratch {
-  unsigned* block_counts = nullptr;  // line starts per LT_BLOCK_BYTES, then their exclusive scan
-};
 
 // room for `want` elements, by at least half the capacity at a time; the first `used` elements are kept
 template <typename T>
@@ -47,16 +44,9 @@ int process_text_region(mals_ingest g, size_t region) {
   if (region >= 0xffffff00ull) return fail(g, MALS_INVALID_ARG, "text block too large");
   // HIP-event time of the kernels only: allocations (which cost milliseconds to seconds, depending on the box) sit
   // between the timed segments
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ICHK(g, hipEventCreate(&e0));
-  ICHK(g, hipEventCreate(&e1));
-  struct Ev {
-    hipEvent_t &a, &b;
-    ~Ev() {
-      (void)hipEventDestroy(a);
-      (void)hipEventDestroy(b);
-    }
-  } ev{e0, e1};
+  EventPair ev;
+  ICHK(g, ev.create());
+  const hipEvent_t e0 = ev.begin, e1 = ev.end;
   auto seg_end = [&]() -> int {
     ICHK(g, hipEventRecord(e1, g->stream));
     ICHK(g, hipEventSynchronize(e1));
@@ -74,8 +64,7 @@ int process_text_region(mals_ingest g, size_t region) {
   Scratch s;
   s.tile_sums = g->t_tile_sums.get();
   s.total = g->t_tile_sums.get() + tiles;  // one word behind the tile sums
-  hipLaunchKernelGGL(line_count_kernel, dim3((unsigned)n_blk), dim3(256), 0, g->stream, g->d_text.get(), (int64_t)region, g->t_block_counts.get());
-  ICHK(g, hipGetLastError());
+  ITRY(launch_grid(g, {(unsigned)n_blk}, line_count_kernel, g->d_text.get(), (int64_t)region, g->t_block_counts.get()));
   unsigned n_lines = 0;
   if (int rc = scan_u32(g, s, g->t_block_counts.get(), g->t_block_counts.get(), n_blk, &n_lines)) return rc;
   if (int rc = seg_end()) return rc;
@@ -106,22 +95,19 @@ int process_text_region(mals_ingest g, size_t region) {
   TextCounters* counters = reinterpret_cast<TextCounters*>(g->t_counters.get());
   ICHK(g, hipEventRecord(e0, g->stream));
   ICHK(g, hipMemsetAsync(counters, 0, sizeof(TextCounters) + 2 * sizeof(unsigned), g->stream));
-  hipLaunchKernelGGL(line_starts_kernel, dim3((unsigned)n_blk), dim3(256), 0, g->stream, g->d_text.get(), (int64_t)region, g->t_block_counts.get(),
-                     g->t_starts.get());
+  ITRY(launch_grid(g, {(unsigned)n_blk}, line_starts_kernel, g->d_text.get(), (int64_t)region, g->t_block_counts.get(), g->t_starts.get()));
   const unsigned lgrid = (unsigned)((L + 255) / 256);
   const int first = g->lines == 0 ? 1 : 0;
   // 3. parse: the bulk, then whatever it handed on
-  hipLaunchKernelGGL(parse_lines_kernel, dim3(lgrid), dim3(256), 0, g->stream, g->d_text.get(), g->t_starts.get(), (int64_t)L, (unsigned)region, first,
-                     g->t_status.get(), g->t_user.get(), g->t_item.get(), g->t_value.get(), g->t_defer.get(), counters);
-  hipLaunchKernelGGL(parse_deferred_kernel, dim3((unsigned)std::min<size_t>((L + 63) / 64, 4096)), dim3(64), 0, g->stream, g->d_text.get(),
-                     g->t_starts.get(), (int64_t)L, (unsigned)region, first, g->t_status.get(), g->t_user.get(), g->t_item.get(), g->t_value.get(), g->t_defer.get(),
-                     counters);
+  ITRY(launch_grid(g, {lgrid}, parse_lines_kernel, g->d_text.get(), g->t_starts.get(), (int64_t)L, (unsigned)region, first, g->t_status.get(), g->t_user.get(),
+                   g->t_item.get(), g->t_value.get(), g->t_defer.get(), counters));
+  ITRY(launch_grid(g, {(unsigned)std::min<size_t>((L + 63) / 64, 4096), 64}, parse_deferred_kernel, g->d_text.get(), g->t_starts.get(), (int64_t)L, (unsigned)region,
+                   first, g->t_status.get(), g->t_user.get(), g->t_item.get(), g->t_value.get(), g->t_defer.get(), counters));
   const int64_t ct = ((int64_t)L + CT_TILE - 1) / CT_TILE;  // t_flag: records per tile, then their exclusive scan
-  hipLaunchKernelGGL(line_summary_kernel, dim3((unsigned)ct), dim3(256), 0, g->stream, g->t_status.get(), (int64_t)L, g->t_flag.get(), counters);
+  ITRY(launch_grid(g, {(unsigned)ct}, line_summary_kernel, g->t_status.get(), (int64_t)L, g->t_flag.get(), counters));
   unsigned n_records = 0;
-  if (int rc = scan_u32(g, s, g->t_flag.get(), g->t_flag.get(), ct, nullptr)) return rc;
+  ITRY(scan_u32(g, s, g->t_flag.get(), g->t_flag.get(), ct, nullptr));
   ICHK(g, hipMemcpyAsync(&n_records, s.total, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
-  ICHK(g, hipGetLastError());
   TextCounters c;
   ICHK(g, hipMemcpyAsync(&c, counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
   if (int rc = seg_end()) return rc;
@@ -149,7 +135,7 @@ int process_text_region(mals_ingest g, size_t region) {
       if (k == text::ST_BAD) ++bad;
     }
   }
-  if (g->finished) free_results(g);   // any accepted text (also lines that yield no record) makes the last finish stale
+  if (g->finished) g->free_results();   // any accepted text (also lines that yield no record) makes the last finish stale
   g->bad_lines += c.bad;
   g->abort_armed = g->bad_lines > 100;
   g->lines += (int64_t)L;
@@ -161,19 +147,17 @@ int process_text_region(mals_ingest g, size_t region) {
     if (g->n + (int64_t)c.records >= MALS_INGEST_MAX_RECORDS) return text_fail(g, MALS_INVALID_ARG, "at most 2^36 records per ingest");
     if (int rc = ensure_record_capacity(g, c.records)) return rc;
     ICHK(g, hipEventRecord(e0, g->stream));
-    hipLaunchKernelGGL(compact_records_kernel, dim3((unsigned)ct), dim3(256), 0, g->stream, g->t_status.get(), g->t_flag.get(), (int64_t)L, g->t_user.get(),
-                       g->t_item.get(), g->t_value.get(), g->d_user.get() + g->n, g->d_item.get() + g->n, g->d_value.get() + g->n);
-    ICHK(g, hipGetLastError());
-    if (int rc = seg_end()) return rc;
+    ITRY(launch_grid(g, {(unsigned)ct}, compact_records_kernel, g->t_status.get(), g->t_flag.get(), (int64_t)L, g->t_user.get(), g->t_item.get(), g->t_value.get(),
+                     g->d_user.get() + g->n, g->d_item.get() + g->n, g->d_value.get() + g->n));
+    ITRY(seg_end());
     g->n += c.records;
   }
   if (c.user_tags || c.item_tags) {
     if (int rc = reserve_text(g, g->d_tags[0], g->n_tags_raw[0] + c.user_tags, g->n_tags_raw[0])) return rc;
     if (int rc = reserve_text(g, g->d_tags[1], g->n_tags_raw[1] + c.item_tags, g->n_tags_raw[1])) return rc;
     unsigned* cursors = reinterpret_cast<unsigned*>(counters + 1);
-    hipLaunchKernelGGL(collect_tags_kernel, dim3(blocks_for((int64_t)L)), dim3(256), 0, g->stream, g->t_status.get(), (int64_t)L, g->t_user.get(), g->t_item.get(),
-                       g->d_tags[0].get() + g->n_tags_raw[0], g->d_tags[1].get() + g->n_tags_raw[1], cursors);
-    ICHK(g, hipGetLastError());
+    ITRY(launch(g, (int64_t)L, collect_tags_kernel, g->t_status.get(), (int64_t)L, g->t_user.get(), g->t_item.get(), g->d_tags[0].get() + g->n_tags_raw[0],
+                g->d_tags[1].get() + g->n_tags_raw[1], cursors));
     g->n_tags_raw[0] += c.user_tags;
     g->n_tags_raw[1] += c.item_tags;
   }
@@ -200,17 +184,14 @@ int append_text_impl(mals_ingest g, const uint8_t* bytes, int64_t n_bytes, int m
     const bool last = eof && off + (int64_t)m == n_bytes;
     const size_t total = g->carry_len + m;
     if (total + TEXT_PAD > g->d_text.capacity()) ICHK(g, g->d_text.alloc(((std::max(total, block) + TEXT_PAD + 4095) / 4096) * 4096));
-    if (!g->t_ev[0]) {
-      ICHK(g, hipEventCreate(&g->t_ev[0]));
-      ICHK(g, hipEventCreate(&g->t_ev[1]));
-    }
-    ICHK(g, hipEventRecord(g->t_ev[0], g->stream));
+    if (!g->t_ev.begin) ICHK(g, g->t_ev.create());
+    ICHK(g, hipEventRecord(g->t_ev.begin, g->stream));
     if (g->carry_len) ICHK(g, hipMemcpyAsync(g->d_text.get(), g->d_carry.get(), g->carry_len, hipMemcpyDeviceToDevice, g->stream));
     if (m)
       ICHK(g, hipMemcpyAsync(g->d_text.get() + g->carry_len, bytes + off, m, mem_kind == MALS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                              g->stream));
     ICHK(g, hipMemsetAsync(g->d_text.get() + total, 0, TEXT_PAD, g->stream));
-    ICHK(g, hipEventRecord(g->t_ev[1], g->stream));
+    ICHK(g, hipEventRecord(g->t_ev.end, g->stream));
     // where the complete lines end
     size_t region;
     uint8_t last_byte = 0;
@@ -242,8 +223,8 @@ int append_text_impl(mals_ingest g, const uint8_t* bytes, int64_t n_bytes, int m
     if (int rc = process_text_region(g, region)) return rc;
     {
       float ms = 0.f;
-      ICHK(g, hipEventSynchronize(g->t_ev[1]));
-      ICHK(g, hipEventElapsedTime(&ms, g->t_ev[0], g->t_ev[1]));
+      ICHK(g, hipEventSynchronize(g->t_ev.end));
+      ICHK(g, hipEventElapsedTime(&ms, g->t_ev.begin, g->t_ev.end));
       g->stage_ms += ms;  // bringing the block in front of the kernels: PCIe for host bytes, a device copy otherwise
     }
     // the tail waits for the next block
@@ -251,10 +232,8 @@ int append_text_impl(mals_ingest g, const uint8_t* bytes, int64_t n_bytes, int m
     if (rest) {
       if (rest > g->d_carry.capacity()) ICHK(g, g->d_carry.alloc(rest + rest / 2 + 4096));
       ICHK(g, hipMemcpyAsync(g->d_carry.get(), g->d_text.get() + region, rest, hipMemcpyDeviceToDevice, g->stream));
-      ICHK(g, hipStreamSynchronize(g->stream));
-    } else {
-      ICHK(g, hipStreamSynchronize(g->stream));
     }
+    ICHK(g, hipStreamSynchronize(g->stream));
     g->carry_len = rest;
     if (m) g->carry_ends_cr = rest > 0 && last_byte == '\r';
     else if (!rest) g->carry_ends_cr = false;

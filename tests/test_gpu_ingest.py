@@ -13,9 +13,22 @@ pytestmark = pytest.mark.gpu
 NaN = np.float32("nan")
 
 
+def compare_with_oracle(g, u, i, v, thr=1.0e-4):
+    """the finished ingest g against the oracle's replay of the records"""
+    (uid, rp, col, val), (iid, cp, ccol, cval) = io.expected_matrices(u, i, v, thr)
+    c = g.counts()
+    assert c == {"records": len(u), "users": len(uid), "items": len(iid), "nnz": len(col)}
+    assert np.array_equal(g.ids(pkg.SIDE_X), uid) and np.array_equal(g.ids(pkg.SIDE_Y), iid)
+    grp, gcol, gval = g.csr(pkg.SIDE_X)
+    assert np.array_equal(grp, rp) and np.array_equal(gcol, col)
+    assert np.array_equal(gval.view(np.uint32), val.view(np.uint32))
+    gcp, gccol, gcval = g.csr(pkg.SIDE_Y)
+    assert np.array_equal(gcp, cp) and np.array_equal(gccol, ccol)
+    assert np.array_equal(gcval.view(np.uint32), cval.view(np.uint32))
+
+
 def check(u, i, v, thr=1.0e-4, part=None):
     """part: MALS_INGEST_OPT_PARTITION_RECORDS -- the finish then runs user-id range by user-id range (ingest_big_host.h)"""
-    (uid, rp, col, val), (iid, cp, ccol, cval) = io.expected_matrices(u, i, v, thr)
     with ingest.Ingest(0, thr) as g:
         if part:
             g.set_option(_lib.INGEST_OPT_PARTITION_RECORDS, part)
@@ -23,15 +36,7 @@ def check(u, i, v, thr=1.0e-4, part=None):
         g.finish()
         if part and len(u) > part:
             assert g.partitions()[0] >= 2, g.partitions()
-        c = g.counts()
-        assert c == {"records": len(u), "users": len(uid), "items": len(iid), "nnz": len(col)}
-        assert np.array_equal(g.ids(pkg.SIDE_X), uid) and np.array_equal(g.ids(pkg.SIDE_Y), iid)
-        grp, gcol, gval = g.csr(pkg.SIDE_X)
-        assert np.array_equal(grp, rp) and np.array_equal(gcol, col)
-        assert np.array_equal(gval.view(np.uint32), val.view(np.uint32))
-        gcp, gccol, gcval = g.csr(pkg.SIDE_Y)
-        assert np.array_equal(gcp, cp) and np.array_equal(gccol, ccol)
-        assert np.array_equal(gcval.view(np.uint32), cval.view(np.uint32))
+        compare_with_oracle(g, u, i, v, thr)
         return g.stats()
 
 
@@ -98,6 +103,36 @@ def test_appending_in_batches_equals_one_batch():
         b.finish()
         for side in (pkg.SIDE_X, pkg.SIDE_Y):
             assert all(np.array_equal(x, y) for x, y in zip(a.csr(side), b.csr(side)))
+
+
+def _bits(arrays):
+    return [a.view(np.uint32) if a.dtype == np.float32 else a for a in arrays]
+
+
+@pytest.mark.parametrize("part", [None, 300])
+def test_finishing_twice_gives_the_same_result(part):
+    """A second finish of the same records on the same object resets the results and reuses the workspace of the first:
+    it leaves the same matrices, tables and knownItemIDs bit for bit, and the same accounting."""
+    rng = np.random.default_rng(4097 + 50)
+    u, i, v = random_stream(rng, 4097, 50, 40, 0.2)
+    with ingest.Ingest(0) as g:
+        g.set_option(_lib.INGEST_OPT_KNOWN_ITEMS, 1)
+        if part:
+            g.set_option(_lib.INGEST_OPT_PARTITION_RECORDS, part)
+        g.append(u, i, v)
+        seen = []
+        for _ in range(2):
+            g.finish()
+            st = g.stats()
+            seen.append((g.counts(), (st["bytes_moved"], st["radix_passes"]), g.partitions(),
+                         _bits([g.ids(pkg.SIDE_X), g.ids(pkg.SIDE_Y), *g.csr(pkg.SIDE_X), *g.csr(pkg.SIDE_Y), *g.known_items()])))
+    (c0, st0, p0, a0), (c1, st1, p1, a1) = seen
+    assert c0 == c1 and c0["records"] == len(u) and c0["nnz"] > 0
+    assert st0 == st1 and st0[0] > 0 and p0 == p1
+    assert (p0[0] >= 2) if part else (p0 == (0, 0))
+    assert len(a0) == len(a1) == 10
+    for x, y in zip(a0, a1):
+        assert x.dtype == y.dtype and np.array_equal(x, y)
 
 
 def test_ingest_feeds_the_factorizer():

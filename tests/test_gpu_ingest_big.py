@@ -55,6 +55,22 @@ def test_a_user_that_does_not_fit_a_range_is_refused():
             g.finish()
 
 
+def test_a_refused_finish_leaves_the_ingest_usable():
+    """the same 5 000 records of one user: refused at 1 000 records per range, then finished on the same object once the
+    range holds them (one pipeline at 8 000), with the oracle's result"""
+    u = np.zeros(5000, np.int64)
+    i = np.arange(5000, dtype=np.int64)
+    v = np.ones(5000, np.float32)
+    with ingest.Ingest(0) as g:
+        g.set_option(_lib.INGEST_OPT_PARTITION_RECORDS, 1000)
+        g.append(u, i, v)
+        with pytest.raises(pkg.MalsError, match="one user id owns too many lines"):
+            g.finish()
+        g.set_option(_lib.INGEST_OPT_PARTITION_RECORDS, 8000)
+        g.finish()
+        rec.compare_with_oracle(g, u, i, v)
+
+
 _MORE = [(3000 + i, 2000 + 41 * (i % 71), [0.05, 0.25, 0.5, 0.75, 0.95][i % 5]) for i in range(int(os.environ.get("MALS_TEXT_SEEDS", "0")) // 4)]
 
 
