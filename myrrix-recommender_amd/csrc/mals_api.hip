@@ -763,6 +763,8 @@ int prepare_dual_host(mals_handle h, int side, mals_handle from) {
   h->rotate_f64 = (lmax + la) > 1.0e5 * (std::max(lmin, 0.0) + la);
   if (const char* ev = std::getenv("MALS_ROTATE_F64")) h->rotate_f64 = std::atoi(ev) != 0;  // tests / A-B
   h->rotate_split = k % 8 == 0 && !std::getenv("MALS_ROTATE_NO_SPLIT");
+  if (std::getenv("MALS_DEBUG_LISTS"))  // which of the rotation kernels this half-iteration runs (prepare_dual_device, launch_dual_chunk)
+    std::fprintf(stderr, "[lists] rotation forward %s, back %s\n", h->rotate_f64 ? "fp64" : (h->rotate_split ? "split" : "fp32"), h->rotate_split ? "split" : "fp32");
   if (h->rotate_split) {
     std::vector<int32_t> Bs;
     for (int op = 0; op < 2; ++op) {

@@ -41,9 +41,10 @@ def table_shape(k):
     return (4200, 0.1) if k == 1 else (6000, 0.5)
 
 
-def table(k, kind, seed=0):
-    """float32 [n, k].  Every feature is the hot one of n / k rows (+-1), so the Gramian's diagonal is level."""
-    n, p2 = table_shape(k)
+def table(k, kind, seed=0, shape=None):
+    """float32 [n, k].  Every feature is the hot one of n / k rows (+-1), so the Gramian's diagonal is level.
+    shape: another (rows, share of rows with scale 2) than table_shape(k) (tests/dual_cases.py)."""
+    n, p2 = shape or table_shape(k)
     rng = np.random.default_rng([seed, k, kind])
     f = rng.permutation(n) % k
     s = np.where(rng.random(n) < p2, 2.0, 1.0).astype(np.float32)
