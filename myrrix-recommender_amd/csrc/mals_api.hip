@@ -14,6 +14,7 @@
 #include "mals_handle.h"
 #include "hip_buffer.h"
 #include "work_plan.h"
+#include "convergence.h"
 
 #include <hip/hip_runtime.h>
 
@@ -892,17 +893,6 @@ int ensure_gramian_buffers(mals_handle h, SideState& s) {
   if (!s.Gf) HIPCHK(h, s.Gf.alloc((size_t)tri(h->T) * 256));
   if (!s.d_ymax) HIPCHK(h, s.d_ymax.alloc(YMAX_SLOTS));
   return MALS_OK;
-}
-
-// DoubleWeightedMean.increment (common/src/net/myrrix/common/stats/DoubleWeightedMean.java:73-81)
-void dwm_increment(double& total_weight, double& mean, double datum, double weight) {
-  const double old = total_weight;
-  total_weight += weight;
-  if (old <= 0) {
-    mean = datum;
-  } else {
-    mean = mean * old / total_weight + datum * weight / total_weight;
-  }
 }
 
 }  // namespace
@@ -1992,63 +1982,49 @@ int mals_sample_dots(mals_handle h, const int64_t* test_users, int32_t n_test_us
   return MALS_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// mals_factorize's side of the loop in convergence.h: one handle, its own cancel flag, n_local rows per half
+struct HandleFactorize {
+  mals_handle h;
+  int64_t rows0 = 0, nnz0 = 0;
+  int fail(int code, const char* msg) { return ::fail(h, code, msg); }
+  void clear_cancel() { h->cancelled.store(0); }
+  int cancelled() { return h->cancelled.load() ? ::fail(h, MALS_CANCELLED, "cancelled") : MALS_OK; }
+  int half_iteration(int side) { return mals_half_iteration(h, side); }
+  int sample_dots(const int64_t* users, int32_t n_users, const int64_t* items, int32_t n_items, double* out) {
+    return mals_sample_dots(h, users, n_users, items, n_items, out);
+  }
+  mals_iteration_fn callback(void** user) {
+    *user = h->iter_user;
+    return h->iter_fn;
+  }
+  void count(int point) {
+    if (point == 0) rows0 = h->stats.rows_solved, nnz0 = h->stats.nnz_gathered;
+  }
+  void report(mals_iteration_info* info) {
+    info->x_rows = h->side[MALS_SIDE_X].n_local;
+    info->y_rows = h->side[MALS_SIDE_Y].n_local;
+    info->entries_gathered = h->stats.nnz_gathered - nnz0;
+    info->algorithmic_bytes = (double)info->entries_gathered * (4.0 * h->cfg.features + 8.0) +
+                              (double)(h->stats.rows_solved - rows0) * (4.0 * h->cfg.features + 8.0);
+    info->devices = 1;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
 int mals_factorize(mals_handle h, double convergence_threshold, int32_t max_iterations, int32_t random_y, int32_t iterate,
                    const int64_t* test_users, int32_t n_test_users, const int64_t* test_items, int32_t n_test_items,
                    int32_t* iterations_out, double* convergence_out) {
   if (!h) return MALS_INVALID_ARG;
-  if (iterations_out) *iterations_out = 0;
-  if (convergence_out) *convergence_out = std::numeric_limits<double>::quiet_NaN();
-  // ALS:140-141 threshold must be in (0,1)
-  if (!(convergence_threshold > 0.0 && convergence_threshold < 1.0))
-    return fail(h, MALS_INVALID_ARG, "threshold must be in (0,1)");
-  if (n_test_users < 0 || n_test_items < 0 || (n_test_users > 0 && !test_users) || (n_test_items > 0 && !test_items))
-    return fail(h, MALS_INVALID_ARG, "bad convergence sample");
-  h->cancelled.store(0);
-  if (!iterate) return mals_half_iteration(h, MALS_SIDE_X);  // ALS:196-204
-  std::vector<double> est((size_t)n_test_users * (size_t)n_test_items, 0.0);  // ALS:215: X empty => 0
-  std::vector<double> fresh(est.size());
-  int it = 0;
-  for (;;) {
-    const double t_it = now_us();
-    const int64_t rows0 = h->stats.rows_solved, nnz0 = h->stats.nnz_gathered;
-    if (h->cancelled.load()) return fail(h, MALS_CANCELLED, "cancelled");
-    if (int rc = mals_half_iteration(h, MALS_SIDE_X)) return rc;  // ALS:228
-    if (h->cancelled.load()) return fail(h, MALS_CANCELLED, "cancelled");
-    if (int rc = mals_half_iteration(h, MALS_SIDE_Y)) return rc;  // ALS:229
-    // the sample dots on the device (ALS:234), the order-dependent running mean on the host (ALS:237)
-    if (int rc = mals_sample_dots(h, test_users, n_test_users, test_items, n_test_items, fresh.data())) return rc;
-    double tw = 0.0, mean = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; i < n_test_users; ++i) {
-      for (int j = 0; j < n_test_items; ++j) {  // ALS:231-238
-        const double nv = fresh[(size_t)i * n_test_items + j];
-        const double ov = est[(size_t)i * n_test_items + j];
-        est[(size_t)i * n_test_items + j] = nv;
-        dwm_increment(tw, mean, std::fabs(nv - ov), nv > 0.0 ? nv : 0.0);
-      }
-    }
-    ++it;
-    if (iterations_out) *iterations_out = it;
-    if (convergence_out) *convergence_out = mean;
-    if (h->iter_fn) {   // what the reference logs per iteration (ALS:241-246, 351-358)
-      mals_iteration_info info;
-      std::memset(&info, 0, sizeof(info));
-      info.struct_size = (int32_t)sizeof(info);
-      info.iteration = it;
-      info.avg_abs_difference = mean;
-      info.seconds = (now_us() - t_it) * 1e-6;
-      info.x_rows = h->side[MALS_SIDE_X].n_local;
-      info.y_rows = h->side[MALS_SIDE_Y].n_local;
-      info.entries_gathered = h->stats.nnz_gathered - nnz0;
-      info.algorithmic_bytes = (double)info.entries_gathered * (4.0 * h->cfg.features + 8.0) +
-                               (double)(h->stats.rows_solved - rows0) * (4.0 * h->cfg.features + 8.0);
-      info.devices = 1;
-      h->iter_fn(h->iter_user, &info);
-    }
-    if (max_iterations > 0 && it >= max_iterations) break;                 // ALS:242-245
-    if (!std::isfinite(mean)) break;                                       // ALS:248-251
-    if (!(random_y && it == 1) && mean < convergence_threshold) break;     // ALS:253-256
-  }
-  return MALS_OK;
+  HandleFactorize d{h};
+  return factorize_loop(d, convergence_threshold, max_iterations, random_y, iterate, test_users, n_test_users, test_items, n_test_items,
+                        iterations_out, convergence_out);
 }
 
 int mals_reconstruction_error(mals_handle h, double* sum_out, int64_t* count_out) {

@@ -15,6 +15,8 @@
 #include "mals_internal.h"
 #include "hip_buffer.h"
 #include "factor_digest.h"
+#include "group_plan.h"
+#include "convergence.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -22,7 +24,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -31,6 +32,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -198,24 +200,41 @@ int mfail(mals_group g, const Member& mb, int rc) {
     if ((side) != MALS_SIDE_X && (side) != MALS_SIDE_Y) return gfail(g, MALS_INVALID_ARG, "side must be MALS_SIDE_X or _Y"); \
   } while (0)
 
-// the rank that holds user u's known items: the slice with its row; users past the installed matrix (rows the replicas
-// grew by, mals_group_grow_factor_rows) are the last rank's
-int owner_of(const std::vector<int64_t>& bounds, int64_t u) {
-  const int world = (int)bounds.size() - 1;
-  return std::min(world - 1, (int)(std::upper_bound(bounds.begin(), bounds.end(), u) - bounds.begin()) - 1);
-}
-
 int64_t chunk_rows_of(const mals_group g, int side, int rank) {
-  const int64_t n = g->bounds[side][(size_t)rank + 1] - g->bounds[side][(size_t)rank];
-  return std::max<int64_t>(1, (n + g->side_chunks[side] - 1) / g->side_chunks[side]);
+  return mals::chunk_rows_of(g->bounds[side][(size_t)rank], g->bounds[side][(size_t)rank + 1], g->side_chunks[side]);
 }
 
 // rows [lo, hi) (global) of chunk c of rank's slice
 void chunk_range(const mals_group g, int side, int rank, int c, int64_t* lo, int64_t* hi) {
-  const int64_t b0 = g->bounds[side][(size_t)rank], b1 = g->bounds[side][(size_t)rank + 1];
-  const int64_t cr = chunk_rows_of(g, side, rank);
-  *lo = std::min(b1, b0 + (int64_t)c * cr);
-  *hi = std::min(b1, b0 + (int64_t)(c + 1) * cr);
+  mals::chunk_range(g->bounds[side][(size_t)rank], g->bounds[side][(size_t)rank + 1], g->side_chunks[side], c, lo, hi);
+}
+
+// Every local member in turn with its device current (one thread drives all devices: the set-device before a member's HIP
+// calls is part of their correctness).  body(member) or body(member, i) -> status; the first failure ends the loop.
+template <class Body>
+int for_members(mals_group g, Body&& body) {
+  for (size_t i = 0; i < g->m.size(); ++i) {
+    Member& mb = g->m[i];
+    GHIP(g, hipSetDevice(mb.device));
+    int rc;
+    if constexpr (std::is_invocable_v<Body, Member&, size_t>) rc = body(mb, i); else rc = body(mb);
+    if (rc) return rc;
+  }
+  return MALS_OK;
+}
+
+// `to` goes on behind everything `from` holds now
+int hand_off(mals_group g, hipStream_t from, hipEvent_t ev, hipStream_t to) {
+  GHIP(g, hipEventRecord(ev, from));
+  GHIP(g, hipStreamWaitEvent(to, ev, 0));
+  return MALS_OK;
+}
+
+int sync_comm(mals_group g) {
+  return for_members(g, [&](Member& mb) -> int {
+    GHIP(g, hipStreamSynchronize(mb.comm));
+    return MALS_OK;
+  });
 }
 
 int init_member(mals_group g, Member& mb, const mals_config& cfg, int device, int rank) {
@@ -264,42 +283,112 @@ void destroy_member(Member& mb) {
   mb = Member();   // and the member's buffers, with its device current
 }
 
-// out[i] = op over all ranks of the members' d_stat[0..n) (op: 0 = sum, 1 = max); result in every d_stat
-int allreduce_stat(mals_group g, int n, int op) {
+// ---- the collectives: each stated once, with both transports (RCCL, peer copy) inside ----
+
+// One ncclGroupStart/End around the RCCL calls of every local member (one thread drives all devices).  call(member, i) issues
+// local member i's calls on ITS comm stream -- a communicator is never used from two streams at once -- and returns the first
+// result that is not ncclSuccess: the group is then ended, that result ignored, and the failure is "<label>: <RCCL's text>".
+template <class Call>
+int rccl_group(mals_group g, const char* label, Call&& call) {
+  GNCCL(g, g_rccl.GroupStart());
+  for (size_t i = 0; i < g->m.size(); ++i) {
+    const ncclResult_t r = call(g->m[i], i);
+    if (r != ncclSuccess) {
+      (void)g_rccl.GroupEnd();
+      return gfail(g, MALS_COMM_ERROR, std::string(label) + ": " + g_rccl.GetErrorString(r));
+    }
+  }
+  GNCCL(g, g_rccl.GroupEnd());
+  return MALS_OK;
+}
+
+// one all-reduce in place: dev[i] = local member i's n elements of ncclDouble or ncclInt64 (ncclSum, ncclMax) or ncclFloat (ncclMax
+// of non-negative values)
+struct Reduce {
+  void* const* dev;
+  size_t n;
+  ncclDataType_t type;
+  ncclRedOp_t op;
+  size_t bytes() const { return n * (type == ncclFloat ? sizeof(float) : sizeof(double)); }
+};
+
+void reduce_identity(const Reduce& r, void* acc) {
+  if (r.type == ncclDouble) std::fill_n(static_cast<double*>(acc), r.n, r.op == ncclMax ? -std::numeric_limits<double>::infinity() : 0.0);
+  else if (r.type == ncclInt64) std::fill_n(static_cast<int64_t*>(acc), r.n, r.op == ncclMax ? std::numeric_limits<int64_t>::min() : 0);
+  else std::fill_n(static_cast<float*>(acc), r.n, 0.f);
+}
+
+template <class T>
+void reduce_fold(T* acc, const T* v, size_t n, ncclRedOp_t op) {
+  for (size_t i = 0; i < n; ++i) acc[i] = op == ncclMax ? std::max(acc[i], v[i]) : acc[i] + v[i];
+}
+
+void reduce_fold(const Reduce& r, void* acc, const void* v) {
+  if (r.type == ncclDouble) return reduce_fold(static_cast<double*>(acc), static_cast<const double*>(v), r.n, r.op);
+  if (r.type == ncclInt64) return reduce_fold(static_cast<int64_t*>(acc), static_cast<const int64_t*>(v), r.n, r.op);
+  float* a = static_cast<float*>(acc);
+  const float* f = static_cast<const float*>(v);
+  for (size_t i = 0; i < r.n; ++i)
+    if (!(f[i] <= a[i])) a[i] = f[i];   // an inf pattern wins and makes the consumer fall back
+}
+
+// when an all-reduce over RCCL counts as done: the host waits for the comm streams (status words, value statistics, the
+// ingest's counters), or -- no host wait -- the comm streams start behind the compute streams and the compute streams go on
+// behind the comm streams (the Gramian: partial Gramian -> all-reduce behind whatever exchange is still queued -> solve)
+enum class Done { HOST_WAITS, COMPUTE_FOLLOWS };
+
+// The all-reduces `parts` over every rank, the results in every member's buffers.  Nothing to do for a one-rank group without
+// a communicator.  RCCL: all parts of all local members in ONE group, on the comm streams.  Peer copy: staged through the
+// host on the compute streams and folded in member order 0, 1, ... -- that fixed order makes this backend deterministic --
+// and complete when it returns, whatever `done` says.
+int all_reduce(mals_group g, std::initializer_list<Reduce> parts, Done done) {
   if (g->world == 1 && !g->m[0].nccl) return MALS_OK;
   if (g->backend == MALS_GROUP_PEER_COPY) {
-    std::vector<double> acc((size_t)n, op ? -std::numeric_limits<double>::infinity() : 0.0), tmp((size_t)n);
-    for (Member& mb : g->m) {
-      GHIP(g, hipSetDevice(mb.device));
-      GHIP(g, hipMemcpyAsync(tmp.data(), mb.d_stat.get(), sizeof(double) * n, hipMemcpyDeviceToHost, mb.compute));
-      GHIP(g, hipStreamSynchronize(mb.compute));
-      for (int i = 0; i < n; ++i) acc[(size_t)i] = op ? std::max(acc[(size_t)i], tmp[(size_t)i]) : acc[(size_t)i] + tmp[(size_t)i];
+    std::vector<std::vector<double>> acc, tmp;   // 8-byte words under elements of any of the three types
+    for (const Reduce& r : parts) {
+      acc.emplace_back((r.bytes() + 7) / 8);
+      tmp.emplace_back((r.bytes() + 7) / 8);
+      reduce_identity(r, acc.back().data());
     }
-    for (Member& mb : g->m) {
+    for (size_t i = 0; i < g->m.size(); ++i) {
+      Member& mb = g->m[i];
       GHIP(g, hipSetDevice(mb.device));
-      GHIP(g, hipMemcpyAsync(mb.d_stat.get(), acc.data(), sizeof(double) * n, hipMemcpyHostToDevice, mb.compute));
+      size_t p = 0;
+      for (const Reduce& r : parts) GHIP(g, hipMemcpyAsync(tmp[p++].data(), r.dev[i], r.bytes(), hipMemcpyDeviceToHost, mb.compute));
+      GHIP(g, hipStreamSynchronize(mb.compute));
+      p = 0;
+      for (const Reduce& r : parts) reduce_fold(r, acc[p].data(), tmp[p].data()), ++p;
+    }
+    for (size_t i = 0; i < g->m.size(); ++i) {
+      Member& mb = g->m[i];
+      GHIP(g, hipSetDevice(mb.device));
+      size_t p = 0;
+      for (const Reduce& r : parts) GHIP(g, hipMemcpyAsync(r.dev[i], acc[p++].data(), r.bytes(), hipMemcpyHostToDevice, mb.compute));
       GHIP(g, hipStreamSynchronize(mb.compute));
     }
     return MALS_OK;
   }
-  // every RCCL call of a rank goes to ITS comm stream: one communicator is never used from two streams at once
-  GNCCL(g, g_rccl.GroupStart());
-  for (Member& mb : g->m) {
-    const ncclResult_t r = g_rccl.AllReduce(mb.d_stat.get(), mb.d_stat.get(), (size_t)n, ncclDouble, op ? ncclMax : ncclSum, mb.nccl, mb.comm);
-    if (r != ncclSuccess) {
-      (void)g_rccl.GroupEnd();
-      return gfail(g, MALS_COMM_ERROR, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
-    }
-  }
-  GNCCL(g, g_rccl.GroupEnd());
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipStreamSynchronize(mb.comm));
-  }
-  return MALS_OK;
+  if (done == Done::COMPUTE_FOLLOWS)
+    if (int rc = for_members(g, [&](Member& mb) { return hand_off(g, mb.compute, mb.ev_solved, mb.comm); })) return rc;
+  const int rc = rccl_group(g, "ncclAllReduce", [&](Member& mb, size_t i) {
+    ncclResult_t r = ncclSuccess;
+    for (const Reduce& p : parts)
+      if (r == ncclSuccess) r = g_rccl.AllReduce(p.dev[i], p.dev[i], p.n, p.type, p.op, mb.nccl, mb.comm);
+    return r;
+  });
+  if (rc != MALS_OK) return rc;
+  if (done == Done::HOST_WAITS) return sync_comm(g);
+  return for_members(g, [&](Member& mb) { return hand_off(g, mb.comm, mb.ev_exchanged, mb.compute); });
 }
 
-// every member's d_stat[0..n) <- host values (one per member), then all-reduce, then read back (member 0)
+// the d_stat words of every local member
+std::vector<void*> stat_words(mals_group g) {
+  std::vector<void*> dev;
+  for (Member& mb : g->m) dev.push_back(mb.d_stat.get());
+  return dev;
+}
+
+// every member's d_stat[0..n) <- host values (one per member), then all-reduce (op: 0 = sum, 1 = max), then read back (member 0)
 int allreduce_host(mals_group g, const std::vector<std::vector<double>>& per_member, int n, int op, double* out) {
   for (size_t i = 0; i < g->m.size(); ++i) {
     Member& mb = g->m[i];
@@ -307,7 +396,8 @@ int allreduce_host(mals_group g, const std::vector<std::vector<double>>& per_mem
     GHIP(g, hipMemcpyAsync(mb.d_stat.get(), per_member[i].data(), sizeof(double) * n, hipMemcpyHostToDevice, mb.compute));
     GHIP(g, hipStreamSynchronize(mb.compute));  // the source is a pageable temporary
   }
-  if (int rc = allreduce_stat(g, n, op)) return rc;
+  const std::vector<void*> dev = stat_words(g);
+  if (int rc = all_reduce(g, {Reduce{dev.data(), (size_t)n, ncclDouble, op ? ncclMax : ncclSum}}, Done::HOST_WAITS)) return rc;
   Member& m0 = g->m[0];
   GHIP(g, hipSetDevice(m0.device));
   GHIP(g, hipMemcpyAsync(out, m0.d_stat.get(), sizeof(double) * n, hipMemcpyDeviceToHost, m0.compute));
@@ -358,148 +448,159 @@ int refresh_replica_ptrs(mals_group g, int side) {
   return MALS_OK;
 }
 
-// slices planned, every member told its chunking; called with the full row_ptr on the host
-int plan_side(mals_group g, int side, const int64_t* row_ptr, int64_t n_rows) {
-  g->n_rows[side] = n_rows;
+// slices at given bounds: every member told its chunking
+int set_side_bounds(mals_group g, int side, const std::vector<int64_t>& bounds) {
+  g->n_rows[side] = bounds.back();
   g->side_chunks[side] = g->exchange_chunks;
-  g->bounds[side].assign((size_t)g->world + 1, 0);
-  if (int rc = mals_plan_shards(row_ptr, n_rows, g->world, -1.0, g->cfg.features, g->bounds[side].data()))
-    return gfail(g, rc, "mals_plan_shards failed");
+  g->bounds[side] = bounds;
   for (Member& mb : g->m)
     if (int rc = mals_set_chunk_rows(mb.h, side, chunk_rows_of(g, side, mb.rank))) return mfail(g, mb, rc);
   return MALS_OK;
+}
+
+// slices planned from the full row_ptr on the host, then set
+int plan_side(mals_group g, int side, const int64_t* row_ptr, int64_t n_rows) {
+  std::vector<int64_t> bounds((size_t)g->world + 1, 0);
+  if (int rc = mals_plan_shards(row_ptr, n_rows, g->world, -1.0, g->cfg.features, bounds.data())) return gfail(g, rc, "mals_plan_shards failed");
+  return set_side_bounds(g, side, bounds);
+}
+
+// The compute streams behind the previous exchange: a half-iteration's gather reads every row of the opposite replica.
+int await_exchange(mals_group g) {
+  if (int rc = for_members(g, [&](Member& mb) -> int {
+        GHIP(g, hipStreamWaitEvent(mb.compute, mb.ev_exchanged, 0));
+        return MALS_OK;
+      }))
+    return rc;
+  if (!(g->single_process && g->backend == MALS_GROUP_PEER_COPY)) return MALS_OK;
+  // peer copies INTO a replica run on the SOURCE's comm stream: every member also waits for every other member's exchange
+  for (Member& mb : g->m)
+    for (Member& other : g->m) {
+      GHIP(g, hipSetDevice(mb.device));
+      GHIP(g, hipStreamWaitEvent(mb.compute, other.ev_exchanged, 0));
+    }
+  return MALS_OK;
+}
+
+// ... and the event they wait for: everything the comm streams hold now (the chunks of an exchange) is in
+int mark_exchanged(mals_group g) {
+  return for_members(g, [&](Member& mb) -> int {
+    GHIP(g, hipEventRecord(mb.ev_exchanged, mb.comm));
+    return MALS_OK;
+  });
 }
 
 // The freshly solved rows of chunk c of every slice into every replica (comm streams).
 int exchange_chunk(mals_group g, int side, int c) {
   const int k = g->cfg.features;
   if (g->world == 1) return MALS_OK;
-  if (g->backend == MALS_GROUP_PEER_COPY) {
-    for (Member& src : g->m) {
+  if (g->backend == MALS_GROUP_PEER_COPY)
+    return for_members(g, [&](Member& src) -> int {
       int64_t lo, hi;
       chunk_range(g, side, src.rank, c, &lo, &hi);
-      if (hi <= lo) continue;
-      GHIP(g, hipSetDevice(src.device));
-      for (Member& dst : g->m) {
-        if (dst.rank == src.rank) continue;
-        GHIP(g, hipMemcpyPeerAsync(dst.F[side] + lo * k, dst.device, src.F[side] + lo * k, src.device, sizeof(float) * (size_t)(hi - lo) * k,
-                                   src.comm));
-      }
-    }
-    return MALS_OK;
-  }
-  GNCCL(g, g_rccl.GroupStart());
-  for (Member& mb : g->m) {
+      for (Member& dst : g->m)
+        if (dst.rank != src.rank && hi > lo)
+          GHIP(g, hipMemcpyPeerAsync(dst.F[side] + lo * k, dst.device, src.F[side] + lo * k, src.device, sizeof(float) * (size_t)(hi - lo) * k,
+                                     src.comm));
+      return MALS_OK;
+    });
+  return rccl_group(g, "ncclSend/ncclRecv", [&](Member& mb, size_t) {
     int64_t lo, hi;
     chunk_range(g, side, mb.rank, c, &lo, &hi);
-    for (int q = 0; q < g->world; ++q) {
+    ncclResult_t r = ncclSuccess;
+    for (int q = 0; q < g->world && r == ncclSuccess; ++q) {
       if (q == mb.rank) continue;
-      ncclResult_t r = ncclSuccess;
       if (hi > lo) r = g_rccl.Send(mb.F[side] + lo * k, (size_t)(hi - lo) * k, ncclFloat, q, mb.nccl, mb.comm);
       int64_t qlo, qhi;
       chunk_range(g, side, q, c, &qlo, &qhi);
       if (r == ncclSuccess && qhi > qlo) r = g_rccl.Recv(mb.F[side] + qlo * k, (size_t)(qhi - qlo) * k, ncclFloat, q, mb.nccl, mb.comm);
-      if (r != ncclSuccess) {
-        (void)g_rccl.GroupEnd();
-        return gfail(g, MALS_COMM_ERROR, std::string("ncclSend/ncclRecv: ") + g_rccl.GetErrorString(r));
-      }
     }
-  }
-  GNCCL(g, g_rccl.GroupEnd());
-  return MALS_OK;
+    return r;
+  });
 }
+
+// The first LOCAL failure of a half-iteration (MALS_OOM, MALS_INVALID_ARG ... of one member) and its text.  Such a failure
+// never leaves a rank between two collectives: the member contributes zeros or skips its solves, every rank's calls stay
+// matched, and the status is agreed at the end of the half-iteration.
+struct LocalFailure {
+  int rc = MALS_OK;
+  std::string msg;
+  void note(const Member& mb, int code) {
+    if (rc != MALS_OK) return;
+    rc = code;
+    msg = std::string("rank ") + std::to_string(mb.rank) + ": " + mals_last_error(mb.h);
+  }
+};
 
 // G = sum over ranks of the partial Gramians of `side`'s replica, installed on every member.  Every
 // replica is complete when this runs (the caller has waited for the exchange), so the rows -- stale Y rows
 // behind the matrix included (ALS:304-308) -- are simply cut into `world` equal ranges: the work of M^T M
 // is proportional to rows, not to entries.
-// A LOCAL failure of a member's partial Gramian or of installing the sum (MALS_OOM ...) does not leave the collective:
-// the member contributes zeros, every rank's all-reduces stay matched, and the failure is handed back through
-// local_rc / local_msg for the caller to skip the solves and agree on the status at the end of the half-iteration.
-// The return value is for failures that end the half-iteration on the spot (communication, device).
-int group_gramian(mals_group g, int side, int* local_rc, std::string* local_msg) {
-  auto member_failed = [&](const Member& mb, int rc) {
-    if (*local_rc == MALS_OK) {
-      *local_rc = rc;
-      *local_msg = std::string("rank ") + std::to_string(mb.rank) + ": " + mals_last_error(mb.h);
-    }
-  };
-  const int k = g->cfg.features;
-  const size_t kk = (size_t)k * k;
+// A LOCAL failure of a member's partial Gramian or of installing the sum goes to `local` (the member contributes zeros); the
+// return value is for failures that end the half-iteration on the spot (communication, device).
+int group_gramian(mals_group g, int side, LocalFailure& local) {
+  const size_t kk = (size_t)g->cfg.features * g->cfg.features, ns = (size_t)malsi_ymax_slots();
   const int64_t per = (g->n_total[side] + g->world - 1) / g->world;
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
-    const int64_t r0 = std::min(g->n_total[side], per * mb.rank);
-    const int64_t r1 = std::min(g->n_total[side], per * (mb.rank + 1));
-    // the kernels that form the partial Gramian also record the largest |element| of their rows: summed Gramian + the
-    // maximum over all ranks give every member the exact operand bound of the split-precision gather (instead of
-    // sqrt(max_f G_ff), which at 1e8 rows is 13 binades loose)
-    GHIP(g, hipMemsetAsync(mb.d_ymax.get(), 0, sizeof(float) * (size_t)malsi_ymax_slots(), mb.compute));
-    int prc = MALS_OK;
-    if (r1 > r0) {
-      prc = malsi_gramian_partial(mb.h, side, r0, r1 - r0, mb.d_gp.get(), reinterpret_cast<unsigned*>(mb.d_ymax.get()));
-      if (prc == MALS_HIP_ERROR) return mfail(g, mb, prc);
-      if (prc != MALS_OK) member_failed(mb, prc);
-    }
-    if (r1 <= r0 || prc != MALS_OK) GHIP(g, hipMemsetAsync(mb.d_gp.get(), 0, sizeof(double) * kk, mb.compute));
-  }
-  if (g->world > 1 || g->m[0].nccl) {
-    if (g->backend == MALS_GROUP_PEER_COPY) {  // fixed summation order (rank 0, 1, ...): deterministic
-      std::vector<double> acc(kk, 0.0), tmp(kk);
-      const size_t ns = (size_t)malsi_ymax_slots();
-      std::vector<float> ymax(ns, 0.f), ytmp(ns, 0.f);
-      for (Member& mb : g->m) {
-        GHIP(g, hipSetDevice(mb.device));
-        GHIP(g, hipMemcpyAsync(tmp.data(), mb.d_gp.get(), sizeof(double) * kk, hipMemcpyDeviceToHost, mb.compute));
-        GHIP(g, hipMemcpyAsync(ytmp.data(), mb.d_ymax.get(), sizeof(float) * ns, hipMemcpyDeviceToHost, mb.compute));
-        GHIP(g, hipStreamSynchronize(mb.compute));
-        for (size_t i = 0; i < kk; ++i) acc[i] += tmp[i];
-        for (size_t i = 0; i < ns; ++i)
-          if (!(ytmp[i] <= ymax[i])) ymax[i] = ytmp[i];   // an inf pattern wins and makes the consumer fall back
-      }
-      for (Member& mb : g->m) {
-        GHIP(g, hipSetDevice(mb.device));
-        GHIP(g, hipMemcpyAsync(mb.d_gp.get(), acc.data(), sizeof(double) * kk, hipMemcpyHostToDevice, mb.compute));
-        GHIP(g, hipMemcpyAsync(mb.d_ymax.get(), ymax.data(), sizeof(float) * ns, hipMemcpyHostToDevice, mb.compute));
-        GHIP(g, hipStreamSynchronize(mb.compute));
-      }
-    } else {
-      // partial Gramian (compute stream) -> all-reduce (comm stream, behind whatever exchange is still on it) -> compute
-      for (Member& mb : g->m) {
-        GHIP(g, hipSetDevice(mb.device));
-        GHIP(g, hipEventRecord(mb.ev_solved, mb.compute));
-        GHIP(g, hipStreamWaitEvent(mb.comm, mb.ev_solved, 0));
-      }
-      GNCCL(g, g_rccl.GroupStart());
-      for (Member& mb : g->m) {
-        ncclResult_t r = g_rccl.AllReduce(mb.d_gp.get(), mb.d_gp.get(), kk, ncclDouble, ncclSum, mb.nccl, mb.comm);
-        if (r == ncclSuccess) r = g_rccl.AllReduce(mb.d_ymax.get(), mb.d_ymax.get(), (size_t)malsi_ymax_slots(), ncclFloat, ncclMax, mb.nccl, mb.comm);
-        if (r != ncclSuccess) {
-          (void)g_rccl.GroupEnd();
-          return gfail(g, MALS_COMM_ERROR, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
+  std::vector<void*> gp, ymax;
+  if (int rc = for_members(g, [&](Member& mb) -> int {
+        const int64_t r0 = std::min(g->n_total[side], per * mb.rank);
+        const int64_t r1 = std::min(g->n_total[side], per * (mb.rank + 1));
+        // the kernels that form the partial Gramian also record the largest |element| of their rows: summed Gramian + the
+        // maximum over all ranks give every member the exact operand bound of the split-precision gather (instead of
+        // sqrt(max_f G_ff), which at 1e8 rows is 13 binades loose)
+        GHIP(g, hipMemsetAsync(mb.d_ymax.get(), 0, sizeof(float) * ns, mb.compute));
+        int prc = MALS_OK;
+        if (r1 > r0) {
+          prc = malsi_gramian_partial(mb.h, side, r0, r1 - r0, mb.d_gp.get(), reinterpret_cast<unsigned*>(mb.d_ymax.get()));
+          if (prc == MALS_HIP_ERROR) return mfail(g, mb, prc);
+          if (prc != MALS_OK) local.note(mb, prc);
         }
-      }
-      GNCCL(g, g_rccl.GroupEnd());
-      for (Member& mb : g->m) {
-        GHIP(g, hipSetDevice(mb.device));
-        GHIP(g, hipEventRecord(mb.ev_exchanged, mb.comm));
-        GHIP(g, hipStreamWaitEvent(mb.compute, mb.ev_exchanged, 0));
-      }
-    }
-  }
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
+        if (r1 <= r0 || prc != MALS_OK) GHIP(g, hipMemsetAsync(mb.d_gp.get(), 0, sizeof(double) * kk, mb.compute));
+        gp.push_back(mb.d_gp.get());
+        ymax.push_back(mb.d_ymax.get());
+        return MALS_OK;
+      }))
+    return rc;
+  if (int rc = all_reduce(g, {Reduce{gp.data(), kk, ncclDouble, ncclSum}, Reduce{ymax.data(), ns, ncclFloat, ncclMax}}, Done::COMPUTE_FOLLOWS))
+    return rc;
+  return for_members(g, [&](Member& mb) -> int {
     if (int rc = malsi_set_gramian(mb.h, side, mb.d_gp.get(), MALS_MEM_DEVICE, reinterpret_cast<const unsigned*>(mb.d_ymax.get()))) {
       if (rc == MALS_HIP_ERROR) return mfail(g, mb, rc);
-      member_failed(mb, rc);
+      local.note(mb, rc);
     }
-  }
+    return MALS_OK;
+  });
+}
+
+// "This member's n elements at src on device src_dev": src itself when it lives on the member's device and no copy is forced,
+// else a copy in `own`, enqueued on the member's compute stream (*copied: the caller waits for that stream before the use).
+template <class T>
+int member_slice(mals_group g, Member& mb, const T* src, int src_dev, bool force_copy, int64_t n, mals::DeviceBuffer<T>& own, const T** out,
+                 bool* copied) {
+  *out = src;
+  if (n <= 0 || (mb.device == src_dev && !force_copy)) return MALS_OK;
+  GHIP(g, own.alloc((size_t)n));
+  GHIP(g, hipMemcpyPeerAsync(own.get(), mb.device, src, src_dev, sizeof(T) * (size_t)n, mb.compute));
+  *out = own.get();
+  *copied = true;
   return MALS_OK;
 }
 
-int finish_matrix(mals_group g, int side) {
-  if (int rc = sync_value_stats(g, side)) return rc;
+// a slice's rebased row pointers on the member's device
+int upload_row_ptr(mals_group g, mals::DeviceBuffer<int64_t>& dst, const std::vector<int64_t>& local) {
+  GHIP(g, dst.alloc(local.size()));
+  GHIP(g, hipMemcpy(dst.get(), local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
   return MALS_OK;
+}
+
+// what both create calls do when one of their steps failed
+int create_failed(mals_group g, const char* call, int rc) {
+  std::fprintf(stderr, "%s: %s\n", call, g->err.c_str());
+  malsi_set_create_error((std::string(call) + ": " + g->err).c_str());
+  for (Member& mb : g->m) destroy_member(mb);
+  delete g;
+  (void)hipGetLastError();   // a failed create leaves no sticky error behind for the next group of this process
+  return rc;
 }
 
 }  // namespace
@@ -508,27 +609,7 @@ int finish_matrix(mals_group g, int side) {
 extern "C" {
 
 int mals_plan_shards(const int64_t* row_ptr, int64_t n_rows, int32_t world, double row_cost, int32_t features, int64_t* bounds_out) {
-  if (!row_ptr || !bounds_out || n_rows < 0 || world <= 0) return MALS_INVALID_ARG;
-  if (row_cost < 0.0) row_cost = features > 0 ? (double)features * features / 200.0 : 0.0;
-  const double total = (double)(row_ptr[n_rows] - row_ptr[0]) + row_cost * (double)n_rows;
-  bounds_out[0] = 0;
-  int64_t r = 0;
-  for (int j = 1; j < world; ++j) {
-    const double target = total * (double)j / (double)world;
-    // first r with cost(rows [0, r)) >= target, then the closer of r-1 and r
-    auto cost = [&](int64_t rr) { return (double)(row_ptr[rr] - row_ptr[0]) + row_cost * (double)rr; };
-    int64_t lo = r, hi = n_rows;
-    while (lo < hi) {
-      const int64_t mid = lo + (hi - lo) / 2;
-      if (cost(mid) >= target) hi = mid; else lo = mid + 1;
-    }
-    int64_t b = lo;
-    if (b > r && target - cost(b - 1) < cost(b) - target) b = b - 1;
-    bounds_out[j] = std::max(b, r);
-    r = bounds_out[j];
-  }
-  bounds_out[world] = n_rows;
-  return MALS_OK;
+  return mals::plan_shards(row_ptr, n_rows, world, row_cost, features, bounds_out) ? MALS_OK : MALS_INVALID_ARG;
 }
 
 int mals_group_create(const mals_config* cfg, const int32_t* devices, int32_t n_devices, int32_t backend, mals_group* out) {
@@ -577,14 +658,7 @@ int mals_group_create(const mals_config* cfg, const int32_t* devices, int32_t n_
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();  // copies then stage through the host
       }
   }
-  if (rc != MALS_OK) {
-    std::fprintf(stderr, "mals_group_create: %s\n", g->err.c_str());
-    malsi_set_create_error(("mals_group_create: " + g->err).c_str());
-    for (Member& mb : g->m) destroy_member(mb);
-    delete g;
-    (void)hipGetLastError();   // a failed create leaves no sticky error behind for the next group of this process
-    return rc;
-  }
+  if (rc != MALS_OK) return create_failed(g, "mals_group_create", rc);
   malsi_set_create_error("");
   *out = g;
   return MALS_OK;
@@ -636,14 +710,7 @@ int mals_group_create_rank(const mals_config* cfg, int32_t world, int32_t rank, 
       if (r != ncclSuccess) rc = gfail(g, MALS_COMM_ERROR, std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r));
     }
   }
-  if (rc != MALS_OK) {
-    std::fprintf(stderr, "mals_group_create_rank: %s\n", g->err.c_str());
-    malsi_set_create_error(("mals_group_create_rank: " + g->err).c_str());
-    destroy_member(g->m[0]);
-    delete g;
-    (void)hipGetLastError();
-    return rc;
-  }
+  if (rc != MALS_OK) return create_failed(g, "mals_group_create_rank", rc);
   malsi_set_create_error("");
   *out = g;
   return MALS_OK;
@@ -784,27 +851,22 @@ int mals_group_set_matrix(mals_group g, int side, int64_t n_rows, int64_t nnz, c
   }
   if (rp[0] != 0 || rp[n_rows] != nnz) return gfail(g, MALS_INVALID_ARG, "row_ptr must start at 0 and end at nnz");
   if (int rc = plan_side(g, side, rp, n_rows)) return rc;
-  for (Member& mb : g->m) {
-    const int64_t r0 = g->bounds[side][(size_t)mb.rank], r1 = g->bounds[side][(size_t)mb.rank + 1];
-    const int64_t e0 = rp[r0], e1 = rp[r1];
-    std::vector<int64_t> local((size_t)(r1 - r0) + 1);
-    for (int64_t r = r0; r <= r1; ++r) local[(size_t)(r - r0)] = rp[r] - e0;
-    GHIP(g, hipSetDevice(mb.device));
-    int rc;
-    if (mem_kind == MALS_MEM_HOST) {
-      rc = mals_set_matrix(mb.h, side, r0, r1 - r0, e1 - e0, local.data(), col_idx + e0, val + e0, MALS_MEM_HOST);
-    } else {
-      // (slices an earlier mals_ingest_install_group copied for this member are not this matrix: let them go once the handle
-      // has taken the new arrays below -- mals_set_matrix synchronises the member's stream before it drops the old ones)
-      GHIP(g, mb.d_row_ptr[side].alloc(local.size()));
-      GHIP(g, hipMemcpy(mb.d_row_ptr[side].get(), local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
-      rc = mals_set_matrix(mb.h, side, r0, r1 - r0, e1 - e0, mb.d_row_ptr[side].get(), col_idx + e0, val + e0, MALS_MEM_DEVICE);
-    }
-    if (rc) return mfail(g, mb, rc);
-    mb.own_col[side].reset();
-    mb.own_val[side].reset();
-  }
-  return finish_matrix(g, side);
+  if (int rc = for_members(g, [&](Member& mb) -> int {
+        const mals::CsrSlice s = mals::csr_slice(rp, g->bounds[side][(size_t)mb.rank], g->bounds[side][(size_t)mb.rank + 1]);
+        const int64_t* local = s.local.data();
+        if (mem_kind == MALS_MEM_DEVICE) {
+          if (int rc = upload_row_ptr(g, mb.d_row_ptr[side], s.local)) return rc;
+          local = mb.d_row_ptr[side].get();
+        }
+        if (int rc = mals_set_matrix(mb.h, side, s.r0, s.rows(), s.entries(), local, col_idx + s.e0, val + s.e0, mem_kind)) return mfail(g, mb, rc);
+        // (slices an earlier mals_ingest_install_group copied for this member are not this matrix: they go now that the handle
+        // has taken the new arrays -- mals_set_matrix synchronises the member's stream before it drops the old ones)
+        mb.own_col[side].reset();
+        mb.own_val[side].reset();
+        return MALS_OK;
+      }))
+    return rc;
+  return sync_value_stats(g, side);
 }
 
 // InputFilesReader.readInputFiles -> DelegateGenerationManager.java:406-410, for a group: see include/myrrix_als.h
@@ -833,30 +895,22 @@ int mals_ingest_install_group(mals_ingest in, mals_group g, int32_t flags) {
     GHIP(g, hipMemcpy(rp.data(), d_ptr, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost));
     if (rp[0] != 0 || rp[(size_t)n_rows[sd]] != nnz) return gfail(g, MALS_INVALID_ARG, "the ingest's row pointers do not match its entry count");
     if (int rc = plan_side(g, sd, rp.data(), n_rows[sd])) return rc;
-    for (Member& mb : g->m) {
-      const int64_t r0 = g->bounds[sd][(size_t)mb.rank], r1 = g->bounds[sd][(size_t)mb.rank + 1];
-      const int64_t e0 = rp[(size_t)r0], e1 = rp[(size_t)r1];
-      std::vector<int64_t> local((size_t)(r1 - r0) + 1);
-      for (int64_t r = r0; r <= r1; ++r) local[(size_t)(r - r0)] = rp[(size_t)r] - e0;
-      GHIP(g, hipSetDevice(mb.device));
-      mb.own_col[sd].reset();
-      mb.own_val[sd].reset();
-      GHIP(g, mb.d_row_ptr[sd].alloc(local.size()));
-      GHIP(g, hipMemcpy(mb.d_row_ptr[sd].get(), local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
-      const int32_t* col = d_col + e0;
-      const float* val = d_val + e0;
-      if ((mb.device != in_dev || force_copy) && e1 > e0) {
-        GHIP(g, mb.own_col[sd].alloc((size_t)(e1 - e0)));
-        GHIP(g, mb.own_val[sd].alloc((size_t)(e1 - e0)));
-        GHIP(g, hipMemcpyPeerAsync(mb.own_col[sd].get(), mb.device, col, in_dev, sizeof(int32_t) * (size_t)(e1 - e0), mb.compute));
-        GHIP(g, hipMemcpyPeerAsync(mb.own_val[sd].get(), mb.device, val, in_dev, sizeof(float) * (size_t)(e1 - e0), mb.compute));
-        GHIP(g, hipStreamSynchronize(mb.compute));
-        col = mb.own_col[sd].get();
-        val = mb.own_val[sd].get();
-      }
-      if (int rc = mals_set_matrix(mb.h, sd, r0, r1 - r0, e1 - e0, mb.d_row_ptr[sd].get(), col, val, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
-    }
-    if (int rc = finish_matrix(g, sd)) return rc;
+    if (int rc = for_members(g, [&](Member& mb) -> int {
+          const mals::CsrSlice s = mals::csr_slice(rp.data(), g->bounds[sd][(size_t)mb.rank], g->bounds[sd][(size_t)mb.rank + 1]);
+          mb.own_col[sd].reset();
+          mb.own_val[sd].reset();
+          if (int rc = upload_row_ptr(g, mb.d_row_ptr[sd], s.local)) return rc;
+          const int32_t* col = nullptr;
+          const float* val = nullptr;
+          bool copied = false;
+          if (int rc = member_slice(g, mb, d_col + s.e0, in_dev, force_copy, s.entries(), mb.own_col[sd], &col, &copied)) return rc;
+          if (int rc = member_slice(g, mb, d_val + s.e0, in_dev, force_copy, s.entries(), mb.own_val[sd], &val, &copied)) return rc;
+          if (copied) GHIP(g, hipStreamSynchronize(mb.compute));
+          if (int rc = mals_set_matrix(mb.h, sd, s.r0, s.rows(), s.entries(), mb.d_row_ptr[sd].get(), col, val, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
+          return MALS_OK;
+        }))
+      return rc;
+    if (int rc = sync_value_stats(g, sd)) return rc;
   }
   // knownItemIDs: every member the rows of its own users (mals_recommend by user index is answered by the member that
   // holds the user's row); userTagIDs: every member the whole mask
@@ -871,37 +925,26 @@ int mals_ingest_install_group(mals_ingest in, mals_group g, int32_t flags) {
     GHIP(g, hipSetDevice(in_dev));
     GHIP(g, hipMemcpy(kp.data(), k_ptr, sizeof(int64_t) * kp.size(), hipMemcpyDeviceToHost));
   }
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
+  return for_members(g, [&](Member& mb) -> int {
     mb.own_known_ptr.reset();
     mb.own_known_idx.reset();
     mb.own_tag_idx.reset();
     if (k_ptr) {
-      const int64_t r0 = g->bounds[0][(size_t)mb.rank], r1 = g->bounds[0][(size_t)mb.rank + 1];
-      const int64_t e0 = kp[(size_t)r0], e1 = kp[(size_t)r1];
-      std::vector<int64_t> local((size_t)(r1 - r0) + 1);
-      for (int64_t r = r0; r <= r1; ++r) local[(size_t)(r - r0)] = kp[(size_t)r] - e0;
-      GHIP(g, mb.own_known_ptr.alloc(local.size()));
-      GHIP(g, hipMemcpy(mb.own_known_ptr.get(), local.data(), sizeof(int64_t) * local.size(), hipMemcpyHostToDevice));
-      const int32_t* idx = k_idx + e0;
-      if ((mb.device != in_dev || force_copy) && e1 > e0) {
-        GHIP(g, mb.own_known_idx.alloc((size_t)(e1 - e0)));
-        GHIP(g, hipMemcpyPeerAsync(mb.own_known_idx.get(), mb.device, idx, in_dev, sizeof(int32_t) * (size_t)(e1 - e0), mb.compute));
-        GHIP(g, hipStreamSynchronize(mb.compute));
-        idx = mb.own_known_idx.get();
-      }
-      if (int rc = mals_set_known_items(mb.h, r1 - r0, mb.own_known_ptr.get(), idx, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
+      const mals::CsrSlice s = mals::csr_slice(kp.data(), g->bounds[0][(size_t)mb.rank], g->bounds[0][(size_t)mb.rank + 1]);
+      if (int rc = upload_row_ptr(g, mb.own_known_ptr, s.local)) return rc;
+      const int32_t* idx = nullptr;
+      bool copied = false;
+      if (int rc = member_slice(g, mb, k_idx + s.e0, in_dev, force_copy, s.entries(), mb.own_known_idx, &idx, &copied)) return rc;
+      if (copied) GHIP(g, hipStreamSynchronize(mb.compute));
+      if (int rc = mals_set_known_items(mb.h, s.rows(), mb.own_known_ptr.get(), idx, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
     }
-    const int64_t* tags = t_idx;
-    if (n_tags > 0 && (mb.device != in_dev || force_copy)) {
-      GHIP(g, mb.own_tag_idx.alloc((size_t)n_tags));
-      GHIP(g, hipMemcpyPeerAsync(mb.own_tag_idx.get(), mb.device, t_idx, in_dev, sizeof(int64_t) * (size_t)n_tags, mb.compute));
-      GHIP(g, hipStreamSynchronize(mb.compute));
-      tags = mb.own_tag_idx.get();
-    }
+    const int64_t* tags = nullptr;
+    bool copied = false;
+    if (int rc = member_slice(g, mb, t_idx, in_dev, force_copy, n_tags, mb.own_tag_idx, &tags, &copied)) return rc;
+    if (copied) GHIP(g, hipStreamSynchronize(mb.compute));
     if (int rc = mals_set_tag_items(mb.h, n_tags, tags, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
-  }
-  return MALS_OK;
+    return MALS_OK;
+  });
 }
 
 }  // extern "C"
@@ -912,37 +955,8 @@ namespace {
 const char* shard_ops_error(void* ctx) { return static_cast<mals_group>(ctx)->err.c_str(); }
 
 int shard_ops_allreduce(void* ctx, int64_t* const* dev, int64_t n, int op_max) {
-  mals_group g = static_cast<mals_group>(ctx);
-  if (g->world == 1 && !g->m[0].nccl) return MALS_OK;
-  if (g->backend == MALS_GROUP_PEER_COPY) {
-    std::vector<int64_t> acc((size_t)n), tmp((size_t)n);
-    for (size_t i = 0; i < g->m.size(); ++i) {
-      GHIP(g, hipSetDevice(g->m[i].device));
-      GHIP(g, hipMemcpy(i == 0 ? acc.data() : tmp.data(), dev[i], sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
-      if (i > 0)
-        for (int64_t k = 0; k < n; ++k) acc[(size_t)k] = op_max ? std::max(acc[(size_t)k], tmp[(size_t)k]) : acc[(size_t)k] + tmp[(size_t)k];
-    }
-    for (size_t i = 0; i < g->m.size(); ++i) {
-      GHIP(g, hipSetDevice(g->m[i].device));
-      GHIP(g, hipMemcpy(dev[i], acc.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice));
-    }
-    return MALS_OK;
-  }
-  GNCCL(g, g_rccl.GroupStart());
-  for (size_t i = 0; i < g->m.size(); ++i) {
-    Member& mb = g->m[i];
-    const ncclResult_t r = g_rccl.AllReduce(dev[i], dev[i], (size_t)n, ncclInt64, op_max ? ncclMax : ncclSum, mb.nccl, mb.comm);
-    if (r != ncclSuccess) {
-      (void)g_rccl.GroupEnd();
-      return gfail(g, MALS_COMM_ERROR, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
-    }
-  }
-  GNCCL(g, g_rccl.GroupEnd());
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipStreamSynchronize(mb.comm));
-  }
-  return MALS_OK;
+  const std::vector<void*> d(dev, dev + static_cast<mals_group>(ctx)->m.size());
+  return all_reduce(static_cast<mals_group>(ctx), {Reduce{d.data(), (size_t)n, ncclInt64, op_max ? ncclMax : ncclSum}}, Done::HOST_WAITS);
 }
 
 // every member's run for rank q (send_off row of the member) into q's receive buffer at q's offset for the sender
@@ -961,19 +975,13 @@ int shard_ops_exchange(void* ctx, const uint8_t* const* send, const int64_t* sen
           GHIP(g, hipMemcpyPeerAsync(recv[j] + recv_off[j * (W + 1) + src.rank], dst.device, send[i] + b, src.device, (size_t)(e - b), src.comm));
       }
     }
-    for (Member& mb : g->m) {
-      GHIP(g, hipSetDevice(mb.device));
-      GHIP(g, hipStreamSynchronize(mb.comm));
-    }
-    return MALS_OK;
+    return sync_comm(g);
   }
-  GNCCL(g, g_rccl.GroupStart());
-  for (size_t i = 0; i < nl; ++i) {
-    Member& mb = g->m[i];
-    for (int q = 0; q < W; ++q) {
+  const int rc = rccl_group(g, "ncclSend/ncclRecv", [&](Member& mb, size_t i) {
+    ncclResult_t r = ncclSuccess;
+    for (int q = 0; q < W && r == ncclSuccess; ++q) {
       const int64_t sb = send_off[i * (W + 1) + q], se = send_off[i * (W + 1) + q + 1];
       const int64_t rb = recv_off[i * (W + 1) + q], re = recv_off[i * (W + 1) + q + 1];
-      ncclResult_t r = ncclSuccess;
       if (q == mb.rank) {
         if (se > sb && hipSetDevice(mb.device) == hipSuccess &&
             hipMemcpyAsync(recv[i] + rb, send[i] + sb, (size_t)(se - sb), hipMemcpyDeviceToDevice, mb.comm) != hipSuccess)
@@ -982,18 +990,10 @@ int shard_ops_exchange(void* ctx, const uint8_t* const* send, const int64_t* sen
         if (se > sb) r = g_rccl.Send(send[i] + sb, (size_t)(se - sb), ncclUint8, q, mb.nccl, mb.comm);
         if (r == ncclSuccess && re > rb) r = g_rccl.Recv(recv[i] + rb, (size_t)(re - rb), ncclUint8, q, mb.nccl, mb.comm);
       }
-      if (r != ncclSuccess) {
-        (void)g_rccl.GroupEnd();
-        return gfail(g, MALS_COMM_ERROR, std::string("ncclSend/ncclRecv: ") + g_rccl.GetErrorString(r));
-      }
     }
-  }
-  GNCCL(g, g_rccl.GroupEnd());
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipStreamSynchronize(mb.comm));
-  }
-  return MALS_OK;
+    return r;
+  });
+  return rc != MALS_OK ? rc : sync_comm(g);
 }
 
 int shard_ops_agree(void* ctx, const int* local_rc) {
@@ -1007,16 +1007,6 @@ int shard_ops_agree(void* ctx, const int* local_rc) {
   double agreed = 0.0;
   if (int rc = allreduce_host(g, v, 1, 1, &agreed)) return rc == MALS_COMM_ERROR ? MALS_COMM_ERROR : -1;
   return (int)agreed;
-}
-
-// slices at given bounds (plan_side without the plan)
-int set_side_bounds(mals_group g, int side, const std::vector<int64_t>& bounds) {
-  g->n_rows[side] = bounds.back();
-  g->side_chunks[side] = g->exchange_chunks;
-  g->bounds[side] = bounds;
-  for (Member& mb : g->m)
-    if (int rc = mals_set_chunk_rows(mb.h, side, chunk_rows_of(g, side, mb.rank))) return mfail(g, mb, rc);
-  return MALS_OK;
 }
 
 }  // namespace
@@ -1060,7 +1050,7 @@ int mals_group_ingest_finish(mals_group g, mals_ingest* ingests, int32_t n_local
       mb.own_val[sd].reset();
       if (int rc = mals_set_matrix(mb.h, sd, r0, r1 - r0, nnz, d_ptr, d_col, d_val, MALS_MEM_DEVICE)) return mfail(g, mb, rc);
     }
-    if (int rc = finish_matrix(g, sd)) return rc;
+    if (int rc = sync_value_stats(g, sd)) return rc;
   }
   for (int32_t i = 0; i < n_local; ++i) {
     Member& mb = g->m[(size_t)i];
@@ -1082,35 +1072,86 @@ int mals_group_ingest_finish(mals_group g, mals_ingest* ingests, int32_t n_local
 
 }  // extern "C"
 
+namespace {
+
+// mals_group_factorize's side of the loop in convergence.h: a cancellation is local knowledge and agreed on before a collective
+// is entered; the report counts what THIS process's members solved and gathered, from their stats before, between and after
+// the halves
+struct GroupFactorize {
+  mals_group g;
+  int64_t rows[2] = {0, 0}, entries0 = 0;   // rows solved up to: the iteration's start, the end of its X half
+  void totals(int64_t* rows_out, int64_t* entries_out) {
+    *rows_out = *entries_out = 0;
+    for (Member& mb : g->m) {
+      mals_stats st;
+      (void)mals_get_stats(mb.h, &st);
+      *rows_out += st.rows_solved;
+      *entries_out += st.nnz_gathered;
+    }
+  }
+  int fail(int code, const char* msg) { return gfail(g, code, msg); }
+  void clear_cancel() { g->cancelled.store(0); }
+  int cancelled() { return agree_status(g, g->cancelled.load() ? MALS_CANCELLED : MALS_OK, "cancelled"); }
+  int half_iteration(int side) { return mals_group_half_iteration(g, side); }
+  // from one complete replica: every replica holds the same factors once the exchange is in
+  int sample_dots(const int64_t* users, int32_t n_users, const int64_t* items, int32_t n_items, double* out) {
+    if (int rc = mals_group_synchronize(g)) return rc;
+    if (int rc = mals_sample_dots(g->m[0].h, users, n_users, items, n_items, out)) return mfail(g, g->m[0], rc);
+    return MALS_OK;
+  }
+  mals_iteration_fn callback(void** user) {
+    *user = g->iter_user;
+    return g->iter_fn;
+  }
+  void count(int point) {
+    int64_t e = 0;
+    totals(&rows[point], point == 0 ? &entries0 : &e);
+  }
+  void report(mals_iteration_info* info) {
+    int64_t rows_now = 0, entries_now = 0;
+    totals(&rows_now, &entries_now);
+    info->entries_gathered = entries_now - entries0;
+    info->x_rows = rows[1] - rows[0];
+    info->y_rows = rows_now - rows[0] - info->x_rows;
+    info->algorithmic_bytes = (double)(info->entries_gathered + rows_now - rows[0]) * (4.0 * g->cfg.features + 8.0);
+    info->devices = (int32_t)g->m.size();
+  }
+};
+
+// Every member holds full replicas of X and Y but only its own users' rows of R / knownItemIDs, so a user is answered by the
+// member whose slice holds its row: runs of consecutive queries with one owner go to that member in one call,
+// call(handle, q0, n).  any_member: the replicas alone answer, so a run whose owner is another process's rank goes to member 0.
+// (No message on a refusal: request threads share the group's error string.)
+template <class Call>
+int route_by_owner(mals_group g, const int64_t* user_idx, int32_t n_queries, bool any_member, Call&& call) {
+  const std::vector<int64_t>& b = g->bounds[MALS_SIDE_X];
+  if (b.empty()) return MALS_INVALID_ARG;
+  for (int32_t q0 = 0, q1 = 0; q0 < n_queries; q0 = q1) {
+    int owner = 0;
+    if (!mals::owner_run(b, g->users_end.load(std::memory_order_acquire), user_idx, n_queries, q0, &q1, &owner)) return MALS_INVALID_ARG;
+    const Member* mb = any_member ? &g->m[0] : nullptr;
+    for (const Member& m : g->m)
+      if (m.rank == owner) mb = &m;
+    if (!mb) return MALS_INVALID_ARG;   // the owner is another process's rank
+    if (int rc = call(mb->h, q0, q1 - q0)) return rc;
+  }
+  return MALS_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
-// ServerRecommender.recommend(userID, ...) on a group: every member holds full replicas of X and Y but only its own users' rows
-// of R / knownItemIDs, so a user is answered by the member whose slice holds its row.
+// ServerRecommender.recommend(userID, ...) on a group.  consider_known_items: any member can answer (the replicas are
+// complete); else only the owner knows the user's items
 int mals_group_recommend(mals_group g, const int64_t* user_idx, int32_t n_queries, int32_t how_many, int32_t consider_known_items,
                          int64_t* item_idx_out, float* score_out, int32_t* n_out) {
   if (!g) return MALS_INVALID_ARG;
   if (n_queries < 0 || how_many <= 0 || (n_queries > 0 && (!user_idx || !item_idx_out || !score_out))) return MALS_INVALID_ARG;
-  if (g->bounds[MALS_SIDE_X].empty()) return MALS_INVALID_ARG;   // (no message: request threads share the group's error string)
-  const std::vector<int64_t>& b = g->bounds[MALS_SIDE_X];
-  // runs of consecutive queries with the same owner go to that member in one call (a one-user call is one run)
-  for (int32_t q0 = 0; q0 < n_queries;) {
-    const int64_t u = user_idx[q0];
-    if (u < 0 || u >= std::max(b.back(), g->users_end.load(std::memory_order_acquire))) return MALS_INVALID_ARG;
-    const int owner = owner_of(b, u);
-    int32_t q1 = q0 + 1;
-    while (q1 < n_queries && user_idx[q1] >= 0 && owner_of(b, user_idx[q1]) == owner) ++q1;
-    const Member* mb = nullptr;
-    for (const Member& m : g->m)
-      if (m.rank == owner) mb = &m;
-    // consider_known_items: any member can answer (the replicas are complete); else only the owner knows the user's items
-    if (!mb && consider_known_items) mb = &g->m[0];
-    if (!mb) return MALS_INVALID_ARG;   // the owner is another process's rank
-    if (int rc = mals_recommend(mb->h, user_idx + q0, q1 - q0, how_many, consider_known_items, item_idx_out + (size_t)q0 * how_many,
-                                score_out + (size_t)q0 * how_many, n_out ? n_out + q0 : nullptr))
-      return rc;
-    q0 = q1;
-  }
-  return MALS_OK;
+  return route_by_owner(g, user_idx, n_queries, consider_known_items != 0, [&](mals_handle h, int32_t q0, int32_t n) {
+    return mals_recommend(h, user_idx + q0, n, how_many, consider_known_items, item_idx_out + (size_t)q0 * how_many,
+                          score_out + (size_t)q0 * how_many, n_out ? n_out + q0 : nullptr);
+  });
 }
 
 // mostSimilarItems / similarityToItem on a group: the Y replicas are complete on every member, any local member answers
@@ -1130,24 +1171,10 @@ int mals_group_recommended_because(mals_group g, const int64_t* user_idx, const 
                                    int64_t* item_idx_out, float* score_out, int32_t* n_out) {
   if (!g) return MALS_INVALID_ARG;
   if (n_queries < 0 || how_many <= 0 || (n_queries > 0 && (!user_idx || !item_idx || !item_idx_out || !score_out))) return MALS_INVALID_ARG;
-  if (g->bounds[MALS_SIDE_X].empty()) return MALS_INVALID_ARG;
-  const std::vector<int64_t>& b = g->bounds[MALS_SIDE_X];
-  for (int32_t q0 = 0; q0 < n_queries;) {
-    const int64_t u = user_idx[q0];
-    if (u < 0 || u >= std::max(b.back(), g->users_end.load(std::memory_order_acquire))) return MALS_INVALID_ARG;
-    const int owner = owner_of(b, u);
-    int32_t q1 = q0 + 1;
-    while (q1 < n_queries && user_idx[q1] >= 0 && owner_of(b, user_idx[q1]) == owner) ++q1;
-    const Member* mb = nullptr;
-    for (const Member& m : g->m)
-      if (m.rank == owner) mb = &m;
-    if (!mb) return MALS_INVALID_ARG;   // the owner is another process's rank
-    if (int rc = mals_recommended_because(mb->h, user_idx + q0, item_idx + q0, q1 - q0, how_many, item_idx_out + (size_t)q0 * how_many,
-                                          score_out + (size_t)q0 * how_many, n_out ? n_out + q0 : nullptr))
-      return rc;
-    q0 = q1;
-  }
-  return MALS_OK;
+  return route_by_owner(g, user_idx, n_queries, false, [&](mals_handle h, int32_t q0, int32_t n) {
+    return mals_recommended_because(h, user_idx + q0, item_idx + q0, n, how_many, item_idx_out + (size_t)q0 * how_many,
+                                    score_out + (size_t)q0 * how_many, n_out ? n_out + q0 : nullptr);
+  });
 }
 
 int mals_group_begin_matrix(mals_group g, int side, int64_t n_rows, const int64_t* row_ptr) {
@@ -1175,10 +1202,9 @@ int mals_group_append_rows(mals_group g, int side, int64_t n_rows, const int32_t
   for (Member& mb : g->m) {  // the part of [a, b) inside this member's slice
     const int64_t r0 = std::max(a, g->bounds[side][(size_t)mb.rank]), r1 = std::min(b, g->bounds[side][(size_t)mb.rank + 1]);
     if (r1 <= r0) continue;
-    std::vector<int64_t> local((size_t)(r1 - r0) + 1);
-    for (int64_t r = r0; r <= r1; ++r) local[(size_t)(r - r0)] = rp[(size_t)r] - rp[(size_t)r0];
-    const int64_t off = rp[(size_t)r0] - base;
-    if (int rc = mals_append_rows(mb.h, side, r1 - r0, local.data(), col_idx ? col_idx + off : nullptr, val ? val + off : nullptr))
+    const mals::CsrSlice s = mals::csr_slice(rp.data(), r0, r1);
+    const int64_t off = s.e0 - base;
+    if (int rc = mals_append_rows(mb.h, side, s.rows(), s.local.data(), col_idx ? col_idx + off : nullptr, val ? val + off : nullptr))
       return mfail(g, mb, rc);
   }
   g->up_next_row[side] = b;
@@ -1194,7 +1220,7 @@ int mals_group_end_matrix(mals_group g, int side) {
   if (!complete) return gfail(g, MALS_INVALID_ARG, "appended rows do not match the declared matrix size");
   for (Member& mb : g->m)
     if (int rc = mals_end_matrix(mb.h, side)) return mfail(g, mb, rc);
-  return finish_matrix(g, side);
+  return sync_value_stats(g, side);
 }
 
 int mals_group_bounds(mals_group g, int side, int64_t* bounds_out) {
@@ -1211,99 +1237,73 @@ int mals_group_half_iteration(mals_group g, int side) {
   // A failure of the local solve (MALS_OOM, MALS_INVALID_ARG ...) must not leave the peers alone in a collective:
   // the remaining exchanges of the half-iteration are still issued (only the solves are skipped), so that every rank
   // arrives at the agreed status with matching calls behind it.  Only a communication / device failure ends it here.
-  int solve_rc = MALS_OK;
-  std::string solve_msg;
-  auto member_failed = [&](const Member& mb, int rc) {
-    if (solve_rc == MALS_OK) {
-      solve_rc = rc;
-      solve_msg = std::string("rank ") + std::to_string(mb.rank) + ": " + mals_last_error(mb.h);
-    }
-  };
+  LocalFailure local;
   auto run = [&]() -> int {
-    // the gather of this half reads every row of the opposite replica: all of the previous exchange must be in
-    for (Member& mb : g->m) {
-      GHIP(g, hipSetDevice(mb.device));
-      GHIP(g, hipStreamWaitEvent(mb.compute, mb.ev_exchanged, 0));
-    }
-    if (g->single_process && g->backend == MALS_GROUP_PEER_COPY)  // peer copies INTO a replica run on the source's stream
-      for (Member& mb : g->m)
-        for (Member& other : g->m) {
-          GHIP(g, hipSetDevice(mb.device));
-          GHIP(g, hipStreamWaitEvent(mb.compute, other.ev_exchanged, 0));
-        }
-    if (int rc = group_gramian(g, 1 - side, &solve_rc, &solve_msg)) return rc;  // ALS:342 / ALS:369
+    if (int rc = await_exchange(g)) return rc;
+    if (int rc = group_gramian(g, 1 - side, local)) return rc;  // ALS:342 / ALS:369
     const bool alternate = g->alternate_streams && g->side_chunks[side] > 1;
-    if (alternate)
-      for (Member& mb : g->m) {   // the second stream starts behind everything the first has seen so far
-        GHIP(g, hipSetDevice(mb.device));
-        GHIP(g, hipEventRecord(mb.ev_half, mb.compute));
-        GHIP(g, hipStreamWaitEvent(mb.compute2, mb.ev_half, 0));
-      }
+    if (alternate)   // the second stream starts behind everything the first has seen so far
+      if (int rc = for_members(g, [&](Member& mb) { return hand_off(g, mb.compute, mb.ev_half, mb.compute2); })) return rc;
     for (int c = 0; c < g->side_chunks[side]; ++c) {
       const bool odd = alternate && (c & 1);
       if (alternate)
-        for (Member& mb : g->m) {
-          GHIP(g, hipSetDevice(mb.device));
-          if (int rc = mals_set_stream(mb.h, odd ? mb.compute2 : mb.compute)) return mfail(g, mb, rc);
-          // ... and behind what the half-iteration sets up once, in its first chunk (operand scale, images, rotated copy)
-          if (c == 1) GHIP(g, hipStreamWaitEvent(mb.compute2, (hipEvent_t)malsi_ready_event(mb.h), 0));
-        }
+        if (int rc = for_members(g, [&](Member& mb) -> int {
+              if (int rc = mals_set_stream(mb.h, odd ? mb.compute2 : mb.compute)) return mfail(g, mb, rc);
+              // ... and behind what the half-iteration sets up once, in its first chunk (operand scale, images, rotated copy)
+              if (c == 1) GHIP(g, hipStreamWaitEvent(mb.compute2, (hipEvent_t)malsi_ready_event(mb.h), 0));
+              return MALS_OK;
+            }))
+          return rc;
       // Like the reference's pool, where every worker is started before any result is awaited (ALS:186-191,391-410):
       // the direct kernels of EVERY member are enqueued before any host work; the k x k eigendecomposition of the
       // dual path (the same G on every member after the all-reduce) is then computed once, under those kernels, and
       // handed to the others; only then the members' dual kernels follow.
       std::vector<char> has(g->m.size(), 0);
-      for (size_t i = 0; i < g->m.size(); ++i) {
-        Member& mb = g->m[i];
-        GHIP(g, hipSetDevice(mb.device));
-        int32_t mine = 0;
-        if (int rc = mals_num_chunks(mb.h, side, &mine)) return mfail(g, mb, rc);
-        has[i] = c < mine && solve_rc == MALS_OK;
-        if (has[i])
-          if (int rc = malsi_solve_chunk_begin(mb.h, side, c)) {  // ALS:344 / ALS:371
-            member_failed(mb, rc);
-            has[i] = 0;
-          }
-      }
+      if (int rc = for_members(g, [&](Member& mb, size_t i) -> int {
+            int32_t mine = 0;
+            if (int rc = mals_num_chunks(mb.h, side, &mine)) return mfail(g, mb, rc);
+            has[i] = c < mine && local.rc == MALS_OK;
+            if (has[i])
+              if (int rc = malsi_solve_chunk_begin(mb.h, side, c)) {  // ALS:344 / ALS:371
+                local.note(mb, rc);
+                has[i] = 0;
+              }
+            return MALS_OK;
+          }))
+        return rc;
       Member* decomposed = nullptr;
       for (size_t i = 0; i < g->m.size(); ++i) {
         Member& mb = g->m[i];
         if (!has[i] || !malsi_dual_pending(mb.h)) continue;
         GHIP(g, hipSetDevice(mb.device));
         if (int rc = malsi_dual_host(mb.h, side, decomposed ? decomposed->h : nullptr)) {
-          member_failed(mb, rc);
+          local.note(mb, rc);
           has[i] = 0;
           continue;
         }
         if (!decomposed) decomposed = &mb;
       }
-      for (size_t i = 0; i < g->m.size(); ++i) {
-        Member& mb = g->m[i];
-        GHIP(g, hipSetDevice(mb.device));
-        if (has[i])
-          if (int rc = malsi_solve_chunk_end(mb.h, side, c)) member_failed(mb, rc);
-        GHIP(g, hipEventRecord(mb.ev_solved, odd ? mb.compute2 : mb.compute));
-        GHIP(g, hipStreamWaitEvent(mb.comm, mb.ev_solved, 0));
-      }
+      if (int rc = for_members(g, [&](Member& mb, size_t i) -> int {
+            if (has[i])
+              if (int rc = malsi_solve_chunk_end(mb.h, side, c)) local.note(mb, rc);
+            return hand_off(g, odd ? mb.compute2 : mb.compute, mb.ev_solved, mb.comm);
+          }))
+        return rc;
       if (int rc = exchange_chunk(g, side, c)) return rc;
     }
-    if (alternate)
-      for (Member& mb : g->m) {   // join: everything after this half-iteration assumes the one compute stream
-        GHIP(g, hipSetDevice(mb.device));
-        GHIP(g, hipEventRecord(mb.ev_join, mb.compute2));
-        GHIP(g, hipStreamWaitEvent(mb.compute, mb.ev_join, 0));
-        if (int rc = mals_set_stream(mb.h, mb.compute)) return mfail(g, mb, rc);
-      }
-    for (Member& mb : g->m) {
-      GHIP(g, hipSetDevice(mb.device));
-      GHIP(g, hipEventRecord(mb.ev_exchanged, mb.comm));
-    }
-    if (solve_rc != MALS_OK) return gfail(g, solve_rc, solve_msg);
-    for (Member& mb : g->m) {  // ALS:346-361: f.get() of every worker
-      GHIP(g, hipSetDevice(mb.device));
+    if (alternate)   // join: everything after this half-iteration assumes the one compute stream
+      if (int rc = for_members(g, [&](Member& mb) -> int {
+            if (int rc = hand_off(g, mb.compute2, mb.ev_join, mb.compute)) return rc;
+            if (int rc = mals_set_stream(mb.h, mb.compute)) return mfail(g, mb, rc);
+            return MALS_OK;
+          }))
+        return rc;
+    if (int rc = mark_exchanged(g)) return rc;
+    if (local.rc != MALS_OK) return gfail(g, local.rc, local.msg);
+    return for_members(g, [&](Member& mb) -> int {  // ALS:346-361: f.get() of every worker
       if (int rc = mals_check(mb.h)) return mfail(g, mb, rc);
-    }
-    return MALS_OK;
+      return MALS_OK;
+    });
   };
   const int local_rc = run();
   const std::string local_msg = g->err;
@@ -1334,18 +1334,10 @@ int mals_group_singular_info(mals_group g, int32_t* side, int64_t* row, int32_t*
 int mals_group_exchange_only(mals_group g, int side) {
   GSIDE(g, side);
   if (g->bounds[side].empty()) return gfail(g, MALS_INVALID_ARG, "matrix of this side not set");
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipEventRecord(mb.ev_solved, mb.compute));
-    GHIP(g, hipStreamWaitEvent(mb.comm, mb.ev_solved, 0));
-  }
+  if (int rc = for_members(g, [&](Member& mb) { return hand_off(g, mb.compute, mb.ev_solved, mb.comm); })) return rc;
   for (int c = 0; c < g->side_chunks[side]; ++c)
     if (int rc = exchange_chunk(g, side, c)) return rc;
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipEventRecord(mb.ev_exchanged, mb.comm));
-  }
-  return MALS_OK;
+  return mark_exchanged(g);
 }
 
 int mals_group_cancel(mals_group g) {
@@ -1356,98 +1348,20 @@ int mals_group_cancel(mals_group g) {
 
 int mals_group_synchronize(mals_group g) {
   if (!g) return MALS_INVALID_ARG;
-  for (Member& mb : g->m) {
-    GHIP(g, hipSetDevice(mb.device));
+  return for_members(g, [&](Member& mb) -> int {
     GHIP(g, hipStreamSynchronize(mb.compute));
     GHIP(g, hipStreamSynchronize(mb.comm));
-  }
-  return MALS_OK;
+    return MALS_OK;
+  });
 }
 
 int mals_group_factorize(mals_group g, double convergence_threshold, int32_t max_iterations, int32_t random_y, int32_t iterate,
                          const int64_t* test_users, int32_t n_test_users, const int64_t* test_items, int32_t n_test_items,
                          int32_t* iterations_out, double* convergence_out) {
   if (!g) return MALS_INVALID_ARG;
-  if (iterations_out) *iterations_out = 0;
-  if (convergence_out) *convergence_out = std::numeric_limits<double>::quiet_NaN();
-  if (!(convergence_threshold > 0.0 && convergence_threshold < 1.0)) return gfail(g, MALS_INVALID_ARG, "threshold must be in (0,1)");  // ALS:140-141
-  if (n_test_users < 0 || n_test_items < 0 || (n_test_users > 0 && !test_users) || (n_test_items > 0 && !test_items))
-    return gfail(g, MALS_INVALID_ARG, "bad convergence sample");
-  g->cancelled.store(0);
-  if (!iterate) return mals_group_half_iteration(g, MALS_SIDE_X);  // ALS:196-204
-  std::vector<double> est((size_t)n_test_users * (size_t)n_test_items, 0.0), fresh(est.size());
-  int it = 0;
-  for (;;) {
-    const auto t_it = std::chrono::steady_clock::now();
-    mals_stats st0;
-    // the callback is sampled ONCE per iteration (one installed while an iteration runs starts with the next one)
-    const mals_iteration_fn iter_fn = g->iter_fn;
-    void* const iter_user = g->iter_user;
-    std::vector<std::pair<int64_t, int64_t>> before;   // (rows_solved, nnz_gathered) of every local member
-    auto rows_now = [&]() {
-      int64_t r = 0;
-      for (Member& mb : g->m) {
-        (void)mals_get_stats(mb.h, &st0);
-        r += st0.rows_solved;
-      }
-      return r;
-    };
-    int64_t rows_before = 0, rows_after_x = 0;
-    if (iter_fn) {
-      for (Member& mb : g->m) {
-        (void)mals_get_stats(mb.h, &st0);
-        before.emplace_back(st0.rows_solved, st0.nnz_gathered);
-        rows_before += st0.rows_solved;
-      }
-    }
-    // a cancellation is local knowledge: agree on it before entering a collective
-    if (int rc = agree_status(g, g->cancelled.load() ? MALS_CANCELLED : MALS_OK, "cancelled")) return rc;
-    if (int rc = mals_group_half_iteration(g, MALS_SIDE_X)) return rc;  // ALS:228
-    if (iter_fn) rows_after_x = rows_now();  // what THIS process's members solved in the X half, exactly
-    if (int rc = agree_status(g, g->cancelled.load() ? MALS_CANCELLED : MALS_OK, "cancelled")) return rc;
-    if (int rc = mals_group_half_iteration(g, MALS_SIDE_Y)) return rc;  // ALS:229
-    // ALS:231-238: the sample dots (SimpleVectorMath.dot) on the device from a complete replica (every replica
-    // holds the same factors once the exchange is in), DoubleWeightedMean.increment on the host
-    if (int rc = mals_group_synchronize(g)) return rc;
-    if (int rc = mals_sample_dots(g->m[0].h, test_users, n_test_users, test_items, n_test_items, fresh.data())) return mfail(g, g->m[0], rc);
-    double tw = 0.0, mean = std::numeric_limits<double>::quiet_NaN();
-    for (int i = 0; i < n_test_users; ++i)
-      for (int j = 0; j < n_test_items; ++j) {
-        const double nv = fresh[(size_t)i * n_test_items + j];
-        double& slot = est[(size_t)i * n_test_items + j];
-        const double datum = std::fabs(nv - slot), weight = nv > 0.0 ? nv : 0.0;
-        slot = nv;
-        const double old = tw;
-        tw += weight;
-        mean = old <= 0 ? datum : mean * old / tw + datum * weight / tw;
-      }
-    ++it;
-    if (iterations_out) *iterations_out = it;
-    if (convergence_out) *convergence_out = mean;
-    if (iter_fn && before.size() == g->m.size()) {   // what the reference logs per iteration (ALS:241-246, 351-358)
-      mals_iteration_info info;
-      std::memset(&info, 0, sizeof(info));
-      info.struct_size = (int32_t)sizeof(info);
-      info.iteration = it;
-      info.avg_abs_difference = mean;
-      info.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_it).count();
-      int64_t rows = 0;
-      for (size_t i = 0; i < g->m.size(); ++i) {
-        (void)mals_get_stats(g->m[i].h, &st0);
-        rows += st0.rows_solved - before[i].first;
-        info.entries_gathered += st0.nnz_gathered - before[i].second;
-      }
-      info.x_rows = rows_after_x - rows_before;
-      info.y_rows = rows - info.x_rows;
-      info.algorithmic_bytes = (double)(info.entries_gathered + rows) * (4.0 * g->cfg.features + 8.0);
-      info.devices = (int32_t)g->m.size();
-      iter_fn(iter_user, &info);
-    }
-    if (max_iterations > 0 && it >= max_iterations) break;              // ALS:242-245
-    if (!std::isfinite(mean)) break;                                    // ALS:248-251
-    if (!(random_y && it == 1) && mean < convergence_threshold) break;  // ALS:253-256
-  }
-  return MALS_OK;
+  GroupFactorize d{g};
+  return mals::factorize_loop(d, convergence_threshold, max_iterations, random_y, iterate, test_users, n_test_users, test_items, n_test_items,
+                              iterations_out, convergence_out);
 }
 
 }  // extern "C"
