@@ -1,8 +1,26 @@
 // foldin_host.h -- host side of the online write path (mals_set_preferences, mals_remove_preferences,
-// mals_grow_factor_rows, the fold-in reads; include/myrrix_als.h; kernels in foldin_kernels.h).  Included by
-// mals_serving.hip inside its anonymous namespace, after topn_host.h: every call here runs as an exclusive ticket of the
-// serving front (topn_front_submit), so the passes formed before it have finished and the passes formed after it wait
-// for its work on the handle's stream (ev_begin), and the state below is only ever touched by the front's leader.
+// mals_grow_factor_rows, the fold-in reads; include/myrrix_als.h; kernels in foldin_kernels.h; the logic that needs no
+// device in foldin_plan.h).  Included by mals_serving.hip inside its anonymous namespace, after topn_host.h: every call
+// here runs as an exclusive ticket of the serving front (topn_front_submit), so the passes formed before it have finished
+// and the passes formed after it wait for its work on the handle's stream (ev_begin), and the state below is only ever
+// touched by the front's leader.
+//
+// ONE DRIVER PER WRITE.  A write is the same steps on a handle and on the members of a group (every member applies the same
+// batch to its own replicas with the same deterministic kernels; only a user's owner keeps its known items), so each has one
+// driver over (hs, n_members) -- foldin_set_members, foldin_remove_members, foldin_grow_members, popular_members
+// (popular_host.h) -- that runs INSIDE the ticket its caller holds: foldin_exclusive for a handle, which passes (&h, 1),
+// foldin_exclusive_all for a group.  What the two say differently is `via_group` (which users a batch may name, who marks the
+// rows recent, the hints of the texts) and the owners.
+//
+// THE MEMBER LOOP (member_loop), which they and malsi_group_factor_digest share: an enqueue step per member, then a finish step
+// per member, so that every member's device work is on its way before the first wait.  Its rules:
+//   1. member m's device is current for both of its steps and for the release of its slot (the per-member temporaries);
+//   2. the first failure's code and message are the call's, and no step runs after it (no finish after a failed enqueue);
+//   3. after a failure nothing of the call still runs when it returns: the members touched so far are waited for (all of them
+//      once the finish phase has begun), before any slot is released.
+// Set relies on 2 and 3 (a member that answers otherwise than member 0 fails the call), remove and grow on all three (their
+// slots are device buffers the enqueued work reads), the digest on 3 (the enqueued copy writes the caller's array), popular
+// on 1 and 2, and on 3 for the partial array of its sum.
 #pragma once
 
 // Errors of the calls below never go to h->err from inside a ticket (other request threads write it under the front's
@@ -26,15 +44,8 @@ struct FoldinState {
   FoldinSide solver[2];
   double rate = 1.0;                   // FOLDIN_LEARN_RATE
   double big_total = 0.0;              // smallest t with sqrt(t) > BIG_FOLDIN_THRESHOLD
-  // knownItemIDs after the writes of this generation, beside the base CSR (the installed known items or the rows of R,
-  // never written): per local user row a chain of added items in one pool (O(1) per write, duplicates dropped when read),
-  // and -- after the user's first removal -- the whole set, sorted (the base row and the chain no longer count)
-  std::vector<uint32_t> head;                          // local row -> newest pool entry, UINT32_MAX = none
-  std::vector<std::pair<int32_t, uint32_t>> pool;      // (item, next entry)
-  std::unordered_map<int64_t, std::vector<int32_t>> replaced;
-  // per batch: row -> last level, an open-addressing table sized by the batch (cache-resident, nothing per model row)
-  std::vector<int64_t> lk[2];
-  std::vector<uint32_t> lv[2];
+  KnownOverlay known;                  // knownItemIDs after the writes of this generation, by local user row (foldin_plan.h)
+  FoldinPlanScratch plan_scratch;      // the level plan's table, reused from batch to batch
   DeviceBuffer<int64_t> d_rows;        // [2][n] user rows | item rows, level order
   DeviceBuffer<float> d_val;
   DeviceBuffer<int32_t> d_status;
@@ -66,11 +77,7 @@ void foldin_free(mals_handle h) {
 // a new generation (mals_set_known_items, mals_set_matrix of side X, mals_set_factor_rows / mals_bind_factors of X)
 void foldin_drop_overlay(mals_handle h) {
   h->grown_users_end.store(-1, std::memory_order_release);
-  FoldinState* fs = h->serving->fo;
-  if (!fs) return;
-  std::vector<uint32_t>().swap(fs->head);
-  std::vector<std::pair<int32_t, uint32_t>>().swap(fs->pool);
-  fs->replaced.clear();
+  if (FoldinState* fs = h->serving->fo) fs->known.clear();
 }
 
 // rows of the base known-item CSR (users past them -- grown rows -- have an empty base set)
@@ -89,41 +96,15 @@ int64_t foldin_user_rows_end(mals_handle h) {
 
 bool foldin_has_overlay(mals_handle h) {
   const FoldinState* fs = h->serving->fo;
-  return (fs && (!fs->pool.empty() || !fs->replaced.empty())) || h->grown_users_end.load(std::memory_order_acquire) >= 0 ||
+  return (fs && fs->known.any()) || h->grown_users_end.load(std::memory_order_acquire) >= 0 ||
          foldin_base_rows(h) < h->side[MALS_SIDE_X].n_local;
 }
 
 // what a recommend pass needs of a user's known items beyond its base row: the items to exclude (appended to out,
 // possibly repeated) and whether the base row is dropped (a replaced set, or a grown row the base CSR does not have)
 bool foldin_known_view(mals_handle h, int64_t local_row, std::vector<int64_t>& out) {
-  bool drop = local_row >= foldin_base_rows(h);
   const FoldinState* fs = h->serving->fo;
-  if (!fs) return drop;
-  if (!fs->replaced.empty()) {
-    auto it = fs->replaced.find(local_row);
-    if (it != fs->replaced.end()) {
-      out.insert(out.end(), it->second.begin(), it->second.end());
-      return true;
-    }
-  }
-  if (local_row < (int64_t)fs->head.size())
-    for (uint32_t e = fs->head[(size_t)local_row]; e != UINT32_MAX; e = fs->pool[e].second) out.push_back(fs->pool[e].first);
-  return drop;
-}
-
-void foldin_overlay_add(FoldinState& fs, int64_t local_row, int32_t item) {
-  if (!fs.replaced.empty()) {
-    auto it = fs.replaced.find(local_row);
-    if (it != fs.replaced.end()) {
-      std::vector<int32_t>& v = it->second;
-      auto p = std::lower_bound(v.begin(), v.end(), item);
-      if (p == v.end() || *p != item) v.insert(p, item);
-      return;
-    }
-  }
-  if (local_row >= (int64_t)fs.head.size()) fs.head.resize((size_t)local_row + 1, UINT32_MAX);
-  fs.pool.push_back({item, fs.head[(size_t)local_row]});
-  fs.head[(size_t)local_row] = (uint32_t)(fs.pool.size() - 1);
+  return fs ? fs->known.view(local_row, foldin_base_rows(h), out) : local_row >= foldin_base_rows(h);
 }
 
 // the base rows of several local users from the device, with two synchronisations in all: outs[j] sorted, distinct
@@ -171,8 +152,20 @@ int foldin_known_full(mals_handle h, const std::vector<int64_t>& rows, std::vect
   return MALS_OK;
 }
 
-// a call that runs alone on the handle, in the front's queue order; a failure's message is published under the mutex
-int foldin_exclusive(mals_handle h, const std::function<int()>& fn, const std::string& msg, const char* call) {
+// ---- the tickets ------------------------------------------------------------------------------------------------------------
+// via_group: the call comes from the member's group (a mals_group_* twin), which routes the known items to their owner
+int foldin_refuse(mals_handle h, const char* call, bool via_group = false) {
+  if (h->group_member && !via_group)
+    return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": not for a member of a group (writes and fold-in reads go through the group: mals_group_set_preferences ...)").c_str());
+  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
+  return MALS_OK;
+}
+
+// body(msg) runs alone on the handle, in the front's queue order; a failure's message is published under the mutex
+template <class Body>
+int foldin_exclusive(mals_handle h, const char* call, Body&& body) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int { return body(msg); };
   TopnRequest rq;
   rq.kind = TOPN_KIND_CALL;
   rq.call = &fn;
@@ -202,6 +195,52 @@ int foldin_exclusive_all(mals_handle* hs, int n, int i, const std::function<int(
   return rc;
 }
 
+// ---- the member loop (the rules: at the head of this file) --------------------------------------------------------------------
+// One slot of temporaries per member, the caller's; member 0's is inline, so that a single handle allocates nothing.
+template <class T>
+struct MemberSlots {
+  explicit MemberSlots(int n_members) : more((size_t)std::max(0, n_members - 1)) {}
+  T& operator[](int m) { return m == 0 ? first : more[(size_t)m - 1]; }
+  void release(int m) { (*this)[m] = T(); }
+  T first;
+  std::vector<T> more;
+};
+struct NoSlots { void release(int) {} };
+
+// enqueue(m, msg) for every member, then finish(m, msg) for every member: both -> MALS_OK or the call's failure
+template <class Slots, class Enqueue, class Finish>
+int member_loop(mals_handle* hs, int n_members, Slots& slots, std::string& msg, Enqueue&& enqueue, Finish&& finish) {
+  // member m's device current.  hipSetDevice is not free even where it changes nothing, so it is called only when the
+  // device does change: never for a handle, nor for members that share a device
+  int dev = -1;
+  FCHK(msg, hipGetDevice(&dev));
+  auto on_device = [&](int m) -> hipError_t {
+    if (hs[m]->cfg.device == dev) return hipSuccess;
+    const hipError_t e = hipSetDevice(hs[m]->cfg.device);
+    dev = e == hipSuccess ? hs[m]->cfg.device : -1;
+    return e;
+  };
+  auto step = [&](int m, auto& fn) -> int {
+    FCHK(msg, on_device(m));
+    return fn(m, msg);
+  };
+  int rc = MALS_OK, touched = 0;
+  while (rc == MALS_OK && touched < n_members) rc = step(touched++, enqueue);
+  if constexpr (!std::is_null_pointer_v<std::decay_t<Finish>>)   // (member_each has no second walk)
+    for (int m = 0; m < n_members && rc == MALS_OK; ++m) rc = step(m, finish);
+  for (int m = 0; rc != MALS_OK && m < touched; ++m)   // nothing of the call may still run when it returns
+    if (on_device(m) == hipSuccess) (void)hipStreamSynchronize(hs[m]->stream);
+  for (int m = 0; !std::is_same_v<Slots, NoSlots> && m < n_members; ++m)
+    if (on_device(m) == hipSuccess) slots.release(m);
+  return rc;
+}
+
+// one step per member that leaves nothing enqueued (host work, or device work it waits for itself)
+template <class Slots, class Step>
+int member_each(mals_handle* hs, int n_members, Slots& slots, std::string& msg, Step&& step) {
+  return member_loop(hs, n_members, slots, msg, step, nullptr);
+}
+
 int foldin_lds_limit(std::string& msg) {
   static std::once_flag once;
   static hipError_t e = hipSuccess;
@@ -219,55 +258,88 @@ int foldin_lds_limit(std::string& msg) {
 
 FoldinSolverView foldin_view(const FoldinSide& s) { return {s.a.get(), s.tau.get(), s.ipiv.get()}; }
 
-// row -> level of the last update of the batch that touched it (open addressing, linear probing)
-uint32_t& foldin_slot(std::vector<int64_t>& keys, std::vector<uint32_t>& vals, int64_t row) {
-  const size_t mask = keys.size() - 1;
-  size_t i = (size_t)(((uint64_t)row * 0x9E3779B97F4A7C15ull) >> 20) & mask;
-  while (keys[i] != row && keys[i] != -1) i = (i + 1) & mask;
-  if (keys[i] == -1) {
-    keys[i] = row;
-    vals[i] = 0;
-  }
-  return vals[i];
-}
-
-// ---- mals_set_preferences -------------------------------------------------------------------------------------------
-// A batch runs in three steps, so that a group can have every member's kernels enqueued before it waits for any of them
-// (mals_group_set_preferences): the level plan (the same for every replica the batch goes to), the enqueue half (uploads,
-// the level kernels and the status copy on the handle's stream, no wait) and the collect half (the wait and the host-side
-// bookkeeping).  One handle runs the three back to back.
-struct FoldinPlan {
-  std::vector<int64_t> off, order;   // updates of level l: order[off[l] .. off[l + 1])
-  uint32_t n_levels = 0;
-};
-
-void foldin_set_plan(FoldinState& fs, int64_t n, const int64_t* urow, const int64_t* irow, FoldinPlan& p) {
-  // levels: 1 + the larger level of the last update of the same X row and of the same Y row
-  size_t cap = 16;
-  while (cap < 2 * (size_t)n) cap <<= 1;
+// every write is a new model: the next half-iteration re-pads and recomputes its Gramian (the generation's solvers stay)
+void foldin_new_model(mals_handle h) {
   for (int s = 0; s < 2; ++s) {
-    fs.lk[s].assign(cap, -1);
-    fs.lv[s].resize(cap);
+    h->side[s].G_valid = false;
+    ++h->side[s].F_epoch;
   }
-  std::vector<uint32_t> level((size_t)n);
-  uint32_t n_levels = 0;
-  for (int64_t t = 0; t < n; ++t) {
-    uint32_t& lu = foldin_slot(fs.lk[0], fs.lv[0], urow[t]);
-    uint32_t& li = foldin_slot(fs.lk[1], fs.lv[1], irow[t]);
-    const uint32_t l = std::max(lu, li) + 1;
-    level[(size_t)t] = lu = li = l;
-    n_levels = std::max(n_levels, l);
-  }
-  std::vector<int64_t>& off = p.off;
-  off.assign((size_t)n_levels + 2, 0);
-  for (int64_t t = 0; t < n; ++t) ++off[level[(size_t)t] + 1];
-  for (uint32_t l = 1; l <= n_levels + 1; ++l) off[l] += off[l - 1];
-  std::vector<int64_t> pos(off.begin(), off.end());
-  p.order.resize((size_t)n);
-  for (int64_t t = 0; t < n; ++t) p.order[(size_t)pos[level[(size_t)t]]++] = t;
-  p.n_levels = n_levels;
 }
 
+// ---- mals_set_foldin_solver / mals_set_foldin_learn_rate --------------------------------------------------------------------
+// inside a ticket: the solver's factors onto the handle's device (ipiv: the inverse of its pivot permutation)
+int foldin_solver_install(mals_handle h, int side, mals_solver s, const std::vector<int32_t>& ipiv, std::string& msg) {
+  const int k = h->cfg.features;
+  FoldinSide& fs = foldin_state(h)->solver[side];
+  fs.present = false;
+  if (!s) return MALS_OK;
+  if (!fs.a.get()) {
+    FCHK(msg, fs.a.alloc((size_t)k * k));
+    FCHK(msg, fs.tau.alloc((size_t)k));
+    FCHK(msg, fs.ipiv.alloc((size_t)k));
+  }
+  FCHK(msg, hipMemcpyAsync(fs.a.get(), s->qr.factors(), sizeof(double) * (size_t)k * k, hipMemcpyHostToDevice, h->stream));
+  FCHK(msg, hipMemcpyAsync(fs.tau.get(), s->qr.taus(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, h->stream));
+  FCHK(msg, hipMemcpyAsync(fs.ipiv.get(), ipiv.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, h->stream));
+  FCHK(msg, hipStreamSynchronize(h->stream));
+  fs.present = true;
+  return MALS_OK;
+}
+
+std::vector<int32_t> foldin_solver_ipiv(mals_solver s, int k) {
+  std::vector<int32_t> ipiv((size_t)k);
+  if (s)
+    for (int j = 0; j < k; ++j) ipiv[(size_t)s->qr.pivots()[j]] = j;
+  return ipiv;
+}
+
+int foldin_solver_members(mals_handle* hs, int n_members, int side, mals_solver s, std::string& msg) {
+  const std::vector<int32_t> ipiv = foldin_solver_ipiv(s, hs[0]->cfg.features);
+  NoSlots none;
+  return member_each(hs, n_members, none, msg, [&](int m, std::string& why) { return foldin_solver_install(hs[m], side, s, ipiv, why); });
+}
+
+int foldin_rate_members(mals_handle* hs, int n_members, double rate) {
+  for (int m = 0; m < n_members; ++m) foldin_state(hs[m])->rate = rate;
+  return MALS_OK;
+}
+
+// the pairs against the replicas as they stand inside the ticket (a concurrent grow is ordered before or after it).
+// local_users: a batch names the users whose known items this handle holds, [row_offset, min(foldin_user_rows_end, n_total));
+// else any user of the replica
+int foldin_check_pairs(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, bool allow_unknown, bool local_users,
+                       std::string& msg) {
+  const SideState& x = h->side[MALS_SIDE_X];
+  const SideState& y = h->side[MALS_SIDE_Y];
+  if (!x.F || !y.F) {
+    msg = "factor replicas not available";
+    return MALS_INVALID_ARG;
+  }
+  const int64_t u_lo = local_users ? x.row_offset : 0, u_hi = local_users ? std::min(foldin_user_rows_end(h), x.n_total) : x.n_total;
+  for (int64_t t = 0; t < n; ++t) {
+    const bool u_ok = (user_row[t] >= u_lo && user_row[t] < u_hi) || (allow_unknown && user_row[t] == -1);
+    const bool i_ok = (item_row[t] >= 0 && item_row[t] < y.n_total) || (allow_unknown && item_row[t] == -1);
+    if (!u_ok || !i_ok) {
+      msg = "pair " + std::to_string(t) + ": row outside the factor replicas (or the user's known items are not on this handle)";
+      return MALS_INVALID_ARG;
+    }
+  }
+  return MALS_OK;
+}
+
+// a write's batch before any work: a handle's call names its own users and marks the rows recent (doAppend,
+// DelegateGenerationManager.java:179-186); a group's names any user (each member is asked all the same) and does not mark
+int foldin_write_ready(mals_handle* hs, int n_members, bool via_group, int64_t n, const int64_t* user_row, const int64_t* item_row, std::string& msg) {
+  for (int m = 0; m < n_members; ++m)
+    if (int rc = foldin_check_pairs(hs[m], n, user_row, item_row, false, !via_group, msg)) return rc;
+  if (!via_group) generation_mark_pairs(hs[0], n, user_row, item_row);
+  return MALS_OK;
+}
+
+// ---- mals_set_preferences -------------------------------------------------------------------------------------------------
+// The level plan (foldin_plan.h, the same for every replica the batch goes to), then per member the enqueue half (uploads, the
+// level kernels and the status copy on the handle's stream, no wait) and the collect half (the wait and the host-side
+// bookkeeping).
 int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const float* value, const FoldinPlan& p,
                        std::string& msg) {
   FoldinState& fs = *foldin_state(h);
@@ -275,9 +347,6 @@ int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int6
   SideState& y = h->side[MALS_SIDE_Y];
   const int k = h->cfg.features;
   if (int rc = foldin_lds_limit(msg)) return rc;
-  const std::vector<int64_t>& off = p.off;
-  const std::vector<int64_t>& order = p.order;
-  const uint32_t n_levels = p.n_levels;
   // level order on the device: user rows | item rows | values, one copy
   const size_t bytes = sizeof(int64_t) * 2 * (size_t)n + sizeof(float) * (size_t)n;
   FCHK(msg, fs.h_stage.reserve(std::max(bytes, sizeof(int32_t) * (size_t)n), h->stream));
@@ -291,7 +360,7 @@ int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int6
   int64_t* hi = hu + n;
   float* hv = reinterpret_cast<float*>(hi + n);
   for (int64_t j = 0; j < n; ++j) {
-    const int64_t t = order[(size_t)j];
+    const int64_t t = p.order[(size_t)j];
     hu[j] = urow[t];
     hi[j] = irow[t];
     hv[j] = value[t];
@@ -302,8 +371,8 @@ int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int6
   const FoldinSide& SY = fs.solver[MALS_SIDE_Y];
   const size_t lds = (size_t)k * FOLDIN_LANES * sizeof(double);
   FCHK(msg, hipEventRecord(fs.ev[0], h->stream));
-  for (uint32_t l = 1; l <= n_levels; ++l) {
-    const int64_t u0 = off[l], u1 = off[l + 1];
+  for (uint32_t l = 1; l <= p.n_levels; ++l) {
+    const int64_t u0 = p.off[l], u1 = p.off[l + 1];
     hipLaunchKernelGGL(foldin_update_kernel, dim3((unsigned)((u1 - u0 + FOLDIN_LANES - 1) / FOLDIN_LANES)), dim3(FOLDIN_LANES), lds, h->stream, x.F,
                        y.F, k, fs.d_rows.get(), fs.d_rows.get() + n, fs.d_val.get(), u0, u1, foldin_view(SX), foldin_view(SY), SX.present ? 1 : 0,
                        SY.present ? 1 : 0, fs.rate, fs.big_total, fs.d_fold.get(), fs.d_status.get());
@@ -321,97 +390,94 @@ int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int6
                        int32_t* status_out, std::string& msg) {
   FoldinState& fs = *foldin_state(h);
   SideState& x = h->side[MALS_SIDE_X];
-  const std::vector<int64_t>& order = p.order;
-  const uint32_t n_levels = p.n_levels;
   const int32_t* hs = reinterpret_cast<const int32_t*>(fs.h_stage.get());
   FCHK(msg, hipStreamSynchronize(h->stream));
   float dev_ms = 0.f;
   FCHK(msg, hipEventElapsedTime(&dev_ms, fs.ev[0], fs.ev[1]));
-  // every write is a new model: the next half-iteration re-pads and recomputes its Gramian (the generation's solvers stay)
-  for (int s = 0; s < 2; ++s) {
-    h->side[s].G_valid = false;
-    ++h->side[s].F_epoch;
-  }
+  foldin_new_model(h);
   int first = MALS_OK, first_why = 0;
   int64_t first_t = -1, applied = 0, failed = 0, big = 0;
   for (int64_t j = 0; j < n; ++j) {
-    const int64_t t = order[(size_t)j];
-    const int32_t w = hs[j];
-    const int code = w & 0xff;
-    big += (w >> 16) & 3;
-    if (status_out) status_out[t] = code;
-    if (code != MALS_OK) {
+    const int64_t t = p.order[(size_t)j];
+    const FoldinStatus st = foldin_status_decode(hs[j]);
+    big += st.big;
+    if (status_out) status_out[t] = st.code;
+    if (st.code != MALS_OK) {
       ++failed;
       if (first_t < 0 || t < first_t) {
         first_t = t;
-        first = code;
-        first_why = (w >> 8) & 0xff;
+        first = st.code;
+        first_why = st.why;
       }
       continue;
     }
     ++applied;
-    if (urow[t] >= own_lo && urow[t] < own_hi)
-      foldin_overlay_add(fs, urow[t] - x.row_offset, (int32_t)irow[t]);   // knownItemIDs.get(userID).add(itemID) (:813-836)
+    if (urow[t] >= own_lo && urow[t] < own_hi) fs.known.add(urow[t] - x.row_offset, (int32_t)irow[t]);   // knownItemIDs.get(userID).add(itemID) (:813-836)
   }
   if (applied) popular_touch(h, false);   // known items were added: what mals_most_popular_items counted is stale
   std::atomic<int64_t>* c = h->foldin_counters;
   c[0] += applied;
   c[1] += failed;
   c[2] += big;
-  c[3] += n_levels;
+  c[3] += p.n_levels;
   c[4] += (int64_t)((double)dev_ms * 1e6);
   c[5].store((int64_t)((double)dev_ms * 1e6));
-  if (first != MALS_OK) {
-    static const char* why[] = {"", "estimate is not finite (foldInWeight: checkState)", "item fold-in delta is not finite (checkState, item loop)",
-                                "user fold-in delta is not finite (checkState, user loop)",
-                                "X^T X solver set without a Y^T Y solver: the reference's item branch reads norm(null)"};
-    msg = "update " + std::to_string(first_t) + ": " + why[first_why < 5 ? first_why : 0];
-  }
+  if (first != MALS_OK) msg = "update " + std::to_string(first_t) + ": " + foldin_why_text(first_why);
   return first;
 }
 
-int foldin_set_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const float* value, int32_t* status_out,
-                   std::string& msg) {
-  FoldinPlan p;
-  foldin_set_plan(*foldin_state(h), n, urow, irow, p);
-  if (int rc = foldin_set_enqueue(h, n, urow, irow, value, p, msg)) return rc;
-  return foldin_set_collect(h, n, urow, irow, p, std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max(), status_out, msg);
+// own (n_members + 1): member m records the known items of the users own[m] <= u < own[m + 1]
+int foldin_set_members(mals_handle* hs, int n_members, const int64_t* own, bool via_group, int64_t n, const int64_t* urow, const int64_t* irow,
+                       const float* value, int32_t* status_out, std::string& msg) {
+  if (int rc = foldin_write_ready(hs, n_members, via_group, n, urow, irow, msg)) return rc;
+  FoldinPlan plan;
+  foldin_set_plan(foldin_state(hs[0])->plan_scratch, n, urow, irow, plan);
+  // The statuses are every replica's own (the same arithmetic on the same bits); the caller gets member 0's, failed updates
+  // among them, and a member that answers otherwise is a failure of its own
+  int first = MALS_OK;
+  std::string first_msg;
+  NoSlots none;
+  const int rc = member_loop(
+      hs, n_members, none, msg, [&](int m, std::string& why) { return foldin_set_enqueue(hs[m], n, urow, irow, value, plan, why); },
+      [&](int m, std::string& why) -> int {
+        std::string mine;
+        const int r = foldin_set_collect(hs[m], n, urow, irow, plan, own[m], own[m + 1], m == 0 ? status_out : nullptr, mine);
+        if (m == 0) {
+          first = r;
+          first_msg.swap(mine);
+          return MALS_OK;
+        }
+        if (r == first) return MALS_OK;
+        why = "member " + std::to_string(m) + " answered " + std::to_string(r) + " where member 0 answered " + std::to_string(first) + ": " + mine;
+        return r == MALS_OK ? MALS_HIP_ERROR : r;
+      });
+  if (rc != MALS_OK) return rc;
+  msg.swap(first_msg);
+  return first;
 }
 
 // ---- mals_remove_preferences ----------------------------------------------------------------------------------------
-// Three steps as well (mals_group_remove_preferences): the decision, which is the known items' holder's alone -- the pairs
-// whose user lies in [own_lo, own_hi) against this handle's sets; (position in the batch, user) of every user a pair
-// empties is appended to `emptied` -- then zeroing those rows of X (enqueue) and the wait (collect), which every replica
-// runs with the same list.
+// The decision first, which is the known items' holder's alone -- the pairs whose user lies in [own_lo, own_hi) against this
+// handle's sets; (position in the batch, user) of every user a pair empties is appended to `emptied` -- then zeroing those
+// rows of X (enqueue) and the wait (collect), which every replica runs with the same list.
 int foldin_remove_decide(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, int64_t own_lo, int64_t own_hi,
                          std::vector<std::pair<int64_t, int64_t>>& emptied, std::string& msg) {
-  FoldinState& fs = *foldin_state(h);
+  KnownOverlay& known = foldin_state(h)->known;
   SideState& x = h->side[MALS_SIDE_X];
   auto mine = [&](int64_t t) { return urow[t] >= own_lo && urow[t] < own_hi; };
-  // every user of the batch without a replaced set gets one first: its base row and additions, fetched together
+  // every user of the batch without a whole set gets one first: its base row and additions, fetched together
   std::vector<int64_t> need;
-  for (int64_t t = 0; t < n; ++t) {
-    if (!mine(t)) continue;
-    const int64_t lr = urow[t] - x.row_offset;
-    if (!fs.replaced.count(lr)) need.push_back(lr);
-  }
+  for (int64_t t = 0; t < n; ++t)
+    if (mine(t) && !known.has_set(urow[t] - x.row_offset)) need.push_back(urow[t] - x.row_offset);
   std::sort(need.begin(), need.end());
   need.erase(std::unique(need.begin(), need.end()), need.end());
   std::vector<std::vector<int32_t>> full;
   if (int rc = foldin_known_full(h, need, full, msg)) return rc;
   popular_touch(h, false);   // (conservative: a batch that removes nothing recounts too)
-  for (size_t j = 0; j < need.size(); ++j) {
-    if (need[j] < (int64_t)fs.head.size()) fs.head[(size_t)need[j]] = UINT32_MAX;
-    fs.replaced[need[j]].swap(full[j]);   // (an empty set: a user without known items, whose removals are ignored)
-  }
-  for (int64_t t = 0; t < n; ++t) {
-    if (!mine(t)) continue;
-    std::vector<int32_t>& v = fs.replaced[urow[t] - x.row_offset];
-    auto p = std::lower_bound(v.begin(), v.end(), (int32_t)irow[t]);
-    if (p == v.end() || *p != (int32_t)irow[t]) continue;  // an unknown user, or an item it does not know: ignored (:1024-1033)
-    v.erase(p);
-    if (v.empty()) emptied.push_back({t, urow[t]});  // the user goes (:1040-1058)
-  }
+  for (size_t j = 0; j < need.size(); ++j) known.install(need[j], full[j]);   // (an empty set: a user without known items, whose removals are ignored)
+  for (int64_t t = 0; t < n; ++t)
+    // an item the user does not know: ignored (:1024-1033); its last one: the user goes (:1040-1058)
+    if (mine(t) && known.remove(urow[t] - x.row_offset, (int32_t)irow[t]) == KnownOverlay::EMPTIED) emptied.push_back({t, urow[t]});
   return MALS_OK;
 }
 
@@ -430,31 +496,42 @@ int foldin_remove_enqueue(mals_handle h, const std::vector<int64_t>& removed, De
 
 int foldin_remove_collect(mals_handle h, bool any_removed, std::string& msg) {
   if (any_removed) FCHK(msg, hipStreamSynchronize(h->stream));
-  for (int s = 0; s < 2; ++s) {
-    h->side[s].G_valid = false;
-    ++h->side[s].F_epoch;
-  }
+  foldin_new_model(h);
   return MALS_OK;
 }
 
-int foldin_remove_run(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, int64_t* removed_out, int64_t* n_removed_out,
-                      std::string& msg) {
+int foldin_remove_members(mals_handle* hs, int n_members, const int64_t* own, bool via_group, int64_t n, const int64_t* urow, const int64_t* irow,
+                          int64_t* removed_out, int64_t* n_removed_out, std::string& msg) {
+  for (int m = 0; m < n_members; ++m)
+    if (!hs[m]->side[MALS_SIDE_X].has_matrix && !hs[m]->known_ptr) {
+      msg = std::string("the user-side matrix (or ") + (via_group ? "the installed known items" : "mals_set_known_items") + ") holds the known items";
+      return MALS_INVALID_ARG;
+    }
+  if (int rc = foldin_write_ready(hs, n_members, via_group, n, urow, irow, msg)) return rc;
+  // the owners decide (small reads of their own known items, each waited for), in batch order within each owner; a user has
+  // one owner.  Every decision is made before any row is zeroed
   std::vector<std::pair<int64_t, int64_t>> emptied;
-  if (int rc = foldin_remove_decide(h, n, urow, irow, std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max(), emptied, msg))
+  NoSlots none;
+  if (int rc = member_each(hs, n_members, none, msg, [&](int m, std::string& why) {
+        return foldin_remove_decide(hs[m], n, urow, irow, own[m], own[m + 1], emptied, why);
+      }))
     return rc;
+  std::sort(emptied.begin(), emptied.end());
   std::vector<int64_t> removed;
   for (const auto& e : emptied) removed.push_back(e.second);
-  DeviceBuffer<int64_t> d;
-  if (int rc = foldin_remove_enqueue(h, removed, d, msg)) return rc;
-  if (int rc = foldin_remove_collect(h, !removed.empty(), msg)) return rc;
+  // every replica zeroes the same rows
+  MemberSlots<DeviceBuffer<int64_t>> d(n_members);
+  if (int rc = member_loop(
+          hs, n_members, d, msg, [&](int m, std::string& why) { return foldin_remove_enqueue(hs[m], removed, d[m], why); },
+          [&](int m, std::string& why) { return foldin_remove_collect(hs[m], !removed.empty(), why); }))
+    return rc;
   if (removed_out) std::copy(removed.begin(), removed.end(), removed_out);
   if (n_removed_out) *n_removed_out = (int64_t)removed.size();
   return MALS_OK;
 }
 
 // ---- mals_grow_factor_rows ------------------------------------------------------------------------------------------
-// Two steps (mals_group_grow_factor_rows enqueues every member's copies before it waits for any): the new blocks and the
-// copies into them on the handle's stream, then the wait and the swap.
+// Per member the new blocks and the copies into them on the handle's stream (enqueue), then the wait and the swap (finish).
 struct FoldinGrow {
   DeviceBuffer<float> rows;      // the larger replica, when the capacity did not do
   DeviceBuffer<uint32_t> bits;   // the longer userTagIDs mask (side Y)
@@ -515,12 +592,17 @@ int foldin_grow_finish(mals_handle h, int side, int64_t n_rows, FoldinGrow& gw, 
   return MALS_OK;
 }
 
-int foldin_grow_run(mals_handle h, int side, int64_t n_rows, std::string& msg) {
-  // grown users are this handle's when its users already reached the end of the old replica (a single handle)
-  const bool owns = foldin_user_rows_end(h) >= h->side[side].n_total;
-  FoldinGrow gw;
-  if (int rc = foldin_grow_enqueue(h, side, n_rows, gw, msg)) return rc;
-  return foldin_grow_finish(h, side, n_rows, gw, owns, msg);
+// grown_owner: the member that owns the users past the installed matrix, or -1
+int foldin_grow_members(mals_handle* hs, int n_members, int side, int64_t n_rows, int grown_owner, bool via_group, std::string& msg) {
+  for (int m = 0; m < n_members; ++m)
+    if (!hs[m]->side[side].F) {
+      msg = std::string("the replica is not declared (") + (via_group ? "mals_group_set_factor_rows" : "mals_set_factor_rows") + ")";
+      return MALS_INVALID_ARG;
+    }
+  MemberSlots<FoldinGrow> gw(n_members);   // (what a failure left behind goes with its device current)
+  return member_loop(
+      hs, n_members, gw, msg, [&](int m, std::string& why) { return foldin_grow_enqueue(hs[m], side, n_rows, gw[m], why); },
+      [&](int m, std::string& why) { return foldin_grow_finish(hs[m], side, n_rows, gw[m], m == grown_owner, why); });
 }
 
 // ---- mals_anonymous_features / mals_estimate_for_anonymous ----------------------------------------------------------

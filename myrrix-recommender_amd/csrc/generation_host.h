@@ -342,7 +342,7 @@ struct GenPrepared {
   DeviceBuffer<int64_t> known_ptr;
   DeviceBuffer<int32_t> known_idx;
   std::unordered_map<int64_t, std::vector<int32_t>> kept_sets;       // merged user row -> its known items as merged item rows
-                                                                     // (the form of FoldinState::replaced: swapped in whole)
+                                                                     // (KnownOverlay::Sets, foldin_plan.h: swapped in whole)
   std::vector<int64_t> tag_users;                                    // merged user rows: ascending, unique
   DeviceBuffer<uint32_t> tag_bits;
   int64_t n_tag_items = 0;
@@ -401,7 +401,7 @@ void generation_swap(mals_handle h, GenPrepared& p) {
     x.n_local = h->known_rows;
     // the kept users: rows past the base CSR with a whole set of their own, as grown users are after a removal
     if (p.side[MALS_SIDE_X].n_kept > 0) {
-      foldin_state(h)->replaced.swap(p.kept_sets);   // (malsi_clear_known_items left it empty)
+      foldin_state(h)->known.install_all(p.kept_sets);   // (malsi_clear_known_items left it empty)
       h->grown_users_end.store(x.n_total, std::memory_order_release);
     }
   }

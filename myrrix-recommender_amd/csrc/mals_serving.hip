@@ -13,6 +13,7 @@
 #include "factor_digest.h"
 #include "mals_internal.h"
 #include "mals_handle.h"
+#include "foldin_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -33,6 +34,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -93,6 +95,17 @@ bool foldin_known_view(mals_handle h, int64_t local_row, std::vector<int64_t>& o
 bool foldin_has_overlay(mals_handle h);
 int foldin_known_full(mals_handle h, const std::vector<int64_t>& rows, std::vector<std::vector<int32_t>>& outs, std::string& msg);
 #include "topn_host.h"
+
+// (a failed argument check of a recommend call: the message under the front's mutex -- other request threads may be
+// inside the same handle)
+int topn_fail(mals_handle h, int code, const char* msg) {
+  std::lock_guard<std::mutex> lk(topn_front(h)->mu);
+  h->err = msg;
+  return code;
+}
+
+// generation_host.h (included after foldin_host.h, whose writes mark their rows recent through this)
+void generation_mark_pairs(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row);
 #include "foldin_host.h"
 #include "popular_host.h"
 #include "generation_host.h"
@@ -134,14 +147,6 @@ void malsi_popular_new_generation(mals_handle h, bool new_rows) { popular_new_ge
 void malsi_generation_drop_recent(mals_handle h, int side) { generation_drop_recent(h, side); }
 
 extern "C" {
-
-// (a failed argument check of a recommend call: the message under the front's mutex -- other request threads may be
-// inside the same handle)
-static int topn_fail(mals_handle h, int code, const char* msg) {
-  std::lock_guard<std::mutex> lk(topn_front(h)->mu);
-  h->err = msg;
-  return code;
-}
 
 // the last checks of a call that scores items: the tag items fit the catalogue, the calling thread is on the handle's device
 static int topn_serving_ready(mals_handle h) {
@@ -460,61 +465,18 @@ void malsi_mark_group_member(mals_handle h) {
   if (h) h->group_member = true;
 }
 
-// via_group: the call comes from the member's group (a mals_group_* twin), which routes the known items to their owner
-static int foldin_refuse(mals_handle h, const char* call, bool via_group = false) {
-  if (h->group_member && !via_group)
-    return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": not for a member of a group (writes and fold-in reads go through the group: mals_group_set_preferences ...)").c_str());
-  if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
-  return MALS_OK;
-}
-
-// inside a ticket: the solver's factors onto the handle's device (ipiv: the inverse of its pivot permutation)
-static int foldin_solver_install(mals_handle h, int side, mals_solver s, const std::vector<int32_t>& ipiv, std::string& msg) {
-  const int k = h->cfg.features;
-  FoldinSide& fs = foldin_state(h)->solver[side];
-  fs.present = false;
-  if (!s) return MALS_OK;
-  if (!fs.a.get()) {
-    FCHK(msg, fs.a.alloc((size_t)k * k));
-    FCHK(msg, fs.tau.alloc((size_t)k));
-    FCHK(msg, fs.ipiv.alloc((size_t)k));
-  }
-  FCHK(msg, hipMemcpyAsync(fs.a.get(), s->qr.factors(), sizeof(double) * (size_t)k * k, hipMemcpyHostToDevice, h->stream));
-  FCHK(msg, hipMemcpyAsync(fs.tau.get(), s->qr.taus(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, h->stream));
-  FCHK(msg, hipMemcpyAsync(fs.ipiv.get(), ipiv.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, h->stream));
-  FCHK(msg, hipStreamSynchronize(h->stream));
-  fs.present = true;
-  return MALS_OK;
-}
-
-static std::vector<int32_t> foldin_solver_ipiv(mals_solver s, int k) {
-  std::vector<int32_t> ipiv((size_t)k);
-  if (s)
-    for (int j = 0; j < k; ++j) ipiv[(size_t)s->qr.pivots()[j]] = j;
-  return ipiv;
-}
-
 int mals_set_foldin_solver(mals_handle h, int side, mals_solver s) {
   CHECK_SIDE(h, side);
   if (int rc = foldin_refuse(h, "mals_set_foldin_solver")) return rc;
-  const int k = h->cfg.features;
-  if (s && s->qr.dim() != k) return topn_fail(h, MALS_INVALID_ARG, "mals_set_foldin_solver: the solver's dimension is not the handle's features");
-  const std::vector<int32_t> ipiv = foldin_solver_ipiv(s, k);
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int { return foldin_solver_install(h, side, s, ipiv, msg); };
-  return foldin_exclusive(h, fn, msg, "mals_set_foldin_solver");
+  if (s && s->qr.dim() != h->cfg.features) return topn_fail(h, MALS_INVALID_ARG, "mals_set_foldin_solver: the solver's dimension is not the handle's features");
+  return foldin_exclusive(h, "mals_set_foldin_solver", [&](std::string& msg) -> int { return foldin_solver_members(&h, 1, side, s, msg); });
 }
 
 int mals_set_foldin_learn_rate(mals_handle h, double rate) {
   if (!h) return MALS_INVALID_ARG;
   if (!std::isfinite(rate)) return topn_fail(h, MALS_INVALID_ARG, "the fold-in learning rate must be finite");
   if (int rc = foldin_refuse(h, "mals_set_foldin_learn_rate")) return rc;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    foldin_state(h)->rate = rate;
-    return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_set_foldin_learn_rate");
+  return foldin_exclusive(h, "mals_set_foldin_learn_rate", [&](std::string&) -> int { return foldin_rate_members(&h, 1, rate); });
 }
 
 int mals_foldin_stats(mals_handle h, int64_t* out6) {
@@ -523,26 +485,8 @@ int mals_foldin_stats(mals_handle h, int64_t* out6) {
   return MALS_OK;
 }
 
-// the pairs against the replicas as they stand inside the ticket (a concurrent grow is ordered before or after it)
-static int foldin_check_pairs(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, bool allow_unknown, bool local_users,
-                              std::string& msg) {
-  const SideState& x = h->side[MALS_SIDE_X];
-  const SideState& y = h->side[MALS_SIDE_Y];
-  if (!x.F || !y.F) {
-    msg = "factor replicas not available";
-    return MALS_INVALID_ARG;
-  }
-  const int64_t u_lo = local_users ? x.row_offset : 0, u_hi = local_users ? std::min(foldin_user_rows_end(h), x.n_total) : x.n_total;
-  for (int64_t t = 0; t < n; ++t) {
-    const bool u_ok = (user_row[t] >= u_lo && user_row[t] < u_hi) || (allow_unknown && user_row[t] == -1);
-    const bool i_ok = (item_row[t] >= 0 && item_row[t] < y.n_total) || (allow_unknown && item_row[t] == -1);
-    if (!u_ok || !i_ok) {
-      msg = "pair " + std::to_string(t) + ": row outside the factor replicas (or the user's known items are not on this handle)";
-      return MALS_INVALID_ARG;
-    }
-  }
-  return MALS_OK;
-}
+// a handle owns every user its pair check lets through (foldin_write_ready)
+static const int64_t FOLDIN_OWN_ALL[2] = {std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max()};
 
 int mals_set_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
   if (!h) return MALS_INVALID_ARG;
@@ -550,13 +494,9 @@ int mals_set_preferences(mals_handle h, int64_t n, const int64_t* user_row, cons
   if (n < 0 || (n > 0 && (!user_row || !item_row || !value))) return topn_fail(h, MALS_INVALID_ARG, "mals_set_preferences: bad arguments");
   if (n > (int64_t)1 << 30) return topn_fail(h, MALS_INVALID_ARG, "mals_set_preferences: at most 2^30 updates per call");
   if (n == 0) return MALS_OK;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    if (int rc = foldin_check_pairs(h, n, user_row, item_row, false, true, msg)) return rc;
-    generation_mark_pairs(h, n, user_row, item_row);   // doAppend (DelegateGenerationManager.java:179-186)
-    return foldin_set_run(h, n, user_row, item_row, value, status_out, msg);
-  };
-  return foldin_exclusive(h, fn, msg, "mals_set_preferences");
+  return foldin_exclusive(h, "mals_set_preferences", [&](std::string& msg) -> int {
+    return foldin_set_members(&h, 1, FOLDIN_OWN_ALL, false, n, user_row, item_row, value, status_out, msg);
+  });
 }
 
 int mals_remove_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,
@@ -566,31 +506,19 @@ int mals_remove_preferences(mals_handle h, int64_t n, const int64_t* user_row, c
   if (int rc = foldin_refuse(h, "mals_remove_preferences")) return rc;
   if (n < 0 || (n > 0 && (!user_row || !item_row))) return topn_fail(h, MALS_INVALID_ARG, "mals_remove_preferences: bad arguments");
   if (n == 0) return MALS_OK;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    if (!h->side[MALS_SIDE_X].has_matrix && !h->known_ptr) {
-      msg = "the user-side matrix (or mals_set_known_items) holds the known items";
-      return MALS_INVALID_ARG;
-    }
-    if (int rc = foldin_check_pairs(h, n, user_row, item_row, false, true, msg)) return rc;
-    generation_mark_pairs(h, n, user_row, item_row);
-    return foldin_remove_run(h, n, user_row, item_row, removed_users_out, n_removed_out, msg);
-  };
-  return foldin_exclusive(h, fn, msg, "mals_remove_preferences");
+  return foldin_exclusive(h, "mals_remove_preferences", [&](std::string& msg) -> int {
+    return foldin_remove_members(&h, 1, FOLDIN_OWN_ALL, false, n, user_row, item_row, removed_users_out, n_removed_out, msg);
+  });
 }
 
 int mals_grow_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
   CHECK_SIDE(h, side);
   if (int rc = foldin_refuse(h, "mals_grow_factor_rows")) return rc;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    if (!h->side[side].F) {
-      msg = "the replica is not declared (mals_set_factor_rows)";
-      return MALS_INVALID_ARG;
-    }
-    return foldin_grow_run(h, side, n_rows_total, msg);
-  };
-  return foldin_exclusive(h, fn, msg, "mals_grow_factor_rows");
+  return foldin_exclusive(h, "mals_grow_factor_rows", [&](std::string& msg) -> int {
+    // grown users are this handle's when its users already reached the end of the old replica
+    const int grown_owner = foldin_user_rows_end(h) >= h->side[side].n_total ? 0 : -1;
+    return foldin_grow_members(&h, 1, side, n_rows_total, grown_owner, false, msg);
+  });
 }
 
 static int foldin_estimate_impl(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out, bool via_group) {
@@ -598,8 +526,7 @@ static int foldin_estimate_impl(mals_handle h, int64_t n, const int64_t* user_ro
   if (int rc = foldin_refuse(h, "mals_estimate_preferences", via_group)) return rc;
   if (n < 0 || (n > 0 && (!user_row || !item_row || !out))) return topn_fail(h, MALS_INVALID_ARG, "mals_estimate_preferences: bad arguments");
   if (n == 0) return MALS_OK;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, "mals_estimate_preferences", [&](std::string& msg) -> int {
     if (int rc = foldin_check_pairs(h, n, user_row, item_row, true, false, msg)) return rc;
     DeviceBuffer<int64_t> d_rows;
     DeviceBuffer<float> d_out;
@@ -618,8 +545,7 @@ static int foldin_estimate_impl(mals_handle h, int64_t n, const int64_t* user_ro
         return MALS_INVALID_ARG;
       }
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_estimate_preferences");
+  });
 }
 
 int mals_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, float* out) {
@@ -638,8 +564,7 @@ static int foldin_anonymous(mals_handle h, int32_t n_queries, const int64_t* ite
   if (n_queries == 0) return MALS_OK;
   std::vector<int32_t> found((size_t)n_queries, 0);
   bool no_solver = false;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  const int rc = foldin_exclusive(h, call, [&](std::string& msg) -> int {
     const SideState& y = h->side[MALS_SIDE_Y];
     if (!y.F) {
       msg = "item factor replica not available";
@@ -658,8 +583,8 @@ static int foldin_anonymous(mals_handle h, int32_t n_queries, const int64_t* ite
     no_solver = !foldin_state(h)->solver[MALS_SIDE_Y].present;
     if (no_solver) return MALS_OK;
     return foldin_anonymous_run(h, n_queries, item_ptr, item_row, values, out, found.data(), to_item, dot_out, msg);
-  };
-  if (int rc = foldin_exclusive(h, fn, msg, call)) return rc;
+  });
+  if (rc != MALS_OK) return rc;
   int first = MALS_OK;
   for (int32_t q = 0; q < n_queries; ++q) {
     // no Y^T Y solver: NotReadyException (:570-573); no item of the query has a row: NoSuchItemException (:603-605)
@@ -749,8 +674,7 @@ int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, do
   if (n_rhs < 0 || (n_rhs > 0 && (!b || !x_out))) return topn_fail(h, MALS_INVALID_ARG, "mals_foldin_solve: bad arguments");
   if (n_rhs == 0) return MALS_OK;
   const int k = h->cfg.features;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, "mals_foldin_solve", [&](std::string& msg) -> int {
     FoldinState& fs = *foldin_state(h);
     if (!fs.solver[side].present) {
       msg = "no solver on that side (mals_set_foldin_solver)";
@@ -768,8 +692,7 @@ int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, do
     FCHK(msg, hipMemcpyAsync(x_out, d_x.get(), sizeof(double) * (size_t)n_rhs * k, hipMemcpyDeviceToHost, h->stream));
     FCHK(msg, hipStreamSynchronize(h->stream));
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_foldin_solve");
+  });
 }
 
 // ---- mostPopularItems (popular_host.h) ------------------------------------------------------------------------------------
@@ -784,8 +707,7 @@ int mals_set_tag_users(mals_handle h, int64_t n, const int64_t* user_idx, int me
     HIPCHK(h, hipMemcpy(host.data(), user_idx, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
     user_idx = host.data();
   }
-  popular_set_tag_users(h, n, user_idx);
-  return MALS_OK;
+  return popular_set_tag_users(&h, 1, n, user_idx);
 }
 
 int mals_get_tag_user_count(mals_handle h, int64_t* n_out) {
@@ -800,9 +722,9 @@ int mals_most_popular_items(mals_handle h, mals_rescorer r, int32_t how_many, in
   if (int rc = foldin_refuse(h, "mals_most_popular_items")) return rc;
   if (how_many <= 0 || how_many > 4096 || !item_idx_out || !score_out)
     return topn_fail(h, MALS_INVALID_ARG, "mals_most_popular_items: bad arguments (how_many in 1..4096)");
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int { return popular_run(h, r, how_many, item_idx_out, score_out, n_out, msg); };
-  return foldin_exclusive(h, fn, msg, "mals_most_popular_items");
+  return foldin_exclusive(h, "mals_most_popular_items", [&](std::string& msg) -> int {
+    return popular_members(&h, 1, false, r, how_many, item_idx_out, score_out, n_out, msg);
+  });
 }
 
 int mals_most_popular_stats(mals_handle h, int64_t* out4) {
@@ -824,8 +746,7 @@ int mals_load_generation(mals_handle h, const mals_generation_load* load, mals_g
          L.n_cur[sd] < ((int64_t)1 << 31) && L.n_new[sd] < ((int64_t)1 << 31);
   ok = ok && L.n_item_tag_ids >= 0 && L.n_user_tag_ids >= 0 && (L.n_item_tag_ids == 0 || L.item_tag_ids) && (L.n_user_tag_ids == 0 || L.user_tag_ids);
   if (!ok) return topn_fail(h, MALS_INVALID_ARG, "mals_load_generation: bad arguments (mem kinds, counts in [0, 2^31), null arrays)");
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, "mals_load_generation", [&](std::string& msg) -> int {
     if (int rc = generation_load_run(h, L, result_out, msg)) return rc;
     if (L.flags & MALS_GENERATION_RECOMPUTE_SOLVERS) {   // Generation.recomputeState: the solvers of the merged X and Y
       int first = MALS_OK;
@@ -840,17 +761,14 @@ int mals_load_generation(mals_handle h, const mals_generation_load* load, mals_g
       if (result_out) result_out->solver_status = first;
     }
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_load_generation");
+  });
 }
 
 static int generation_get_impl(mals_handle h, int side, bool ids, int64_t* out, const char* call) {
   CHECK_SIDE(h, side);
   if (!out) return topn_fail(h, MALS_INVALID_ARG, "the output array must not be NULL");
   if (hipSetDevice(h->cfg.device) != hipSuccess) return topn_fail(h, MALS_HIP_ERROR, "hipSetDevice failed");
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int { return generation_get(h, side, ids, out, msg); };
-  return foldin_exclusive(h, fn, msg, call);
+  return foldin_exclusive(h, call, [&](std::string& msg) -> int { return generation_get(h, side, ids, out, msg); });
 }
 int mals_generation_get_ids(mals_handle h, int side, int64_t* ids_out) { return generation_get_impl(h, side, true, ids_out, "mals_generation_get_ids"); }
 int mals_generation_get_map(mals_handle h, int side, int64_t* map_out) { return generation_get_impl(h, side, false, map_out, "mals_generation_get_map"); }
@@ -858,8 +776,7 @@ int mals_generation_get_map(mals_handle h, int side, int64_t* map_out) { return 
 int mals_mark_recent(mals_handle h, int side, int64_t n, const int64_t* rows) {
   CHECK_SIDE(h, side);
   if (n < 0 || (n > 0 && !rows)) return topn_fail(h, MALS_INVALID_ARG, "mals_mark_recent: bad arguments");
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, "mals_mark_recent", [&](std::string& msg) -> int {
     const int64_t n_rows = h->side[side].F ? h->side[side].n_total : 0;
     for (int64_t t = 0; t < n; ++t)
       if (rows[t] < 0 || rows[t] >= n_rows) {
@@ -868,15 +785,13 @@ int mals_mark_recent(mals_handle h, int side, int64_t n, const int64_t* rows) {
       }
     for (int64_t t = 0; t < n; ++t) generation_mark(h, side, rows[t]);
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_mark_recent");
+  });
 }
 
 int mals_get_recent(mals_handle h, int side, int64_t* rows_out, int64_t* n_out) {
   CHECK_SIDE(h, side);
   if (!n_out) return topn_fail(h, MALS_INVALID_ARG, "mals_get_recent: n_out must not be NULL");
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, "mals_get_recent", [&](std::string& msg) -> int {
     const std::vector<uint32_t>& b = generation_state(h)->recent[side];
     const int64_t n_rows = h->side[side].F ? h->side[side].n_total : 0;   // (rows_out holds the replica's rows: never more)
     int64_t n = 0;
@@ -889,8 +804,7 @@ int mals_get_recent(mals_handle h, int side, int64_t* rows_out, int64_t* n_out) 
       }
     *n_out = n;
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_get_recent");
+  });
 }
 
 uint64_t mals_generation_hash_host(int64_t id) { return gen_hash(id); }
@@ -903,166 +817,55 @@ int mals_generation_join_host(const int64_t* cur_ids, int64_t n_cur, const int64
 }  // extern "C"
 
 // ---- the write path on the members of a group (mals_group.cpp: the mals_group_* twins) ---------------------------------
-// A group write is a replicated state machine: every member applies the same batch to its own replicas of X and Y with the
-// same deterministic kernels, nothing is exchanged, and only the owner of a user (own[m] <= user < own[m + 1]) keeps that
-// user's known-item overlay.  Each call below holds the fronts of ALL members (foldin_exclusive_all) while it enqueues
-// every member's device work and only then waits for each: the members work side by side, and a read of any member sees
-// the model before the write or after it.  The caller (the group) orders the writes among themselves.
+// Each call below holds the fronts of ALL members (foldin_exclusive_all) while the write's one driver (foldin_host.h,
+// popular_host.h) enqueues every member's device work and only then waits for each: the members work side by side, and a
+// read of any member sees the model before the write or after it.  The caller (the group) orders the writes among themselves.
 namespace {
-
-// on the device of member m for the rest of the scope's iteration
-int group_on_device(mals_handle h, std::string& msg) {
-  FCHK(msg, hipSetDevice(h->cfg.device));
-  return MALS_OK;
-}
-
-// after an enqueue failed: nothing of the call may still run when it returns
-void group_drain(mals_handle* hs, int n) {
-  for (int m = 0; m < n; ++m)
-    if (hipSetDevice(hs[m]->cfg.device) == hipSuccess) (void)hipStreamSynchronize(hs[m]->stream);
-}
-
-int group_finish(int rc, const std::string& msg, std::string* err) {
+// body(msg) with every member's front held; a failure's text goes to *err
+template <class Body>
+int group_call(mals_handle* hs, int n_members, std::string* err, Body&& body) {
+  std::string msg;
+  const std::function<int()> fn = [&]() -> int { return body(msg); };
+  const int rc = foldin_exclusive_all(hs, n_members, 0, fn);
   if (rc != MALS_OK && err) *err = msg.empty() ? std::string("failed") : msg;
   return rc;
 }
-
 }  // namespace
 
 int malsi_group_set_foldin_solver(mals_handle* hs, int n_members, int side, mals_solver s, std::string* err) {
-  const int k = hs[0]->cfg.features;
-  if (s && s->qr.dim() != k) return group_finish(MALS_INVALID_ARG, "the solver's dimension is not the group's features", err);
-  const std::vector<int32_t> ipiv = foldin_solver_ipiv(s, k);
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    for (int m = 0; m < n_members; ++m) {
-      if (int rc = group_on_device(hs[m], msg)) return rc;
-      if (int rc = foldin_solver_install(hs[m], side, s, ipiv, msg)) return rc;
-    }
-    return MALS_OK;
-  };
-  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+  if (s && s->qr.dim() != hs[0]->cfg.features) {
+    if (err) *err = "the solver's dimension is not the group's features";
+    return MALS_INVALID_ARG;
+  }
+  return group_call(hs, n_members, err, [&](std::string& msg) { return foldin_solver_members(hs, n_members, side, s, msg); });
 }
 
 int malsi_group_set_foldin_learn_rate(mals_handle* hs, int n_members, double rate, std::string* err) {
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    for (int m = 0; m < n_members; ++m) foldin_state(hs[m])->rate = rate;
-    return MALS_OK;
-  };
-  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+  return group_call(hs, n_members, err, [&](std::string&) { return foldin_rate_members(hs, n_members, rate); });
 }
 
 int malsi_group_set_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n, const int64_t* user_row, const int64_t* item_row,
                                 const float* value, int32_t* status_out, std::string* err) {
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    for (int m = 0; m < n_members; ++m)   // (the replicas have one size; each member is asked all the same)
-      if (int rc = foldin_check_pairs(hs[m], n, user_row, item_row, false, false, msg)) return rc;
-    FoldinPlan plan;
-    foldin_set_plan(*foldin_state(hs[0]), n, user_row, item_row, plan);
-    for (int m = 0; m < n_members; ++m) {
-      int rc = group_on_device(hs[m], msg);
-      if (rc == MALS_OK) rc = foldin_set_enqueue(hs[m], n, user_row, item_row, value, plan, msg);
-      if (rc != MALS_OK) {
-        group_drain(hs, m + 1);
-        return rc;
-      }
-    }
-    // every member's kernels are on their way: collect.  The statuses are every replica's own (the same arithmetic on the
-    // same bits); the caller gets member 0's, and a member that answers otherwise is a failure of its own
-    int first = MALS_OK;
-    for (int m = 0; m < n_members; ++m) {
-      std::string mine;
-      int rc = group_on_device(hs[m], mine);
-      if (rc == MALS_OK) rc = foldin_set_collect(hs[m], n, user_row, item_row, plan, own[m], own[m + 1], m == 0 ? status_out : nullptr, mine);
-      if (m == 0) {
-        first = rc;
-        msg = mine;
-      } else if (rc != first) {
-        group_drain(hs, n_members);
-        msg = "member " + std::to_string(m) + " answered " + std::to_string(rc) + " where member 0 answered " + std::to_string(first) + ": " + mine;
-        return rc == MALS_OK ? MALS_HIP_ERROR : rc;
-      }
-    }
-    return first;
-  };
-  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+  return group_call(hs, n_members, err, [&](std::string& msg) -> int {
+    return foldin_set_members(hs, n_members, own, true, n, user_row, item_row, value, status_out, msg);
+  });
 }
 
 int malsi_group_remove_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n, const int64_t* user_row, const int64_t* item_row,
                                    int64_t* removed_users_out, int64_t* n_removed_out, std::string* err) {
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    for (int m = 0; m < n_members; ++m) {
-      if (!hs[m]->side[MALS_SIDE_X].has_matrix && !hs[m]->known_ptr) {
-        msg = "the user-side matrix (or the installed known items) holds the known items";
-        return MALS_INVALID_ARG;
-      }
-      if (int rc = foldin_check_pairs(hs[m], n, user_row, item_row, false, false, msg)) return rc;
-    }
-    // the owners decide (small reads of their own known items), in batch order within each owner; a user has one owner
-    std::vector<std::pair<int64_t, int64_t>> emptied;
-    for (int m = 0; m < n_members; ++m) {
-      if (int rc = group_on_device(hs[m], msg)) return rc;
-      if (int rc = foldin_remove_decide(hs[m], n, user_row, item_row, own[m], own[m + 1], emptied, msg)) return rc;
-    }
-    std::sort(emptied.begin(), emptied.end());
-    std::vector<int64_t> removed;
-    for (const auto& e : emptied) removed.push_back(e.second);
-    // every replica zeroes the same rows
-    std::vector<DeviceBuffer<int64_t>> d((size_t)n_members);
-    int rc = MALS_OK;
-    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
-      rc = group_on_device(hs[m], msg);
-      if (rc == MALS_OK) rc = foldin_remove_enqueue(hs[m], removed, d[(size_t)m], msg);
-    }
-    if (rc != MALS_OK) group_drain(hs, n_members);
-    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
-      rc = group_on_device(hs[m], msg);
-      if (rc == MALS_OK) rc = foldin_remove_collect(hs[m], !removed.empty(), msg);
-    }
-    for (int m = 0; m < n_members; ++m)
-      if (hipSetDevice(hs[m]->cfg.device) == hipSuccess) d[(size_t)m].reset();
-    if (rc != MALS_OK) return rc;
-    if (removed_users_out) std::copy(removed.begin(), removed.end(), removed_users_out);
-    if (n_removed_out) *n_removed_out = (int64_t)removed.size();
-    return MALS_OK;
-  };
-  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+  return group_call(hs, n_members, err, [&](std::string& msg) -> int {
+    return foldin_remove_members(hs, n_members, own, true, n, user_row, item_row, removed_users_out, n_removed_out, msg);
+  });
 }
 
 // grown_owner: the member that owns the users past the installed matrix (the last rank), or -1
 int malsi_group_grow_factor_rows(mals_handle* hs, int n_members, int side, int64_t n_rows_total, int grown_owner, std::string* err) {
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    for (int m = 0; m < n_members; ++m)
-      if (!hs[m]->side[side].F) {
-        msg = "the replica is not declared (mals_group_set_factor_rows)";
-        return MALS_INVALID_ARG;
-      }
-    std::vector<FoldinGrow> gw((size_t)n_members);
-    int rc = MALS_OK;
-    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
-      rc = group_on_device(hs[m], msg);
-      if (rc == MALS_OK) rc = foldin_grow_enqueue(hs[m], side, n_rows_total, gw[(size_t)m], msg);
-    }
-    if (rc != MALS_OK) group_drain(hs, n_members);
-    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
-      rc = group_on_device(hs[m], msg);
-      if (rc == MALS_OK) rc = foldin_grow_finish(hs[m], side, n_rows_total, gw[(size_t)m], m == grown_owner, msg);
-    }
-    for (int m = 0; m < n_members; ++m)   // (what a failure left behind goes with its device current)
-      if (hipSetDevice(hs[m]->cfg.device) == hipSuccess) gw[(size_t)m] = FoldinGrow();
-    return rc;
-  };
-  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+  return group_call(hs, n_members, err, [&](std::string& msg) { return foldin_grow_members(hs, n_members, side, n_rows_total, grown_owner, true, msg); });
 }
 
 // the digest of rows [row_begin, row_begin + n_rows) of every handle's replica, all taken between the same two writes
 int malsi_group_factor_digest(mals_handle* hs, int n_members, int side, int64_t row_begin, int64_t n_rows, uint64_t* out, std::string* err) {
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return group_call(hs, n_members, err, [&](std::string& msg) -> int {
     for (int m = 0; m < n_members; ++m) {
       const SideState& s = hs[m]->side[side];
       if (!s.F) {
@@ -1080,113 +883,34 @@ int malsi_group_factor_digest(mals_handle* hs, int n_members, int side, int64_t 
     const int64_t e0 = row_begin * k, e1 = (row_begin + n_rows) * k;
     // enough workgroups to keep every CU streaming (8 per CU of 256), never more than the float4s ask for
     const unsigned grid = (unsigned)std::min<int64_t>(2048, std::max<int64_t>(1, ((e1 - e0) / 4 + 255) / 256));
-    std::vector<DeviceBuffer<unsigned long long>> cell((size_t)n_members);
+    MemberSlots<DeviceBuffer<unsigned long long>> cell(n_members);
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the digest cell is 64 bits");
-    int rc = MALS_OK;
-    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
-      rc = group_on_device(hs[m], msg);
-      if (rc != MALS_OK) break;
-      rc = [&]() -> int {
-        FCHK(msg, cell[(size_t)m].alloc(1));
-        FCHK(msg, hipMemsetAsync(cell[(size_t)m].get(), 0, sizeof(unsigned long long), hs[m]->stream));
-        hipLaunchKernelGGL(factor_digest_kernel, dim3(grid), dim3(256), 0, hs[m]->stream, hs[m]->side[side].F, e0, e1, cell[(size_t)m].get());
-        FCHK(msg, hipGetLastError());
-        FCHK(msg, hipMemcpyAsync(out + m, cell[(size_t)m].get(), sizeof(uint64_t), hipMemcpyDeviceToHost, hs[m]->stream));
-        return MALS_OK;
-      }();
-    }
-    for (int m = 0; m < n_members; ++m) {
-      if (hipSetDevice(hs[m]->cfg.device) != hipSuccess) continue;
-      const hipError_t e = hipStreamSynchronize(hs[m]->stream);
-      if (e != hipSuccess && rc == MALS_OK) {
-        msg = std::string("hipStreamSynchronize: ") + hipGetErrorString(e);
-        rc = MALS_HIP_ERROR;
-      }
-      cell[(size_t)m].reset();
-    }
-    return rc;
-  };
-  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+    return member_loop(
+        hs, n_members, cell, msg,
+        [&](int m, std::string& why) -> int {
+          FCHK(why, cell[m].alloc(1));
+          FCHK(why, hipMemsetAsync(cell[m].get(), 0, sizeof(unsigned long long), hs[m]->stream));
+          hipLaunchKernelGGL(factor_digest_kernel, dim3(grid), dim3(256), 0, hs[m]->stream, hs[m]->side[side].F, e0, e1, cell[m].get());
+          FCHK(why, hipGetLastError());
+          FCHK(why, hipMemcpyAsync(out + m, cell[m].get(), sizeof(uint64_t), hipMemcpyDeviceToHost, hs[m]->stream));
+          return MALS_OK;
+        },
+        [&](int m, std::string& why) -> int {
+          FCHK(why, hipStreamSynchronize(hs[m]->stream));
+          return MALS_OK;
+        });
+  });
 }
 
-// mals_group_set_tag_users: every member keeps the rows it owns (a handle ignores rows outside its users)
 int malsi_group_set_tag_users(mals_handle* hs, int n_members, int64_t n, const int64_t* user_idx, std::string* err) {
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    for (int m = 0; m < n_members; ++m) popular_set_tag_users(hs[m], n, user_idx);
-    return MALS_OK;
-  };
-  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+  return group_call(hs, n_members, err, [&](std::string&) { return popular_set_tag_users(hs, n_members, n, user_idx); });
 }
 
-// mals_group_most_popular_items: every member counts the users it owns, side by side; the partial arrays are added on
-// member 0 (peer copies), which saturates, strikes the tag items and selects -- after the sum, as one handle would
 int malsi_group_most_popular_items(mals_handle* hs, int n_members, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out,
                                    std::string* err) {
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
-    int64_t n_items = 0;
-    bool any_known = false;
-    for (int m = 0; m < n_members; ++m) {
-      const SideState& y = hs[m]->side[MALS_SIDE_Y];
-      if (!y.F || y.n_total <= 0 || (m > 0 && y.n_total != n_items)) {
-        msg = "the item factor rows are not declared alike on every member";
-        return MALS_INVALID_ARG;
-      }
-      n_items = y.n_total;
-      any_known = any_known || popular_has_known(hs[m]);
-    }
-    if (!any_known) {
-      msg = "no known items: neither a user-side matrix, nor installed known items, nor writes";
-      return MALS_INVALID_ARG;
-    }
-    if (hs[0]->tag_bits.get() && hs[0]->tag_bits_items != n_items) {
-      msg = "the tag items were set for another item count";
-      return MALS_INVALID_ARG;
-    }
-    std::vector<char> rec((size_t)n_members, 0);
-    std::vector<int64_t> n_override((size_t)n_members, 0);
-    int rc = MALS_OK;
-    for (int m = 0; m < n_members && rc == MALS_OK; ++m) {
-      rc = group_on_device(hs[m], msg);
-      bool recounted = false;
-      if (rc == MALS_OK) rc = popular_count_enqueue(hs[m], n_items, &recounted, &n_override[(size_t)m], msg);
-      rec[(size_t)m] = recounted ? 1 : 0;
-    }
-    if (rc != MALS_OK) group_drain(hs, n_members);
-    for (int m = 0; m < n_members; ++m) {
-      int64_t pairs = 0;
-      if (rec[(size_t)m]) {
-        std::string mine;
-        int r2 = group_on_device(hs[m], mine);
-        if (r2 == MALS_OK) r2 = popular_count_finish(hs[m], &pairs, mine);
-        if (r2 != MALS_OK && rc == MALS_OK) {
-          rc = r2;
-          msg = mine;
-        }
-      }
-      if (rc == MALS_OK) popular_note(hs[m], rec[(size_t)m] != 0, n_override[(size_t)m], pairs);
-    }
-    if (rc != MALS_OK) return rc;
-    // the sum, on member 0's device and stream (every member's array is complete: the waits above)
-    mals_handle h0 = hs[0];
-    if (int r0 = group_on_device(h0, msg)) return r0;
-    PopularState& p0 = *popular_state(h0);
-    const size_t bytes = sizeof(uint32_t) * (size_t)n_items;
-    FCHK(msg, p0.d_sum.reserve((size_t)n_items, h0->stream));
-    FCHK(msg, hipMemcpyAsync(p0.d_sum.get(), p0.count.get(), bytes, hipMemcpyDeviceToDevice, h0->stream));
-    DeviceBuffer<uint32_t> part;
-    if (n_members > 1) FCHK(msg, part.alloc((size_t)n_items));
-    for (int m = 1; m < n_members; ++m) {
-      FCHK(msg, hipMemcpyPeerAsync(part.get(), h0->cfg.device, popular_state(hs[m])->count.get(), hs[m]->cfg.device, bytes, h0->stream));
-      hipLaunchKernelGGL(popular_add_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, h0->stream, p0.d_sum.get(), part.get(), n_items);
-      FCHK(msg, hipGetLastError());
-    }
-    rc = popular_select_run(h0, p0.d_sum.get(), n_items, nullptr, how_many, item_idx_out, score_out, n_out, msg);
-    if (rc != MALS_OK) (void)hipStreamSynchronize(h0->stream);   // `part` goes: nothing may still read it
-    return rc;
-  };
-  return group_finish(foldin_exclusive_all(hs, n_members, 0, fn), msg, err);
+  return group_call(hs, n_members, err, [&](std::string& msg) -> int {
+    return popular_members(hs, n_members, true, nullptr, how_many, item_idx_out, score_out, n_out, msg);
+  });
 }
 
 // the fold-in reads on ONE member (any: the replicas and the solvers are complete everywhere)
@@ -1301,8 +1025,7 @@ int rescorer_upload(mals_handle h, RescorerState& st) {
 // a new definition = the current one changed by `edit`, swapped in as an exclusive ticket of the front
 int rescorer_replace(mals_rescorer r, const char* call, const std::function<std::string(RescorerState&)>& edit) {
   mals_handle h = r->h;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, call, [&](std::string& msg) -> int {
     auto st = std::make_shared<RescorerState>();
     st->filt_idx = r->st->filt_idx;
     st->scale = r->st->scale;
@@ -1322,8 +1045,7 @@ int rescorer_replace(mals_rescorer r, const char* call, const std::function<std:
     }
     r->st = std::move(st);
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, call);
+  });
 }
 template <typename T>
 bool rescorer_host_copy(mals_handle h, const T* p, int64_t n, int mem_kind, std::vector<T>& out) {
@@ -1502,22 +1224,18 @@ int mals_lsh_build(mals_handle h, int32_t num_hashes, int32_t max_bits_differing
   if (num_hashes < 1 || num_hashes > 64) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_build: num_hashes in 1..64 (LocationSensitiveHash.java:75)");
   if (max_bits_differing < -1 || max_bits_differing > num_hashes) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_build: max_bits_differing in -1..num_hashes");
   if (!random_vectors) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_build: random_vectors is NULL");
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int { return lsh_build_run(h, num_hashes, max_bits_differing, random_vectors, mean, msg); };
-  return foldin_exclusive(h, fn, msg, "mals_lsh_build");
+  return foldin_exclusive(h, "mals_lsh_build", [&](std::string& msg) -> int { return lsh_build_run(h, num_hashes, max_bits_differing, random_vectors, mean, msg); });
 }
 
 int mals_lsh_clear(mals_handle h) {
   if (!h) return MALS_INVALID_ARG;
   if (int rc = foldin_refuse(h, "mals_lsh_clear")) return rc;
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, "mals_lsh_clear", [&](std::string& msg) -> int {
     FCHK(msg, hipStreamSynchronize(h->stream));
     std::lock_guard<std::mutex> lk(topn_front(h)->mu);
     h->lsh.clear();
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_lsh_clear");
+  });
 }
 
 // a read of a few words under the front's mutex: no ticket, the serving front is not drained for a statistics query (and
@@ -1539,8 +1257,7 @@ int mals_lsh_get(mals_handle h, double* mean_out, int64_t row_begin, int64_t n_r
   if (!h) return MALS_INVALID_ARG;
   if (int rc = foldin_refuse(h, "mals_lsh_get")) return rc;
   if (n_rows < 0 || row_begin < 0 || (n_rows > 0 && !signatures_out)) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_get: bad arguments");
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, "mals_lsh_get", [&](std::string& msg) -> int {
     const LshState& l = h->lsh;
     if (l.H == 0) {
       msg = "no candidate filter is built (mals_lsh_build)";
@@ -1555,16 +1272,14 @@ int mals_lsh_get(mals_handle h, double* mean_out, int64_t row_begin, int64_t n_r
       FCHK(msg, hipMemcpyAsync(signatures_out, l.d_sig.get() + row_begin, sizeof(uint64_t) * (size_t)n_rows, hipMemcpyDeviceToHost, h->stream));
     FCHK(msg, hipStreamSynchronize(h->stream));
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_lsh_get");
+  });
 }
 
 int mals_lsh_signatures(mals_handle h, const float* vectors, int32_t n, uint64_t* out) {
   if (!h) return MALS_INVALID_ARG;
   if (int rc = foldin_refuse(h, "mals_lsh_signatures")) return rc;
   if (n < 0 || (n > 0 && (!vectors || !out))) return topn_fail(h, MALS_INVALID_ARG, "mals_lsh_signatures: bad arguments");
-  std::string msg;
-  const std::function<int()> fn = [&]() -> int {
+  return foldin_exclusive(h, "mals_lsh_signatures", [&](std::string& msg) -> int {
     const LshState& l = h->lsh;
     if (l.H == 0) {
       msg = "no candidate filter is built (mals_lsh_build)";
@@ -1583,6 +1298,5 @@ int mals_lsh_signatures(mals_handle h, const float* vectors, int32_t n, uint64_t
     FCHK(msg, hipMemcpyAsync(out, d_s.get(), sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     FCHK(msg, hipStreamSynchronize(h->stream));
     return MALS_OK;
-  };
-  return foldin_exclusive(h, fn, msg, "mals_lsh_signatures");
+  });
 }

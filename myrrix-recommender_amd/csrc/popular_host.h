@@ -1,7 +1,8 @@
 // popular_host.h -- host side of mals_most_popular_items / mals_set_tag_users (include/myrrix_als.h; kernels in
 // popular_kernels.h).  Included by mals_serving.hip inside its anonymous namespace, after foldin_host.h: the read runs as an
 // exclusive ticket of the serving front (foldin_exclusive), so the state below is only ever touched by the front's leader --
-// except the tag users, which follow the rule of mals_set_tag_items (not while calls are in flight).
+// except the tag users, which follow the rule of mals_set_tag_items (not while calls are in flight).  One driver
+// (popular_members) serves a handle and the members of a group, over the member loop of foldin_host.h.
 //
 // THE COUNT CACHE.  The per-item count array stays on the device.  The handle carries a counter (pop_epoch) that every
 // call which may change a counted user's set bumps (popular_touch: a new generation's known items or user-side matrix, a
@@ -12,7 +13,8 @@
 struct PopularState {
   std::vector<int64_t> tag_users;          // itemTagIDs as local user rows: ascending, unique
   DeviceBuffer<uint32_t> count;            // [n_items]: this handle's users
-  uint64_t counted_epoch = 0;              // the pop_epoch `count` was counted at (0: never)
+  uint64_t counted_epoch = 0;              // the pop_epoch `count` was counted at (0: never), set once the recount is waited for
+  uint64_t enqueued_epoch = 0;             // ... and the one of a recount on its way (popular_count_enqueue -> _finish)
   int64_t counted_items = -1;
   uint64_t ascending_epoch = 0;            // the pop_base_epoch base_ascending was decided at (0: never)
   bool base_ascending = false;             // every row of the base CSR is strictly ascending
@@ -52,17 +54,21 @@ void popular_new_generation(mals_handle h, bool new_rows) {
   if (new_rows) std::vector<int64_t>().swap(ps->tag_users);
 }
 
-// itemTagIDs (ServerRecommender.java:626, :638): global user rows (host); those outside this handle's users are ignored
-void popular_set_tag_users(mals_handle h, int64_t n, const int64_t* user_idx) {
-  PopularState& ps = *popular_state(h);
-  const int64_t lo = h->side[MALS_SIDE_X].row_offset, hi = foldin_user_rows_end(h);
-  std::vector<int64_t> v;
-  for (int64_t j = 0; j < n; ++j)
-    if (user_idx[j] >= lo && user_idx[j] < hi) v.push_back(user_idx[j] - lo);
-  std::sort(v.begin(), v.end());
-  v.erase(std::unique(v.begin(), v.end()), v.end());
-  ps.tag_users.swap(v);
-  popular_touch(h, false);
+// itemTagIDs (ServerRecommender.java:626, :638): global user rows (host); every member keeps the rows it owns (those outside
+// a handle's users are ignored)
+int popular_set_tag_users(mals_handle* hs, int n_members, int64_t n, const int64_t* user_idx) {
+  for (int m = 0; m < n_members; ++m) {
+    mals_handle h = hs[m];
+    const int64_t lo = h->side[MALS_SIDE_X].row_offset, hi = foldin_user_rows_end(h);
+    std::vector<int64_t> v;
+    for (int64_t j = 0; j < n; ++j)
+      if (user_idx[j] >= lo && user_idx[j] < hi) v.push_back(user_idx[j] - lo);
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    popular_state(h)->tag_users.swap(v);
+    popular_touch(h, false);
+  }
+  return MALS_OK;
 }
 
 unsigned popular_grid(mals_handle h, int64_t n_units, int per_block) {
@@ -90,14 +96,7 @@ int popular_count_enqueue(mals_handle h, int64_t n_items, bool* recounted, int64
   const int32_t* bidx = h->known_ptr ? h->known_idx : x.col;
   // users whose current set is not their base row: an added chain or a replaced set (grown users have nothing else)
   const FoldinState* fs = h->serving->fo;
-  std::vector<int64_t> orows;
-  if (fs) {
-    for (size_t r = 0; r < fs->head.size(); ++r)
-      if (fs->head[r] != UINT32_MAX) orows.push_back((int64_t)r);
-    for (const auto& kv : fs->replaced) orows.push_back(kv.first);
-    std::sort(orows.begin(), orows.end());
-    orows.erase(std::unique(orows.begin(), orows.end()), orows.end());
-  }
+  const std::vector<int64_t> orows = fs ? fs->known.override_rows() : std::vector<int64_t>();
   // the skip bits of the base pass: tag users and the users of the override CSR; the override CSR leaves the tag users out
   const size_t words = (size_t)((n_base + 31) / 32);
   std::vector<uint32_t>& skip = ps.h_skip;
@@ -172,7 +171,7 @@ int popular_count_enqueue(mals_handle h, int64_t n_items, bool* recounted, int64
   }
   *recounted = true;
   ps.counted_items = n_items;
-  ps.counted_epoch = epoch;   // (withdrawn by popular_count_finish if the recount fails)
+  ps.enqueued_epoch = epoch;   // (counted_epoch stays 0 until popular_count_finish: a recount nobody waited for does not count)
   return MALS_OK;
 }
 
@@ -182,10 +181,8 @@ int popular_count_finish(mals_handle h, int64_t* pairs, std::string& msg) {
   unsigned long long p = 0;
   hipError_t e = hipMemcpyAsync(&p, ps.d_pairs.get(), sizeof(p), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) {
-    ps.counted_epoch = 0;
-    FCHK(msg, e);
-  }
+  FCHK(msg, e);
+  ps.counted_epoch = ps.enqueued_epoch;
   *pairs = (int64_t)p;
   return MALS_OK;
 }
@@ -233,19 +230,26 @@ int popular_select_run(mals_handle h, const uint32_t* count, int64_t n_items, co
   return MALS_OK;
 }
 
-// what both the single call and the group twin check inside their ticket
-int popular_ready(mals_handle h, int64_t* n_items, std::string& msg) {
-  *n_items = h->side[MALS_SIDE_Y].n_total;
-  if (!h->side[MALS_SIDE_Y].F || *n_items <= 0) {
-    msg = "the item factor rows are not declared (they say how many items there are)";
+// what a call checks inside its ticket, over the members (a handle: one).  The texts are each caller's
+int popular_ready(mals_handle* hs, int n_members, bool via_group, int64_t* n_items, std::string& msg) {
+  bool any_known = false;
+  for (int m = 0; m < n_members; ++m) {
+    const SideState& y = hs[m]->side[MALS_SIDE_Y];
+    if (!y.F || y.n_total <= 0 || (m > 0 && y.n_total != *n_items)) {
+      msg = via_group ? "the item factor rows are not declared alike on every member"
+                      : "the item factor rows are not declared (they say how many items there are)";
+      return MALS_INVALID_ARG;
+    }
+    *n_items = y.n_total;
+    any_known = any_known || popular_has_known(hs[m]);
+  }
+  if (!any_known) {
+    msg = via_group ? "no known items: neither a user-side matrix, nor installed known items, nor writes"
+                    : "no known items: neither a user-side matrix, nor mals_set_known_items, nor writes (the reference throws UnsupportedOperationException)";
     return MALS_INVALID_ARG;
   }
-  if (!popular_has_known(h)) {
-    msg = "no known items: neither a user-side matrix, nor mals_set_known_items, nor writes (the reference throws UnsupportedOperationException)";
-    return MALS_INVALID_ARG;
-  }
-  if (h->tag_bits.get() && h->tag_bits_items != *n_items) {
-    msg = "the tag items were set for another item count: call mals_set_tag_items again";
+  if (hs[0]->tag_bits.get() && hs[0]->tag_bits_items != *n_items) {
+    msg = via_group ? "the tag items were set for another item count" : "the tag items were set for another item count: call mals_set_tag_items again";
     return MALS_INVALID_ARG;
   }
   return MALS_OK;
@@ -261,14 +265,45 @@ void popular_note(mals_handle h, bool recounted, int64_t n_override, int64_t pai
   }
 }
 
-int popular_run(mals_handle h, const mals_rescorer_s* r, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out,
-                std::string& msg) {
-  int64_t n_items = 0, n_override = 0, pairs = 0;
-  if (int rc = popular_ready(h, &n_items, msg)) return rc;
-  bool recounted = false;
-  if (int rc = popular_count_enqueue(h, n_items, &recounted, &n_override, msg)) return rc;
-  if (recounted)
-    if (int rc = popular_count_finish(h, &pairs, msg)) return rc;
-  popular_note(h, recounted, n_override, pairs);
-  return popular_select_run(h, popular_state(h)->count.get(), n_items, r, how_many, item_idx_out, score_out, n_out, msg);
+// Every member counts the users it owns, side by side; member 0 saturates, strikes the tag items and selects (r: a handle's
+// rescorer, a group has none).  One member selects from its own array; of several, the partial arrays are added on member 0
+// first (peer copies into d_sum) -- after the sum, as one handle would.
+int popular_members(mals_handle* hs, int n_members, bool via_group, const mals_rescorer_s* r, int32_t how_many, int64_t* item_idx_out,
+                    float* score_out, int32_t* n_out, std::string& msg) {
+  int64_t n_items = 0;
+  if (int rc = popular_ready(hs, n_members, via_group, &n_items, msg)) return rc;
+  struct Recount { bool recounted = false; int64_t n_override = 0; };
+  MemberSlots<Recount> rec(n_members);
+  if (int rc = member_loop(
+          hs, n_members, rec, msg,
+          [&](int m, std::string& why) { return popular_count_enqueue(hs[m], n_items, &rec[m].recounted, &rec[m].n_override, why); },
+          [&](int m, std::string& why) -> int {
+            int64_t pairs = 0;
+            if (rec[m].recounted)
+              if (int rc = popular_count_finish(hs[m], &pairs, why)) return rc;
+            popular_note(hs[m], rec[m].recounted, rec[m].n_override, pairs);
+            return MALS_OK;
+          }))
+    return rc;
+  // The sum and the selection are member 0's alone.  They go through the member loop all the same, over that one member:
+  // it makes member 0's device current and, on a failure, waits for its stream before `part` goes (rules 1 and 3)
+  MemberSlots<DeviceBuffer<uint32_t>> part(1);
+  return member_each(hs, 1, part, msg, [&](int, std::string& why) -> int {
+    mals_handle h0 = hs[0];
+    PopularState& p0 = *popular_state(h0);
+    const uint32_t* count = p0.count.get();
+    if (n_members > 1) {
+      const size_t bytes = sizeof(uint32_t) * (size_t)n_items;
+      FCHK(why, p0.d_sum.reserve((size_t)n_items, h0->stream));
+      FCHK(why, hipMemcpyAsync(p0.d_sum.get(), p0.count.get(), bytes, hipMemcpyDeviceToDevice, h0->stream));
+      FCHK(why, part[0].alloc((size_t)n_items));
+      for (int m = 1; m < n_members; ++m) {
+        FCHK(why, hipMemcpyPeerAsync(part[0].get(), h0->cfg.device, popular_state(hs[m])->count.get(), hs[m]->cfg.device, bytes, h0->stream));
+        hipLaunchKernelGGL(popular_add_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, h0->stream, p0.d_sum.get(), part[0].get(), n_items);
+        FCHK(why, hipGetLastError());
+      }
+      count = p0.d_sum.get();
+    }
+    return popular_select_run(h0, count, n_items, r, how_many, item_idx_out, score_out, n_out, why);
+  });
 }
