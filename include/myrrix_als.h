@@ -999,7 +999,7 @@ int mals_factor_digest_host(const float* rows, int32_t features, int64_t row_beg
  * was written since the last load.  On the device the model is dense rows, so the merge is an id join, a compaction and a
  * row gather (csrc/generation_kernels.h), run as ONE exclusive ticket of the serving front on the handle's stream: a
  * concurrent mals_recommend* sees the old generation or the new one, never a mixture.  For handles outside a group
- * (a member is MALS_INVALID_ARG, like the writes; the mals_group_* twin is not built yet).
+ * (a member is MALS_INVALID_ARG, like the writes; a group loads through mals_group_load_generation below).
  *
  * RECENT ROWS (recentlyActiveUsers / recentlyActiveItems, DelegateGenerationManager.java:179-186): the handle records,
  * per side, the user row and the item row of every datum given to mals_set_preferences and mals_remove_preferences whose
@@ -1087,6 +1087,48 @@ int mals_get_recent(mals_handle h, int side, int64_t* rows_out, int64_t* n_out);
 uint64_t mals_generation_hash_host(int64_t id);
 int mals_generation_join_host(const int64_t* cur_ids, int64_t n_cur, const int64_t* new_ids, int64_t n_new, const int64_t* recent_rows,
                               int64_t n_recent, int32_t flags, int64_t* map_out, int64_t* counts_out);
+
+/* ---- loading a new generation into a group ---------------------------------------------------------------------------
+ * mals_group_load_generation: mals_load_generation for a group all of whose ranks live in this process (mals_group_create,
+ * or mals_group_create_rank with world 1; a rank of a multi-process group is MALS_INVALID_ARG, like the write twins).  The
+ * structs are mals_load_generation's, unchanged.  What differs:
+ *   - the new model is given WHOLE -- ids, rows, the known-item CSR over all new users, the two tag-id sets -- not sliced;
+ *     MALS_MEM_DEVICE arrays live on the device of the group's first local member (the others read peer copies).
+ *   - n_cur = the rows of the replicas, which every member holds whole.  Every member runs the join, the compaction and the
+ *     row gather on its own replicas and its own stream (the replicated state machine of the write path); afterwards every
+ *     member's X and Y, the merged ids and the maps are bit for bit what ONE handle holding the whole live model would hold
+ *     after mals_load_generation with the same arguments and the same history of writes and mark_recent calls, and so are
+ *     the result's counts and every answer of the group's readers.  n_known_dropped and n_tag_ids_without_row are counted
+ *     once per group; the device times are the slowest member's.
+ *   - RECENT ROWS: mals_group_set_preferences and mals_group_remove_preferences record the user row and the item row of
+ *     every datum of a batch that passed its argument checks, once per group and in global rows; mals_group_mark_recent /
+ *     mals_group_get_recent are the twins of mals_mark_recent / mals_get_recent.  A successful load clears both sides.
+ *   - OWNERSHIP: known items stay with a user's owner, and the owners are planned anew.  bounds[X] over the n_merged users
+ *     = mals_plan_shards (default row cost, the group's features) over the row pointer "new_known_ptr, then the running
+ *     sum of the kept users' set sizes" (all zeros without known items: the plan cuts by rows alone); bounds[Y] = the same
+ *     over n_merged items without entries.  mals_group_bounds returns them; users grown later go to the last rank as
+ *     before.  A kept user whose set is its base row moves as a row of its owner's CSR, re-indexed on the device in
+ *     base-row order (csrc/generation_group_kernels.h); one with additions, a replaced set or a grown row is installed on
+ *     its new owner as a whole set.  itemTagIDs are split by the new owners as mals_group_set_tag_users does.
+ *   - the members' matrices are released: a loaded group serves and is not iterated until mals_group_set_matrix starts a
+ *     new generation.  With MALS_GENERATION_RECOMPUTE_SOLVERS the solvers are computed once and installed on every member.
+ *   - ALL OR NOTHING ACROSS MEMBERS: the call holds every member's serving front and the group's write lock; every member
+ *     builds aside, and only when all are ready do they swap and the bounds change.  Any failure leaves every member, the
+ *     bounds and the recent rows as they were.  A read racing the load is answered from the old generation or the new one.
+ * mals_group_generation_get_ids / _get_map: of the last successful load, as mals_generation_get_ids / _get_map.
+ * mals_group_generation_plan_host: the ownership plan alone, no device.  kept_rows = the kept users' live rows (n_kept,
+ * strictly ascending: their old owners follow from old_bounds, world + 1 bounds or NULL = all on the last rank);
+ * kept_sizes = their set sizes; new_known_ptr = n_new + 1 offsets (host) or NULL.  bounds_out: world + 1.  moves_out
+ * (nullable): world x world x 2, [old][new] = the run [begin, end) of the OLD member's own kept list that the new member
+ * gets -- contiguous, and in new-member order, because kept users are a tail of the merged order in old-owner order. */
+int mals_group_load_generation(mals_group g, const mals_generation_load* load, mals_generation_result* result_out);
+int mals_group_generation_get_ids(mals_group g, int side, int64_t* ids_out);
+int mals_group_generation_get_map(mals_group g, int side, int64_t* map_out);
+int mals_group_mark_recent(mals_group g, int side, int64_t n, const int64_t* rows);
+int mals_group_get_recent(mals_group g, int side, int64_t* rows_out, int64_t* n_out);
+int mals_group_generation_plan_host(int32_t world, int32_t features, int64_t n_new, const int64_t* new_known_ptr, int64_t n_kept,
+                                    const int64_t* kept_sizes, const int64_t* kept_rows, const int64_t* old_bounds, int64_t* bounds_out,
+                                    int64_t* moves_out);
 
 /* iterateXFromY / iterateYFromX (ALS:340-389) and call() (ALS:176-262) on the group; arguments as for
  * mals_half_iteration / mals_factorize. */

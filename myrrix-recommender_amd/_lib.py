@@ -287,6 +287,12 @@ SYMBOLS = {
     "mals_generation_get_map": (ctypes.c_int, [_H, ctypes.c_int, _P]),
     "mals_mark_recent": (ctypes.c_int, [_H, ctypes.c_int, _I64, _P]),
     "mals_get_recent": (ctypes.c_int, [_H, ctypes.c_int, _P, ctypes.POINTER(_I64)]),
+    "mals_group_load_generation": (ctypes.c_int, [_H, ctypes.POINTER(GenerationLoad), ctypes.POINTER(GenerationResult)]),
+    "mals_group_generation_get_ids": (ctypes.c_int, [_H, ctypes.c_int, _P]),
+    "mals_group_generation_get_map": (ctypes.c_int, [_H, ctypes.c_int, _P]),
+    "mals_group_mark_recent": (ctypes.c_int, [_H, ctypes.c_int, _I64, _P]),
+    "mals_group_get_recent": (ctypes.c_int, [_H, ctypes.c_int, _P, ctypes.POINTER(_I64)]),
+    "mals_group_generation_plan_host": (ctypes.c_int, [_I32, _I32, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "mals_generation_hash_host": (ctypes.c_uint64, [_I64]),
     "mals_generation_join_host": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _P]),
     "mals_group_half_iteration": (ctypes.c_int, [_H, ctypes.c_int]),

@@ -203,6 +203,75 @@ class Rescorer:
         self.close()
 
 
+def _load_generation(features, load, get_ids, get_map, cur_user_ids, cur_item_ids, new_user_ids, new_item_ids, new_X, new_Y, new_known,
+                     item_tag_ids, user_tag_ids, keep_not_updated, recompute_solvers):
+    """The argument marshalling and the return shape of ALSCore.load_generation and GroupALS.load_generation: load(L, R) makes
+    the C call (and raises), get_ids / get_map(side, pointer) fetch the merged ids and the maps."""
+
+    arrays = [new_user_ids, new_item_ids, new_X, new_Y] + (list(new_known) if new_known is not None else []) + \
+             [a for a in (item_tag_ids, user_tag_ids) if a is not None]
+    device = any(_is_torch(a) for a in arrays)
+    keep = []
+
+    def ptr(a, dtype):
+        if a is None:
+            return None, 0
+        if device:
+            assert _is_torch(a) and a.is_cuda and str(a.dtype) == "torch." + np.dtype(dtype).name, "the new model: all device or all host"
+            a = a.contiguous()
+            keep.append(a)
+            return (ctypes.c_void_p(a.data_ptr()) if a.numel() else None), int(a.shape[0])
+        a = _host(a, dtype)
+        keep.append(a)
+        return (a.ctypes.data_as(ctypes.c_void_p) if a.size else None), int(a.shape[0])
+
+    cur_device = _is_torch(cur_user_ids)
+    if cur_device:     # the live ids on the device too (both)
+        assert _is_torch(cur_item_ids) and cur_user_ids.is_cuda and cur_item_ids.is_cuda and str(cur_user_ids.dtype) == str(cur_item_ids.dtype) == "torch.int64"
+        cur = [cur_user_ids.contiguous(), cur_item_ids.contiguous()]
+    else:
+        cur = [_host(cur_user_ids, np.int64), _host(cur_item_ids, np.int64)]
+    L = _lib.GenerationLoad()
+    L.struct_size = ctypes.sizeof(_lib.GenerationLoad)
+    L.flags = (_lib.GENERATION_KEEP_NOT_UPDATED if keep_not_updated else 0) | (_lib.GENERATION_RECOMPUTE_SOLVERS if recompute_solvers else 0)
+    L.features = features
+    L.cur_mem_kind = MEM_DEVICE if cur_device else MEM_HOST
+    L.new_mem_kind = MEM_DEVICE if device else MEM_HOST
+    for s, (ids, rows) in enumerate(((new_user_ids, new_X), (new_item_ids, new_Y))):
+        if not len(cur[s]):
+            L.cur_ids[s] = None
+        else:
+            L.cur_ids[s] = ctypes.c_void_p(cur[s].data_ptr()) if cur_device else cur[s].ctypes.data_as(ctypes.c_void_p)
+        L.n_cur[s] = len(cur[s])
+        L.new_ids[s], L.n_new[s] = ptr(ids, np.int64)
+        p, n = ptr(rows, np.float32)
+        if n != L.n_new[s] or (n and tuple(keep[-1].shape) != (n, features)):
+            raise ValueError("load_generation: the new rows must be n_new x features")
+        L.new_rows[s] = p
+    if new_known is not None:
+        L.new_known_ptr, n = ptr(new_known[0], np.int64)
+        if n != L.n_new[0] + 1:
+            raise ValueError("load_generation: new_known[0] holds n_new users + 1 offsets")
+        L.new_known_idx, _ = ptr(new_known[1], np.int32)
+    L.item_tag_ids, L.n_item_tag_ids = ptr(item_tag_ids, np.int64)
+    L.user_tag_ids, L.n_user_tag_ids = ptr(user_tag_ids, np.int64)
+    R = _lib.GenerationResult()
+    R.struct_size = ctypes.sizeof(_lib.GenerationResult)
+    load(ctypes.byref(L), ctypes.byref(R))
+    res = {name: (list(getattr(R, name)) if hasattr(getattr(R, name), "__len__") else getattr(R, name))
+           for name, _ in _lib.GenerationResult._fields_ if name != "struct_size"}
+    ids, maps = [], []
+    for side in (SIDE_X, SIDE_Y):
+        i = np.empty(int(R.n_merged[side]), dtype=np.int64)
+        m = np.empty(len(cur[side]), dtype=np.int64)
+        get_ids(side, i.ctypes.data_as(ctypes.c_void_p))
+        if len(m):
+            get_map(side, m.ctypes.data_as(ctypes.c_void_p))
+        ids.append(i)
+        maps.append(m)
+    return res, tuple(ids), tuple(maps)
+
+
 class ALSCore:
     def __init__(self, features, alpha=1.0, lam=0.1, flags=0, device=0, segment_nnz=0,
                  singularity_threshold=1e-5, chunk_rows=0, gramian_mode=0, solve_mode=0):
@@ -782,71 +851,15 @@ class ALSCore:
         (row_ptr, item_idx) over the new users or None, the two updated tag-id sets -- is all numpy or all torch CUDA
         tensors (int64 ids and offsets, float32 rows, int32 item indices).  Returns (result dict, (merged user ids, merged
         item ids), (user map, item map)): map[r] = the merged row of live row r, -1 = pruned."""
-        arrays = [new_user_ids, new_item_ids, new_X, new_Y] + (list(new_known) if new_known is not None else []) + \
-                 [a for a in (item_tag_ids, user_tag_ids) if a is not None]
-        device = any(_is_torch(a) for a in arrays)
-        keep = []
-
-        def ptr(a, dtype):
-            if a is None:
-                return None, 0
-            if device:
-                assert _is_torch(a) and a.is_cuda and str(a.dtype) == "torch." + np.dtype(dtype).name, "the new model: all device or all host"
-                a = a.contiguous()
-                keep.append(a)
-                return (ctypes.c_void_p(a.data_ptr()) if a.numel() else None), int(a.shape[0])
-            a = _host(a, dtype)
-            keep.append(a)
-            return (a.ctypes.data_as(ctypes.c_void_p) if a.size else None), int(a.shape[0])
-
-        cur_device = _is_torch(cur_user_ids)
-        if cur_device:     # the live ids on the device too (both)
-            assert _is_torch(cur_item_ids) and cur_user_ids.is_cuda and cur_item_ids.is_cuda and str(cur_user_ids.dtype) == str(cur_item_ids.dtype) == "torch.int64"
-            cur = [cur_user_ids.contiguous(), cur_item_ids.contiguous()]
-        else:
-            cur = [_host(cur_user_ids, np.int64), _host(cur_item_ids, np.int64)]
-        L = _lib.GenerationLoad()
-        L.struct_size = ctypes.sizeof(_lib.GenerationLoad)
-        L.flags = (_lib.GENERATION_KEEP_NOT_UPDATED if keep_not_updated else 0) | (_lib.GENERATION_RECOMPUTE_SOLVERS if recompute_solvers else 0)
-        L.features = self.features
-        L.cur_mem_kind = MEM_DEVICE if cur_device else MEM_HOST
-        L.new_mem_kind = MEM_DEVICE if device else MEM_HOST
-        for s, (ids, rows) in enumerate(((new_user_ids, new_X), (new_item_ids, new_Y))):
-            if not len(cur[s]):
-                L.cur_ids[s] = None
-            else:
-                L.cur_ids[s] = ctypes.c_void_p(cur[s].data_ptr()) if cur_device else cur[s].ctypes.data_as(ctypes.c_void_p)
-            L.n_cur[s] = len(cur[s])
-            L.new_ids[s], L.n_new[s] = ptr(ids, np.int64)
-            p, n = ptr(rows, np.float32)
-            if n != L.n_new[s] or (n and tuple(keep[-1].shape) != (n, self.features)):
-                raise ValueError("load_generation: the new rows must be n_new x features")
-            L.new_rows[s] = p
-        if new_known is not None:
-            L.new_known_ptr, n = ptr(new_known[0], np.int64)
-            if n != L.n_new[0] + 1:
-                raise ValueError("load_generation: new_known[0] holds n_new users + 1 offsets")
-            L.new_known_idx, _ = ptr(new_known[1], np.int32)
-        L.item_tag_ids, L.n_item_tag_ids = ptr(item_tag_ids, np.int64)
-        L.user_tag_ids, L.n_user_tag_ids = ptr(user_tag_ids, np.int64)
-        R = _lib.GenerationResult()
-        R.struct_size = ctypes.sizeof(_lib.GenerationResult)
-        self._chk(self._L.mals_load_generation(self._h, ctypes.byref(L), ctypes.byref(R)))
+        out = _load_generation(self.features, lambda L, R: self._chk(self._L.mals_load_generation(self._h, L, R)),
+                               lambda side, p: self._chk(self._L.mals_generation_get_ids(self._h, side, p)),
+                               lambda side, p: self._chk(self._L.mals_generation_get_map(self._h, side, p)),
+                               cur_user_ids, cur_item_ids, new_user_ids, new_item_ids, new_X, new_Y, new_known, item_tag_ids, user_tag_ids,
+                               keep_not_updated, recompute_solvers)
         for side in (SIDE_X, SIDE_Y):     # the replicas and matrices are the library's own from here on
             self._keep.pop(("F", side), None)
             self._keep.pop(("M", side), None)
-        res = {name: (list(getattr(R, name)) if hasattr(getattr(R, name), "__len__") else getattr(R, name))
-               for name, _ in _lib.GenerationResult._fields_ if name != "struct_size"}
-        ids, maps = [], []
-        for side in (SIDE_X, SIDE_Y):
-            i = np.empty(int(R.n_merged[side]), dtype=np.int64)
-            m = np.empty(len(cur[side]), dtype=np.int64)
-            self._chk(self._L.mals_generation_get_ids(self._h, side, i.ctypes.data_as(ctypes.c_void_p)))
-            if len(m):
-                self._chk(self._L.mals_generation_get_map(self._h, side, m.ctypes.data_as(ctypes.c_void_p)))
-            ids.append(i)
-            maps.append(m)
-        return res, tuple(ids), tuple(maps)
+        return out
 
     def factor_digest(self, side, row_begin=0, n_rows=None):
         """mals_factor_digest: the 64-bit digest of rows [row_begin, row_begin + n_rows) of side's replica, computed on the

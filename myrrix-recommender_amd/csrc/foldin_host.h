@@ -9,8 +9,8 @@
 // batch to its own replicas with the same deterministic kernels; only a user's owner keeps its known items), so each has one
 // driver over (hs, n_members) -- foldin_set_members, foldin_remove_members, foldin_grow_members, popular_members
 // (popular_host.h) -- that runs INSIDE the ticket its caller holds: foldin_exclusive for a handle, which passes (&h, 1),
-// foldin_exclusive_all for a group.  What the two say differently is `via_group` (which users a batch may name, who marks the
-// rows recent, the hints of the texts) and the owners.
+// foldin_exclusive_all for a group.  What the two say differently is `via_group` (which users a batch may name, the hints of
+// the texts) and the owners; both mark the batch's rows recent on hs[0] (a group's record lives on its first member).
 //
 // THE MEMBER LOOP (member_loop), which they and malsi_group_factor_digest share: an enqueue step per member, then a finish step
 // per member, so that every member's device work is on its way before the first wait.  Its rules:
@@ -327,12 +327,13 @@ int foldin_check_pairs(mals_handle h, int64_t n, const int64_t* user_row, const 
   return MALS_OK;
 }
 
-// a write's batch before any work: a handle's call names its own users and marks the rows recent (doAppend,
-// DelegateGenerationManager.java:179-186); a group's names any user (each member is asked all the same) and does not mark
+// a write's batch before any work: a handle's call names its own users, a group's any user (each member is asked all the
+// same).  Both mark the rows recent (doAppend, DelegateGenerationManager.java:179-186): a group keeps that record once, in
+// global rows, on its first member (mals_group_load_generation reads it there)
 int foldin_write_ready(mals_handle* hs, int n_members, bool via_group, int64_t n, const int64_t* user_row, const int64_t* item_row, std::string& msg) {
   for (int m = 0; m < n_members; ++m)
     if (int rc = foldin_check_pairs(hs[m], n, user_row, item_row, false, !via_group, msg)) return rc;
-  if (!via_group) generation_mark_pairs(hs[0], n, user_row, item_row);
+  generation_mark_pairs(hs[0], n, user_row, item_row);
   return MALS_OK;
 }
 

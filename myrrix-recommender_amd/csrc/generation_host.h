@@ -156,13 +156,22 @@ struct GenSide {
   std::unordered_map<int64_t, int64_t> kept_row_of_id;   // id -> merged row, of the kept rows
   std::vector<uint32_t> recent_img;             // host image of the recent bits (outlives the asynchronous copy made from it)
   size_t e0 = 0;                                // first of this side's six events
+  // between generation_side_begin and generation_side_end: the live ids' table, {duplicate row of new, of cur, hits, kept
+  // rows} on the device and where its copy lands, the keep flags and their tile sums, the recent bits
+  DeviceBuffer<unsigned long long> cur_table, flags;
+  unsigned long long got[4] = {~0ull, ~0ull, 0ull, 0ull};
+  DeviceBuffer<unsigned> keep, tile_sums;
+  DeviceBuffer<uint32_t> d_recent;
+  int64_t n_tiles = 0;
 };
 
 unsigned generation_grid(mals_handle h, int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->n_cu * 8, (n + 255) / 256)); }
 
-int generation_side(mals_handle h, int side, const mals_generation_load& L, GenEvents& ev, GenSide& g, std::string& msg) {
-  SideState& s = h->side[side];
-  const int k = h->cfg.features;
+// One side in three steps, so that a group enqueues every member's step before it waits for any (generation_group_host.h); a
+// handle runs them back to back (generation_side).  BEGIN: the uploads, JOIN, KEEP and the scan's sums, and the copy of the
+// four counters to g.got -- nothing waited for.  `recent`: the recent bits of the side (a group keeps them on its first member).
+int generation_side_begin(mals_handle h, int side, const mals_generation_load& L, const std::vector<uint32_t>& recent, GenEvents& ev, GenSide& g,
+                          std::string& msg) {
   const bool keep_all = (L.flags & MALS_GENERATION_KEEP_NOT_UPDATED) != 0;
   g.n_cur = L.n_cur[side];
   g.n_new = L.n_new[side];
@@ -182,19 +191,19 @@ int generation_side(mals_handle h, int side, const mals_generation_load& L, GenE
   // JOIN: the table of the new ids, the live ids' own table (it only finds their duplicates), the probe
   const uint64_t slots = gen_table_slots(g.n_new), cur_slots = gen_table_slots(g.n_cur);
   g.mask = slots - 1;
-  DeviceBuffer<unsigned long long> cur_table, flags;   // flags: duplicate row of new, of cur, hits, kept rows
-  DeviceBuffer<unsigned> keep, tile_sums;
-  DeviceBuffer<uint32_t> d_recent;
-  const int64_t n_tiles = (g.n_cur + GEN_SCAN_TILE - 1) / GEN_SCAN_TILE;
+  DeviceBuffer<unsigned long long>& cur_table = g.cur_table;
+  DeviceBuffer<unsigned long long>& flags = g.flags;
+  DeviceBuffer<unsigned>& keep = g.keep;
+  DeviceBuffer<unsigned>& tile_sums = g.tile_sums;
+  DeviceBuffer<uint32_t>& d_recent = g.d_recent;
+  const int64_t n_tiles = g.n_tiles = (g.n_cur + GEN_SCAN_TILE - 1) / GEN_SCAN_TILE;
   FCHK(msg, g.table.alloc((size_t)(2 * slots)));
   FCHK(msg, flags.alloc(4));
   FCHK(msg, g.map.alloc((size_t)std::max<int64_t>(g.n_cur, 1)));
   FCHK(msg, keep.alloc((size_t)std::max<int64_t>(g.n_cur, 1)));
   FCHK(msg, tile_sums.alloc((size_t)std::max<int64_t>(n_tiles, 1)));
   static const unsigned long long init[4] = {~0ull, ~0ull, 0ull, 0ull};
-  unsigned long long got[4] = {~0ull, ~0ull, 0ull, 0ull};
   FCHK(msg, hipMemcpyAsync(flags.get(), init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-  const std::vector<uint32_t>& recent = generation_state(h)->recent[side];
   std::vector<uint32_t>& recent_img = g.recent_img;
   const size_t rwords = (size_t)((g.n_cur + 31) / 32);
   if (!keep_all && g.n_cur > 0 && !recent.empty()) {
@@ -227,9 +236,20 @@ int generation_side(mals_handle h, int side, const mals_generation_load& L, GenE
   }
   FCHK(msg, ev.record(h->stream));   // e0 + 2: the scan's sums are enqueued
   // the kept rows size everything behind the scan: one wait per side (the wait and the allocations are in no phase's time)
-  FCHK(msg, hipMemcpyAsync(got, flags.get(), sizeof(got), hipMemcpyDeviceToHost, h->stream));
-  FCHK(msg, hipStreamSynchronize(h->stream));
-  cur_table.reset();
+  FCHK(msg, hipMemcpyAsync(g.got, flags.get(), sizeof(g.got), hipMemcpyDeviceToHost, h->stream));
+  return MALS_OK;
+}
+
+// MID, once the stream has been waited for: the duplicates' verdict, then MAP and GATHER and the copy of the kept rows and
+// their ids to the host -- nothing waited for
+int generation_side_mid(mals_handle h, int side, const mals_generation_load& L, GenEvents& ev, GenSide& g, std::string& msg) {
+  SideState& s = h->side[side];
+  const int k = h->cfg.features;
+  const unsigned long long* got = g.got;
+  const int64_t n_tiles = g.n_tiles;
+  DeviceBuffer<unsigned>& keep = g.keep;
+  DeviceBuffer<unsigned>& tile_sums = g.tile_sums;
+  g.cur_table.reset();
   if (got[0] != ~0ull || got[1] != ~0ull) {
     const bool in_new = got[0] != ~0ull;
     msg = std::string("side ") + (side == MALS_SIDE_X ? "X" : "Y") + ": " + (in_new ? "new_ids" : "cur_ids") + " holds an id twice (row " +
@@ -280,8 +300,24 @@ int generation_side(mals_handle h, int side, const mals_generation_load& L, GenE
     FCHK(msg, hipMemcpyAsync(g.h_kept_rows.data(), g.kept_rows.get(), sizeof(int64_t) * (size_t)g.n_kept, hipMemcpyDeviceToHost, h->stream));
     FCHK(msg, hipMemcpyAsync(g.h_kept_ids.data(), g.ids.get() + g.n_new, sizeof(int64_t) * (size_t)g.n_kept, hipMemcpyDeviceToHost, h->stream));
   }
-  FCHK(msg, hipStreamSynchronize(h->stream));
+  return MALS_OK;
+}
+
+// END, once the stream has been waited for again: the join's temporaries go, the kept ids are indexed
+void generation_side_end(GenSide& g) {
+  g.flags.reset();
+  g.keep.reset();
+  g.tile_sums.reset();
+  g.d_recent.reset();
   for (int64_t i = 0; i < g.n_kept; ++i) g.kept_row_of_id[g.h_kept_ids[(size_t)i]] = g.n_new + i;
+}
+
+int generation_side(mals_handle h, int side, const mals_generation_load& L, GenEvents& ev, GenSide& g, std::string& msg) {
+  if (int rc = generation_side_begin(h, side, L, generation_state(h)->recent[side], ev, g, msg)) return rc;
+  FCHK(msg, hipStreamSynchronize(h->stream));
+  if (int rc = generation_side_mid(h, side, L, ev, g, msg)) return rc;
+  FCHK(msg, hipStreamSynchronize(h->stream));
+  generation_side_end(g);
   return MALS_OK;
 }
 
@@ -335,6 +371,29 @@ int generation_tag_rows(mals_handle h, const GenSide& g, const int64_t* ids, int
   return MALS_OK;
 }
 
+// The single handle's way to a kept user's set, and a group's for the few users with an overlay view: the whole current sets of
+// the local user rows `rows` (foldin_known_full: base row + additions, or the replaced set), every item re-indexed through the
+// item map gy.map, sorted.  Items without a merged row are dropped and counted (the reference keeps the bare id: only
+// mostPopularItems could see it).
+int generation_kept_sets(mals_handle h, const GenSide& gy, const std::vector<int64_t>& rows, std::vector<std::vector<int32_t>>& out, int64_t* dropped,
+                         std::string& msg) {
+  std::vector<std::vector<int32_t>> sets;
+  if (int rc = foldin_known_full(h, rows, sets, msg)) return rc;   // base row + overlay, sorted, distinct
+  std::vector<int64_t> flat, mapped;
+  for (const auto& v : sets) flat.insert(flat.end(), v.begin(), v.end());
+  if (int rc = generation_map_rows(h, gy, flat, mapped, msg)) return rc;
+  out.assign(sets.size(), {});
+  size_t at = 0;
+  for (size_t i = 0; i < sets.size(); ++i) {
+    for (size_t j = 0; j < sets[i].size(); ++j, ++at) {
+      if (mapped[at] >= 0) out[i].push_back((int32_t)mapped[at]);
+      else ++*dropped;
+    }
+    std::sort(out[i].begin(), out[i].end());
+  }
+  return MALS_OK;
+}
+
 // everything generation_swap installs
 struct GenPrepared {
   GenSide side[2];
@@ -347,6 +406,10 @@ struct GenPrepared {
   DeviceBuffer<uint32_t> tag_bits;
   int64_t n_tag_items = 0;
   std::vector<uint32_t> tag_recent_img;   // host image of the recent item bits (outlives the asynchronous copy made from it)
+  // a member of a group (generation_group_host.h): it owns the merged users own_lo <= u < own_hi; known_ptr / known_idx are
+  // its base CSR over exactly those users (new rows and kept rows alike), kept_sets and tag_users are keyed by u - own_lo
+  bool member = false;
+  int64_t own_lo = 0, own_hi = 0;
 };
 
 // Everything that can fail comes before the swap: the states the swap writes exist, the list of the requests the swap hands
@@ -397,10 +460,14 @@ void generation_swap(mals_handle h, GenPrepared& p) {
     h->known_idx_copy = std::move(p.known_idx);
     h->known_ptr = h->known_ptr_copy.get();
     h->known_idx = h->known_idx_copy.get();
-    h->known_rows = p.side[MALS_SIDE_X].n_new;
+    h->known_rows = p.member ? p.own_hi - p.own_lo : p.side[MALS_SIDE_X].n_new;
     x.n_local = h->known_rows;
-    // the kept users: rows past the base CSR with a whole set of their own, as grown users are after a removal
-    if (p.side[MALS_SIDE_X].n_kept > 0) {
+    if (p.member) {
+      // the slice of the merged users this member owns; its kept users with an overlay view have an empty base row and a whole set
+      x.row_offset = p.own_lo;
+      if (!p.kept_sets.empty()) foldin_state(h)->known.install_all(p.kept_sets);
+    } else if (p.side[MALS_SIDE_X].n_kept > 0) {
+      // the kept users: rows past the base CSR with a whole set of their own, as grown users are after a removal
       foldin_state(h)->known.install_all(p.kept_sets);   // (malsi_clear_known_items left it empty)
       h->grown_users_end.store(x.n_total, std::memory_order_release);
     }
@@ -414,8 +481,12 @@ void generation_swap(mals_handle h, GenPrepared& p) {
   topn_generation_swap_end(h);
 }
 
-int generation_load_body(mals_handle h, const mals_generation_load& L, mals_generation_result* R, GenPrepared& p, std::string& msg) {
-  const auto t0 = std::chrono::steady_clock::now();
+// what a handle's known items are made of before a load
+bool generation_holds_known(mals_handle h) { return h->side[MALS_SIDE_X].has_matrix || h->known_ptr || foldin_has_overlay(h); }
+
+// the checks that need no device work.  via_group: a member of a group holds a shard (row_offset != 0 is its normal state) and
+// the group decides whether the new model's known items are needed (any member may hold some)
+int generation_load_check(mals_handle h, const mals_generation_load& L, bool via_group, std::string& msg) {
   const int k = h->cfg.features;
   SideState& x = h->side[MALS_SIDE_X];
   if (L.features != k) {
@@ -429,13 +500,12 @@ int generation_load_body(mals_handle h, const mals_generation_load& L, mals_gene
             std::to_string((long long)L.n_cur[sd]) + " ids)";
       return MALS_INVALID_ARG;
     }
-    if (s.row_offset != 0) {
+    if (s.row_offset != 0 && !via_group) {
       msg = "the handle holds a shard of a larger model (row_offset != 0)";
       return MALS_INVALID_ARG;
     }
   }
-  const bool holds_known = x.has_matrix || h->known_ptr || foldin_has_overlay(h);
-  if (holds_known && !L.new_known_ptr) {
+  if (!via_group && generation_holds_known(h) && !L.new_known_ptr) {
     msg = "the handle holds known items: the new model's are needed (new_known_ptr)";
     return MALS_INVALID_ARG;
   }
@@ -443,6 +513,100 @@ int generation_load_body(mals_handle h, const mals_generation_load& L, mals_gene
     msg = "the installed known items do not match the local user rows";
     return MALS_INVALID_ARG;
   }
+  return MALS_OK;
+}
+
+// TAG SETS: updated ids, plus the live tags that are recent (updateTagIDs :108-115, removeNotUpdated :88-95).
+// itemTagIDs: user-side ids -> the tag users of mals_most_popular_items as merged user rows (ascending, unique).  live: the
+// live tag users as GLOBAL live rows; recent_x: the recent bits of side X
+int generation_tag_users(mals_handle h, const GenSide& gx, const mals_generation_load& L, const std::vector<uint32_t>& recent_x,
+                         const std::vector<int64_t>& live_all, std::vector<int64_t>& tag_users, int64_t* without_row, std::string& msg) {
+  const bool keep_all = (L.flags & MALS_GENERATION_KEEP_NOT_UPDATED) != 0;
+  std::vector<int64_t> live, live_mapped;
+  for (int64_t r : live_all)
+    if (keep_all || generation_is_recent(recent_x, r)) live.push_back(r);
+  if (int rc = generation_map_rows(h, gx, live, live_mapped, msg)) return rc;
+  if (int rc = generation_tag_rows(h, gx, L.item_tag_ids, L.n_item_tag_ids, L.new_mem_kind, tag_users, without_row, msg)) return rc;
+  for (int64_t m : live_mapped)
+    if (m >= 0) tag_users.push_back(m);
+  std::sort(tag_users.begin(), tag_users.end());
+  tag_users.erase(std::unique(tag_users.begin(), tag_users.end()), tag_users.end());
+  return MALS_OK;
+}
+
+// userTagIDs: item-side ids -> one bit per merged item (p.tag_bits, p.n_tag_items); recent_y: the recent bits of side Y
+int generation_tag_items(mals_handle h, const GenSide& gy, const mals_generation_load& L, const std::vector<uint32_t>& recent_y, GenPrepared& p,
+                         int64_t* without_row, std::string& msg) {
+  const bool keep_all = (L.flags & MALS_GENERATION_KEEP_NOT_UPDATED) != 0;
+  std::vector<int64_t> tag_items;
+  if (int rc = generation_tag_rows(h, gy, L.user_tag_ids, L.n_user_tag_ids, L.new_mem_kind, tag_items, without_row, msg)) return rc;
+  if (h->tag_bits.get() || !tag_items.empty()) {
+    const int64_t n_items = gy.n_new + gy.n_kept;
+    const size_t words = ((size_t)((n_items + 31) / 32) + 1) & ~(size_t)1;   // (the layout of mals_set_tag_items)
+    const size_t tail = sizeof(unsigned long long) / sizeof(uint32_t);
+    FCHK(msg, p.tag_bits.alloc(words + tail));
+    unsigned long long* d_n = reinterpret_cast<unsigned long long*>(p.tag_bits.get() + words);
+    FCHK(msg, hipMemsetAsync(p.tag_bits.get(), 0, sizeof(uint32_t) * (words + tail), h->stream));
+    DeviceBuffer<uint32_t> d_recent;
+    DeviceBuffer<int64_t> d_rows;
+    std::vector<uint32_t>& recent_img = p.tag_recent_img;
+    if (h->tag_bits.get() && h->tag_bits_items == gy.n_cur && gy.n_cur > 0) {
+      const size_t rwords = (size_t)((gy.n_cur + 31) / 32);
+      const std::vector<uint32_t>& recent = recent_y;
+      if (!keep_all && !recent.empty()) {
+        recent_img.assign(rwords, 0u);
+        std::copy(recent.begin(), recent.begin() + std::min(rwords, recent.size()), recent_img.begin());
+        FCHK(msg, d_recent.alloc(rwords));
+        FCHK(msg, hipMemcpyAsync(d_recent.get(), recent_img.data(), sizeof(uint32_t) * rwords, hipMemcpyHostToDevice, h->stream));
+      }
+      if (keep_all || d_recent.get())
+        hipLaunchKernelGGL(gen_tag_remap_kernel, dim3(generation_grid(h, gy.n_cur)), dim3(256), 0, h->stream, (const uint32_t*)h->tag_bits.get(), gy.n_cur,
+                           (const uint32_t*)d_recent.get(), keep_all ? 1 : 0, (const int64_t*)gy.map.get(), n_items, p.tag_bits.get(), d_n);
+    }
+    if (!tag_items.empty()) {
+      FCHK(msg, d_rows.alloc(tag_items.size()));
+      FCHK(msg, hipMemcpyAsync(d_rows.get(), tag_items.data(), sizeof(int64_t) * tag_items.size(), hipMemcpyHostToDevice, h->stream));
+      hipLaunchKernelGGL(topn_tag_bits_kernel, dim3((unsigned)((tag_items.size() + 255) / 256)), dim3(256), 0, h->stream, (const int64_t*)d_rows.get(),
+                         (int64_t)tag_items.size(), n_items, p.tag_bits.get(), d_n);
+    }
+    FCHK(msg, hipGetLastError());
+    unsigned long long n_set = 0;
+    FCHK(msg, hipMemcpyAsync(&n_set, d_n, sizeof(n_set), hipMemcpyDeviceToHost, h->stream));
+    FCHK(msg, hipStreamSynchronize(h->stream));
+    p.n_tag_items = (int64_t)n_set;
+    if (n_set == 0) p.tag_bits.reset();   // (as mals_set_tag_items: nothing to strike)
+  }
+  return MALS_OK;
+}
+
+double generation_wall_ms(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+  return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+// the counts and the device times of one handle's two sides (ev: the events of side sd; a handle's two sides share one list)
+void generation_result_sides(mals_generation_result* R, const GenPrepared& p, const GenEvents& ev_x, const GenEvents& ev_y) {
+  const int32_t size = R->struct_size;
+  std::memset(R, 0, sizeof(*R));
+  R->struct_size = size;
+  for (int sd = 0; sd < 2; ++sd) {
+    const GenSide& g = p.side[sd];
+    const GenEvents& ev = sd == MALS_SIDE_X ? ev_x : ev_y;
+    R->n_merged[sd] = g.n_new + g.n_kept;
+    R->n_updated[sd] = g.n_hit;
+    R->n_kept[sd] = g.n_kept;
+    R->n_pruned[sd] = g.n_cur - g.n_hit - g.n_kept;
+    R->join_ms[sd] = ev.ms(g.e0, g.e0 + 1);
+    R->scan_ms[sd] = ev.ms(g.e0 + 1, g.e0 + 2) + ev.ms(g.e0 + 3, g.e0 + 4);
+    R->gather_ms[sd] = ev.ms(g.e0 + 4, g.e0 + 5);
+  }
+}
+
+// PREPARE (everything aside), then generation_swap_prepare, then generation_swap: a handle runs the three here; a group runs
+// the same three for every member (generation_group_host.h) and swaps only when every member is ready.
+int generation_load_body(mals_handle h, const mals_generation_load& L, mals_generation_result* R, GenPrepared& p, std::string& msg) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = generation_load_check(h, L, false, msg)) return rc;
+  const bool holds_known = generation_holds_known(h);
   GenEvents ev;
   for (int sd = 0; sd < 2; ++sd)
     if (int rc = generation_side(h, sd, L, ev, p.side[sd], msg)) return rc;
@@ -472,109 +636,35 @@ int generation_load_body(mals_handle h, const mals_generation_load& L, mals_gene
     if (nnz > 0) FCHK(msg, hipMemcpyAsync(p.known_idx.get(), L.new_known_idx, sizeof(int32_t) * (size_t)nnz, kind, h->stream));
     if (gx.n_kept > 0 && holds_known) {
       std::vector<std::vector<int32_t>> sets;
-      if (int rc = foldin_known_full(h, gx.h_kept_rows, sets, msg)) return rc;   // base row + overlay, sorted, distinct
-      std::vector<int64_t> flat, mapped;
-      for (const auto& v : sets) flat.insert(flat.end(), v.begin(), v.end());
-      if (int rc = generation_map_rows(h, gy, flat, mapped, msg)) return rc;
-      size_t at = 0;
-      for (size_t i = 0; i < sets.size(); ++i) {
-        std::vector<int32_t> out;
-        for (size_t j = 0; j < sets[i].size(); ++j, ++at) {
-          if (mapped[at] >= 0) out.push_back((int32_t)mapped[at]);
-          else ++known_dropped;   // (the reference keeps the bare id: only mostPopularItems could see it)
-        }
-        std::sort(out.begin(), out.end());
-        if (!out.empty()) p.kept_sets[gx.n_new + (int64_t)i] = std::move(out);
-      }
+      if (int rc = generation_kept_sets(h, gy, gx.h_kept_rows, sets, &known_dropped, msg)) return rc;
+      for (size_t i = 0; i < sets.size(); ++i)
+        if (!sets[i].empty()) p.kept_sets[gx.n_new + (int64_t)i] = std::move(sets[i]);
     }
     FCHK(msg, hipStreamSynchronize(h->stream));
   }
   const auto t2 = std::chrono::steady_clock::now();
 
-  // TAG SETS: updated ids, plus the live tags that are recent (updateTagIDs :108-115, removeNotUpdated :88-95)
-  const bool keep_all = (L.flags & MALS_GENERATION_KEEP_NOT_UPDATED) != 0;
   int64_t without_row = 0;
   {
-    // itemTagIDs: user-side ids -> the tag users of mals_most_popular_items
     const GenerationState& gs = *generation_state(h);
-    std::vector<int64_t> live, live_mapped;
-    if (h->serving->pop)
-      for (int64_t r : popular_state(h)->tag_users)
-        if (keep_all || generation_is_recent(gs.recent[MALS_SIDE_X], r)) live.push_back(r);
-    if (int rc = generation_map_rows(h, gx, live, live_mapped, msg)) return rc;
-    if (int rc = generation_tag_rows(h, gx, L.item_tag_ids, L.n_item_tag_ids, L.new_mem_kind, p.tag_users, &without_row, msg)) return rc;
-    for (int64_t m : live_mapped)
-      if (m >= 0) p.tag_users.push_back(m);
-    std::sort(p.tag_users.begin(), p.tag_users.end());
-    p.tag_users.erase(std::unique(p.tag_users.begin(), p.tag_users.end()), p.tag_users.end());
-    // userTagIDs: item-side ids -> one bit per merged item
-    std::vector<int64_t> tag_items;
-    if (int rc = generation_tag_rows(h, gy, L.user_tag_ids, L.n_user_tag_ids, L.new_mem_kind, tag_items, &without_row, msg)) return rc;
-    if (h->tag_bits.get() || !tag_items.empty()) {
-      const int64_t n_items = gy.n_new + gy.n_kept;
-      const size_t words = ((size_t)((n_items + 31) / 32) + 1) & ~(size_t)1;   // (the layout of mals_set_tag_items)
-      const size_t tail = sizeof(unsigned long long) / sizeof(uint32_t);
-      FCHK(msg, p.tag_bits.alloc(words + tail));
-      unsigned long long* d_n = reinterpret_cast<unsigned long long*>(p.tag_bits.get() + words);
-      FCHK(msg, hipMemsetAsync(p.tag_bits.get(), 0, sizeof(uint32_t) * (words + tail), h->stream));
-      DeviceBuffer<uint32_t> d_recent;
-      DeviceBuffer<int64_t> d_rows;
-      std::vector<uint32_t>& recent_img = p.tag_recent_img;
-      if (h->tag_bits.get() && h->tag_bits_items == gy.n_cur && gy.n_cur > 0) {
-        const size_t rwords = (size_t)((gy.n_cur + 31) / 32);
-        const std::vector<uint32_t>& recent = gs.recent[MALS_SIDE_Y];
-        if (!keep_all && !recent.empty()) {
-          recent_img.assign(rwords, 0u);
-          std::copy(recent.begin(), recent.begin() + std::min(rwords, recent.size()), recent_img.begin());
-          FCHK(msg, d_recent.alloc(rwords));
-          FCHK(msg, hipMemcpyAsync(d_recent.get(), recent_img.data(), sizeof(uint32_t) * rwords, hipMemcpyHostToDevice, h->stream));
-        }
-        if (keep_all || d_recent.get())
-          hipLaunchKernelGGL(gen_tag_remap_kernel, dim3(generation_grid(h, gy.n_cur)), dim3(256), 0, h->stream, (const uint32_t*)h->tag_bits.get(), gy.n_cur,
-                             (const uint32_t*)d_recent.get(), keep_all ? 1 : 0, (const int64_t*)gy.map.get(), n_items, p.tag_bits.get(), d_n);
-      }
-      if (!tag_items.empty()) {
-        FCHK(msg, d_rows.alloc(tag_items.size()));
-        FCHK(msg, hipMemcpyAsync(d_rows.get(), tag_items.data(), sizeof(int64_t) * tag_items.size(), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(topn_tag_bits_kernel, dim3((unsigned)((tag_items.size() + 255) / 256)), dim3(256), 0, h->stream, (const int64_t*)d_rows.get(),
-                           (int64_t)tag_items.size(), n_items, p.tag_bits.get(), d_n);
-      }
-      FCHK(msg, hipGetLastError());
-      unsigned long long n_set = 0;
-      FCHK(msg, hipMemcpyAsync(&n_set, d_n, sizeof(n_set), hipMemcpyDeviceToHost, h->stream));
-      FCHK(msg, hipStreamSynchronize(h->stream));
-      p.n_tag_items = (int64_t)n_set;
-      if (n_set == 0) p.tag_bits.reset();   // (as mals_set_tag_items: nothing to strike)
-    }
+    static const std::vector<int64_t> none;
+    if (int rc = generation_tag_users(h, gx, L, gs.recent[MALS_SIDE_X], h->serving->pop ? popular_state(h)->tag_users : none, p.tag_users, &without_row, msg))
+      return rc;
+    if (int rc = generation_tag_items(h, gy, L, gs.recent[MALS_SIDE_Y], p, &without_row, msg)) return rc;
   }
   FCHK(msg, hipStreamSynchronize(h->stream));
   const auto t3 = std::chrono::steady_clock::now();
-  auto wall_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
-  };
   if (R) {
-    const int32_t size = R->struct_size;
-    std::memset(R, 0, sizeof(*R));
-    R->struct_size = size;
-    for (int sd = 0; sd < 2; ++sd) {
-      const GenSide& g = p.side[sd];
-      R->n_merged[sd] = g.n_new + g.n_kept;
-      R->n_updated[sd] = g.n_hit;
-      R->n_kept[sd] = g.n_kept;
-      R->n_pruned[sd] = g.n_cur - g.n_hit - g.n_kept;
-      R->join_ms[sd] = ev.ms(g.e0, g.e0 + 1);
-      R->scan_ms[sd] = ev.ms(g.e0 + 1, g.e0 + 2) + ev.ms(g.e0 + 3, g.e0 + 4);
-      R->gather_ms[sd] = ev.ms(g.e0 + 4, g.e0 + 5);
-    }
+    generation_result_sides(R, p, ev, ev);
     R->n_known_dropped = known_dropped;
     R->n_tag_ids_without_row = without_row;
-    R->sides_ms = wall_ms(t0, t1);
-    R->known_ms = wall_ms(t1, t2);
-    R->tags_ms = wall_ms(t2, t3);
+    R->sides_ms = generation_wall_ms(t0, t1);
+    R->known_ms = generation_wall_ms(t1, t2);
+    R->tags_ms = generation_wall_ms(t2, t3);
   }
   if (int rc = generation_swap_prepare(h, msg)) return rc;
   generation_swap(h, p);
-  if (R) R->total_ms = wall_ms(t0, std::chrono::steady_clock::now());
+  if (R) R->total_ms = generation_wall_ms(t0, std::chrono::steady_clock::now());
   return MALS_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "hip_buffer.h"
 #include "factor_digest.h"
 #include "group_plan.h"
+#include "generation_group_plan.h"
 #include "convergence.h"
 
 #include <dlfcn.h>
@@ -30,6 +31,7 @@
 #include <cstring>
 #include <limits>
 #include <mutex>
+#include <thread>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -166,6 +168,9 @@ struct mals_group_s {
   std::mutex err_mu;                   // the failure text of a read: request threads share the group's string
   std::atomic<uint32_t> next_reader{0};
   std::atomic<int64_t> users_end{0};   // rows of the X replicas: users past the installed matrix belong to the last rank
+  // mals_group_load_generation changes bounds[X] and every member's slice while request threads route by them: odd while a load
+  // runs; a routed read that began under another value is repeated (route_by_owner)
+  std::atomic<uint64_t> generation_seq{0};
   std::string err;
 };
 
@@ -1124,18 +1129,31 @@ struct GroupFactorize {
 // (No message on a refusal: request threads share the group's error string.)
 template <class Call>
 int route_by_owner(mals_group g, const int64_t* user_idx, int32_t n_queries, bool any_member, Call&& call) {
-  const std::vector<int64_t>& b = g->bounds[MALS_SIDE_X];
-  if (b.empty()) return MALS_INVALID_ARG;
-  for (int32_t q0 = 0, q1 = 0; q0 < n_queries; q0 = q1) {
-    int owner = 0;
-    if (!mals::owner_run(b, g->users_end.load(std::memory_order_acquire), user_idx, n_queries, q0, &q1, &owner)) return MALS_INVALID_ARG;
-    const Member* mb = any_member ? &g->m[0] : nullptr;
-    for (const Member& m : g->m)
-      if (m.rank == owner) mb = &m;
-    if (!mb) return MALS_INVALID_ARG;   // the owner is another process's rank
-    if (int rc = call(mb->h, q0, q1 - q0)) return rc;
+  for (;;) {
+    // a load of a new generation (mals_group_load_generation) moves users between members: what was routed by the old bounds
+    // and answered after the swap is asked again
+    const uint64_t seq = g->generation_seq.load(std::memory_order_acquire);
+    if (seq & 1) {
+      std::this_thread::yield();
+      continue;
+    }
+    int rc = MALS_OK;
+    const std::vector<int64_t>& b = g->bounds[MALS_SIDE_X];
+    if (b.empty()) rc = MALS_INVALID_ARG;
+    for (int32_t q0 = 0, q1 = 0; rc == MALS_OK && q0 < n_queries; q0 = q1) {
+      int owner = 0;
+      if (!mals::owner_run(b, g->users_end.load(std::memory_order_acquire), user_idx, n_queries, q0, &q1, &owner)) {
+        rc = MALS_INVALID_ARG;
+        break;
+      }
+      const Member* mb = any_member ? &g->m[0] : nullptr;
+      for (const Member& m : g->m)
+        if (m.rank == owner) mb = &m;
+      if (!mb) rc = MALS_INVALID_ARG;   // the owner is another process's rank
+      else rc = call(mb->h, q0, q1 - q0);
+    }
+    if (g->generation_seq.load(std::memory_order_acquire) == seq) return rc;
   }
-  return MALS_OK;
 }
 
 }  // namespace
@@ -1569,6 +1587,155 @@ int mals_factor_digest_host(const float* rows, int32_t features, int64_t row_beg
     sum += mals::factor_digest_term(j0 + e, bits);
   }
   *out = sum;
+  return MALS_OK;
+}
+
+}  // extern "C"
+
+// ---- loading a new generation into a group (include/myrrix_als.h; the members' side: generation_group_host.h) -----------------
+namespace {
+
+// the arrays of a load that live on `src_dev`, as a member on another device reads them: peer copies on its compute stream
+struct LoadCopies {
+  mals::DeviceBuffer<int64_t> i64[7];
+  mals::DeviceBuffer<float> f32[2];
+  mals::DeviceBuffer<int32_t> i32;
+};
+
+template <class T>
+int load_copy(mals_group g, Member& mb, int src_dev, const T** field, int64_t n, mals::DeviceBuffer<T>& own) {
+  if (!*field || n <= 0) return MALS_OK;
+  bool copied = false;
+  return member_slice(g, mb, *field, src_dev, false, n, own, field, &copied);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mals_group_load_generation(mals_group g, const mals_generation_load* load, mals_generation_result* result_out) {
+  if (!g) return MALS_INVALID_ARG;
+  if (!load || load->struct_size != (int32_t)sizeof(mals_generation_load) || (result_out && result_out->struct_size != (int32_t)sizeof(mals_generation_result)))
+    return gfail(g, MALS_INVALID_ARG, "mals_group_load_generation: null argument or struct_size mismatch");
+  if (int rc = foldin_group_ready(g, "mals_group_load_generation")) return rc;
+  const mals_generation_load& L = *load;
+  bool ok = (L.cur_mem_kind == MALS_MEM_HOST || L.cur_mem_kind == MALS_MEM_DEVICE) && (L.new_mem_kind == MALS_MEM_HOST || L.new_mem_kind == MALS_MEM_DEVICE);
+  for (int sd = 0; sd < 2 && ok; ++sd)
+    ok = L.n_cur[sd] >= 0 && L.n_new[sd] >= 0 && (L.n_cur[sd] == 0 || L.cur_ids[sd]) && (L.n_new[sd] == 0 || (L.new_ids[sd] && L.new_rows[sd])) &&
+         L.n_cur[sd] < ((int64_t)1 << 31) && L.n_new[sd] < ((int64_t)1 << 31);
+  ok = ok && L.n_item_tag_ids >= 0 && L.n_user_tag_ids >= 0 && (L.n_item_tag_ids == 0 || L.item_tag_ids) && (L.n_user_tag_ids == 0 || L.user_tag_ids);
+  if (!ok) return gfail(g, MALS_INVALID_ARG, "mals_group_load_generation: bad arguments (mem kinds, counts in [0, 2^31), null arrays)");
+  std::vector<mals_handle> hs = member_handles(g);
+  const size_t n = hs.size();
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  // device arrays live on the first member's device: a member elsewhere reads its own copies
+  const int src_dev = g->m[0].device;
+  std::vector<mals_generation_load> loads(n, L);
+  std::vector<LoadCopies> copies(n);
+  const int k = g->cfg.features;
+  if (int rc = for_members(g, [&](Member& mb, size_t i) -> int {
+        if (mb.device == src_dev) return MALS_OK;
+        mals_generation_load& M = loads[i];
+        LoadCopies& c = copies[i];
+        if (L.cur_mem_kind == MALS_MEM_DEVICE)
+          for (int sd = 0; sd < 2; ++sd)
+            if (int rc = load_copy(g, mb, src_dev, &M.cur_ids[sd], L.n_cur[sd], c.i64[sd])) return rc;
+        if (L.new_mem_kind == MALS_MEM_DEVICE) {
+          for (int sd = 0; sd < 2; ++sd) {
+            if (int rc = load_copy(g, mb, src_dev, &M.new_ids[sd], L.n_new[sd], c.i64[2 + sd])) return rc;
+            if (int rc = load_copy(g, mb, src_dev, &M.new_rows[sd], L.n_new[sd] * k, c.f32[sd])) return rc;
+          }
+          if (L.new_known_ptr) {
+            int64_t nnz = 0;
+            if (L.n_new[MALS_SIDE_X] > 0)
+              GHIP(g, hipMemcpy(&nnz, L.new_known_ptr + L.n_new[MALS_SIDE_X], sizeof(int64_t), hipMemcpyDeviceToHost));
+            if (nnz < 0) return gfail(g, MALS_INVALID_ARG, "mals_group_load_generation: bad known-item arrays of the new model");
+            if (int rc = load_copy(g, mb, src_dev, &M.new_known_ptr, L.n_new[MALS_SIDE_X] + 1, c.i64[4])) return rc;
+            if (int rc = load_copy(g, mb, src_dev, &M.new_known_idx, nnz, c.i32)) return rc;
+          }
+          if (int rc = load_copy(g, mb, src_dev, &M.item_tag_ids, L.n_item_tag_ids, c.i64[5])) return rc;
+          if (int rc = load_copy(g, mb, src_dev, &M.user_tag_ids, L.n_user_tag_ids, c.i64[6])) return rc;
+        }
+        GHIP(g, hipStreamSynchronize(mb.compute));
+        return MALS_OK;
+      }))
+    return rc;
+  const bool had_bounds = g->bounds[MALS_SIDE_X].size() == n + 1;
+  std::vector<int64_t> bx(n + 1, 0), by(n + 1, 0);
+  std::string msg;
+  g->generation_seq.fetch_add(1, std::memory_order_acq_rel);   // odd: routed reads wait, and repeat what they began before
+  const int rc = malsi_group_load_generation(hs.data(), (int)n, loads.data(), result_out, had_bounds ? g->bounds[MALS_SIDE_X].data() : nullptr, bx.data(),
+                                             by.data(), &msg);
+  int rc2 = MALS_OK;
+  if (rc == MALS_OK) {
+    const int64_t n_users = bx.back(), n_items = by.back();
+    for (int sd = 0; sd < 2; ++sd) {
+      const std::vector<int64_t>& nb = sd == MALS_SIDE_X ? bx : by;
+      if (g->bounds[sd].size() == nb.size()) std::copy(nb.begin(), nb.end(), g->bounds[sd].begin());   // (in place: readers hold no stale block)
+      else g->bounds[sd] = nb;
+      g->n_rows[sd] = g->n_total[sd] = sd == MALS_SIDE_X ? n_users : n_items;
+    }
+    g->users_end.store(n_users, std::memory_order_release);
+    // the members' matrices and installed slices named live rows: the handles dropped them, the group's copies go too
+    for (Member& mb : g->m) {
+      (void)hipSetDevice(mb.device);
+      for (int sd = 0; sd < 2; ++sd) {
+        mb.d_row_ptr[sd].reset();
+        mb.own_col[sd].reset();
+        mb.own_val[sd].reset();
+      }
+      mb.own_known_ptr.reset();
+      mb.own_known_idx.reset();
+      mb.own_tag_idx.reset();
+    }
+    for (int sd = 0; sd < 2 && rc2 == MALS_OK; ++sd) rc2 = refresh_replica_ptrs(g, sd);
+  }
+  g->generation_seq.fetch_add(1, std::memory_order_acq_rel);
+  for (size_t i = 0; i < n; ++i) {   // a member's copies go with its device current
+    (void)hipSetDevice(g->m[i].device);
+    copies[i] = LoadCopies();
+  }
+  if (rc != MALS_OK) return write_failed(g, rc, "mals_group_load_generation", msg);
+  return rc2;
+}
+
+static int group_generation_get(mals_group g, int side, bool ids, int64_t* out, const char* call) {
+  if (int rc = foldin_group_ready(g, call)) return rc;
+  GSIDE(g, side);
+  Member& mb = g->m[0];   // (every member holds the same ids and maps)
+  const int rc = ids ? mals_generation_get_ids(mb.h, side, out) : mals_generation_get_map(mb.h, side, out);
+  return rc == MALS_OK ? rc : mfail(g, mb, rc);
+}
+int mals_group_generation_get_ids(mals_group g, int side, int64_t* ids_out) { return group_generation_get(g, side, true, ids_out, "mals_group_generation_get_ids"); }
+int mals_group_generation_get_map(mals_group g, int side, int64_t* map_out) { return group_generation_get(g, side, false, map_out, "mals_group_generation_get_map"); }
+
+// the group's recent rows are its first member's record, in global rows
+int mals_group_mark_recent(mals_group g, int side, int64_t n, const int64_t* rows) {
+  if (int rc = foldin_group_ready(g, "mals_group_mark_recent")) return rc;
+  GSIDE(g, side);
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  Member& mb = g->m[0];
+  const int rc = mals_mark_recent(mb.h, side, n, rows);
+  return rc == MALS_OK ? rc : mfail(g, mb, rc);
+}
+
+int mals_group_get_recent(mals_group g, int side, int64_t* rows_out, int64_t* n_out) {
+  if (int rc = foldin_group_ready(g, "mals_group_get_recent")) return rc;
+  GSIDE(g, side);
+  std::lock_guard<std::mutex> lk(g->write_mu);
+  Member& mb = g->m[0];
+  const int rc = mals_get_recent(mb.h, side, rows_out, n_out);
+  return rc == MALS_OK ? rc : mfail(g, mb, rc);
+}
+
+int mals_group_generation_plan_host(int32_t world, int32_t features, int64_t n_new, const int64_t* new_known_ptr, int64_t n_kept,
+                                    const int64_t* kept_sizes, const int64_t* kept_rows, const int64_t* old_bounds, int64_t* bounds_out,
+                                    int64_t* moves_out) {
+  if (!bounds_out) return MALS_INVALID_ARG;
+  mals::GenGroupPlan p;
+  if (!mals::generation_group_plan(world, features, n_new, new_known_ptr, n_kept, kept_sizes, kept_rows, old_bounds, p)) return MALS_INVALID_ARG;
+  std::copy(p.bounds.begin(), p.bounds.end(), bounds_out);
+  if (moves_out) std::copy(p.move.begin(), p.move.end(), moves_out);
   return MALS_OK;
 }
 

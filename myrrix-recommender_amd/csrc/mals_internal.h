@@ -52,6 +52,11 @@ __attribute__((visibility("hidden"))) int malsi_group_factor_digest(mals_handle*
 __attribute__((visibility("hidden"))) int malsi_group_set_tag_users(mals_handle* hs, int n_members, int64_t n, const int64_t* user_idx, std::string* err);
 __attribute__((visibility("hidden"))) int malsi_group_most_popular_items(mals_handle* hs, int n_members, int32_t how_many, int64_t* item_idx_out,
                                                                        float* score_out, int32_t* n_out, std::string* err);
+// mals_group_load_generation (generation_group_host.h): loads[m] = the call's arguments as member m reads them (device arrays on
+// ITS device); old_bounds_x: the group's bounds[X] (n_members + 1) or NULL; the new bounds (n_members + 1 each) on success
+__attribute__((visibility("hidden"))) int malsi_group_load_generation(mals_handle* hs, int n_members, const mals_generation_load* loads,
+                                                                    mals_generation_result* result_out, const int64_t* old_bounds_x,
+                                                                    int64_t* bounds_x_out, int64_t* bounds_y_out, std::string* err);
 // the fold-in reads on one member's handle (any member answers: replicas and solvers are complete everywhere)
 __attribute__((visibility("hidden"))) int malsi_member_estimate_preferences(mals_handle h, int64_t n, const int64_t* user_row,
                                                                           const int64_t* item_row, float* out);

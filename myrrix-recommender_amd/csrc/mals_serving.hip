@@ -9,11 +9,13 @@
 #include "foldin_kernels.h"
 #include "popular_kernels.h"
 #include "generation_kernels.h"
+#include "generation_group_kernels.h"
 #define MALS_FACTOR_DIGEST_KERNEL
 #include "factor_digest.h"
 #include "mals_internal.h"
 #include "mals_handle.h"
 #include "foldin_plan.h"
+#include "generation_group_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -109,6 +111,7 @@ void generation_mark_pairs(mals_handle h, int64_t n, const int64_t* user_row, co
 #include "foldin_host.h"
 #include "popular_host.h"
 #include "generation_host.h"
+#include "generation_group_host.h"
 }  // namespace
 
 // ---- what mals_api.hip calls of this unit (mals_handle.h) ------------------------------------------------------------------
@@ -910,6 +913,29 @@ int malsi_group_most_popular_items(mals_handle* hs, int n_members, int32_t how_m
                                    std::string* err) {
   return group_call(hs, n_members, err, [&](std::string& msg) -> int {
     return popular_members(hs, n_members, true, nullptr, how_many, item_idx_out, score_out, n_out, msg);
+  });
+}
+
+// mals_group_load_generation (generation_group_host.h): loads[m] = the arguments as member m reads them; old_bounds_x = the
+// group's bounds[X] (n_members + 1) or NULL; on success bounds_x_out / bounds_y_out (n_members + 1 each) are the new ones
+int malsi_group_load_generation(mals_handle* hs, int n_members, const mals_generation_load* loads, mals_generation_result* result_out,
+                                const int64_t* old_bounds_x, int64_t* bounds_x_out, int64_t* bounds_y_out, std::string* err) {
+  return group_call(hs, n_members, err, [&](std::string& msg) -> int {
+    if (int rc = generation_group_run(hs, n_members, loads, result_out, old_bounds_x, bounds_x_out, bounds_y_out, msg)) return rc;
+    if (loads[0].flags & MALS_GENERATION_RECOMPUTE_SOLVERS) {   // the merged replicas are the same everywhere: computed once, installed on all
+      int first = MALS_OK;
+      mals_solver sv[2] = {nullptr, nullptr};
+      if (hipSetDevice(hs[0]->cfg.device) != hipSuccess) first = MALS_HIP_ERROR;
+      for (int sd = 0; sd < 2 && first == MALS_OK; ++sd) first = mals_recompute_solver(hs[0], sd, &sv[sd], nullptr);
+      for (int sd = 0; sd < 2 && first == MALS_OK; ++sd) {
+        std::string why;
+        first = foldin_solver_members(hs, n_members, sd, sv[sd], why);
+      }
+      for (mals_solver s : sv)
+        if (s) (void)mals_solver_destroy(s);
+      if (result_out) result_out->solver_status = first;
+    }
+    return MALS_OK;
   });
 }
 

@@ -15,7 +15,31 @@ import numpy as np
 
 from . import _lib
 from ._lib import MEM_DEVICE, MEM_HOST, SIDE_X, SIDE_Y
-from .core import ALSCore, Cancelled, MalsError, SingularSystem, _host, _item_queries
+from .core import ALSCore, Cancelled, MalsError, SingularSystem, _host, _item_queries, _load_generation
+
+
+def generation_plan_host(world, features, new_known_ptr, kept_sizes, kept_rows, old_bounds, n_new=None):
+    """mals_group_generation_plan_host: who owns which merged user after GroupALS.load_generation.  new_known_ptr: n_new + 1
+    offsets or None (then n_new says how many new users); kept_rows: the kept users' live rows, ascending; kept_sizes:
+    their set sizes; old_bounds: world + 1 or None.  Returns (bounds[world + 1], moves[world][world][2]): moves[m][j] = the run
+    of old member m's own kept list that new member j gets.  Host only."""
+    L = _lib.load()
+    rp = np.ascontiguousarray(new_known_ptr, dtype=np.int64) if new_known_ptr is not None else None
+    n_new = len(rp) - 1 if rp is not None else int(n_new or 0)
+    ks = np.ascontiguousarray(kept_sizes, dtype=np.int64)
+    kr = np.ascontiguousarray(kept_rows, dtype=np.int64)
+    ob = np.ascontiguousarray(old_bounds, dtype=np.int64) if old_bounds is not None else None
+    assert len(ks) == len(kr) and (ob is None or len(ob) == world + 1)
+    bounds = np.zeros(world + 1, dtype=np.int64)
+    moves = np.zeros((world, world, 2), dtype=np.int64)
+    rc = L.mals_group_generation_plan_host(int(world), int(features), n_new, rp.ctypes.data_as(ctypes.c_void_p) if rp is not None else None,
+                                           len(ks), ks.ctypes.data_as(ctypes.c_void_p) if len(ks) else None,
+                                           kr.ctypes.data_as(ctypes.c_void_p) if len(kr) else None,
+                                           ob.ctypes.data_as(ctypes.c_void_p) if ob is not None else None,
+                                           bounds.ctypes.data_as(ctypes.c_void_p), moves.ctypes.data_as(ctypes.c_void_p))
+    if rc != _lib.OK:
+        raise MalsError(rc, "mals_group_generation_plan_host")
+    return bounds, moves
 
 
 def plan_shards(row_ptr, world, features, row_cost=-1.0):
@@ -382,6 +406,36 @@ class GroupALS:
             self._chk(rc)
         return out, st
 
+    # -- a new generation into the live group (the mals_group_* twins of ALSCore's methods of the same names) ------
+    def mark_recent(self, side, rows):
+        """mals_group_mark_recent: global rows of `side` written elsewhere since the last load."""
+        r = _host(rows, np.int64)
+        self._chk(self._L.mals_group_mark_recent(self._g, side, len(r), r.ctypes.data_as(ctypes.c_void_p) if len(r) else None))
+
+    def get_recent(self, side):
+        """mals_group_get_recent: the global rows of `side` written since the last load (the group's writes and
+        mark_recent), ascending."""
+        n = ctypes.c_int64(0)
+        self._chk(self._L.mals_group_get_recent(self._g, side, None, ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.int64)
+        if n.value:
+            self._chk(self._L.mals_group_get_recent(self._g, side, out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n)))
+        return out[:n.value]
+
+    def load_generation(self, cur_user_ids, cur_item_ids, new_user_ids, new_item_ids, new_X, new_Y, new_known=None,
+                        item_tag_ids=None, user_tag_ids=None, keep_not_updated=False, recompute_solvers=False):
+        """mals_group_load_generation: ALSCore.load_generation for the group -- the same arguments (the new model WHOLE; torch
+        CUDA tensors on the first local member's device) and the same return shape.  Afterwards bounds(SIDE_X) is the new
+        ownership plan."""
+        out = _load_generation(self.features, lambda L, R: self._chk(self._L.mals_group_load_generation(self._g, L, R)),
+                               lambda side, p: self._chk(self._L.mals_group_generation_get_ids(self._g, side, p)),
+                               lambda side, p: self._chk(self._L.mals_group_generation_get_map(self._g, side, p)),
+                               cur_user_ids, cur_item_ids, new_user_ids, new_item_ids, new_X, new_Y, new_known, item_tag_ids, user_tag_ids,
+                               keep_not_updated, recompute_solvers)
+        for side in (SIDE_X, SIDE_Y):     # the members' matrices are released: nothing of the caller's is borrowed any more
+            self._keep.pop(("M", side), None)
+        return out
+
     def replica_digest(self, side, row_begin=0, n_rows=None):
         """mals_group_replica_digest: (uint64 digest of the range on every local member, whether they all agree), taken
         between the same two group writes on every member.  n_rows None: to the end of the replica."""
@@ -432,4 +486,4 @@ class GroupALS:
         return it.value, conv.value
 
 
-__all__ = ["GroupALS", "plan_shards", "SIDE_X", "SIDE_Y"]
+__all__ = ["GroupALS", "plan_shards", "generation_plan_host", "SIDE_X", "SIDE_Y"]

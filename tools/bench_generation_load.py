@@ -11,6 +11,10 @@ the same new model again with the kept rows marked recent again, so every timed 
     the head copy and the tail gather;
   * the only route the library had before: mals_set_factors of both sides from host memory plus mals_set_known_items on
     a handle of the merged shape.
+--members W loads the same shape through a W-member group on device 0 (peer-copy backend, mals_group_load_generation): the
+phase times are then the slowest member's, known_ms is the group's known-item step (the device path for plain kept users and
+the assembly of every new owner's CSR).  --live-known-per-user gives every live user a base row of that many items, and
+--keep-not-updated keeps every live row the new model lacks, so that the --kept users are plain kept users with real rows.
 Prints one JSON line last.  Not part of bench.py."""
 import argparse
 import json
@@ -44,6 +48,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--skip-parent-route", action="store_true")
+    ap.add_argument("--members", type=int, default=0, help="load through a group of this many members on device 0 (0: one handle)")
+    ap.add_argument("--keep-not-updated", action="store_true", help="MALS_GENERATION_KEEP_NOT_UPDATED")
+    ap.add_argument("--live-known-per-user", type=int, default=0, help="known items of every live user before the first load")
     a = ap.parse_args()
 
     import torch
@@ -61,10 +68,18 @@ def main():
     kp = torch.arange(0, (n[0] + 1) * a.known_per_user, a.known_per_user, device=dev, dtype=torch.int64)
     ki = torch.randint(0, n[1], (n[0] * a.known_per_user,), device=dev, generator=g, dtype=torch.int32)
 
-    core = pkg.ALSCore(k)
+    if a.members > 0:
+        from myrrix_recommender_amd import _lib
+        core = pkg.GroupALS.single_process(k, [0] * a.members, backend=_lib.GROUP_PEER_COPY)
+    else:
+        core = pkg.ALSCore(k)
     for s in range(2):
         core.set_factor_rows(s, n[s])
-    core.set_matrix(X_, np.zeros(n[0] + 1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32))
+    lk = a.live_known_per_user
+    live_ptr = np.arange(0, (n[0] + 1) * lk, max(lk, 1), dtype=np.int64) if lk else np.zeros(n[0] + 1, np.int64)
+    live_idx = np.random.default_rng(2).integers(0, n[1], n[0] * lk, dtype=np.int32)
+    core.set_matrix(X_, live_ptr, live_idx, np.ones(len(live_idx), np.float32))
+    del live_ptr, live_idx
     cur = [torch.arange(n[s], device=dev, dtype=torch.int64) for s in range(2)]
     for s in range(2):
         core.mark_recent(s, np.arange(a.kept, dtype=np.int64))          # ids [0, kept): not in the new model
@@ -72,7 +87,8 @@ def main():
     results = []
     for it in range(a.warmup + a.reps):
         t0 = time.perf_counter()
-        res, ids, _ = core.load_generation(cur[0], cur[1], new_ids[0], new_ids[1], new_rows[0], new_rows[1], new_known=(kp, ki))
+        res, ids, _ = core.load_generation(cur[0], cur[1], new_ids[0], new_ids[1], new_rows[0], new_rows[1], new_known=(kp, ki),
+                                           keep_not_updated=a.keep_not_updated)
         res["call_ms"] = (time.perf_counter() - t0) * 1e3     # includes the two id / map read-backs of the binding
         assert res["n_kept"] == [a.kept, a.kept], res
         if it >= a.warmup:
@@ -81,7 +97,8 @@ def main():
         for s in range(2):
             core.mark_recent(s, np.arange(n[s], n[s] + a.kept, dtype=np.int64))   # the kept rows sit behind the new ones
 
-    out = {"tool": "bench_generation_load", "users": n[0], "items": n[1], "features": k, "kept": a.kept, "reps": a.reps, "phases": {}}
+    out = {"tool": "bench_generation_load", "users": n[0], "items": n[1], "features": k, "kept": a.kept, "reps": a.reps, "members": a.members,
+           "keep_not_updated": a.keep_not_updated, "live_known_per_user": lk, "phases": {}}
     names = ["users", "items"]
     for s in range(2):
         n_new, n_cur, n_kept = n[s], n[s] + a.kept, a.kept
@@ -124,7 +141,7 @@ def main():
         out["memcpy_dtod"][names[s]] = {"ms": ms, "bytes_copied": nbytes, "GBps_moved": 2 * nbytes / ms / 1e6}
         del src, dst
 
-    if not a.skip_parent_route:
+    if not a.skip_parent_route and a.members == 0:
         # what a caller had before: every row of both sides from host memory, and the known items, onto the serving handle
         merged = [n[s] + a.kept for s in range(2)]
         host_rows = [np.ascontiguousarray(torch.cat([new_rows[s], torch.zeros((a.kept, k), device=dev)]).cpu().numpy()) for s in range(2)]
