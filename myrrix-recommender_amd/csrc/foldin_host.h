@@ -51,7 +51,7 @@ struct FoldinState {
   DeviceBuffer<int32_t> d_status;
   DeviceBuffer<double> d_fold;         // userFoldIn of every update of the batch
   PinnedBuffer<uint8_t> h_stage;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  EventPair ev;                        // around a batch's update kernels (timing enabled: mals_foldin_stats reads the time)
 };
 
 FoldinState* foldin_state(mals_handle h) {
@@ -66,11 +66,7 @@ FoldinState* foldin_state(mals_handle h) {
 }
 
 void foldin_free(mals_handle h) {
-  FoldinState* fs = h->serving->fo;
-  if (fs)
-    for (hipEvent_t e : fs->ev)
-      if (e) (void)hipEventDestroy(e);
-  delete fs;
+  delete h->serving->fo;
   h->serving->fo = nullptr;
 }
 
@@ -355,8 +351,7 @@ int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int6
   FCHK(msg, fs.d_val.reserve((size_t)n, h->stream));
   FCHK(msg, fs.d_status.reserve((size_t)n, h->stream));
   FCHK(msg, fs.d_fold.reserve((size_t)n * k, h->stream));
-  for (hipEvent_t& e : fs.ev)
-    if (!e) FCHK(msg, hipEventCreate(&e));
+  FCHK(msg, fs.ev.ensure());
   int64_t* hu = reinterpret_cast<int64_t*>(fs.h_stage.get());
   int64_t* hi = hu + n;
   float* hv = reinterpret_cast<float*>(hi + n);
@@ -371,7 +366,7 @@ int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int6
   const FoldinSide& SX = fs.solver[MALS_SIDE_X];
   const FoldinSide& SY = fs.solver[MALS_SIDE_Y];
   const size_t lds = (size_t)k * FOLDIN_LANES * sizeof(double);
-  FCHK(msg, hipEventRecord(fs.ev[0], h->stream));
+  FCHK(msg, hipEventRecord(fs.ev.begin, h->stream));
   for (uint32_t l = 1; l <= p.n_levels; ++l) {
     const int64_t u0 = p.off[l], u1 = p.off[l + 1];
     hipLaunchKernelGGL(foldin_update_kernel, dim3((unsigned)((u1 - u0 + FOLDIN_LANES - 1) / FOLDIN_LANES)), dim3(FOLDIN_LANES), lds, h->stream, x.F,
@@ -379,7 +374,7 @@ int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int6
                        SY.present ? 1 : 0, fs.rate, fs.big_total, fs.d_fold.get(), fs.d_status.get());
   }
   FCHK(msg, hipGetLastError());
-  FCHK(msg, hipEventRecord(fs.ev[1], h->stream));
+  FCHK(msg, hipEventRecord(fs.ev.end, h->stream));
   int32_t* hs = reinterpret_cast<int32_t*>(fs.h_stage.get());
   FCHK(msg, hipMemcpyAsync(hs, fs.d_status.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   return MALS_OK;
@@ -394,7 +389,7 @@ int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int6
   const int32_t* hs = reinterpret_cast<const int32_t*>(fs.h_stage.get());
   FCHK(msg, hipStreamSynchronize(h->stream));
   float dev_ms = 0.f;
-  FCHK(msg, hipEventElapsedTime(&dev_ms, fs.ev[0], fs.ev[1]));
+  FCHK(msg, hipEventElapsedTime(&dev_ms, fs.ev.begin, fs.ev.end));
   foldin_new_model(h);
   int first = MALS_OK, first_why = 0;
   int64_t first_t = -1, applied = 0, failed = 0, big = 0;

@@ -125,16 +125,13 @@ int generation_join_host(const int64_t* cur_ids, int64_t n_cur, const int64_t* n
 
 // ---- the load ---------------------------------------------------------------------------------------------------------
 struct GenEvents {   // HIP events of one call
-  std::vector<hipEvent_t> ev;
-  ~GenEvents() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
+  std::vector<Event> ev;
   hipError_t record(hipStream_t st) {
-    hipEvent_t e = nullptr;
-    hipError_t rc = hipEventCreate(&e);
+    Event e;
+    hipError_t rc = e.ensure();
     if (rc != hipSuccess) return rc;
-    ev.push_back(e);
-    return hipEventRecord(e, st);
+    ev.push_back(std::move(e));
+    return hipEventRecord(ev.back(), st);
   }
   double ms(size_t a, size_t b) const {
     float t = 0.f;

@@ -1,7 +1,9 @@
-// hip_buffer.h -- the owner of every block of device or pinned host memory the library allocates (host code only).
-// A buffer knows its block and its capacity in elements; it releases the block when it is reset, reallocated, assigned
-// to or destroyed.  Memory the library only borrows (caller-bound factors, an installed ingest's matrices) stays a raw
-// pointer, and so do views into an owned block.  Fallible calls return the hipError_t of the call that failed.
+// hip_buffer.h -- the owners of what the library takes from the HIP runtime (host code only): every block of device or
+// pinned host memory (HipBuffer), every event (Event, EventPair) and every stream (Stream) it creates.  An owner releases
+// what it holds when it is reset, assigned to or destroyed -- a buffer also when it is reallocated -- so a holder's teardown
+// lists nothing, and a half-built holder leaks nothing.  What the library only borrows stays raw: caller-bound factors, an
+// installed ingest's matrices, views into an owned block, the caller's stream (mals_set_stream), every hipStream_t /
+// hipEvent_t parameter.  Fallible calls return the hipError_t of the call that failed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -99,20 +101,114 @@ using DeviceBuffer = HipBuffer<T, DeviceMemory>;
 template <typename T>
 using PinnedBuffer = HipBuffer<T, PinnedMemory>;
 
-// the two events around a timed stretch of a stream, destroyed with their holder on whichever path it is left
-struct EventPair {
-  hipEvent_t begin = nullptr, end = nullptr;
-  EventPair() = default;
-  EventPair(const EventPair&) = delete;
-  EventPair& operator=(const EventPair&) = delete;
-  ~EventPair() {
-    if (begin) (void)hipEventDestroy(begin);
-    if (end) (void)hipEventDestroy(end);
+// ---- events and streams ------------------------------------------------------------------------------------------
+// The runtime calls of the two owners below, as a policy (a host test puts a recording fake in their place).
+struct HipEventApi {
+  static hipError_t create(hipEvent_t* e, unsigned flags) { return hipEventCreateWithFlags(e, flags); }
+  static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+};
+struct HipStreamApi {
+  static hipError_t create(hipStream_t* s, unsigned flags) { return hipStreamCreateWithFlags(s, flags); }
+  static void synchronize(hipStream_t s) { (void)hipStreamSynchronize(s); }
+  static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+};
+
+// An event: empty until ensure(), destroyed on reset, assignment and destruction.  Converts to the raw handle, so it is
+// passed to HIP calls as it stands.
+template <typename Api>
+class BasicEvent {
+ public:
+  BasicEvent() = default;
+  BasicEvent(const BasicEvent&) = delete;
+  BasicEvent& operator=(const BasicEvent&) = delete;
+  BasicEvent(BasicEvent&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+  BasicEvent& operator=(BasicEvent&& o) noexcept {
+    if (this != &o) {
+      reset();
+      e_ = o.e_;
+      o.e_ = nullptr;
+    }
+    return *this;
   }
-  hipError_t create() {
-    const hipError_t e = hipEventCreate(&begin);
-    return e != hipSuccess ? e : hipEventCreate(&end);
+  ~BasicEvent() { reset(); }
+
+  hipEvent_t get() const { return e_; }
+  operator hipEvent_t() const { return e_; }
+  explicit operator bool() const { return e_ != nullptr; }
+
+  void reset() {
+    if (e_) Api::destroy(e_);
+    e_ = nullptr;
+  }
+
+  // creates the event unless there is one (whose flags then stay); a failure leaves the owner empty
+  hipError_t ensure(unsigned flags = hipEventDefault) {
+    if (e_) return hipSuccess;
+    hipEvent_t q = nullptr;
+    const hipError_t e = Api::create(&q, flags);
+    if (e == hipSuccess) e_ = q;
+    return e;
+  }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+
+// A stream, the same; it is synchronised before it is destroyed, so nothing it ran is in flight once its owner is gone.
+// A holder whose buffers the stream's work uses still waits for it itself before it lets go of the first of them.
+template <typename Api>
+class BasicStream {
+ public:
+  BasicStream() = default;
+  BasicStream(const BasicStream&) = delete;
+  BasicStream& operator=(const BasicStream&) = delete;
+  BasicStream(BasicStream&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+  BasicStream& operator=(BasicStream&& o) noexcept {
+    if (this != &o) {
+      reset();
+      s_ = o.s_;
+      o.s_ = nullptr;
+    }
+    return *this;
+  }
+  ~BasicStream() { reset(); }
+
+  hipStream_t get() const { return s_; }
+  operator hipStream_t() const { return s_; }
+  explicit operator bool() const { return s_ != nullptr; }
+
+  void reset() {
+    if (s_) {
+      Api::synchronize(s_);
+      Api::destroy(s_);
+    }
+    s_ = nullptr;
+  }
+
+  hipError_t ensure(unsigned flags = hipStreamNonBlocking) {
+    if (s_) return hipSuccess;
+    hipStream_t q = nullptr;
+    const hipError_t e = Api::create(&q, flags);
+    if (e == hipSuccess) s_ = q;
+    return e;
+  }
+
+ private:
+  hipStream_t s_ = nullptr;
+};
+
+// the two events around a timed stretch of a stream; after a failure halfway the next ensure() completes the pair
+template <typename Api>
+struct BasicEventPair {
+  BasicEvent<Api> begin, end;
+  hipError_t ensure(unsigned flags = hipEventDefault) {
+    const hipError_t e = begin.ensure(flags);
+    return e != hipSuccess ? e : end.ensure(flags);
   }
 };
+
+using Event = BasicEvent<HipEventApi>;
+using Stream = BasicStream<HipStreamApi>;
+using EventPair = BasicEventPair<HipEventApi>;
 
 }  // namespace mals

@@ -132,7 +132,7 @@ int mals_ingest_finish(mals_ingest g) {
   g->bytes_moved = 0.0;
   g->radix_passes = 0;
   EventPair ev;
-  ICHK(g, ev.create());
+  ICHK(g, ev.ensure());
   g->last_workspace_ms = 0.0;
   const int rc = finish_impl(g, ev.begin);
   if (rc != MALS_OK) {

@@ -159,7 +159,7 @@ int shard_split(mals_ingest g, const int64_t* key, const std::vector<int64_t>& s
   ICHK(g, sums.alloc((size_t)scan_tiles + 1));
   if (!splitters.empty()) ICHK(g, hipMemcpy(spl.get(), splitters.data(), sizeof(int64_t) * splitters.size(), hipMemcpyHostToDevice));
   EventPair ev;
-  ICHK(g, ev.create());
+  ICHK(g, ev.ensure());
   ICHK(g, hipEventRecord(ev.begin, g->stream));
   ITRY(launch_grid(g, {(unsigned)n_tiles}, split_count_kernel, key, n, spl.get(), nb - 1, n_tiles, dest.get(), counts_d.get()));
   ITRY(launch_grid(g, {(unsigned)scan_tiles}, big_scan64_reduce_kernel, counts_d.get(), n_counts, sums.get()));

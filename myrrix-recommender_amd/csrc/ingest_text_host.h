@@ -45,7 +45,7 @@ int process_text_region(mals_ingest g, size_t region) {
   // HIP-event time of the kernels only: allocations (which cost milliseconds to seconds, depending on the box) sit
   // between the timed segments
   EventPair ev;
-  ICHK(g, ev.create());
+  ICHK(g, ev.ensure());
   const hipEvent_t e0 = ev.begin, e1 = ev.end;
   auto seg_end = [&]() -> int {
     ICHK(g, hipEventRecord(e1, g->stream));
@@ -184,7 +184,7 @@ int append_text_impl(mals_ingest g, const uint8_t* bytes, int64_t n_bytes, int m
     const bool last = eof && off + (int64_t)m == n_bytes;
     const size_t total = g->carry_len + m;
     if (total + TEXT_PAD > g->d_text.capacity()) ICHK(g, g->d_text.alloc(((std::max(total, block) + TEXT_PAD + 4095) / 4096) * 4096));
-    if (!g->t_ev.begin) ICHK(g, g->t_ev.create());
+    ICHK(g, g->t_ev.ensure());
     ICHK(g, hipEventRecord(g->t_ev.begin, g->stream));
     if (g->carry_len) ICHK(g, hipMemcpyAsync(g->d_text.get(), g->d_carry.get(), g->carry_len, hipMemcpyDeviceToDevice, g->stream));
     if (m)

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -251,24 +252,25 @@ int validate_columns(mals_handle h, int side) {
 int begin_timed(mals_handle h, int kind, double bytes, PendingEvent& pe) {
   pe.kind = kind;
   pe.bytes = bytes;
-  pe.a = pe.b = nullptr;
   if (!h->timing) return MALS_OK;
-  HIPCHK(h, hipEventCreate(&pe.a));
-  HIPCHK(h, hipEventCreate(&pe.b));
-  HIPCHK(h, hipEventRecord(pe.a, h->stream));
+  HIPCHK(h, pe.ev.ensure());   // (a pe whose pair end_timed moved out is empty again)
+  HIPCHK(h, hipEventRecord(pe.ev.begin, h->stream));
   return MALS_OK;
 }
 int end_timed(mals_handle h, PendingEvent& pe) {
   if (!h->timing) return MALS_OK;
-  HIPCHK(h, hipEventRecord(pe.b, h->stream));
-  h->pending.push_back(pe);
+  HIPCHK(h, hipEventRecord(pe.ev.end, h->stream));
+  h->pending.push_back(std::move(pe));
   return MALS_OK;
 }
+// the list leaves the handle first: on whichever path this returns, h->pending is empty and every event destroyed once
 int drain_events(mals_handle h) {
-  for (PendingEvent& pe : h->pending) {
-    HIPCHK(h, hipEventSynchronize(pe.b));
+  const std::vector<PendingEvent> pending = std::move(h->pending);
+  h->pending.clear();
+  for (const PendingEvent& pe : pending) {
+    HIPCHK(h, hipEventSynchronize(pe.ev.end));
     float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, pe.a, pe.b));
+    HIPCHK(h, hipEventElapsedTime(&ms, pe.ev.begin, pe.ev.end));
     mals_stats& st = h->stats;
     switch (pe.kind) {
       case 0: st.rows_ms += ms; st.rows_launches += 1; st.rows_bytes += pe.bytes; break;
@@ -278,10 +280,7 @@ int drain_events(mals_handle h) {
       case 5: st.rotate_ms += ms; st.rotate_launches += 1; st.rotate_bytes += pe.bytes; break;
       default: st.gramian_ms += ms; st.gramian_launches += 1; st.gramian_bytes += pe.bytes; break;
     }
-    (void)hipEventDestroy(pe.a);
-    (void)hipEventDestroy(pe.b);
   }
-  h->pending.clear();
   return MALS_OK;
 }
 
@@ -955,7 +954,8 @@ int mals_create(const mals_config* cfg, mals_handle* out) {
   }
   if (cfg->device < 0 || cfg->device >= n_dev)
     return create_fail(MALS_HIP_ERROR, "mals_create: device ordinal " + std::to_string(cfg->device) + " outside 0.." + std::to_string(n_dev - 1));
-  mals_handle h = new (std::nothrow) mals_handle_s();
+  std::unique_ptr<mals_handle_s> owner(new (std::nothrow) mals_handle_s());   // an error return below destroys what was built
+  const mals_handle h = owner.get();
   if (!h) return create_fail(MALS_OOM, "mals_create: out of host memory");
   h->cfg = *cfg;
   h->cfg.flags &= 3;
@@ -971,13 +971,10 @@ int mals_create(const mals_config* cfg, mals_handle* out) {
     case MALS_GRAMIAN_FP32: h->split_f16 = false; break;
     case MALS_GRAMIAN_SPLIT_F16: h->split_f16 = true; break;
     case MALS_GRAMIAN_SPLIT3_F16:
-      if (h->T != 4) {
-        delete h;
-        return create_fail(MALS_INVALID_ARG, "mals_create: MALS_GRAMIAN_SPLIT3_F16 is built for 49..64 features");
-      }
+      if (h->T != 4) return create_fail(MALS_INVALID_ARG, "mals_create: MALS_GRAMIAN_SPLIT3_F16 is built for 49..64 features");
       h->split_f16 = h->split3 = true;
       break;
-    default: delete h; return create_fail(MALS_INVALID_ARG, "mals_create: unknown gramian_mode");
+    default: return create_fail(MALS_INVALID_ARG, "mals_create: unknown gramian_mode");
   }
   // a negative alpha (accepted by the reference, ALS:506-509) has no real sqrt(alpha |r|): fp32 gather
   if (cfg->alpha < 0.0) h->split_f16 = false;
@@ -985,7 +982,7 @@ int mals_create(const mals_config* cfg, mals_handle* out) {
     case MALS_SOLVE_AUTO: h->dual_blocks = h->T >= 3 ? dual_max_blocks(h->T) : 0; break;
     case MALS_SOLVE_DIRECT: h->dual_blocks = 0; break;
     case MALS_SOLVE_DUAL: h->dual_blocks = dual_max_blocks(h->T); break;
-    default: delete h; return create_fail(MALS_INVALID_ARG, "mals_create: unknown solve_mode");
+    default: return create_fail(MALS_INVALID_ARG, "mals_create: unknown solve_mode");
   }
   if (h->cfg.flags != 0 || !(cfg->alpha > 0.0)) h->dual_blocks = 0;  // the dual path covers the default mode only
   {
@@ -1007,24 +1004,16 @@ int mals_create(const mals_config* cfg, mals_handle* out) {
   if (st == hipSuccess) st = hipMemset(h->d_refined.get(), 0, sizeof(unsigned long long));
   if (st == hipSuccess) st = hipMemset(h->d_zscale.get(), 0, 4 * sizeof(float));   // (mals_get_gather_scale before any split-precision gather: zeros)
   if (st == hipSuccess) st = hipMemset(h->d_bad.get(), 0xff, 4 * sizeof(unsigned long long));
-  if (st != hipSuccess) {
-    delete h;   // and whatever it allocated
-    return create_fail(MALS_HIP_ERROR, "mals_create: device " + std::to_string(cfg->device) + ": " + hipGetErrorString(st));
-  }
+  if (st != hipSuccess) return create_fail(MALS_HIP_ERROR, "mals_create: device " + std::to_string(cfg->device) + ": " + hipGetErrorString(st));
   if (const char* e = std::getenv("MALS_REFINE_LIMIT")) h->refine_limit = std::max(0.f, (float)std::atof(e));
-  if (hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_refine, hipEventDisableTiming) != hipSuccess) {
-    delete h;
-    return create_fail(MALS_HIP_ERROR, "mals_create: hipEventCreate failed");
-  }
+  if (h->ev_ready.ensure(hipEventDisableTiming) != hipSuccess || h->ev_refine.ensure(hipEventDisableTiming) != hipSuccess)
+    return create_fail(MALS_HIP_ERROR, "mals_create: creating the handle's events failed");
   h->lds_gather = h->cfg.features == 128;   // the LDS-staged rows / segments kernels (lds_kernels.h); MALS_LDS_GATHER=0: A/B against the register-staged ones
   if (const char* e = std::getenv("MALS_LDS_GATHER")) h->lds_gather = h->lds_gather && std::atoi(e) != 0;
   if (const char* e = std::getenv("MALS_OVERLAP")) h->overlap = std::atoi(e) != 0;
   if (h->overlap) {
-    bool ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 2 && ok; ++i)
-      ok = hipStreamCreateWithFlags(&h->aux[i], hipStreamNonBlocking) == hipSuccess &&
-           hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming) == hipSuccess;
+    bool ok = h->ev_fork.ensure(hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < 2 && ok; ++i) ok = h->aux[i].ensure() == hipSuccess && h->ev_join[i].ensure(hipEventDisableTiming) == hipSuccess;
     if (!ok) h->overlap = false;
   }
 #ifdef MALS_PROFILING
@@ -1035,7 +1024,7 @@ int mals_create(const mals_config* cfg, mals_handle* out) {
 #endif
   t_create_error.clear();
   malsi_serving_create(h);
-  *out = h;
+  *out = owner.release();
   return MALS_OK;
 }
 
@@ -1044,6 +1033,8 @@ int mals_destroy(mals_handle h) {
   (void)hipSetDevice(h->cfg.device);
   malsi_serving_stop_front(h);
   (void)hipStreamSynchronize(h->stream);
+  for (const Stream& a : h->aux)
+    if (a) (void)hipStreamSynchronize(a);
   if (h->d_trace) {  // dump the last launch's per-phase cycle stamps (profiling aid)
     std::vector<unsigned long long> t(64 * 64 * 6);
     (void)hipMemcpy(t.data(), h->d_trace.get(), t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
@@ -1059,22 +1050,8 @@ int mals_destroy(mals_handle h) {
       if (b[5] > a[5]) std::fprintf(stderr, "[trace] wave %d: %llu cycles in %llu wall ticks (100 MHz) = %.0f MHz; %.0f cycles per row\n", w, b[3] - a[3], b[5] - a[5], 100.0 * (double)(b[3] - a[3]) / (double)(b[5] - a[5]), (double)(b[3] - a[3]) / 63.0);
     }
   }
-  for (PendingEvent& pe : h->pending) {
-    (void)hipEventDestroy(pe.a);
-    (void)hipEventDestroy(pe.b);
-  }
-  if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
-  if (h->ev_refine) (void)hipEventDestroy(h->ev_refine);
-  for (int i = 0; i < 2; ++i) {
-    if (h->aux[i]) (void)hipStreamSynchronize(h->aux[i]);
-    if (h->aux[i]) (void)hipStreamDestroy(h->aux[i]);
-    if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]);
-  }
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_G) (void)hipEventDestroy(h->ev_G);
   malsi_serving_free(h);
-  delete h;   // every buffer the handle owns, with its device current
-
+  delete h;   // every buffer, event and stream the handle owns, with its device current
   return MALS_OK;
 }
 
@@ -1537,7 +1514,7 @@ static int solve_setup(mals_handle h, int side, int chunk_begin, int chunk_end, 
   if (g_to_host) {  // the Gramian goes to the host first so that its eigendecomposition runs while the direct kernels of
                     // the first chunk execute
     if (!h->h_G) HIPCHK(h, h->h_G.alloc((size_t)k * k));
-    if (!h->ev_G) HIPCHK(h, hipEventCreateWithFlags(&h->ev_G, hipEventDisableTiming));
+    HIPCHK(h, h->ev_G.ensure(hipEventDisableTiming));
     HIPCHK(h, hipMemcpyAsync(h->h_G.get(), o.G.get(), sizeof(double) * (size_t)k * k, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipEventRecord(h->ev_G, h->stream));
   }
@@ -1743,7 +1720,7 @@ int malsi_solve_chunk_end(mals_handle h, int side, int32_t chunk) {
   return solve_chunks(h, side, chunk, chunk + 1, SOLVE_END);
 }
 int malsi_dual_pending(mals_handle h) { return h && h->dual_pending ? 1 : 0; }
-void* malsi_ready_event(mals_handle h) { return h ? (void*)h->ev_ready : nullptr; }
+void* malsi_ready_event(mals_handle h) { return h ? (void*)h->ev_ready.get() : nullptr; }
 int malsi_ymax_slots(void) { return YMAX_SLOTS; }
 int malsi_dual_host(mals_handle h, int side, mals_handle from) {
   CHECK_SIDE(h, side);

@@ -118,10 +118,10 @@ struct Member {
   mals_handle h = nullptr;
   int device = 0;
   int rank = 0;
-  hipStream_t compute = nullptr, comm = nullptr;
-  hipStream_t compute2 = nullptr;   // odd chunks of a half-iteration (alternate_streams)
-  hipEvent_t ev_solved = nullptr, ev_exchanged = nullptr;
-  hipEvent_t ev_half = nullptr, ev_join = nullptr;
+  mals::Stream compute, comm;
+  mals::Stream compute2;   // odd chunks of a half-iteration (alternate_streams)
+  mals::Event ev_solved, ev_exchanged;
+  mals::Event ev_half, ev_join;
   ncclComm_t nccl = nullptr;
   mals::DeviceBuffer<double> d_gp;    // k*k: partial Gramian / all-reduce buffer
   mals::DeviceBuffer<double> d_stat;  // 4 doubles: value statistics, status
@@ -255,13 +255,13 @@ int init_member(mals_group g, Member& mb, const mals_config& cfg, int device, in
   malsi_mark_group_member(mb.h);
   mb.device = device;
   GHIP(g, hipSetDevice(device));
-  GHIP(g, hipStreamCreateWithFlags(&mb.compute, hipStreamNonBlocking));
-  GHIP(g, hipStreamCreateWithFlags(&mb.comm, hipStreamNonBlocking));
-  GHIP(g, hipStreamCreateWithFlags(&mb.compute2, hipStreamNonBlocking));
-  GHIP(g, hipEventCreateWithFlags(&mb.ev_half, hipEventDisableTiming));
-  GHIP(g, hipEventCreateWithFlags(&mb.ev_join, hipEventDisableTiming));
-  GHIP(g, hipEventCreateWithFlags(&mb.ev_solved, hipEventDisableTiming));
-  GHIP(g, hipEventCreateWithFlags(&mb.ev_exchanged, hipEventDisableTiming));
+  GHIP(g, mb.compute.ensure());
+  GHIP(g, mb.comm.ensure());
+  GHIP(g, mb.compute2.ensure());
+  GHIP(g, mb.ev_half.ensure(hipEventDisableTiming));
+  GHIP(g, mb.ev_join.ensure(hipEventDisableTiming));
+  GHIP(g, mb.ev_solved.ensure(hipEventDisableTiming));
+  GHIP(g, mb.ev_exchanged.ensure(hipEventDisableTiming));
   GHIP(g, hipEventRecord(mb.ev_exchanged, mb.comm));
   const size_t kk = (size_t)cfg.features * cfg.features;
   GHIP(g, mb.d_gp.alloc(kk));
@@ -277,15 +277,8 @@ void destroy_member(Member& mb) {
   if (mb.compute2) (void)hipStreamSynchronize(mb.compute2);
   if (mb.comm) (void)hipStreamSynchronize(mb.comm);
   if (mb.nccl && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(mb.nccl);
-  if (mb.h) (void)mals_destroy(mb.h);
-  if (mb.ev_solved) (void)hipEventDestroy(mb.ev_solved);
-  if (mb.ev_half) (void)hipEventDestroy(mb.ev_half);
-  if (mb.ev_join) (void)hipEventDestroy(mb.ev_join);
-  if (mb.compute2) (void)hipStreamDestroy(mb.compute2);
-  if (mb.ev_exchanged) (void)hipEventDestroy(mb.ev_exchanged);
-  if (mb.comm) (void)hipStreamDestroy(mb.comm);
-  if (mb.compute) (void)hipStreamDestroy(mb.compute);
-  mb = Member();   // and the member's buffers, with its device current
+  if (mb.h) (void)mals_destroy(mb.h);   // before `compute`, which it borrows
+  mb = Member();   // the member's streams, events and buffers, with its device current
 }
 
 // ---- the collectives: each stated once, with both transports (RCCL, peer copy) inside ----

@@ -94,7 +94,7 @@ struct HalfStamp {  // what a cache that is rebuilt once per half-iteration hold
 };
 
 struct PendingEvent {
-  hipEvent_t a, b;
+  EventPair ev;   // around the launch; created per timed launch (begin_timed), empty while timing is off
   int kind;  // 0 = rows, 1 = segments, 2 = finish, 3 = gramian, 4 = dual, 5 = rotate
   double bytes;
 };
@@ -134,7 +134,7 @@ struct mals_handle_s {
   float* d_lam = nullptr;     // [2][16T]: eigenvalues, 1/sqrt(L + lambda alpha)
   DeviceBuffer<unsigned> d_zbound;
   PinnedBuffer<double> h_G;   // k x k
-  hipEvent_t ev_G = nullptr;
+  Event ev_G;
   // host half of the dual preparation: the eigendecomposition of G turned into what the device half uploads, in ONE
   // pinned block (asynchronous copies straight out of it, no stream synchronisation): Q | Q^T (doubles), the same in
   // fp32, eigenvalues | 1/sqrt(L + lambda alpha), and Q / Q^T as split-f16 B operands
@@ -153,7 +153,7 @@ struct mals_handle_s {
   // once, in its first chunk (operand scale, padded / permuted images, the rotated copy of the dual path), is enqueued
   // behind it -- a later chunk on the OTHER stream waits for it; ev_refine serialises the chunks' refinement blocks
   // (gramian_ref_kernel's arrival ticket assumes one launch at a time)
-  hipEvent_t ev_ready = nullptr, ev_refine = nullptr;
+  Event ev_ready, ev_refine;
   bool refine_recorded = false;
   mals_iteration_fn iter_fn = nullptr;   // mals_set_iteration_callback
   void* iter_user = nullptr;
@@ -168,7 +168,7 @@ struct mals_handle_s {
   DeviceBuffer<int> d_colrange;
   int n_cu = 256;
   SideState side[2];
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;   // borrowed (mals_set_stream), or the null stream
   // The three independent parts of a chunk -- rows list, long rows (segments + finish), dual lists (rotation + dual
   // kernels) -- are enqueued on three streams between a fork and a join event: the small launches (a few hundred
   // workgroups: the long rows of C2, the dual classes, the rotations) fill the slots the rows kernel's tail leaves
@@ -176,8 +176,8 @@ struct mals_handle_s {
   // 2.18 ms, C4 81.8 -> 80.6, C5 rank 168.8 -> 165.3, C3 14.8 -> 15.3 (worse: its long rows then fight the rows
   // kernel for the cache-resident table) -- 1-2 %, and every per-kernel HIP-event time (the roofline figures of
   // mals_stats) then includes the other streams' contention.  So: OFF unless MALS_OVERLAP=1.
-  hipStream_t aux[2] = {nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
+  Stream aux[2];
+  Event ev_fork, ev_join[2];
   bool overlap = false;
   bool forked[2] = {false, false};
   std::string err;

@@ -10,8 +10,8 @@ constexpr int TOPN_SLOTS = 6;  // passes in flight, each on its own stream (3 ->
 // beside it instead of in its shadow -- serialised on one stream they and the launch gaps between them were two thirds
 // of a pass.
 struct TopnSlot {
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;
+  Stream stream;
+  Event ev;
   // inputs of the pass: ONE device block, the image of the slot's pinned block (one copy); the pointers below are views
   // into it
   DeviceBuffer<uint8_t> d_in;
@@ -39,7 +39,7 @@ struct TopnSlot {
 
 struct TopnWorkspace {
   TopnSlot slot[TOPN_SLOTS];
-  hipEvent_t ev_begin = nullptr;  // the caller's stream at the start of the call: every slot stream waits for it
+  Event ev_begin;  // the caller's stream at the start of the call: every slot stream waits for it
   // dense path
   DeviceBuffer<float> d_scores;
   DeviceBuffer<uint32_t> d_sel;
@@ -50,13 +50,9 @@ struct TopnWorkspace {
 void topn_free(mals_handle h) {
   TopnWorkspace* w = h->serving->tn_ws;
   if (!w) return;
-  for (TopnSlot& s : w->slot) {
+  for (TopnSlot& s : w->slot)
     if (s.stream) (void)hipStreamSynchronize(s.stream);
-    if (s.ev) (void)hipEventDestroy(s.ev);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-  }
-  if (w->ev_begin) (void)hipEventDestroy(w->ev_begin);
-  delete w;   // and its buffers
+  delete w;   // its buffers, events and streams
   h->serving->tn_ws = nullptr;
 }
 
@@ -674,10 +670,10 @@ bool topn_dense_only(mals_handle h, int how_many, const mals_rescorer_s* r = nul
 // streams, events and pinned result blocks of the slots; every slot stream ordered after the work already on the handle's
 int topn_prepare_slots(mals_handle h, TopnWorkspace* w) {
   for (TopnSlot& sl : w->slot) {
-    if (!sl.stream) HIPCHK(h, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-    if (!sl.ev) HIPCHK(h, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    HIPCHK(h, sl.stream.ensure());
+    HIPCHK(h, sl.ev.ensure(hipEventDisableTiming));
   }
-  if (!w->ev_begin) HIPCHK(h, hipEventCreateWithFlags(&w->ev_begin, hipEventDisableTiming));
+  HIPCHK(h, w->ev_begin.ensure(hipEventDisableTiming));
   return MALS_OK;
 }
 

@@ -1,6 +1,7 @@
 """Device memory the native library allocates is released: on an error return (an allocation that fails halfway through
 a growth leaves nothing behind) and at the end of every object's life (create / use / destroy cycles of a handle, an
-ingest and a group come back to the free memory they started from).  Free memory is read with torch.cuda.mem_get_info
+ingest and a group come back to the free memory they started from; a handle destroyed with the events of timed launches
+still pending).  Free memory is read with torch.cuda.mem_get_info
 while no torch tensor is alive; the tolerance is 1 GiB because the device may be shared."""
 import numpy as np
 import pytest
@@ -87,6 +88,59 @@ def group_cycle(devices, seed):
         g.set_matrix(pkg.SIDE_Y, *c_csr)
         g.set_factors(pkg.SIDE_Y, Y0)
         g.iterate(2)
+
+
+def timed_handle(problem):
+    """A handle with timing on after two half-iterations: every timed launch's pair of events is on its pending list.
+    48 features: the dual path is on by default; segment_nnz=64: two item rows are long (segments + finish)."""
+    r_csr, c_csr, Y0 = problem
+    core = pkg.ALSCore(48, segment_nnz=64)
+    try:
+        core.set_factor_rows(pkg.SIDE_X, len(r_csr[0]) - 1)
+        core.set_factor_rows(pkg.SIDE_Y, len(c_csr[0]) - 1)
+        core.set_matrix(pkg.SIDE_X, *r_csr)
+        core.set_matrix(pkg.SIDE_Y, *c_csr)
+        core.set_factors(pkg.SIDE_Y, Y0)
+        core.enable_timing(True)
+        core.half_iteration(pkg.SIDE_X)
+        core.half_iteration(pkg.SIDE_Y)
+    except BaseException:
+        core.close()
+        raise
+    return core
+
+
+@pytest.mark.parametrize("overlap", [None, "1"], ids=["one-stream", "overlap"])
+def test_timed_launches_pending_at_destroy_and_drained_twice(overlap):
+    """The events of timed launches belong to the handle's pending list until the statistics are read: (a) a handle closed
+    with the list full destroys them (no test read the statistics last before), (b) reading the statistics twice drains the
+    list once -- the second read finds it empty and changes nothing.  With MALS_OVERLAP=1 the handle also owns its two
+    auxiliary streams with their fork and join events."""
+    import os
+    n_users, n_items = 96, 64
+    problem = synth.numpy_problem(n_users, n_items, 3000, 48, seed=5)   # 1542 entries
+    assert int((np.diff(problem[1][0]) > 64).sum()) == 2, "two long item rows"
+    saved = os.environ.pop("MALS_OVERLAP", None)
+    if overlap is not None:
+        os.environ["MALS_OVERLAP"] = overlap
+    try:
+        timed_handle(problem).close()   # warm-up: code objects, runtime state
+        base = free_bytes([0])
+        timed_handle(problem).close()   # (a)
+        with timed_handle(problem) as core:   # (b)
+            first = core.stats()
+            second = core.stats()
+    finally:
+        os.environ.pop("MALS_OVERLAP", None)
+        if saved is not None:
+            os.environ["MALS_OVERLAP"] = saved
+    print("overlap=%s: %s" % (overlap, first))
+    assert first["rows_launches"] > 0 and first["segments_launches"] > 0 and first["finish_launches"] > 0 and first["dual_launches"] > 0, first
+    assert first["rows_solved"] == n_users + n_items, first
+    assert list(first) == list(second)
+    for name in first:
+        assert first[name] == second[name], (name, first[name], second[name])
+    assert_back_at(base, "timed handles, overlap=%s" % overlap)
 
 
 def test_create_use_destroy_cycles_return_to_the_baseline():
