@@ -456,13 +456,42 @@ int mals_lsh_signatures(mals_handle h, const float* vectors, int32_t n, uint64_t
  * fp32 products / squares, fp64 sums in feature order; the product of the norms first, then the division) -- bit-identical;
  * n counts duplicates.  Skipped: tag items (:77), the query's own items (:81-85), items with a non-finite s_j (:104: a
  * zero or NaN row, or a query item of zero norm, gives fewer results, never an error).  The how_many best come back best
- * first, ties in ascending item index; padding -1 / -inf; n_out (may be NULL): results per query.  Rescorers and mapping IDs
- * to indices stay with the caller.  An index outside [0, rows of Y) is MALS_INVALID_ARG; how_many in 1..4096.  The same
+ * first, ties in ascending item index; padding -1 / -inf; n_out (may be NULL): results per query.  Mapping IDs to indices
+ * stays with the caller; a Rescorer<LongPair> is mals_most_similar_items_rescored, below.  An index outside [0, rows of Y) is MALS_INVALID_ARG; how_many in 1..4096.  The same
  * filter as mals_recommend (a bf16 MFMA pass with a proven cosine margin, then the exact rescore; csrc/topn_kernels.h)
  * over the resident Y.  Threads: as mals_recommend* (any number of request threads, together with recommend calls); calls
  * of fewer than 64 queries are folded into passes of their own kind, larger ones run exclusively. */
 int mals_most_similar_items(mals_handle h, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
                             int64_t* item_idx_out, float* score_out, int32_t* n_out);
+/* mostSimilarItems(long[] itemIDs, int howMany, Rescorer<LongPair> rescorer) (ServerRecommender.java:1180-1265, scored by
+ * MostSimilarItemIterator.java:87-117) with a mals_rescorer (above) as the pair rescorer.  For the pair (candidate c, query
+ * item q_j):
+ *     isFiltered(pair) = c is in the filter set F; with MALS_SIMILAR_FILTER_QUERY_ITEMS in `flags` also q_j in F -- "either
+ *         end of the pair", the shape of FilterHalfRescorerProvider.getMostSimilarItemsRescorer.  A query with a filtered query
+ *         item then comes back empty (n_out = 0), which is no error;
+ *     rescore(pair, s) = fl(fl(scale_c * s) + offset_c)   (fp64, no contraction)
+ * Per candidate, in the order of MostSimilarItemIterator.next(): 1. tag items are struck (:77); 2. the query's own items are
+ * struck (:81-85); 3. for each query item j in order: a filtered pair skips the candidate; s_j = the cosine of
+ * mals_most_similar_items, not finite skips the candidate; r_j = rescore(pair, s_j), not finite skips the candidate (:109),
+ * never an error; total += r_j; 4. the result is (float)(total / n).  A result that is not finite fails THAT CALL with
+ * MALS_INVALID_ARG, "Bad similarity value" (checkState, :117); the other calls folded into the same pass are answered as if
+ * alone.  The rescore is PER TERM -- unlike mals_recommend_rescored, where it acts on the sum before the division: with n >= 2
+ * query items the offset is added n times and divided once, so the mean is scale_c * mean(s_j) + offset_c up to rounding, with
+ * no 1 / n on the offset.  Ties in ascending item index, padding -1 / -inf, how_many in 1..4096, as mals_most_similar_items.
+ * r = NULL is exactly mals_most_similar_items (same kernels, same bits); a rescorer bound to another handle is
+ * MALS_INVALID_ARG.  Threads: a ticket of the serving front like the other rescored calls; calls with the same rescorer, flags
+ * and how_many and fewer than 64 queries fold into passes of their own, different rescorers never share a pass, and
+ * mals_rescorer_set_* stays an exclusive ticket: a call sees the rescorer as it was when queued.  The filter path runs for
+ * rescorers whose unfiltered weights lie in scale [2^-20, 2^20], |offset| <= 2^6 * scale (csrc/topn_kernels.h, RESCORED COSINE
+ * MODE: the bound), up to four items outside that range allowed (candidates of every query; the exact rescore decides); any
+ * other rescorer is answered exactly by the dense path, one call at a time.  Not for members of a group.
+ * mals_similar_stats: out4 = {mostSimilarItems queries answered by the filter path, ... by the dense path (the fallbacks of a
+ * filter pass included), ... answered empty by a filter pass before scoring (a dead or a filtered query item), the rescored
+ * queries among all of these} since mals_create; plain and rescored calls both count; read without a ticket. */
+enum { MALS_SIMILAR_FILTER_QUERY_ITEMS = 1 };
+int mals_most_similar_items_rescored(mals_handle h, mals_rescorer r, int32_t flags, const int64_t* item_idx, const int64_t* item_ptr,
+                                     int32_t n_queries, int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out);
+int mals_similar_stats(mals_handle h, int64_t* out4);
 /* ServerRecommender.similarityToItem (ServerRecommender.java:1268-1304): out[j] = (float)(dot(Y_ij, Y_to) / (norm(Y_ij) *
  * norm(Y_to))) for the n items item_idx[j]; NaN is returned as NaN (no skip, no exclusion). */
 int mals_similarity_to_item(mals_handle h, int64_t to_item, const int64_t* item_idx, int32_t n, float* out);

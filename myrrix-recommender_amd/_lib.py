@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("MALS_LIB") or os.path.join(_HERE, "csrc", "libmyrrix_
 OK, SINGULAR, INVALID_ARG, HIP_ERROR, COMM_ERROR, CANCELLED, OOM, ILL_CONDITIONED, IO_ERROR = range(9)
 SIDE_X, SIDE_Y = 0, 1
 FLAG_RECONSTRUCT_R, FLAG_LOSS_IGNORES_UNSPECIFIED = 1, 2
+SIMILAR_FILTER_QUERY_ITEMS = 1   # MALS_SIMILAR_FILTER_QUERY_ITEMS
 MEM_HOST, MEM_DEVICE = 0, 1
 GRAMIAN_AUTO, GRAMIAN_FP32, GRAMIAN_SPLIT_F16, GRAMIAN_SPLIT3_F16 = 0, 1, 2, 3
 SOLVE_AUTO, SOLVE_DIRECT, SOLVE_DUAL = 0, 1, 2
@@ -174,6 +175,8 @@ SYMBOLS = {
     "mals_recommend_set_depth": (ctypes.c_int, [_H, _I32]),
     "mals_recommend_set_spin_us": (ctypes.c_int, [_H, _I32]),
     "mals_most_similar_items": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
+    "mals_most_similar_items_rescored": (ctypes.c_int, [_H, _H, _I32, _P, _P, _I32, _I32, _P, _P, _P]),
+    "mals_similar_stats": (ctypes.c_int, [_H, _P]),
     "mals_similarity_to_item": (ctypes.c_int, [_H, ctypes.c_int64, _P, _I32, _P]),
     "mals_recommended_because": (ctypes.c_int, [_H, _P, _P, _I32, _I32, _P, _P, _P]),
     "mals_set_foldin_solver": (ctypes.c_int, [_H, ctypes.c_int, _H]),

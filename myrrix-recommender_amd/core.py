@@ -682,18 +682,32 @@ class ALSCore:
             self._chk(self._L.mals_recommend_to_many_rescored(self._h, rescorer.handle, *args))
         return idx, sc, cnt
 
-    def most_similar_items(self, items, how_many):
+    def most_similar_items(self, items, how_many, rescorer=None, filter_query_items=False):
         """mostSimilarItems (ServerRecommender.java:1171-1266): items = a sequence of item indices (one item per query) or a
         list of sequences (several items per query); the score is the mean cosine to the query's items
-        (MostSimilarItemIterator.java:73-120).  Returns (item_idx [q][how_many] int64, scores float32, counts)."""
+        (MostSimilarItemIterator.java:73-120).  Returns (item_idx [q][how_many] int64, scores float32, counts).
+        rescorer: a Rescorer of this handle used as the Rescorer<LongPair> (None: none): a candidate in its filter set is
+        skipped -- with filter_query_items also every candidate of a query that has a filtered query item ("either end of the
+        pair") -- and every cosine is rescored scale_c * s + offset_c before the mean."""
         flat, ptr = _item_queries(items)
         idx = np.empty((len(ptr) - 1, how_many), dtype=np.int64)
         sc = np.empty((len(ptr) - 1, how_many), dtype=np.float32)
         cnt = np.empty(len(ptr) - 1, dtype=np.int32)
-        self._chk(self._L.mals_most_similar_items(self._h, flat.ctypes.data_as(ctypes.c_void_p), ptr.ctypes.data_as(ctypes.c_void_p),
-                                                  len(ptr) - 1, int(how_many), idx.ctypes.data_as(ctypes.c_void_p),
-                                                  sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        args = (flat.ctypes.data_as(ctypes.c_void_p), ptr.ctypes.data_as(ctypes.c_void_p), len(ptr) - 1, int(how_many),
+                idx.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p))
+        if rescorer is None:
+            self._chk(self._L.mals_most_similar_items(self._h, *args))
+        else:
+            flags = _lib.SIMILAR_FILTER_QUERY_ITEMS if filter_query_items else 0
+            self._chk(self._L.mals_most_similar_items_rescored(self._h, rescorer.handle, flags, *args))
         return idx, sc, cnt
+
+    def similar_stats(self):
+        """{filter, dense, empty, rescored}: mostSimilarItems queries answered by the filter path, by the dense path, answered
+        empty by a filter pass before scoring, and the rescored ones among them, since the handle was created."""
+        o = np.zeros(4, dtype=np.int64)
+        self._chk(self._L.mals_similar_stats(self._h, o.ctypes.data_as(ctypes.c_void_p)))
+        return {"filter": int(o[0]), "dense": int(o[1]), "empty": int(o[2]), "rescored": int(o[3])}
 
     def similarity_to_item(self, to_item, items):
         """similarityToItem (ServerRecommender.java:1268-1304): the cosine of every item to to_item, NaN as NaN."""

@@ -77,6 +77,7 @@ struct RescorerState {
   DeviceBuffer<uint4> d_fdata;
   TopnRescore args;
   bool filter_ok = true;                 // every weight inside the filter's range (topn_kernels.h), else the dense path answers
+  bool cos_filter_ok = true;             // ... inside the narrower range of RESCORED COSINE MODE (mals_most_similar_items_rescored)
 };
 struct mals_rescorer_s {
   mals_handle h = nullptr;
@@ -85,6 +86,7 @@ struct mals_rescorer_s {
 
 namespace {
 bool rescorer_filter_ok(const mals_rescorer_s* r) { return r->st->filter_ok; }
+bool rescorer_cos_filter_ok(const mals_rescorer_s* r) { return r->st->cos_filter_ok; }
 void rescorer_bind(const mals_rescorer_s* r, std::shared_ptr<const RescorerState>& keep, TopnRescore& args) {
   keep = r->st;
   args = keep->args;
@@ -333,9 +335,12 @@ static int topn_check_items(mals_handle h, const int64_t* idx, int64_t n) {
   return MALS_OK;
 }
 
-static int topn_most_similar_once(mals_handle h, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
-                            int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+static int topn_most_similar_once(mals_handle h, mals_rescorer r, int32_t flags, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries,
+                                  int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
   if (!h) return MALS_INVALID_ARG;
+  if (r && r->h != h) return topn_fail(h, MALS_INVALID_ARG, "the rescorer belongs to another handle");
+  if (flags & ~MALS_SIMILAR_FILTER_QUERY_ITEMS) return topn_fail(h, MALS_INVALID_ARG, "unknown mostSimilarItems flags");
+  if (r && h->group_member) return topn_fail(h, MALS_INVALID_ARG, "rescorers are not available on the members of a group");
   SideState& y = h->side[MALS_SIDE_Y];
   if (!y.F || y.n_total == 0) return topn_fail(h, MALS_INVALID_ARG, "item factor replica not available");
   if (n_queries < 0 || how_many <= 0 || how_many > 4096 || (n_queries > 0 && (!item_idx || !item_idx_out || !score_out)))
@@ -367,12 +372,23 @@ static int topn_most_similar_once(mals_handle h, const int64_t* item_idx, const 
   rq.item_idx_out = item_idx_out;
   rq.score_out = score_out;
   rq.n_out = n_out;
-  // a small call is folded into a pass with other callers' mostSimilarItems calls
+  rq.rescorer = r;
+  rq.flags = r ? flags : 0;   // (without a rescorer no pair is filtered: the plain call, whatever the flags)
+  // a small call is folded into a pass with other callers' mostSimilarItems calls (of the same rescorer and flags)
   return topn_front_submit(h, rq, n_queries < TOPN_FRONT_BULK && how_many <= TOPN_FILTER_MAX_N && item_ptr[n_queries] <= 4 * TOPN_FRONT_BULK);
 }
 int mals_most_similar_items(mals_handle h, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries, int32_t how_many,
                             int64_t* item_idx_out, float* score_out, int32_t* n_out) {
-  return topn_generation_guard(h, [&]() -> int { return topn_most_similar_once(h, item_idx, item_ptr, n_queries, how_many, item_idx_out, score_out, n_out); });
+  return topn_generation_guard(h, [&]() -> int { return topn_most_similar_once(h, nullptr, 0, item_idx, item_ptr, n_queries, how_many, item_idx_out, score_out, n_out); });
+}
+int mals_most_similar_items_rescored(mals_handle h, mals_rescorer r, int32_t flags, const int64_t* item_idx, const int64_t* item_ptr, int32_t n_queries,
+                                     int32_t how_many, int64_t* item_idx_out, float* score_out, int32_t* n_out) {
+  return topn_generation_guard(h, [&]() -> int { return topn_most_similar_once(h, r, flags, item_idx, item_ptr, n_queries, how_many, item_idx_out, score_out, n_out); });
+}
+int mals_similar_stats(mals_handle h, int64_t* out4) {
+  if (!h || !out4) return MALS_INVALID_ARG;
+  for (int i = 0; i < 4; ++i) out4[i] = topn_front(h)->similar[i].load(std::memory_order_relaxed);
+  return MALS_OK;
 }
 
 static int topn_similarity_to_once(mals_handle h, int64_t to_item, const int64_t* item_idx, int32_t n, float* out) {
@@ -984,7 +1000,7 @@ float rescorer_bf16_value(uint16_t b) {
   return f;
 }
 // the filter's 16 bytes of one item (topn_kernels.h)
-uint4 rescorer_fdata(double s, double o, bool filtered) {
+uint4 rescorer_fdata(double s, double o, bool filtered, bool wild = false) {
   if (filtered) {
     const float nan = std::numeric_limits<float>::quiet_NaN();
     uint32_t z;
@@ -997,7 +1013,7 @@ uint4 rescorer_fdata(double s, double o, bool filtered) {
   const float sf = (float)s;
   uint32_t z;
   std::memcpy(&z, &sf, 4);
-  return make_uint4((uint32_t)rh | ((uint32_t)rl << 16), (uint32_t)oh | ((uint32_t)ol << 16), z, 0u);
+  return make_uint4((uint32_t)rh | ((uint32_t)rl << 16), (uint32_t)oh | ((uint32_t)ol << 16), z, wild ? TOPN_FDATA_WILD : 0u);
 }
 bool rescorer_in_range(double s, double o) {
   return s >= 1.0 / TOPN_RS_MAX_SCALE && s <= TOPN_RS_MAX_SCALE && std::fabs(o) <= TOPN_RS_MAX_OFFSET;
@@ -1009,13 +1025,17 @@ int rescorer_upload(mals_handle h, RescorerState& st) {
   std::vector<uint32_t> bits((size_t)((n_filt + 31) / 32), 0u);
   for (int64_t i : st.filt_idx) bits[(size_t)(i >> 5)] |= 1u << (i & 31);
   st.filter_ok = rescorer_in_range(st.us, st.uo);
+  st.cos_filter_ok = topn_cos_rs_in_range(st.us, st.uo);
   std::vector<uint4> fd((size_t)n_f);
+  int64_t n_wild = 0;
   for (int64_t i = 0; i < n_f; ++i) {
     const bool arr = i < st.n_rows;
     const double s = arr && !st.scale.empty() ? st.scale[(size_t)i] : st.us, o = arr && !st.offset.empty() ? st.offset[(size_t)i] : st.uo;
     const bool f = i < n_filt && ((bits[(size_t)(i >> 5)] >> (i & 31)) & 1u);
     if (!f && !rescorer_in_range(s, o)) st.filter_ok = false;
-    fd[(size_t)i] = rescorer_fdata(s, o, f);
+    const bool wild = !f && !topn_cos_rs_in_range(s, o);   // rescored cosine mode: a candidate of every query, up to a few of them
+    if (wild && ++n_wild > TOPN_COS_RS_MAX_WILD) st.cos_filter_ok = false;
+    fd[(size_t)i] = rescorer_fdata(s, o, f, wild);
   }
   TopnRescore& a = st.args;
   a = TopnRescore();

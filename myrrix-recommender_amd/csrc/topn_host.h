@@ -94,11 +94,15 @@ struct TopnRequest {
   // state it had when the call's turn came: a mals_rescorer_set_* is an exclusive ticket of the front)
   const mals_rescorer_s* rescorer = nullptr;
   const TopnRescore* rs = nullptr;
+  // mals_most_similar_items_rescored (cosine with a rescorer): MALS_SIMILAR_* of the call, how the pair rescorer reads its filter
+  int32_t flags = 0;
   // per query: 1 = its result is not finite (RecommendIterator.java:105) -- the query's caller fails, the others are answered.
   // NULL: the whole request fails
   uint8_t* bad_q = nullptr;
 };
 constexpr const char* TOPN_BAD_VALUE = "Bad recommendation value: a non-finite score (non-finite factors; RecommendIterator.java:105 throws IllegalStateException)";
+constexpr const char* TOPN_BAD_SIMILARITY = "Bad similarity value: a non-finite rescored similarity (MostSimilarItemIterator.java:117 throws IllegalStateException)";
+inline const char* topn_bad_value(const TopnRequest& rq) { return rq.cosine ? TOPN_BAD_SIMILARITY : TOPN_BAD_VALUE; }
 enum { TOPN_KIND_SCORE = 0, TOPN_KIND_BECAUSE = 1, TOPN_KIND_SIMILARITY_TO = 2, TOPN_KIND_CALL = 3 };
 
 inline TopnOut topn_out(const TopnRequest& rq, size_t qq) {
@@ -234,12 +238,13 @@ TopnVariant topn_variant(mals_handle h, const TopnRequest& rq) {
   return {rq.cosine, rq.rs != nullptr, h->lsh.H > 0 && rq.kind == TOPN_KIND_SCORE && !rq.cosine};
 }
 
-// f(COS, RS, LSH) with the variant as std::bool_constants: the five combinations the library is built for
+// f(COS, RS, LSH) with the variant as std::bool_constants: the six combinations the library is built for
 template <class F>
 auto topn_dispatch(const TopnVariant& v, F&& f) {
-  assert(!(v.cos && (v.rs || v.lsh)));   // no entry point takes a rescorer for a cosine call, none of them consults the filter
+  assert(!(v.cos && v.lsh));   // no cosine call consults the candidate filter (the reference passes none to similarity)
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
+  if (v.cos && v.rs) return f(yes, yes, no);
   if (v.cos) return f(yes, no, no);
   if (v.rs && v.lsh) return f(no, yes, yes);
   if (v.rs) return f(no, yes, no);
@@ -252,10 +257,11 @@ struct TopnVariantArgs {
   uint32_t* qflag;          // cosine: the per-query flags of topn_prepare_kernel<true>, else NULL
   TopnRescore rs;           // rescored: what the pass reads of the rescorer, else the identity
   TopnImgTrailer trailer;   // rescored: the items' filter data behind the query image, else none
+  int pair_flags;           // rescored cosine: TOPN_PAIR_* (= the call's MALS_SIMILAR_* flags), else 0
 };
 // (after the pass's sl.d_qn has its size: the pointer is taken here)
 TopnVariantArgs topn_variant_args(const TopnVariant& v, const TopnSlot& sl, const TopnRequest& rq) {
-  TopnVariantArgs a{nullptr, nullptr, TopnRescore(), TopnImgTrailer()};
+  TopnVariantArgs a{nullptr, nullptr, TopnRescore(), TopnImgTrailer(), 0};
   if (v.cos) {
     a.qn = sl.d_qn.get();
     a.qflag = sl.d_qflag.get();
@@ -263,9 +269,15 @@ TopnVariantArgs topn_variant_args(const TopnVariant& v, const TopnSlot& sl, cons
   if (v.rs) {
     a.rs = *rq.rs;
     a.trailer = TopnImgTrailer{rq.rs->fdata, rq.rs->n_fdata, rq.rs->fdef};
+    if (v.cos) a.pair_flags = a.rs.pair_flags = rq.flags;
   }
   return a;
 }
+
+// mals_similar_stats: which path answered the queries of mostSimilarItems calls (plain and rescored), counted where a pass
+// decides it per query.  A query the filter hands to the dense path counts there only.
+enum { TOPN_SIMILAR_FILTER = 0, TOPN_SIMILAR_DENSE = 1, TOPN_SIMILAR_EMPTY = 2, TOPN_SIMILAR_RESCORED = 3 };
+void topn_similar_count(mals_handle h, int which, int n, bool rescored);
 
 // the known-items CSR of a handle: knownItemIDs if the caller installed them, else the rows of R
 struct TopnKnown {
@@ -328,6 +340,7 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
   if (!w->d_hist.get()) HIPCHK(h, w->d_hist.alloc(256 * TOPN_MAX_QUERIES));
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_items + 63) / 64, (int64_t)h->n_cu * 8));
   const TopnVariant v = topn_variant(h, rq);
+  if (v.cos && rq.kind == TOPN_KIND_SCORE) topn_similar_count(h, TOPN_SIMILAR_DENSE, nq, v.rs);
   if (v.cos) {
     HIPCHK(h, sl.d_qn.reserve((size_t)std::max<int64_t>(ps.n_vecs, 1), h->stream));
     hipLaunchKernelGGL(topn_qnorm_kernel, dim3((unsigned)((ps.n_vecs + 63) / 64)), dim3(64), 0, h->stream, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs, k,
@@ -389,7 +402,7 @@ int topn_pass_dense(mals_handle h, TopnWorkspace* w, TopnSlot& sl, const TopnReq
     }
     const TopnOut o_q = topn_out(rq, (size_t)(ps.q0 + q));
     if (!topn_emit(cand, how_many, o_q.items, o_q.scores, o_q.n)) {
-      if (!rq.bad_q) return fail(h, MALS_INVALID_ARG, TOPN_BAD_VALUE);
+      if (!rq.bad_q) return fail(h, MALS_INVALID_ARG, topn_bad_value(rq));
       rq.bad_q[ps.q0 + q] = 1;   // this query's caller fails; the rest of the pass is answered
     }
   }
@@ -561,7 +574,7 @@ int topn_pass_filter_launch(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
     hipLaunchKernelGGL(topn_qnorm_kernel, dim3((unsigned)((ps.n_vecs + 63) / 64)), dim3(64), 0, st, sl.d_vecs, sl.d_vrow, (int)ps.n_vecs, k, sl.d_qn.get());
   topn_dispatch(v, [&](auto COS, auto RS, auto) {
     hipLaunchKernelGGL((topn_prepare_kernel<COS, RS>), dim3(16), dim3(256), 0, st, sl.d_vecs, sl.d_vrow, sl.d_vptr, nq, k, p.S, sl.d_img.get(),
-                       sl.d_count.get(), topn_overflow_word(sl), va.qn, va.qflag, va.trailer);
+                       sl.d_count.get(), topn_overflow_word(sl), va.qn, va.qflag, va.trailer, va.pair_flags);
   });
   // the candidate filter: the signatures of the pass's vectors, and the pass's view of the filter behind the query image
   TopnLsh lv;
@@ -627,7 +640,8 @@ int topn_pass_filter_finish(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
   const unsigned* count = o.count();
   const float* tau = o.tau();
   const unsigned wave_overflow = *o.overflow();
-  const bool lsh = topn_variant(h, rq).lsh;
+  const TopnVariant v = topn_variant(h, rq);
+  const bool lsh = v.lsh;
   failed.assign((size_t)ps.nq, 0);
   *any_failed = false;
   for (int q = 0; q < ps.nq; ++q)
@@ -652,19 +666,22 @@ int topn_pass_filter_finish(mals_handle h, TopnSlot& sl, const TopnRequest& rq, 
     }
     if (o_q.n) *o_q.n = n;
     if (lsh) h->lsh.q_filter.fetch_add(1);
+    // (cosine: a query with a dead or filtered query item comes back with the threshold no candidate reaches)
+    if (v.cos) topn_similar_count(h, tau[q] == TOPN_COS_DEAD_TAU ? TOPN_SIMILAR_EMPTY : TOPN_SIMILAR_FILTER, 1, v.rs);
     // (rescored mode: a result that is not finite comes back as THE NaN, ranked first -- RecommendIterator.java:105)
     if (n > 0 && !std::isfinite(o_q.scores[0])) {
-      if (!rq.bad_q) return fail(h, MALS_INVALID_ARG, TOPN_BAD_VALUE);
+      if (!rq.bad_q) return fail(h, MALS_INVALID_ARG, topn_bad_value(rq));
       rq.bad_q[ps.q0 + q] = 1;
     }
   }
   return MALS_OK;
 }
 
-bool topn_dense_only(mals_handle h, int how_many, const mals_rescorer_s* r = nullptr) {
+bool topn_dense_only(mals_handle h, int how_many, const mals_rescorer_s* r = nullptr, bool cosine = false) {
   const int64_t n_items = h->side[MALS_SIDE_Y].n_total;
+  // (a rescorer outside the filter's range -- RESCORED MODE's, or RESCORED COSINE MODE's for a cosine call: topn_kernels.h)
   return n_items < 131072 || n_items >= 0xffffffffll || how_many > TOPN_FILTER_MAX_N || n_items / 16 < 64 * (int64_t)how_many ||
-         std::getenv("MALS_TOPN_FULL") || (r && !rescorer_filter_ok(r));   // (a rescorer outside the filter's range: topn_kernels.h)
+         std::getenv("MALS_TOPN_FULL") || (r && !(cosine ? rescorer_cos_filter_ok(r) : rescorer_filter_ok(r)));
 }
 
 // streams, events and pinned result blocks of the slots; every slot stream ordered after the work already on the handle's
@@ -810,7 +827,7 @@ int topn_run(mals_handle h, const TopnRequest& rq) {
   if (rq.kind == TOPN_KIND_BECAUSE) return topn_because_run(h, w, rq);
   if (rq.kind == TOPN_KIND_SIMILARITY_TO) return topn_similarity_to_run(h, rq);
   if (rq.kind == TOPN_KIND_CALL) return (*rq.call)();
-  if (topn_dense_only(h, rq.how_many, rq.rescorer)) {
+  if (topn_dense_only(h, rq.how_many, rq.rescorer, rq.cosine)) {
     for (int q0 = 0; q0 < rq.n_queries; q0 += TOPN_MAX_QUERIES) {
       TopnPass ps;
       ps.q0 = q0;
@@ -950,6 +967,7 @@ struct TopnFrontPass {
 };
 
 struct TopnFront {
+  std::atomic<int64_t> similar[4] = {};   // mals_similar_stats (TOPN_SIMILAR_*), read without a ticket
   std::mutex mu;
   std::deque<TopnTicket*> queue;
   bool leader = false;
@@ -972,6 +990,11 @@ struct TopnFront {
 constexpr int TOPN_RETRY = -1000;   // internal: never leaves the library
 
 TopnFront* topn_front(mals_handle h) { return h->serving->tn_front; }
+void topn_similar_count(mals_handle h, int which, int n, bool rescored) {
+  TopnFront* f = topn_front(h);
+  f->similar[which].fetch_add(n, std::memory_order_relaxed);
+  if (rescored) f->similar[TOPN_SIMILAR_RESCORED].fetch_add(n, std::memory_order_relaxed);
+}
 
 struct TopnGenStamp {
   mals_handle h = nullptr;
@@ -1036,7 +1059,7 @@ void topn_front_complete(TopnFrontPass& fp, int rc, const std::string& err) {  /
         if (fp.bad[q]) trc = MALS_INVALID_ARG;
     q0 += (size_t)t->rq.n_queries;
     t->rc = trc;
-    if (trc != MALS_OK) t->err = rc != MALS_OK ? err : std::string(TOPN_BAD_VALUE);
+    if (trc != MALS_OK) t->err = rc != MALS_OK ? err : std::string(topn_bad_value(t->rq));
     t->done = true;
     if (!t->is_leader) ++waiting;
   }
@@ -1121,7 +1144,7 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
   };
   while (!me->done) {
     TopnTicket* head = f->queue.empty() ? nullptr : f->queue.front();
-    if (head && (!head->fold || topn_dense_only(h, head->rq.how_many, head->rq.rescorer))) {
+    if (head && (!head->fold || topn_dense_only(h, head->rq.how_many, head->rq.rescorer, head->rq.cosine))) {
       // a request that is passes of its own (or a catalogue the dense path answers): alone on the workspace, as it is
       while (f->n_busy > 0) finish_oldest();
       if (me->done && head != me) break;   // (own answer arrived while draining: let the successor run it)
@@ -1159,7 +1182,7 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
       while (!f->queue.empty()) {
         TopnTicket* t = f->queue.front();
         const TopnRequest& r = t->rq;
-        if (!t->fold || r.how_many != how_many || kind_of(t) != kind || r.rescorer != head->rq.rescorer || (int)fp.outs.size() + r.n_queries > cap) break;
+        if (!t->fold || r.how_many != how_many || kind_of(t) != kind || r.rescorer != head->rq.rescorer || r.flags != head->rq.flags || (int)fp.outs.size() + r.n_queries > cap) break;
         f->queue.pop_front();
         fp.tickets.push_back(t);
         for (int q = 0; q < r.n_queries; ++q) {
@@ -1207,6 +1230,7 @@ void topn_front_lead(mals_handle h, TopnFront* f, std::unique_lock<std::mutex>& 
       fp.rq.out_q = fp.outs.data();
       if (head->rq.rescorer) {
         fp.rq.rescorer = head->rq.rescorer;
+        fp.rq.flags = head->rq.flags;
         rescorer_bind(head->rq.rescorer, fp.rs_keep, fp.rs_args);
         fp.rq.rs = &fp.rs_args;
       }

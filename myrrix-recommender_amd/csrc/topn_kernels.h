@@ -172,6 +172,73 @@ __device__ __forceinline__ bool topn_cos_score(const float* __restrict__ y, cons
 constexpr float TOPN_RS_COVER = 6.103515625e-05f;  // 2^-14 (bound above)
 constexpr double TOPN_RS_MAX_SCALE = 1048576.0;     // 2^20: the filter's range of scale_i (and 2^-20 below) ...
 constexpr double TOPN_RS_MAX_OFFSET = 18446744073709551616.0;  // ... and of |offset_i| (2^64)
+// RESCORED COSINE MODE (template flags COS and RS: mals_most_similar_items_rescored, the Rescorer<LongPair> of
+// MostSimilarItemIterator.java:87-117 in the shape of RESCORED MODE).  For the pair (candidate i, query item q_j):
+// isFiltered = i in F (with MALS_SIMILAR_FILTER_QUERY_ITEMS also q_j in F: "either end of the pair"), rescore(pair, s) =
+// fl(fl(scale_i * s) + offset_i) in fp64 without contraction.  The exact score of an unfiltered item for a query of n items:
+//     r_j = fl(fl(scale_i * s_j) + offset_i),  s_j = the cosine of COSINE MODE;  s_j or r_j not finite: the item is SKIPPED;
+//     result = (float)((r_1 + ... + r_n) / n);  result not finite: the query FAILS (checkState, :117)
+// The rescore is PER TERM: the offset is added n times and divided once, so the exact mean is T = scale (m + os), m the mean
+// cosine, os = offset_i / scale_i -- no 1 / n on the offset, unlike RESCORED MODE, where it acts on the sum.
+// topn_cos_rs_score computes exactly that in the rescore and the dense path.  The filter runs the hit test in the domain
+// divided by scale_i AND multiplied by |y_i| (both folds at once): with rs = 1 / scale_i, Y = norm(Y_i) exactly,
+//     result >= tau   implies   approx + M_c |y_i|' + floor + Q - tau P + covers >= 0,   P = |y_i| rs,  Q = |y_i| os
+// P and Q are formed once per item per stage in fp32 from the kernel's |y_i| (n0) and the item's 16 bytes, and each split
+// into a bf16 pair; nothing is added per (item, query) pair.  Margin step: lane group 0 = COSINE MODE's with P in the
+// place of |y_i| in slots 2-5 ({P hi, lo, hi, lo} against {-tau hi, hi, lo, lo}); group 1 = {Q hi, Q lo} against {1, 1};
+// group 2 = the covers {P hi, |Q hi|} against {2^-14 1.01 |tau|, 2^-14 1.01}.  Bound (weights in the range below), term by
+// term, every term relative to Y unless it names P or Q:
+//   (a) operand rounding and the fp32 accumulation of the contraction, as COSINE MODE (a), (c), (d):
+//       |approx - Y m'| <= 2.01 * 2^-8 * 1.000001 Y, m' = the mean cosine in exact arithmetic; |y_i|' >= Y (1 - k 2^-25);
+//   (b) the reference's roundings PER TERM: s_j differs from the exact cosine by <= 2^-22 (COSINE MODE (b)); each r_j has
+//       two fp64 roundings, their fp64 sum n - 1 more (n <= 2^20), then the division and the cast to fp32:
+//       |result - T| <= (2^-22 + 2^-23.9) scale + 2^-23.9 scale |os|: in the divided domain times Y that is 2^-21.5 Y (into the
+//       slack of M_c) and 2^-23.9 Y |os| <= 2^-23.8 |Q| (into the cover of Q);
+//   (c) the fp32 products: rs32 = rs hi + rs lo and os32 = os hi + os lo (the item's bf16 pairs, each within 2^-16 of its
+//       value; the fp32 sum adds 2^-24), n0 within k 2^-25 <= 2^-18 of Y, P = fl32(n0 rs32), Q = fl32(n0 os32): 2^-24 each;
+//       |P - Y rs| <= (2^-16 + 2^-18 + 2^-23) Y rs, the same for Q;
+//   (d) the bf16 pairs of P and Q (lo rounded to nearest): 2^-16 of each; of -tau: lo rounded UP, which only ever adds
+//       (P hi + P lo > 0), so it needs no cover;
+//   (e) the range of |tau|, now in the rescored domain: tau is the bucket maximum of a lower bound of some item's rescored
+//       score, |tau| <= 2^20 (1 + 2^-5 + 2^6) < 2^27, and tau rs <= 2^47: with |y_f| < 2^64 every product stays finite in fp32.
+//       No constant absorbs tau P here (COSINE MODE's 1.7 * 2^-15 did, for |tau| <= 1 + 2^-5): its errors are covered in
+//       proportion, by the cover slot, whatever |tau| is;
+//   (f) the fp32 accumulation of the margin step (<= 33 terms): <= 2^-18.9 (1.02 Y + |Q| + P |tau|);
+// so the parts that go with Y sum to < (2.01 * 1.000001 * 2^-8 + 2^-21.5 + 2^-18.8) Y < 2.02 * 2^-8 Y < M_c |y_i|'
+// (TOPN_COS_MARGIN suffices: the 1.7 * 2^-15 it reserved for tau |y| is not drawn on), and the parts that go with P |tau|
+// and with |Q| to (2 * 2^-16 + 2^-18 + 2^-18.9 + 2^-22.9) = 2^-14.7 of each, below the covers 2^-14 * 1.01 * (1 - 2^-8) > 2^-14
+// (TOPN_RS_COVER suffices; the cover operands are rounded up, P hi and |Q hi| are within 2^-8 of P and |Q|).  The sample
+// (MODE 0) keeps ((approx - M_c |y_i|' - floor + Q - cover |Q hi|) / n0) * scale_f32: by the same bound the accumulator is at most
+// Y T / scale - 2^-10.2 Y - 2^-15.4 |Q|, and the two fp32 products, n0 and scale_f32 move the quotient by <= 2^-17.9 of
+// |acc| / Y <= 1.02 + 1.01 |os| -- inside those two slacks -- so it is a lower bound of the rescored result and tau a lower
+// bound of the N-th best RESCORED score.  A filtered item (scale NaN) never wins a bucket and enters the hit test as P = 0,
+// Q = -1e30 (not times |y_i|: that product could overflow into a NaN, which the hit test counts as a hit).
+// Range of weights the filter runs for: scale_i in [2^-20, 2^20] as in RESCORED MODE, and |offset_i| <= 2^6 scale_i
+// (|os| <= TOPN_COS_RS_MAX_OS).  The covers grow with |os| -- 2 * 2^-14 * 1.01 (|os| + |tau| rs) of a cosine -- and at
+// |os| = 2^6 they reach 2^-7, the size of M_c itself: beyond that the candidates of a query are set by the covers, not by
+// the operands' rounding, and the dense path is the cheaper exact answer (rescorer_cos_filter_ok; other rescorers: dense).
+// A rescorer with at most TOPN_COS_RS_MAX_WILD unfiltered items outside that range (and uniform weights inside it) still runs
+// on the filter: such a WILD item (bit TOPN_FDATA_WILD of the fourth word of its 16 bytes) takes no part in the bound at all.
+// In the sample its scale reads NaN, so it never wins a bucket and tau is reached by N in-range items as before; in the hit
+// test it enters as P = 0, Q = +1e30 -- a hit of every query of the pass, whatever tau is -- and the exact rescore decides what
+// it scores: skipped, a finite score, or a result that is not finite, which fails that query of the pass and no other.  The
+// limit keeps the hits a wild item adds (one per query of the pass) inside a wave's hit list.
+// With MALS_SIMILAR_FILTER_QUERY_ITEMS a query with an item in F is answered empty (qflag 1, like a query item of norm 0).
+// Underflow.  The bound above speaks of overflow only; below, nothing is assumed about subnormal bf16 operands of the matrix
+// instruction (whether it flushes them is not established here): an operand below 2^-126 may read as zero.  P = fl32(n0 rs32)
+// goes subnormal 2^20 earlier than |y_i| does in COSINE MODE (rs down to 2^-20).  For |y_i| >= 2^-75: P >= 2^-95 is normal, and
+// P lo = P - P hi is zero or a multiple of P's fp32 unit, >= 2^-119: normal too, so the tau P products lose nothing.  Q and
+// Q lo can be subnormal however large |y_i| is (a tiny offset): flushed, each loses < 2^-126, not multiplied by tau, and the
+// absolute floor TOPN_MARGIN_FLOOR = 1e-30 (slot 1 of group 0) covers both, as it covers the subnormal range in the other
+// modes.  Rows with 0 < |y_i| < 2^-75 are outside the supported range of this mode (as rows whose squares overflow are in
+// COSINE MODE): there a flushed P lo could lose up to |tau| 2^-126 < 2^-99, which the floor does not bound.
+constexpr int TOPN_COS_RS_MAX_WILD = 4;      // most unfiltered items outside that range a rescorer may have on the filter path
+constexpr uint32_t TOPN_FDATA_WILD = 1u;     // fourth word of an item's 16 bytes: outside the range of rescored cosine mode
+constexpr double TOPN_COS_RS_MAX_OS = 64.0;  // 2^6: the filter's range of |offset_i| / scale_i in rescored cosine mode
+__host__ __device__ inline bool topn_cos_rs_in_range(double scale, double offset) {
+  return scale >= 1.0 / TOPN_RS_MAX_SCALE && scale <= TOPN_RS_MAX_SCALE && (offset < 0 ? -offset : offset) <= TOPN_COS_RS_MAX_OS * scale;
+}
+enum { TOPN_PAIR_FILTER_QUERY_ITEMS = 1 };  // = MALS_SIMILAR_FILTER_QUERY_ITEMS (include/myrrix_als.h)
 struct TopnRescore {
   const uint32_t* filt = nullptr;  // filter bits of items [0, filt_items)
   int64_t filt_items = 0;
@@ -182,6 +249,7 @@ struct TopnRescore {
   const uint4* fdata = nullptr;    // the filter's 16 bytes of items [0, n_fdata), `def` for the others
   int64_t n_fdata = 0;
   uint4 fdef = {0u, 0u, 0u, 0u};
+  int32_t pair_flags = 0;          // rescored cosine mode: TOPN_PAIR_* of the call
 };
 // where the rescored filter finds the items' 16 bytes: behind the pass's query image (TOPN_IMG_ENTRIES operands, the most
 // an instantiation reads), written by topn_prepare_kernel<false, true>
@@ -220,6 +288,31 @@ __device__ __forceinline__ bool topn_rs_score(const float* __restrict__ y, const
   const double r = topn_rs_affine(s, sum, o);
   if (!(fabs(r) < __builtin_huge_val())) return false;
   const float res = (float)(r / (double)(v1 - v0));
+  *out = fabsf(res) < __builtin_huge_valf() ? res : __builtin_nanf("");
+  return true;
+}
+// RESCORED COSINE MODE, MostSimilarItemIterator.java:87-117 for the query items [v0, v1) of the pass (rows vrow[v] of Y, norms
+// qn[v]) and candidate `item`: false if the pair (item, q_j) is filtered for some j, or a similarity or a rescored similarity
+// is not finite (the item is skipped); else *out = (float)(total / n), THE NaN if that is not finite (the query fails).  The
+// rescore acts on every TERM (:108), not on the sum as topn_rs_score's
+__device__ __forceinline__ bool topn_cos_rs_score(const float* __restrict__ y, const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
+                                                  const double* __restrict__ qn, int v0, int v1, int k, const TopnRescore& rs, int64_t item,
+                                                  float* out) {
+  const bool arr = item < rs.n_rows;
+  const double s = arr && rs.scale ? rs.scale[item] : rs.us, o = arr && rs.offset ? rs.offset[item] : rs.uo;
+  const bool cand_filtered = topn_rs_filtered(rs, item);
+  const bool both_ends = (rs.pair_flags & TOPN_PAIR_FILTER_QUERY_ITEMS) != 0 && vrow != nullptr;
+  const double ny = topn_ref_norm(y, k);
+  double total = 0.0;
+  for (int v = v0; v < v1; ++v) {
+    if (cand_filtered || (both_ends && topn_rs_filtered(rs, vrow[v]))) return false;   // isFiltered(pair), :98
+    const double sim = topn_ref_dot(y, vecs + (vrow ? vrow[v] : (int64_t)v) * k, k) / (ny * qn[v]);
+    if (!(fabs(sim) < __builtin_huge_val())) return false;   // :104
+    const double r = topn_rs_affine(s, sim, o);
+    if (!(fabs(r) < __builtin_huge_val())) return false;     // :109
+    total += r;
+  }
+  const float res = (float)(total / (double)(v1 - v0));
   *out = fabsf(res) < __builtin_huge_valf() ? res : __builtin_nanf("");
   return true;
 }
@@ -284,12 +377,15 @@ __device__ __forceinline__ __bf16 bf16_up(float v) {
 // norm (the query is answered empty), 2: a vector whose norm overflows (the dense path answers), else 0.
 // RS (rescored mode): lanes (1, c) also carry {0, 0, 0, 0 (-tau hi, hi, lo, lo: the filter fills them), 1/n hi, hi, lo, lo}
 // and lanes (2, c) {0 (the tau cover: the filter), 2^-14 * 1.01 / n rounded up}, n = the query's vector count.
+// COS and RS (rescored cosine mode): lanes (1, c) carry {1, 1} (against Q hi, lo) and lanes (2, c) {0 (the tau cover: the
+// filter), 2^-14 * 1.01 rounded up}; with TOPN_PAIR_FILTER_QUERY_ITEMS in pair_flags a query with a filtered item (the NaN
+// scale of its 16 bytes) gets qflag 1: every pair of it is filtered, it is answered empty.
 template <bool COS, bool RS = false>
 __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restrict__ vecs, const int64_t* __restrict__ vrow,
                                                            const int32_t* __restrict__ vptr, int n_queries, int k, int S,
                                                            bf16x8* __restrict__ img, unsigned* __restrict__ count,
                                                            unsigned* __restrict__ overflow, const double* __restrict__ qn,
-                                                           uint32_t* __restrict__ qflag, TopnImgTrailer trailer) {
+                                                           uint32_t* __restrict__ qflag, TopnImgTrailer trailer, int pair_flags) {
   __shared__ float xb[16][129];
   __shared__ float nrm[16];
   const int t = blockIdx.x, qi = threadIdx.x >> 4, sub = threadIdx.x & 15;  // 16 threads per query
@@ -312,6 +408,11 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
       if (!(s > 0.0)) flag = 1;
       else if (!(s < __builtin_huge_val()) && flag == 0) flag = 2;
     }
+    if (RS && (pair_flags & TOPN_PAIR_FILTER_QUERY_ITEMS) != 0 && vrow != nullptr)
+      for (int v = v0; v < v1; ++v) {
+        const int64_t it = vrow[v];
+        if (it < trailer.n_fdata && (trailer.fdata[it].z & 0x7fffffffu) > 0x7f800000u) flag = 1;   // a filtered item's scale: NaN (rescorer_fdata)
+      }
     for (int f = sub; f < 128; f += 16) {
       double mean = 0.0;
       if (f < k && flag == 0)
@@ -360,7 +461,15 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
         m[2] = (__bf16)(-1e30f);  // a padding query never has a candidate
       }
     }
-    if (RS && (g == 1 || g == 2) && 16 * t + c < n_queries) {
+    if (RS && COS && 16 * t + c < n_queries) {
+      if (g == 1) {
+        m[0] = (__bf16)1.f;
+        m[1] = (__bf16)1.f;
+      } else if (g == 2) {
+        m[1] = bf16_up(TOPN_RS_COVER * 1.01f);
+      }
+    }
+    if (RS && !COS && (g == 1 || g == 2) && 16 * t + c < n_queries) {
       const int nv = vptr[16 * t + c + 1] - vptr[16 * t + c];
       const float ninv = (float)(1.0 / (double)nv);
       if (g == 1) {
@@ -408,6 +517,9 @@ __global__ __launch_bounds__(256) void topn_prepare_kernel(const float* __restri
 // the query's {-tau hi, hi, lo, lo, 1/n hi, hi, lo, lo}, and lanes (2, c) = {rs hi, +-|os hi|} against the covers {2^-14
 // 1.01 |tau|, 2^-14 1.01 / n}: the item's 16 bytes ride with its row (prefetched a stage ahead), nothing is added per
 // (item, query) pair of the filter; the sample multiplies its accumulators by the items' fp32 scales (through LDS, 256 B).
+// COS and RS (rescored cosine mode, above): COS's operand with P = |y_i| rs in the place of |y_i| in slots 2-5, lanes (1, c) =
+// {Q hi, Q lo} (Q = |y_i| os) against {1, 1}, lanes (2, c) = {P hi, +-|Q hi|} against the covers; the sample multiplies its
+// quotients by the items' fp32 scales.
 // LSH (candidate filter, lsh_kernels.h; never with COS): the one invariant of the proof the filter can break is that tau must be
 // reached by at least N unmasked CANDIDATE items, so the sample must not let a non-candidate win a bucket: the popcount test
 // bitCount(sig_i ^ sig_q) <= maxBitsDiffering (LSH:201) runs per (item, query) BEFORE the bucket maximum -- dropping the buckets
@@ -444,7 +556,14 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
 #pragma unroll
     for (int s = 0; s < S; ++s) bq[j][s] = img[(t * (S + 1) + s) * 64 + lane];
     bf16x8 m = img[(t * (S + 1) + S) * 64 + lane];
-    if (MODE == 1 && RS && (g == 1 || g == 2)) {  // -tau_q = hi + lo (lo rounded up) against rs; its cover
+    if (MODE == 1 && RS && COS && g == 2) {  // rescored cosine mode: the cover of tau P (-tau itself: COS's slots, below)
+      const int q = 16 * t + c;
+      if (q < n_queries) {
+        const float tq = tau[q];
+        m[0] = bf16_up(TOPN_RS_COVER * 1.01f * (tq > -__builtin_huge_valf() ? __builtin_fabsf(tq) : 1e30f));
+      }
+    }
+    if (MODE == 1 && RS && !COS && (g == 1 || g == 2)) {  // -tau_q = hi + lo (lo rounded up) against rs; its cover
       const int q = 16 * t + c;
       if (q < n_queries) {
         const float tq = tau[q];
@@ -462,7 +581,7 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
         }
       }
     }
-    if (MODE == 1 && g == 0 && !RS) {  // -tau_q = hi + lo (lo rounded up) into slots 2, 3 of the margin entry
+    if (MODE == 1 && g == 0 && (!RS || COS)) {  // -tau_q = hi + lo (lo rounded up) into slots 2, 3 of the margin entry
       const int q = 16 * t + c;
       if (q < n_queries) {
         const float tq = tau[q];
@@ -615,7 +734,7 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
           sny[buf][w][c] = n0;
           am[0] = MODE == 0 ? (__bf16)(-(float)bf16_up(ny)) : bf16_up(ny);
           am[1] = (__bf16)(MODE == 0 || !finite ? -1.f : 1.f);  // a zero row: -floor, never a hit
-          if (MODE == 1) {
+          if (MODE == 1 && !RS) {
             const __bf16 hi = (__bf16)n0;
             const __bf16 lo = (__bf16)(n0 - (float)hi);
             am[2] = hi;
@@ -624,13 +743,39 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
             am[5] = lo;
           }
         }
+        if (RS) {  // rescored cosine mode (header): P = |y| rs against -tau, Q = |y| os against 1, their covers
+          const bool filtered = (fv.z & 0x7fffffffu) > 0x7f800000u;  // the NaN scale of a filtered item
+          const float rs32 = __uint_as_float(fv.x << 16) + __uint_as_float(fv.x & 0xffff0000u);
+          const float os32 = __uint_as_float(fv.y << 16) + __uint_as_float(fv.y & 0xffff0000u);
+          const bool wild = (fv.w & TOPN_FDATA_WILD) != 0u;          // weights outside the range: a candidate of every query
+          const float P = filtered || wild ? 0.f : n0 * rs32, Q = filtered ? -1e30f : wild ? 1e30f : n0 * os32;
+          const __bf16 ph = (__bf16)P, qh = (__bf16)Q;
+          if (g == 0) {
+            if (MODE == 1) {
+              const __bf16 pl = (__bf16)(P - (float)ph);
+              am[2] = ph;
+              am[3] = pl;
+              am[4] = ph;
+              am[5] = pl;
+            } else {
+              ssc[buf][w][c] = wild ? __builtin_nanf("") : __uint_as_float(fv.z);   // (a wild item never wins a bucket)
+            }
+          } else if (g == 1) {
+            am[0] = qh;
+            am[1] = (__bf16)(Q - (float)qh);
+          } else if (g == 2) {
+            am[0] = ph;  // (MODE 0: against 0)
+            const float qa = __builtin_fabsf((float)qh);
+            am[1] = (__bf16)(MODE == 0 ? -qa : qa);  // the sample subtracts the cover
+          }
+        }
       } else if (g == 0) {
         am[0] = MODE == 0 ? (__bf16)(-(float)bf16_up(ny)) : bf16_up(ny);  // the sample wants approx - margin
         am[1] = (__bf16)(MODE == 0 ? -1.f : 1.f);
         am[2] = (__bf16)1.f;
         am[3] = (__bf16)1.f;
       }
-      if (RS) {
+      if (RS && !COS) {
         const __bf16 rh = __builtin_bit_cast(__bf16, (uint16_t)(fv.x & 0xffffu)), rl = __builtin_bit_cast(__bf16, (uint16_t)(fv.x >> 16));
         const __bf16 oh = __builtin_bit_cast(__bf16, (uint16_t)(fv.y & 0xffffu)), ol = __builtin_bit_cast(__bf16, (uint16_t)(fv.y >> 16));
         if (g == 1) {
@@ -692,9 +837,10 @@ __global__ __launch_bounds__(256, 2) void topn_stream_kernel(const float* __rest
           const float nr = sny[cb][jt][4 * g + r];
           const bool in = it < n_items && nr > 0.f && nr < __builtin_huge_valf();
           const float rn = 1.f / nr;
+          const float sc = RS ? ssc[cb][jt][4 * g + r] : 1.f;  // rescored cosine mode: into the rescored domain (NaN: a filtered item)
 #pragma unroll
           for (int j = 0; j < QT; ++j) {
-            const float lb = acc[j][r] * rn;
+            const float lb = RS ? acc[j][r] * rn * sc : acc[j][r] * rn;
             if (in && lb > best[j][r]) {  // a NaN never wins
               best[j][r] = lb;
               besti[j][r] = (uint32_t)it;
@@ -974,6 +1120,7 @@ __global__ __launch_bounds__(1024) void topn_threshold_kernel(float* __restrict_
 // the overflow word), as is an index outside [0, n_items) (a known-item list entry of recommendedBecause)
 // RS: filtered candidates are struck, the score is topn_rs_score's (a skipped item struck; a result that is not finite
 // becomes THE NaN, which topn_final_kernel ranks first and the host reports as the query's failure -- not the pass's)
+// COS and RS: topn_cos_rs_score's, with the same conventions
 template <bool COS, bool RS = false>
 __global__ __launch_bounds__(64) void topn_rescore_kernel(const float* __restrict__ Y, int k, const float* __restrict__ vecs,
                                                           const int64_t* __restrict__ vrow, const int32_t* __restrict__ vptr, const unsigned* __restrict__ count, int cap,
@@ -1068,7 +1215,11 @@ __global__ __launch_bounds__(64) void topn_rescore_kernel(const float* __restric
     __syncthreads();
     if (valid) {
       uint64_t out = 0;
-      if (COS) {
+      if (COS && RS) {
+        float sc;
+        if (!struck && topn_cos_rs_score(ys + lane * pitch, vecs, vrow, qn, v0, v1, k, rsc, (int64_t)it, &sc))
+          out = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xffffffffu - it);
+      } else if (COS) {
         float sc;
         if (!struck && topn_cos_score(ys + lane * pitch, vecs, vrow, qn, v0, v1, k, &sc))
           out = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xffffffffu - it);
@@ -1172,6 +1323,12 @@ __global__ __launch_bounds__(256) void topn_exact_dense_kernel(const float* __re
       const float* y = ys + lane * pitch;
       for (int q = w; q < n_queries; q += 4) {
         const int v0 = __builtin_amdgcn_readfirstlane(vptr[q]), v1 = __builtin_amdgcn_readfirstlane(vptr[q + 1]);
+        if (COS && RS) {
+          float sc;
+          if (!topn_cos_rs_score(y, vecs, vrow, qn, v0, v1, k, rsc, i0 + lane, &sc)) sc = -__builtin_huge_valf();
+          scores[(int64_t)q * n_items + i0 + lane] = sc;
+          continue;
+        }
         if (COS) {
           float sc;
           if (!topn_cos_score(y, vecs, vrow, qn, v0, v1, k, &sc)) sc = -__builtin_huge_valf();

@@ -12,6 +12,10 @@ usage: python tools/bench_topn.py [--items N] [--users U] [--features K] [--how-
        LocationSensitiveHash) off and at each sample ratio in the same run, the build time next to its bytes bounds (the
        signatures read Y once, n k 4 bytes; with the mean computed on the device Y is read twice) and how many queries the bf16 filter path / the dense path answered; with --lib-root of a checkout that has
        no candidate filter only the filter-off leg runs (the A/B of unfiltered passes against an older build)
+       python tools/bench_topn.py --similar-rescored [--how-many 64] [--lib-root DIR]: one pass of mostSimilarItems per call
+       (240 queries at 64 features), plain and with a rescorer (per-item scale and offset, mals_most_similar_items_rescored),
+       next to the plain and rescored recommend pass in the same run; with --lib-root of a checkout without the rescored
+       call only the plain legs run (the A/B of the unrescored cosine pass against an older build)
        python tools/bench_topn.py --popular [--items 1000000] [--entries 100000000] [--how-many 100]: mostPopularItems
        (mals_most_popular_items) over a seeded known-item CSR resident on the device: the first call (the recount), the
        second (counts cached) and, in the same run, a device-to-device copy of the same index array as the yardstick"""
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--how-many", type=int, default=10)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--similar", action="store_true")
+    ap.add_argument("--similar-rescored", action="store_true")
+    ap.add_argument("--label", default=None, help="--similar-rescored: recorded as \"run\" in place of the library's path")
     ap.add_argument("--lib-root", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rescorer", action="store_true")
@@ -45,6 +51,8 @@ def main():
         return popular(a)
     if a.lsh:
         return lsh(a)
+    if a.similar_rescored:
+        return similar_rescored(a)
     if a.similar:
         return similar(a)
     if a.rescorer:
@@ -253,6 +261,56 @@ def rescored(a):
         out["rescored_over_plain"] = {b: out["rescored"][b]["queries_per_s"] / out["plain"][b]["queries_per_s"] for b in out["plain"]}
         r.close()
     out["value"] = out["rescored"]["4096"]["queries_per_s"]
+    print(json.dumps(out))
+
+
+def similar_rescored(a):
+    """one pass per call (per_pass queries): mostSimilarItems plain and rescored (per-item scale in [0.5, 2], offset ~ 0.1
+    N(0, 1): csrc/topn_kernels.h, RESCORED COSINE MODE), recommend plain and rescored with the same weights, same run; every
+    leg min and all of --reps runs of 40 calls, and which path answered the similarity queries (mals_similar_stats)"""
+    if a.lib_root:
+        sys.path.insert(0, os.path.abspath(a.lib_root))
+    import numpy as np
+    import myrrix_recommender_amd as pkg
+    rng = np.random.default_rng(1234567890)
+    k = a.features
+    Y = (rng.standard_normal((a.items, k)) / np.sqrt(k)).astype(np.float32)
+    X = (rng.standard_normal((a.users, k)) / np.sqrt(k)).astype(np.float32)
+    per_pass = 16 * {1: 16, 2: 15, 3: 10, 4: 7}[(k + 31) // 32]
+    out = {"metric": "us per pass of %d queries: mostSimilarItems and recommend, plain and rescored, same run" % per_pass, "unit": "us", "items": a.items,
+           "features": k, "how_many": a.how_many, "queries_per_pass": per_pass, "legs": {}}
+    out.update({"run": a.label} if a.label else {"lib": pkg._lib.LIB_PATH})
+    with pkg.ALSCore(k) as core:
+        core.set_factor_rows(pkg.SIDE_X, a.users)
+        core.set_factor_rows(pkg.SIDE_Y, a.items)
+        core.set_factors(pkg.SIDE_X, X)
+        core.set_factors(pkg.SIDE_Y, Y)
+        items = rng.integers(0, a.items, per_pass).astype(np.int64)
+        users = rng.integers(0, a.users, per_pass).astype(np.int64)
+        legs = {"similar_plain": lambda: core.most_similar_items(items, a.how_many),
+                "recommend_plain": lambda: core.recommend(users, a.how_many, consider_known_items=True)}
+        r = None
+        if hasattr(core, "similar_stats"):
+            r = core.rescorer()
+            r.set_weights(rng.uniform(0.5, 2.0, a.items), rng.standard_normal(a.items) * 0.1)
+            legs["similar_rescored"] = lambda: core.most_similar_items(items, a.how_many, rescorer=r)
+            legs["recommend_rescored"] = lambda: core.recommend(users, a.how_many, consider_known_items=True, rescorer=r)
+        for name, fn in legs.items():
+            fn()                                                        # warm
+        for name, fn in legs.items():
+            runs = []
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                for _ in range(40):
+                    fn()
+                runs.append((time.perf_counter() - t0) / 40 * 1e6)
+            out["legs"][name] = {"us_per_pass": min(runs), "us_per_pass_runs": runs, "queries_per_s": per_pass / min(runs) * 1e6}
+        if r is not None:
+            out["similar_stats"] = core.similar_stats()
+            out["similar_rescored_over_plain"] = out["legs"]["similar_rescored"]["us_per_pass"] / out["legs"]["similar_plain"]["us_per_pass"]
+            out["recommend_rescored_over_plain"] = out["legs"]["recommend_rescored"]["us_per_pass"] / out["legs"]["recommend_plain"]["us_per_pass"]
+            r.close()
+    out["value"] = out["legs"]["similar_plain"]["us_per_pass"]
     print(json.dumps(out))
 
 
