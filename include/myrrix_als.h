@@ -509,7 +509,8 @@ int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64
  * result bit-identical to the CPU restatement tests/foldin_oracle.py).  For handles OUTSIDE a group: a member's handle is
  * refused (MALS_INVALID_ARG); a group is written and read through the mals_group_* twins further down, which route every
  * user's known items to their owner.  Rows are dense indices (user = row of X,
- * item = row of Y); mapping ids, the candidate filter, clustering, tags and generationManager.append stay with the caller.
+ * item = row of Y); ids become rows through the id directory (mals_ids_* below); the candidate filter, clustering, tags
+ * and generationManager.append stay with the caller.
  * THREADS: every call below may be made from any thread while mals_recommend* / similarity calls run on the same handle.
  * Each (but mals_foldin_stats) is an exclusive ticket in the serving front's queue -- mals_recommend_to_anonymous is two,
  * see there: passes formed before it see the old model, passes formed after it the new one; concurrent writes are
@@ -577,6 +578,37 @@ int mals_recommend_to_anonymous(mals_handle h, int32_t n_queries, const int64_t*
 /* estimateForAnonymous (:734-759): out[q] = (float)dot(anonymous features of query q, y_to_item[q]). */
 int mals_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
                                 const float* values, float* out, int32_t* status_out);
+
+/* ---- the id directory: 64-bit ids <-> dense rows, resident on the handle -------------------------------------------
+ * Per side the handle can hold row -> id (a dense device array) and id -> row (an open-addressing table on the device:
+ * the slots and hash of mals_load_generation's join, at most half full, every 64-bit pattern a legal id), so that a
+ * caller needs no dictionary of its own and no trip through the host per batch.  For handles OUTSIDE a group (a member
+ * is MALS_INVALID_ARG, as on the write path).  Every call is an exclusive ticket of the serving front: a lookup sees
+ * every resolve queued before it.
+ * COVER: a side's directory must hold exactly one id per row of its replica.  Only mals_ids_resolve grows both together.
+ * A side that was never set, or whose replica was grown by mals_grow_factor_rows directly, is refused by every call
+ * below (MALS_INVALID_ARG; the message says which rows have no id) until mals_ids_set installs the ids of the rows as
+ * they are.  Whatever renumbers or replaces a side's rows DROPS its directory: mals_load_generation (install the merged
+ * ids it hands back: mals_generation_get_ids), mals_set_factor_rows, mals_bind_factors.
+ * A user that mals_remove_preferences empties keeps its id and its zeroed row: a later set of that id finds the row,
+ * which is exactly the vector getFeatures (:838-863) creates for a returning user.
+ *
+ * mals_ids_set: the ids of rows [0, n); n must be the rows of the side's replica; ids in host or device memory
+ * (mem_kind), e.g. what mals_ingest_get_ids returned.  An id that appears twice is MALS_INVALID_ARG -- the message names
+ * the smallest row that repeats an earlier row's id -- and nothing changes.  n = 0 with ids = NULL clears the side. */
+int mals_ids_set(mals_handle h, int side, int64_t n, const int64_t* ids, int mem_kind);
+/* rows_out[t] = the row of ids[t], or -1 if the directory does not know it (host arrays).  Changes nothing. */
+int mals_ids_lookup(mals_handle h, int side, int64_t n, const int64_t* ids, int64_t* rows_out);
+/* The same, except that an unknown id gets a new row: rows, rows + 1, ... in ORDER OF FIRST APPEARANCE in the batch,
+ * every later occurrence of the id the same row -- the result of a dictionary that reads the batch front to back,
+ * whatever the device's scheduling.  The replica grows as by mals_grow_factor_rows (new rows zero, userTagIDs extended,
+ * new users own no known items, capacity doubling; a bound replica is MALS_INVALID_ARG and nothing changes); the table
+ * is rebuilt at twice the slots -- as often as the batch needs -- before it would pass half full.  *n_new_out
+ * (nullable): the rows added.  n <= 2^30. */
+int mals_ids_resolve(mals_handle h, int side, int64_t n, const int64_t* ids, int64_t* rows_out, int64_t* n_new_out);
+/* ids_out[j] = the id of row row_begin + j, j < n (host); *n_out = the rows that have an id. */
+int mals_ids_get(mals_handle h, int side, int64_t row_begin, int64_t n, int64_t* ids_out);
+int mals_ids_count(mals_handle h, int side, int64_t* n_out);
 
 /* ---- mostPopularItems on the device -----------------------------------------------------------------------------
  * ServerRecommender.mostPopularItems(howMany, rescorer) (online/src/net/myrrix/online/ServerRecommender.java:611-673,
@@ -654,6 +686,41 @@ int mals_ingest_device_csr(mals_ingest g, int side, const int64_t** row_ptr, con
 /* mals_set_matrix(MALS_MEM_DEVICE) of both sides into a factorizer handle on the same device; the
  * handle borrows the arrays, so the ingest object must outlive their use. */
 int mals_ingest_install(mals_ingest g, mals_handle h);
+
+/* ---- ServerRecommender.ingest(Reader): input lines applied to the live model ---------------------------------------
+ * (ServerRecommender.java:204-309.)  g holds the records appended since its creation or its last mals_ingest_apply --
+ * through mals_ingest_append_text, mals_ingest_read_file or mals_ingest_append -- and is on h's device; h is a handle
+ * outside a group with both id directories in place (above), and, if the stream removes anything, with known items.
+ *  1. A record whose value is NaN (an empty third token) is a remove, any other a set.
+ *  2. The ids of the sets go through mals_ids_resolve, users and items, in record order: new ids get rows and the
+ *     replicas grow.  The ids of the removes are then looked up: a remove whose user or item has no row is dropped
+ *     (:1033-1042) and never creates one; a remove that stands before the set that creates its user finds a user
+ *     without known items, which mals_remove_preferences ignores as the reference does.
+ *  3. The stream is cut into maximal runs of sets and of removes (a dropped remove cuts nothing), and the runs go, in
+ *     order, through mals_set_preferences and mals_remove_preferences: every row's arithmetic is theirs.  The whole call
+ *     is one ticket of the serving front.
+ *  4. stats_out8 (nullable) = {records, sets, removes passed on, removes dropped for an unknown id, sets failed, new
+ *     users, new items, write calls made}.  removed_user_ids_out (capacity removed_cap; *n_removed_out of them): the IDS
+ *     of the users the removes emptied, in order.  removed_cap smaller than the number of remove records is
+ *     MALS_INVALID_ARG before anything changes.  Returns the code of the first failed update in stream order; the other
+ *     updates go on.
+ *  5. Afterwards the applied records are released from g; its line, bad-line and header counters and a carried partial
+ *     line stay, so append_text(end_of_file = 0) -> apply -> append_text -> apply streams a file of any length, and
+ *     "header" still means line 1 of the stream.
+ * REFUSED WHOLE (MALS_INVALID_ARG, nothing changed, the records stay in g): an ingest whose text has failed (more than
+ * 100 bad lines, a lone-quote token); an ingest that has seen a tag in either column (setUserTag / setItemTag change
+ * features without touching known items, which the write path does not do); a finished, sharded or spent ingest; g on
+ * another device; a member of a group; a directory that does not cover its side.  THE ONE DIFFERENCE from the reference:
+ * it would have applied the lines in front of the fatal one; the caller can feed those lines again in a new ingest.
+ * The failure's text is mals_ingest_last_error(g). */
+int mals_ingest_apply(mals_ingest g, mals_handle h, int64_t* stats_out8, int64_t* removed_user_ids_out, int64_t removed_cap,
+                      int64_t* n_removed_out);
+/* Where the last mals_ingest_apply on h that ran to its end spent its time, in ms: out4 = {the ids on the device -- gather,
+ * resolve, lookup and the copy of the rows to the host, HIP events on the handle's stream (the host's waits between the
+ * kernels are inside); classification, cut and batches on the host; the write drivers (their level kernels alone:
+ * mals_foldin_stats); the whole ticket}.  The parse has its own times (mals_ingest_text_info). */
+int mals_ingest_apply_times(mals_handle h, double* out4);
+
 /* The device the ingest lives on, and its userTagIDs as rows of R^T: device_idx_out = a device array owned by the ingest
  * (valid until the next finish / destroy) holding, per userTagID in ascending id order (mals_ingest_get_tag_ids), its dense
  * item index, or -1 for a tag that owns no row at the end of the stream; n_out = the number of userTagIDs.  What
@@ -708,7 +775,13 @@ int mals_ingest_partitions(mals_ingest g, int32_t* user_ranges, int32_t* item_ra
  * stream's start; mals_group_ingest_finish).  A share > 0 takes an unparseable first line as a header CANDIDATE: the group
  * finish counts it as the header when every earlier share is empty, as a bad line otherwise. */
 enum { MALS_INGEST_OPT_KNOWN_ITEMS = 1, MALS_INGEST_OPT_TEXT_BLOCK_BYTES = 2, MALS_INGEST_OPT_RESERVE_RECORDS = 3, MALS_INGEST_OPT_PARTITION_RECORDS = 4,
-       MALS_INGEST_OPT_SHARE = 5 };
+       MALS_INGEST_OPT_SHARE = 5,
+       /* ServerRecommender.ingest(Reader) splits a line at commas AND tabs (DELIMITER, ServerRecommender.java:95), where the
+        * input-file reader splits at commas alone (COMMA, InputFilesReader.java:51) and trims a tab as white space.  Value 1:
+        * every tab of the text appended from then on is read as a comma -- both are then delimiters, which is exactly the
+        * former splitter (quotes protect nothing in either).  Set it before the first text of a stream that goes to
+        * mals_ingest_apply; default 0, the input-file reader's lines. */
+       MALS_INGEST_OPT_TAB_DELIMITER = 6 };
 enum { MALS_ITEM_TAG_IDS = 0, MALS_USER_TAG_IDS = 1 };
 int mals_ingest_set_option(mals_ingest g, int32_t option, int64_t value);
 int mals_ingest_append_text(mals_ingest g, const void* bytes, int64_t n_bytes, int mem_kind, int32_t end_of_file);

@@ -18,6 +18,7 @@ SOLVE_AUTO, SOLVE_DIRECT, SOLVE_DUAL = 0, 1, 2
 ABI_VERSION = 5
 GROUP_RCCL, GROUP_PEER_COPY = 0, 1
 INGEST_OPT_KNOWN_ITEMS, INGEST_OPT_TEXT_BLOCK_BYTES, INGEST_OPT_RESERVE_RECORDS, INGEST_OPT_PARTITION_RECORDS, INGEST_OPT_SHARE = 1, 2, 3, 4, 5
+INGEST_OPT_TAB_DELIMITER = 6
 ITEM_TAG_IDS, USER_TAG_IDS = 0, 1
 INSTALL_COPY = 1
 
@@ -282,6 +283,13 @@ SYMBOLS = {
     "mals_group_anonymous_features": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P]),
     "mals_group_recommend_to_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "mals_group_estimate_for_anonymous": (ctypes.c_int, [_H, _I32, _P, _P, _P, _P, _P, _P]),
+    "mals_ids_set": (ctypes.c_int, [_H, ctypes.c_int, _I64, _P, ctypes.c_int]),
+    "mals_ids_lookup": (ctypes.c_int, [_H, ctypes.c_int, _I64, _P, _P]),
+    "mals_ids_resolve": (ctypes.c_int, [_H, ctypes.c_int, _I64, _P, _P, ctypes.POINTER(_I64)]),
+    "mals_ids_get": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, _P]),
+    "mals_ids_count": (ctypes.c_int, [_H, ctypes.c_int, ctypes.POINTER(_I64)]),
+    "mals_ingest_apply": (ctypes.c_int, [_H, _H, _P, _P, _I64, ctypes.POINTER(_I64)]),
+    "mals_ingest_apply_times": (ctypes.c_int, [_H, _P]),
     "mals_factor_digest": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, ctypes.POINTER(ctypes.c_uint64)]),
     "mals_group_replica_digest": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, _P, ctypes.POINTER(_I32)]),
     "mals_factor_digest_host": (ctypes.c_int, [_P, _I32, _I64, _I64, ctypes.POINTER(ctypes.c_uint64)]),

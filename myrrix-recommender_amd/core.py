@@ -779,6 +779,46 @@ class ALSCore:
     def grow_factor_rows(self, side, n_rows_total):
         self._chk(self._L.mals_grow_factor_rows(self._h, side, int(n_rows_total)))
 
+    def set_ids(self, side, ids):
+        """mals_ids_set: the ids of rows [0, n) of `side` (numpy, or a torch int64 CUDA tensor), one per row of its replica; an
+        empty array clears the side.  A duplicate id raises (the message names the row) and nothing changes."""
+        if _is_torch(ids):
+            assert ids.is_cuda and str(ids.dtype) == "torch.int64"
+            d = ids.contiguous()
+            self._chk(self._L.mals_ids_set(self._h, side, int(d.numel()), ctypes.c_void_p(d.data_ptr()) if d.numel() else None, MEM_DEVICE))
+        else:
+            a = _host(ids, np.int64)
+            self._chk(self._L.mals_ids_set(self._h, side, len(a), a.ctypes.data_as(ctypes.c_void_p) if len(a) else None, MEM_HOST))
+
+    def rows_of(self, side, ids, add=False):
+        """The row of each id (-1: unknown).  add=True (mals_ids_resolve): an unknown id gets a new row, numbered in order of
+        first appearance in `ids`, and the replica grows; returns (rows, rows added)."""
+        a = _host(ids, np.int64)
+        rows = np.empty(len(a), dtype=np.int64)
+        if not add:
+            self._chk(self._L.mals_ids_lookup(self._h, side, len(a), a.ctypes.data_as(ctypes.c_void_p), rows.ctypes.data_as(ctypes.c_void_p)))
+            return rows
+        n_new = ctypes.c_int64(0)
+        self._chk(self._L.mals_ids_resolve(self._h, side, len(a), a.ctypes.data_as(ctypes.c_void_p), rows.ctypes.data_as(ctypes.c_void_p),
+                                           ctypes.byref(n_new)))
+        return rows, n_new.value
+
+    def ids_of(self, side, row_begin=0, n=None):
+        """The ids of rows [row_begin, row_begin + n) (n=None: to the last row)."""
+        if n is None:
+            c = ctypes.c_int64(0)
+            self._chk(self._L.mals_ids_count(self._h, side, ctypes.byref(c)))
+            n = c.value - int(row_begin)
+        out = np.empty(max(int(n), 0), dtype=np.int64)
+        self._chk(self._L.mals_ids_get(self._h, side, int(row_begin), int(n), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def ingest_apply_times(self):
+        """mals_ingest_apply_times: ms of the last Ingest.apply on this handle, by stage."""
+        out = np.zeros(4, dtype=np.float64)
+        self._chk(self._L.mals_ingest_apply_times(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return dict(zip(("ids_ms", "plan_ms", "writes_ms", "total_ms"), out.tolist()))
+
     def estimate_preferences(self, users, items):
         u, i = _host(users, np.int64), _host(items, np.int64)
         out = np.empty(len(u), dtype=np.float32)

@@ -446,6 +446,7 @@ void generation_swap(mals_handle h, GenPrepared& p) {
     gs.d_map[sd] = std::move(g.map);
     gs.n_ids[sd] = s.n_total;
     gs.n_map[sd] = g.n_cur;
+    ids_drop(h, sd);   // the rows are renumbered: the caller installs the merged ids (mals_generation_get_ids -> mals_ids_set)
     std::vector<uint32_t>().swap(gs.recent[sd]);   // recentlyActiveUsers.clear() / recentlyActiveItems.clear() (:97-98)
   }
   gs.loaded = true;

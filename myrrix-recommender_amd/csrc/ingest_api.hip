@@ -225,6 +225,28 @@ int mals_ingest_install(mals_ingest g, mals_handle h) {
   return MALS_OK;
 }
 
+// ServerRecommender.ingest(Reader): the records appended since the ingest's creation or its last apply go into the live model
+// of h (ids_host.h).  Refused whole -- nothing changed, the records stay -- unless the ingest could still be finished and
+// has seen no tag; afterwards the records are released and the stream's counters and carried partial line stay.
+int mals_ingest_apply(mals_ingest g, mals_handle h, int64_t* stats_out8, int64_t* removed_user_ids_out, int64_t removed_cap, int64_t* n_removed_out) {
+  if (!g || !h) return MALS_INVALID_ARG;
+  if (n_removed_out) *n_removed_out = 0;
+  if (stats_out8) std::memset(stats_out8, 0, 8 * sizeof(int64_t));
+  if (g->spent || g->sharded) return fail(g, MALS_INVALID_ARG, "mals_ingest_apply: the ingest's records went into mals_group_ingest_finish");
+  if (g->finished) return fail(g, MALS_INVALID_ARG, "mals_ingest_apply: the ingest is finished (its records became matrices: mals_ingest_install)");
+  if (g->text_failed) return fail(g, MALS_INVALID_ARG, "mals_ingest_apply: the ingest's text has failed (" + g->text_fail_msg + "); nothing of it is applied");
+  if (g->n_tags_raw[0] || g->n_tags_raw[1])
+    return fail(g, MALS_INVALID_ARG, "mals_ingest_apply: the text holds tag lines (setUserTag / setItemTag), which the live write path does not serve");
+  ICHK(g, hipSetDevice(g->device));
+  ICHK(g, hipStreamSynchronize(g->stream));   // the records are whole before the handle's stream reads them
+  int changed = 0;
+  const int rc = malsi_ingest_apply(h, g->device, g->n, g->d_user.get(), g->d_item.get(), g->d_value.get(), stats_out8, removed_user_ids_out, removed_cap,
+                                    n_removed_out, &changed);
+  if (rc != MALS_OK) g->err = std::string("mals_ingest_apply: ") + mals_last_error(h);
+  if (rc == MALS_OK || changed) g->n = 0;   // applied (a failed update is reported, the others went on): released
+  return rc;
+}
+
 int mals_ingest_device(mals_ingest g, int32_t* device_out) {
   if (!g || !device_out) return MALS_INVALID_ARG;
   *device_out = g->device;

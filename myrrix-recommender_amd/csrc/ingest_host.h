@@ -58,6 +58,7 @@ struct mals_ingest_s {
   DeviceBuffer<int64_t> d_tags[2];   // [0]: itemTagIDs (tags seen in the user column), [1]: userTagIDs; with repeats
   size_t n_tags_raw[2] = {0, 0};
   int64_t lines = 0, bad_lines = 0, header_lines = 0, skipped_lines = 0, slow_lines = 0, text_bytes = 0;
+  bool tab_delimiter = false;  // MALS_INGEST_OPT_TAB_DELIMITER: tabs are read as commas (ServerRecommender.ingest's splitter)
   bool abort_armed = false;    // badLines > 100: the next line throws (IFR:96-98)
   bool text_failed = false;
   int text_fail_code = 0;

@@ -191,6 +191,8 @@ int append_text_impl(mals_ingest g, const uint8_t* bytes, int64_t n_bytes, int m
       ICHK(g, hipMemcpyAsync(g->d_text.get() + g->carry_len, bytes + off, m, mem_kind == MALS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                              g->stream));
     ICHK(g, hipMemsetAsync(g->d_text.get() + total, 0, TEXT_PAD, g->stream));
+    // (the carried tail was translated with its own block: translating it again changes nothing)
+    if (g->tab_delimiter && total) ITRY(launch(g, (int64_t)total, text_tabs_to_commas_kernel, g->d_text.get(), (int64_t)total));
     ICHK(g, hipEventRecord(g->t_ev.end, g->stream));
     // where the complete lines end
     size_t region;
@@ -283,6 +285,9 @@ int mals_ingest_set_option(mals_ingest g, int32_t option, int64_t value) {
       if (value < 0 || value >= MALS_SPLIT_MAX_SHARES) return fail(g, MALS_INVALID_ARG, "share: 0 .. 255");
       if (g->n || g->lines || g->text_bytes || g->carry_len) return fail(g, MALS_INVALID_ARG, "the share is set before the first append");
       g->share = (int32_t)value;
+      return MALS_OK;
+    case MALS_INGEST_OPT_TAB_DELIMITER:
+      g->tab_delimiter = value != 0;
       return MALS_OK;
     case MALS_INGEST_OPT_TEXT_BLOCK_BYTES:
       if (value < 1 || value > (int64_t)1 << 31) return fail(g, MALS_INVALID_ARG, "text block: 1 byte .. 2 GiB");

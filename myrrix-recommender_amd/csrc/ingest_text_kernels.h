@@ -436,4 +436,12 @@ __global__ void compact_known_kernel(const uint64_t* __restrict__ keys, const un
   }
 }
 
+// MALS_INGEST_OPT_TAB_DELIMITER: a pass over a staged block BEFORE the parser sees it -- every tab becomes a comma (a tab is one
+// byte in UTF-8 and never part of a longer sequence), so that the parser's comma split is ServerRecommender.ingest's split at
+// commas and tabs.  The parser itself is the input-file reader's, unchanged.
+__global__ void text_tabs_to_commas_kernel(uint8_t* __restrict__ text, int64_t n) {
+  MALS_GRID_STRIDE(i, n)
+    if (text[i] == (uint8_t)'\t') text[i] = (uint8_t)',';
+}
+
 }  // namespace mals

@@ -1080,6 +1080,7 @@ int mals_set_factor_rows(mals_handle h, int side, int64_t n_rows_total) {
   ++s.F_epoch;
   if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
   malsi_generation_drop_recent(h, side);                         // ... and no rows written since the last load
+  malsi_ids_drop(h, side);                                       // ... and no ids: the rows are not the ones they named
   if (side == MALS_SIDE_X) popular_touch(h, false);
   if (side == MALS_SIDE_Y) h->lsh.clear();                 // ... and its rows are not the ones the candidate filter signed
   return MALS_OK;
@@ -1097,6 +1098,7 @@ int mals_bind_factors(mals_handle h, int side, float* device_ptr, int64_t n_rows
   ++s.F_epoch;
   if (side == MALS_SIDE_X) h->grown_users_end.store(-1);   // a new replica: no grown users
   malsi_generation_drop_recent(h, side);                         // ... and no rows written since the last load
+  malsi_ids_drop(h, side);                                       // ... and no ids: the rows are not the ones they named
   if (side == MALS_SIDE_X) popular_touch(h, false);
   if (side == MALS_SIDE_Y) h->lsh.clear();
   return MALS_OK;

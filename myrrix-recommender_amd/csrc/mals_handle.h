@@ -282,8 +282,9 @@ __attribute__((visibility("hidden"))) void malsi_serving_create(mals_handle h);
 __attribute__((visibility("hidden"))) void malsi_serving_stop_front(mals_handle h);
 __attribute__((visibility("hidden"))) void malsi_serving_free(mals_handle h);
 // the matrix and factor setters: a new generation's known items (overlay, installed known items and popular counts go),
-// new user rows (popular_new_generation), new factor rows (generation_drop_recent)
+// new user rows (popular_new_generation), new factor rows (generation_drop_recent; ids_drop: their ids are not the old rows')
 __attribute__((visibility("hidden"))) void malsi_clear_known_items(mals_handle h);
 __attribute__((visibility("hidden"))) void malsi_popular_new_generation(mals_handle h, bool new_rows);
 __attribute__((visibility("hidden"))) void malsi_generation_drop_recent(mals_handle h, int side);
+__attribute__((visibility("hidden"))) void malsi_ids_drop(mals_handle h, int side);
 }

@@ -70,6 +70,14 @@ __attribute__((visibility("hidden"))) int malsi_member_estimate_for_anonymous(ma
                                                                             const int64_t* item_ptr, const int64_t* item_row, const float* values,
                                                                             float* out, int32_t* status_out);
 
+// mals_ingest_apply: the ingest side (ingest_api.hip) checks its own state and hands the serving side (ids_host.h) the records
+// as they lie on the device; *changed_out = 0: the call was refused whole and the handle is as it was.  The failure's text is
+// the handle's (mals_last_error).
+__attribute__((visibility("hidden"))) int malsi_ingest_apply(mals_handle h, int32_t ingest_device, int64_t n, const int64_t* d_user,
+                                                           const int64_t* d_item, const float* d_value, int64_t* stats_out8,
+                                                           int64_t* removed_user_ids_out, int64_t removed_cap, int64_t* n_removed_out,
+                                                           int* changed_out);
+
 // mals_group_ingest_finish (mals_group.cpp) hands the ingest side (ingest_group_host.h) the group's transport: collectives over
 // every rank, called with one device buffer per LOCAL member (on that member's device), returning once they are complete.
 struct malsi_group_ops {

@@ -9,12 +9,14 @@
 #include "foldin_kernels.h"
 #include "popular_kernels.h"
 #include "generation_kernels.h"
+#include "ids_kernels.h"
 #include "generation_group_kernels.h"
 #define MALS_FACTOR_DIGEST_KERNEL
 #include "factor_digest.h"
 #include "mals_internal.h"
 #include "mals_handle.h"
 #include "foldin_plan.h"
+#include "ingest_live_plan.h"
 #include "generation_group_plan.h"
 
 #include <hip/hip_runtime.h>
@@ -49,6 +51,7 @@ struct TopnFront;
 struct FoldinState;
 struct PopularState;
 struct GenerationState;
+struct IdsState;
 }  // namespace
 
 // What a handle holds of this unit (mals_handle_s::serving), made by mals_create and freed by mals_destroy.  The front lives
@@ -60,6 +63,7 @@ struct ServingState {
   FoldinState* fo = nullptr;          // the online write path (foldin_host.h): device solvers, known-item overlay, levels
   PopularState* pop = nullptr;        // mals_most_popular_items (popular_host.h): the count cache and the tag users
   GenerationState* gen = nullptr;     // mals_load_generation (generation_host.h): the recent rows, the ids and maps of the last load
+  IdsState* ids = nullptr;            // the id directory of mals_ids_* and mals_ingest_apply (ids_host.h): row -> id, id -> row per side
 };
 
 // ---- rescorers (mals_rescorer_*, include/myrrix_als.h; the kernels' side in topn_kernels.h, RESCORED MODE) ---------------
@@ -112,6 +116,7 @@ int topn_fail(mals_handle h, int code, const char* msg) {
 void generation_mark_pairs(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row);
 #include "foldin_host.h"
 #include "popular_host.h"
+#include "ids_host.h"
 #include "generation_host.h"
 #include "generation_group_host.h"
 }  // namespace
@@ -134,6 +139,7 @@ void malsi_serving_free(mals_handle h) {
   foldin_free(h);
   popular_free(h);
   generation_free(h);
+  ids_free(h);
   delete h->serving;
   h->serving = nullptr;
 }
@@ -150,6 +156,7 @@ void malsi_clear_known_items(mals_handle h) {
 
 void malsi_popular_new_generation(mals_handle h, bool new_rows) { popular_new_generation(h, new_rows); }
 void malsi_generation_drop_recent(mals_handle h, int side) { generation_drop_recent(h, side); }
+void malsi_ids_drop(mals_handle h, int side) { ids_drop(h, side); }
 
 extern "C" {
 
@@ -826,6 +833,59 @@ int mals_get_recent(mals_handle h, int side, int64_t* rows_out, int64_t* n_out) 
   });
 }
 
+// ---- the id directory (ids_host.h, ids_kernels.h) ---------------------------------------------------------------------------
+int mals_ids_set(mals_handle h, int side, int64_t n, const int64_t* ids, int mem_kind) {
+  CHECK_SIDE(h, side);
+  if (int rc = foldin_refuse(h, "mals_ids_set")) return rc;
+  if (n < 0 || (n > 0 && !ids) || n > (int64_t)1 << 30 || (mem_kind != MALS_MEM_HOST && mem_kind != MALS_MEM_DEVICE))
+    return topn_fail(h, MALS_INVALID_ARG, "mals_ids_set: bad arguments (n in [0, 2^30], ids, mem_kind)");
+  return foldin_exclusive(h, "mals_ids_set", [&](std::string& msg) -> int { return ids_set_run(h, side, n, ids, mem_kind, msg); });
+}
+
+static int ids_rows_of(mals_handle h, int side, int64_t n, const int64_t* ids, int64_t* rows_out, int64_t* n_new_out, bool add, const char* call) {
+  CHECK_SIDE(h, side);
+  if (n_new_out) *n_new_out = 0;
+  if (int rc = foldin_refuse(h, call)) return rc;
+  if (n < 0 || (n > 0 && (!ids || !rows_out)) || n > (int64_t)1 << 30)
+    return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": bad arguments (n in [0, 2^30], ids, rows_out)").c_str());
+  return foldin_exclusive(h, call, [&](std::string& msg) -> int { return ids_rows_of_run(h, side, n, ids, rows_out, n_new_out, add, msg); });
+}
+
+int mals_ids_lookup(mals_handle h, int side, int64_t n, const int64_t* ids, int64_t* rows_out) {
+  return ids_rows_of(h, side, n, ids, rows_out, nullptr, false, "mals_ids_lookup");
+}
+
+int mals_ids_resolve(mals_handle h, int side, int64_t n, const int64_t* ids, int64_t* rows_out, int64_t* n_new_out) {
+  return ids_rows_of(h, side, n, ids, rows_out, n_new_out, true, "mals_ids_resolve");
+}
+
+int mals_ids_get(mals_handle h, int side, int64_t row_begin, int64_t n, int64_t* ids_out) {
+  CHECK_SIDE(h, side);
+  if (int rc = foldin_refuse(h, "mals_ids_get")) return rc;
+  if (n > 0 && !ids_out) return topn_fail(h, MALS_INVALID_ARG, "mals_ids_get: ids_out must not be NULL");
+  return foldin_exclusive(h, "mals_ids_get", [&](std::string& msg) -> int { return ids_get_run(h, side, row_begin, n, ids_out, msg); });
+}
+
+int mals_ids_count(mals_handle h, int side, int64_t* n_out) {
+  CHECK_SIDE(h, side);
+  if (int rc = foldin_refuse(h, "mals_ids_count")) return rc;
+  if (!n_out) return topn_fail(h, MALS_INVALID_ARG, "mals_ids_count: n_out must not be NULL");
+  return foldin_exclusive(h, "mals_ids_count", [&](std::string& msg) -> int {
+    if (int rc = ids_ready(h, side, msg)) return rc;
+    *n_out = ids_state(h)->side[side].n;
+    return MALS_OK;
+  });
+}
+
+int mals_ingest_apply_times(mals_handle h, double* out4) {
+  if (!h || !out4) return MALS_INVALID_ARG;
+  return foldin_exclusive(h, "mals_ingest_apply_times", [&](std::string&) -> int {
+    const IdsState* st = h->serving->ids;
+    for (int i = 0; i < 4; ++i) out4[i] = st ? st->apply_ms[i] : 0.0;
+    return MALS_OK;
+  });
+}
+
 uint64_t mals_generation_hash_host(int64_t id) { return gen_hash(id); }
 
 int mals_generation_join_host(const int64_t* cur_ids, int64_t n_cur, const int64_t* new_ids, int64_t n_new, const int64_t* recent_rows,
@@ -973,6 +1033,23 @@ int malsi_member_recommend_to_anonymous(mals_handle h, int32_t n_queries, const 
 int malsi_member_estimate_for_anonymous(mals_handle h, int32_t n_queries, const int64_t* to_item, const int64_t* item_ptr, const int64_t* item_row,
                                         const float* values, float* out, int32_t* status_out) {
   return foldin_estimate_anonymous_impl(h, n_queries, to_item, item_ptr, item_row, values, out, status_out, true);
+}
+
+// ---- mals_ingest_apply (ingest_api.hip holds the records; ids_host.h applies them) --------------------------------------------
+int malsi_ingest_apply(mals_handle h, int32_t ingest_device, int64_t n, const int64_t* d_user, const int64_t* d_item, const float* d_value,
+                       int64_t* stats_out8, int64_t* removed_user_ids_out, int64_t removed_cap, int64_t* n_removed_out, int* changed_out) {
+  *changed_out = 0;
+  if (!h) return MALS_INVALID_ARG;
+  if (int rc = foldin_refuse(h, "mals_ingest_apply")) return rc;
+  if (ingest_device != h->cfg.device) return topn_fail(h, MALS_INVALID_ARG, "mals_ingest_apply: the ingest's records are on another device than the handle");
+  if (removed_cap < 0) return topn_fail(h, MALS_INVALID_ARG, "mals_ingest_apply: removed_cap must not be negative");
+  if (n > (int64_t)1 << 30) return topn_fail(h, MALS_INVALID_ARG, "mals_ingest_apply: at most 2^30 records per call");
+  bool changed = false;
+  const int rc = foldin_exclusive(h, "mals_ingest_apply", [&](std::string& msg) -> int {
+    return ids_apply_run(h, n, d_user, d_item, d_value, stats_out8, removed_user_ids_out, removed_cap, n_removed_out, &changed, msg);
+  });
+  *changed_out = changed ? 1 : 0;
+  return rc;
 }
 
 extern "C" int mals_factor_digest(mals_handle h, int side, int64_t row_begin, int64_t n_rows, uint64_t* out) {

@@ -166,6 +166,29 @@ class Ingest:
         self._chk(self._L.mals_ingest_install(self._g, core._h))
         core._keep[("ingest",)] = self
 
+    APPLY_STATS = ("records", "sets", "removes", "removes_dropped", "sets_failed", "new_users", "new_items", "write_calls")
+
+    def apply(self, core, raise_on_error=True):
+        """mals_ingest_apply (ServerRecommender.ingest): the records appended since the last apply go into the live model of
+        `core`, ids resolved on the device through its id directory (ALSCore.set_ids).  Returns (stats dict, ids of the users
+        the removes emptied); the records are released, the stream's counters and a carried partial line stay.  A failed
+        update raises unless raise_on_error is False (then stats["status"] holds its code); a refused call always raises."""
+        stats = np.zeros(8, dtype=np.int64)
+        removed = np.zeros(max(self.counts_records(), 1), dtype=np.int64)
+        n = ctypes.c_int64(0)
+        rc = self._L.mals_ingest_apply(self._g, core._h, stats.ctypes.data_as(ctypes.c_void_p), removed.ctypes.data_as(ctypes.c_void_p),
+                                       len(removed), ctypes.byref(n))
+        out = dict(zip(self.APPLY_STATS, (int(x) for x in stats)))
+        out["status"] = rc
+        if rc != _lib.OK and (raise_on_error or out["sets_failed"] == 0):
+            self._chk(rc)
+        return out, removed[:n.value].copy()
+
+    def counts_records(self):
+        n = ctypes.c_int64(0)
+        self._chk(self._L.mals_ingest_counts(self._g, ctypes.byref(n), None, None, None))
+        return n.value
+
     def install_group(self, group, copy=False):
         """mals_ingest_install_group: both matrices cut at the group's bounds, every member its slices device to device,
         knownItemIDs and the userTagIDs mask included.  copy=False: slices are borrowed where the member shares the device

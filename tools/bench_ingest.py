@@ -9,7 +9,14 @@ usage: python tools/bench_ingest.py [--records N] [--users U] [--items I] [--rem
        python tools/bench_ingest.py --ranks 1,2,4 [--records N]   the same text cut into N shares, one single-process group of N
            members on device 0 (MALS_GROUP_PEER_COPY) and mals_group_ingest_finish: one JSON line per N with the split kernels'
            time, traffic and rate, the device bytes every member's ingest holds afterwards next to one whole-input ingest plus
-           mals_ingest_install_group, and the entry imbalance of the X slices"""
+           mals_ingest_install_group, and the entry imbalance of the X slices
+       python tools/bench_ingest.py --live [--live-users U] [--live-items I] [--live-lines N] [--features K] [--repeat R]
+           the id directory and mals_ingest_apply: (1) mals_ids_resolve on a directory of 1M ids, batches of 1e6 ids of which a
+           tenth is new, next to the join of mals_load_generation over as many ids and to one CPU thread with
+           std::unordered_map (tools/ubench/ids_map_baseline.cpp, compiled here); (2) R + 1 streams of N lines applied to a
+           U x I model with Ingest.apply, and the same records driven by hand (a Python dict, grow_factor_rows,
+           set_preferences / remove_preferences run by run) on a second handle: per-stream wall times of both, the spread of
+           the by-hand figure, apply's time by stage, and whether the two handles end bit-identical"""
 import argparse
 import json
 import os
@@ -37,7 +44,13 @@ def main():
     ap.add_argument("--partition-records", type=int, default=0, help="MALS_INGEST_OPT_PARTITION_RECORDS (0: the library's default)")
     ap.add_argument("--ranks", type=str, default="", help="comma-separated member counts: the sharded ingest (mals_group_ingest_finish)")
     ap.add_argument("--features", type=int, default=32, help="--ranks: k of the group (its factor replicas are declared by the finish)")
+    ap.add_argument("--live", action="store_true", help="the id directory and mals_ingest_apply against the same stream driven by hand")
+    ap.add_argument("--live-users", type=int, default=1_000_000)
+    ap.add_argument("--live-items", type=int, default=100_000)
+    ap.add_argument("--live-lines", type=int, default=100_000)
     a = ap.parse_args()
+    if a.live:
+        return live(a)
     if a.ranks:
         return ranks(a)
     if a.from_text:
@@ -312,6 +325,168 @@ def ranks(a):
         for g in ings:
             g.close()
         print(json.dumps(out), flush=True)
+
+
+def live(a):
+    import shutil
+    import subprocess
+    import tempfile
+    import numpy as np
+    import myrrix_recommender_amd as pkg
+    from myrrix_recommender_amd import ingest
+    from myrrix_recommender_amd.core import HostSolver
+    X_, Y_ = pkg.SIDE_X, pkg.SIDE_Y
+    rng = np.random.default_rng(20240607)
+    out = {"metric": "id directory and mals_ingest_apply (live ingest)", "features": a.features}
+
+    # ---- 1. resolve rate -----------------------------------------------------------------------------------------------
+    n_dir, n_batch, batches = 1_000_000, 1_000_000, 5
+    ids = rng.permutation(np.arange(1, 4 * n_dir, dtype=np.int64) * 2654435761)[:n_dir + batches * n_batch // 10]
+    dir_ids, fresh = ids[:n_dir], ids[n_dir:]
+    with pkg.ALSCore(8) as c:
+        c.set_factor_rows(X_, n_dir)
+        t0 = time.perf_counter()
+        c.set_ids(X_, dir_ids)
+        set_ms = (time.perf_counter() - t0) * 1e3
+        res_ms, look_ms = [], []
+        for b in range(batches):
+            batch = dir_ids[rng.integers(0, n_dir, n_batch)]
+            where = rng.permutation(n_batch)[:n_batch // 10]
+            batch[where] = fresh[b * (n_batch // 10):(b + 1) * (n_batch // 10)]
+            t0 = time.perf_counter()
+            c.rows_of(X_, batch)
+            look_ms.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            rows, n_new = c.rows_of(X_, batch, add=True)
+            res_ms.append((time.perf_counter() - t0) * 1e3)
+            assert n_new == n_batch // 10 and rows.max() == n_dir + (b + 1) * (n_batch // 10) - 1
+        out["resolve"] = {"directory_ids": n_dir, "batch_ids": n_batch, "new_per_batch": n_batch // 10, "set_ids_ms": set_ms,
+                          "resolve_ms": res_ms, "lookup_ms": look_ms, "resolve_ids_per_s": n_batch / min(res_ms) * 1e3,
+                          "lookup_ids_per_s": n_batch / min(look_ms) * 1e3,
+                          "what": "wall time of mals_ids_resolve / mals_ids_lookup with host arrays: 8 MB up, 8 MB down, and for "
+                                  "resolve the growth of the k = 8 replica by 100k rows; best of %d batches" % batches}
+    with pkg.ALSCore(8) as c:      # the join of mals_load_generation over as many ids: 1M live against 1M new, half of them shared
+        c.set_factor_rows(X_, n_dir)
+        c.set_factor_rows(Y_, 64)
+        new_ids = np.concatenate([dir_ids[:n_dir // 2], fresh[:n_dir // 2]])
+        res, _, _ = c.load_generation(dir_ids, np.arange(64, dtype=np.int64), new_ids, np.arange(64, dtype=np.int64),
+                                      np.zeros((n_dir, 8), np.float32), np.zeros((64, 8), np.float32), keep_not_updated=True)
+        out["load_generation_join"] = {"live_ids": n_dir, "new_ids": n_dir, "join_ms": res["join_ms"][0],
+                                       "probed_ids_per_s": n_dir / res["join_ms"][0] * 1e3,
+                                       "what": "HIP events around the join of side X: two tables of 1M ids built, 1M ids probed"}
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    if cxx:
+        with tempfile.TemporaryDirectory() as td:
+            exe = os.path.join(td, "ids_map_baseline")
+            subprocess.check_call([cxx, "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "ubench", "ids_map_baseline.cpp")])
+            r = subprocess.run([exe, str(n_dir), str(n_batch), "100", str(batches)], capture_output=True, text=True, check=True)
+            out["cpu_baseline"] = {"value": float(r.stdout.split()[0]), "unit": "ids/s", "cores": 1, "kind": "std::unordered_map, one thread, the same batches"}
+
+    # ---- 2. apply against the same stream by hand ---------------------------------------------------------------------------
+    U, I, k, N = a.live_users, a.live_items, a.features, a.live_lines
+    X = (rng.standard_normal((U, k)) * 0.1).astype(np.float32)
+    Y = (rng.standard_normal((I, k)) * 0.1).astype(np.float32)
+    uid = np.arange(U, dtype=np.int64) * 7 + 1_000_000_000
+    iid = np.arange(I, dtype=np.int64) * 3 + 5
+    ptr = np.arange(0, 3 * U + 1, 3, dtype=np.int64)
+    col = (rng.integers(0, I - 3, U)[:, None] + np.arange(3)).ravel().astype(np.int32)    # three known items per user
+    Ys = Y[:20000].astype(np.float64)
+    sx = HostSolver.create(X[:20000].astype(np.float64).T @ X[:20000].astype(np.float64) * (U / 20000) + np.eye(k) * 0.1)
+    sy = HostSolver.create(Ys.T @ Ys * (I / 20000) + np.eye(k) * 0.1)
+
+    def handle():
+        c = pkg.ALSCore(k)
+        c.set_factor_rows(X_, U)
+        c.set_factor_rows(Y_, I)
+        c.set_factors(X_, X)
+        c.set_factors(Y_, Y)
+        c.set_matrix(X_, ptr, col, np.ones(len(col), np.float32))
+        c.set_foldin_solver(X_, sx)
+        c.set_foldin_solver(Y_, sy)
+        return c
+
+    def stream(r):
+        """N lines: 5 % of the users and 2 % of the items new (ids of this stream alone), a quarter removes, half of them of a
+        pair the stream set before"""
+        u = uid[rng.integers(0, U, N)]
+        i = iid[rng.integers(0, I, N)]
+        nu = rng.random(N) < 0.05
+        u[nu] = -(r * 10_000_000 + rng.integers(1, N, nu.sum()))
+        ni = rng.random(N) < 0.02
+        i[ni] = -(r * 10_000_000 + rng.integers(1, N // 4, ni.sum()))
+        v = rng.choice(np.array([1.0, 2.0, 3.0, 5.0, -1.0], np.float32), N)
+        rem = np.nonzero(rng.random(N) < 0.25)[0]
+        v[rem] = np.nan
+        back = rem[rng.random(len(rem)) < 0.5]
+        src = (back * rng.random(len(back))).astype(np.int64)
+        u[back], i[back] = u[src], i[src]
+        text = "".join("%d,%d,%s\n" % (x, y, "" if z != z else "%g" % z) for x, y, z in zip(u.tolist(), i.tolist(), v.tolist())).encode()
+        return u, i, v, text
+
+    ca, ch = handle(), handle()
+    ca.set_ids(X_, uid)
+    ca.set_ids(Y_, iid)
+    urow = {int(x): r for r, x in enumerate(uid.tolist())}
+    irow = {int(x): r for r, x in enumerate(iid.tolist())}
+
+    def by_hand(u, i, v):
+        is_set = v == v
+        ul, il = u.tolist(), i.tolist()
+        for t in np.nonzero(is_set)[0].tolist():
+            urow.setdefault(ul[t], len(urow))
+            irow.setdefault(il[t], len(irow))
+        ch.grow_factor_rows(X_, len(urow))
+        ch.grow_factor_rows(Y_, len(irow))
+        ur = np.array([urow.get(x, -1) for x in ul], np.int64)
+        ir = np.array([irow.get(x, -1) for x in il], np.int64)
+        live = is_set | ((ur >= 0) & (ir >= 0))
+        ur, ir, vv, ss = ur[live], ir[live], v[live], is_set[live]
+        cut = np.concatenate([[0], np.nonzero(ss[1:] != ss[:-1])[0] + 1, [len(ss)]])
+        calls = 0
+        for b, e in zip(cut[:-1].tolist(), cut[1:].tolist()):
+            if ss[b]:
+                ch.set_preferences(ur[b:e], ir[b:e], vv[b:e], raise_on_error=False)
+            else:
+                ch.remove_preferences(ur[b:e], ir[b:e])
+            calls += 1
+        return calls
+
+    rows = []
+    with ingest.Ingest(0) as g:
+        for r in range(a.repeat + 1):      # the first stream warms both routes up
+            u, i, v, text = stream(r + 1)
+            parse0 = g.text_info()["parse_ms"] if r else 0.0
+            g.append_text(text)
+            parse_ms = g.text_info()["parse_ms"] - parse0
+            lev0 = ca.foldin_stats()["device_ms_total"]
+            t0 = time.perf_counter()
+            st, _ = g.apply(ca, raise_on_error=False)
+            apply_ms = (time.perf_counter() - t0) * 1e3
+            times = ca.ingest_apply_times()
+            levels_ms = ca.foldin_stats()["device_ms_total"] - lev0
+            t0 = time.perf_counter()
+            calls = by_hand(u, i, v)
+            hand_ms = (time.perf_counter() - t0) * 1e3
+            same = all(ca.factor_digest(s) == ch.factor_digest(s) for s in (X_, Y_))
+            rows.append({"apply_ms": apply_ms, "by_hand_ms": hand_ms, "parse_ms": parse_ms, "ids_ms": times["ids_ms"], "plan_ms": times["plan_ms"],
+                         "writes_ms": times["writes_ms"], "level_kernels_ms": levels_ms, "write_calls": st["write_calls"],
+                         "by_hand_calls": calls, "new_users": st["new_users"], "new_items": st["new_items"], "bit_identical": same})
+    timed = rows[1:]
+    hand = np.array([x["by_hand_ms"] for x in timed])
+    app = np.array([x["apply_ms"] for x in timed])
+    out["apply"] = {"users": U, "items": I, "lines": N, "streams": timed, "warm_up": rows[0],
+                    "apply_ms_median": float(np.median(app)), "apply_ms_min": float(app.min()), "apply_ms_max": float(app.max()),
+                    "by_hand_ms_median": float(np.median(hand)), "by_hand_ms_min": float(hand.min()), "by_hand_ms_max": float(hand.max()),
+                    "by_hand_spread_ms": float(hand.max() - hand.min()),
+                    "apply_slower_than_by_hand_beyond_spread": bool(np.median(app) > np.median(hand) + (hand.max() - hand.min())),
+                    "all_bit_identical": all(x["bit_identical"] for x in rows),
+                    "what": "wall ms per stream; apply starts from the parsed records in the ingest (parse_ms: HIP events of the text "
+                            "kernels, outside apply_ms), by hand from the same records as numpy arrays; ids_ms: HIP events on the "
+                            "handle's stream around gather, resolve and lookup; plan_ms, writes_ms: host clock inside the ticket; "
+                            "level_kernels_ms: HIP events around the update kernels (mals_foldin_stats)"}
+    ca.close()
+    ch.close()
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
