@@ -509,8 +509,9 @@ int mals_recommended_because(mals_handle h, const int64_t* user_idx, const int64
  * result bit-identical to the CPU restatement tests/foldin_oracle.py).  For handles OUTSIDE a group: a member's handle is
  * refused (MALS_INVALID_ARG); a group is written and read through the mals_group_* twins further down, which route every
  * user's known items to their owner.  Rows are dense indices (user = row of X,
- * item = row of Y); ids become rows through the id directory (mals_ids_* below); the candidate filter, clustering, tags
- * and generationManager.append stay with the caller.
+ * item = row of Y); ids become rows through the id directory (mals_ids_* below), a tag's id is mals_tag_id_host of the tag
+ * (setUserTag / setItemTag: mals_set_user_tags / mals_set_item_tags); the candidate filter, clustering and
+ * generationManager.append stay with the caller.
  * THREADS: every call below may be made from any thread while mals_recommend* / similarity calls run on the same handle.
  * Each (but mals_foldin_stats) is an exclusive ticket in the serving front's queue -- mals_recommend_to_anonymous is two,
  * see there: passes formed before it see the old model, passes formed after it the new one; concurrent writes are
@@ -547,6 +548,26 @@ int mals_foldin_solve(mals_handle h, int side, const float* b, int32_t n_rhs, do
  * the next half-iteration recompute its Gramian.  Updates that touch disjoint rows run side by side on the device; an
  * update waits for the last earlier update of its user and of its item (a hot item updated m times is m levels). */
 int mals_set_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out);
+/* setUserTag (:1076-1120) and setItemTag (:1122-1165) for n updates, in array order like mals_set_preferences and with
+ * its status words, return code and row rules (dense rows: mals_ids_resolve / mals_grow_factor_rows first; a tag id is
+ * mals_tag_id_host of the tag, and owns a row like any other id -- one that collides with a numeric id is the same row).
+ *   mals_set_user_tags: the tag's row is a row of Y.  It joins the userTagIDs (the mask of mals_set_tag_items: the row is
+ *     never recommended, similar or popular from then on; a handle without a mask gets one), then
+ *     updateFeatures(x_user, y_tag, value) runs -- the update of mals_set_preferences, bit for bit.
+ *   mals_set_item_tags: the tag's row is a row of X.  It joins the itemTagIDs (the tag users of mals_set_tag_users: the
+ *     row is not counted by mals_most_popular_items), then updateFeatures(x_tag, y_item, value) runs.
+ * Neither adds a known item.  The mark is made before the update and whatever becomes of it: a failed update (estimate not
+ * finite, an X^T X solver without a Y^T Y solver) and a value of NaN (weight 0) leave it.  Each call is one exclusive
+ * ticket; the rows are marked recent, so mals_load_generation carries them. */
+int mals_set_user_tags(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* tag_item_row, const float* value, int32_t* status_out);
+int mals_set_item_tags(mals_handle h, int64_t n, const int64_t* tag_user_row, const int64_t* item_row, const float* value, int32_t* status_out);
+/* The tag sets as they stand (a ticket): side Y = userTagIDs as rows of Y, side X = itemTagIDs as user rows of this handle,
+ * ascending.  *n_out = the set's size; rows_out (capacity cap, nullable when cap is 0) takes the first min(cap, size).  A
+ * member of a group answers for itself: the mask every member holds, the tag users it owns (global rows). */
+int mals_get_tag_rows(mals_handle h, int side, int64_t* rows_out, int64_t cap, int64_t* n_out);
+/* tagHasher.toLongID(tag) (OneWayMigrator: the first 8 bytes of the MD5 of the tag's UTF-8 form, big-endian) of the tag whose
+ * UTF-8 bytes are given: what the text parser makes of the token "<bytes>".  Host only, no handle. */
+int mals_tag_id_host(const void* utf8, int64_t n_bytes, int64_t* id_out);
 /* removePreference (:1001-1074) for n pairs in order: a user without known items, or an item the user does not know, is
  * ignored; otherwise the item leaves the user's known items, and when that empties them the user is removed: its row of
  * X is zeroed (a later setPreference recreates it from zeros, getFeatures :838-863) and reported in removed_users_out
@@ -707,9 +728,16 @@ int mals_ingest_install(mals_ingest g, mals_handle h);
  *  5. Afterwards the applied records are released from g; its line, bad-line and header counters and a carried partial
  *     line stay, so append_text(end_of_file = 0) -> apply -> append_text -> apply streams a file of any length, and
  *     "header" still means line 1 of the stream.
+ *  6. TAG LINES, with MALS_INGEST_OPT_LIVE_TAGS = 1 (:281-293): a line with a tag in the user column is a setItemTag, one
+ *     with a tag in the item column a setUserTag (mals_set_item_tags / mals_set_user_tags), unless its value is empty: a
+ *     tag remove is ignored altogether -- no row, no mark, no cut of a run.  Tag sets are sets of step 1: their ids are
+ *     resolved with the others' in record order (the user column on side X, the item column on side Y), they ride in the
+ *     same runs and stats_out8 counts them among sets, new users and new items.  A line that SETS the empty tag (a tag token
+ *     of two chars: "", but also "a -- substring(1, length - 1) is empty) throws out of the reference's ingest; here the
+ *     text fails when it is appended, like the lone quote.  mals_ingest_apply_tag_stats has the tag lines' own counts.
  * REFUSED WHOLE (MALS_INVALID_ARG, nothing changed, the records stay in g): an ingest whose text has failed (more than
- * 100 bad lines, a lone-quote token); an ingest that has seen a tag in either column (setUserTag / setItemTag change
- * features without touching known items, which the write path does not do); a finished, sharded or spent ingest; g on
+ * 100 bad lines, a lone-quote token, with live tags a set of the empty tag); without MALS_INGEST_OPT_LIVE_TAGS an ingest
+ * that has seen a tag in either column; a finished, sharded or spent ingest; g on
  * another device; a member of a group; a directory that does not cover its side.  THE ONE DIFFERENCE from the reference:
  * it would have applied the lines in front of the fatal one; the caller can feed those lines again in a new ingest.
  * The failure's text is mals_ingest_last_error(g). */
@@ -720,6 +748,9 @@ int mals_ingest_apply(mals_ingest g, mals_handle h, int64_t* stats_out8, int64_t
  * kernels are inside); classification, cut and batches on the host; the write drivers (their level kernels alone:
  * mals_foldin_stats); the whole ticket}.  The parse has its own times (mals_ingest_text_info). */
 int mals_ingest_apply_times(mals_handle h, double* out4);
+/* Of the last mals_ingest_apply on h: out4 = {setItemTag records, setUserTag records, tag removes ignored, rows newly marked
+ * (new members of the userTagIDs and of the itemTagIDs)}. */
+int mals_ingest_apply_tag_stats(mals_handle h, int64_t* out4);
 
 /* The device the ingest lives on, and its userTagIDs as rows of R^T: device_idx_out = a device array owned by the ingest
  * (valid until the next finish / destroy) holding, per userTagID in ascending id order (mals_ingest_get_tag_ids), its dense
@@ -781,7 +812,11 @@ enum { MALS_INGEST_OPT_KNOWN_ITEMS = 1, MALS_INGEST_OPT_TEXT_BLOCK_BYTES = 2, MA
         * every tab of the text appended from then on is read as a comma -- both are then delimiters, which is exactly the
         * former splitter (quotes protect nothing in either).  Set it before the first text of a stream that goes to
         * mals_ingest_apply; default 0, the input-file reader's lines. */
-       MALS_INGEST_OPT_TAB_DELIMITER = 6 };
+       MALS_INGEST_OPT_TAB_DELIMITER = 6,
+       /* 1: the tag lines of the text are writes of mals_ingest_apply (setUserTag / setItemTag; see there): every record keeps
+        * its kind, one byte.  Set before the first append; default 0 (mals_ingest_apply refuses a text with tag lines).
+        * mals_ingest_finish reads the records as before either way. */
+       MALS_INGEST_OPT_LIVE_TAGS = 7 };
 enum { MALS_ITEM_TAG_IDS = 0, MALS_USER_TAG_IDS = 1 };
 int mals_ingest_set_option(mals_ingest g, int32_t option, int64_t value);
 int mals_ingest_append_text(mals_ingest g, const void* bytes, int64_t n_bytes, int mem_kind, int32_t end_of_file);
@@ -1021,7 +1056,8 @@ int mals_group_bounds(mals_group g, int side, int64_t* bounds_out);
  * global indices.  For groups whose ranks all live in this process (mals_group_create with either backend, or
  * mals_group_create_rank with world 1); on a rank of a multi-process group every call below is MALS_INVALID_ARG -- like
  * mals_group_recommend, it cannot reach another process's owner.
- * WRITES (set_foldin_solver, set_foldin_learn_rate, set_preferences, remove_preferences, grow_factor_rows) are a
+ * WRITES (set_foldin_solver, set_foldin_learn_rate, set_preferences, set_user_tags, set_item_tags, remove_preferences,
+ * grow_factor_rows) are a
  * replicated state machine: every member holds complete replicas of X and Y, the update kernels are deterministic, so
  * every local member applies the same batch in the same order to its own replicas and nothing is exchanged.  Afterwards
  * every member's X and Y are bit for bit what ONE handle holding the whole model would hold after the same call.  A
@@ -1047,6 +1083,11 @@ int mals_group_bounds(mals_group g, int side, int64_t* bounds_out);
 int mals_group_set_foldin_solver(mals_group g, int side, mals_solver s);
 int mals_group_set_foldin_learn_rate(mals_group g, double rate);
 int mals_group_foldin_stats(mals_group g, int64_t* out6);
+/* setUserTag / setItemTag on a group (mals_set_user_tags / mals_set_item_tags): writes like mals_group_set_preferences.  Every
+ * member marks the tag's row of Y in its own mask; the member that owns a tag's row of X (grown rows: the last rank's) keeps it
+ * among its tag users, as mals_group_set_tag_users splits them. */
+int mals_group_set_user_tags(mals_group g, int64_t n, const int64_t* user_row, const int64_t* tag_item_row, const float* value, int32_t* status_out);
+int mals_group_set_item_tags(mals_group g, int64_t n, const int64_t* tag_user_row, const int64_t* item_row, const float* value, int32_t* status_out);
 int mals_group_set_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value,
                                int32_t* status_out);
 int mals_group_remove_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,

@@ -23,11 +23,11 @@ from .factorizer import (AlternatingLeastSquares, ExecutionException, Interrupte
                          SolverException, System)
 from .group import GroupALS, plan_shards
 from .generation import Generation, IllConditionedSolverException, Solver
-from .ingest import Ingest, readInputRecords
+from .ingest import Ingest, readInputRecords, tag_id
 from .serializer import GenerationSerializer, SerializedGeneration
 from ._lib import (FLAG_LOSS_IGNORES_UNSPECIFIED, FLAG_RECONSTRUCT_R, SIDE_X, SIDE_Y)
 
-__all__ = ["lsh_max_bits_differing", "factor_digest_host", "GroupALS", "plan_shards", "GenerationSerializer", "SerializedGeneration", "ALSCore", "Rescorer", "HostSolver", "IllConditioned", "Generation", "Solver", "Ingest", "readInputRecords",
+__all__ = ["lsh_max_bits_differing", "factor_digest_host", "GroupALS", "plan_shards", "GenerationSerializer", "SerializedGeneration", "ALSCore", "Rescorer", "HostSolver", "IllConditioned", "Generation", "Solver", "Ingest", "readInputRecords", "tag_id",
            "IllConditionedSolverException", "MalsError", "SingularSystem", "Cancelled", "AlternatingLeastSquares",
            "MatrixFactorizer", "MatrixUtils", "System", "ExecutionException",
            "InterruptedException", "SolverException", "SingularMatrixSolverException",

@@ -19,6 +19,7 @@ ABI_VERSION = 5
 GROUP_RCCL, GROUP_PEER_COPY = 0, 1
 INGEST_OPT_KNOWN_ITEMS, INGEST_OPT_TEXT_BLOCK_BYTES, INGEST_OPT_RESERVE_RECORDS, INGEST_OPT_PARTITION_RECORDS, INGEST_OPT_SHARE = 1, 2, 3, 4, 5
 INGEST_OPT_TAB_DELIMITER = 6
+INGEST_OPT_LIVE_TAGS = 7
 ITEM_TAG_IDS, USER_TAG_IDS = 0, 1
 INSTALL_COPY = 1
 
@@ -185,6 +186,10 @@ SYMBOLS = {
     "mals_foldin_stats": (ctypes.c_int, [_H, _P]),
     "mals_foldin_solve": (ctypes.c_int, [_H, ctypes.c_int, _P, _I32, _P]),
     "mals_set_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P, _P]),
+    "mals_set_user_tags": (ctypes.c_int, [_H, _I64, _P, _P, _P, _P]),
+    "mals_set_item_tags": (ctypes.c_int, [_H, _I64, _P, _P, _P, _P]),
+    "mals_get_tag_rows": (ctypes.c_int, [_H, ctypes.c_int, _P, _I64, ctypes.POINTER(_I64)]),
+    "mals_tag_id_host": (ctypes.c_int, [_P, _I64, ctypes.POINTER(_I64)]),
     "mals_remove_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
     "mals_grow_factor_rows": (ctypes.c_int, [_H, ctypes.c_int, _I64]),
     "mals_estimate_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P]),
@@ -277,6 +282,8 @@ SYMBOLS = {
     "mals_group_set_foldin_learn_rate": (ctypes.c_int, [_H, ctypes.c_double]),
     "mals_group_foldin_stats": (ctypes.c_int, [_H, _P]),
     "mals_group_set_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P, _P]),
+    "mals_group_set_user_tags": (ctypes.c_int, [_H, _I64, _P, _P, _P, _P]),
+    "mals_group_set_item_tags": (ctypes.c_int, [_H, _I64, _P, _P, _P, _P]),
     "mals_group_remove_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P, ctypes.POINTER(_I64)]),
     "mals_group_grow_factor_rows": (ctypes.c_int, [_H, ctypes.c_int, _I64]),
     "mals_group_estimate_preferences": (ctypes.c_int, [_H, _I64, _P, _P, _P]),
@@ -290,6 +297,7 @@ SYMBOLS = {
     "mals_ids_count": (ctypes.c_int, [_H, ctypes.c_int, ctypes.POINTER(_I64)]),
     "mals_ingest_apply": (ctypes.c_int, [_H, _H, _P, _P, _I64, ctypes.POINTER(_I64)]),
     "mals_ingest_apply_times": (ctypes.c_int, [_H, _P]),
+    "mals_ingest_apply_tag_stats": (ctypes.c_int, [_H, _P]),
     "mals_factor_digest": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, ctypes.POINTER(ctypes.c_uint64)]),
     "mals_group_replica_digest": (ctypes.c_int, [_H, ctypes.c_int, _I64, _I64, _P, ctypes.POINTER(_I32)]),
     "mals_factor_digest_host": (ctypes.c_int, [_P, _I32, _I64, _I64, ctypes.POINTER(ctypes.c_uint64)]),

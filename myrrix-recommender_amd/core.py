@@ -766,6 +766,34 @@ class ALSCore:
             self._chk(rc)
         return st
 
+    def _set_tags(self, fn, users, items, values, raise_on_error):
+        u, i, v = _host(users, np.int64), _host(items, np.int64), _host(values, np.float32)
+        assert len(u) == len(i) == len(v)
+        st = np.zeros(len(u), dtype=np.int32)
+        rc = fn(self._h, len(u), u.ctypes.data_as(ctypes.c_void_p), i.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p),
+                st.ctypes.data_as(ctypes.c_void_p))
+        if raise_on_error or rc not in (_lib.OK, _lib.INVALID_ARG) or not st.any():
+            self._chk(rc)
+        return st
+
+    def set_user_tags(self, users, tag_items, values, raise_on_error=True):
+        """setUserTag for each (users[t], tag_items[t], values[t]) in order: tag_items are the tags' rows of Y (the row of
+        tag_id(tag) on side Y).  The rows join the userTagIDs whatever their updates' statuses; no known item is added."""
+        return self._set_tags(self._L.mals_set_user_tags, users, tag_items, values, raise_on_error)
+
+    def set_item_tags(self, tag_users, items, values, raise_on_error=True):
+        """setItemTag for each (tag_users[t], items[t], values[t]) in order: tag_users are the tags' rows of X."""
+        return self._set_tags(self._L.mals_set_item_tags, tag_users, items, values, raise_on_error)
+
+    def tag_rows(self, side):
+        """The tag sets as they stand, ascending: SIDE_Y the userTagIDs as rows of Y, SIDE_X the itemTagIDs as user rows."""
+        n = ctypes.c_int64(0)
+        self._chk(self._L.mals_get_tag_rows(self._h, side, None, 0, ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.int64)
+        if n.value:
+            self._chk(self._L.mals_get_tag_rows(self._h, side, out.ctypes.data_as(ctypes.c_void_p), len(out), ctypes.byref(n)))
+        return out[:n.value]
+
     def remove_preferences(self, users, items):
         """removePreference for each pair in order.  Returns the user rows that lost their last known item (zeroed)."""
         u, i = _host(users, np.int64), _host(items, np.int64)
@@ -818,6 +846,12 @@ class ALSCore:
         out = np.zeros(4, dtype=np.float64)
         self._chk(self._L.mals_ingest_apply_times(self._h, out.ctypes.data_as(ctypes.c_void_p)))
         return dict(zip(("ids_ms", "plan_ms", "writes_ms", "total_ms"), out.tolist()))
+
+    def ingest_apply_tag_stats(self):
+        """mals_ingest_apply_tag_stats: the tag lines of the last Ingest.apply on this handle."""
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self._L.mals_ingest_apply_tag_stats(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return dict(zip(("item_tag_sets", "user_tag_sets", "tag_removes_ignored", "rows_marked"), (int(x) for x in out)))
 
     def estimate_preferences(self, users, items):
         u, i = _host(users, np.int64), _host(items, np.int64)

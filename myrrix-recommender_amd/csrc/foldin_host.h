@@ -1,5 +1,5 @@
-// foldin_host.h -- host side of the online write path (mals_set_preferences, mals_remove_preferences,
-// mals_grow_factor_rows, the fold-in reads; include/myrrix_als.h; kernels in foldin_kernels.h; the logic that needs no
+// foldin_host.h -- host side of the online write path (mals_set_preferences, mals_set_user_tags, mals_set_item_tags,
+// mals_remove_preferences, mals_grow_factor_rows, the fold-in reads; include/myrrix_als.h; kernels in foldin_kernels.h; the logic that needs no
 // device in foldin_plan.h).  Included by mals_serving.hip inside its anonymous namespace, after topn_host.h: every call
 // here runs as an exclusive ticket of the serving front (topn_front_submit), so the passes formed before it have finished
 // and the passes formed after it wait for its work on the handle's stream (ev_begin), and the state below is only ever
@@ -50,9 +50,13 @@ struct FoldinState {
   DeviceBuffer<float> d_val;
   DeviceBuffer<int32_t> d_status;
   DeviceBuffer<double> d_fold;         // userFoldIn of every update of the batch
+  DeviceBuffer<uint8_t> d_kind;        // per update, level order: FOLDIN_KIND_* (a batch with tag updates only)
+  bool tag_marked = false;             // the batch in flight ran foldin_tag_mark_kernel
   PinnedBuffer<uint8_t> h_stage;
   EventPair ev;                        // around a batch's update kernels (timing enabled: mals_foldin_stats reads the time)
 };
+
+void popular_add_tag_users(mals_handle h, std::vector<int64_t>& local_rows);   // popular_host.h
 
 FoldinState* foldin_state(mals_handle h) {
   if (!h->serving->fo) {
@@ -333,20 +337,63 @@ int foldin_write_ready(mals_handle* hs, int n_members, bool via_group, int64_t n
   return MALS_OK;
 }
 
-// ---- mals_set_preferences -------------------------------------------------------------------------------------------------
+// ---- mals_set_preferences / mals_set_user_tags / mals_set_item_tags ---------------------------------------------------------
+// userTagIDs.add of a batch, on the handle's stream behind its level kernels (d_rows holds the level-ordered rows).  A handle
+// without a mask gets one, zeroed, for the rows of Y as they stand (a grow of the same call has lengthened an existing one:
+// foldin_grow_enqueue); it is published as foldin_grow_finish publishes a longer one -- plain stores inside the ticket, which
+// the passes formed after it read.  The mask's counter word carries n_tag_items to the kernel and back.
+// the stage of a batch of n: user rows | item rows | values (the status words come back over them) | kinds | the mask's counter
+size_t foldin_stage_kind_at(int64_t n) { return sizeof(int64_t) * 2 * (size_t)n + sizeof(float) * (size_t)n; }
+size_t foldin_stage_count_at(int64_t n) { return (foldin_stage_kind_at(n) + (size_t)n + 7) & ~(size_t)7; }
+
+int foldin_tag_mark_enqueue(mals_handle h, int64_t n, const uint8_t* kind, const FoldinPlan& p, std::string& msg) {
+  FoldinState& fs = *foldin_state(h);
+  const int64_t n_items = h->side[MALS_SIDE_Y].n_total;
+  const size_t words = ((size_t)((n_items + 31) / 32) + 1) & ~(size_t)1;   // (the layout of mals_set_tag_items)
+  const size_t tail = sizeof(unsigned long long) / sizeof(uint32_t);
+  if (h->tag_bits.get() && h->tag_bits_items != n_items) {
+    msg = "the tag items were set for another item count";
+    return MALS_INVALID_ARG;
+  }
+  if (!h->tag_bits.get()) {
+    DeviceBuffer<uint32_t> bits;
+    FCHK(msg, bits.alloc(words + tail));
+    FCHK(msg, hipMemsetAsync(bits.get(), 0, sizeof(uint32_t) * (words + tail), h->stream));
+    h->tag_bits = std::move(bits);
+    h->tag_bits_items = n_items;
+    h->n_tag_items = 0;
+  }
+  FCHK(msg, fs.d_kind.reserve((size_t)n, h->stream));
+  uint8_t* hk = fs.h_stage.get() + foldin_stage_kind_at(n);   // (foldin_set_enqueue reserved the stage for them)
+  unsigned long long* hn = reinterpret_cast<unsigned long long*>(fs.h_stage.get() + foldin_stage_count_at(n));
+  for (int64_t j = 0; j < n; ++j) hk[j] = kind[p.order[(size_t)j]];
+  unsigned long long* d_n = reinterpret_cast<unsigned long long*>(h->tag_bits.get() + words);
+  *hn = (unsigned long long)h->n_tag_items;
+  FCHK(msg, hipMemcpyAsync(fs.d_kind.get(), hk, (size_t)n, hipMemcpyHostToDevice, h->stream));
+  FCHK(msg, hipMemcpyAsync(d_n, hn, sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(foldin_tag_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const int64_t*)(fs.d_rows.get() + n),
+                     (const uint8_t*)fs.d_kind.get(), n, n_items, h->tag_bits.get(), d_n);
+  FCHK(msg, hipGetLastError());
+  FCHK(msg, hipMemcpyAsync(hn, d_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  fs.tag_marked = true;
+  return MALS_OK;
+}
+
 // The level plan (foldin_plan.h, the same for every replica the batch goes to), then per member the enqueue half (uploads, the
 // level kernels and the status copy on the handle's stream, no wait) and the collect half (the wait and the host-side
 // bookkeeping).
-int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const float* value, const FoldinPlan& p,
-                       std::string& msg) {
+// kind (FOLDIN_KIND_* per update, or nullptr: all preferences): a tag update is the same kernel on (row of X, row of Y, value);
+// behind the levels the Y rows of the setUserTag updates go into the userTagIDs mask, whatever became of their updates
+int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const float* value, const uint8_t* kind,
+                       const FoldinPlan& p, std::string& msg) {
   FoldinState& fs = *foldin_state(h);
   SideState& x = h->side[MALS_SIDE_X];
   SideState& y = h->side[MALS_SIDE_Y];
   const int k = h->cfg.features;
   if (int rc = foldin_lds_limit(msg)) return rc;
   // level order on the device: user rows | item rows | values, one copy
-  const size_t bytes = sizeof(int64_t) * 2 * (size_t)n + sizeof(float) * (size_t)n;
-  FCHK(msg, fs.h_stage.reserve(std::max(bytes, sizeof(int32_t) * (size_t)n), h->stream));
+  const size_t bytes = foldin_stage_count_at(n) + sizeof(unsigned long long);
+  FCHK(msg, fs.h_stage.reserve(bytes, h->stream));
   FCHK(msg, fs.d_rows.reserve(2 * (size_t)n, h->stream));
   FCHK(msg, fs.d_val.reserve((size_t)n, h->stream));
   FCHK(msg, fs.d_status.reserve((size_t)n, h->stream));
@@ -377,13 +424,20 @@ int foldin_set_enqueue(mals_handle h, int64_t n, const int64_t* urow, const int6
   FCHK(msg, hipEventRecord(fs.ev.end, h->stream));
   int32_t* hs = reinterpret_cast<int32_t*>(fs.h_stage.get());
   FCHK(msg, hipMemcpyAsync(hs, fs.d_status.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  fs.tag_marked = false;
+  bool any_user_tag = false;
+  for (int64_t t = 0; kind && t < n && !any_user_tag; ++t) any_user_tag = kind[t] == FOLDIN_KIND_USER_TAG;
+  if (any_user_tag) return foldin_tag_mark_enqueue(h, n, kind, p, msg);
   return MALS_OK;
 }
 
 // the known items of the applied updates are recorded for the users in [own_lo, own_hi) only: on a group the owner of a
 // user keeps its overlay (a single handle owns every user foldin_check_pairs let through)
-int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const FoldinPlan& p, int64_t own_lo, int64_t own_hi,
-                       int32_t* status_out, std::string& msg) {
+// A tag update (kind 1 or 2) adds no known item (setUserTag / setItemTag never touch knownItemIDs); the tag's mark is made
+// whatever its update's status: the Y rows are in the mask by now (foldin_tag_mark_kernel), the X rows of the setItemTag
+// updates join the tag users of their owner here (itemTagIDs.add, :1139)
+int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int64_t* irow, const uint8_t* kind, const FoldinPlan& p, int64_t own_lo,
+                       int64_t own_hi, int32_t* status_out, std::string& msg) {
   FoldinState& fs = *foldin_state(h);
   SideState& x = h->side[MALS_SIDE_X];
   const int32_t* hs = reinterpret_cast<const int32_t*>(fs.h_stage.get());
@@ -391,6 +445,16 @@ int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int6
   float dev_ms = 0.f;
   FCHK(msg, hipEventElapsedTime(&dev_ms, fs.ev.begin, fs.ev.end));
   foldin_new_model(h);
+  if (fs.tag_marked) {
+    h->n_tag_items = (int64_t)*reinterpret_cast<const unsigned long long*>(fs.h_stage.get() + foldin_stage_count_at(n));
+    fs.tag_marked = false;
+  }
+  if (kind) {
+    std::vector<int64_t> tag_users;
+    for (int64_t t = 0; t < n; ++t)
+      if (kind[t] == FOLDIN_KIND_ITEM_TAG && urow[t] >= own_lo && urow[t] < own_hi) tag_users.push_back(urow[t] - x.row_offset);
+    if (!tag_users.empty()) popular_add_tag_users(h, tag_users);
+  }
   int first = MALS_OK, first_why = 0;
   int64_t first_t = -1, applied = 0, failed = 0, big = 0;
   for (int64_t j = 0; j < n; ++j) {
@@ -408,6 +472,7 @@ int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int6
       continue;
     }
     ++applied;
+    if (kind && kind[t] != FOLDIN_KIND_PREF) continue;
     if (urow[t] >= own_lo && urow[t] < own_hi) fs.known.add(urow[t] - x.row_offset, (int32_t)irow[t]);   // knownItemIDs.get(userID).add(itemID) (:813-836)
   }
   if (applied) popular_touch(h, false);   // known items were added: what mals_most_popular_items counted is stale
@@ -424,7 +489,7 @@ int foldin_set_collect(mals_handle h, int64_t n, const int64_t* urow, const int6
 
 // own (n_members + 1): member m records the known items of the users own[m] <= u < own[m + 1]
 int foldin_set_members(mals_handle* hs, int n_members, const int64_t* own, bool via_group, int64_t n, const int64_t* urow, const int64_t* irow,
-                       const float* value, int32_t* status_out, std::string& msg) {
+                       const float* value, const uint8_t* kind, int32_t* status_out, std::string& msg) {
   if (int rc = foldin_write_ready(hs, n_members, via_group, n, urow, irow, msg)) return rc;
   FoldinPlan plan;
   foldin_set_plan(foldin_state(hs[0])->plan_scratch, n, urow, irow, plan);
@@ -434,10 +499,10 @@ int foldin_set_members(mals_handle* hs, int n_members, const int64_t* own, bool 
   std::string first_msg;
   NoSlots none;
   const int rc = member_loop(
-      hs, n_members, none, msg, [&](int m, std::string& why) { return foldin_set_enqueue(hs[m], n, urow, irow, value, plan, why); },
+      hs, n_members, none, msg, [&](int m, std::string& why) { return foldin_set_enqueue(hs[m], n, urow, irow, value, kind, plan, why); },
       [&](int m, std::string& why) -> int {
         std::string mine;
-        const int r = foldin_set_collect(hs[m], n, urow, irow, plan, own[m], own[m + 1], m == 0 ? status_out : nullptr, mine);
+        const int r = foldin_set_collect(hs[m], n, urow, irow, kind, plan, own[m], own[m + 1], m == 0 ? status_out : nullptr, mine);
         if (m == 0) {
           first = r;
           first_msg.swap(mine);

@@ -274,4 +274,18 @@ __global__ void foldin_zero_rows_kernel(float* __restrict__ F, int k, const int6
   if (t < n * k) F[(size_t)rows[t / k] * k + (size_t)(t % k)] = 0.f;
 }
 
+// setUserTag's userTagIDs.add(tagID) (:1094) for a batch: the item row of every update whose kind is FOLDIN_KIND_USER_TAG
+// is ORed into the mask that top-N, similarity and popular read (topn_tagged), and *n_set counts the bits that were clear
+// before -- the old word decides, so a row repeated within the batch counts once.  n_items bounds the mask's words.
+enum : uint8_t { FOLDIN_KIND_PREF = 0, FOLDIN_KIND_ITEM_TAG = 1, FOLDIN_KIND_USER_TAG = 2 };
+__global__ __launch_bounds__(256) void foldin_tag_mark_kernel(const int64_t* __restrict__ irow, const uint8_t* __restrict__ kind, int64_t n,
+                                                              int64_t n_items, uint32_t* __restrict__ bits, unsigned long long* __restrict__ n_set) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n || kind[t] != FOLDIN_KIND_USER_TAG) return;
+  const int64_t it = irow[t];
+  if (it < 0 || it >= n_items) return;
+  const uint32_t bit = 1u << (it & 31);
+  if ((atomicOr(&bits[it >> 5], bit) & bit) == 0u) atomicAdd(n_set, 1ull);
+}
+
 }  // namespace mals

@@ -29,6 +29,9 @@ struct IdsState {
   // ticket (host clock)} in ms
   EventPair ev;
   double apply_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  // mals_ingest_apply_tag_stats, of the last apply: {setItemTag records, setUserTag records, tag removes ignored, rows newly
+  // marked (bits of the userTagIDs mask + tag users)}
+  int64_t tag_stats[4] = {0, 0, 0, 0};
 };
 
 IdsState* ids_state(mals_handle h) {
@@ -240,7 +243,9 @@ int ids_get_run(mals_handle h, int side, int64_t row_begin, int64_t n, int64_t* 
 // it was (from the first resolve on); before that a failure is a refusal of the whole call.
 const int64_t IDS_OWN_ALL[2] = {std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max()};
 
-int ids_apply_run(mals_handle h, int64_t n, const int64_t* d_user, const int64_t* d_item, const float* d_value, int64_t* stats_out8,
+// d_kind (MALS_INGEST_OPT_LIVE_TAGS; else nullptr): the records' kinds -- tag sets ride in the set runs, tag removes are ignored
+int ids_apply_run(mals_handle h, int64_t n, const int64_t* d_user, const int64_t* d_item, const float* d_value, const uint8_t* d_kind,
+                  int64_t* stats_out8,
                   int64_t* removed_ids_out, int64_t removed_cap, int64_t* n_removed_out, bool* changed, std::string& msg) {
   *changed = false;
   int64_t stats[8] = {n, 0, 0, 0, 0, 0, 0, 0}, n_removed = 0;
@@ -255,15 +260,22 @@ int ids_apply_run(mals_handle h, int64_t n, const int64_t* d_user, const int64_t
   using Clock = std::chrono::steady_clock;
   auto ms_since = [](Clock::time_point a) { return std::chrono::duration<double, std::milli>(Clock::now() - a).count(); };
   IdsState& st = *ids_state(h);
+  std::fill(st.tag_stats, st.tag_stats + 4, (int64_t)0);
   const Clock::time_point t_begin = Clock::now();
   double plan_ms = 0.0;
   FCHK(msg, st.ev.ensure());
   std::vector<float> val((size_t)n);
+  std::vector<uint8_t> kinds(d_kind ? (size_t)n : 0), set_kind;
   FCHK(msg, hipMemcpyAsync(val.data(), d_value, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  if (d_kind) FCHK(msg, hipMemcpyAsync(kinds.data(), d_kind, (size_t)n, hipMemcpyDeviceToHost, h->stream));
   FCHK(msg, hipStreamSynchronize(h->stream));
   LiveClasses cls;
-  live_classify(n, val.data(), cls);
-  const int64_t ns = (int64_t)cls.set_pos.size(), nr = (int64_t)cls.rem_pos.size();
+  LiveTagCounts tags;
+  if (d_kind) live_classify_kinds(n, val.data(), kinds.data(), cls, set_kind, tags);
+  else live_classify(n, val.data(), cls);
+  const int64_t ns = (int64_t)cls.set_pos.size(), nr = (int64_t)cls.rem_pos.size(), n_used = ns + nr;
+  auto marked_rows = [&] { return h->n_tag_items + (h->serving->pop ? (int64_t)popular_state(h)->tag_users.size() : 0); };
+  const int64_t marked_before = marked_rows();
   if (nr > removed_cap || (nr > 0 && !removed_ids_out)) {
     msg = "removed_cap (" + std::to_string((long long)removed_cap) + ") is smaller than the remove records (" + std::to_string((long long)nr) + ")";
     return MALS_INVALID_ARG;
@@ -283,7 +295,7 @@ int ids_apply_run(mals_handle h, int64_t n, const int64_t* d_user, const int64_t
   FCHK(msg, d_pos.alloc((size_t)n));
   FCHK(msg, d_ids.alloc(2 * (size_t)n));
   FCHK(msg, d_rows.alloc(2 * (size_t)n));
-  FCHK(msg, hipMemcpyAsync(d_pos.get(), pos.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  if (n_used) FCHK(msg, hipMemcpyAsync(d_pos.get(), pos.data(), sizeof(int64_t) * (size_t)n_used, hipMemcpyHostToDevice, h->stream));   // (ignored tag removes: n_used < n)
   int64_t* ids_su = d_ids.get();
   int64_t* ids_si = ids_su + ns;
   int64_t* ids_ru = ids_si + ns;
@@ -309,7 +321,7 @@ int ids_apply_run(mals_handle h, int64_t n, const int64_t* d_user, const int64_t
   if (int rc = ids_lookup_dev(h, MALS_SIDE_Y, nr, ids_ri, rows_su + 2 * ns + nr, msg)) return rc;
   // the rows to the host, once: the level plan and the known items are host work
   std::vector<int64_t> rows(2 * (size_t)n), rem_uid((size_t)nr);
-  FCHK(msg, hipMemcpyAsync(rows.data(), d_rows.get(), sizeof(int64_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  if (n_used) FCHK(msg, hipMemcpyAsync(rows.data(), d_rows.get(), sizeof(int64_t) * 2 * (size_t)n_used, hipMemcpyDeviceToHost, h->stream));
   if (nr > 0) FCHK(msg, hipMemcpyAsync(rem_uid.data(), ids_ru, sizeof(int64_t) * (size_t)nr, hipMemcpyDeviceToHost, h->stream));
   FCHK(msg, hipEventRecord(st.ev.end, h->stream));
   FCHK(msg, hipStreamSynchronize(h->stream));
@@ -345,13 +357,18 @@ int ids_apply_run(mals_handle h, int64_t n, const int64_t* d_user, const int64_t
     st.apply_ms[1] = plan_ms;
     st.apply_ms[2] = ms_since(t_writes);
     st.apply_ms[3] = ms_since(t_begin);
+    st.tag_stats[0] = tags.item_tag_sets;
+    st.tag_stats[1] = tags.user_tag_sets;
+    st.tag_stats[2] = tags.removes_ignored;
+    st.tag_stats[3] = marked_rows() - marked_before;
   };
   for (const LiveRun& run : plan.runs) {
     const int64_t b = run.begin, len = run.end - run.begin;
     std::string why;
     ++stats[7];
     if (run.is_set) {
-      const int rc = foldin_set_members(&h, 1, IDS_OWN_ALL, false, len, set_u + b, set_i + b, set_v.data() + b, status.data() + b, why);
+      const uint8_t* run_kind = d_kind ? live_run_kinds(set_kind, run.begin, run.end) : nullptr;
+      const int rc = foldin_set_members(&h, 1, IDS_OWN_ALL, false, len, set_u + b, set_i + b, set_v.data() + b, run_kind, status.data() + b, why);
       int64_t failed = 0;
       for (int64_t j = 0; j < len; ++j) failed += status[(size_t)(b + j)] != MALS_OK ? 1 : 0;
       stats[4] += failed;

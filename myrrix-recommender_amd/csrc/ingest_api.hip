@@ -117,6 +117,7 @@ int mals_ingest_append(mals_ingest g, int64_t n, const int64_t* user_ids, const 
   ICHK(g, hipMemcpyAsync(g->d_user.get() + g->n, user_ids, sizeof(int64_t) * (size_t)n, kind, g->stream));
   ICHK(g, hipMemcpyAsync(g->d_item.get() + g->n, item_ids, sizeof(int64_t) * (size_t)n, kind, g->stream));
   ICHK(g, hipMemcpyAsync(g->d_value.get() + g->n, values, sizeof(float) * (size_t)n, kind, g->stream));
+  if (g->live_tags) ICHK(g, hipMemsetAsync(g->d_kind.get() + g->n, 0, (size_t)n, g->stream));   // records are preferences
   ICHK(g, hipStreamSynchronize(g->stream));
   g->n += n;
   return MALS_OK;
@@ -227,7 +228,7 @@ int mals_ingest_install(mals_ingest g, mals_handle h) {
 
 // ServerRecommender.ingest(Reader): the records appended since the ingest's creation or its last apply go into the live model
 // of h (ids_host.h).  Refused whole -- nothing changed, the records stay -- unless the ingest could still be finished and
-// has seen no tag; afterwards the records are released and the stream's counters and carried partial line stay.
+// has seen no tag (with MALS_INGEST_OPT_LIVE_TAGS its tag lines are writes like the others); afterwards the records are released and the stream's counters and carried partial line stay.
 int mals_ingest_apply(mals_ingest g, mals_handle h, int64_t* stats_out8, int64_t* removed_user_ids_out, int64_t removed_cap, int64_t* n_removed_out) {
   if (!g || !h) return MALS_INVALID_ARG;
   if (n_removed_out) *n_removed_out = 0;
@@ -235,16 +236,29 @@ int mals_ingest_apply(mals_ingest g, mals_handle h, int64_t* stats_out8, int64_t
   if (g->spent || g->sharded) return fail(g, MALS_INVALID_ARG, "mals_ingest_apply: the ingest's records went into mals_group_ingest_finish");
   if (g->finished) return fail(g, MALS_INVALID_ARG, "mals_ingest_apply: the ingest is finished (its records became matrices: mals_ingest_install)");
   if (g->text_failed) return fail(g, MALS_INVALID_ARG, "mals_ingest_apply: the ingest's text has failed (" + g->text_fail_msg + "); nothing of it is applied");
-  if (g->n_tags_raw[0] || g->n_tags_raw[1])
+  if (!g->live_tags && (g->n_tags_raw[0] || g->n_tags_raw[1]))
     return fail(g, MALS_INVALID_ARG, "mals_ingest_apply: the text holds tag lines (setUserTag / setItemTag), which the live write path does not serve");
   ICHK(g, hipSetDevice(g->device));
   ICHK(g, hipStreamSynchronize(g->stream));   // the records are whole before the handle's stream reads them
   int changed = 0;
-  const int rc = malsi_ingest_apply(h, g->device, g->n, g->d_user.get(), g->d_item.get(), g->d_value.get(), stats_out8, removed_user_ids_out, removed_cap,
-                                    n_removed_out, &changed);
+  const int rc = malsi_ingest_apply(h, g->device, g->n, g->d_user.get(), g->d_item.get(), g->d_value.get(), g->live_tags ? g->d_kind.get() : nullptr,
+                                    stats_out8, removed_user_ids_out, removed_cap, n_removed_out, &changed);
   if (rc != MALS_OK) g->err = std::string("mals_ingest_apply: ") + mals_last_error(h);
-  if (rc == MALS_OK || changed) g->n = 0;   // applied (a failed update is reported, the others went on): released
+  if (rc == MALS_OK || changed) {   // applied (a failed update is reported, the others went on): released
+    g->n = 0;
+    if (g->live_tags) g->n_tags_raw[0] = g->n_tags_raw[1] = 0;   // (the tag lines were among them)
+  }
   return rc;
+}
+
+// tagHasher.toLongID(tag): the parser's own hash (text_parse.h) of the token "<tag>"
+int mals_tag_id_host(const void* utf8, int64_t n_bytes, int64_t* id_out) {
+  if (!id_out || n_bytes < 0 || n_bytes > (int64_t)1 << 30 || (n_bytes > 0 && !utf8)) return MALS_INVALID_ARG;
+  std::string token((size_t)n_bytes + 2, '"');
+  if (n_bytes) std::memcpy(&token[1], utf8, (size_t)n_bytes);
+  const text::PtrSrc src{reinterpret_cast<const uint8_t*>(token.data())};
+  *id_out = text::tag_to_long(src, 0, (uint32_t)token.size());
+  return MALS_OK;
 }
 
 int mals_ingest_device(mals_ingest g, int32_t* device_out) {

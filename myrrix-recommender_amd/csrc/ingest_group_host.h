@@ -415,7 +415,7 @@ int shard_redistribute(ShardCtx& c, ShardRuns& R, bool records_are_source, Split
   ITRY(shard_allreduce(c, per, 0, &mat));
   for (int i = 0; i < c.nl && records_are_source; ++i) {   // the split copies hold the records now
     (void)hipSetDevice(c.g[i]->device);
-    c.g[i]->d_user.reset(); c.g[i]->d_item.reset(); c.g[i]->d_value.reset();
+    c.g[i]->d_user.reset(); c.g[i]->d_item.reset(); c.g[i]->d_value.reset(); c.g[i]->d_kind.reset();
   }
   return shard_exchange(c, mat, R.sa, R.sb, R.sv, R.ra, R.rb, R.rv, &R.n_recv);
 }
@@ -738,7 +738,7 @@ int mals_ingest_memory(mals_ingest g, int64_t* work_bytes, int64_t* result_bytes
   if (!g) return MALS_INVALID_ARG;
   int64_t w = 0, r = 0;
   auto add = [](int64_t& acc, const auto& b) { acc += (int64_t)(b.capacity() * sizeof(*b.get())); };
-  add(w, g->d_user); add(w, g->d_item); add(w, g->d_value);
+  add(w, g->d_user); add(w, g->d_item); add(w, g->d_value); add(w, g->d_kind);
   for (int b = 0; b < mals_ingest_s::N_WS; ++b) add(w, g->ws[b]);
   add(w, g->d_text); add(w, g->d_carry); add(w, g->t_block_counts); add(w, g->t_tile_sums); add(w, g->t_starts); add(w, g->t_flag);
   add(w, g->t_defer); add(w, g->t_status); add(w, g->t_user); add(w, g->t_item); add(w, g->t_value); add(w, g->t_counters);

@@ -26,6 +26,7 @@ struct mals_ingest_s {
   int64_t n = 0;
   DeviceBuffer<int64_t> d_user, d_item;
   DeviceBuffer<float> d_value;
+  DeviceBuffer<uint8_t> d_kind;   // MALS_INGEST_OPT_LIVE_TAGS only: 0 a preference, 1 setItemTag, 2 setUserTag (compact_records_kernel)
   // results
   bool finished = false;
   int64_t n_users = 0, n_items = 0, nnz = 0;
@@ -58,6 +59,7 @@ struct mals_ingest_s {
   DeviceBuffer<int64_t> d_tags[2];   // [0]: itemTagIDs (tags seen in the user column), [1]: userTagIDs; with repeats
   size_t n_tags_raw[2] = {0, 0};
   int64_t lines = 0, bad_lines = 0, header_lines = 0, skipped_lines = 0, slow_lines = 0, text_bytes = 0;
+  bool live_tags = false;      // MALS_INGEST_OPT_LIVE_TAGS: tag lines are writes of mals_ingest_apply (the records carry their kind)
   bool tab_delimiter = false;  // MALS_INGEST_OPT_TAB_DELIMITER: tabs are read as commas (ServerRecommender.ingest's splitter)
   bool abort_armed = false;    // badLines > 100: the next line throws (IFR:96-98)
   bool text_failed = false;
@@ -100,7 +102,7 @@ struct mals_ingest_s {
   }
   // records, workspace and text buffers: what a group finish releases before the factor replicas are declared
   void release_work() {
-    d_user.reset(); d_item.reset(); d_value.reset();
+    d_user.reset(); d_item.reset(); d_value.reset(); d_kind.reset();
     for (int b = 0; b < N_WS; ++b) ws[b].reset();
     d_text.reset(); d_carry.reset();
     t_block_counts.reset(); t_tile_sums.reset(); t_starts.reset(); t_flag.reset(); t_defer.reset();
@@ -241,15 +243,18 @@ int radix_sort(mals_ingest g, Scratch& s, K* const (&keys)[2], P* const (&pay)[2
 
 int64_t record_capacity(mals_ingest g) { return (int64_t)g->d_user.capacity(); }
 
-// the three record arrays moved to blocks of `cap` records, the first g->n kept.  All three new blocks exist before the old
-// ones go: a failed allocation leaves the records as they were (and allocates nothing).
+// the record arrays (three, and the kinds of MALS_INGEST_OPT_LIVE_TAGS) moved to blocks of `cap` records, the first g->n kept.
+// All new blocks exist before the old ones go: a failed allocation leaves the records as they were (and allocates nothing).
 int grow_records(mals_ingest g, int64_t cap) {
   DeviceBuffer<int64_t> u, it;
   DeviceBuffer<float> v;
+  DeviceBuffer<uint8_t> kd;
   ICHK(g, u.alloc((size_t)cap));
   ICHK(g, it.alloc((size_t)cap));
   ICHK(g, v.alloc((size_t)cap));
+  if (g->live_tags) ICHK(g, kd.alloc((size_t)cap));
   if (g->n) {
+    if (g->live_tags) ICHK(g, hipMemcpyAsync(kd.get(), g->d_kind.get(), (size_t)g->n, hipMemcpyDeviceToDevice, g->stream));
     ICHK(g, hipMemcpyAsync(u.get(), g->d_user.get(), sizeof(int64_t) * (size_t)g->n, hipMemcpyDeviceToDevice, g->stream));
     ICHK(g, hipMemcpyAsync(it.get(), g->d_item.get(), sizeof(int64_t) * (size_t)g->n, hipMemcpyDeviceToDevice, g->stream));
     ICHK(g, hipMemcpyAsync(v.get(), g->d_value.get(), sizeof(float) * (size_t)g->n, hipMemcpyDeviceToDevice, g->stream));
@@ -258,6 +263,7 @@ int grow_records(mals_ingest g, int64_t cap) {
   g->d_user = std::move(u);
   g->d_item = std::move(it);
   g->d_value = std::move(v);
+  g->d_kind = std::move(kd);
   return MALS_OK;
 }
 

@@ -91,10 +91,10 @@ int process_text_region(mals_ingest g, size_t region) {
     s.tile_sums = g->t_tile_sums.get();
     s.total = g->t_tile_sums.get() + std::max(lt, tiles);
   }
-  if (!g->t_counters) ICHK(g, g->t_counters.alloc(sizeof(TextCounters) + 2 * sizeof(unsigned)));
+  if (!g->t_counters) ICHK(g, g->t_counters.alloc(sizeof(TextCounters) + 3 * sizeof(unsigned)));   // (+ the tag cursors and the empty-tag line)
   TextCounters* counters = reinterpret_cast<TextCounters*>(g->t_counters.get());
   ICHK(g, hipEventRecord(e0, g->stream));
-  ICHK(g, hipMemsetAsync(counters, 0, sizeof(TextCounters) + 2 * sizeof(unsigned), g->stream));
+  ICHK(g, hipMemsetAsync(counters, 0, sizeof(TextCounters) + 3 * sizeof(unsigned), g->stream));
   ITRY(launch_grid(g, {(unsigned)n_blk}, line_starts_kernel, g->d_text.get(), (int64_t)region, g->t_block_counts.get(), g->t_starts.get()));
   const unsigned lgrid = (unsigned)((L + 255) / 256);
   const int first = g->lines == 0 ? 1 : 0;
@@ -135,6 +135,18 @@ int process_text_region(mals_ingest g, size_t region) {
       if (k == text::ST_BAD) ++bad;
     }
   }
+  // MALS_INGEST_OPT_LIVE_TAGS: a line that sets the empty tag throws out of ServerRecommender.ingest; here the text fails
+  if (g->live_tags && (c.user_tags || c.item_tags)) {
+    unsigned* first_empty = reinterpret_cast<unsigned*>(counters + 1) + 2;
+    unsigned got = 0;
+    ITRY(launch(g, (int64_t)L, empty_tag_set_kernel, g->t_status.get(), g->t_value.get(), (int64_t)L, first_empty));
+    ICHK(g, hipMemcpyAsync(&got, first_empty, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
+    ICHK(g, hipStreamSynchronize(g->stream));
+    if (got)
+      return text_fail(g, MALS_INVALID_ARG,
+                       "line " + std::to_string(g->lines + (int64_t)(0xffffffffu - got) + 1) +
+                           ": a line that sets the empty tag (the reference's setUserTag / setItemTag throw IllegalArgumentException here)");
+  }
   if (g->finished) g->free_results();   // any accepted text (also lines that yield no record) makes the last finish stale
   g->bad_lines += c.bad;
   g->abort_armed = g->bad_lines > 100;
@@ -148,7 +160,7 @@ int process_text_region(mals_ingest g, size_t region) {
     if (int rc = ensure_record_capacity(g, c.records)) return rc;
     ICHK(g, hipEventRecord(e0, g->stream));
     ITRY(launch_grid(g, {(unsigned)ct}, compact_records_kernel, g->t_status.get(), g->t_flag.get(), (int64_t)L, g->t_user.get(), g->t_item.get(), g->t_value.get(),
-                     g->d_user.get() + g->n, g->d_item.get() + g->n, g->d_value.get() + g->n));
+                     g->d_user.get() + g->n, g->d_item.get() + g->n, g->d_value.get() + g->n, g->live_tags ? g->d_kind.get() + g->n : nullptr));
     ITRY(seg_end());
     g->n += c.records;
   }
@@ -288,6 +300,15 @@ int mals_ingest_set_option(mals_ingest g, int32_t option, int64_t value) {
       return MALS_OK;
     case MALS_INGEST_OPT_TAB_DELIMITER:
       g->tab_delimiter = value != 0;
+      return MALS_OK;
+    case MALS_INGEST_OPT_LIVE_TAGS:
+      if (g->n || g->lines || g->text_bytes || g->carry_len) return fail(g, MALS_INVALID_ARG, "live tags are chosen before the first append");
+      g->live_tags = value != 0;
+      g->d_kind.reset();
+      if (g->live_tags && record_capacity(g) > 0) {   // (MALS_INGEST_OPT_RESERVE_RECORDS came first)
+        ICHK(g, hipSetDevice(g->device));
+        ICHK(g, g->d_kind.alloc((size_t)record_capacity(g)));
+      }
       return MALS_OK;
     case MALS_INGEST_OPT_TEXT_BLOCK_BYTES:
       if (value < 1 || value > (int64_t)1 << 31) return fail(g, MALS_INVALID_ARG, "text block: 1 byte .. 2 GiB");

@@ -380,7 +380,7 @@ __global__ __launch_bounds__(256) void compact_records_kernel(const uint8_t* __r
                                                               int64_t n_lines, const int64_t* __restrict__ user,
                                                               const int64_t* __restrict__ item, const uint32_t* __restrict__ value,
                                                               int64_t* __restrict__ user_out, int64_t* __restrict__ item_out,
-                                                              float* __restrict__ value_out) {
+                                                              float* __restrict__ value_out, uint8_t* __restrict__ kind_out) {
   // eight rounds of 256 consecutive lines, one line per thread: reads and writes stay coalesced
   unsigned base = tile_offsets[blockIdx.x];
 #pragma unroll 1
@@ -393,8 +393,26 @@ __global__ __launch_bounds__(256) void compact_records_kernel(const uint8_t* __r
       user_out[at] = user[i];
       item_out[at] = item[i];
       value_out[at] = __uint_as_float(value[i]);
+      // MALS_INGEST_OPT_LIVE_TAGS: what ServerRecommender.ingest makes of the record (:281-293) -- 0 a preference, 1 a tag in
+      // the user column (setItemTag), 2 a tag in the item column (setUserTag); a line never has both
+      if (kind_out) {
+        const int fl = status[i] >> 4;
+        kind_out[at] = (fl & text::FL_USER_TAG) ? (uint8_t)1 : (fl & text::FL_ITEM_TAG) ? (uint8_t)2 : (uint8_t)0;
+      }
     }
     base += total;
+  }
+}
+
+// MALS_INGEST_OPT_LIVE_TAGS: the first record line that SETS an empty tag (FL_EMPTY_TAG and a value that is no remove), as
+// *first = 0xffffffff - line (0: none; the caller zeroes it): setUserTag / setItemTag throw there (checkArgument(!tag.isEmpty()))
+__global__ void empty_tag_set_kernel(const uint8_t* __restrict__ status, const uint32_t* __restrict__ value, int64_t n_lines,
+                                     unsigned* __restrict__ first) {
+  MALS_GRID_STRIDE(i, n_lines) {
+    const uint8_t st = status[i];
+    if ((st & 15) != text::ST_RECORD || !((st >> 4) & text::FL_EMPTY_TAG)) continue;
+    if ((value[i] & 0x7fffffffu) > 0x7f800000u) continue;   // NaN: a tag remove, which ingest ignores
+    atomicMax(first, 0xffffffffu - (unsigned)i);
   }
 }
 

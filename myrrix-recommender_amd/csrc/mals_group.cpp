@@ -1453,18 +1453,32 @@ int mals_group_foldin_stats(mals_group g, int64_t* out6) {
   return MALS_OK;
 }
 
-int mals_group_set_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
-  if (int rc = foldin_group_ready(g, "mals_group_set_preferences")) return rc;
-  if (n < 0 || (n > 0 && (!user_row || !item_row || !value))) return gfail(g, MALS_INVALID_ARG, "mals_group_set_preferences: bad arguments");
-  if (n > (int64_t)1 << 30) return gfail(g, MALS_INVALID_ARG, "mals_group_set_preferences: at most 2^30 updates per call");
+// the group twins of setPreference, setUserTag and setItemTag: one batch of one kind
+static int group_set_impl(mals_group g, const char* call, int kind, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value,
+                   int32_t* status_out) {
+  if (int rc = foldin_group_ready(g, call)) return rc;
+  if (n < 0 || (n > 0 && (!user_row || !item_row || !value))) return gfail(g, MALS_INVALID_ARG, std::string(call) + ": bad arguments");
+  if (n > (int64_t)1 << 30) return gfail(g, MALS_INVALID_ARG, std::string(call) + ": at most 2^30 updates per call");
   if (n == 0) return MALS_OK;
   std::vector<mals_handle> hs = member_handles(g);
   std::lock_guard<std::mutex> lk(g->write_mu);
   std::vector<int64_t> own;
-  if (int rc = owned_users(g, "mals_group_set_preferences", own)) return rc;
+  if (int rc = owned_users(g, call, own)) return rc;
   std::string msg;
-  return write_failed(g, malsi_group_set_preferences(hs.data(), (int)hs.size(), own.data(), n, user_row, item_row, value, status_out, &msg),
-                      "mals_group_set_preferences", msg);
+  return write_failed(g, malsi_group_set_preferences(hs.data(), (int)hs.size(), own.data(), n, user_row, item_row, value, kind, status_out, &msg), call,
+                      msg);
+}
+
+int mals_group_set_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
+  return group_set_impl(g, "mals_group_set_preferences", 0, n, user_row, item_row, value, status_out);
+}
+
+int mals_group_set_user_tags(mals_group g, int64_t n, const int64_t* user_row, const int64_t* tag_item_row, const float* value, int32_t* status_out) {
+  return group_set_impl(g, "mals_group_set_user_tags", 2, n, user_row, tag_item_row, value, status_out);
+}
+
+int mals_group_set_item_tags(mals_group g, int64_t n, const int64_t* tag_user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
+  return group_set_impl(g, "mals_group_set_item_tags", 1, n, tag_user_row, item_row, value, status_out);
 }
 
 int mals_group_remove_preferences(mals_group g, int64_t n, const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,

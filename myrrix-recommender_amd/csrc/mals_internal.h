@@ -39,7 +39,7 @@ __attribute__((visibility("hidden"))) int malsi_group_set_foldin_solver(mals_han
 __attribute__((visibility("hidden"))) int malsi_group_set_foldin_learn_rate(mals_handle* hs, int n_members, double rate, std::string* err);
 __attribute__((visibility("hidden"))) int malsi_group_set_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n,
                                                                     const int64_t* user_row, const int64_t* item_row, const float* value,
-                                                                    int32_t* status_out, std::string* err);
+                                                                    int kind, int32_t* status_out, std::string* err);   // kind: 0 preferences, 1 setItemTag, 2 setUserTag
 __attribute__((visibility("hidden"))) int malsi_group_remove_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n,
                                                                        const int64_t* user_row, const int64_t* item_row, int64_t* removed_users_out,
                                                                        int64_t* n_removed_out, std::string* err);
@@ -74,8 +74,8 @@ __attribute__((visibility("hidden"))) int malsi_member_estimate_for_anonymous(ma
 // as they lie on the device; *changed_out = 0: the call was refused whole and the handle is as it was.  The failure's text is
 // the handle's (mals_last_error).
 __attribute__((visibility("hidden"))) int malsi_ingest_apply(mals_handle h, int32_t ingest_device, int64_t n, const int64_t* d_user,
-                                                           const int64_t* d_item, const float* d_value, int64_t* stats_out8,
-                                                           int64_t* removed_user_ids_out, int64_t removed_cap, int64_t* n_removed_out,
+                                                           const int64_t* d_item, const float* d_value, const uint8_t* d_kind,
+                                                           int64_t* stats_out8, int64_t* removed_user_ids_out, int64_t removed_cap, int64_t* n_removed_out,
                                                            int* changed_out);
 
 // mals_group_ingest_finish (mals_group.cpp) hands the ingest side (ingest_group_host.h) the group's transport: collectives over

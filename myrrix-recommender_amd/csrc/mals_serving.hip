@@ -514,14 +514,57 @@ int mals_foldin_stats(mals_handle h, int64_t* out6) {
 // a handle owns every user its pair check lets through (foldin_write_ready)
 static const int64_t FOLDIN_OWN_ALL[2] = {std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max()};
 
-int mals_set_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
+// setPreference, setUserTag and setItemTag: one batch of one kind (FOLDIN_KIND_*), one exclusive ticket
+static int foldin_set_impl(mals_handle h, const char* call, uint8_t kind, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value,
+                           int32_t* status_out) {
   if (!h) return MALS_INVALID_ARG;
-  if (int rc = foldin_refuse(h, "mals_set_preferences")) return rc;
-  if (n < 0 || (n > 0 && (!user_row || !item_row || !value))) return topn_fail(h, MALS_INVALID_ARG, "mals_set_preferences: bad arguments");
-  if (n > (int64_t)1 << 30) return topn_fail(h, MALS_INVALID_ARG, "mals_set_preferences: at most 2^30 updates per call");
+  if (int rc = foldin_refuse(h, call)) return rc;
+  if (n < 0 || (n > 0 && (!user_row || !item_row || !value))) return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": bad arguments").c_str());
+  if (n > (int64_t)1 << 30) return topn_fail(h, MALS_INVALID_ARG, (std::string(call) + ": at most 2^30 updates per call").c_str());
   if (n == 0) return MALS_OK;
-  return foldin_exclusive(h, "mals_set_preferences", [&](std::string& msg) -> int {
-    return foldin_set_members(&h, 1, FOLDIN_OWN_ALL, false, n, user_row, item_row, value, status_out, msg);
+  const std::vector<uint8_t> kinds(kind == FOLDIN_KIND_PREF ? 0 : (size_t)n, kind);
+  return foldin_exclusive(h, call, [&](std::string& msg) -> int {
+    return foldin_set_members(&h, 1, FOLDIN_OWN_ALL, false, n, user_row, item_row, value, kinds.empty() ? nullptr : kinds.data(), status_out, msg);
+  });
+}
+
+int mals_set_preferences(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
+  return foldin_set_impl(h, "mals_set_preferences", FOLDIN_KIND_PREF, n, user_row, item_row, value, status_out);
+}
+
+int mals_set_user_tags(mals_handle h, int64_t n, const int64_t* user_row, const int64_t* tag_item_row, const float* value, int32_t* status_out) {
+  return foldin_set_impl(h, "mals_set_user_tags", FOLDIN_KIND_USER_TAG, n, user_row, tag_item_row, value, status_out);
+}
+
+int mals_set_item_tags(mals_handle h, int64_t n, const int64_t* tag_user_row, const int64_t* item_row, const float* value, int32_t* status_out) {
+  return foldin_set_impl(h, "mals_set_item_tags", FOLDIN_KIND_ITEM_TAG, n, tag_user_row, item_row, value, status_out);
+}
+
+// the tag sets as they stand, read inside a ticket: side Y = the set bits of the userTagIDs mask, side X = the tag users
+// (global rows), ascending.  *n_out is the set's size whatever cap is; rows_out takes the first min(cap, size)
+int mals_get_tag_rows(mals_handle h, int side, int64_t* rows_out, int64_t cap, int64_t* n_out) {
+  CHECK_SIDE(h, side);
+  if (!n_out || cap < 0 || (cap > 0 && !rows_out)) return topn_fail(h, MALS_INVALID_ARG, "mals_get_tag_rows: bad arguments");
+  *n_out = 0;
+  if (int rc = foldin_refuse(h, "mals_get_tag_rows", true)) return rc;   // (a read of one handle's own sets: a group's member answers too)
+  return foldin_exclusive(h, "mals_get_tag_rows", [&](std::string& msg) -> int {
+    std::vector<int64_t> rows;
+    if (side == MALS_SIDE_X) {
+      if (h->serving->pop)
+        for (int64_t r : popular_state(h)->tag_users) rows.push_back(r + h->side[MALS_SIDE_X].row_offset);
+    } else if (h->tag_bits.get()) {
+      std::vector<uint32_t> words((size_t)((h->tag_bits_items + 31) / 32));
+      FCHK(msg, hipMemcpyAsync(words.data(), h->tag_bits.get(), sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost, h->stream));
+      FCHK(msg, hipStreamSynchronize(h->stream));
+      for (size_t w = 0; w < words.size(); ++w)
+        for (uint32_t b = words[w]; b; b &= b - 1) {
+          const int64_t r = (int64_t)w * 32 + __builtin_ctz(b);
+          if (r < h->tag_bits_items) rows.push_back(r);
+        }
+    }
+    *n_out = (int64_t)rows.size();
+    std::copy(rows.begin(), rows.begin() + std::min<int64_t>(cap, (int64_t)rows.size()), rows_out);
+    return MALS_OK;
   });
 }
 
@@ -886,6 +929,15 @@ int mals_ingest_apply_times(mals_handle h, double* out4) {
   });
 }
 
+int mals_ingest_apply_tag_stats(mals_handle h, int64_t* out4) {
+  if (!h || !out4) return MALS_INVALID_ARG;
+  return foldin_exclusive(h, "mals_ingest_apply_tag_stats", [&](std::string&) -> int {
+    const IdsState* st = h->serving->ids;
+    for (int i = 0; i < 4; ++i) out4[i] = st ? st->tag_stats[i] : 0;
+    return MALS_OK;
+  });
+}
+
 uint64_t mals_generation_hash_host(int64_t id) { return gen_hash(id); }
 
 int mals_generation_join_host(const int64_t* cur_ids, int64_t n_cur, const int64_t* new_ids, int64_t n_new, const int64_t* recent_rows,
@@ -924,9 +976,10 @@ int malsi_group_set_foldin_learn_rate(mals_handle* hs, int n_members, double rat
 }
 
 int malsi_group_set_preferences(mals_handle* hs, int n_members, const int64_t* own, int64_t n, const int64_t* user_row, const int64_t* item_row,
-                                const float* value, int32_t* status_out, std::string* err) {
+                                const float* value, int kind, int32_t* status_out, std::string* err) {
+  const std::vector<uint8_t> kinds(kind == FOLDIN_KIND_PREF ? 0 : (size_t)n, (uint8_t)kind);
   return group_call(hs, n_members, err, [&](std::string& msg) -> int {
-    return foldin_set_members(hs, n_members, own, true, n, user_row, item_row, value, status_out, msg);
+    return foldin_set_members(hs, n_members, own, true, n, user_row, item_row, value, kinds.empty() ? nullptr : kinds.data(), status_out, msg);
   });
 }
 
@@ -1037,7 +1090,7 @@ int malsi_member_estimate_for_anonymous(mals_handle h, int32_t n_queries, const 
 
 // ---- mals_ingest_apply (ingest_api.hip holds the records; ids_host.h applies them) --------------------------------------------
 int malsi_ingest_apply(mals_handle h, int32_t ingest_device, int64_t n, const int64_t* d_user, const int64_t* d_item, const float* d_value,
-                       int64_t* stats_out8, int64_t* removed_user_ids_out, int64_t removed_cap, int64_t* n_removed_out, int* changed_out) {
+                       const uint8_t* d_kind, int64_t* stats_out8, int64_t* removed_user_ids_out, int64_t removed_cap, int64_t* n_removed_out, int* changed_out) {
   *changed_out = 0;
   if (!h) return MALS_INVALID_ARG;
   if (int rc = foldin_refuse(h, "mals_ingest_apply")) return rc;
@@ -1046,7 +1099,7 @@ int malsi_ingest_apply(mals_handle h, int32_t ingest_device, int64_t n, const in
   if (n > (int64_t)1 << 30) return topn_fail(h, MALS_INVALID_ARG, "mals_ingest_apply: at most 2^30 records per call");
   bool changed = false;
   const int rc = foldin_exclusive(h, "mals_ingest_apply", [&](std::string& msg) -> int {
-    return ids_apply_run(h, n, d_user, d_item, d_value, stats_out8, removed_user_ids_out, removed_cap, n_removed_out, &changed, msg);
+    return ids_apply_run(h, n, d_user, d_item, d_value, d_kind, stats_out8, removed_user_ids_out, removed_cap, n_removed_out, &changed, msg);
   });
   *changed_out = changed ? 1 : 0;
   return rc;

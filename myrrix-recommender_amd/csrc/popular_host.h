@@ -1,7 +1,8 @@
 // popular_host.h -- host side of mals_most_popular_items / mals_set_tag_users (include/myrrix_als.h; kernels in
 // popular_kernels.h).  Included by mals_serving.hip inside its anonymous namespace, after foldin_host.h: the read runs as an
 // exclusive ticket of the serving front (foldin_exclusive), so the state below is only ever touched by the front's leader --
-// except the tag users, which follow the rule of mals_set_tag_items (not while calls are in flight).  One driver
+// except that mals_set_tag_users replaces the tag users under the rule of mals_set_tag_items (not while calls are in flight);
+// a write's setItemTag updates add to them inside their ticket (popular_add_tag_users).  One driver
 // (popular_members) serves a handle and the members of a group, over the member loop of foldin_host.h.
 //
 // THE COUNT CACHE.  The per-item count array stays on the device.  The handle carries a counter (pop_epoch) that every
@@ -69,6 +70,20 @@ int popular_set_tag_users(mals_handle* hs, int n_members, int64_t n, const int64
     popular_touch(h, false);
   }
   return MALS_OK;
+}
+
+// itemTagIDs.add of a write batch (foldin_set_collect, inside its ticket): local user rows of this handle, in any order, repeats
+// allowed, merged into the ascending set; what was counted is stale only if the set grew
+void popular_add_tag_users(mals_handle h, std::vector<int64_t>& local_rows) {
+  std::vector<int64_t>& have = popular_state(h)->tag_users;
+  std::sort(local_rows.begin(), local_rows.end());
+  local_rows.erase(std::unique(local_rows.begin(), local_rows.end()), local_rows.end());
+  std::vector<int64_t> merged;
+  merged.reserve(have.size() + local_rows.size());
+  std::set_union(have.begin(), have.end(), local_rows.begin(), local_rows.end(), std::back_inserter(merged));
+  if (merged.size() == have.size()) return;
+  have.swap(merged);
+  popular_touch(h, false);
 }
 
 unsigned popular_grid(mals_handle h, int64_t n_units, int per_block) {

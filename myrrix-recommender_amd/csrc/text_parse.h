@@ -55,7 +55,9 @@ enum : uint8_t {
   ST_FATAL = 4,   // the token '"' alone: String.substring(1, 0) throws out of readInputFiles
   ST_DEFER = 5    // fast mode only: the line needs the full parser
 };
-enum : uint8_t { FL_USER_TAG = 1, FL_ITEM_TAG = 2 };
+// FL_EMPTY_TAG: the line's tag token is two chars long, so the tag itself is "" (ServerRecommender.setUserTag / setItemTag
+// refuse it; the input-file reader hashes it like any other -- only MALS_INGEST_OPT_LIVE_TAGS looks at the flag)
+enum : uint8_t { FL_USER_TAG = 1, FL_ITEM_TAG = 2, FL_EMPTY_TAG = 4 };
 
 struct Parsed {
   int64_t user, item;
@@ -788,6 +790,14 @@ MALS_HD Parsed parse_line(const Src& s, uint32_t b, uint32_t e, bool first) {
       }
       id = tag_to_long(s, x, y);
       r.flags |= t == 0 ? FL_USER_TAG : FL_ITEM_TAG;
+      // token.length() == 2 (chars again: one char behind the quote, and a supplementary code point is two):
+      // substring(1, 1) is the empty tag
+      {
+        uint32_t cp;
+        bool valid;
+        const int len = utf8_step(s, x + 1, y, &cp, &valid);
+        if (x + 1 + (uint32_t)len == y && !(valid && len == 4)) r.flags |= FL_EMPTY_TAG;
+      }
     } else if (!parse_long<FULL>(s, x, y, &id)) {
       r.status = illegal;
       return r;

@@ -345,6 +345,24 @@ class GroupALS:
             self._chk(rc)
         return st
 
+    def _set_tags(self, fn, users, items, values, raise_on_error):
+        u, i, v = _host(users, np.int64), _host(items, np.int64), _host(values, np.float32)
+        assert len(u) == len(i) == len(v)
+        st = np.zeros(len(u), dtype=np.int32)
+        rc = fn(self._g, len(u), u.ctypes.data_as(ctypes.c_void_p), i.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p),
+                st.ctypes.data_as(ctypes.c_void_p))
+        if raise_on_error or rc not in (_lib.OK, _lib.INVALID_ARG) or not st.any():
+            self._chk(rc)
+        return st
+
+    def set_user_tags(self, users, tag_items, values, raise_on_error=True):
+        """setUserTag on every member (ALSCore.set_user_tags): tag_items are the tags' rows of Y."""
+        return self._set_tags(self._L.mals_group_set_user_tags, users, tag_items, values, raise_on_error)
+
+    def set_item_tags(self, tag_users, items, values, raise_on_error=True):
+        """setItemTag on every member (ALSCore.set_item_tags): tag_users are the tags' rows of X."""
+        return self._set_tags(self._L.mals_group_set_item_tags, tag_users, items, values, raise_on_error)
+
     def remove_preferences(self, users, items):
         u, i = _host(users, np.int64), _host(items, np.int64)
         assert len(u) == len(i)

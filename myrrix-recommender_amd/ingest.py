@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import MEM_DEVICE, MEM_HOST, SIDE_X, SIDE_Y
+from ._lib import INGEST_OPT_LIVE_TAGS   # 1: the text's tag lines are writes of Ingest.apply (before the first append)
 from .core import MalsError, _is_torch
 
 
@@ -252,4 +253,14 @@ def readInputFiles(inputDir, device=0, zero_threshold=None, known_items=True):
                 "knownItemIDs": g.known_items() if known_items else None, "info": info}
 
 
-__all__ = ["Ingest", "readInputRecords", "readInputFiles"]
+def tag_id(tag):
+    """tagHasher.toLongID(tag): the id a tag has on either side (str, or its UTF-8 bytes) -- mals_tag_id_host."""
+    b = tag.encode("utf-8") if isinstance(tag, str) else bytes(tag)
+    out = ctypes.c_int64(0)
+    rc = _lib.load().mals_tag_id_host(ctypes.c_char_p(b) if b else None, len(b), ctypes.byref(out))
+    if rc != _lib.OK:
+        raise MalsError(rc, "mals_tag_id_host failed")
+    return out.value
+
+
+__all__ = ["Ingest", "readInputRecords", "readInputFiles", "tag_id", "INGEST_OPT_LIVE_TAGS"]

@@ -10,7 +10,7 @@ usage: python tools/bench_ingest.py [--records N] [--users U] [--items I] [--rem
            members on device 0 (MALS_GROUP_PEER_COPY) and mals_group_ingest_finish: one JSON line per N with the split kernels'
            time, traffic and rate, the device bytes every member's ingest holds afterwards next to one whole-input ingest plus
            mals_ingest_install_group, and the entry imbalance of the X slices
-       python tools/bench_ingest.py --live [--live-users U] [--live-items I] [--live-lines N] [--features K] [--repeat R]
+       python tools/bench_ingest.py --live [--live-users U] [--live-items I] [--live-lines N] [--features K] [--repeat R] [--tags]
            the id directory and mals_ingest_apply: (1) mals_ids_resolve on a directory of 1M ids, batches of 1e6 ids of which a
            tenth is new, next to the join of mals_load_generation over as many ids and to one CPU thread with
            std::unordered_map (tools/ubench/ids_map_baseline.cpp, compiled here); (2) R + 1 streams of N lines applied to a
@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--live-users", type=int, default=1_000_000)
     ap.add_argument("--live-items", type=int, default=100_000)
     ap.add_argument("--live-lines", type=int, default=100_000)
+    ap.add_argument("--tags", action="store_true",
+                    help="--live: every tenth line of the stream is a tag line (setUserTag / setItemTag by turns, 1000 tags), applied with "
+                         "MALS_INGEST_OPT_LIVE_TAGS")
     a = ap.parse_args()
     if a.live:
         return live(a)
@@ -420,16 +423,29 @@ def live(a):
         back = rem[rng.random(len(rem)) < 0.5]
         src = (back * rng.random(len(back))).astype(np.int64)
         u[back], i[back] = u[src], i[src]
-        text = "".join("%d,%d,%s\n" % (x, y, "" if z != z else "%g" % z) for x, y, z in zip(u.tolist(), i.tolist(), v.tolist())).encode()
-        return u, i, v, text
+        kd = np.zeros(N, np.uint8)           # 0 a preference, 1 a tag in the user column (setItemTag), 2 in the item column (setUserTag)
+        us, its = [str(x) for x in u.tolist()], [str(y) for y in i.tolist()]
+        if a.tags:
+            at = np.arange(9, N, 10)
+            kd[at] = 1 + (at // 10) % 2
+            for t, name in zip(at.tolist(), rng.integers(0, 1000, len(at)).tolist()):
+                if kd[t] == 1:
+                    u[t], us[t] = tag_ids[name], '"tag%d"' % name
+                else:
+                    i[t], its[t] = tag_ids[name], '"tag%d"' % name
+        text = "".join("%s,%s,%s\n" % (x, y, "" if z != z else "%g" % z) for x, y, z in zip(us, its, v.tolist())).encode()
+        return u, i, v, kd, text
 
+    tag_ids = [pkg.tag_id("tag%d" % j) for j in range(1000)] if a.tags else []
     ca, ch = handle(), handle()
     ca.set_ids(X_, uid)
     ca.set_ids(Y_, iid)
     urow = {int(x): r for r, x in enumerate(uid.tolist())}
     irow = {int(x): r for r, x in enumerate(iid.tolist())}
 
-    def by_hand(u, i, v):
+    def by_hand(u, i, v, kd):
+        keep = (v == v) | (kd == 0)          # a tag remove is ignored altogether
+        u, i, v, kd = u[keep], i[keep], v[keep], kd[keep]
         is_set = v == v
         ul, il = u.tolist(), i.tolist()
         for t in np.nonzero(is_set)[0].tolist():
@@ -440,12 +456,13 @@ def live(a):
         ur = np.array([urow.get(x, -1) for x in ul], np.int64)
         ir = np.array([irow.get(x, -1) for x in il], np.int64)
         live = is_set | ((ur >= 0) & (ir >= 0))
-        ur, ir, vv, ss = ur[live], ir[live], v[live], is_set[live]
+        ur, ir, vv = ur[live], ir[live], v[live]
+        ss = np.where(is_set[live], 1 + kd[live].astype(np.int64), 0)     # a batch of the existing calls holds one kind of write
         cut = np.concatenate([[0], np.nonzero(ss[1:] != ss[:-1])[0] + 1, [len(ss)]])
         calls = 0
         for b, e in zip(cut[:-1].tolist(), cut[1:].tolist()):
             if ss[b]:
-                ch.set_preferences(ur[b:e], ir[b:e], vv[b:e], raise_on_error=False)
+                (ch.set_preferences, ch.set_item_tags, ch.set_user_tags)[ss[b] - 1](ur[b:e], ir[b:e], vv[b:e], raise_on_error=False)
             else:
                 ch.remove_preferences(ur[b:e], ir[b:e])
             calls += 1
@@ -453,8 +470,10 @@ def live(a):
 
     rows = []
     with ingest.Ingest(0) as g:
+        if a.tags:
+            g.set_option(ingest.INGEST_OPT_LIVE_TAGS, 1)
         for r in range(a.repeat + 1):      # the first stream warms both routes up
-            u, i, v, text = stream(r + 1)
+            u, i, v, kd, text = stream(r + 1)
             parse0 = g.text_info()["parse_ms"] if r else 0.0
             g.append_text(text)
             parse_ms = g.text_info()["parse_ms"] - parse0
@@ -465,16 +484,20 @@ def live(a):
             times = ca.ingest_apply_times()
             levels_ms = ca.foldin_stats()["device_ms_total"] - lev0
             t0 = time.perf_counter()
-            calls = by_hand(u, i, v)
+            calls = by_hand(u, i, v, kd)
             hand_ms = (time.perf_counter() - t0) * 1e3
             same = all(ca.factor_digest(s) == ch.factor_digest(s) for s in (X_, Y_))
             rows.append({"apply_ms": apply_ms, "by_hand_ms": hand_ms, "parse_ms": parse_ms, "ids_ms": times["ids_ms"], "plan_ms": times["plan_ms"],
                          "writes_ms": times["writes_ms"], "level_kernels_ms": levels_ms, "write_calls": st["write_calls"],
                          "by_hand_calls": calls, "new_users": st["new_users"], "new_items": st["new_items"], "bit_identical": same})
+            if a.tags:
+                rows[-1]["tag_stats"] = ca.ingest_apply_tag_stats()
+                same_sets = all(np.array_equal(ca.tag_rows(s), ch.tag_rows(s)) for s in (X_, Y_))
+                rows[-1]["bit_identical"] = same and same_sets
     timed = rows[1:]
     hand = np.array([x["by_hand_ms"] for x in timed])
     app = np.array([x["apply_ms"] for x in timed])
-    out["apply"] = {"users": U, "items": I, "lines": N, "streams": timed, "warm_up": rows[0],
+    out["apply"] = {"users": U, "items": I, "lines": N, "tag_lines": bool(a.tags), "streams": timed, "warm_up": rows[0],
                     "apply_ms_median": float(np.median(app)), "apply_ms_min": float(app.min()), "apply_ms_max": float(app.max()),
                     "by_hand_ms_median": float(np.median(hand)), "by_hand_ms_min": float(hand.min()), "by_hand_ms_max": float(hand.max()),
                     "by_hand_spread_ms": float(hand.max() - hand.min()),
